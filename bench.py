@@ -2,11 +2,20 @@
 """Headline benchmark: Mpix/s through extract_features (4 octaves x 4 sublevels) on synthetic
 1920x1080 frames, one process per GPU, frames sharded one-per-GPU-slot across ranks.
 
-    python bench.py --gpus N --steps K --warmup W [--frames F] [--width 1920 --height 1080]
+    python bench.py --gpus N --steps K --warmup W [--frames F] [--width 1920 --height 1080] [--dump-outputs DIR] [--full]
     python bench.py --gpus N --workload c5     (BASELINE configs[4]: 4K frames, 5 x 5, exchange + cross-GPU all-pairs match)
 
-The timed region of K steps is run --regions times (default 5) in one process; `value` / `ms_per_step` are the MEDIAN region
-(config.regions holds all of them): the pool's boxes differ by +-3 % from run to run, which is as much as a round's gain.
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed region of exactly K steps, the outputs of
+its last step if --dump-outputs is given, and the JSON line.  Everything else -- the extra objects listed below, the second
+timed region from host memory, the stage-profiled step and the spans behind the rooflines -- runs with --full only.
+
+With --full the timed region of K steps is run --regions times (default 5) in one process; `value` / `ms_per_step` are the
+MEDIAN region (config.regions holds all of them): the pool's boxes differ by +-3 % from run to run, which is as much as a
+round's gain.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it, to DIR/*.npy (float32 /
+float64, at most 64 MB in all: beyond that a fixed, seeded sample of the keypoint rows).  The frames are synthetic and seeded
+by their index, so two runs with the same arguments see the same inputs and two builds can be compared file by file.
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES the N ranks (children with
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; the parent never touches a GPU), forwards rank 0's JSON line and
@@ -19,7 +28,7 @@ of the shard's descriptor rows (what a following brute-force match needs), enque
 extraction pipeline and retired one step later (the last one inside the timed region); extraction itself has
 no collective.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+Extra objects on that line (--full):
   roofline      the kernel with the largest share of the step (the detector march or the FED kernel): ALGORITHMIC
                 bytes per launch / average launch duration measured with HIP events on the launching
                 stream inside the timed steps, against the 8 TB/s HBM peak.  `traffic` = HBM bytes per launch from the
@@ -99,8 +108,14 @@ def parse_args(argv=None):
     # up for ten steps and time forty: 0.3 s in all)
     ap.add_argument("--steps", type=int, default=None, help="timed steps per region (default 40; 8 with --workload c5)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 10; 3 with --workload c5)")
-    ap.add_argument("--regions", type=int, default=5,
-                    help="timed regions of --steps steps each, back to back in one process; the line reports the median region")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of --steps steps each, back to back in one process; the line reports the median region "
+                         "(default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra leg, check and per-kernel figure (see the module docstring); a plain run only "
+                         "times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--workload", choices=["frames", "c5"], default="frames",
                     help="frames: BASELINE configs[1]/[3] (1080p frames, 4 x 4, descriptor gather with N > 1) -- the headline; "
                          "c5: BASELINE configs[4] -- 3840x2160 frames, 5 octaves x 5 sublevels, frame f on rank f mod N, descriptors "
@@ -165,12 +180,14 @@ def parse_args(argv=None):
                     help="launcher self-test without a GPU: a stub context (sleeps, fake rows) and the gloo backend; the "
                          "line it prints says so and is not a measurement")
     args = ap.parse_args(argv)
+    if args.dump_outputs is not None and args.stub:
+        ap.error("--dump-outputs needs the real extraction (not with --stub)")
     c5 = args.workload == "c5"
     for name, frames_default, c5_default in (("steps", 40, 8), ("warmup", 10, 3), ("frames", 32, 8), ("width", 1920, 3840),
                                              ("height", 1080, 2160), ("sublevels", 4, 5), ("octaves", 4, 5)):
         if getattr(args, name) is None:
             setattr(args, name, c5_default if c5 else frames_default)
-    args.regions = max(1, args.regions)
+    args.regions = max(1, args.regions if args.regions is not None else (5 if args.full else 1))
     return args
 
 
@@ -360,6 +377,45 @@ class _StubContext:
 
 
 # --------------------------------------------------------------------------------------------------
+# --dump-outputs
+# --------------------------------------------------------------------------------------------------
+DUMP_MAX_BYTES = 64 << 20
+KEYPOINT_COLUMNS = ("x", "y", "response", "size", "octave", "class_id", "angle")
+
+
+def step_outputs(results, cut, frames):
+    """What extract_features hands its caller for the frames of one step, in frame order: the keypoints (one float64 row of
+    KEYPOINT_COLUMNS each), their descriptor bytes (float32) and the keypoints per frame.  Beyond DUMP_MAX_BYTES the
+    keypoint rows are a fixed, seeded sample whose row numbers go along as sample_rows."""
+    import numpy as np
+    kps, descs = [], []
+    for k in range(frames):
+        part = next(i for i in range(len(results)) if cut[i] <= k < cut[i + 1])
+        res, kb = results[part], k - cut[part]
+        kp = res.keypoints(kb)
+        kps.append(np.stack([kp[c].astype(np.float64) for c in KEYPOINT_COLUMNS], axis=1))
+        descs.append(res.descriptors(kb).astype(np.float32))
+    out = {"keypoints_per_frame": np.array([len(a) for a in kps], np.float64),
+           "keypoints": np.concatenate(kps), "descriptors": np.concatenate(descs)}
+    rows = len(out["keypoints"])
+    row_bytes = out["keypoints"].itemsize * out["keypoints"].shape[1] + out["descriptors"].itemsize * out["descriptors"].shape[1]
+    budget = DUMP_MAX_BYTES - out["keypoints_per_frame"].nbytes - (1 << 16)  # (.npy headers)
+    if rows * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(rows, budget // (row_bytes + 8), replace=False))
+        out["keypoints"], out["descriptors"] = out["keypoints"][keep], out["descriptors"][keep]
+        out["sample_rows"] = keep.astype(np.float64)
+    return out
+
+
+def write_outputs(directory, outs, prefix=""):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, f"{prefix}{name}.npy"), a)
+
+
+# --------------------------------------------------------------------------------------------------
 # one rank
 # --------------------------------------------------------------------------------------------------
 def main_rank(args):
@@ -379,6 +435,7 @@ def main_rank(args):
     import torch.distributed as dist
 
     stub = args.stub
+    full = args.full                                  # the extra legs, checks and per-kernel figures (a plain run: the headline only)
     c5 = args.workload == "c5"
     use_dist = world > 1 or args.force_dist          # a process group exists (rendezvous, barriers, reductions)
     use_xch = use_dist or c5                          # a step has an exchange (c5: also at N = 1, the all-pairs match reads gathered blocks)
@@ -471,7 +528,7 @@ def main_rank(args):
     # the same batches in pinned host memory (the reference's extract_features starts from host data, lib.rs:171-178):
     # second timed region, upload of batch j+1 on the context's copy stream under the kernels of batch j
     h_batches = None
-    if not stub and not args.no_host_input and not c5:
+    if full and not stub and not args.no_host_input and not c5:
         h_frames = torch.from_numpy(frames).pin_memory()
         h_batches = [h_frames[cut[i]:cut[i + 1]] for i in range(NP)]
     frame_src = {"host": False}
@@ -664,16 +721,20 @@ def main_rank(args):
 
     if args.warmup:
         run_steps(args.warmup)
-    # one extra untimed step with full stage profiling (informational stage_ms_per_step); the timed region only
-    # records the FED and detector spans needed for the rooflines (light mode: ~40 instead of ~190 HIP events per batch)
-    ctx.set_profiling(0 if args.no_profile else 1)
-    ctx.get_profile(reset=True)
-    run_steps(1)
-    warm_prof = ctx.get_profile(reset=True)
-    if not stub:
-        ctx.kernel_rows(reset=True)  # (the rows below cover the timed regions only)
-    ctx.set_profiling(0 if args.no_profile else 2)
-    want_check = not stub and not c5 and ((rank == 0 and not args.no_self_check) or use_dist or F <= 4)
+    warm_prof = None
+    if full:
+        # one extra untimed step with full stage profiling (informational stage_ms_per_step); the timed region only
+        # records the FED and detector spans needed for the rooflines (light mode: ~40 instead of ~190 HIP events per batch)
+        ctx.set_profiling(0 if args.no_profile else 1)
+        ctx.get_profile(reset=True)
+        run_steps(1)
+        warm_prof = ctx.get_profile(reset=True)
+        if not stub:
+            ctx.kernel_rows(reset=True)  # (the rows below cover the timed regions only)
+    # (a plain run records no spans: they feed the rooflines of --full only)
+    ctx.set_profiling(0 if args.no_profile or not full else 2)
+    want_check = full and not stub and not c5 and ((rank == 0 and not args.no_self_check) or use_dist or F <= 4)
+    dump = args.dump_outputs is not None
     # The timed region -- exactly args.steps steps between two barriers -- is run args.regions times back to back; the
     # line reports the MEDIAN region (max over ranks per region) and lists them all: one 0.2 s region per run cannot
     # resolve a 2 % change on boxes that differ by 3 % from run to run.
@@ -684,12 +745,23 @@ def main_rank(args):
     for reg in range(args.regions):
         barrier()
         t0 = time.perf_counter()
-        nk = run_steps(args.steps, keep_final=want_check and reg == args.regions - 1)
+        nk = run_steps(args.steps, keep_final=(want_check or (dump and not c5)) and reg == args.regions - 1)
         barrier()
         el = time.perf_counter() - t0
         regions.append((host_max(el), el))
-    prof = ctx.get_profile(reset=True)  # spans of ALL regions: the rooflines average over args.regions * args.steps steps
-    kernel_rows = [] if stub else ctx.kernel_rows(reset=True)  # the same spans by kernel variant and launch shape
+    if dump:
+        if c5:  # what the step's caller reads back: the totals of the all-pairs match (akz_pairs_totals)
+            outs = {"all_pairs_totals": np.array([xch["lists"], xch["matches"], xch["dist"]], np.float64)}
+        else:
+            outs = step_outputs(keep_last["results"], cut, F)
+        write_outputs(args.dump_outputs, outs, f"rank{rank}_" if world > 1 else "")
+        if not want_check:
+            for r in keep_last["results"] or []:
+                r.close()
+            keep_last["results"] = None
+    if full:
+        prof = ctx.get_profile(reset=True)  # spans of ALL regions: the rooflines average over args.regions * args.steps steps
+        kernel_rows = [] if stub else ctx.kernel_rows(reset=True)  # the same spans by kernel variant and launch shape
     ctx.set_profiling(False)
     timed_steps = args.steps * args.regions
     host_ms_timed = dict(host_ms)  # the accumulators go on counting in the host-input leg below: the line reports the timed regions
@@ -759,20 +831,6 @@ def main_rank(args):
         return out
 
     det_bpp = 4 + 8 + 4 + (0 if args.lean else 12)  # Lsmooth in; Lx, Ly, Ldet (+ Lxx, Lyy, Lxy) out: each once
-    roof_det = roof(A.lib().akz_detector_kernel_name().decode(), prof["detector"], prof["det_launches"],
-                    float(det_bpp) * prof["det_px"],
-                    f"all detector launches of the timed steps ({det_bpp} B per level pixel: Lsmooth read once, every output "
-                    "plane written once); time = sum of HIP-event spans around each launch on the launching stream. In the "
-                    "step the fine-octave launches share the chip with the coarse octaves' chain and the previous batch's "
-                    "keypoint kernels (that overlap is worth +7 % throughput), which stretches the spans: standalone_frac "
-                    "is the same kernel alone on HBM-cold planes (detector_standalone)")
-    roof_fed = roof(A.lib().akz_fed_kernel_name().decode(), prof["fed"], prof["fed_launches"],
-                    FED_BYTES_PER_PX_STEP * prof["fed_px_steps"] + 12.0 * prof["fused_px"],
-                    "all diffusion launches of the timed steps (levels 1..15, 1920x1080 down to 240x135): k_level_march "
-                    "(level preparation + the level's first <= 4 FED steps in one launch, levels of 4 Mpx and more) and "
-                    "k_fed_own (<= 8 steps per launch); 12 B per pixel-step ALGORITHMIC plus 12 B per pixel for a "
-                    "preparation that runs inside the launch — steps are fused, so frac can exceed 1; traffic_frac is "
-                    "the DRAM figure")
     # ---- the rows behind the two groups: one per kernel NAME (as rocprofv3's kernel stats list them, so that avg_launch_us can
     # be held against profiles/*_kernel_stats.csv), with the launch shapes it ran on ----
     def per_kernel_traffic(name):
@@ -820,15 +878,31 @@ def main_rank(args):
                              "traffic_frac": round(tr / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if tr and us > 0 else None,
                              "shapes": e["shapes"]})
         return out_rows
-    roof_det["kernels"] = kernel_table((4, 5))
-    roof_fed["kernels"] = kernel_table((1, 2, 3))
-    # the detector march is the kernel with the largest share of the step when each kernel runs alone (2.2 of 5.7 ms of
-    # kernel time); since the fork the two groups' spans overlap in the step, so their sums no longer rank them
-    roofline, roofline_2 = roof_det, roof_fed
+    roofline = roofline_2 = None
+    if full:
+        roof_det = roof(A.lib().akz_detector_kernel_name().decode(), prof["detector"], prof["det_launches"],
+                        float(det_bpp) * prof["det_px"],
+                        f"all detector launches of the timed steps ({det_bpp} B per level pixel: Lsmooth read once, every output "
+                        "plane written once); time = sum of HIP-event spans around each launch on the launching stream. In the "
+                        "step the fine-octave launches share the chip with the coarse octaves' chain and the previous batch's "
+                        "keypoint kernels (that overlap is worth +7 % throughput), which stretches the spans: standalone_frac "
+                        "is the same kernel alone on HBM-cold planes (detector_standalone)")
+        roof_fed = roof(A.lib().akz_fed_kernel_name().decode(), prof["fed"], prof["fed_launches"],
+                        FED_BYTES_PER_PX_STEP * prof["fed_px_steps"] + 12.0 * prof["fused_px"],
+                        "all diffusion launches of the timed steps (levels 1..15, 1920x1080 down to 240x135): k_level_march "
+                        "(level preparation + the level's first <= 4 FED steps in one launch, levels of 4 Mpx and more) and "
+                        "k_fed_own (<= 8 steps per launch); 12 B per pixel-step ALGORITHMIC plus 12 B per pixel for a "
+                        "preparation that runs inside the launch — steps are fused, so frac can exceed 1; traffic_frac is "
+                        "the DRAM figure")
+        roof_det["kernels"] = kernel_table((4, 5))
+        roof_fed["kernels"] = kernel_table((1, 2, 3))
+        # the detector march is the kernel with the largest share of the step when each kernel runs alone (2.2 of 5.7 ms of
+        # kernel time); since the fork the two groups' spans overlap in the step, so their sums no longer rank them
+        roofline, roofline_2 = roof_det, roof_fed
 
     # ---- the FED kernel alone: 3840x2160 plane (north-star target point) and a 32 x 1080p level (HBM-resident) ----
     fed_alone = None
-    if rank == 0 and world == 1 and not args.no_fed4k and not c5:  # N = 1 information
+    if full and rank == 0 and world == 1 and not args.no_fed4k and not c5:  # N = 1 information
         fed_alone = {}
         for name, shape, nst in (("4k_plane", (2160, 3840), 40), ("level_32x1080p", (32, 1080, 1920), 8)):
             lt = torch.rand(shape, dtype=torch.float32, device=dev)
@@ -881,7 +955,7 @@ def main_rank(args):
     # re-reads the plane it read last time finds most of it in the 256 MB Infinity Cache and looks 25 % faster than any
     # launch of the pyramid, where every level's Lsmooth was written long before) ----
     det_alone = None
-    if rank == 0 and world == 1 and not args.no_fed4k and not args.lean and not c5:
+    if full and rank == 0 and world == 1 and not args.no_fed4k and not args.lean and not c5:
         n_, h_, w_ = 32, 1080, 1920
         pb = n_ * h_ * w_ * 4
         big = torch.empty(4 * 7 * pb + (1 << 21), dtype=torch.uint8, device=dev)  # carved like the product's slab
@@ -920,7 +994,7 @@ def main_rank(args):
     # keypoints + descriptor bytes of the first frames of each shard, gathered to rank 0.  A --gpus 2 --share-gpu run and
     # a single-rank run over the same frames must print the same table (tests/test_gpu_gather.py). ----
     frame_sha = None
-    if not stub and keep_last["results"]:
+    if full and not stub and keep_last["results"]:
         import hashlib
         mine = {}
         gidx = A.shard_frames(world * F, rank, world)
@@ -964,7 +1038,7 @@ def main_rank(args):
 
     # ---- the matcher (BASELINE configs[2] / [4]: Hamming match of two descriptor sets), untimed leg, rank 0 ------
     match_leg = None
-    if rank == 0 and world == 1 and not args.no_match and not c5:  # N = 1 information; the scaling runs only need `value`
+    if full and rank == 0 and world == 1 and not args.no_match and not c5:  # N = 1 information; the scaling runs only need `value`
         g = torch.Generator(device=dev).manual_seed(7)
         legs = []
         for n_m in (11264, 65536):  # a 4K frame's keypoint count; a gathered multi-frame set
@@ -1013,7 +1087,7 @@ def main_rank(args):
 
     # ---- BASELINE configs[2] and configs[4] end to end (extra legs, rank 0, own clocks) --------------------------------
     c3_leg = c5_leg = None
-    if rank == 0 and world == 1 and not args.no_match and not c5:
+    if full and rank == 0 and world == 1 and not args.no_match and not c5:
         ctx.set_profiling(0)
         # configs[2]: a 3840x2160 pair -- ONE extract call on the two-frame batch (host frames, descriptors back on the
         # host) + match_features with its reference signature (descriptor_match on the GPU, RANSAC filter on the host)
@@ -1114,7 +1188,7 @@ def main_rank(args):
 
     # ---- BASELINE configs[1] taken literally: ONE frame per extract call (untimed extra leg, rank 0) -----------
     single = None
-    if rank == 0 and world == 1 and not args.no_single and not c5:
+    if full and rank == 0 and world == 1 and not args.no_single and not c5:
         ctx.set_profiling(0)
         one = d_frames[:1]
         for _ in range(10):
@@ -1281,10 +1355,10 @@ def main_rank(args):
     # as its thread budget; this process is idle meanwhile.  The host half of a batch (candidate
     # bucketing, keypoint selection, libm) must still hide under the next batch's kernels. ----
     host_share_leg = None
-    if rank == 0 and world == 1 and not args.no_host_share_leg and not args.host_share and not stub and not c5:
+    if full and rank == 0 and world == 1 and not args.no_host_share_leg and not args.host_share and not stub and not c5:
         try:
             torch.cuda.synchronize()
-            cmd = [sys.executable, os.path.abspath(__file__), "--host-share", "8", "--steps", str(min(args.steps, 20)),
+            cmd = [sys.executable, os.path.abspath(__file__), "--host-share", "8", "--regions", str(args.regions), "--steps", str(min(args.steps, 20)),
                    "--warmup", str(min(args.warmup, 5)), "--frames", str(F), "--width", str(W), "--height", str(H),
                    "--octaves", str(args.octaves), "--sublevels", str(args.sublevels), "--no-cpu-baseline", "--no-fed4k",
                    "--no-single", "--no-match", "--no-self-check", "--no-host-input", "--no-host-share-leg"] + (["--lean"] if args.lean else [])
@@ -1305,6 +1379,12 @@ def main_rank(args):
         dist_job = host_sum(float(xch["dist_sum"]) / steps_seen)       # descriptor pairs whose distance a step forms, all ranks
         lists_all = host_allgather(float(xch["lists"]))
         matches_job = host_sum(float(xch["matches"]))
+        c5_info = {"descriptor_pairs_per_step": int(dist_job),
+                   "Tdistances_per_s": round(dist_job * args.steps / elapsed / 1e12, 3),
+                   "match_lists_held_per_rank": [int(v) for v in lists_all],
+                   "matches_per_step": int(matches_job),
+                   "match_context": args.match_ctx}
+    if c5 and full:
         # one more step, synchronously, keeping the gather and the pairs object
         ress = [ctx.extract_begin(bt, cfg, keep_all_planes=not args.lean, host_descriptors=False).finish() for bt in batches]
         gth = xch["comm"].gather_begin(ress, xch["cap"])
@@ -1350,19 +1430,14 @@ def main_rank(args):
         pr.free()
         gth.free()
         ok_all = host_sum(0.0 if (ok_pairs and holders_ok) else 1.0) == 0.0
-        c5_info = {"images_per_step": n_images, "unordered_image_pairs_per_step": n_images * (n_images - 1) // 2,
-                   "descriptor_pairs_per_step": int(dist_job),
-                   "Tdistances_per_s": round(dist_job * args.steps / elapsed / 1e12, 3),
-                   "match_lists_held_per_rank": [int(v) for v in lists_all],
-                   "matches_per_step": int(matches_job),
-                   "pairs_check": {"sampled_pairs_per_rank": len(picks), "both_directions_equal_descriptor_match": bool(ok_all)},
-                   "match_context": args.match_ctx}
+        c5_info.update({"images_per_step": n_images, "unordered_image_pairs_per_step": n_images * (n_images - 1) // 2,
+                        "pairs_check": {"sampled_pairs_per_rank": len(picks), "both_directions_equal_descriptor_match": bool(ok_all)}})
         if not ok_all:
             raise SystemExit("bench.py --workload c5: a sampled pair's lists differ from akz_descriptor_match_device of the pair")
 
     # ---- CPU baseline: the oracle on the host cores, bounded sample, rank 0 at N=1 only -------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import akaze_ref as R
         cores = effective_cpus()  # affinity mask and cgroup quota, not the machine's core count
@@ -1383,46 +1458,48 @@ def main_rank(args):
                "seconds": round(dt, 2)}
 
     if rank == 0:
-        stage_ms = {k: round(warm_prof[k], 3) for k in A.STAGES}
-        stage_ms["note"] = ("one untimed step with full stage profiling, un-pipelined and on ONE stream (the coarse octaves' chain is "
-                            "not forked, so that every stage's time is its own); timed steps record FED and detector spans only")
-        # algorithmic HBM bytes of each GPU stage of one step (SURVEY.md 8(d) model: every stage input read once, every
-        # kept plane written once) against that stage's time in the profiled step: where the path stands kernel by kernel
-        lv = A.plan_levels(W, H, cfg)
-        px = [l["w"] * l["h"] * F for l in lv]
-        half = [i > 0 and lv[i]["octave"] > lv[i - 1]["octave"] for i in range(len(lv))]
-        stage_bytes = {
-            "blur0": px[0] * (1 + 4),                                   # u8 in, f32 Lt0 out
-            "contrast": px[0] * 4 * 2,                                  # two passes over Lt0
-            # level preparation ([2x2 mean: 4 px in, Lt out,] Lsmooth, Lflow out) + diffusion: one line, because large levels run
-            # both in one kernel (k_level_march)
-            "prep+fed": sum((16 + 12 if half[i] else 4 + 8) * px[i] for i in range(1, len(lv))) +
-                        sum(FED_BYTES_PER_PX_STEP * len(lv[i]["tau"]) * px[i] for i in range(1, len(lv))),
-            "detector": sum(det_bpp * p for p in px),                   # Lsmooth in; Lx, Ly, Ldet (+ Lxx, Lyy, Lxy) out, each once
-        }
-        stage_t = dict(warm_prof)
-        stage_t["prep+fed"] = warm_prof["prep"] + warm_prof["fed"]
-        stage_roofline = {k: {"algorithmic_GB": round(b / 1e9, 3), "ms": round(stage_t[k], 3),
-                              "achieved_GBps": round(b / 1e9 / (stage_t[k] * 1e-3), 1),
-                              "frac": round(b / 1e9 / (stage_t[k] * 1e-3) / HBM_PEAK_GBS, 3)}
-                          for k, b in stage_bytes.items() if stage_t[k] > 0}
         steps = max(1, args.steps)
-        # THE whole-path byte model is SURVEY.md 8(d)'s: level 0 60 B/px; a level that continues its octave 64 + 12 n_l; the first
-        # level of an octave 76 + 12 n_l (n_l diffusion steps) -- 575.8 B per input pixel at 4 x 4, 704.3 at 5 x 5, all planes kept
-        whole = sum((60 if i == 0 else (76 if half[i] else 64) + 12 * len(lv[i]["tau"])) * px[i] for i in range(len(lv)))
-        whole_gbs = whole / 1e9 / (elapsed / steps) if world == 1 else None
-        stage_sum = sum(stage_bytes.values())
-        stage_roofline["whole_path"] = {"model": "SURVEY.md 8(d)", "algorithmic_GB": round(whole / 1e9, 3),
-                                        "B_per_input_pixel": round(whole / (float(W) * H * F), 1),
-                                        "achieved_GBps": round(whole_gbs, 1) if whole_gbs else None,
-                                        "frac": round(whole_gbs / HBM_PEAK_GBS, 3) if whole_gbs else None,
-                                        "stage_sum_B_per_input_pixel": round(stage_sum / (float(W) * H * F), 1),
-                                        "note": "SURVEY.md 8(d)'s bytes per input pixel x the step's pixels / the timed step (pipelined, keypoint "
-                                                "kernels included).  The model counts every diffusion step as a pass over HBM and the "
-                                                "derivative planes as written and read again: the kernels here fuse both, so the path can sit "
-                                                "above 'its' roofline -- the DRAM figure is roofline.traffic_frac and profiles/*_pmc_per_kernel.txt.  "
-                                                "stage_sum_B_per_input_pixel is the sum of the per-stage rows above (each stage's own inputs and "
-                                                "outputs once), a smaller model kept for the per-stage fractions only"}
+        stage_ms = stage_roofline = None
+        if full:
+            stage_ms = {k: round(warm_prof[k], 3) for k in A.STAGES}
+            stage_ms["note"] = ("one untimed step with full stage profiling, un-pipelined and on ONE stream (the coarse octaves' chain is "
+                                "not forked, so that every stage's time is its own); timed steps record FED and detector spans only")
+            # algorithmic HBM bytes of each GPU stage of one step (SURVEY.md 8(d) model: every stage input read once, every
+            # kept plane written once) against that stage's time in the profiled step: where the path stands kernel by kernel
+            lv = A.plan_levels(W, H, cfg)
+            px = [l["w"] * l["h"] * F for l in lv]
+            half = [i > 0 and lv[i]["octave"] > lv[i - 1]["octave"] for i in range(len(lv))]
+            stage_bytes = {
+                "blur0": px[0] * (1 + 4),                                   # u8 in, f32 Lt0 out
+                "contrast": px[0] * 4 * 2,                                  # two passes over Lt0
+                # level preparation ([2x2 mean: 4 px in, Lt out,] Lsmooth, Lflow out) + diffusion: one line, because large levels run
+                # both in one kernel (k_level_march)
+                "prep+fed": sum((16 + 12 if half[i] else 4 + 8) * px[i] for i in range(1, len(lv))) +
+                            sum(FED_BYTES_PER_PX_STEP * len(lv[i]["tau"]) * px[i] for i in range(1, len(lv))),
+                "detector": sum(det_bpp * p for p in px),                   # Lsmooth in; Lx, Ly, Ldet (+ Lxx, Lyy, Lxy) out, each once
+            }
+            stage_t = dict(warm_prof)
+            stage_t["prep+fed"] = warm_prof["prep"] + warm_prof["fed"]
+            stage_roofline = {k: {"algorithmic_GB": round(b / 1e9, 3), "ms": round(stage_t[k], 3),
+                                  "achieved_GBps": round(b / 1e9 / (stage_t[k] * 1e-3), 1),
+                                  "frac": round(b / 1e9 / (stage_t[k] * 1e-3) / HBM_PEAK_GBS, 3)}
+                              for k, b in stage_bytes.items() if stage_t[k] > 0}
+            # THE whole-path byte model is SURVEY.md 8(d)'s: level 0 60 B/px; a level that continues its octave 64 + 12 n_l; the first
+            # level of an octave 76 + 12 n_l (n_l diffusion steps) -- 575.8 B per input pixel at 4 x 4, 704.3 at 5 x 5, all planes kept
+            whole = sum((60 if i == 0 else (76 if half[i] else 64) + 12 * len(lv[i]["tau"])) * px[i] for i in range(len(lv)))
+            whole_gbs = whole / 1e9 / (elapsed / steps) if world == 1 else None
+            stage_sum = sum(stage_bytes.values())
+            stage_roofline["whole_path"] = {"model": "SURVEY.md 8(d)", "algorithmic_GB": round(whole / 1e9, 3),
+                                            "B_per_input_pixel": round(whole / (float(W) * H * F), 1),
+                                            "achieved_GBps": round(whole_gbs, 1) if whole_gbs else None,
+                                            "frac": round(whole_gbs / HBM_PEAK_GBS, 3) if whole_gbs else None,
+                                            "stage_sum_B_per_input_pixel": round(stage_sum / (float(W) * H * F), 1),
+                                            "note": "SURVEY.md 8(d)'s bytes per input pixel x the step's pixels / the timed step (pipelined, keypoint "
+                                                    "kernels included).  The model counts every diffusion step as a pass over HBM and the "
+                                                    "derivative planes as written and read again: the kernels here fuse both, so the path can sit "
+                                                    "above 'its' roofline -- the DRAM figure is roofline.traffic_frac and profiles/*_pmc_per_kernel.txt.  "
+                                                    "stage_sum_B_per_input_pixel is the sum of the per-stage rows above (each stage's own inputs and "
+                                                    "outputs once), a smaller model kept for the per-stage fractions only"}
         out = {
             "metric": f"Mpix/s through extract_features ({args.octaves} oct x {args.sublevels} sub)" +
                       (" + exchange + cross-GPU all-pairs match" if c5 else ""),
@@ -1443,6 +1520,7 @@ def main_rank(args):
                                     "(BASELINE configs[1] frame shape; configs[3] sharding: one image per GPU slot)"),
                        "regions": {"n": args.regions, "reported": "median", "Mpix_s": region_values,
                                    "min": min(region_values), "max": max(region_values)},
+                       "full": full,
                        "all_pairs": c5_info,
                        "frames_per_gpu": F, "width": W, "height": H, "batches_per_step": NP,
                        "pipelining": f"begin(batch j+{args.depth}) before finish(batch j) on one context, across steps" + (", finish half on the context's own thread" if args.eager else ""),
@@ -1490,7 +1568,7 @@ def main_rank(args):
     # too.  A watchdog guards the headline: if the leg does not finish, rank 0 prints the line with the error in the leg's place and
     # every rank exits NON-zero (a hung collective or matcher is a failed run, whatever the line says).
     leg = None
-    if world > 1 and not stub and not c5 and not args.no_c5_leg and xch["comm"] is not None and exchange in ("capi", "external"):
+    if full and world > 1 and not stub and not c5 and not args.no_c5_leg and xch["comm"] is not None and exchange in ("capi", "external"):
         import threading
         wd_lock = threading.Lock()
         wd_state = {"over": False}

@@ -306,7 +306,7 @@ def test_bench_force_dist_capi_world1():
     import json
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--steps", "3", "--warmup", "1",
                         "--frames", "4", "--no-cpu-baseline", "--no-fed4k", "--no-single", "--no-match"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr
@@ -321,7 +321,7 @@ def _bench_json(extra, timeout=900):
     import json
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--regions", "2", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--regions", "2", "--no-cpu-baseline",
                         "--no-fed4k", "--no-single", "--no-match", "--no-host-share-leg", "--width", "960", "--height", "540"] + extra,
                        env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-3000:]

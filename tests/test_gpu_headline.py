@@ -112,3 +112,39 @@ def test_job_size_gates_both_entry_points(ctx, amd, ref, w, h, n):
         rf.close()
     sync.close()
     asyn.close()
+
+
+def test_plain_bench_run_dumps_its_last_step(ctx, amd, tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: one timed region of exactly --steps steps, none of the extra legs, and the
+    files hold what extract_features gives a caller for the same synthetic frames."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--frames", "3", "--width", "960", "--height", "540", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["config"]["regions"]["n"] == 1 and line["config"]["full"] is False
+    assert line["roofline"] is None and line["self_check"] is None and line["cpu_baseline"] is None
+    outs = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(outs) == ["descriptors", "keypoints", "keypoints_per_frame"]
+    assert all(a.dtype in (np.float32, np.float64) for a in outs.values())
+    frames = np.stack([amd.synth_frame(960, 540, i) for i in range(3)])
+    res = ctx.extract_features(torch.from_numpy(frames).cuda(), keep_all_planes=True)
+    o = 0
+    for img in range(3):
+        kp, desc = res.keypoints(img), res.descriptors(img)
+        n = len(kp)
+        assert n > 0 and outs["keypoints_per_frame"][img] == n
+        for j, c in enumerate(("x", "y", "response", "size", "octave", "class_id", "angle")):
+            assert np.array_equal(outs["keypoints"][o:o + n, j], kp[c].astype(np.float64)), (img, c)
+        assert np.array_equal(outs["descriptors"][o:o + n], desc.astype(np.float32)), img
+        o += n
+    assert o == len(outs["keypoints"])
+    res.close()

@@ -4,9 +4,9 @@
 There is no Rust toolchain in the build image, so the shim cannot be compiled; this script is the next best check:
 
   1. the public items of the reference crate (`pub fn` with parameter names / types / return type, `pub struct` with
-     its public fields, trait methods) are read from the reference sources when they are available
-     (`--reference DIR`, default /root/reference) and written to tests/golden/reference_api.json; without the
-     sources that snapshot is used;
+     its public fields, trait methods) are read from the reference sources when they are given
+     (`--reference DIR`: the crate's checkout) and written to tests/golden/reference_api.json; without them that
+     snapshot is used, so the check needs nothing outside this repository;
   2. the same items are read from the shim, module path by module path;
   3. every `extern "C"` declaration of the shim must name a function of include/akaze_hip.h with the same number
      of parameters.
@@ -282,13 +282,15 @@ def twin_bodies(path, known):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--reference", default=None, help="checkout of the reference crate (default: the committed snapshot)")
     ap.add_argument("--shim", default=os.path.join(ROOT, "akaze-rust_amd", "rust", "src", "lib.rs"))
     ap.add_argument("--snapshot", default=os.path.join(ROOT, "tests", "golden", "reference_api.json"))
     ap.add_argument("--twin", default=os.path.join(ROOT, "tests", "shim_twin", "shim_twin.cpp"))
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args()
-    if os.path.isdir(os.path.join(args.reference, "akaze", "src")):
+    if args.reference:
+        if not os.path.isdir(os.path.join(args.reference, "akaze", "src")):
+            ap.error(f"--reference {args.reference}: no akaze/src in it")
         ref = reference_api(args.reference)
         os.makedirs(os.path.dirname(args.snapshot), exist_ok=True)
         json.dump(ref, open(args.snapshot, "w"), indent=1, sort_keys=True)

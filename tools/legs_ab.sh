@@ -3,7 +3,7 @@
 # instead of the headline (args: tag rounds "name:bench args" ...)
 tag=$1; rounds=$2; shift 2
 O=gpurun_out/$tag; mkdir -p $O
-B="--no-cpu-baseline --no-fed4k --no-self-check --no-host-input --no-host-share-leg --regions 1 --steps 10 --warmup 4"
+B="--full --no-cpu-baseline --no-fed4k --no-self-check --no-host-input --no-host-share-leg --regions 1 --steps 10 --warmup 4"
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     name=${v%%:*}; args=${v#*:}

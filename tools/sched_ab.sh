@@ -2,7 +2,7 @@
 # Alternating bench.py runs over schedule variants on ONE box (args: tag rounds "name:--sched k=v,..." ...); prints value per run
 tag=$1; rounds=$2; shift 2
 O=gpurun_out/$tag; mkdir -p $O
-B="--no-cpu-baseline --no-single --no-match --no-fed4k --no-self-check --no-host-input --no-host-share-leg --regions 5"
+B="--full --no-cpu-baseline --no-single --no-match --no-fed4k --no-self-check --no-host-input --no-host-share-leg --regions 5"
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
     name=${v%%:*}; args=${v#*:}
