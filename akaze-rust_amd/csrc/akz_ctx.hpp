@@ -317,6 +317,10 @@ AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
         b.p = nullptr;
         b.bytes = 0;
     }
+    if (&b == &c->small) {  // fresh memory holds nothing known: hipMalloc may hand back the address just freed
+        c->small_zero_p = nullptr;
+        c->small_zero = 0;
+    }
     const size_t want = bytes + bytes / 8 + 256;
     AKZ_HIP_TRY(hipMalloc(&b.p, want));
     b.bytes = want;

@@ -533,6 +533,13 @@ k_contrast_hist(const float* __restrict__ blurred, int w, int h, Scharr1 sk,
         if (v) atomicAdd(&d_hist[(size_t)blockIdx.z * nbins + b], v);
     }
 }
+// Rust's `as usize` from an f64 saturates (contrast_factor.rs:61): NaN and negatives -> 0, 2^64 and above (+inf included) -> MAX.
+// A plain conversion is undefined there; a percentile of +inf or 1e300 is an accepted Config.
+__device__ __forceinline__ unsigned long long sat_usize(double v) {
+    if (!(v > 0.0)) return 0ull;
+    if (v >= 18446744073709551615.0) return ~0ull;
+    return (unsigned long long)v;
+}
 // One workgroup per image: the histogram is staged in LDS by all threads, then thread 0 replays the sequential
 // percentile scan of contrast_factor.rs:56-70 (a single thread walking the bins in global memory took 38 us).
 __global__ void __launch_bounds__(256)
@@ -548,8 +555,7 @@ k_contrast_final(const unsigned long long* __restrict__ d_hmax_bits, const unsig
     const double hmax = __longlong_as_double((long long)d_hmax_bits[img]);
     unsigned long long num_points = 0;
     for (unsigned b = 0; b < nbins; ++b) num_points += s_bins[b];
-    const double tf = (double)num_points * percentile;
-    const unsigned long long threshold = tf > 0.0 ? (unsigned long long)tf : 0ull;
+    const unsigned long long threshold = sat_usize((double)num_points * percentile);
     unsigned long long k = 0, num_elements = 0;
     while (num_elements < threshold && k < nbins) {
         num_elements += s_bins[k];
@@ -642,8 +648,7 @@ k_contrast_hist_final(const float* __restrict__ gxp, const float* __restrict__ g
     if (tid != 0) return;
     unsigned long long num_points = 0;
     for (unsigned b = 0; b < nbins; ++b) num_points += s_hist[b];
-    const double tf = (double)num_points * percentile;
-    const unsigned long long threshold = tf > 0.0 ? (unsigned long long)tf : 0ull;
+    const unsigned long long threshold = sat_usize((double)num_points * percentile);
     unsigned long long k = 0, num_elements = 0;
     while (num_elements < threshold && k < nbins) {
         num_elements += s_hist[k];

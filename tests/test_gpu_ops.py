@@ -71,7 +71,7 @@ def test_half_size(ctx, ref, shape):
 
 
 @pytest.mark.parametrize("shape", SHAPES)
-@pytest.mark.parametrize("sigma", [1, 2, 3, 4])
+@pytest.mark.parametrize("sigma", [1, 2, 3, 4, 5, 6])
 def test_scharr(ctx, ref, shape, sigma):
     img = rand_img(*shape, seed=4, lo=-1.0)
     same(host(ctx.scharr(dev(img), True, False, sigma)), ref.scharr(img, True, False, sigma))
@@ -207,6 +207,81 @@ def test_detector_response(ctx, ref, sigma):
         same(host(got[name]), exp)
     lean = ctx.detector_response(dev(ls), sigma, keep_second=False)
     same(host(lean["Ldet"]), ldet)
+
+
+def detector_expected(ref, ls, sigma):
+    lx = ref.scharr(ls, True, False, sigma)
+    ly = ref.scharr(ls, False, True, sigma)
+    exp = {"Lx": lx, "Ly": ly, "Lxx": ref.scharr(lx, True, False, sigma), "Lyy": ref.scharr(ly, False, True, sigma),
+           "Lxy": ref.scharr(lx, False, True, sigma)}
+    exp["Ldet"] = ((exp["Lxx"] * exp["Lyy"]) - (exp["Lxy"] * exp["Lxy"])) * np.float32(sigma ** 4)
+    return exp
+
+
+@pytest.mark.parametrize("mode", [0, 4, 5, 2], ids=["multi_kernel", "tiled", "march", "auto"])
+@pytest.mark.parametrize("sigma", [1, 2, 3, 4, 5, 6])
+def test_detector_response_every_sigma_every_mode(ctx, ref, mode, sigma):
+    """Every detector sigma the plan accepts under every detector mode: the one-kernel tiled form and the column march stop
+    at sigma 4, and sigma 5 / 6 take the two-kernel detector whatever is forced.  A batch of two, with and without the second
+    derivatives kept."""
+    ls = np.stack([rand_img(70, 517, seed=60 + sigma), rand_img(70, 517, seed=70 + sigma, lo=-1.0)])
+    ctx.set_detector_mode(mode)
+    try:
+        full = {k: host(v) for k, v in ctx.detector_response(dev(ls), sigma).items()}
+        lean = {k: host(v) for k, v in ctx.detector_response(dev(ls), sigma, keep_second=False).items()}
+    finally:
+        ctx.set_detector_mode(2)
+    assert set(lean) == {"Lx", "Ly", "Ldet"}
+    for i in range(2):
+        exp = detector_expected(ref, ls[i], sigma)
+        for name, v in exp.items():
+            same(full[name][i], v)
+        for name in ("Lx", "Ly", "Ldet"):
+            same(lean[name][i], exp[name])
+
+
+@pytest.mark.parametrize("mode", [0, 3, 1], ids=["tiled", "march", "stream"])
+@pytest.mark.parametrize("nbins", [1, 2, 3, 7, 300, 640, 641, 1000, 4095, 4096])
+def test_contrast_factor_whole_histogram(amd, ref, mode, nbins):
+    """compute_contrast_factor, the whole histogram: the percentile walk stops at the first bin whose cumulative count reaches
+    int(N p), so percentiles that put that threshold one below, at and one above the cumulative count of a bin pin every
+    cumulative count (all bins up to 640, a seeded sample of them above).  Against the float64 restatement of
+    tests/test_config_space.py, on random frames, power-of-two-scaled copies of one tile (magnitudes on bin edges, f32 and u8
+    values) and a flat frame; gradient scales 0.5 .. 2.5; the extra percentiles (NaN, negative, 0, 1e300, +inf: the
+    threshold saturates as Rust's `as usize` does) against the oracle too.  Contexts forced to the tiled passes, the column
+    marches (up to 640 bins) and the streaming passes (up to 640 bins)."""
+    import torch
+    from test_config_space import PERCENTILE_EXTRAS, contrast_from_histogram, edge_thresholds, gradient_histogram, \
+        percentile_for, sweep_images
+    c = amd.Context(0, torch.cuda.current_stream().cuda_stream)
+    c.set_prep_mode(mode)
+    try:
+        imgs = sweep_images(ref)
+        d_imgs = dev(imgs)
+        gscales = (0.5, 1.0, 1.5, 2.5) if nbins in (3, 300, 641, 4096) else (1.0,)
+        for gscale in gscales:
+            hists = []
+            for img in imgs:
+                b = ref.gaussian_blur(img, gscale)
+                hists.append(gradient_histogram(ref.scharr(b, True, False, 1), ref.scharr(b, False, True, 1), nbins))
+            ps = set()
+            for i, (hmax, hs, npts) in enumerate(hists):
+                assert npts > 0 and hmax > 0.0
+                ps.update(percentile_for(npts, t) for t in edge_thresholds(hs, None if nbins <= 640 else 96, seed=i))
+            ps = sorted(ps) + PERCENTILE_EXTRAS
+            got = torch.stack([c.contrast_factor(d_imgs, p, gscale, nbins) for p in ps]).cpu().numpy()
+            for j, p in enumerate(ps):
+                for i in range(len(imgs)):
+                    want = contrast_from_histogram(*hists[i], p)
+                    assert float(got[j, i]) == want, (nbins, gscale, p, i, float(got[j, i]), want)
+            for j, p in enumerate(PERCENTILE_EXTRAS):
+                for i in range(len(imgs)):
+                    assert ref.contrast_factor(imgs[i], p, gscale, nbins) == float(got[len(ps) - len(PERCENTILE_EXTRAS) + j, i])
+        flat = np.full((40, 50), 0.25, np.float32)
+        for p in PERCENTILE_EXTRAS:
+            assert float(host(c.contrast_factor(dev(flat), p, 1.0, nbins))[0]) == ref.contrast_factor(flat, p, 1.0, nbins) == 0.0
+    finally:
+        c.close()
 
 
 @pytest.fixture(params=[0, 1, 3], ids=["popcount", "mfma_i8", "mfma_fp4"])

@@ -54,7 +54,7 @@ def test_stream_batch_and_nondefault_config(sctx, amd, ref):
                            planes=False)
 
 
-@pytest.mark.parametrize("sigma", [1, 2, 3, 4])
+@pytest.mark.parametrize("sigma", [1, 2, 3, 4, 5, 6])
 def test_stream_detector_response_op(sctx, ref, sigma):
     import torch
     rng = np.random.default_rng(40 + sigma)
