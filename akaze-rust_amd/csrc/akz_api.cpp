@@ -120,6 +120,21 @@ int akz_ctx_destroy(akz_ctx* c) {
                       &c->ms1.q8, &c->ms1.t8, &c->ms1.pop, &c->ms1.tab, &c->ms1.cols, &c->ms1.rec, &c->ransac_dev};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
+    for (DevBuf& b : c->fetch_tmp)
+        if (b.p) (void)hipFree(b.p);
+    for (auto& set : c->fetch_out)
+        for (DevBuf& b : set)
+            if (b.p) (void)hipFree(b.p);
+    if (c->fetch_stage.p) (void)hipHostFree(c->fetch_stage.p);
+    for (hipEvent_t* e : {&c->fetch_chunk[0], &c->fetch_chunk[1], &c->fetch_chunk[2], &c->fetch_chunk[3], &c->fetch_start,
+                          &c->fetch_join, &c->fetch_ready[0], &c->fetch_ready[1], &c->fetch_free[0], &c->fetch_free[1]}) {
+        if (*e) (void)hipEventDestroy(*e);
+        *e = nullptr;
+    }
+    for (hipStream_t& s : c->fetch) {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    }
     for (DevBuf& b : c->pin)
         if (b.p) (void)hipHostFree(b.p);
     if (c->ransac_pin.p) (void)hipHostFree(c->ransac_pin.p);

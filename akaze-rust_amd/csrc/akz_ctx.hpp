@@ -219,6 +219,14 @@ struct akz_ctx {
         if (!workers) workers.reset(new WorkerPool(std::min(host_threads ? host_threads : host_cpu_share(), 16u) - 1));
         return *workers;
     }
+    // akz_fetch_pyramid (akz_extract.cpp), private to it like `lazy`: the streams its downloads run on, the pinned staging ring
+    // pageable destinations are filled through, and the recomputation of lean results -- temporaries that only the
+    // context's stream touches, and two sets of outputs (Lxx, Lyy, Lxy, Lstep) that the downloads read alternately
+    hipStream_t fetch[2] = {nullptr, nullptr};  // downloads alternate between two streams (two copy engines)
+    DevBuf fetch_stage;                      // pinned: kFetchStageBufs buffers of kFetchStageBytes
+    hipEvent_t fetch_chunk[4] = {nullptr, nullptr, nullptr, nullptr};  // a staging buffer's download is complete
+    DevBuf fetch_tmp[3], fetch_out[2][4];
+    hipEvent_t fetch_start = nullptr, fetch_join = nullptr, fetch_ready[2] = {nullptr, nullptr}, fetch_free[2] = {nullptr, nullptr};
 };
 
 // RAII stage timer: device stages bracket the enqueued work with two events on the stream; they

@@ -2264,5 +2264,217 @@ int akz_fetch_plane(const akz_result* r, uint64_t img, uint64_t level, akz_plane
     return AKZ_OK;
 }
 
+// ---- akz_fetch_pyramid -------------------------------------------------------------------------------------------------
+// Staging of pageable destinations: kFetchStageBufs pinned buffers of kFetchStageBytes.  The downloads of two buffers are
+// queued while the host copies the third one out.  8 MiB: one pinned D2H copy of 1 / 2 / 4 / 8 / 16 / 32 MiB moves
+// 36.1 / 43.6 / 49.2 / 52.9 / 55.2 / 56.1 GB/s on an MI355X (profiles/r07_pyramid_fetch.json), so 8 MiB is 0.94 of the
+// largest copy's rate while the ring stays at 24 MiB of page-locked memory per context.
+static constexpr int kFetchStageBufs = 3;
+static constexpr size_t kFetchStageBytes = (size_t)8 << 20;
+static_assert(kFetchStageBufs <= 4, "akz_ctx::fetch_chunk has 4 events");
+// host copies out of staging are split into pieces of this size across the context's worker threads
+static constexpr size_t kFetchHostPiece = (size_t)512 << 10;
+
+// [p, p + bytes) lies inside one page-locked host allocation (hipHostMalloc / hipHostRegister): the DMA may write it
+// directly.  Anything the runtime cannot vouch for -- pageable memory, a range that runs past the locked block -- is staged.
+static bool pinned_range(const void* p, size_t bytes) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    if (a.type != hipMemoryTypeHost) return false;
+    void* start = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, (hipDeviceptr_t)p) != hipSuccess ||
+        hipPointerGetAttribute(&size, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const uintptr_t b = (uintptr_t)start, q = (uintptr_t)p;
+    return q >= b && q + bytes <= b + size;
+}
+
+static int fetch_events(akz_ctx* c) {
+    for (hipStream_t& s : c->fetch)
+        if (!s) AKZ_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&c->fetch_chunk[0], &c->fetch_chunk[1], &c->fetch_chunk[2], &c->fetch_chunk[3], &c->fetch_start,
+                          &c->fetch_join, &c->fetch_ready[0], &c->fetch_ready[1], &c->fetch_free[0], &c->fetch_free[1]})
+        if (!*e) AKZ_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return AKZ_OK;
+}
+
+namespace {
+// Downloads on the context's two fetch streams, alternately, so that one copy's start-up hides under the other's transfer.
+// A pinned destination is written by the DMA itself; a pageable one goes through the staging ring: a chunk fills one
+// buffer (pieces of consecutive planes back to back, so the small coarse planes share one round trip), completes on its
+// event, and is copied out on the worker pool while the chunks behind it are in flight.
+struct FetchEngine {
+    explicit FetchEngine(akz_ctx* ctx) : c(ctx) {}
+    akz_ctx* c;
+    struct Piece { size_t off; float* dst; size_t bytes; };
+    std::vector<Piece> pieces[kFetchStageBufs];
+    size_t used = 0;
+    uint64_t filled = 0, drained = 0;  // chunks closed / copied out
+    uint64_t direct = 0;               // pinned destinations written
+    char* stage(uint64_t chunk) const { return (char*)c->fetch_stage.p + (chunk % kFetchStageBufs) * kFetchStageBytes; }
+
+    int copy(const float* src, float* dst, size_t bytes) {
+        if (pinned_range(dst, bytes)) {
+            AKZ_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->fetch[direct++ % 2]));
+            return AKZ_OK;
+        }
+        if (!c->fetch_stage.p) AKZ_TRY(ensure_pinned(c, c->fetch_stage, kFetchStageBufs * kFetchStageBytes));
+        const char* s = (const char*)src;
+        char* d = (char*)dst;
+        while (bytes) {
+            if (used == kFetchStageBytes) AKZ_TRY(close());
+            const size_t n = std::min(bytes, kFetchStageBytes - used);
+            AKZ_HIP_TRY(hipMemcpyAsync(stage(filled) + used, s, n, hipMemcpyDeviceToHost, c->fetch[filled % 2]));
+            pieces[filled % kFetchStageBufs].push_back({used, (float*)d, n});
+            used += n, s += n, d += n, bytes -= n;
+        }
+        return AKZ_OK;
+    }
+    // the current chunk is complete on the stream; its buffer's successor must be free before anything is staged into it
+    int close() {
+        if (!used) return AKZ_OK;
+        AKZ_HIP_TRY(hipEventRecord(c->fetch_chunk[filled % kFetchStageBufs], c->fetch[filled % 2]));
+        ++filled;
+        used = 0;
+        if (filled - drained == (uint64_t)kFetchStageBufs) AKZ_TRY(drain());
+        return AKZ_OK;
+    }
+    int drain() {
+        const int b = (int)(drained % kFetchStageBufs);
+        AKZ_HIP_TRY(hipEventSynchronize(c->fetch_chunk[b]));
+        const char* base = stage(drained);
+        struct Part { const char* src; char* dst; size_t bytes; };
+        std::vector<Part> parts;
+        for (const Piece& p : pieces[b])
+            for (size_t o = 0; o < p.bytes; o += kFetchHostPiece)
+                parts.push_back({base + p.off + o, (char*)p.dst + o, std::min(kFetchHostPiece, p.bytes - o)});
+        c->pool().run(parts.size(), [&](size_t i) { std::memcpy(parts[i].dst, parts[i].src, parts[i].bytes); });
+        pieces[b].clear();
+        ++drained;
+        return AKZ_OK;
+    }
+    int finish() {
+        AKZ_TRY(close());
+        while (drained < filled) AKZ_TRY(drain());
+        for (hipStream_t s : c->fetch) AKZ_HIP_TRY(hipStreamSynchronize(s));  // the direct (pinned) downloads
+        return AKZ_OK;
+    }
+};
+}  // namespace
+
+static int fetch_pyramid(const akz_result* r, uint64_t img, float* const* dst, uint64_t* bytes_out) {
+    akz_ctx* c = r->ctx;
+    const size_t L = r->plan.size();
+    auto px_of = [&](size_t l) { return (size_t)r->plan[l].w * r->plan[l].h; };
+    auto img_plane = [&](size_t l, int p) -> const float* {
+        return r->planes[l][p] ? r->planes[l][p] + (size_t)img * px_of(l) : nullptr;
+    };
+    // what each level needs recomputed (Lxx / Lyy / Lxy from Lsmooth, Lstep from the previous level's Lt): the planes
+    // akz_fetch_plane recomputes, requested and not kept
+    std::vector<uint8_t> need_deriv(L, 0), need_step(L, 0);
+    std::vector<size_t> rc;  // the levels to recompute, in order; level rc[k] uses output set k % 2
+    size_t rc_px = 0;
+    for (size_t l = 0; l < L; ++l) {
+        for (int p : {(int)AKZ_LXX, (int)AKZ_LYY, (int)AKZ_LXY})
+            if (dst[l * 10 + p] && !r->planes[l][p] && r->planes[l][AKZ_LSMOOTH]) need_deriv[l] = 1;
+        if (l > 0 && dst[l * 10 + AKZ_LSTEP] && !r->planes[l][AKZ_LSTEP] && r->planes[l - 1][AKZ_LT] && r->planes[l][AKZ_LFLOW])
+            need_step[l] = 1;
+        if (need_deriv[l] || need_step[l]) {
+            rc.push_back(l);
+            rc_px = std::max(rc_px, px_of(l));
+        }
+    }
+    AKZ_TRY(fetch_events(c));
+    if (!rc.empty()) {
+        const size_t pb = std::max(rc_px * sizeof(float), (size_t)4);
+        for (DevBuf& b : c->fetch_tmp) AKZ_TRY(ensure(c, b, pb));
+        for (size_t s = 0; s < std::min<size_t>(rc.size(), 2); ++s)
+            for (DevBuf& b : c->fetch_out[s]) AKZ_TRY(ensure(c, b, pb));
+    }
+    // everything queued on the context's stream so far (the result's own kernels included) comes before the downloads
+    AKZ_HIP_TRY(hipEventRecord(c->fetch_start, c->stream));
+    for (hipStream_t s : c->fetch) AKZ_HIP_TRY(hipStreamWaitEvent(s, c->fetch_start, 0));
+
+    // recomputation k on the context's stream, with the kernels and the argument order of recompute_plane.  Its output
+    // set was last read by the downloads of recomputation k - 2, which are queued by then (see the walk below).
+    auto recompute = [&](size_t k) -> int {
+        const size_t l = rc[k], s = k % 2;
+        const LevelPlan& lv = r->plan[l];
+        float* t[3] = {(float*)c->fetch_tmp[0].p, (float*)c->fetch_tmp[1].p, (float*)c->fetch_tmp[2].p};
+        float* o[4] = {(float*)c->fetch_out[s][0].p, (float*)c->fetch_out[s][1].p, (float*)c->fetch_out[s][2].p,
+                       (float*)c->fetch_out[s][3].p};
+        if (k >= 2) AKZ_HIP_TRY(hipStreamWaitEvent(c->stream, c->fetch_free[s], 0));
+        if (need_deriv[l])
+            AKZ_TRY(detector_impl(c, img_plane(l, AKZ_LSMOOTH), lv.det_sigma, t[0], t[1], o[0], o[1], o[2], t[2], lv.w, lv.h, 1));
+        if (need_step[l]) {
+            const LevelPlan& pv = r->plan[l - 1];
+            const float* in = img_plane(l - 1, AKZ_LT);
+            if (lv.octave > pv.octave) {  // first level of an octave: the 2x2 mean of the previous level's Lt
+                launch::half_size(c->stream, in, t[2], pv.w, pv.h, 1);
+                in = t[2];
+            }
+            if (lv.tau.empty())  // a level without diffusion steps keeps the zero plane (lib.rs:107)
+                AKZ_HIP_TRY(hipMemsetAsync(o[3], 0, px_of(l) * sizeof(float), c->stream));
+            AKZ_TRY(fed_impl(c, in, t[0], t[1], img_plane(l, AKZ_LFLOW), o[3], lv.w, lv.h, 1, lv.tau.data(), (uint32_t)lv.tau.size()));
+        }
+        AKZ_HIP_TRY(hipGetLastError());
+        AKZ_HIP_TRY(hipEventRecord(c->fetch_ready[s], c->stream));
+        return AKZ_OK;
+    };
+
+    FetchEngine eng(c);
+    uint64_t bytes = 0;
+    size_t next_rc = 0, k = 0;  // recomputations queued / the first one at or after the current level
+    for (size_t l = 0; l < L; ++l) {
+        while (k < rc.size() && rc[k] < l) ++k;
+        // one recomputation ahead of the downloads: level l's next one runs while this level is being copied
+        for (; next_rc < rc.size() && next_rc <= k + 1; ++next_rc) AKZ_TRY(recompute(next_rc));
+        const bool mine = k < rc.size() && rc[k] == l;
+        if (mine)
+            for (hipStream_t s : c->fetch) AKZ_HIP_TRY(hipStreamWaitEvent(s, c->fetch_ready[k % 2], 0));
+        for (int p = 0; p < 10; ++p) {
+            float* d = dst[l * 10 + p];
+            if (!d) continue;
+            const float* src = img_plane(l, p);
+            if (!src && mine && p >= AKZ_LXX && p <= AKZ_LXY && need_deriv[l]) src = (const float*)c->fetch_out[k % 2][p - AKZ_LXX].p;
+            if (!src && mine && p == AKZ_LSTEP && need_step[l]) src = (const float*)c->fetch_out[k % 2][3].p;
+            if (!src) continue;  // level 0's Lflow / Lstep
+            const size_t nb = px_of(l) * sizeof(float);
+            AKZ_TRY(eng.copy(src, d, nb));
+            bytes += nb;
+        }
+        if (mine) {  // both streams' downloads of the set are queued: join them into the one event the next user waits for
+            AKZ_HIP_TRY(hipEventRecord(c->fetch_join, c->fetch[1]));
+            AKZ_HIP_TRY(hipStreamWaitEvent(c->fetch[0], c->fetch_join, 0));
+            AKZ_HIP_TRY(hipEventRecord(c->fetch_free[k % 2], c->fetch[0]));
+        }
+    }
+    AKZ_TRY(eng.finish());
+    if (bytes_out) *bytes_out = bytes;
+    return AKZ_OK;
+}
+
+int akz_fetch_pyramid(const akz_result* r, uint64_t img, float* const* dst, uint64_t n_dst, uint64_t* bytes_out) {
+    AKZ_TRY(check_img(r, img));
+    if (!dst || n_dst != (uint64_t)r->plan.size() * 10) {
+        set_error("akz_fetch_pyramid: dst must hold n_levels * 10 entries");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    AKZ_TRY(bind(r->ctx));
+    const int rc = fetch_pyramid(r, img, dst, bytes_out);
+    if (rc != AKZ_OK) {  // nothing of this call may still be writing when it returns
+        for (hipStream_t s : r->ctx->fetch)
+            if (s) (void)hipStreamSynchronize(s);
+        (void)hipStreamSynchronize(r->ctx->stream);
+    }
+    return rc;
+}
+
 
 }  // extern "C"

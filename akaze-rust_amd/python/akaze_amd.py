@@ -187,6 +187,7 @@ def lib():
         "akz_result_copy_device_descriptors": ([vp, vp, u64, pu64], i32),
         "akz_result_level_info": ([vp, u64, pf64, pf64, pu32, pu32, pu32, pu32, pu32, pu64, pf64, u64], i32),
         "akz_fetch_plane": ([vp, u64, u64, i32, vp, pu64], i32),
+        "akz_fetch_pyramid": ([vp, u64, vp, u64, pu64], i32),
         "akz_result_device_plane": ([vp, u64, u64, i32, C.POINTER(vp)], i32),
         "akz_descriptor_match": ([vp, vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_device": ([vp, vp, u64, vp, u64, u64, f64, vp, vp], i32),
@@ -905,6 +906,53 @@ class ExtractResult:
         out = np.empty((info["h"], info["w"]), np.float32)
         _check(lib().akz_fetch_plane(self._h, img, lvl, pid, out.ctypes.data_as(C.c_void_p), C.byref(n)))
         return out
+
+    def pyramid(self, img=0, planes=None, out=None):
+        """Vec<EvolutionStep> of image `img` in one call (akz_fetch_pyramid): one dict per level, {plane name: 2-D float32
+        array}, for the names in `planes` (all of PLANES by default).  The arrays are views into one contiguous float32
+        buffer: `out` if given (e.g. pinned memory, torch.empty(n, pin_memory=True).numpy(); at least
+        pyramid_floats(img, planes) elements), else a fresh np.empty.  Level 0's Lflow / Lstep are (0, 0) arrays.
+        Pass a pinned or a reused `out` when fetching frame after frame: a fresh buffer's pages are first touched by the
+        copy out of staging, which halves the rate (profiles/r07_pyramid_fetch.json)."""
+        shapes = self._pyramid_shapes(img, planes)
+        nl = len(shapes)
+        total = sum(h * w for sh in shapes for h, w in sh.values())
+        if out is None:
+            buf = np.empty(total, np.float32)
+        else:
+            buf = out if isinstance(out, np.ndarray) else out.numpy()
+            if buf.dtype != np.float32 or not buf.flags.c_contiguous or buf.size < total:
+                raise ValueError(f"out must be a C-contiguous float32 buffer of at least {total} elements")
+            buf = buf.reshape(-1)
+        ptrs = (C.c_void_p * (nl * 10))()
+        levels, off = [], 0
+        for lvl, sh in enumerate(shapes):
+            views = {}
+            for name, (h, w) in sh.items():
+                views[name] = buf[off:off + h * w].reshape(h, w)
+                if h * w:
+                    ptrs[lvl * 10 + PLANES.index(name)] = buf.ctypes.data + off * 4
+                off += h * w
+            levels.append(views)
+        nbytes = C.c_uint64()
+        _check(lib().akz_fetch_pyramid(self._h, img, ptrs, nl * 10, C.byref(nbytes)))
+        return levels
+
+    def pyramid_floats(self, img=0, planes=None):
+        """Elements of the buffer pyramid(img, planes) fills."""
+        return sum(h * w for sh in self._pyramid_shapes(img, planes) for h, w in sh.values())
+
+    def _pyramid_shapes(self, img, planes):
+        want = set(PLANES) if planes is None else {planes} if isinstance(planes, str) else set(planes)
+        if want - set(PLANES):
+            raise ValueError(f"unknown planes {sorted(want - set(PLANES))} (names of {PLANES})")
+        names = [name for name in PLANES if name in want]  # the buffer follows akz_plane order
+        shapes = []
+        for lvl in range(self.counts(img)[0]):
+            info = self.level_info(lvl)
+            shapes.append({name: (0, 0) if lvl == 0 and name in ("Lflow", "Lstep") else (info["h"], info["w"])
+                           for name in names})
+        return shapes
 
 
 # ------------------------------------------------------------------------------------------

@@ -292,6 +292,19 @@ int akz_result_level_info(const akz_result* res, uint64_t level, double* etime, 
    EvolutionStep is complete either way.  out may be NULL to query the size. */
 int akz_fetch_plane(const akz_result* res, uint64_t img, uint64_t level, akz_plane plane, float* out,
                     uint64_t* n_px);
+/* The EvolutionStep images of image `img` of a result, all levels at once, into caller memory (Vec<EvolutionStep>,
+   akaze/src/lib.rs:193).  dst has n_levels * 10 entries, level-major, in akz_plane order: dst[level * 10 + plane].
+   A NULL entry skips that plane.  Entry (level, plane) needs room for that level's w*h floats
+   (akz_result_level_info).  Level 0's Lflow / Lstep (0 x 0) are ignored.
+   Planes the extraction did not keep are recomputed, bit-identical to akz_fetch_plane, once per level for all of
+   that level's missing planes.  Page-locked destinations (hipHostMalloc, hipHostRegister) are written by DMA directly;
+   pageable ones through pinned staging buffers of the context.  *bytes_out (may be NULL) = bytes written.  Returns
+   when every byte is in place.  Every argument is checked before the first byte moves (AKZ_ERR_INVALID_ARG: null
+   result, img out of range, dst NULL, n_dst != n_levels * 10; nothing is written then).
+   Thread rules of akz_fetch_plane: call it from the thread that uses the result's context, never while another call
+   on that context runs.  A job of the context that is begun and not yet finished is not disturbed. */
+int akz_fetch_pyramid(const akz_result* res, uint64_t img, float* const* dst, uint64_t n_dst,
+                      uint64_t* bytes_out);
 /* device address of a resident plane (NULL if not kept) */
 int akz_result_device_plane(const akz_result* res, uint64_t img, uint64_t level, akz_plane plane,
                             const float** d_plane);
