@@ -120,6 +120,12 @@ int akz_ctx_destroy(akz_ctx* c) {
                       &c->ms1.q8, &c->ms1.t8, &c->ms1.pop, &c->ms1.tab, &c->ms1.cols, &c->ms1.rec, &c->ransac_dev};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
+    for (DevBuf* b : {&c->jpeg_coef, &c->jpeg_plane, &c->jpeg_frames})
+        if (b->p) (void)hipFree(b->p);
+    for (int k = 0; k < akz_ctx::kJpegSlots; ++k) {
+        if (c->jpeg_up[k]) (void)hipEventDestroy(c->jpeg_up[k]);
+        if (c->jpeg_pin[k].p) (void)hipHostFree(c->jpeg_pin[k].p);
+    }
     for (DevBuf& b : c->fetch_tmp)
         if (b.p) (void)hipFree(b.p);
     for (auto& set : c->fetch_out)
@@ -350,20 +356,6 @@ int akz_ctx_get_profile2(akz_ctx* c, akz_profile* out, uint64_t struct_size, int
 int akz_ctx_get_profile(akz_ctx* c, akz_profile* out, int reset) {
     return akz_ctx_get_profile2(c, out, offsetof(akz_profile, placement_probed), reset);
 }
-// akaze::extract_features(input_image_path, options) — akaze/src/lib.rs:167-194
-int akz_extract_features_file(akz_ctx* c, const char* path, const akz_config* cfg, uint32_t flags, akz_result** out) {
-    if (!c || !path || !out) {
-        set_error("akz_extract_features_file: null argument");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    uint32_t w = 0, h = 0;
-    uint8_t* luma = nullptr;
-    AKZ_TRY(akz_image_load_luma(path, &w, &h, &luma));
-    const int st = akz_extract_gray_u8(c, luma, w, h, cfg, flags, out);
-    akz_image_free(luma);
-    return st;
-}
-
 // types::evolution::write_evolutions — evolution.rs:175-218 (file names: build_path, :163-168)
 int akz_write_evolutions(const akz_result* r, uint64_t img, const char* dir) {
     if (!r || !dir) {

@@ -4,6 +4,7 @@
 //   akz_ops.cpp      the per-op entry points (`pub mod ops` / `types::image`) and the launch helpers the pipeline shares with them
 //   akz_extract.cpp  extract_features: begin / finish halves, jobs, results, stream placement
 //   akz_match_api.cpp  descriptor_match in all its forms, match_features
+//   akz_jpeg_api.cpp   file ingest with JPEG reconstruction on the device (akz_extract_features_file / _files)
 // Every size / host-thread gate that picks between kernel families or paths is a named constant of akz_gates.hpp.
 #pragma once
 #include <algorithm>
@@ -227,7 +228,18 @@ struct akz_ctx {
     hipEvent_t fetch_chunk[4] = {nullptr, nullptr, nullptr, nullptr};  // a staging buffer's download is complete
     DevBuf fetch_tmp[3], fetch_out[2][4];
     hipEvent_t fetch_start = nullptr, fetch_join = nullptr, fetch_ready[2] = {nullptr, nullptr}, fetch_free[2] = {nullptr, nullptr};
+    // JPEG reconstruction (akz_jpeg_api.cpp): pinned staging the host decoder writes coefficients (or a host-decoded luma
+    // frame) into, one slot per decoding thread, each with the event of the upload that last read it; the device's
+    // coefficients and component planes of the frame being reconstructed, the luma frames of a file-based extraction;
+    // jpeg_m orders the uploads of a batch's decoding threads on the stream
+    static constexpr int kJpegSlots = 16;
+    DevBuf jpeg_pin[kJpegSlots];
+    hipEvent_t jpeg_up[kJpegSlots] = {};
+    DevBuf jpeg_coef, jpeg_plane, jpeg_frames;
+    std::mutex jpeg_m;
 };
+// akz_debug_kernel_rows stage of the JPEG rows: the reconstruction has no akz_profile stage of its own
+constexpr int kStageIngest = 10;
 
 // RAII stage timer: device stages bracket the enqueued work with two events on the stream; they
 // are resolved (hipEventElapsedTime) at the end of the extract call, after the final sync.
@@ -299,7 +311,7 @@ AKZ_LOCAL inline void resolve_spans(akz_ctx* c) {
         }
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, sp.a, sp.b) == hipSuccess) {
-            c->prof.ms[sp.stage] += (double)ms;
+            if (sp.stage < kStageIngest) c->prof.ms[sp.stage] += (double)ms;
             if (sp.row >= 0 && (size_t)sp.row < c->rows.size()) c->rows[(size_t)sp.row].ms += (double)ms;
         }
         c->ev_pool.push_back(sp.a);

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "akz_internal.hpp"
+#include "akz_jpeg.hpp"
 
 namespace akz {
 namespace img {
@@ -33,7 +34,7 @@ struct Image {
     std::vector<uint8_t> px;
 };
 
-static bool read_file(const char* path, std::vector<uint8_t>& out) {
+bool read_file(const char* path, std::vector<uint8_t>& out) {
     FILE* f = fopen(path, "rb");
     if (!f) return false;
     fseek(f, 0, SEEK_END);
@@ -233,8 +234,7 @@ struct Component {
     int bw = 0, bh = 0;          // blocks per row / column, padded to whole MCUs
     int cw = 0, chh = 0;         // blocks per row / column actually covering the component (non-interleaved scans)
     int dc_pred = 0, td = 0, ta = 0;
-    std::vector<int16_t> coef;   // bw * bh * 64, natural order
-    std::vector<uint8_t> plane;  // (bw*8) x (bh*8)
+    int16_t* coef = nullptr;     // bw * bh * 64, natural order (in the caller's storage: CoefAlloc)
 };
 
 struct Decoder {
@@ -247,6 +247,8 @@ struct Decoder {
     int width = 0, height = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
     bool progressive = false, have_frame = false;
     int restart_interval = 0;
+    const CoefAlloc* alloc = nullptr;  // where the coefficients go
+    Frame* frame = nullptr;             // their layout, handed to the caller
     // entropy-coded segment reader
     uint32_t bitbuf = 0;
     int bitcnt = 0;
@@ -345,13 +347,28 @@ struct Decoder {
         if (nc == 1) { comp[0].h = comp[0].v = 1; hmax = vmax = 1; }
         mcux = (width + 8 * hmax - 1) / (8 * hmax);
         mcuy = (height + 8 * vmax - 1) / (8 * vmax);
-        for (auto& c : comp) {
+        Frame& f = *frame;
+        f = Frame{};
+        f.width = (uint32_t)width; f.height = (uint32_t)height; f.hmax = (uint32_t)hmax; f.vmax = (uint32_t)vmax; f.nc = (uint32_t)nc;
+        for (int i = 0; i < nc; ++i) {
+            Component& c = comp[i];
             c.bw = mcux * c.h; c.bh = mcuy * c.v;
             const int cwpx = (width * c.h + hmax - 1) / hmax, chpx = (height * c.v + vmax - 1) / vmax;
             c.cw = (cwpx + 7) / 8; c.chh = (chpx + 7) / 8;
             if ((size_t)c.bw * c.bh > (1u << 24)) return fail("jpeg: image too large");
-            c.coef.assign((size_t)c.bw * c.bh * 64, 0);
+            FrameComp& fc = f.c[i];
+            fc.h = (uint32_t)c.h; fc.v = (uint32_t)c.v; fc.bw = (uint32_t)c.bw; fc.bh = (uint32_t)c.bh; fc.pw = (uint32_t)c.bw * 8;
+            fc.cwpx = (uint32_t)cwpx; fc.chpx = (uint32_t)chpx; fc.blk0 = f.nblocks;
+            f.nblocks += fc.bw * fc.bh;
+            fc.plane_off = f.plane_bytes;
+            fc.plane_len = std::max<uint64_t>((uint64_t)fc.pw * fc.bh * 8, (uint64_t)fc.pw * (height - 1) + width);
+            f.plane_bytes += (fc.plane_len + 7) & ~(uint64_t)7;
         }
+        int st = AKZ_OK;
+        int16_t* store = (*alloc)(f, &st);
+        if (!store) return st;
+        memset(store, 0, (size_t)f.nblocks * 64 * sizeof(int16_t));
+        for (int i = 0; i < nc; ++i) comp[i].coef = store + (size_t)f.c[i].blk0 * 64;
         progressive = prog;
         have_frame = true;
         return AKZ_OK;
@@ -501,7 +518,7 @@ struct Decoder {
         eobrun = 0;
         int rcount = 0;
         auto do_block = [&](Component& c, int bx, int by) -> int {
-            int16_t* blk = &c.coef[((size_t)by * c.bw + bx) * 64];
+            int16_t* blk = c.coef + ((size_t)by * c.bw + bx) * 64;
             if (!progressive) return block_baseline(c, blk);
             if (ss == 0) return block_dc_prog(c, blk, ah, al);
             return ah == 0 ? block_ac_first(c, blk, ss, se, al) : block_ac_refine(c, blk, ss, se, al);
@@ -527,64 +544,7 @@ struct Decoder {
         return AKZ_OK;
     }
 
-    // stb-style integer IDCT of one dequantised block.  64-bit intermediates: corrupt files carry coefficients that
-    // overflow the 32-bit form (identical results for every valid stream).
-    static void idct(const int16_t* in, const uint16_t* q, uint8_t* out, int stride) {
-        typedef int64_t I;
-        auto f2f = [](double x) { return (I)(x * 4096 + 0.5); };
-        static const I c0 = f2f(0.5411961), c1 = f2f(-1.847759065), c2 = f2f(0.765366865), c3 = f2f(1.175875602),
-                         c4 = f2f(0.298631336), c5 = f2f(2.053119869), c6 = f2f(3.072711026), c7 = f2f(1.501321110),
-                         c8 = f2f(-0.899976223), c9 = f2f(-2.562915447), c10 = f2f(-1.961570560), c11 = f2f(-0.390180644);
-        I val[64];
-        auto pass = [&](I s0, I s1, I s2, I s3, I s4, I s5, I s6, I s7, I (&x)[4], I (&t)[4]) {
-            I p2 = s2, p3 = s6;
-            I p1 = (p2 + p3) * c0;
-            I t2 = p1 + p3 * c1, t3 = p1 + p2 * c2;
-            p2 = s0; p3 = s4;
-            I t0 = (p2 + p3) * 4096, t1 = (p2 - p3) * 4096;
-            x[0] = t0 + t3; x[3] = t0 - t3; x[1] = t1 + t2; x[2] = t1 - t2;
-            t0 = s7; t1 = s5; t2 = s3; t3 = s1;
-            p3 = t0 + t2;
-            I p4 = t1 + t3;
-            p1 = t0 + t3; p2 = t1 + t2;
-            const I p5 = (p3 + p4) * c3;
-            t0 = t0 * c4; t1 = t1 * c5; t2 = t2 * c6; t3 = t3 * c7;
-            p1 = p5 + p1 * c8; p2 = p5 + p2 * c9; p3 = p3 * c10; p4 = p4 * c11;
-            t[3] = t3 + p1 + p4; t[2] = t2 + p2 + p3; t[1] = t1 + p2 + p4; t[0] = t0 + p1 + p3;
-        };
-        I dq[64];
-        for (int i = 0; i < 64; ++i) dq[i] = (I)in[i] * (I)q[i];
-        for (int i = 0; i < 8; ++i) {  // columns
-            const I* dcol = dq + i;
-            I* v = val + i;
-            if (!dcol[8] && !dcol[16] && !dcol[24] && !dcol[32] && !dcol[40] && !dcol[48] && !dcol[56]) {
-                const I dc = dcol[0] * 4;
-                for (int r = 0; r < 8; ++r) v[r * 8] = dc;
-                continue;
-            }
-            I x[4], t[4];
-            pass(dcol[0], dcol[8], dcol[16], dcol[24], dcol[32], dcol[40], dcol[48], dcol[56], x, t);
-            for (int k = 0; k < 4; ++k) x[k] += 512;
-            v[0] = (x[0] + t[3]) >> 10; v[56] = (x[0] - t[3]) >> 10;
-            v[8] = (x[1] + t[2]) >> 10; v[48] = (x[1] - t[2]) >> 10;
-            v[16] = (x[2] + t[1]) >> 10; v[40] = (x[2] - t[1]) >> 10;
-            v[24] = (x[3] + t[0]) >> 10; v[32] = (x[3] - t[0]) >> 10;
-        }
-        auto clamp8 = [](I x) { return (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x)); };
-        for (int i = 0; i < 8; ++i) {  // rows
-            const I* v = val + 8 * i;
-            uint8_t* o = out + (size_t)i * stride;
-            I x[4], t[4];
-            pass(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], x, t);
-            for (int k = 0; k < 4; ++k) x[k] += 65536 + ((I)128 << 17);
-            o[0] = clamp8((x[0] + t[3]) >> 17); o[7] = clamp8((x[0] - t[3]) >> 17);
-            o[1] = clamp8((x[1] + t[2]) >> 17); o[6] = clamp8((x[1] - t[2]) >> 17);
-            o[2] = clamp8((x[2] + t[1]) >> 17); o[5] = clamp8((x[2] - t[1]) >> 17);
-            o[3] = clamp8((x[3] + t[0]) >> 17); o[4] = clamp8((x[3] - t[0]) >> 17);
-        }
-    }
-
-    int run(Image& im) {
+    int run() {
         if (n < 4 || d[0] != 0xff || d[1] != 0xd8) return fail("jpeg: missing SOI");
         p = 2;
         bool eoi = false;
@@ -618,107 +578,183 @@ struct Decoder {
             p = end;
         }
         if (!have_frame) return fail("jpeg: no frame");
-        // dequantise + IDCT into padded component planes
-        for (auto& c : comp) {
-            if (!qt_present[c.tq]) return fail("jpeg: missing quantisation table");
-            const int pw = c.bw * 8;
-            c.plane.assign((size_t)pw * c.bh * 8, 0);
-            for (int by = 0; by < c.bh; ++by)
-                for (int bx = 0; bx < c.bw; ++bx)
-                    idct(&c.coef[((size_t)by * c.bw + bx) * 64], qt[c.tq], &c.plane[(size_t)by * 8 * pw + bx * 8], pw);
-            std::vector<int16_t>().swap(c.coef);
-        }
-        im.w = (uint32_t)width; im.h = (uint32_t)height;
-        if (comp.size() == 1) {
-            im.ch = 1;
-            im.px.resize((size_t)width * height);
-            const int pw = comp[0].bw * 8;
-            for (int y = 0; y < height; ++y) memcpy(&im.px[(size_t)y * width], &comp[0].plane[(size_t)y * pw], width);
-            return AKZ_OK;
-        }
-        // chroma upsampling (triangle filter for 2x, nearest otherwise) + YCbCr -> RGB
-        im.ch = 3;
-        im.px.resize((size_t)width * height * 3);
-        std::vector<std::vector<uint8_t>> rows(3, std::vector<uint8_t>((size_t)width + 16));
-        for (int y = 0; y < height; ++y) {
-            for (int ci = 0; ci < 3; ++ci) {
-                const Component& c = comp[ci];
-                const int pw = c.bw * 8;
-                const int sh = hmax / c.h, sv = vmax / c.v;
-                const int cwpx = (width * c.h + hmax - 1) / hmax, chpx = (height * c.v + vmax - 1) / vmax;
-                uint8_t* o = rows[ci].data();
-                if (sh == 1 && sv == 1) {
-                    memcpy(o, &c.plane[(size_t)y * pw], width);
-                } else if (sh == 2 && (sv == 1 || sv == 2) && hmax % c.h == 0 && vmax % c.v == 0) {
-                    int yn = y, yf = y;
-                    if (sv == 2) {
-                        yn = y >> 1;
-                        yf = (y & 1) ? std::min(yn + 1, chpx - 1) : std::max(yn - 1, 0);
-                    }
-                    const uint8_t* near_ = &c.plane[(size_t)yn * pw];
-                    const uint8_t* far_ = &c.plane[(size_t)yf * pw];
-                    if (sv == 1) {
-                        if (cwpx == 1) { o[0] = o[1] = near_[0]; }
-                        else {
-                            o[0] = near_[0];
-                            o[1] = (uint8_t)((near_[0] * 3 + near_[1] + 2) >> 2);
-                            for (int i = 1; i < cwpx - 1; ++i) {
-                                const int s = 3 * near_[i] + 2;
-                                o[2 * i] = (uint8_t)((s + near_[i - 1]) >> 2);
-                                o[2 * i + 1] = (uint8_t)((s + near_[i + 1]) >> 2);
-                            }
-                            o[2 * (cwpx - 1)] = (uint8_t)((near_[cwpx - 1] * 3 + near_[cwpx - 2] + 2) >> 2);
-                            o[2 * (cwpx - 1) + 1] = near_[cwpx - 1];
-                        }
-                    } else {
-                        if (cwpx == 1) { o[0] = o[1] = (uint8_t)((3 * near_[0] + far_[0] + 2) >> 2); }
-                        else {
-                            int t1 = 3 * near_[0] + far_[0], t0;
-                            o[0] = (uint8_t)((t1 + 2) >> 2);
-                            for (int i = 1; i < cwpx; ++i) {
-                                t0 = t1;
-                                t1 = 3 * near_[i] + far_[i];
-                                o[2 * i - 1] = (uint8_t)((3 * t0 + t1 + 8) >> 4);
-                                o[2 * i] = (uint8_t)((3 * t1 + t0 + 8) >> 4);
-                            }
-                            o[2 * cwpx - 1] = (uint8_t)((t1 + 2) >> 2);
-                        }
-                    }
-                } else {
-                    const int yy = std::min(y * c.v / vmax, chpx - 1);
-                    for (int x = 0; x < width; ++x) o[x] = c.plane[(size_t)yy * pw + std::min(x * c.h / hmax, cwpx - 1)];
-                }
-            }
-            uint8_t* o = &im.px[(size_t)y * width * 3];
-            auto clamp8 = [](int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
-            for (int x = 0; x < width; ++x) {
-                const float Y = (float)rows[0][x], cb = (float)rows[1][x] - 128.0f, cr = (float)rows[2][x] - 128.0f;
-                const float r = Y + 1.40200f * cr;
-                const float g = Y - 0.34414f * cb - 0.71414f * cr;
-                const float b = Y + 1.77200f * cb;
-                o[3 * x] = clamp8((int)(r + 0.5f));
-                o[3 * x + 1] = clamp8((int)(g + 0.5f));
-                o[3 * x + 2] = clamp8((int)(b + 0.5f));
-            }
+        for (size_t i = 0; i < comp.size(); ++i) {
+            if (!qt_present[comp[i].tq]) return fail("jpeg: missing quantisation table");
+            memcpy(frame->c[i].q, qt[comp[i].tq], sizeof(frame->c[i].q));
         }
         return AKZ_OK;
     }
 };
 
+int decode_coefs(const uint8_t* d, size_t n, const CoefAlloc& alloc, Frame& f) {
+    Decoder dec;
+    dec.d = d;
+    dec.n = n;
+    memset(dec.qt, 0, sizeof(dec.qt));
+    dec.alloc = &alloc;
+    dec.frame = &f;
+    return dec.run();
+}
+
+// stb-style integer IDCT of one dequantised block.  64-bit intermediates: corrupt files carry coefficients that
+// overflow the 32-bit form (identical results for every valid stream).
+static void idct(const int16_t* in, const uint16_t* q, uint8_t* out, int stride) {
+    typedef int64_t I;
+    auto f2f = [](double x) { return (I)(x * 4096 + 0.5); };
+    static const I c0 = f2f(0.5411961), c1 = f2f(-1.847759065), c2 = f2f(0.765366865), c3 = f2f(1.175875602),
+                     c4 = f2f(0.298631336), c5 = f2f(2.053119869), c6 = f2f(3.072711026), c7 = f2f(1.501321110),
+                     c8 = f2f(-0.899976223), c9 = f2f(-2.562915447), c10 = f2f(-1.961570560), c11 = f2f(-0.390180644);
+    I val[64];
+    auto pass = [&](I s0, I s1, I s2, I s3, I s4, I s5, I s6, I s7, I (&x)[4], I (&t)[4]) {
+        I p2 = s2, p3 = s6;
+        I p1 = (p2 + p3) * c0;
+        I t2 = p1 + p3 * c1, t3 = p1 + p2 * c2;
+        p2 = s0; p3 = s4;
+        I t0 = (p2 + p3) * 4096, t1 = (p2 - p3) * 4096;
+        x[0] = t0 + t3; x[3] = t0 - t3; x[1] = t1 + t2; x[2] = t1 - t2;
+        t0 = s7; t1 = s5; t2 = s3; t3 = s1;
+        p3 = t0 + t2;
+        I p4 = t1 + t3;
+        p1 = t0 + t3; p2 = t1 + t2;
+        const I p5 = (p3 + p4) * c3;
+        t0 = t0 * c4; t1 = t1 * c5; t2 = t2 * c6; t3 = t3 * c7;
+        p1 = p5 + p1 * c8; p2 = p5 + p2 * c9; p3 = p3 * c10; p4 = p4 * c11;
+        t[3] = t3 + p1 + p4; t[2] = t2 + p2 + p3; t[1] = t1 + p2 + p4; t[0] = t0 + p1 + p3;
+    };
+    I dq[64];
+    for (int i = 0; i < 64; ++i) dq[i] = (I)in[i] * (I)q[i];
+    for (int i = 0; i < 8; ++i) {  // columns
+        const I* dcol = dq + i;
+        I* v = val + i;
+        if (!dcol[8] && !dcol[16] && !dcol[24] && !dcol[32] && !dcol[40] && !dcol[48] && !dcol[56]) {
+            const I dc = dcol[0] * 4;
+            for (int r = 0; r < 8; ++r) v[r * 8] = dc;
+            continue;
+        }
+        I x[4], t[4];
+        pass(dcol[0], dcol[8], dcol[16], dcol[24], dcol[32], dcol[40], dcol[48], dcol[56], x, t);
+        for (int k = 0; k < 4; ++k) x[k] += 512;
+        v[0] = (x[0] + t[3]) >> 10; v[56] = (x[0] - t[3]) >> 10;
+        v[8] = (x[1] + t[2]) >> 10; v[48] = (x[1] - t[2]) >> 10;
+        v[16] = (x[2] + t[1]) >> 10; v[40] = (x[2] - t[1]) >> 10;
+        v[24] = (x[3] + t[0]) >> 10; v[32] = (x[3] - t[0]) >> 10;
+    }
+    auto clamp8 = [](I x) { return (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x)); };
+    for (int i = 0; i < 8; ++i) {  // rows
+        const I* v = val + 8 * i;
+        uint8_t* o = out + (size_t)i * stride;
+        I x[4], t[4];
+        pass(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], x, t);
+        for (int k = 0; k < 4; ++k) x[k] += 65536 + ((I)128 << 17);
+        o[0] = clamp8((x[0] + t[3]) >> 17); o[7] = clamp8((x[0] - t[3]) >> 17);
+        o[1] = clamp8((x[1] + t[2]) >> 17); o[6] = clamp8((x[1] - t[2]) >> 17);
+        o[2] = clamp8((x[2] + t[1]) >> 17); o[5] = clamp8((x[2] - t[1]) >> 17);
+        o[3] = clamp8((x[3] + t[0]) >> 17); o[4] = clamp8((x[3] - t[0]) >> 17);
+    }
+}
+
+// Part two on the host: dequantise + IDCT into padded component planes, then upsampling and colour conversion.
+void reconstruct_host(const Frame& f, const int16_t* coef, uint32_t* ch, std::vector<uint8_t>& px) {
+    const int width = (int)f.width, height = (int)f.height, hmax = (int)f.hmax, vmax = (int)f.vmax;
+    std::vector<std::vector<uint8_t>> planes(f.nc);
+    for (uint32_t ci = 0; ci < f.nc; ++ci) {
+        const FrameComp& c = f.c[ci];
+        const int pw = (int)c.pw;
+        planes[ci].assign((size_t)c.plane_len, 0);
+        for (uint32_t by = 0; by < c.bh; ++by)
+            for (uint32_t bx = 0; bx < c.bw; ++bx)
+                idct(&coef[((size_t)c.blk0 + (size_t)by * c.bw + bx) * 64], c.q, &planes[ci][(size_t)by * 8 * pw + bx * 8], pw);
+    }
+    if (f.nc == 1) {
+        *ch = 1;
+        px.resize((size_t)width * height);
+        const int pw = (int)f.c[0].pw;
+        for (int y = 0; y < height; ++y) memcpy(&px[(size_t)y * width], &planes[0][(size_t)y * pw], width);
+        return;
+    }
+    // chroma upsampling (triangle filter for 2x, nearest otherwise) + YCbCr -> RGB
+    *ch = 3;
+    px.resize((size_t)width * height * 3);
+    std::vector<std::vector<uint8_t>> rows(3, std::vector<uint8_t>((size_t)width + 16));
+    for (int y = 0; y < height; ++y) {
+        for (int ci = 0; ci < 3; ++ci) {
+            const FrameComp& c = f.c[ci];
+            const uint8_t* plane = planes[ci].data();
+            const int pw = (int)c.pw;
+            const int sh = hmax / (int)c.h, sv = vmax / (int)c.v;
+            const int cwpx = (int)c.cwpx, chpx = (int)c.chpx;
+            uint8_t* o = rows[ci].data();
+            if (sh == 1 && sv == 1) {
+                memcpy(o, &plane[(size_t)y * pw], width);
+            } else if (sh == 2 && (sv == 1 || sv == 2) && hmax % (int)c.h == 0 && vmax % (int)c.v == 0) {
+                int yn = y, yf = y;
+                if (sv == 2) {
+                    yn = y >> 1;
+                    yf = (y & 1) ? std::min(yn + 1, chpx - 1) : std::max(yn - 1, 0);
+                }
+                const uint8_t* near_ = &plane[(size_t)yn * pw];
+                const uint8_t* far_ = &plane[(size_t)yf * pw];
+                if (sv == 1) {
+                    if (cwpx == 1) { o[0] = o[1] = near_[0]; }
+                    else {
+                        o[0] = near_[0];
+                        o[1] = (uint8_t)((near_[0] * 3 + near_[1] + 2) >> 2);
+                        for (int i = 1; i < cwpx - 1; ++i) {
+                            const int s = 3 * near_[i] + 2;
+                            o[2 * i] = (uint8_t)((s + near_[i - 1]) >> 2);
+                            o[2 * i + 1] = (uint8_t)((s + near_[i + 1]) >> 2);
+                        }
+                        o[2 * (cwpx - 1)] = (uint8_t)((near_[cwpx - 1] * 3 + near_[cwpx - 2] + 2) >> 2);
+                        o[2 * (cwpx - 1) + 1] = near_[cwpx - 1];
+                    }
+                } else {
+                    if (cwpx == 1) { o[0] = o[1] = (uint8_t)((3 * near_[0] + far_[0] + 2) >> 2); }
+                    else {
+                        int t1 = 3 * near_[0] + far_[0], t0;
+                        o[0] = (uint8_t)((t1 + 2) >> 2);
+                        for (int i = 1; i < cwpx; ++i) {
+                            t0 = t1;
+                            t1 = 3 * near_[i] + far_[i];
+                            o[2 * i - 1] = (uint8_t)((3 * t0 + t1 + 8) >> 4);
+                            o[2 * i] = (uint8_t)((3 * t1 + t0 + 8) >> 4);
+                        }
+                        o[2 * cwpx - 1] = (uint8_t)((t1 + 2) >> 2);
+                    }
+                }
+            } else {
+                const int yy = std::min(y * (int)c.v / vmax, chpx - 1);
+                for (int x = 0; x < width; ++x) o[x] = plane[(size_t)yy * pw + std::min(x * (int)c.h / hmax, cwpx - 1)];
+            }
+        }
+        uint8_t* o = &px[(size_t)y * width * 3];
+        auto clamp8 = [](int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
+        for (int x = 0; x < width; ++x) {
+            const float Y = (float)rows[0][x], cb = (float)rows[1][x] - 128.0f, cr = (float)rows[2][x] - 128.0f;
+            const float r = Y + 1.40200f * cr;
+            const float g = Y - 0.34414f * cb - 0.71414f * cr;
+            const float b = Y + 1.77200f * cb;
+            o[3 * x] = clamp8((int)(r + 0.5f));
+            o[3 * x + 1] = clamp8((int)(g + 0.5f));
+            o[3 * x + 2] = clamp8((int)(b + 0.5f));
+        }
+    }
+}
+
 }  // namespace jpg
 
 static int decode_jpeg(const std::vector<uint8_t>& d, Image& im) {
-    jpg::Decoder dec;
-    dec.d = d.data();
-    dec.n = d.size();
-    memset(dec.qt, 0, sizeof(dec.qt));
-    return dec.run(im);
+    std::vector<int16_t> coef;
+    jpg::Frame f;
+    AKZ_TRY(jpg::decode_coefs(d.data(), d.size(), [&](const jpg::Frame& fr, int*) {
+        coef.resize((size_t)fr.nblocks * 64);
+        return coef.data();
+    }, f));
+    im.w = f.width; im.h = f.height;
+    jpg::reconstruct_host(f, coef.data(), &im.ch, im.px);
+    return AKZ_OK;
 }
 
-int load(const char* path, Image& im) {
-    if (!path) { set_error("image: null path"); return AKZ_ERR_INVALID_ARG; }
-    std::vector<uint8_t> d;
-    if (!read_file(path, d)) { set_error(std::string("image: cannot read ") + path); return AKZ_ERR_IO; }
+static int decode_bytes(const std::vector<uint8_t>& d, Image& im) {
     static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     try {
         if (d.size() >= 8 && !memcmp(d.data(), png_sig, 8)) return decode_png(d, im);
@@ -732,6 +768,13 @@ int load(const char* path, Image& im) {
     return AKZ_ERR_UNSUPPORTED;
 }
 
+int load(const char* path, Image& im) {
+    if (!path) { set_error("image: null path"); return AKZ_ERR_INVALID_ARG; }
+    std::vector<uint8_t> d;
+    if (!read_file(path, d)) { set_error(std::string("image: cannot read ") + path); return AKZ_ERR_IO; }
+    return decode_bytes(d, im);
+}
+
 // DynamicImage::to_luma of `image` 0.21 (believed: f32 weights, truncating cast)
 void to_luma(const Image& im, std::vector<uint8_t>& out) {
     if (im.ch == 1) { out = im.px; return; }
@@ -740,6 +783,13 @@ void to_luma(const Image& im, std::vector<uint8_t>& out) {
         const float l = 0.2126f * (float)im.px[3 * i] + 0.7152f * (float)im.px[3 * i + 1] + 0.0722f * (float)im.px[3 * i + 2];
         out[i] = (uint8_t)l;
     }
+}
+int load_luma_bytes(const char* path, const std::vector<uint8_t>& d, uint32_t* w, uint32_t* h, std::vector<uint8_t>& luma) {
+    Image im;
+    AKZ_TRY(decode_bytes(d, im));
+    to_luma(im, luma);
+    *w = im.w; *h = im.h;
+    return AKZ_OK;
 }
 void to_rgb(const Image& im, std::vector<uint8_t>& out) {
     if (im.ch == 3) { out = im.px; return; }

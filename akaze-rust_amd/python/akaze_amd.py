@@ -24,6 +24,7 @@ AKZ_KEEP_ALL_PLANES = 1
 AKZ_NO_HOST_DESCRIPTORS = 2
 AKZ_NO_DETECT = 4
 AKZ_INPUT_READY = 8
+AKZ_ERR_BUFFER = -7
 
 PLANES = ["Lt", "Lsmooth", "Lx", "Ly", "Lxx", "Lyy", "Lxy", "Lflow", "Lstep", "Ldet"]
 
@@ -67,7 +68,8 @@ class KernelRow(C.Structure):
                 ("n", C.c_uint32), ("launches", C.c_uint64), ("px", C.c_uint64), ("px_steps", C.c_uint64), ("ms", C.c_double)]
 
 
-KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march"}
+KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march",
+                    6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d"}
 
 
 class Gate(C.Structure):
@@ -219,6 +221,8 @@ def lib():
         "akz_image_load_rgb": ([C.c_char_p, pu32, pu32, C.POINTER(vp)], i32),
         "akz_image_free": ([vp], None),
         "akz_extract_features_file": ([vp, C.c_char_p, C.POINTER(Config), u32, C.POINTER(vp)], i32),
+        "akz_image_load_luma_device": ([vp, C.c_char_p, vp, u64, pu32, pu32], i32),
+        "akz_extract_features_files": ([vp, C.POINTER(C.c_char_p), u64, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_config_to_json": ([C.POINTER(Config), C.c_char_p, u64, pu64], i32),
         "akz_config_from_json": ([C.c_char_p, C.POINTER(Config)], i32),
         "akz_image_save_png": ([C.c_char_p, vp, u32, u32, u32], i32),
@@ -556,6 +560,29 @@ class Context:
         _check(lib().akz_extract_features_file(self._h, os.fsencode(path), C.byref(cfg),
                                                AKZ_KEEP_ALL_PLANES if keep_all_planes else 0, C.byref(res)))
         return ExtractResult(self, res)
+
+    def extract_features_files(self, paths, options=None, keep_all_planes=True):
+        """akz_extract_features_files: one batch job over files of one size (image i of the result = paths[i])."""
+        cfg = options or Config()
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        res = C.c_void_p()
+        _check(lib().akz_extract_features_files(self._h, arr, len(paths), C.byref(cfg),
+                                                AKZ_KEEP_ALL_PLANES if keep_all_planes else 0, C.byref(res)))
+        return ExtractResult(self, res)
+
+    def load_luma_device(self, path):
+        """akz_image_load_luma_device: load_image_luma(path) as a (h, w) uint8 torch CUDA tensor (a JPEG is reconstructed
+        on the device)."""
+        import torch
+        w, h = C.c_uint32(), C.c_uint32()
+        st = lib().akz_image_load_luma_device(self._h, os.fsencode(path), None, 0, C.byref(w), C.byref(h))
+        if st != AKZ_ERR_BUFFER:
+            _check(st)
+        out = torch.empty((h.value, w.value), dtype=torch.uint8, device=f"cuda:{self.device}")
+        torch.cuda.current_stream(out.device).synchronize()  # (the allocation is ordered on torch's stream, the work on ours)
+        _check(lib().akz_image_load_luma_device(self._h, os.fsencode(path), C.c_void_p(out.data_ptr()), out.numel(),
+                                                C.byref(w), C.byref(h)))
+        return out
 
     def extract_from_planes(self, w, h, planes, options=None, detect=True):
         """ops::scale_space_extrema::detect_keypoints / ops::descriptors::extract_descriptors on evolutions the caller

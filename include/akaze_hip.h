@@ -604,8 +604,20 @@ int akz_image_load_rgb(const char* path, uint32_t* width, uint32_t* height, uint
 void akz_image_free(void* pixels);
 /* akaze::extract_features(input_image_path, options) — akaze/src/lib.rs:167-194: decode, to_luma,
    unit float image, scale space, keypoints, descriptors.  Equivalent to akz_image_load_luma +
-   akz_extract_gray_u8. */
+   akz_extract_gray_u8: a JPEG is entropy-decoded on the host and reconstructed on the device (the same pixels). */
 int akz_extract_features_file(akz_ctx* ctx, const char* path, const akz_config* cfg, uint32_t flags, akz_result** out);
+/* akz_image_load_luma into device memory: the w * h luma bytes (row-major) at d_luma, complete on return.  A JPEG is
+   entropy-decoded on the host and reconstructed on the device on the context's stream (bytes identical to
+   akz_image_load_luma); PNG and PNM are decoded on the host and uploaded.  Same errors as akz_image_load_luma.  If
+   capacity < w * h: AKZ_ERR_BUFFER, *width / *height set, nothing written (d_luma may be NULL with capacity 0). */
+int akz_image_load_luma_device(akz_ctx* ctx, const char* path, uint8_t* d_luma, uint64_t capacity, uint32_t* width,
+                               uint32_t* height);
+/* extract_features over n files of one size as one batch job: the result of akz_extract_device_u8 on their luma frames.
+   The files are decoded on the context's host threads (akz_ctx_set_host_threads), each uploaded and reconstructed into
+   its frame while the others are still decoding.  Files of different sizes: AKZ_ERR_INVALID_ARG naming the first path
+   whose size differs from paths[0]'s; an unreadable or corrupt file: the status of akz_image_load_luma.  No result then. */
+int akz_extract_features_files(akz_ctx* ctx, const char* const* paths, uint64_t n, const akz_config* cfg, uint32_t flags,
+                               akz_result** out);
 /* serde_json form of Config (what `-o options.json` reads and writes, extract_features.rs:66-83).
    to_json: writes a NUL-terminated string, *len = its length (AKZ_ERR_BUFFER if cap is too small, *len
    then holds the size needed).  from_json: fields that are absent keep the value already in *cfg

@@ -96,8 +96,12 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    covered by a group of k_fed_own launches, levels inside a k_octave_resident launch, sigma_size of a detector launch;
    (w, h, n): the launch's level size and batch (the largest level of a k_detector_tiled launch over several levels);
    launches, px = level pixels x batch, px_steps = pixel-steps advanced, ms = sum of the spans.  Rows accumulate like
-   akz_profile; reset != 0 zeroes the figures.  *n_rows = rows there are (may exceed cap). */
-enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5 };
+   akz_profile; reset != 0 zeroes the figures.  *n_rows = rows there are (may exceed cap).
+   JPEG reconstruction (akz_extract_features_file / _files, akz_image_load_luma_device) adds rows of stage 10, which no
+   akz_profile stage counts: k_jpeg_idct (px = coefficients), k_jpeg_luma (px = output pixels) and the coefficient upload
+   (px = bytes copied), each with param = components and (w, h, 1) = the frame. */
+enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5,
+       AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8 };
 typedef struct akz_kernel_row {
     uint32_t stage, kind, param, w, h, n;
     uint64_t launches, px, px_steps;
