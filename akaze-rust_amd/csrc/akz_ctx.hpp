@@ -112,6 +112,14 @@ struct akz_ctx {
                                              // single-stream: only ever touched by launches on `stream` (see match_device_impl)
     uint32_t match_epoch = 0;
     DevBuf ransac_dev, ransac_pin;           // match_features: the trials' inputs and outputs on the device / pinned staging of both
+    // akz_match_features_pairs: the sets' rows and x / y; raw lists, their counts and points; pair table and two slots of
+    // trial samples; models and inlier counts; kept lists with their counts -- and the pinned staging of each
+    DevBuf mp_in, mp_raw, mp_tab, mp_trials, mp_keep;
+    DevBuf mp_pin_in, mp_pin_tab, mp_pin_smp[2], mp_pin_out;
+    hipEvent_t mp_smp_ev[2] = {nullptr, nullptr};
+    hipEvent_t mp_split_ev[7] = {};          // akz_debug_match_pairs_split: stage boundaries of a timed call
+    bool mp_split_on = false;
+    double mp_split_ms[6] = {};
     DevBuf mm_q8, mm_t8, mm_pop, mm_tab;     // MFMA matcher: unpacked int8 images of the two sets, bit counts, set tables
     DevBuf mm_cols;                          // both-direction launches: the train rows' (best, second) state, seed records and bound
     void* tab_ring = nullptr;                // pinned staging ring of the multi-set matcher's tables

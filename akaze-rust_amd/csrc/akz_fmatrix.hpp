@@ -79,13 +79,16 @@ AKZ_HD int smallest_singular(M& m, float epsilon, bool* full_rank) {
 }
 
 // the design matrix of eight correspondences (:26-40), products in f32 as the reference forms them
+// (row i of one correspondence: the batched trials of akz_fmatrix.hip form the rows of a matrix on several lanes)
+template <class M>
+AKZ_HD void design_row(M& m, int i, float x0, float y0, float x1, float y1) {
+    const float row[9] = {x0 * x1, x0 * y1, x0, y0 * x1, y0 * y1, y0, x1, y1, 1.0f};
+    AKZ_UNROLL
+    for (int k = 0; k < 9; ++k) m.at(i, k) = (double)row[k];
+}
 template <class M>
 AKZ_HD void design_matrix(M& m, const float (&x0)[8], const float (&y0)[8], const float (&x1)[8], const float (&y1)[8]) {
-    for (int i = 0; i < 8; ++i) {
-        const float row[9] = {x0[i] * x1[i], x0[i] * y1[i], x0[i], y0[i] * x1[i], y0[i] * y1[i], y0[i], x1[i], y1[i], 1.0f};
-        AKZ_UNROLL
-        for (int k = 0; k < 9; ++k) m.at(i, k) = (double)row[k];
-    }
+    for (int i = 0; i < 8; ++i) design_row(m, i, x0[i], y0[i], x1[i], y1[i]);
 }
 // the model from the rotated matrix: the right singular vector of the smallest of the 8 singular values, as
 // [[v0, v3, v6], [v1, v4, v7], [v2, v5, v8]] (:46-66).  false: rank < 8 at `epsilon` (the reference's None, :44).

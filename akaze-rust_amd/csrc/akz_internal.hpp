@@ -49,6 +49,10 @@ struct DefaultSource {
     }
 };
 DefaultSource& default_source();
+// the samples of `trials` RANSAC trials over n_matches matches: 8 ascending indices per trial into out (akz_ransac.cpp;
+// T = uint64_t or uint32_t)
+template <class T>
+void draw_samples(DefaultSource& src, uint64_t n_matches, uint64_t trials, T* out);
 
 #define AKZ_TRY(expr)            \
     do {                         \
@@ -351,6 +355,26 @@ void unpack_bits(hipStream_t s, const uint8_t* d, uint32_t n, uint32_t n_pad, bo
 // one workgroup per RANSAC trial: model of its eight samples (akz_fmatrix.hpp) + inlier count over all matches (akz_fmatrix.hip)
 void ransac_trials(hipStream_t s, const float* d_pts, uint32_t n_matches, const uint32_t* d_samples, uint32_t trials, float epsilon_model,
                    float epsilon_inlier, float* d_models, int32_t* d_inliers);
+// akz_match_features_pairs (akz_fmatrix.hip).  Per pair p: its matches at d_raw + raw_off, their count at d_raw_cnt[cnt_idx];
+// its x0 | y0 | x1 | y1 at d_pts + {0, 1, 2, 3} * pts_stride + raw_off; its trials at trial_off .. + n_trials of the call
+struct PairJobHost {  // = PairJob of akz_fmatrix.hip
+    uint64_t raw_off, kp0_off, kp1_off, trial_off, keep_off, n_trials;
+    uint32_t cnt_idx, pad;
+};
+static_assert(sizeof(PairJobHost) == 56, "the device reads 56-byte pair records");
+// gathers the keypoint coordinates of every pair's matches (kx / ky: x / y of every uploaded set's keypoints)
+void pair_points(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                 const float* d_kx, const float* d_ky, float* d_pts, uint64_t pts_stride);
+// trials first_trial .. + n_trials of the call: d_trials holds this chunk's 8 sample indices per trial (relative to the
+// pair's first match), then the pair of every trial; models / inliers are indexed by the call's trial number
+void ransac_trials_multi(hipStream_t s, const PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
+                         const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier,
+                         float* d_models, int32_t* d_inliers);
+// per pair: the first trial with the most inliers (zero model without one above 0), then the matches it keeps, compacted in
+// order at d_keep + keep_off, their count at d_keep_cnt[pair] (fewer than 8 matches: all of them)
+void ransac_pick_filter(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                        const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float epsilon_inlier,
+                        void* d_keep, uint64_t* d_keep_cnt);
 void unpack_pair(hipStream_t s, const uint8_t* dq, uint32_t nq, uint32_t q_pad, uint8_t* outq, uint32_t* popq, uint32_t* bound, uint32_t threshold,
                  const uint8_t* dt, uint32_t nt, uint32_t t_pad, uint8_t* outt, uint32_t* popt, bool fp4);
 uint32_t match_mfma_tile_rows();

@@ -384,4 +384,271 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
                                 on_device);
 }
 
+// match_features over many pairs (see the header).  Stages, all on the context's stream: every distinct set's 64-byte rows and
+// keypoint x / y through pinned staging; the descriptor scans (one multi-set launch per first set, or the pair matcher for
+// rows of 62..64 bytes); k_pair_points; ONE read-back of the match counts; the samples drawn on the calling thread in pair
+// order, in chunks whose trials (k_ransac_trials_multi) run while the next chunk is drawn; k_ransac_pick_filter; ONE read-back
+// of the kept lists.
+int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                             uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                             akz_match* out, uint64_t* n_out) {
+    if (n_pairs == 0) return AKZ_OK;
+    auto refuse = [](const std::string& msg) {
+        set_error("match_features_pairs: " + msg);
+        return AKZ_ERR_INVALID_ARG;
+    };
+    if (!pairs || !n_out) return refuse("null pairs or n_out");
+    if (desc_bytes == 0 || desc_bytes > 64) return refuse("desc_bytes must be 1..64");
+    if (n_sets && !sets) return refuse("null sets");
+    std::vector<uint8_t> seen((size_t)n_sets, 0);  // 1: checked, 2 .. : checked and placed (see below)
+    uint64_t cap = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const uint64_t k = pairs[2 * p + side];
+            if (k >= n_sets)
+                return refuse("pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(n_sets));
+            if (side == 0) cap += sets[k].n_descriptors;
+            if (seen[(size_t)k]) continue;
+            const akz_feature_set& f = sets[k];
+            const std::string at = "pair " + std::to_string(p) + ", set " + std::to_string(k) + ": ";
+            if (f.n_descriptors > f.n_keypoints) return refuse(at + "more descriptors than keypoints");
+            if ((f.n_keypoints && !f.keypoints) || (f.n_descriptors && !f.descriptors)) return refuse(at + "null keypoints or descriptors");
+            seen[(size_t)k] = 1;
+        }
+    if (cap && !out) return refuse("null out");
+    if (!c) return refuse("null context");
+    AKZ_TRY(bind(c, true, false));
+    const bool timed = c->mp_split_on;
+    if (timed)
+        for (hipEvent_t& e : c->mp_split_ev)
+            if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
+    hipStream_t st = c->stream;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    // every distinct set once, in order of first use: rows (and x / y of its first n_descriptors keypoints, the only ones a
+    // match can name) from row set_row[k]
+    std::vector<uint64_t> set_row((size_t)n_sets, 0), used;
+    uint64_t rows = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const uint64_t k = pairs[2 * p + side];
+            if (seen[(size_t)k] == 2) continue;
+            seen[(size_t)k] = 2;
+            used.push_back(k);
+            set_row[(size_t)k] = rows;
+            rows += sets[k].n_descriptors;
+        }
+    const uint64_t rows1 = std::max<uint64_t>(rows, 1), cap1 = std::max<uint64_t>(cap, 1);
+    const size_t b_rows = up((size_t)rows1 * 64), b_xy = up((size_t)rows1 * 4);
+    const size_t b_raw = up((size_t)cap1 * sizeof(akz_match)), b_cnt = up((size_t)n_pairs * 8), b_pts = (size_t)cap1 * 16;
+    const size_t b_tab = up((size_t)n_pairs * sizeof(launch::PairJobHost));
+    constexpr uint32_t kChunk = 16384;  // trials per launch of k_ransac_trials_multi (and per pinned sample slot)
+    const size_t b_smp = (size_t)kChunk * 9 * sizeof(uint32_t);
+    AKZ_TRY(ensure(c, c->mp_in, b_rows + 2 * b_xy));
+    AKZ_TRY(ensure(c, c->mp_raw, b_raw + b_cnt + b_pts));
+    AKZ_TRY(ensure(c, c->mp_tab, b_tab + 2 * b_smp));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, b_rows + 2 * b_xy));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_tab, b_tab + b_cnt));
+    uint8_t* d_rows = (uint8_t*)c->mp_in.p;
+    float *d_kx = (float*)(d_rows + b_rows), *d_ky = (float*)(d_rows + b_rows + b_xy);
+    akz_match* d_raw = (akz_match*)c->mp_raw.p;
+    uint64_t* d_cnt = (uint64_t*)((char*)c->mp_raw.p + b_raw);
+    float* d_pts = (float*)((char*)c->mp_raw.p + b_raw + b_cnt);
+    launch::PairJobHost* d_tab = (launch::PairJobHost*)c->mp_tab.p;
+    uint32_t* d_smp[2] = {(uint32_t*)((char*)c->mp_tab.p + b_tab), (uint32_t*)((char*)c->mp_tab.p + b_tab + b_smp)};
+    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
+    {
+        uint8_t* h = (uint8_t*)c->mp_pin_in.p;
+        float *hx = (float*)(h + b_rows), *hy = (float*)(h + b_rows + b_xy);
+        for (uint64_t k : used) {
+            const akz_feature_set& f = sets[k];
+            uint8_t* r = h + set_row[(size_t)k] * 64;
+            for (uint64_t i = 0; i < f.n_descriptors; ++i) {
+                std::memcpy(r + i * 64, f.descriptors + i * desc_bytes, (size_t)desc_bytes);
+                if (desc_bytes < 64) std::memset(r + i * 64 + desc_bytes, 0, (size_t)(64 - desc_bytes));
+                hx[set_row[(size_t)k] + i] = f.keypoints[i].x;
+                hy[set_row[(size_t)k] + i] = f.keypoints[i].y;
+            }
+        }
+        AKZ_HIP_TRY(hipMemcpyAsync(d_rows, h, (size_t)rows * 64, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipMemcpyAsync(d_kx, hx, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipMemcpyAsync(d_ky, hy, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+    }
+    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
+    // the scans: pair p's raw list at raw_off, its count at d_cnt[cnt_idx]
+    std::vector<launch::PairJobHost> tab((size_t)n_pairs);
+    AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_pairs * 8, st));
+    uint64_t raw_base = 0;
+    if (desc_bytes > 61) {  // every byte of a row counts: the pair matcher of akz_descriptor_match
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1], na = sets[a].n_descriptors;
+            tab[(size_t)p] = launch::PairJobHost{raw_base, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0, (uint32_t)p, 0};
+            if (na)
+                AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)a] * 64, na, d_rows + set_row[(size_t)b] * 64, sets[b].n_descriptors,
+                                          10000, lowes_ratio, d_raw + raw_base, d_cnt + p, false));
+            raw_base += na;
+        }
+    } else {  // one multi-set launch per first set over its second sets (split at the matcher's limits)
+        std::vector<std::vector<uint64_t>> groups;
+        std::vector<int64_t> group_of((size_t)n_sets, -1);
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            const uint64_t a = pairs[2 * p];
+            if (group_of[(size_t)a] < 0) {
+                group_of[(size_t)a] = (int64_t)groups.size();
+                groups.emplace_back();
+            }
+            groups[(size_t)group_of[(size_t)a]].push_back(p);
+        }
+        uint32_t cnt_base = 0;
+        std::vector<uint64_t> first, nrows;
+        for (const auto& g : groups) {
+            const uint64_t a = pairs[2 * g[0]], n0 = sets[a].n_descriptors;
+            const uint64_t max_sets = std::max<uint64_t>(1, std::min<uint64_t>(65535, n0 ? 0x7fffffffull / launch::match_mfma_rows((uint32_t)n0, true) : 65535));
+            for (size_t i = 0; i < g.size();) {
+                first.clear();
+                nrows.clear();
+                uint64_t train = 0;
+                const size_t i0 = i;
+                while (i < g.size() && first.size() < max_sets) {
+                    const uint64_t b = pairs[2 * g[i] + 1], nb = sets[b].n_descriptors;
+                    if (!first.empty() && train + nb > 0x7fffffffull) break;
+                    first.push_back(set_row[(size_t)b]);
+                    nrows.push_back(nb);
+                    train += nb;
+                    const uint64_t p = g[i];
+                    tab[(size_t)p] = launch::PairJobHost{raw_base + (i - i0) * n0, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0,
+                                                                   cnt_base + (uint32_t)(i - i0), 0};
+                    ++i;
+                }
+                if (n0)
+                    AKZ_TRY(match_sets_at(c, d_rows + set_row[(size_t)a] * 64, n0, d_rows, first.data(), nrows.data(), first.size(), 10000,
+                                          lowes_ratio, d_raw + raw_base, d_cnt + cnt_base, nullptr, nullptr));
+                raw_base += first.size() * n0;
+                cnt_base += (uint32_t)first.size();
+            }
+        }
+    }
+    launch::PairJobHost* h_tab = (launch::PairJobHost*)c->mp_pin_tab.p;
+    uint64_t* h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
+    std::memcpy(h_tab, tab.data(), (size_t)n_pairs * sizeof(launch::PairJobHost));
+    AKZ_HIP_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)n_pairs * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, st));
+    launch::pair_points(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_kx, d_ky, d_pts, cap1);
+    AKZ_HIP_TRY(hipGetLastError());
+    AKZ_HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[2], st));
+    AKZ_HIP_TRY(hipStreamSynchronize(st));
+    // the trials of every pair with 8 matches or more, in pair order; the kept lists side by side
+    uint64_t n_trials = 0, n_keep = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        launch::PairJobHost& j = tab[(size_t)p];
+        const uint64_t n = h_cnt[j.cnt_idx];
+        j.trial_off = n_trials;
+        j.n_trials = 0;
+        j.keep_off = n_keep;
+        n_keep += n;
+        if (n >= 8) n_trials += ransac_trials;
+    }
+    const size_t b_mdl = up((size_t)std::max<uint64_t>(n_trials, 1) * 36), b_inl = up((size_t)std::max<uint64_t>(n_trials, 1) * 4);
+    const size_t b_keep = b_cnt + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
+    AKZ_TRY(ensure(c, c->mp_trials, b_mdl + b_inl));
+    AKZ_TRY(ensure(c, c->mp_keep, b_keep));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_out, b_keep));
+    for (int k = 0; k < 2; ++k) {
+        AKZ_TRY(ensure_pinned(c, c->mp_pin_smp[k], b_smp));
+        if (!c->mp_smp_ev[k]) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->mp_smp_ev[k], hipEventDisableTiming));
+    }
+    float* d_mdl = (float*)c->mp_trials.p;
+    int32_t* d_inl = (int32_t*)((char*)c->mp_trials.p + b_mdl);
+    uint64_t* d_kcnt = (uint64_t*)c->mp_keep.p;
+    akz_match* d_keep = (akz_match*)((char*)c->mp_keep.p + b_cnt);
+    for (uint64_t p = 0; p < n_pairs; ++p)  // (n_trials of the table: the pair's trials, for the pick)
+        if (h_cnt[tab[(size_t)p].cnt_idx] >= 8) tab[(size_t)p].n_trials = ransac_trials;
+    std::memcpy(h_tab, tab.data(), (size_t)n_pairs * sizeof(launch::PairJobHost));
+    AKZ_HIP_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)n_pairs * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, st));
+    // draws on this thread, in pair order; a full slot goes to the device and its trials start while the next one fills
+    double t_draw = 0.0;
+    DefaultSource& src = default_source();
+    int slot = 0;
+    uint32_t fill = 0;
+    uint64_t chunk_first = 0;
+    bool launched = false;
+    uint32_t* hs = nullptr;
+    auto flush = [&]() -> int {
+        if (fill == 0) return AKZ_OK;
+        // (the slot's samples of fill trials sit at the front, then their pairs: close the gap)
+        std::memmove(hs + (size_t)fill * 8, hs + (size_t)kChunk * 8, (size_t)fill * 4);
+        AKZ_HIP_TRY(hipMemcpyAsync(d_smp[slot], hs, (size_t)fill * 36, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipEventRecord(c->mp_smp_ev[slot], st));
+        if (timed && !launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
+        launched = true;
+        launch::ransac_trials_multi(st, d_tab, d_smp[slot], chunk_first, fill, d_cnt, d_pts, cap1, 0.05f, ransac_epsilon_inliers, d_mdl,
+                                    d_inl);
+        AKZ_HIP_TRY(hipGetLastError());
+        chunk_first += fill;
+        fill = 0;
+        slot ^= 1;
+        hs = nullptr;
+        return AKZ_OK;
+    };
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint64_t n = h_cnt[tab[(size_t)p].cnt_idx];
+        if (n < 8) continue;
+        for (uint64_t left = ransac_trials; left;) {
+            if (!hs) {  // the slot's previous copy must be done before it is written again
+                AKZ_HIP_TRY(hipEventSynchronize(c->mp_smp_ev[slot]));
+                hs = (uint32_t*)c->mp_pin_smp[slot].p;
+            }
+            const uint32_t take = (uint32_t)std::min<uint64_t>(left, kChunk - fill);
+            const double t0 = now_ms();
+            draw_samples(src, n, take, hs + (size_t)fill * 8);
+            t_draw += now_ms() - t0;
+            for (uint32_t t = 0; t < take; ++t) hs[(size_t)kChunk * 8 + fill + t] = (uint32_t)p;
+            fill += take;
+            left -= take;
+            if (fill == kChunk) AKZ_TRY(flush());
+        }
+    }
+    AKZ_TRY(flush());
+    if (timed) {
+        if (!launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
+        AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[4], st));
+    }
+    launch::ransac_pick_filter(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep, d_kcnt);
+    AKZ_HIP_TRY(hipGetLastError());
+    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
+    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_cnt + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
+    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
+    AKZ_HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t* h_kcnt = (const uint64_t*)c->mp_pin_out.p;
+    const akz_match* h_keep = (const akz_match*)((const char*)c->mp_pin_out.p + b_cnt);
+    uint64_t at = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint64_t k = h_kcnt[p];
+        if (k) std::memcpy(out + at, h_keep + tab[(size_t)p].keep_off, (size_t)k * sizeof(akz_match));
+        n_out[p] = k;
+        at += sets[pairs[2 * p]].n_descriptors;
+    }
+    if (timed) {
+        float ms[6] = {};
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[0], c->mp_split_ev[0], c->mp_split_ev[1]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[1], c->mp_split_ev[1], c->mp_split_ev[2]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[3], c->mp_split_ev[3], c->mp_split_ev[4]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[4], c->mp_split_ev[4], c->mp_split_ev[5]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[5], c->mp_split_ev[5], c->mp_split_ev[6]));
+        for (int k = 0; k < 6; ++k) c->mp_split_ms[k] = ms[k];
+        c->mp_split_ms[2] = t_draw;
+    }
+    return AKZ_OK;
+}
+
+int akz_debug_match_pairs_split(akz_ctx* c, int enable, double* ms) {
+    if (!c) {
+        set_error("null context");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    c->mp_split_on = enable != 0;
+    if (ms)
+        for (int k = 0; k < 6; ++k) ms[k] = c->mp_split_ms[k];
+    return AKZ_OK;
+}
+
 }  // extern "C"

@@ -65,9 +65,58 @@ float model_error(const Model& md, const akz_keypoint& k0, const akz_keypoint& k
 }
 
 }  // namespace
+
+// The samples of `trials` RANSAC trials over n_matches >= 1 matches, 8 ascending indices per trial, from `src` in trial
+// order: per trial `set.insert(source.read::<usize>() % matches.len())` until the set holds 8 distinct indices (:117-121),
+// sorted (the reference iterates its HashSet: arbitrary order).  The remainder is the exact `%`: q = mulhi(v, m) with
+// m = floor((2^64 - 1) / n) undershoots v / n by at most 2 (q <= v / n < q + 3), so r = v - q n < 3 n needs at most two
+// corrections -- one multiplication in place of a 64-bit division per draw.  Both match_features paths draw here.
+template <class T>
+void draw_samples(DefaultSource& src, uint64_t n_matches, uint64_t trials, T* out) {
+    const uint64_t m = ~0ull / n_matches;
+    for (uint64_t trial = 0; trial < trials; ++trial) {
+        uint64_t picked[8];
+        int k = 0;
+        while (k < 8) {
+            const uint64_t v = src.next();
+            uint64_t r = v - (uint64_t)(((unsigned __int128)v * m) >> 64) * n_matches;
+            if (r >= n_matches) r -= n_matches;
+            if (r >= n_matches) r -= n_matches;
+            int at = k;  // insertion into the ascending list, unless already drawn
+            bool dup = false;
+            while (at > 0 && picked[at - 1] >= r) {
+                if (picked[at - 1] == r) {
+                    dup = true;
+                    break;
+                }
+                --at;
+            }
+            if (dup) continue;
+            for (int j = k; j > at; --j) picked[j] = picked[j - 1];
+            picked[at] = r;
+            ++k;
+        }
+        for (int i = 0; i < 8; ++i) out[trial * 8 + i] = (T)picked[i];
+    }
+}
+template void draw_samples<uint64_t>(DefaultSource&, uint64_t, uint64_t, uint64_t*);
+template void draw_samples<uint32_t>(DefaultSource&, uint64_t, uint64_t, uint32_t*);
 }  // namespace akz
 
 using namespace akz;
+
+// draw_samples from a source of its own seeded [s0, s1] (tests hold it to the plain `%` loop)
+extern "C" int akz_debug_ransac_samples(uint64_t s0, uint64_t s1, uint64_t n_matches, uint64_t trials, uint64_t* out) {
+    if (n_matches == 0 || (trials && !out)) {
+        set_error("debug_ransac_samples: bad arguments");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    DefaultSource src;
+    src.s0 = s0;
+    src.s1 = s1;
+    draw_samples(src, n_matches, trials, out);
+    return AKZ_OK;
+}
 
 // trials_on_device (match_features with a context): runs the trials elsewhere -- px0 .. py1 (n_matches floats each), the
 // samples (8 per trial), -> models (9 floats per trial), inliers (-1: no model); AKZ_OK or an error (the host path then
@@ -93,20 +142,8 @@ int akz::remove_outliers_impl(const akz_keypoint* keypoints_0, uint64_t n0, cons
     // order (as the sequential loop of :111-147 draws them), the models and inlier counts are computed on a few host
     // threads, and the winner is picked in trial order with the reference's strict `>` -- the same model as the
     // sequential loop returns (12 ms -> 1.5 ms for the 8 000 matches of a 4K pair at 1 000 trials).
-    DefaultSource& src = default_source();
     std::vector<uint64_t> samples((size_t)num_trials * 8);
-    {
-        std::vector<uint64_t> picked;
-        for (uint64_t trial = 0; trial < num_trials; ++trial) {
-            picked.clear();  // `set.insert(source.read::<usize>() % matches.len())` until 8 distinct indices (:117-121)
-            while (picked.size() < 8) {
-                const uint64_t j = src.next() % n_matches;
-                if (std::find(picked.begin(), picked.end(), j) == picked.end()) picked.push_back(j);
-            }
-            std::sort(picked.begin(), picked.end());  // the reference iterates the HashSet: arbitrary order
-            std::copy(picked.begin(), picked.end(), samples.begin() + (size_t)trial * 8);
-        }
-    }
+    draw_samples(default_source(), n_matches, num_trials, samples.data());
     std::vector<Model> models((size_t)num_trials);
     std::vector<int64_t> inliers((size_t)num_trials, -1);  // -1: no model (rank-deficient sample)
     // the matched point pairs side by side (x0, y0, x1, y1 as four arrays): the inlier count of a trial -- model_error over

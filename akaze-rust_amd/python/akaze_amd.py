@@ -107,6 +107,12 @@ KEYPOINT_DTYPE = np.dtype(
      ("octave", "<u8"), ("class_id", "<u8"), ("angle", "<f4"), ("_pad", "<u4")])
 MATCH_DTYPE = np.dtype([("index_0", "<u8"), ("index_1", "<u8"), ("distance", "<f8")])
 
+
+class FeatureSet(C.Structure):
+    """akz_feature_set: host keypoints and descriptors of one set (akz_match_features_pairs)."""
+    _fields_ = [("keypoints", C.c_void_p), ("n_keypoints", C.c_uint64), ("descriptors", C.c_void_p),
+                ("n_descriptors", C.c_uint64)]
+
 _lib = None
 
 
@@ -209,6 +215,9 @@ def lib():
         "akz_remove_outliers": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64], i32),
         "akz_estimate_fundamental_matrix": ([vp, u64, vp, u64, vp, C.c_float, fp, C.POINTER(i32)], i32),
         "akz_match_features": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64], i32),
+        "akz_match_features_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64], i32),
+        "akz_debug_ransac_samples": ([u64, u64, u64, u64, pu64], i32),
+        "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
         "akz_write_matches": ([C.c_char_p, vp, u64], i32),
@@ -660,6 +669,37 @@ class Context:
                                           n1, nb, distance_threshold, lowes_ratio, out.ctypes.data_as(C.c_void_p),
                                           C.byref(n)))
         return out[:n.value].copy()
+
+    def match_features_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
+        """match_features (lib.rs:252-275) over many pairs in one call (akz_match_features_pairs): features is a list of
+        (keypoints, descriptors) arrays (KEYPOINT_DTYPE / uint8 [n, desc_bytes]), pairs a sequence of (first, second) indices
+        into it.  Returns one MATCH_DTYPE array per pair, each equal to what match_features returns for that pair when the
+        pairs are matched in order on this thread."""
+        ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
+        ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
+        nbs = {d.shape[1] for d in ds if d.ndim == 2 and len(d)}
+        if len(nbs) > 1:
+            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
+        nb = nbs.pop() if nbs else 61
+        sets = (FeatureSet * max(1, len(ks)))()
+        for i, (k, d) in enumerate(zip(ks, ds)):
+            nd = len(d) if d.ndim == 2 else 0
+            sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k),
+                                 d.ctypes.data_as(C.c_void_p) if nd else None, nd)
+        pr = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+        rows = [len(ds[int(a)]) if ds[int(a)].ndim == 2 else 0 for a in pr[:, 0]] if len(ks) else []
+        if len(ks) == 0 and len(pr):
+            raise IndexError("pair refers to a set that does not exist")
+        out = np.zeros(max(1, sum(rows)), MATCH_DTYPE)
+        n = np.zeros(max(1, len(pr)), np.uint64)
+        _check(lib().akz_match_features_pairs(self._h, C.cast(sets, C.c_void_p), len(ks), pr.ctypes.data_as(C.c_void_p), len(pr), nb, lowes_ratio,
+                                              ransac_trials, ransac_epsilon_inliers, out.ctypes.data_as(C.c_void_p),
+                                              n.ctypes.data_as(C.POINTER(C.c_uint64))))
+        res, at = [], 0
+        for p, r in enumerate(rows):
+            res.append(out[at:at + int(n[p])].copy())
+            at += r
+        return res
 
     def descriptor_match_sets_device(self, q, train, rows, distance_threshold=10000, lowes_ratio=0.86):
         """One query set against several train sets in one launch: q [n0, 64] uint8 CUDA tensor, train the sets'
@@ -1167,6 +1207,11 @@ def match_features(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes
                                     nb0 or nb1 or 61, lowes_ratio, ransac_trials,
                                     ransac_epsilon_inliers, out.ctypes.data_as(C.c_void_p), C.byref(n)))
     return out[:n.value].copy()
+
+
+def match_features_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
+    """Context.match_features_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers)
 
 
 # ------------------------------------------------------------------------------------------

@@ -492,6 +492,34 @@ int akz_match_features(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n
                        uint64_t n_descriptors_0, const akz_keypoint* keypoints_1, uint64_t n_keypoints_1,
                        const uint8_t* descriptors_1, uint64_t n_descriptors_1, uint64_t desc_bytes, double lowes_ratio,
                        uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out);
+/* A feature set of akz_match_features_pairs: host keypoints and host descriptors (n_descriptors x desc_bytes, unpadded). */
+typedef struct akz_feature_set {
+    const akz_keypoint* keypoints;
+    uint64_t n_keypoints;
+    const uint8_t* descriptors;
+    uint64_t n_descriptors;
+} akz_feature_set;
+/* akz_match_features over many pairs in one call (a loop of akaze/src/lib.rs:252-275).  pairs: 2 x n_pairs set indices,
+   (first, second) per pair; pairs may repeat, be reversed or be (a, a).
+   * Same result as the loop: pair p's list is what akz_match_features(sets[a], sets[b], desc_bytes, lowes_ratio,
+     ransac_trials, ransac_epsilon_inliers) returns when it is called for p = 0, 1, ... in order on the calling thread, from
+     the same state of that thread's random source, bit for bit; afterwards the source is in the state that loop leaves it in.
+   * Output: pair p's list starts at out + sum_{q<p} sets[pairs[2q]].n_descriptors, its length goes to n_out[p]; out must
+     hold sum_p sets[pairs[2p]].n_descriptors entries (fixed room per pair: a call never needs a retry).
+   * Refusals (AKZ_ERR_INVALID_ARG, the message names the pair or set) all come before the first random draw and before any
+     GPU work, and then nothing is written and the random source is untouched: every refusal akz_match_features makes for
+     a pair (a set with more descriptors than keypoints, desc_bytes outside 1..64, null pointers), a set index >= n_sets,
+     a null ctx while n_pairs > 0.  n_pairs = 0 is AKZ_OK.
+   * No new limits: every argument akz_match_features accepts; pairs with fewer than 8 matches are returned unchanged and draw
+     nothing; ransac_trials = 0 gives the zero model (every match kept if epsilon > 0).  desc_bytes 62..64 compare every byte
+     of a row, as akz_descriptor_match does.
+   * Work runs on the context's stream with the context's scratch; the call returns synchronously.  What may run on the
+     context at the same time is the same as for akz_match_features.
+   Each distinct set is uploaded once; the descriptor scans, the keypoint gather, the trials of all pairs, the choice of
+   each winner and the final filter run on the GPU; the samples are drawn on the calling thread in pair order. */
+int akz_match_features_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                             uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                             float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out /* n_pairs */);
 
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.

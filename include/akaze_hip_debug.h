@@ -126,6 +126,14 @@ int akz_debug_set_select(akz_ctx* ctx, int mode);
    info[4 .. 7] = 10 ns ticks of k_select's phases on image 0 (first states, turns, second pass, output).  info: 8 ints. */
 int akz_debug_select_info(akz_ctx* ctx, int* info);
 
+/* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
+   source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */
+int akz_debug_ransac_samples(uint64_t s0, uint64_t s1, uint64_t n_matches, uint64_t trials, uint64_t* out);
+/* Where akz_match_features_pairs spends its time: enable != 0 times the context's later calls (events on its stream);
+   ms (optional, 6 doubles) receives the last timed call's uploads, scans, host draws, trials, pick + filter and read-back
+   in ms (the trials: first trial launch to last trial's end, overlapping the draws). */
+int akz_debug_match_pairs_split(akz_ctx* ctx, int enable, double* ms);
+
 /* ---- kernel-family selectors and the synthetic frame generator (tests, bench, tools): every mode gives bit-identical
    results; a drop-in host never calls these ---------------------------------------------------------------------- */
 /* Deterministic synthetic 8-bit luma frame (integer-only, SplitMix64-seeded):
