@@ -49,9 +49,9 @@ struct DefaultSource {
     }
 };
 DefaultSource& default_source();
-// the samples of `trials` RANSAC trials over n_matches matches: 8 ascending indices per trial into out (akz_ransac.cpp;
-// T = uint64_t or uint32_t)
-template <class T>
+// the samples of `trials` RANSAC trials over n_matches >= K matches: K ascending indices per trial into out (akz_ransac.cpp;
+// K = 8 or 4, T = uint64_t or uint32_t)
+template <int K, class T>
 void draw_samples(DefaultSource& src, uint64_t n_matches, uint64_t trials, T* out);
 
 #define AKZ_TRY(expr)            \
@@ -375,6 +375,16 @@ void ransac_trials_multi(hipStream_t s, const PairJobHost* d_pairs, const uint32
 void ransac_pick_filter(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                         const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float epsilon_inlier,
                         void* d_keep, uint64_t* d_keep_cnt);
+// akz_match_features_homography(_pairs) (akz_homography.hip): the same pair records; d_trials holds this chunk's 4 sample
+// indices per trial, then the pair of every trial
+void homography_trials(hipStream_t s, const PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
+                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier,
+                       float* d_models, int32_t* d_inliers);
+// per pair: the winner (strict `>` from 0 in trial order), its H at d_h + 9 pair and found at d_found[pair] (none: zeros, found
+// 0, every match kept), the kept matches compacted in order at d_keep + keep_off, their count at d_keep_cnt[pair]
+void homography_pick_filter(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                            const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float epsilon_inlier,
+                            void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found);
 void unpack_pair(hipStream_t s, const uint8_t* dq, uint32_t nq, uint32_t q_pad, uint8_t* outq, uint32_t* popq, uint32_t* bound, uint32_t threshold,
                  const uint8_t* dt, uint32_t nt, uint32_t t_pad, uint8_t* outt, uint32_t* popt, bool fp4);
 uint32_t match_mfma_tile_rows();

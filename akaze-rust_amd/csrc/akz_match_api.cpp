@@ -384,17 +384,61 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
                                 on_device);
 }
 
+}  // extern "C"
+
+// The geometric model of the pairs orchestration below: K match indices per sample, the trial and pick / filter kernels, and
+// whether the call hands back a model per pair (H, found).
+namespace {
+struct FundamentalModel {  // akz_match_features_pairs: k_ransac_trials_multi, k_ransac_pick_filter (akz_fmatrix.hip)
+    static constexpr int K = 8;
+    static constexpr bool kModelOut = false;
+    static constexpr float kEpsilonModel = 0.05f;
+    static constexpr const char* kName = "match_features_pairs: ";
+    static void trials(hipStream_t s, const launch::PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
+                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float eps_model, float eps_inlier, float* d_models,
+                       int32_t* d_inliers) {
+        launch::ransac_trials_multi(s, d_pairs, d_trials, first_trial, n_trials, d_raw_cnt, d_pts, pts_stride, eps_model, eps_inlier, d_models,
+                                    d_inliers);
+    }
+    static void pick_filter(hipStream_t s, const launch::PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                            const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float eps_inlier,
+                            void* d_keep, uint64_t* d_keep_cnt, float*, int32_t*) {
+        launch::ransac_pick_filter(s, d_pairs, n_pairs, d_raw, d_raw_cnt, d_pts, pts_stride, d_models, d_inliers, eps_inlier, d_keep,
+                                   d_keep_cnt);
+    }
+};
+struct HomographyModel {  // akz_match_features_homography(_pairs): k_homography_trials, k_homography_pick_filter
+    static constexpr int K = 4;
+    static constexpr bool kModelOut = true;
+    static constexpr float kEpsilonModel = AKZ_HOMOGRAPHY_EPSILON_MODEL;
+    static constexpr const char* kName = "match_features_homography_pairs: ";
+    static void trials(hipStream_t s, const launch::PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
+                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float eps_model, float eps_inlier, float* d_models,
+                       int32_t* d_inliers) {
+        launch::homography_trials(s, d_pairs, d_trials, first_trial, n_trials, d_raw_cnt, d_pts, pts_stride, eps_model, eps_inlier, d_models,
+                                  d_inliers);
+    }
+    static void pick_filter(hipStream_t s, const launch::PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                            const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float eps_inlier,
+                            void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found) {
+        launch::homography_pick_filter(s, d_pairs, n_pairs, d_raw, d_raw_cnt, d_pts, pts_stride, d_models, d_inliers, eps_inlier, d_keep,
+                                       d_keep_cnt, d_h, d_found);
+    }
+};
+
 // match_features over many pairs (see the header).  Stages, all on the context's stream: every distinct set's 64-byte rows and
 // keypoint x / y through pinned staging; the descriptor scans (one multi-set launch per first set, or the pair matcher for
 // rows of 62..64 bytes); k_pair_points; ONE read-back of the match counts; the samples drawn on the calling thread in pair
-// order, in chunks whose trials (k_ransac_trials_multi) run while the next chunk is drawn; k_ransac_pick_filter; ONE read-back
-// of the kept lists.
-int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                             uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
-                             akz_match* out, uint64_t* n_out) {
+// order, in chunks whose trials (Model::trials) run while the next chunk is drawn; Model::pick_filter; ONE read-back of the
+// kept lists (and, for a model that is handed back, every pair's model and found flag).
+template <class Model>
+int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
+                     double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out, float* model_out,
+                     int* found_out) {
+    constexpr int K = Model::K;
     if (n_pairs == 0) return AKZ_OK;
     auto refuse = [](const std::string& msg) {
-        set_error("match_features_pairs: " + msg);
+        set_error(Model::kName + msg);
         return AKZ_ERR_INVALID_ARG;
     };
     if (!pairs || !n_out) return refuse("null pairs or n_out");
@@ -545,10 +589,13 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
         j.n_trials = 0;
         j.keep_off = n_keep;
         n_keep += n;
-        if (n >= 8) n_trials += ransac_trials;
+        if (n >= (uint64_t)K) n_trials += ransac_trials;
     }
     const size_t b_mdl = up((size_t)std::max<uint64_t>(n_trials, 1) * 36), b_inl = up((size_t)std::max<uint64_t>(n_trials, 1) * 4);
-    const size_t b_keep = b_cnt + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
+    // (a model handed back: every pair's 9 floats and found flag between the counts and the kept lists)
+    const size_t b_hm = Model::kModelOut ? up((size_t)n_pairs * 36) : 0, b_hf = Model::kModelOut ? up((size_t)n_pairs * 4) : 0;
+    const size_t b_head = b_cnt + b_hm + b_hf;
+    const size_t b_keep = b_head + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
     AKZ_TRY(ensure(c, c->mp_trials, b_mdl + b_inl));
     AKZ_TRY(ensure(c, c->mp_keep, b_keep));
     AKZ_TRY(ensure_pinned(c, c->mp_pin_out, b_keep));
@@ -559,9 +606,11 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
     float* d_mdl = (float*)c->mp_trials.p;
     int32_t* d_inl = (int32_t*)((char*)c->mp_trials.p + b_mdl);
     uint64_t* d_kcnt = (uint64_t*)c->mp_keep.p;
-    akz_match* d_keep = (akz_match*)((char*)c->mp_keep.p + b_cnt);
+    float* d_hm = (float*)((char*)c->mp_keep.p + b_cnt);
+    int32_t* d_hf = (int32_t*)((char*)c->mp_keep.p + b_cnt + b_hm);
+    akz_match* d_keep = (akz_match*)((char*)c->mp_keep.p + b_head);
     for (uint64_t p = 0; p < n_pairs; ++p)  // (n_trials of the table: the pair's trials, for the pick)
-        if (h_cnt[tab[(size_t)p].cnt_idx] >= 8) tab[(size_t)p].n_trials = ransac_trials;
+        if (h_cnt[tab[(size_t)p].cnt_idx] >= (uint64_t)K) tab[(size_t)p].n_trials = ransac_trials;
     std::memcpy(h_tab, tab.data(), (size_t)n_pairs * sizeof(launch::PairJobHost));
     AKZ_HIP_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)n_pairs * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, st));
     // draws on this thread, in pair order; a full slot goes to the device and its trials start while the next one fills
@@ -575,13 +624,13 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
     auto flush = [&]() -> int {
         if (fill == 0) return AKZ_OK;
         // (the slot's samples of fill trials sit at the front, then their pairs: close the gap)
-        std::memmove(hs + (size_t)fill * 8, hs + (size_t)kChunk * 8, (size_t)fill * 4);
-        AKZ_HIP_TRY(hipMemcpyAsync(d_smp[slot], hs, (size_t)fill * 36, hipMemcpyHostToDevice, st));
+        std::memmove(hs + (size_t)fill * K, hs + (size_t)kChunk * K, (size_t)fill * 4);
+        AKZ_HIP_TRY(hipMemcpyAsync(d_smp[slot], hs, (size_t)fill * (K + 1) * 4, hipMemcpyHostToDevice, st));
         AKZ_HIP_TRY(hipEventRecord(c->mp_smp_ev[slot], st));
         if (timed && !launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         launched = true;
-        launch::ransac_trials_multi(st, d_tab, d_smp[slot], chunk_first, fill, d_cnt, d_pts, cap1, 0.05f, ransac_epsilon_inliers, d_mdl,
-                                    d_inl);
+        Model::trials(st, d_tab, d_smp[slot], chunk_first, fill, d_cnt, d_pts, cap1, Model::kEpsilonModel, ransac_epsilon_inliers, d_mdl,
+                      d_inl);
         AKZ_HIP_TRY(hipGetLastError());
         chunk_first += fill;
         fill = 0;
@@ -591,7 +640,7 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
     };
     for (uint64_t p = 0; p < n_pairs; ++p) {
         const uint64_t n = h_cnt[tab[(size_t)p].cnt_idx];
-        if (n < 8) continue;
+        if (n < (uint64_t)K) continue;
         for (uint64_t left = ransac_trials; left;) {
             if (!hs) {  // the slot's previous copy must be done before it is written again
                 AKZ_HIP_TRY(hipEventSynchronize(c->mp_smp_ev[slot]));
@@ -599,9 +648,9 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
             }
             const uint32_t take = (uint32_t)std::min<uint64_t>(left, kChunk - fill);
             const double t0 = now_ms();
-            draw_samples(src, n, take, hs + (size_t)fill * 8);
+            draw_samples<K>(src, n, take, hs + (size_t)fill * K);
             t_draw += now_ms() - t0;
-            for (uint32_t t = 0; t < take; ++t) hs[(size_t)kChunk * 8 + fill + t] = (uint32_t)p;
+            for (uint32_t t = 0; t < take; ++t) hs[(size_t)kChunk * K + fill + t] = (uint32_t)p;
             fill += take;
             left -= take;
             if (fill == kChunk) AKZ_TRY(flush());
@@ -612,20 +661,27 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
         if (!launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[4], st));
     }
-    launch::ransac_pick_filter(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep, d_kcnt);
+    Model::pick_filter(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep, d_kcnt, d_hm, d_hf);
     AKZ_HIP_TRY(hipGetLastError());
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
-    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_cnt + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_head + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
     AKZ_HIP_TRY(hipStreamSynchronize(st));
     const uint64_t* h_kcnt = (const uint64_t*)c->mp_pin_out.p;
-    const akz_match* h_keep = (const akz_match*)((const char*)c->mp_pin_out.p + b_cnt);
+    const akz_match* h_keep = (const akz_match*)((const char*)c->mp_pin_out.p + b_head);
     uint64_t at = 0;
     for (uint64_t p = 0; p < n_pairs; ++p) {
         const uint64_t k = h_kcnt[p];
         if (k) std::memcpy(out + at, h_keep + tab[(size_t)p].keep_off, (size_t)k * sizeof(akz_match));
         n_out[p] = k;
         at += sets[pairs[2 * p]].n_descriptors;
+    }
+    if (Model::kModelOut) {
+        const float* h_hm = (const float*)((const char*)c->mp_pin_out.p + b_cnt);
+        const int32_t* h_hf = (const int32_t*)((const char*)c->mp_pin_out.p + b_cnt + b_hm);
+        if (model_out) std::memcpy(model_out, h_hm, (size_t)n_pairs * 36);
+        if (found_out)
+            for (uint64_t p = 0; p < n_pairs; ++p) found_out[p] = h_hf[p];
     }
     if (timed) {
         float ms[6] = {};
@@ -637,6 +693,44 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
         for (int k = 0; k < 6; ++k) c->mp_split_ms[k] = ms[k];
         c->mp_split_ms[2] = t_draw;
     }
+    return AKZ_OK;
+}
+}  // namespace
+
+extern "C" {
+int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                             uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                             akz_match* out, uint64_t* n_out) {
+    return match_pairs_impl<FundamentalModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                              out, n_out, nullptr, nullptr);
+}
+
+// the homography RANSAC over many pairs (see the header): the orchestration above with 4-point samples
+int akz_match_features_homography_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                                        uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                        akz_match* out, uint64_t* n_out, float* h, int* found) {
+    return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                             out, n_out, h, found);
+}
+
+// one pair: the pairs call with sets {0, 1} and the pair (0, 1); refusals are those of akz_match_features
+int akz_match_features_homography(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                  const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                  double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out,
+                                  uint64_t* n_out, float* h, int* found) {
+    if (!n_out) return AKZ_ERR_INVALID_ARG;
+    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
+        set_error("match_features_homography: a feature set has more descriptors than keypoints");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
+    const uint64_t pair[2] = {0, 1};
+    int fnd = 0;
+    float hm[9];
+    AKZ_TRY(match_pairs_impl<HomographyModel>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out,
+                                              hm, &fnd));
+    if (found) *found = fnd;
+    if (h && fnd) std::memcpy(h, hm, sizeof(hm));
     return AKZ_OK;
 }
 

@@ -27,11 +27,13 @@
 #include <thread>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <vector>
 
 #include "akz_fmatrix.hpp"
+#include "akz_homography.hpp"
 #include "akz_internal.hpp"
 #include "akz_pool.hpp"
 
@@ -64,20 +66,57 @@ float model_error(const Model& md, const akz_keypoint& k0, const akz_keypoint& k
     return fundamental_error(md.f, k0.x, k0.y, k1.x, k1.y);
 }
 
+// run_trials(lo, hi) over trials 0 .. num_trials on nthreads host threads (one pool for both RANSAC models)
+void run_trials_pooled(uint64_t num_trials, unsigned nthreads, const std::function<void(uint64_t, uint64_t)>& run_trials) {
+    if (nthreads <= 1) {
+        run_trials(0, num_trials);
+        return;
+    }
+    // the trials go to a pool of host threads that lives as long as the process (starting 16 threads per call was a
+    // third of a 1 000-trial call's 1.3 ms); a second caller at the same time starts its own threads, as before
+    // The pool is never destroyed (its threads end with the process) and belongs to the process that made it: after a
+    // fork() the child inherits the object but none of its threads, so a pid that differs drops it (leaked: joining
+    // threads that do not exist would hang) and starts a new one.  A child forked while another thread held pool_m
+    // never gets the lock and takes the per-call threads below.
+    static std::mutex pool_m;
+    static WorkerPool* pool = nullptr;
+    static pid_t pool_pid = 0;
+    std::unique_lock<std::mutex> lk(pool_m, std::try_to_lock);
+    if (lk.owns_lock()) {
+        const pid_t me = getpid();
+        if (pool && pool_pid != me) pool = nullptr;
+        if (!pool || pool->size() < nthreads) {
+            if (pool && pool_pid == me) delete pool;
+            pool = new WorkerPool(nthreads - 1);
+            pool_pid = me;
+        }
+        // handed out dynamically, four pieces per thread -- unless the pool is wider than this call wants (it was grown by
+        // a larger one): then exactly nthreads pieces, so that a small call does not wake sixteen threads
+        const uint64_t per = std::max<uint64_t>(1, num_trials / ((pool->size() > nthreads ? 1ull : 4ull) * nthreads));
+        const size_t pieces = (size_t)((num_trials + per - 1) / per);
+        pool->run(pieces, [&](size_t i) { run_trials((uint64_t)i * per, std::min<uint64_t>(num_trials, ((uint64_t)i + 1) * per)); });
+    } else {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nthreads; ++t)
+            th.emplace_back(run_trials, num_trials * t / nthreads, num_trials * (t + 1) / nthreads);
+        for (auto& t : th) t.join();
+    }
+}
+
 }  // namespace
 
-// The samples of `trials` RANSAC trials over n_matches >= 1 matches, 8 ascending indices per trial, from `src` in trial
-// order: per trial `set.insert(source.read::<usize>() % matches.len())` until the set holds 8 distinct indices (:117-121),
-// sorted (the reference iterates its HashSet: arbitrary order).  The remainder is the exact `%`: q = mulhi(v, m) with
+// The samples of `trials` RANSAC trials over n_matches >= K matches, K ascending indices per trial (8: the fundamental matrix,
+// 4: the homography), from `src` in trial order: per trial `set.insert(source.read::<usize>() % matches.len())` until the
+// set holds K distinct indices (:117-121), sorted (the reference iterates its HashSet: arbitrary order).  The remainder is the exact `%`: q = mulhi(v, m) with
 // m = floor((2^64 - 1) / n) undershoots v / n by at most 2 (q <= v / n < q + 3), so r = v - q n < 3 n needs at most two
 // corrections -- one multiplication in place of a 64-bit division per draw.  Both match_features paths draw here.
-template <class T>
+template <int K, class T>
 void draw_samples(DefaultSource& src, uint64_t n_matches, uint64_t trials, T* out) {
     const uint64_t m = ~0ull / n_matches;
     for (uint64_t trial = 0; trial < trials; ++trial) {
-        uint64_t picked[8];
+        uint64_t picked[K];
         int k = 0;
-        while (k < 8) {
+        while (k < K) {
             const uint64_t v = src.next();
             uint64_t r = v - (uint64_t)(((unsigned __int128)v * m) >> 64) * n_matches;
             if (r >= n_matches) r -= n_matches;
@@ -96,11 +135,13 @@ void draw_samples(DefaultSource& src, uint64_t n_matches, uint64_t trials, T* ou
             picked[at] = r;
             ++k;
         }
-        for (int i = 0; i < 8; ++i) out[trial * 8 + i] = (T)picked[i];
+        for (int i = 0; i < K; ++i) out[trial * K + i] = (T)picked[i];
     }
 }
-template void draw_samples<uint64_t>(DefaultSource&, uint64_t, uint64_t, uint64_t*);
-template void draw_samples<uint32_t>(DefaultSource&, uint64_t, uint64_t, uint32_t*);
+template void draw_samples<8, uint64_t>(DefaultSource&, uint64_t, uint64_t, uint64_t*);
+template void draw_samples<8, uint32_t>(DefaultSource&, uint64_t, uint64_t, uint32_t*);
+template void draw_samples<4, uint64_t>(DefaultSource&, uint64_t, uint64_t, uint64_t*);
+template void draw_samples<4, uint32_t>(DefaultSource&, uint64_t, uint64_t, uint32_t*);
 }  // namespace akz
 
 using namespace akz;
@@ -114,7 +155,21 @@ extern "C" int akz_debug_ransac_samples(uint64_t s0, uint64_t s1, uint64_t n_mat
     DefaultSource src;
     src.s0 = s0;
     src.s1 = s1;
-    draw_samples(src, n_matches, trials, out);
+    draw_samples<8>(src, n_matches, trials, out);
+    return AKZ_OK;
+}
+
+// the same for k = 8 or 4 indices per trial (the homography draws 4); n_matches < k is refused (the loop could not end)
+extern "C" int akz_debug_ransac_samples_k(uint64_t s0, uint64_t s1, uint64_t n_matches, uint64_t trials, int k, uint64_t* out) {
+    if ((k != 4 && k != 8) || n_matches < (uint64_t)k || (trials && !out)) {
+        set_error("debug_ransac_samples_k: bad arguments (k must be 4 or 8, n_matches >= k)");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    DefaultSource src;
+    src.s0 = s0;
+    src.s1 = s1;
+    if (k == 8) draw_samples<8>(src, n_matches, trials, out);
+    else draw_samples<4>(src, n_matches, trials, out);
     return AKZ_OK;
 }
 
@@ -143,7 +198,7 @@ int akz::remove_outliers_impl(const akz_keypoint* keypoints_0, uint64_t n0, cons
     // threads, and the winner is picked in trial order with the reference's strict `>` -- the same model as the
     // sequential loop returns (12 ms -> 1.5 ms for the 8 000 matches of a 4K pair at 1 000 trials).
     std::vector<uint64_t> samples((size_t)num_trials * 8);
-    draw_samples(default_source(), n_matches, num_trials, samples.data());
+    draw_samples<8>(default_source(), n_matches, num_trials, samples.data());
     std::vector<Model> models((size_t)num_trials);
     std::vector<int64_t> inliers((size_t)num_trials, -1);  // -1: no model (rank-deficient sample)
     // the matched point pairs side by side (x0, y0, x1, y1 as four arrays): the inlier count of a trial -- model_error over
@@ -187,41 +242,7 @@ int akz::remove_outliers_impl(const akz_keypoint* keypoints_0, uint64_t n0, cons
     // (a model costs ~5-9 us -- the 8 x 9 singular value decomposition -- and an inlier count ~0.3-1 ns per match)
     const unsigned nthreads = (unsigned)std::min<uint64_t>(std::min(host_cpu_share(), 16u),
                                                           std::max<uint64_t>(1, num_trials * (n_matches + 9000) / 2000000));  // ~0.1 ms of work per thread at least
-    if (on_device) {
-        // (done)
-    } else if (nthreads <= 1) {
-        run_trials(0, num_trials);
-    } else {
-        // the trials go to a pool of host threads that lives as long as the process (starting 16 threads per call was a
-        // third of a 1 000-trial call's 1.3 ms); a second caller at the same time starts its own threads, as before
-        // The pool is never destroyed (its threads end with the process) and belongs to the process that made it: after a
-        // fork() the child inherits the object but none of its threads, so a pid that differs drops it (leaked: joining
-        // threads that do not exist would hang) and starts a new one.  A child forked while another thread held pool_m
-        // never gets the lock and takes the per-call threads below.
-        static std::mutex pool_m;
-        static WorkerPool* pool = nullptr;
-        static pid_t pool_pid = 0;
-        std::unique_lock<std::mutex> lk(pool_m, std::try_to_lock);
-        if (lk.owns_lock()) {
-            const pid_t me = getpid();
-            if (pool && pool_pid != me) pool = nullptr;
-            if (!pool || pool->size() < nthreads) {
-                if (pool && pool_pid == me) delete pool;
-                pool = new WorkerPool(nthreads - 1);
-                pool_pid = me;
-            }
-            // handed out dynamically, four pieces per thread -- unless the pool is wider than this call wants (it was grown by
-            // a larger one): then exactly nthreads pieces, so that a small call does not wake sixteen threads
-            const uint64_t per = std::max<uint64_t>(1, num_trials / ((pool->size() > nthreads ? 1ull : 4ull) * nthreads));
-            const size_t pieces = (size_t)((num_trials + per - 1) / per);
-            pool->run(pieces, [&](size_t i) { run_trials((uint64_t)i * per, std::min<uint64_t>(num_trials, ((uint64_t)i + 1) * per)); });
-        } else {
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < nthreads; ++t)
-                th.emplace_back(run_trials, num_trials * t / nthreads, num_trials * (t + 1) / nthreads);
-            for (auto& t : th) t.join();
-        }
-    }
+    if (!on_device) run_trials_pooled(num_trials, nthreads, run_trials);
     int64_t max_inliers = 0;
     Model final_model;
     std::memset(&final_model, 0, sizeof(final_model));
@@ -262,6 +283,103 @@ extern "C" int akz_estimate_fundamental_matrix(const akz_keypoint* keypoints_0, 
     Model md;
     *found = estimate(keypoints_0, keypoints_1, matches8, epsilon, md) ? 1 : 0;
     if (*found) std::memcpy(f, md.f, sizeof(md.f));
+    return AKZ_OK;
+}
+
+// ---- the homography (no reference counterpart; akz_homography.hpp) ------------------------------------------
+namespace {
+bool estimate_h(const akz_keypoint* k0, const akz_keypoint* k1, const akz_match* sample, float epsilon, float (&h)[9]) {
+    float x0[4], y0[4], x1[4], y1[4];
+    for (int i = 0; i < 4; ++i) {
+        x0[i] = k0[sample[i].index_0].x; y0[i] = k0[sample[i].index_0].y;
+        x1[i] = k1[sample[i].index_1].x; y1[i] = k1[sample[i].index_1].y;
+    }
+    return homography_from_4(x0, y0, x1, y1, epsilon, h);
+}
+}  // namespace
+
+extern "C" int akz_estimate_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                       const akz_match* matches4, float epsilon, float* h, int* found) {
+    if (!keypoints_0 || !keypoints_1 || !matches4 || !h || !found) {
+        set_error("estimate_homography: null pointer");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < 4; ++i)
+        if (matches4[i].index_0 >= n0 || matches4[i].index_1 >= n1) {
+            set_error("estimate_homography: match index out of range");
+            return AKZ_ERR_INVALID_ARG;
+        }
+    float m[9];
+    *found = estimate_h(keypoints_0, keypoints_1, matches4, epsilon, m) ? 1 : 0;
+    if (*found) std::memcpy(h, m, sizeof(m));
+    return AKZ_OK;
+}
+
+// The host path of the homography RANSAC: remove_outliers_impl's structure with 4-point samples -- the samples from the
+// thread's source in trial order, the trials on the host pool, the winner in trial order with a strict `>` from 0, the final
+// filter in match order.  Fewer than 4 matches: returned unchanged, nothing drawn; no model with an inlier: all kept, found 0.
+extern "C" int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                              const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
+                                              float epsilon_inlier, akz_match* out, uint64_t* n_out, float* h, int* found) {
+    if (!n_out || (n_matches && (!matches || !out))) {
+        set_error("remove_outliers_homography: null pointer");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n_matches; ++i)
+        if (matches[i].index_0 >= n0 || matches[i].index_1 >= n1 || !keypoints_0 || !keypoints_1) {
+            set_error("remove_outliers_homography: match index out of range");
+            return AKZ_ERR_INVALID_ARG;
+        }
+    if (found) *found = 0;
+    if (n_matches < 4) {
+        if (n_matches) std::memcpy(out, matches, n_matches * sizeof(akz_match));
+        *n_out = n_matches;
+        return AKZ_OK;
+    }
+    std::vector<uint64_t> samples((size_t)num_trials * 4);
+    draw_samples<4>(default_source(), n_matches, num_trials, samples.data());
+    std::vector<Model> models((size_t)num_trials);
+    std::vector<int64_t> inliers((size_t)num_trials, -1);
+    std::vector<float> px0((size_t)n_matches), py0((size_t)n_matches), px1((size_t)n_matches), py1((size_t)n_matches);
+    for (uint64_t i = 0; i < n_matches; ++i) {
+        px0[(size_t)i] = keypoints_0[matches[i].index_0].x; py0[(size_t)i] = keypoints_0[matches[i].index_0].y;
+        px1[(size_t)i] = keypoints_1[matches[i].index_1].x; py1[(size_t)i] = keypoints_1[matches[i].index_1].y;
+    }
+    auto run_trials = [&](uint64_t lo, uint64_t hi) {
+        const float *x0 = px0.data(), *y0 = py0.data(), *x1 = px1.data(), *y1 = py1.data();
+        for (uint64_t trial = lo; trial < hi; ++trial) {
+            akz_match sample[4];
+            for (int i = 0; i < 4; ++i) sample[i] = matches[samples[(size_t)trial * 4 + i]];
+            Model model;
+            if (!estimate_h(keypoints_0, keypoints_1, sample, epsilon_model, model.f)) continue;
+            int64_t inl = 0;
+            for (uint64_t i = 0; i < n_matches; ++i) inl += homography_inlier(model.f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier) ? 1 : 0;
+            models[(size_t)trial] = model;
+            inliers[(size_t)trial] = inl;
+        }
+    };
+    const unsigned nthreads = (unsigned)std::min<uint64_t>(std::min(host_cpu_share(), 16u),
+                                                          std::max<uint64_t>(1, num_trials * (n_matches + 9000) / 2000000));
+    run_trials_pooled(num_trials, nthreads, run_trials);
+    int64_t max_inliers = 0;
+    uint64_t best = 0;
+    for (uint64_t trial = 0; trial < num_trials; ++trial)
+        if (inliers[(size_t)trial] > max_inliers) {
+            max_inliers = inliers[(size_t)trial];
+            best = trial;
+        }
+    uint64_t k = 0;
+    if (max_inliers == 0) {  // no model: everything is kept
+        std::memcpy(out, matches, n_matches * sizeof(akz_match));
+        k = n_matches;
+    } else {
+        const Model& md = models[(size_t)best];
+        for (uint64_t i = 0; i < n_matches; ++i)
+            if (homography_inlier(md.f, px0[(size_t)i], py0[(size_t)i], px1[(size_t)i], py1[(size_t)i], epsilon_inlier)) out[k++] = matches[i];
+        if (h) std::memcpy(h, md.f, sizeof(md.f));
+        if (found) *found = 1;
+    }
+    *n_out = k;
     return AKZ_OK;
 }
 

@@ -217,6 +217,12 @@ def lib():
         "akz_match_features": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64], i32),
         "akz_match_features_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64], i32),
         "akz_debug_ransac_samples": ([u64, u64, u64, u64, pu64], i32),
+        "akz_debug_ransac_samples_k": ([u64, u64, u64, u64, i32, pu64], i32),
+        "akz_estimate_homography": ([vp, u64, vp, u64, vp, C.c_float, fp, C.POINTER(i32)], i32),
+        "akz_remove_outliers_homography": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
+        "akz_match_features_homography": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp,
+                                           C.POINTER(i32)], i32),
+        "akz_match_features_homography_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
@@ -675,6 +681,15 @@ class Context:
         (keypoints, descriptors) arrays (KEYPOINT_DTYPE / uint8 [n, desc_bytes]), pairs a sequence of (first, second) indices
         into it.  Returns one MATCH_DTYPE array per pair, each equal to what match_features returns for that pair when the
         pairs are matched in order on this thread."""
+        return self._pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, False)
+
+    def match_features_homography_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
+        """match_features_homography over many pairs in one call (akz_match_features_homography_pairs), arguments as for
+        match_features_pairs.  Returns one (matches, H or None) per pair, each equal to what match_features_homography returns
+        for that pair when the pairs are matched in order on this thread."""
+        return self._pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, True)
+
+    def _pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, homography):
         ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
         ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
         nbs = {d.shape[1] for d in ds if d.ndim == 2 and len(d)}
@@ -692,12 +707,19 @@ class Context:
             raise IndexError("pair refers to a set that does not exist")
         out = np.zeros(max(1, sum(rows)), MATCH_DTYPE)
         n = np.zeros(max(1, len(pr)), np.uint64)
-        _check(lib().akz_match_features_pairs(self._h, C.cast(sets, C.c_void_p), len(ks), pr.ctypes.data_as(C.c_void_p), len(pr), nb, lowes_ratio,
-                                              ransac_trials, ransac_epsilon_inliers, out.ctypes.data_as(C.c_void_p),
-                                              n.ctypes.data_as(C.POINTER(C.c_uint64))))
+        args = (self._h, C.cast(sets, C.c_void_p), len(ks), pr.ctypes.data_as(C.c_void_p), len(pr), nb, lowes_ratio, ransac_trials,
+                ransac_epsilon_inliers, out.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.POINTER(C.c_uint64)))
+        if homography:
+            h = np.zeros((max(1, len(pr)), 9), np.float32)
+            found = np.zeros(max(1, len(pr)), np.int32)
+            _check(lib().akz_match_features_homography_pairs(*args, h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                             found.ctypes.data_as(C.POINTER(C.c_int32))))
+        else:
+            _check(lib().akz_match_features_pairs(*args))
         res, at = [], 0
         for p, r in enumerate(rows):
-            res.append(out[at:at + int(n[p])].copy())
+            m = out[at:at + int(n[p])].copy()
+            res.append((m, h[p].reshape(3, 3).copy() if found[p] else None) if homography else m)
             at += r
         return res
 
@@ -1212,6 +1234,72 @@ def match_features(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes
 def match_features_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
     """Context.match_features_pairs on ctx (default: the default context)."""
     return (ctx or default_context()).match_features_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers)
+
+
+# ---- homography RANSAC (an addition; include/akaze_hip.h, DESIGN.md 8) ----------------------------------------------------
+HOMOGRAPHY_EPSILON_MODEL = 1e-6  # AKZ_HOMOGRAPHY_EPSILON_MODEL: the epsilon_model of the context calls
+
+
+def estimate_homography(keypoints_0, keypoints_1, matches4, epsilon):
+    """The 4-point homography of exactly 4 matches (akz_estimate_homography): 3x3 float32 H with H[2, 2] = 1, or None."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches4, MATCH_DTYPE)
+    if len(m) != 4:
+        raise ValueError("exactly 4 matches")
+    h = np.zeros(9, np.float32)
+    found = C.c_int()
+    _check(lib().akz_estimate_homography(k0.ctypes.data, len(k0), k1.ctypes.data, len(k1), m.ctypes.data, epsilon,
+                                         h.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
+    return h.reshape(3, 3) if found.value else None
+
+
+def remove_outliers_homography(keypoints_0, keypoints_1, matches, num_trials, epsilon_model, epsilon_inlier):
+    """The homography RANSAC on the host (akz_remove_outliers_homography) -> (matches kept, H or None)."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    n = C.c_uint64()
+    h = np.zeros(9, np.float32)
+    found = C.c_int()
+    _check(lib().akz_remove_outliers_homography(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                                m.ctypes.data_as(C.c_void_p), len(m), num_trials, epsilon_model, epsilon_inlier,
+                                                out.ctypes.data_as(C.c_void_p), C.byref(n), h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                C.byref(found)))
+    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+
+
+def match_features_homography(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                              ransac_epsilon_inliers, ctx=None):
+    """descriptor_match(d0, d1, 10000, ratio), then the homography RANSAC, all on the GPU (akz_match_features_homography)
+    -> (matches kept, H or None); equal to remove_outliers_homography(k0, k1, that list, ransac_trials,
+    HOMOGRAPHY_EPSILON_MODEL, ransac_epsilon_inliers) from the same random state."""
+    c = ctx or default_context()
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
+    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
+    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
+    n = C.c_uint64()
+    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
+    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
+    if nb0 is not None and nb1 is not None and nb0 != nb1:
+        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
+    h = np.zeros(9, np.float32)
+    found = C.c_int()
+    _check(lib().akz_match_features_homography(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), len(d0),
+                                               k1.ctypes.data_as(C.c_void_p), len(k1), d1.ctypes.data_as(C.c_void_p), len(d1),
+                                               nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                               out.ctypes.data_as(C.c_void_p), C.byref(n), h.ctypes.data_as(C.POINTER(C.c_float)),
+                                               C.byref(found)))
+    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+
+
+def match_features_homography_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
+    """Context.match_features_homography_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_homography_pairs(features, pairs, lowes_ratio, ransac_trials,
+                                                                      ransac_epsilon_inliers)
 
 
 # ------------------------------------------------------------------------------------------

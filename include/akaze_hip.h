@@ -521,6 +521,46 @@ int akz_match_features_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t
                              uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
                              float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out /* n_pairs */);
 
+/* ---- homography RANSAC (an addition: the reference filters with the fundamental matrix only) --------------------------
+   For planar scenes and pure rotations, where F is not determined.  Model: the 4-point DLT with Hartley normalisation,
+   decomposed by the one-sided Jacobi SVD of the fundamental-matrix path, in f64 with one source for host and device (same
+   bits).  Samples whose normalised points are collinear in either image (|cross product| <= 1e-9, two equal points
+   included) or whose triples change orientation between the images give no model.  H is row-major with H[8] = 1 (it maps
+   image 0 onto image 1); a match is an inlier iff w = h6 x0 + h7 y0 + h8 > 0 and |H p0 - p1| < epsilon_inlier, evaluated
+   without a division as (U - x1 w)^2 + (V - y1 w)^2 < (epsilon_inlier w)^2 in f32.  The returned H is the winning trial's
+   model (no refit on the inliers).  Samples come from the calling thread's default random source, 4 per trial (see
+   akz_random_seed).  DESIGN.md 8. */
+/* epsilon_model of the two context calls: every rotated row norm of the normalised 8 x 9 design matrix must exceed it */
+#define AKZ_HOMOGRAPHY_EPSILON_MODEL 1e-6f
+/* The model of exactly 4 matches: *found = 0 for a degenerate sample or a rank below 8 at epsilon; h receives H. */
+int akz_estimate_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                            const akz_match* matches4, float epsilon, float* h /* 9 */, int* found);
+/* The host RANSAC (akz_remove_outliers with the homography): fewer than 4 matches are returned unchanged with *found = 0 and
+   nothing drawn; no trial with a model of more than 0 inliers: every match kept, *found = 0; otherwise *found = 1, h = the
+   winner (the first trial with the most inliers) and its inliers in match order.  out must hold n_matches entries; h and
+   found may be NULL. */
+int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                   const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
+                                   float epsilon_inlier, akz_match* out, uint64_t* n_out, float* h /* 9, may be NULL */,
+                                   int* found /* may be NULL */);
+/* descriptor_match(d0, d1, 10000, lowes_ratio) on the GPU, then the homography RANSAC with AKZ_HOMOGRAPHY_EPSILON_MODEL, its
+   trials, the winner and the final filter on the GPU: the result of akz_remove_outliers_homography on that list from the
+   same random state, bit for bit (list, H, found, the source's state afterwards).  Arguments and refusals are those of
+   akz_match_features; h (9) and found may be NULL. */
+int akz_match_features_homography(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                  const uint8_t* descriptors_0, uint64_t n_descriptors_0, const akz_keypoint* keypoints_1,
+                                  uint64_t n_keypoints_1, const uint8_t* descriptors_1, uint64_t n_descriptors_1,
+                                  uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                  akz_match* out, uint64_t* n_out, float* h /* 9 */, int* found);
+/* akz_match_features_homography over many pairs, with every promise of akz_match_features_pairs (the loop's lists in pair
+   order from the same random state, the source left where the loop leaves it, all refusals before the first draw and any
+   GPU work, fixed room per pair in out).  h: 9 floats per pair (zeros where found is 0), found: one flag per pair; either
+   may be NULL. */
+int akz_match_features_homography_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                        uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                        float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out /* n_pairs */,
+                                        float* h /* 9 x n_pairs */, int* found /* n_pairs */);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly

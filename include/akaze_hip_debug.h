@@ -129,8 +129,10 @@ int akz_debug_select_info(akz_ctx* ctx, int* info);
 /* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
    source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */
 int akz_debug_ransac_samples(uint64_t s0, uint64_t s1, uint64_t n_matches, uint64_t trials, uint64_t* out);
-/* Where akz_match_features_pairs spends its time: enable != 0 times the context's later calls (events on its stream);
-   ms (optional, 6 doubles) receives the last timed call's uploads, scans, host draws, trials, pick + filter and read-back
+/* The same draw loop with k = 8 or 4 indices per trial (the homography RANSAC draws 4); n_matches < k is refused. */
+int akz_debug_ransac_samples_k(uint64_t s0, uint64_t s1, uint64_t n_matches, uint64_t trials, int k, uint64_t* out);
+/* Where akz_match_features_pairs (or a homography call on a context) spends its time: enable != 0 times the context's later
+   calls (events on its stream); ms (optional, 6 doubles) receives the last timed call's uploads, scans, host draws, trials, pick + filter and read-back
    in ms (the trials: first trial launch to last trial's end, overlapping the draws). */
 int akz_debug_match_pairs_split(akz_ctx* ctx, int enable, double* ms);
 
