@@ -2103,7 +2103,15 @@ int akz_result_describe_keypoints(const akz_result* r, uint64_t img, akz_keypoin
     }
     AKZ_TRY(ensure_aux(c));
     hipStream_t s = c->aux;
-    AKZ_TRY(ensure_pinned(c, c->pin[3], n_kp * sizeof(KpParam)));
+    // The descriptor takes its ratio from the KEYPOINT's octave (descriptors.rs:51), the orientation from the octave of the
+    // keypoint's LEVEL (scale_space_extrema.rs:279).  The detector's keypoints carry their level's octave; a caller's need not:
+    // the orientation launch then reads a second parameter list (behind the first, in the same buffers).
+    bool own_octave = false;
+    if (compute_orientation)
+        for (uint64_t i = 0; i < n_kp && !own_octave; ++i)
+            own_octave = kps[i].class_id < L && kps[i].octave != r->plan[(size_t)kps[i].class_id].octave;
+    const uint64_t n_par = own_octave ? 2 * n_kp : n_kp;
+    AKZ_TRY(ensure_pinned(c, c->pin[3], n_par * sizeof(KpParam)));
     KpParam* params = (KpParam*)c->pin[3].p;
     for (uint64_t i = 0; i < n_kp; ++i) {
         const akz_keypoint& k = kps[i];
@@ -2111,27 +2119,30 @@ int akz_result_describe_keypoints(const akz_result* r, uint64_t img, akz_keypoin
             set_error("akz_result_describe_keypoints: keypoint class_id / octave out of range");
             return AKZ_ERR_INVALID_ARG;
         }
-        KpParam& p = params[i];
-        const float ratio = (float)(1u << k.octave);
-        p.xf = k.x / ratio;
-        p.yf = k.y / ratio;
-        p.scale = std::round(0.5f * k.size / ratio);
-        p.level = (uint32_t)k.class_id;
-        p.img = (uint32_t)img;
-        p._pad[0] = p._pad[1] = p._pad[2] = 0;
+        const float ratios[2] = {(float)(1u << k.octave), (float)(1u << r->plan[(size_t)k.class_id].octave)};
+        for (int q = 0; q < (own_octave ? 2 : 1); ++q) {
+            KpParam& p = params[(size_t)q * n_kp + i];
+            const float ratio = ratios[q];
+            p.xf = k.x / ratio;
+            p.yf = k.y / ratio;
+            p.scale = std::round(0.5f * k.size / ratio);
+            p.level = (uint32_t)k.class_id;
+            p.img = (uint32_t)img;
+            p._pad[0] = p._pad[1] = p._pad[2] = 0;
+        }
     }
-    AKZ_TRY(ensure(c, c->kp_in, n_kp * sizeof(KpParam)));
+    AKZ_TRY(ensure(c, c->kp_in, n_par * sizeof(KpParam)));
     AKZ_TRY(ensure(c, c->kp_out, n_kp * sizeof(OrientOut)));
     AKZ_TRY(ensure(c, c->cosi, n_kp * 2 * sizeof(float)));
     AKZ_TRY(ensure_pinned(c, c->pin[1], n_kp * std::max(sizeof(OrientOut), 2 * sizeof(float))));
     KpParam* d_kp = (KpParam*)c->kp_in.p;
-    AKZ_HIP_TRY(hipMemcpyAsync(d_kp, params, n_kp * sizeof(KpParam), hipMemcpyHostToDevice, s));
+    AKZ_HIP_TRY(hipMemcpyAsync(d_kp, params, n_par * sizeof(KpParam), hipMemcpyHostToDevice, s));
     if (compute_orientation) {
         unsigned long long wmask = 0;
         uint32_t nwin = 0;
         orientation_windows(&wmask, &nwin);
         OrientOut* d_oo = (OrientOut*)c->kp_out.p;
-        launch::orientation(s, tab, d_kp, (uint32_t)n_kp, wmask, nwin, d_oo);
+        launch::orientation(s, tab, own_octave ? d_kp + n_kp : d_kp, (uint32_t)n_kp, wmask, nwin, d_oo);
         AKZ_HIP_TRY(hipGetLastError());
         OrientOut* oo = (OrientOut*)c->pin[1].p;
         AKZ_HIP_TRY(hipMemcpyAsync(oo, d_oo, n_kp * sizeof(OrientOut), hipMemcpyDeviceToHost, s));

@@ -270,7 +270,17 @@ int akz_result_descriptors(const akz_result* res, uint64_t img, uint8_t* out);
    ops::descriptors::extract_descriptors (descriptors.rs:14-35) for caller-supplied keypoints of image `img` on the
    retained pyramid: uses point, size, octave and class_id of every keypoint; with compute_orientation != 0 the
    angle field is (re)computed and written back, otherwise the given angle is used.  descriptors: n x desc_bytes.
-   Keypoints too close to the image border are sampled with clamped coordinates (the reference would panic). */
+   As in the reference, the orientation divides by 2^octave of the keypoint's LEVEL (class_id) and the descriptor by
+   2^octave of the KEYPOINT; the two differ only for keypoints the detector did not emit.  class_id >= n_levels and
+   octave > 30 are refused (AKZ_ERR_INVALID_ARG, nothing written).
+   Samples outside the plane: every sample coordinate is converted to an integer (saturating, NaN to 0; the orientation
+   takes negatives as 0 first, like the reference's `as usize`) and then clamped to [0, w-1] x [0, h-1], so any
+   keypoint, non-finite fields included, is memory-safe.  Where all of a keypoint's samples lie inside its plane the
+   result is the reference's, bit for bit.  Where the reference would read past the end of a row (x >= w, not on the
+   last row: GrayFloatImage::get is the flat buffer[w * y + x], so it reads the next row and completes) this clamps to
+   the row's last pixel instead: a documented deviation, for keypoints the detector never emits (it drops everything
+   within about twice the descriptor's reach of the border).  Elsewhere (an index past the buffer, a negative
+   descriptor coordinate) the reference ends the call with a panic, or wraps, by build profile. */
 int akz_result_describe_keypoints(const akz_result* res, uint64_t img, akz_keypoint* kps, uint64_t n_keypoints,
                                   int compute_orientation, uint8_t* descriptors);
 /* device-resident descriptors, 64-byte rows (desc_bytes used, rest zero), for akz_match_device / RCCL gather */

@@ -802,6 +802,16 @@ def test_describe_caller_supplied_keypoints(ctx, amd, ref):
         assert np.array_equal(got_k["angle"], exp_k["angle"]), orient
         assert np.array_equal(got_d, exp_d), orient
     assert not np.array_equal(got_k["angle"], res.describe_keypoints(inner, compute_orientation=True)[0]["angle"])
+    # 4) the same against the numpy statement of the two ops (tests/mldb_numpy.py), on the planes the result holds; the rest
+    # of the entry point's input space is tests/test_gpu_describe.py's
+    import mldb_numpy
+    planes = [tuple(res.plane(l, p) for p in ("Lt", "Lx", "Ly")) for l in range(res.counts()[0])]
+    octaves = [res.level_info(l)["octave"] for l in range(len(planes))]
+    for orient in (True, False):
+        got_k, got_d = res.describe_keypoints(inner, compute_orientation=orient)
+        exp_a, exp_d, cov = mldb_numpy.describe(planes, octaves, inner, 3, "reference", orient)
+        assert cov.completes.all() and not cov.next_row.any()
+        assert np.array_equal(got_k["angle"].view(np.uint32), exp_a.view(np.uint32)) and np.array_equal(got_d, exp_d), orient
     bad = inner[:2].copy()
     bad["class_id"] = 99
     with pytest.raises(amd.AkazeError):

@@ -184,6 +184,61 @@ def test_isa_has_no_contracted_fma():
     assert seen == 4, seen
 
 
+def test_isa_clamps_every_gather_index_after_the_conversion():
+    """k_orientation and k_mldb turn float sample coordinates into plane indices; akz_result_describe_keypoints feeds them
+    keypoints of any value, NaN and the infinities included.  In the gfx950 code every such conversion must be the hardware's
+    v_cvt_i32_f32 (saturating, NaN -> 0) with its result going through v_min_i32 (the plane's size - 1) and a `> -1` select of
+    0 before it is used: no gather can then leave the plane.  (A float-to-int conversion of NaN is undefined for the
+    compiler, so this is a property of the generated code, not of the source: tests/test_gpu_describe.py runs non-finite
+    keypoints on the strength of it.)"""
+    import re
+    pkg = os.path.join(ROOT, "akaze-rust_amd")
+    asm, src = os.path.join(pkg, "csrc", "akz_kernels.s"), os.path.join(pkg, "csrc", "akz_kernels.hip")
+    if not os.path.exists(asm) or os.path.getmtime(asm) < os.path.getmtime(src):
+        subprocess.check_call(["make", "-C", pkg, "asm"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    s = open(asm).read()
+    want = {"k_orientation": (28, 0), "k_mldb": (14, 1)}  # (gathers: 14 samples x (x, y) / 7 lattice points x (x, y); others)
+    for m in re.finditer(r"^(_ZN3akz\w+):[^\n]*\n(.*?)^\.Lfunc_end", s, re.S | re.M):
+        name = re.sub(r"^_ZN3akz12_GLOBAL__N_1\d+", "", m.group(1))
+        key = next((k for k in want if name.startswith(k + "E")), None)
+        if key is None:
+            continue
+        lines = [l.strip() for l in m.group(2).split("\n")]
+        lines = [l for l in lines if l and not l.startswith((";", ".", "s_nop"))]
+        clamped = other = 0
+        for i, l in enumerate(lines):
+            c = re.match(r"v_cvt_i32_f32_e\d+ (v\d+), ", l)
+            if not c:
+                continue
+            regs, lo, hi = {c.group(1)}, False, False
+            for nxt in lines[i + 1:i + 24]:
+                ops = re.findall(r"\bv\d+\b", nxt)
+                if nxt.startswith("v_cndmask") and regs & set(ops[1:]) and not (lo or hi):
+                    regs.add(ops[0])  # (the orientation's `f > 0 ? (int)f : 0`)
+                elif nxt.startswith("v_min_i32") and regs & set(ops[1:]):
+                    hi = True
+                elif re.match(r"v_cmp_lt_i32_e\d+ (vcc|s\[\d+:\d+\]), -1, ", nxt) and regs & set(ops):
+                    lo = True
+            if lo and hi:
+                clamped += 1
+            else:
+                other += 1
+                assert key == "k_mldb" and "v_rcp_iflag_f32" in " ".join(lines[i - 8:i]), (name, i, l)  # (an integer division: the cell's row)
+        assert (clamped, other) == want.pop(key), (name, clamped, other)
+        # Unsigned conversions: none in k_orientation.  k_mldb has the compiler's 32-bit unsigned division (rel / npairs and
+        # rel % npairs of the 1- and 2-channel bit order, once per unrolled round of 64 bits): v_cvt_f32_ubyte0 of the divisor
+        # (6, 36 or 120), v_rcp_iflag_f32, a multiplication by 0x4f7ffffe, then v_cvt_u32_f32.  Its operand comes from a
+        # constant, never from a keypoint, and it lies behind the kernel's last plane gather.
+        ucvt = [i for i, l in enumerate(lines) if l.startswith("v_cvt_u32_f32")]
+        last_gather = max(i for i, l in enumerate(lines) if l.startswith("global_load_dword "))
+        assert len(ucvt) == (8 if key == "k_mldb" else 0), (name, len(ucvt))
+        for i in ucvt:
+            before = " ".join(lines[i - 8:i])
+            assert i > last_gather and "v_rcp_iflag_f32" in before and "v_cvt_f32_ubyte0" in before and \
+                re.match(r"v_mul_f32_e\d+ v\d+, 0x4f7ffffe, ", lines[i - 1]), (name, i, lines[i - 8:i + 1])
+    assert not want, want
+
+
 def _round_half_away(v):
     v = np.asarray(v, np.float32)
     return np.trunc(v + np.copysign(np.float32(0.5), v)).astype(np.float32)
