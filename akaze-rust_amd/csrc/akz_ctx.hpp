@@ -2,7 +2,10 @@
 // the stage timer, buffer helpers and the entry-point prologue (bind).  The C ABI itself is split by boundary area:
 //   akz_api.cpp      context lifecycle, host-side planning, profile, modes and measurement hooks
 //   akz_ops.cpp      the per-op entry points (`pub mod ops` / `types::image`) and the launch helpers the pipeline shares with them
-//   akz_extract.cpp  extract_features: begin / finish halves, jobs, results, stream placement
+//   akz_extract.cpp  extract_features: the C entry points, lanes and the finisher thread, gate calibration, the graph probe
+//     akz_extract_begin.cpp / akz_extract_finish.cpp  its two halves (private header: akz_extract.hpp)
+//     akz_result.cpp   slab pool, result / job lifetime, the result accessors, plane and pyramid downloads
+//     akz_place.cpp    stream placement
 //   akz_match_api.cpp  descriptor_match in all its forms, match_features
 //   akz_jpeg_api.cpp   file ingest with JPEG reconstruction on the device (akz_extract_features_file / _files)
 // Every size / host-thread gate that picks between kernel families or paths is a named constant of akz_gates.hpp.
@@ -82,6 +85,21 @@ struct Finisher {
     bool quit = false;
 };
 
+// akz_ctx::pin, the pinned host staging.  Ten buffers, two of them with two users that never overlap within a job: which allocation grows
+// when is part of the latency behaviour, so the sharing stays as it is
+enum Pin {
+    PIN_LIST = 0,       // the candidate list, or the device selection's SelKpHost records
+    PIN_COUNT_SUMS,     // the list's length (first word), later the orientation sums of the host's path
+    PIN_ROWS,           // 64-byte descriptor rows
+    PIN_PARAMS,         // keypoint parameters (KpParam)
+    PIN_COSI,           // (cos, sin) per keypoint
+    PIN_CONTRAST,       // contrast factors, one double per image
+    PIN_REL,            // neighbour lists of the candidates
+    PIN_REL_FLAGS,      // ... and their per-image flags
+    PIN_SEL_HDR,        // the device selection's headers (akz_extract.hpp: kSel*)
+    PIN_SPARE,          // (no user: the device selection's records carry their orientation sums)
+    PIN_COUNT_
+};
 struct akz_ctx {
     int device = 0;
     hipStream_t stream = nullptr;            // the stream the enqueueing helpers use: the caller's stream, except while extract_begin
@@ -142,9 +160,7 @@ struct akz_ctx {
     int libm_last = 0;          // how the last finished job got its angles: 0 host libm, 1 / 2 the device's FMA / SSE2 forms
     int dbg_host_sort = -1;                            // akz_debug_set_host_sort: 1 / 0 force the host / the device sort, -1 automatic
     DevBuf cosi;                             // (cos, sin) per keypoint
-    DevBuf pin[10];                          // pinned host staging: candidates, orientation sums, descriptor
-                                             // rows, keypoint params, (cos, sin), contrast factors, neighbour lists, their flags,
-                                             // the device selection's headers, its orientation sums
+    DevBuf pin[PIN_COUNT_];                  // pinned host staging (enum Pin)
     std::vector<std::pair<size_t, void*>> slab_pool;  // freed device blocks (pyramid slabs, descriptor rows)
     std::mutex slab_m;                                // results are freed by the caller while a lane's finisher thread allocates
     // extractions in flight (akz_extract_begin_* / akz_extract_finish)
@@ -155,7 +171,7 @@ struct akz_ctx {
     std::atomic<int> live_results{0};   // akz_result objects (also inside jobs) that still point at this context
     bool dead = false;                  // akz_ctx_destroy was called; the struct lives until the last result is freed
     std::atomic<uint32_t> last_total_cands{0};  // candidates of the previous finished job (speculative fetch size)
-    std::atomic<uint64_t> last_cand_shape{0};   // ... and its shape (w << 40 | h << 16 | n)
+    std::atomic<uint64_t> last_cand_shape{0};   // ... and its shape (akz_extract.hpp: shape_key)
     hipStream_t aux = nullptr;          // finish-side copies and keypoint kernels (created under aux_m: the caller's thread and the finisher's may both be first)
     std::mutex aux_m;
     hipStream_t coarse = nullptr;       // the coarse octaves' chain (diffusion + detectors), next to the fine detectors
@@ -228,7 +244,7 @@ struct akz_ctx {
         if (!workers) workers.reset(new WorkerPool(std::min(host_threads ? host_threads : host_cpu_share(), 16u) - 1));
         return *workers;
     }
-    // akz_fetch_pyramid (akz_extract.cpp), private to it like `lazy`: the streams its downloads run on, the pinned staging ring
+    // akz_fetch_pyramid (akz_result.cpp), private to it like `lazy`: the streams its downloads run on, the pinned staging ring
     // pageable destinations are filled through, and the recomputation of lean results -- temporaries that only the
     // context's stream touches, and two sets of outputs (Lxx, Lyy, Lxy, Lstep) that the downloads read alternately
     hipStream_t fetch[2] = {nullptr, nullptr};  // downloads alternate between two streams (two copy engines)
@@ -333,14 +349,25 @@ AKZ_LOCAL inline double now_ms() {
     return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
 }
 
+// Wait for the context's streams before memory they may still use is freed: the caller's stream, the finish half's, and the
+// side streams of the begin half (coarse chain, early stages, uploads).  The first failure is returned; every stream is waited for.
+enum : unsigned { kSyncMain = 1, kSyncAux = 2, kSyncSide = 4, kSyncAll = 7 };
+AKZ_LOCAL inline hipError_t sync_all_streams(akz_ctx* c, unsigned which = kSyncAll) {
+    hipError_t first = hipSuccess;
+    auto wait = [&](hipStream_t s) {
+        const hipError_t e = hipStreamSynchronize(s);
+        if (first == hipSuccess) first = e;
+    };
+    if (which & kSyncMain) wait(c->main);
+    if ((which & kSyncAux) && c->aux) wait(c->aux);
+    for (hipStream_t s : {c->coarse, c->pre, c->copy})
+        if ((which & kSyncSide) && s) wait(s);
+    return first;
+}
 AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return AKZ_OK;
     if (b.p) {
-        AKZ_HIP_TRY(hipStreamSynchronize(c->main));
-        if (c->aux) AKZ_HIP_TRY(hipStreamSynchronize(c->aux));
-        if (c->coarse) AKZ_HIP_TRY(hipStreamSynchronize(c->coarse));
-        if (c->pre) AKZ_HIP_TRY(hipStreamSynchronize(c->pre));
-        if (c->copy) AKZ_HIP_TRY(hipStreamSynchronize(c->copy));
+        AKZ_HIP_TRY(sync_all_streams(c));
         AKZ_HIP_TRY(hipFree(b.p));
         b.p = nullptr;
         b.bytes = 0;
@@ -356,9 +383,8 @@ AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
 }
 AKZ_LOCAL inline int ensure_pinned(akz_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return AKZ_OK;
-    if (b.p) {
-        AKZ_HIP_TRY(hipStreamSynchronize(c->main));
-        if (c->aux) AKZ_HIP_TRY(hipStreamSynchronize(c->aux));
+    if (b.p) {  // (the caller's stream and the finish half's only, as ever: every user of pinned staging synchronises its stream before it returns)
+        AKZ_HIP_TRY(sync_all_streams(c, kSyncMain | kSyncAux));
         AKZ_HIP_TRY(hipHostFree(b.p));
         b.p = nullptr;
         b.bytes = 0;
@@ -443,6 +469,7 @@ AKZ_LOCAL int detector_family(const akz_ctx* c, uint32_t sigma, uint32_t w, uint
                     bool nms = true);
 AKZ_LOCAL int detector_impl(akz_ctx* c, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy, float* lxy,
                   float* ldet_out, uint32_t w, uint32_t h, uint32_t n);
-// akz_extract.cpp
+// akz_place.cpp
 AKZ_LOCAL int place_streams(akz_ctx* c);
+// akz_extract_finish.cpp
 AKZ_LOCAL int device_libm_mode(akz_ctx* c);  // 0: host libm; 1 / 2: the device's FMA / SSE2 forms reproduce it (akz_libm.hpp)

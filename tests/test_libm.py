@@ -1,7 +1,7 @@
 """csrc/akz_libm.hpp -- glibc's atan2f / cosf / sinf restated as IEEE arithmetic so that the GPU can form a keypoint's angle and
 its cosine / sine without a host round trip -- compiled for the HOST and held to this machine's libm, bit for bit.  The
 device build of the same header is held to libm by tests/test_gpu_libm.py and, in every process that uses it, by the
-library's own self-test (akz_extract.cpp: device_libm_mode)."""
+library's own self-test (akz_extract_finish.cpp: device_libm_mode)."""
 import ctypes as C
 import os
 import platform
