@@ -134,6 +134,9 @@ struct akz_ctx {
     // trial samples; models and inlier counts; kept lists with their counts -- and the pinned staging of each
     DevBuf mp_in, mp_raw, mp_tab, mp_trials, mp_keep;
     DevBuf mp_pin_in, mp_pin_tab, mp_pin_smp[2], mp_pin_out;
+    // guided matching (akz_guided_api.cpp): pair table | models, chunk records, lists of a call; pinned: table | models, counts
+    DevBuf gd_tab, gd_rec, gd_out;
+    DevBuf gd_pin_tab, gd_pin_cnt, gd_pin_out;
     hipEvent_t mp_smp_ev[2] = {nullptr, nullptr};
     hipEvent_t mp_split_ev[7] = {};          // akz_debug_match_pairs_split: stage boundaries of a timed call
     bool mp_split_on = false;
@@ -471,5 +474,30 @@ AKZ_LOCAL int detector_impl(akz_ctx* c, const float* lsmooth, uint32_t sigma, fl
                   float* ldet_out, uint32_t w, uint32_t h, uint32_t n);
 // akz_place.cpp
 AKZ_LOCAL int place_streams(akz_ctx* c);
+// akz_match_api.cpp: the tail of every scan of one train set -- merge of the chunk records, ratio test, ordered compaction
+AKZ_LOCAL int match_finish(akz_ctx* c, MatchRec* rec, uint32_t n0, uint32_t chunks, uint32_t thr, double lowes_ratio, akz_match* d_out,
+                           uint64_t* d_n_out);
+// akz_match_api.cpp: what the pairs calls share -- the refusals, the placement of every distinct set and its upload to c->mp_in
+AKZ_LOCAL int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                             uint64_t desc_bytes, const void* out, const void* n_out, std::vector<uint8_t>& seen, uint64_t& cap);
+AKZ_LOCAL uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, std::vector<uint8_t>& seen,
+                               std::vector<uint64_t>& set_row, std::vector<uint64_t>& used);
+AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint64_t>& used, const std::vector<uint64_t>& set_row,
+                           uint64_t rows, uint64_t desc_bytes, size_t b_rows, size_t b_xy);
+// akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device (rows of 64 bytes, x, y), enqueued on the
+// context's stream -- scan, merge, ratio test and ordered compaction; pair p's list goes to d_out + spec[p].out_off, its
+// length to d_cnt[p].  d_models: 9 floats per pair ON THE DEVICE; d_found (optional): pairs whose flag is 0 give empty lists.
+struct GuidedPairSpec {
+    uint64_t q_row0, n0, t_row0, n1, out_off;
+};
+struct GuidedStage {  // the second stage of akz_match_features_homography_guided(_pairs)
+    float radius;
+    double ratio;
+};
+AKZ_LOCAL int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs,
+                            const std::vector<uint8_t>& seen);
+AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
+                             int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
+                             double lowes_ratio, akz_match* d_out, uint64_t* d_cnt);
 // akz_extract_finish.cpp
 AKZ_LOCAL int device_libm_mode(akz_ctx* c);  // 0: host libm; 1 / 2: the device's FMA / SSE2 forms reproduce it (akz_libm.hpp)

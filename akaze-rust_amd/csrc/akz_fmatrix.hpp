@@ -126,4 +126,32 @@ AKZ_HD float fundamental_error(const float (&f)[9], float x0, float y0, float x1
     return fabsf(s);
 }
 
+// The gate of guided matching for a fundamental matrix (akz_descriptor_match_guided, model_kind 1): the point
+// (x1, y1) lies closer than `radius` pixels to the epipolar line F (x0, y0, 1)^T, without a division or a square root, in
+// f32 in this order.  Per query (epipolar_line):
+//     l_r = (f[3 r] x0 + f[3 r + 1] y0) + f[3 r + 2], r = 0, 1, 2;   n = l0 l0 + l1 l1;   r2n = (radius radius) n
+// per train row (epipolar_near): s = (l0 x1 + l1 y1) + l2, passes iff s s < r2n.  Strict: a zero line (F = 0) passes
+// nothing, and neither does a NaN anywhere.  F has the convention of fundamental_error (p1^T F p0).
+// This is a DISTANCE IN PIXELS and deliberately not the algebraic |p1^T F p0| < epsilon of akz_remove_outliers /
+// fundamental_error, whose scale depends on the normalisation of F: a search band wants a width in pixels.
+struct EpipolarLine {
+    float l0, l1, l2, r2n;
+};
+AKZ_HD EpipolarLine epipolar_line(const float (&f)[9], float x0, float y0, float radius) {
+    EpipolarLine e;
+    e.l0 = (f[0] * x0 + f[1] * y0) + f[2];
+    e.l1 = (f[3] * x0 + f[4] * y0) + f[5];
+    e.l2 = (f[6] * x0 + f[7] * y0) + f[8];
+    const float n = e.l0 * e.l0 + e.l1 * e.l1, r2 = radius * radius;
+    e.r2n = r2 * n;
+    return e;
+}
+AKZ_HD bool epipolar_near(const EpipolarLine& e, float x1, float y1) {
+    const float s = (e.l0 * x1 + e.l1 * y1) + e.l2;
+    return s * s < e.r2n;
+}
+AKZ_HD bool fundamental_near_line(const float (&f)[9], float x0, float y0, float x1, float y1, float radius) {
+    return epipolar_near(epipolar_line(f, x0, y0, radius), x1, y1);
+}
+
 }  // namespace akz

@@ -1,0 +1,231 @@
+// C ABI of libakaze_hip.so, part 5: guided matching -- the host statement, the pair call and the pairs call
+// (the composite with the homography RANSAC is the last stage of match_pairs_impl, akz_match_api.cpp).
+#include "akz_ctx.hpp"
+#include "akz_homography.hpp"
+
+namespace {
+// the refusals every guided call shares; false: refused (message set)
+bool guided_args_ok(const char* name, int model_kind, const float* model, float radius) {
+    if (model_kind != AKZ_GUIDED_HOMOGRAPHY && model_kind != AKZ_GUIDED_FUNDAMENTAL) {
+        set_error(std::string(name) + "model_kind must be AKZ_GUIDED_HOMOGRAPHY (0) or AKZ_GUIDED_FUNDAMENTAL (1)");
+        return false;
+    }
+    if (!model) {
+        set_error(std::string(name) + "null model");
+        return false;
+    }
+    if (!(radius >= 0.0f && std::isfinite(radius))) {
+        set_error(std::string(name) + "radius must be finite and >= 0");
+        return false;
+    }
+    return true;
+}
+bool pair_args_ok(const char* name, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0, const akz_keypoint* kp1,
+                  uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, const akz_match* out, const uint64_t* n_out) {
+    const char* why = nullptr;
+    if (!n_out) why = "null n_out";
+    else if (desc_bytes == 0 || desc_bytes > 64) why = "desc_bytes must be 1..64";
+    else if (n_d0 > n_kp0 || n_d1 > n_kp1) why = "a feature set has more descriptors than keypoints";
+    else if ((n_kp0 && !kp0) || (n_kp1 && !kp1) || (n_d0 && !d0) || (n_d1 && !d1)) why = "null keypoints or descriptors";
+    else if (n_d0 && !out) why = "null out";
+    if (why) set_error(std::string(name) + why);
+    return why == nullptr;
+}
+uint32_t clamp_threshold(uint64_t t) { return (uint32_t)std::min<uint64_t>(t, 0x7fffffffull); }
+}  // namespace
+
+// The sizes one launch of the guided scan takes, checked with the other refusals before any GPU work: rows of a set below
+// 2^31, rows of all sets of the call below 2^32, workgroups (query blocks x at most 64 chunks) below 2^31.
+int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const std::vector<uint8_t>& seen) {
+    uint64_t rows = 0, wg = 0;
+    bool ok = true;
+    for (size_t k = 0; k < seen.size(); ++k)
+        if (seen[k]) {
+            ok = ok && sets[k].n_descriptors <= 0x7fffffffull;
+            rows += std::min<uint64_t>(sets[k].n_descriptors, 0x100000000ull);
+        }
+    for (uint64_t p = 0; p < n_pairs && ok; ++p) {
+        wg += (sets[pairs[2 * p]].n_descriptors + launch::match_guided_block() - 1) / launch::match_guided_block() * 64;
+        ok = wg <= 0x7fffffffull;
+    }
+    if (!ok || rows > 0xffffffffull) {
+        set_error(std::string(name) + "too many rows or pairs for one guided launch");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    return AKZ_OK;
+}
+
+int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
+                        int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
+                        double lowes_ratio, akz_match* d_out, uint64_t* d_cnt) {
+    hipStream_t st = c->stream;
+    const uint32_t thr = clamp_threshold(distance_threshold), block = launch::match_guided_block();
+    AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, spec.size() * sizeof(uint64_t), st));
+    // A pair's train rows are cut into chunks so that the launch fills the chip: 256 compute units take eight workgroups of
+    // four waves each, and a chunk should still be a few LDS tiles long (akz_debug_set_match_chunks forces the pair count).
+    // (sizes: guided_limits has passed)
+    uint64_t qblocks = 0;
+    for (const GuidedPairSpec& s : spec)
+        if (s.n0 && s.n1) qblocks += (s.n0 + block - 1) / block;
+    if (qblocks == 0) return AKZ_OK;
+    const uint64_t want = std::max<uint64_t>(1, (2048 + qblocks - 1) / qblocks);
+    std::vector<launch::GuidedPairHost> tab;
+    uint64_t rec_total = 0, wg = 0;
+    for (size_t p = 0; p < spec.size(); ++p) {
+        const GuidedPairSpec& s = spec[p];
+        if (!s.n0 || !s.n1) continue;
+        const uint32_t tiles = (uint32_t)((s.n1 + block - 1) / block);
+        uint32_t chunks = c->dbg_pair_chunks ? c->dbg_pair_chunks : (uint32_t)std::min<uint64_t>(want, std::max<uint32_t>(1, tiles / 2));
+        chunks = std::max(1u, std::min(std::min(chunks, tiles), 64u));
+        const uint32_t chunk_rows = (uint32_t)((s.n1 + chunks - 1) / chunks);
+        tab.push_back(launch::GuidedPairHost{rec_total, (uint32_t)s.q_row0, (uint32_t)s.n0, (uint32_t)s.t_row0, (uint32_t)s.n1, (uint32_t)wg,
+                                             chunks, chunk_rows, (uint32_t)p});
+        rec_total += s.n0 * (chunks + 1);  // (+ 1: the merged records of a pair with many chunks)
+        wg += (s.n0 + block - 1) / block * chunks;
+    }
+    const size_t b_tab = tab.size() * sizeof(launch::GuidedPairHost);
+    AKZ_TRY(ensure(c, c->gd_tab, b_tab));
+    AKZ_TRY(ensure(c, c->gd_rec, rec_total * sizeof(MatchRec)));
+    AKZ_TRY(ensure_pinned(c, c->gd_pin_tab, b_tab));
+    std::memcpy(c->gd_pin_tab.p, tab.data(), b_tab);
+    AKZ_HIP_TRY(hipMemcpyAsync(c->gd_tab.p, c->gd_pin_tab.p, b_tab, hipMemcpyHostToDevice, st));
+    MatchRec* rec = (MatchRec*)c->gd_rec.p;
+    launch::match_guided(st, kind, d_rows, d_kx, d_ky, (const launch::GuidedPairHost*)c->gd_tab.p, (uint32_t)tab.size(), (uint32_t)wg, d_models,
+                         d_found, radius, thr, rec);
+    AKZ_HIP_TRY(hipGetLastError());
+    for (const launch::GuidedPairHost& g : tab)
+        AKZ_TRY(match_finish(c, rec + g.rec_off, g.n0, g.chunks, thr, lowes_ratio, d_out + spec[g.model].out_off, d_cnt + g.model));
+    AKZ_HIP_TRY(hipGetLastError());
+    return AKZ_OK;
+}
+
+extern "C" {
+
+int akz_descriptor_match_guided_host(const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0, const akz_keypoint* kp1,
+                                     uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, int model_kind,
+                                     const float* model, float radius, uint64_t distance_threshold, double lowes_ratio, akz_match* out,
+                                     uint64_t* n_out) {
+    const char* name = "descriptor_match_guided_host: ";
+    if (!pair_args_ok(name, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, out, n_out) ||
+        !guided_args_ok(name, model_kind, model, radius))
+        return AKZ_ERR_INVALID_ARG;
+    float m[9];
+    std::memcpy(m, model, sizeof(m));
+    const uint32_t thr = clamp_threshold(distance_threshold);
+    const double ratio2 = lowes_ratio * lowes_ratio;
+    uint64_t cnt = 0;
+    for (uint64_t i = 0; i < n_d0; ++i) {  // feature_matching.rs:37-81 with the gate at the top of the inner loop
+        const uint8_t* a = d0 + i * desc_bytes;
+        const float x0 = kp0[i].x, y0 = kp0[i].y;
+        uint32_t min_d = thr, second = thr;
+        uint64_t min_j = 0;
+        for (uint64_t j = 0; j < n_d1; ++j) {
+            const bool pass = model_kind == AKZ_GUIDED_HOMOGRAPHY ? akz::homography_inlier(m, x0, y0, kp1[j].x, kp1[j].y, radius)
+                                                                  : akz::fundamental_near_line(m, x0, y0, kp1[j].x, kp1[j].y, radius);
+            if (!pass) continue;
+            const uint8_t* b = d1 + j * desc_bytes;
+            uint32_t d = 0;
+            uint64_t t = 0;
+            for (; t + 8 <= desc_bytes; t += 8) {
+                uint64_t wa, wb;
+                std::memcpy(&wa, a + t, 8);
+                std::memcpy(&wb, b + t, 8);
+                d += (uint32_t)__builtin_popcountll(wa ^ wb);
+            }
+            for (; t < desc_bytes; ++t) d += (uint32_t)__builtin_popcount((unsigned)(a[t] ^ b[t]));
+            if (d < min_d) {
+                second = min_d;
+                min_d = d;
+                min_j = j;
+            } else if (d < second) {
+                second = d;
+            }
+        }
+        if ((double)min_d < (double)second * ratio2 && min_d < thr) out[cnt++] = akz_match{i, min_j, (double)min_d};
+    }
+    *n_out = cnt;
+    return AKZ_OK;
+}
+
+int akz_descriptor_match_guided_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                                      uint64_t desc_bytes, int model_kind, const float* models, float radius, uint64_t distance_threshold,
+                                      double lowes_ratio, akz_match* out, uint64_t* n_out) {
+    const char* name = "descriptor_match_guided_pairs: ";
+    if (n_pairs == 0) return AKZ_OK;
+    if (!guided_args_ok(name, model_kind, models, radius)) return AKZ_ERR_INVALID_ARG;
+    std::vector<uint8_t> seen;
+    uint64_t cap = 0;
+    AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
+    AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
+    AKZ_TRY(bind(c, true, false));
+    hipStream_t st = c->stream;
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    std::vector<uint64_t> set_row, used;
+    const uint64_t rows = pairs_place(sets, n_sets, pairs, n_pairs, seen, set_row, used);
+    const uint64_t rows1 = std::max<uint64_t>(rows, 1), cap1 = std::max<uint64_t>(cap, 1);
+    const size_t b_rows = up((size_t)rows1 * 64), b_xy = up((size_t)rows1 * 4), b_cnt = up((size_t)n_pairs * 8);
+    const size_t b_mdl = up((size_t)n_pairs * 36);
+    AKZ_TRY(ensure(c, c->mp_in, b_rows + 2 * b_xy));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, b_rows + 2 * b_xy));
+    AKZ_TRY(ensure(c, c->gd_out, b_cnt + b_mdl + (size_t)cap1 * sizeof(akz_match)));
+    AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, b_cnt + b_mdl));
+    const uint8_t* d_rows = (const uint8_t*)c->mp_in.p;
+    const float *d_kx = (const float*)(d_rows + b_rows), *d_ky = (const float*)(d_rows + b_rows + b_xy);
+    uint64_t* d_cnt = (uint64_t*)c->gd_out.p;
+    float* d_models = (float*)((char*)c->gd_out.p + b_cnt);
+    akz_match* d_out = (akz_match*)((char*)c->gd_out.p + b_cnt + b_mdl);
+    uint64_t* h_cnt = (uint64_t*)c->gd_pin_cnt.p;
+    float* h_models = (float*)((char*)c->gd_pin_cnt.p + b_cnt);
+    AKZ_TRY(pairs_upload(c, sets, used, set_row, rows, desc_bytes, b_rows, b_xy));
+    std::memcpy(h_models, models, (size_t)n_pairs * 36);
+    AKZ_HIP_TRY(hipMemcpyAsync(d_models, h_models, (size_t)n_pairs * 36, hipMemcpyHostToDevice, st));
+    std::vector<GuidedPairSpec> spec((size_t)n_pairs);
+    uint64_t off = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+        spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
+        off += sets[a].n_descriptors;
+    }
+    AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, model_kind, d_models, nullptr, radius, distance_threshold, lowes_ratio, d_out, d_cnt));
+    AKZ_HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+    AKZ_HIP_TRY(hipStreamSynchronize(st));
+    // ONE read-back of the span the lists occupy (fixed room per pair), through pinned staging
+    uint64_t span = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        if (h_cnt[p]) span = spec[(size_t)p].out_off + h_cnt[p];
+    if (span) {
+        AKZ_TRY(ensure_pinned(c, c->gd_pin_out, (size_t)span * sizeof(akz_match)));
+        AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_out.p, d_out, (size_t)span * sizeof(akz_match), hipMemcpyDeviceToHost, st));
+        AKZ_HIP_TRY(hipStreamSynchronize(st));
+    }
+    const akz_match* h_out = (const akz_match*)c->gd_pin_out.p;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint64_t k = h_cnt[p], at = spec[(size_t)p].out_off;
+        if (k) std::memcpy(out + at, h_out + at, (size_t)k * sizeof(akz_match));
+        n_out[p] = k;
+    }
+    return AKZ_OK;
+}
+
+// one pair: the pairs call with sets {0, 1} and the pair (0, 1)
+int akz_descriptor_match_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0, const akz_keypoint* kp1,
+                                uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, int model_kind, const float* model,
+                                float radius, uint64_t distance_threshold, double lowes_ratio, akz_match* out, uint64_t* n_out) {
+    const char* name = "descriptor_match_guided: ";
+    if (!pair_args_ok(name, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, out, n_out) ||
+        !guided_args_ok(name, model_kind, model, radius))
+        return AKZ_ERR_INVALID_ARG;
+    if (!c) {
+        set_error(std::string(name) + "null context");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
+    const uint64_t pair[2] = {0, 1};
+    uint64_t cnt = 0;
+    AKZ_TRY(akz_descriptor_match_guided_pairs(c, sets, 2, pair, 1, desc_bytes, model_kind, model, radius, distance_threshold, lowes_ratio, out,
+                                              &cnt));
+    *n_out = cnt;
+    return AKZ_OK;
+}
+
+}  // extern "C"

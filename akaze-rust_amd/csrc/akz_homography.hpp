@@ -175,5 +175,24 @@ AKZ_HD bool homography_inlier(const float (&h)[9], float x0, float y0, float x1,
     const float du = U - x1 * w, dv = V - y1 * w, ew = eps * w;
     return w > 0.0f && du * du + dv * dv < ew * ew;
 }
+// homography_inlier in two halves for a scan that tests one (x0, y0) against many (x1, y1) (akz_guided.hip): what depends
+// on the query alone is formed once -- the same operations on the same values, so transfer_near(transfer_disc(h, x0, y0,
+// eps), x1, y1) has the bits of homography_inlier(h, x0, y0, x1, y1, eps).
+struct TransferDisc {
+    float U, V, w, ew2;
+};
+AKZ_HD TransferDisc transfer_disc(const float (&h)[9], float x0, float y0, float eps) {
+    TransferDisc t;
+    t.w = (h[6] * x0 + h[7] * y0) + h[8];
+    t.U = (h[0] * x0 + h[1] * y0) + h[2];
+    t.V = (h[3] * x0 + h[4] * y0) + h[5];
+    const float ew = eps * t.w;
+    t.ew2 = ew * ew;
+    return t;
+}
+AKZ_HD bool transfer_near(const TransferDisc& t, float x1, float y1) {
+    const float du = t.U - x1 * t.w, dv = t.V - y1 * t.w;
+    return t.w > 0.0f && du * du + dv * dv < t.ew2;
+}
 
 }  // namespace akz

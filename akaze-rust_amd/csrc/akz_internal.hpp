@@ -419,6 +419,20 @@ void match_merge(hipStream_t s, const MatchRec* d_part, uint32_t n0, uint32_t ch
 size_t match_merge_compact_state_bytes(uint32_t n0);
 void match_merge_compact(hipStream_t s, const MatchRec* d_part, uint32_t n0, uint32_t chunks, uint32_t threshold, double ratio2,
                          akz_match* d_out, unsigned long long* d_n_out, void* d_state, uint32_t epoch);
+// guided matching (akz_guided.hip): the scan of `match` over many pairs at once, in which a train row competes for a query
+// only if the pair's model (kind 0: homography, 1: fundamental matrix; d_models + 9 * model) sends the query within
+// `radius` pixels of it.  d_rows / d_kx / d_ky: 64-byte rows and keypoint coordinates of every set; a table entry per
+// pair WITH rows on both sides, its workgroups wg0 .. wg0 + ceil(n0 / match_guided_block()) * chunks - 1; records as
+// `match` writes them, at d_rec[rec_off + chunk * n0 + query].  d_found (optional): pairs with found[model] == 0 get the
+// records of an empty scan.
+struct GuidedPairHost {  // = GuidedPair of akz_guided.hip
+    uint64_t rec_off;
+    uint32_t q_row0, n0, t_row0, n1, wg0, chunks, chunk_rows, model;
+};
+uint32_t match_guided_block();
+void match_guided(hipStream_t s, int kind, const uint8_t* d_rows, const float* d_kx, const float* d_ky, const GuidedPairHost* d_tab,
+                  uint32_t n_tab, uint32_t n_workgroups, const float* d_models, const int32_t* d_found, float radius,
+                  uint32_t threshold, MatchRec* d_rec);
 }  // namespace launch
 
 // ---- host keypoint logic (akz_keypoints.cpp) ---------------------------------------------

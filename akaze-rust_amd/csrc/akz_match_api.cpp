@@ -1,6 +1,40 @@
 // C ABI of libakaze_hip.so, part 4: descriptor_match (pair, multi-set, both directions), match_features.
 #include "akz_ctx.hpp"
 
+// Merge of a query set's chunk records (rec[chunk][query], then room for n0 merged records), ratio test and ordered
+// compaction: what every scan of one train set ends with (akz_descriptor_match_device, the guided scan), on c->stream.
+int match_finish(akz_ctx* c, MatchRec* rec, uint32_t n0, uint32_t chunks, uint32_t thr, double lowes_ratio, akz_match* d_out,
+                 uint64_t* d_n_out) {
+    // more than a few chunks: a parallel merge first (the compaction is ONE workgroup, i.e. one compute unit's load path:
+    // folding 11 chunks of 11 K queries there took 35 us against 5 for the 44-workgroup merge)
+    // Query sets of a few workgroups and more: merge, ratio test and ordered compaction in ONE launch (k_match_merge_compact:
+    // 44 workgroups for a 4K frame's 11 K rows); tiny ones keep the single-workgroup compaction
+    // k_match_merge_compact is a chained look-back: a workgroup publishes its count, then waits for the counts of the
+    // workgroups before it.  Two conditions keep that free of deadlock and of cross-talk, and both are enforced HERE:
+    //   * every workgroup of the grid is resident at once (progress never depends on the order of dispatch): at most 1 024
+    //     workgroups of 256 threads -- four per compute unit -- i.e. query sets of up to 262 144 rows; larger sets take the
+    //     merge + single-workgroup compaction below;
+    //   * match_state (told apart by epoch) belongs to ONE stream: this function, like every user of the context's matcher
+    //     scratch (match_rec, mm_q8, mm_t8, mm_pop), enqueues on c->stream only -- launches of two epochs never overlap.
+    if (n0 >= gates::kMergeCompactMinRows && n0 <= gates::kMergeCompactMaxRows) {
+        const size_t need = launch::match_merge_compact_state_bytes(n0);
+        if (c->match_state.bytes < need) {
+            AKZ_TRY(ensure(c, c->match_state, need * 2));
+            AKZ_HIP_TRY(hipMemsetAsync(c->match_state.p, 0, c->match_state.bytes, c->stream));
+        }
+        if (++c->match_epoch == 0) ++c->match_epoch;
+        launch::match_merge_compact(c->stream, rec, n0, chunks, thr, lowes_ratio * lowes_ratio, d_out,
+                                    (unsigned long long*)d_n_out, c->match_state.p, c->match_epoch);
+        AKZ_HIP_TRY(hipGetLastError());
+        return AKZ_OK;
+    }
+    const bool premerge = chunks > gates::kPremergeChunks;
+    if (premerge) launch::match_merge(c->stream, rec, n0, chunks, thr, rec + (size_t)chunks * n0);
+    launch::match_compact(c->stream, premerge ? rec + (size_t)chunks * n0 : rec, n0, premerge ? 1u : chunks, thr,
+                          lowes_ratio * lowes_ratio, d_out, (unsigned long long*)d_n_out);
+    AKZ_HIP_TRY(hipGetLastError());
+    return AKZ_OK;
+}
 extern "C" {
 // ---------------------------------------------------------------------------------------------
 // descriptor_match
@@ -40,35 +74,7 @@ static int match_device_impl(akz_ctx* c, const uint8_t* d_d0, uint64_t n0, const
     } else {
         launch::match(c->stream, d_d0, (uint32_t)n0, d_d1, (uint32_t)n1, thr, rows_le_61, chunks, rec);
     }
-    // more than a few chunks: a parallel merge first (the compaction is ONE workgroup, i.e. one compute unit's load path:
-    // folding 11 chunks of 11 K queries there took 35 us against 5 for the 44-workgroup merge)
-    // Query sets of a few workgroups and more: merge, ratio test and ordered compaction in ONE launch (k_match_merge_compact:
-    // 44 workgroups for a 4K frame's 11 K rows); tiny ones keep the single-workgroup compaction
-    // k_match_merge_compact is a chained look-back: a workgroup publishes its count, then waits for the counts of the
-    // workgroups before it.  Two conditions keep that free of deadlock and of cross-talk, and both are enforced HERE:
-    //   * every workgroup of the grid is resident at once (progress never depends on the order of dispatch): at most 1 024
-    //     workgroups of 256 threads -- four per compute unit -- i.e. query sets of up to 262 144 rows; larger sets take the
-    //     merge + single-workgroup compaction below;
-    //   * match_state (told apart by epoch) belongs to ONE stream: this function, like every user of the context's matcher
-    //     scratch (match_rec, mm_q8, mm_t8, mm_pop), enqueues on c->stream only -- launches of two epochs never overlap.
-    if (n0 >= gates::kMergeCompactMinRows && n0 <= gates::kMergeCompactMaxRows) {
-        const size_t need = launch::match_merge_compact_state_bytes((uint32_t)n0);
-        if (c->match_state.bytes < need) {
-            AKZ_TRY(ensure(c, c->match_state, need * 2));
-            AKZ_HIP_TRY(hipMemsetAsync(c->match_state.p, 0, c->match_state.bytes, c->stream));
-        }
-        if (++c->match_epoch == 0) ++c->match_epoch;
-        launch::match_merge_compact(c->stream, rec, (uint32_t)n0, chunks, thr, lowes_ratio * lowes_ratio, d_out,
-                                    (unsigned long long*)d_n_out, c->match_state.p, c->match_epoch);
-        AKZ_HIP_TRY(hipGetLastError());
-        return AKZ_OK;
-    }
-    const bool premerge = chunks > gates::kPremergeChunks;
-    if (premerge) launch::match_merge(c->stream, rec, (uint32_t)n0, chunks, thr, rec + (size_t)chunks * n0);
-    launch::match_compact(c->stream, premerge ? rec + (size_t)chunks * n0 : rec, (uint32_t)n0, premerge ? 1u : chunks, thr,
-                          lowes_ratio * lowes_ratio, d_out, (unsigned long long*)d_n_out);
-    AKZ_HIP_TRY(hipGetLastError());
-    return AKZ_OK;
+    return match_finish(c, rec, (uint32_t)n0, chunks, thr, lowes_ratio, d_out, d_n_out);
 }
 
 int akz_descriptor_match_device(akz_ctx* c, const uint8_t* d_d0, uint64_t n0, const uint8_t* d_d1, uint64_t n1,
@@ -386,6 +392,80 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
 
 }  // extern "C"
 
+// The refusals of the pairs calls (akz_match_features_pairs, its homography form, akz_descriptor_match_guided_pairs), all
+// before any GPU work: seen[k] = 1 for every set a pair names, cap = the room of `out` (sum of the first sets' descriptors).
+int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                        uint64_t desc_bytes, const void* out, const void* n_out, std::vector<uint8_t>& seen, uint64_t& cap) {
+    auto refuse = [name](const std::string& msg) {
+        set_error(name + msg);
+        return AKZ_ERR_INVALID_ARG;
+    };
+    if (!pairs || !n_out) return refuse("null pairs or n_out");
+    if (desc_bytes == 0 || desc_bytes > 64) return refuse("desc_bytes must be 1..64");
+    if (n_sets && !sets) return refuse("null sets");
+    seen.assign((size_t)n_sets, 0);  // 1: checked, 2 .. : checked and placed (pairs_upload)
+    cap = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const uint64_t k = pairs[2 * p + side];
+            if (k >= n_sets)
+                return refuse("pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(n_sets));
+            if (side == 0) cap += sets[k].n_descriptors;
+            if (seen[(size_t)k]) continue;
+            const akz_feature_set& f = sets[k];
+            const std::string at = "pair " + std::to_string(p) + ", set " + std::to_string(k) + ": ";
+            if (f.n_descriptors > f.n_keypoints) return refuse(at + "more descriptors than keypoints");
+            if ((f.n_keypoints && !f.keypoints) || (f.n_descriptors && !f.descriptors)) return refuse(at + "null keypoints or descriptors");
+            seen[(size_t)k] = 1;
+        }
+    if (cap && !out) return refuse("null out");
+    if (!c) return refuse("null context");
+    return AKZ_OK;
+}
+// every distinct set once, in order of first use: rows (and x / y of its first n_descriptors keypoints, the only ones a
+// match can name) from row set_row[k]; returns the rows of all used sets
+uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, std::vector<uint8_t>& seen,
+                          std::vector<uint64_t>& set_row, std::vector<uint64_t>& used) {
+    set_row.assign((size_t)n_sets, 0);
+    used.clear();
+    uint64_t rows = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const uint64_t k = pairs[2 * p + side];
+            if (seen[(size_t)k] == 2) continue;
+            seen[(size_t)k] = 2;
+            used.push_back(k);
+            set_row[(size_t)k] = rows;
+            rows += sets[k].n_descriptors;
+        }
+    return rows;
+}
+// every used set's rows (padded to 64 bytes) and the x / y of its first n_descriptors keypoints: through pinned staging to
+// c->mp_in = rows | x | y (b_rows, b_xy: the sizes of the parts), on the context's stream
+int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint64_t>& used, const std::vector<uint64_t>& set_row,
+                      uint64_t rows, uint64_t desc_bytes, size_t b_rows, size_t b_xy) {
+    hipStream_t st = c->stream;
+    uint8_t* d_rows = (uint8_t*)c->mp_in.p;
+    float *d_kx = (float*)(d_rows + b_rows), *d_ky = (float*)(d_rows + b_rows + b_xy);
+    {
+        uint8_t* h = (uint8_t*)c->mp_pin_in.p;
+        float *hx = (float*)(h + b_rows), *hy = (float*)(h + b_rows + b_xy);
+        for (uint64_t k : used) {
+            const akz_feature_set& f = sets[k];
+            uint8_t* r = h + set_row[(size_t)k] * 64;
+            for (uint64_t i = 0; i < f.n_descriptors; ++i) {
+                std::memcpy(r + i * 64, f.descriptors + i * desc_bytes, (size_t)desc_bytes);
+                if (desc_bytes < 64) std::memset(r + i * 64 + desc_bytes, 0, (size_t)(64 - desc_bytes));
+                hx[set_row[(size_t)k] + i] = f.keypoints[i].x;
+                hy[set_row[(size_t)k] + i] = f.keypoints[i].y;
+            }
+        }
+        AKZ_HIP_TRY(hipMemcpyAsync(d_rows, h, (size_t)rows * 64, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipMemcpyAsync(d_kx, hx, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipMemcpyAsync(d_ky, hy, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+    }
+    return AKZ_OK;
+}
 // The geometric model of the pairs orchestration below: K match indices per sample, the trial and pick / filter kernels, and
 // whether the call hands back a model per pair (H, found).
 namespace {
@@ -434,33 +514,17 @@ struct HomographyModel {  // akz_match_features_homography(_pairs): k_homography
 template <class Model>
 int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
                      double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out, float* model_out,
-                     int* found_out) {
+                     int* found_out, const GuidedStage* guided = nullptr) {
     constexpr int K = Model::K;
     if (n_pairs == 0) return AKZ_OK;
-    auto refuse = [](const std::string& msg) {
-        set_error(Model::kName + msg);
+    if (guided && !(guided->radius >= 0.0f && std::isfinite(guided->radius))) {
+        set_error(std::string(Model::kName) + "guided_radius must be finite and >= 0");
         return AKZ_ERR_INVALID_ARG;
-    };
-    if (!pairs || !n_out) return refuse("null pairs or n_out");
-    if (desc_bytes == 0 || desc_bytes > 64) return refuse("desc_bytes must be 1..64");
-    if (n_sets && !sets) return refuse("null sets");
-    std::vector<uint8_t> seen((size_t)n_sets, 0);  // 1: checked, 2 .. : checked and placed (see below)
+    }
+    std::vector<uint8_t> seen;
     uint64_t cap = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        for (int side = 0; side < 2; ++side) {
-            const uint64_t k = pairs[2 * p + side];
-            if (k >= n_sets)
-                return refuse("pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(n_sets));
-            if (side == 0) cap += sets[k].n_descriptors;
-            if (seen[(size_t)k]) continue;
-            const akz_feature_set& f = sets[k];
-            const std::string at = "pair " + std::to_string(p) + ", set " + std::to_string(k) + ": ";
-            if (f.n_descriptors > f.n_keypoints) return refuse(at + "more descriptors than keypoints");
-            if ((f.n_keypoints && !f.keypoints) || (f.n_descriptors && !f.descriptors)) return refuse(at + "null keypoints or descriptors");
-            seen[(size_t)k] = 1;
-        }
-    if (cap && !out) return refuse("null out");
-    if (!c) return refuse("null context");
+    AKZ_TRY(pairs_validate(Model::kName, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
+    if (guided) AKZ_TRY(guided_limits(Model::kName, sets, pairs, n_pairs, seen));
     AKZ_TRY(bind(c, true, false));
     const bool timed = c->mp_split_on;
     if (timed)
@@ -468,19 +532,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
             if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
     hipStream_t st = c->stream;
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    // every distinct set once, in order of first use: rows (and x / y of its first n_descriptors keypoints, the only ones a
-    // match can name) from row set_row[k]
-    std::vector<uint64_t> set_row((size_t)n_sets, 0), used;
-    uint64_t rows = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        for (int side = 0; side < 2; ++side) {
-            const uint64_t k = pairs[2 * p + side];
-            if (seen[(size_t)k] == 2) continue;
-            seen[(size_t)k] = 2;
-            used.push_back(k);
-            set_row[(size_t)k] = rows;
-            rows += sets[k].n_descriptors;
-        }
+    std::vector<uint64_t> set_row, used;
+    const uint64_t rows = pairs_place(sets, n_sets, pairs, n_pairs, seen, set_row, used);
     const uint64_t rows1 = std::max<uint64_t>(rows, 1), cap1 = std::max<uint64_t>(cap, 1);
     const size_t b_rows = up((size_t)rows1 * 64), b_xy = up((size_t)rows1 * 4);
     const size_t b_raw = up((size_t)cap1 * sizeof(akz_match)), b_cnt = up((size_t)n_pairs * 8), b_pts = (size_t)cap1 * 16;
@@ -500,23 +553,7 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     launch::PairJobHost* d_tab = (launch::PairJobHost*)c->mp_tab.p;
     uint32_t* d_smp[2] = {(uint32_t*)((char*)c->mp_tab.p + b_tab), (uint32_t*)((char*)c->mp_tab.p + b_tab + b_smp)};
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
-    {
-        uint8_t* h = (uint8_t*)c->mp_pin_in.p;
-        float *hx = (float*)(h + b_rows), *hy = (float*)(h + b_rows + b_xy);
-        for (uint64_t k : used) {
-            const akz_feature_set& f = sets[k];
-            uint8_t* r = h + set_row[(size_t)k] * 64;
-            for (uint64_t i = 0; i < f.n_descriptors; ++i) {
-                std::memcpy(r + i * 64, f.descriptors + i * desc_bytes, (size_t)desc_bytes);
-                if (desc_bytes < 64) std::memset(r + i * 64 + desc_bytes, 0, (size_t)(64 - desc_bytes));
-                hx[set_row[(size_t)k] + i] = f.keypoints[i].x;
-                hy[set_row[(size_t)k] + i] = f.keypoints[i].y;
-            }
-        }
-        AKZ_HIP_TRY(hipMemcpyAsync(d_rows, h, (size_t)rows * 64, hipMemcpyHostToDevice, st));
-        AKZ_HIP_TRY(hipMemcpyAsync(d_kx, hx, (size_t)rows * 4, hipMemcpyHostToDevice, st));
-        AKZ_HIP_TRY(hipMemcpyAsync(d_ky, hy, (size_t)rows * 4, hipMemcpyHostToDevice, st));
-    }
+    AKZ_TRY(pairs_upload(c, sets, used, set_row, rows, desc_bytes, b_rows, b_xy));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
     // the scans: pair p's raw list at raw_off, its count at d_cnt[cnt_idx]
     std::vector<launch::PairJobHost> tab((size_t)n_pairs);
@@ -666,14 +703,56 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
     AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_head + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
+    // the guided stage: every pair scanned again with the H that the pick kernel left on the device (pairs without one give
+    // empty lists that nobody reads); the sets are those uploaded above
+    akz_match* d_gout = nullptr;
+    if (guided) {
+        AKZ_TRY(ensure(c, c->gd_out, b_cnt + (size_t)cap1 * sizeof(akz_match)));
+        AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, b_cnt));
+        uint64_t* d_gcnt = (uint64_t*)c->gd_out.p;
+        d_gout = (akz_match*)((char*)c->gd_out.p + b_cnt);
+        std::vector<GuidedPairSpec> spec((size_t)n_pairs);
+        uint64_t off = 0;
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+            spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
+            off += sets[a].n_descriptors;
+        }
+        AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, AKZ_GUIDED_HOMOGRAPHY, d_hm, d_hf, guided->radius, 10000, guided->ratio, d_gout,
+                               d_gcnt));
+        AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_cnt.p, d_gcnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+    }
     AKZ_HIP_TRY(hipStreamSynchronize(st));
     const uint64_t* h_kcnt = (const uint64_t*)c->mp_pin_out.p;
     const akz_match* h_keep = (const akz_match*)((const char*)c->mp_pin_out.p + b_head);
+    // the guided lists of the pairs with a model: ONE read-back of the span they occupy, through pinned staging
+    const int32_t* h_found = (const int32_t*)((const char*)c->mp_pin_out.p + b_cnt + b_hm);
+    const akz_match* h_gout = nullptr;
+    if (guided) {
+        uint64_t span = 0, off = 0;
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            if (h_found[p] && ((const uint64_t*)c->gd_pin_cnt.p)[p]) span = off + ((const uint64_t*)c->gd_pin_cnt.p)[p];
+            off += sets[pairs[2 * p]].n_descriptors;
+        }
+        if (span) {
+            AKZ_TRY(ensure_pinned(c, c->gd_pin_out, (size_t)span * sizeof(akz_match)));
+            AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_out.p, d_gout, (size_t)span * sizeof(akz_match), hipMemcpyDeviceToHost, st));
+            AKZ_HIP_TRY(hipStreamSynchronize(st));
+            h_gout = (const akz_match*)c->gd_pin_out.p;
+        }
+    }
     uint64_t at = 0;
     for (uint64_t p = 0; p < n_pairs; ++p) {
         const uint64_t k = h_kcnt[p];
-        if (k) std::memcpy(out + at, h_keep + tab[(size_t)p].keep_off, (size_t)k * sizeof(akz_match));
-        n_out[p] = k;
+        const bool take_guided = guided && h_found[p] != 0;
+        if (take_guided) {  // found: the guided list replaces the filtered one
+            const uint64_t g = ((const uint64_t*)c->gd_pin_cnt.p)[p];
+            if (g) std::memcpy(out + at, h_gout + at, (size_t)g * sizeof(akz_match));
+            n_out[p] = g;
+        } else {
+            if (k) std::memcpy(out + at, h_keep + tab[(size_t)p].keep_off, (size_t)k * sizeof(akz_match));
+            n_out[p] = k;
+        }
         at += sets[pairs[2 * p]].n_descriptors;
     }
     if (Model::kModelOut) {
@@ -745,4 +824,39 @@ int akz_debug_match_pairs_split(akz_ctx* c, int enable, double* ms) {
     return AKZ_OK;
 }
 
+}  // extern "C"
+
+extern "C" {
+// the homography call, then the guided scan with the H it found (see the header): the orchestration above with its last stage
+int akz_match_features_homography_guided_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                               uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                               float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio, akz_match* out,
+                                               uint64_t* n_out, float* h, int* found) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                             out, n_out, h, found, &g);
+}
+int akz_match_features_homography_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                         const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                         double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, float guided_radius,
+                                         double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* h, int* found) {
+    if (!n_out) {
+        set_error("match_features_homography_guided: null n_out");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
+        set_error("match_features_homography_guided: a feature set has more descriptors than keypoints");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
+    const uint64_t pair[2] = {0, 1};
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    int fnd = 0;
+    float hm[9];
+    AKZ_TRY(match_pairs_impl<HomographyModel>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out,
+                                              hm, &fnd, &g));
+    if (found) *found = fnd;
+    if (h && fnd) std::memcpy(h, hm, sizeof(hm));
+    return AKZ_OK;
+}
 }  // extern "C"

@@ -223,6 +223,13 @@ def lib():
         "akz_match_features_homography": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp,
                                            C.POINTER(i32)], i32),
         "akz_match_features_homography_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
+        "akz_descriptor_match_guided_host": ([vp, u64, vp, u64, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
+        "akz_descriptor_match_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
+        "akz_descriptor_match_guided_pairs": ([vp, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
+        "akz_match_features_homography_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp,
+                                                  pu64, fp, C.POINTER(i32)], i32),
+        "akz_match_features_homography_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp, pu64, fp,
+                                                        C.POINTER(i32)], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
@@ -365,6 +372,47 @@ def synth_frame(w, h, frame_index=0, shift=(0, 0)):
     out = np.empty((h, w), np.uint8)
     _check(lib().akz_synth_frame_u8(out.ctypes.data_as(C.c_void_p), w, h, frame_index, shift[0], shift[1]))
     return out
+
+
+class _PairsArgs:
+    """What the pairs calls share: the akz_feature_set array, the pair list and the outputs (head: ctx, sets, n_sets, pairs,
+    n_pairs, desc_bytes; tail: out, n_out), and the split of `out` into one list per pair afterwards."""
+
+    def __init__(self, ctx, features, pairs):
+        self.ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
+        self.ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
+        nbs = {d.shape[1] for d in self.ds if d.ndim == 2 and len(d)}
+        if len(nbs) > 1:
+            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
+        nb = nbs.pop() if nbs else 61
+        self.sets = (FeatureSet * max(1, len(self.ks)))()
+        for i, (k, d) in enumerate(zip(self.ks, self.ds)):
+            nd = len(d) if d.ndim == 2 else 0
+            self.sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k),
+                                      d.ctypes.data_as(C.c_void_p) if nd else None, nd)
+        self.pr = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+        if len(self.ks) == 0 and len(self.pr):
+            raise IndexError("pair refers to a set that does not exist")
+        self.rows = [len(self.ds[int(a)]) if self.ds[int(a)].ndim == 2 else 0 for a in self.pr[:, 0]] if len(self.ks) else []
+        self.out = np.zeros(max(1, sum(self.rows)), MATCH_DTYPE)
+        self.n = np.zeros(max(1, len(self.pr)), np.uint64)
+        self.head = (ctx._h, C.cast(self.sets, C.c_void_p), len(self.ks), self.pr.ctypes.data_as(C.c_void_p), len(self.pr), nb)
+        self.tail = (self.out.ctypes.data_as(C.c_void_p), self.n.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def models(self):
+        self.h = np.zeros((max(1, len(self.pr)), 9), np.float32)
+        self.found = np.zeros(max(1, len(self.pr)), np.int32)
+        return self.h.ctypes.data_as(C.POINTER(C.c_float)), self.found.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def lists(self):
+        res, at = [], 0
+        for p, r in enumerate(self.rows):
+            res.append(self.out[at:at + int(self.n[p])].copy())
+            at += r
+        return res
+
+    def lists_and_models(self):
+        return [(m, self.h[p].reshape(3, 3).copy() if self.found[p] else None) for p, m in enumerate(self.lists())]
 
 
 # ------------------------------------------------------------------------------------------
@@ -681,47 +729,43 @@ class Context:
         (keypoints, descriptors) arrays (KEYPOINT_DTYPE / uint8 [n, desc_bytes]), pairs a sequence of (first, second) indices
         into it.  Returns one MATCH_DTYPE array per pair, each equal to what match_features returns for that pair when the
         pairs are matched in order on this thread."""
-        return self._pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, False)
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers, *a.tail))
+        return a.lists()
 
     def match_features_homography_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
         """match_features_homography over many pairs in one call (akz_match_features_homography_pairs), arguments as for
         match_features_pairs.  Returns one (matches, H or None) per pair, each equal to what match_features_homography returns
         for that pair when the pairs are matched in order on this thread."""
-        return self._pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, True)
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_homography_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers, *a.tail,
+                                                         *a.models()))
+        return a.lists_and_models()
 
-    def _pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, homography):
-        ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
-        ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
-        nbs = {d.shape[1] for d in ds if d.ndim == 2 and len(d)}
-        if len(nbs) > 1:
-            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
-        nb = nbs.pop() if nbs else 61
-        sets = (FeatureSet * max(1, len(ks)))()
-        for i, (k, d) in enumerate(zip(ks, ds)):
-            nd = len(d) if d.ndim == 2 else 0
-            sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k),
-                                 d.ctypes.data_as(C.c_void_p) if nd else None, nd)
-        pr = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
-        rows = [len(ds[int(a)]) if ds[int(a)].ndim == 2 else 0 for a in pr[:, 0]] if len(ks) else []
-        if len(ks) == 0 and len(pr):
-            raise IndexError("pair refers to a set that does not exist")
-        out = np.zeros(max(1, sum(rows)), MATCH_DTYPE)
-        n = np.zeros(max(1, len(pr)), np.uint64)
-        args = (self._h, C.cast(sets, C.c_void_p), len(ks), pr.ctypes.data_as(C.c_void_p), len(pr), nb, lowes_ratio, ransac_trials,
-                ransac_epsilon_inliers, out.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.POINTER(C.c_uint64)))
-        if homography:
-            h = np.zeros((max(1, len(pr)), 9), np.float32)
-            found = np.zeros(max(1, len(pr)), np.int32)
-            _check(lib().akz_match_features_homography_pairs(*args, h.ctypes.data_as(C.POINTER(C.c_float)),
-                                                             found.ctypes.data_as(C.POINTER(C.c_int32))))
-        else:
-            _check(lib().akz_match_features_pairs(*args))
-        res, at = [], 0
-        for p, r in enumerate(rows):
-            m = out[at:at + int(n[p])].copy()
-            res.append((m, h[p].reshape(3, 3).copy() if found[p] else None) if homography else m)
-            at += r
-        return res
+    def match_features_homography_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                               guided_radius, guided_lowes_ratio):
+        """match_features_homography_pairs, then the guided scan with every H found
+        (akz_match_features_homography_guided_pairs).  Returns one (matches, H or None) per pair: with an H the list of
+        descriptor_match_guided(pair, GUIDED_HOMOGRAPHY, H, guided_radius, 10000, guided_lowes_ratio), without one the list
+        of match_features_homography_pairs."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_homography_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                                guided_radius, guided_lowes_ratio, *a.tail, *a.models()))
+        return a.lists_and_models()
+
+    def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
+        """Guided matching over many pairs in one call (akz_descriptor_match_guided_pairs): features and pairs as for
+        match_features_pairs, models one 3x3 (or 9) float32 model per pair, kind GUIDED_HOMOGRAPHY or GUIDED_FUNDAMENTAL.
+        Returns one MATCH_DTYPE array per pair, each equal to descriptor_match_guided on that pair."""
+        a = _PairsArgs(self, features, pairs)
+        md = np.ascontiguousarray(np.asarray(models, np.float32).reshape(-1, 9))
+        if len(md) != len(a.pr):
+            raise ValueError(f"{len(a.pr)} pairs but {len(md)} models")
+        if len(md) == 0:
+            md = np.zeros((1, 9), np.float32)
+        _check(lib().akz_descriptor_match_guided_pairs(*a.head, int(kind), md.ctypes.data_as(C.POINTER(C.c_float)), radius,
+                                                       distance_threshold, lowes_ratio, *a.tail))
+        return a.lists()
 
     def descriptor_match_sets_device(self, q, train, rows, distance_threshold=10000, lowes_ratio=0.86):
         """One query set against several train sets in one launch: q [n0, 64] uint8 CUDA tensor, train the sets'
@@ -1300,6 +1344,87 @@ def match_features_homography_pairs(features, pairs, lowes_ratio, ransac_trials,
     """Context.match_features_homography_pairs on ctx (default: the default context)."""
     return (ctx or default_context()).match_features_homography_pairs(features, pairs, lowes_ratio, ransac_trials,
                                                                       ransac_epsilon_inliers)
+
+
+# ---- guided matching (an addition; include/akaze_hip.h, DESIGN.md 8) -------------------------------------------------------
+GUIDED_HOMOGRAPHY = 0   # AKZ_GUIDED_HOMOGRAPHY: the model is H, the gate a disc around the transferred point
+GUIDED_FUNDAMENTAL = 1  # AKZ_GUIDED_FUNDAMENTAL: the model is F, the gate a band around the epipolar line
+
+
+def _guided_pair(fn, first, keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind, radius, distance_threshold,
+                 lowes_ratio):
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
+    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
+    n0 = len(d0) if d0.ndim == 2 else 0
+    n1 = len(d1) if d1.ndim == 2 else 0
+    nb0 = d0.shape[1] if n0 else None
+    nb1 = d1.shape[1] if n1 else None
+    if nb0 is not None and nb1 is not None and nb0 != nb1:
+        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
+    md = np.ascontiguousarray(np.asarray(model, np.float32).reshape(9))
+    out = np.zeros(max(1, n0), MATCH_DTYPE)
+    n = C.c_uint64()
+    _check(fn(*first, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), n0, k1.ctypes.data_as(C.c_void_p), len(k1),
+              d1.ctypes.data_as(C.c_void_p), n1, nb0 or nb1 or 61, int(kind), md.ctypes.data_as(C.POINTER(C.c_float)), radius,
+              distance_threshold, lowes_ratio, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def descriptor_match_guided_host(keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind, radius,
+                                 distance_threshold=10000, lowes_ratio=0.86):
+    """descriptor_match in which descriptor j of set 1 competes for descriptor i of set 0 only if keypoint j lies within
+    `radius` pixels of where the model sends keypoint i (kind GUIDED_HOMOGRAPHY: model = H, the transferred point;
+    GUIDED_FUNDAMENTAL: model = F, the epipolar line).  The plain host statement (akz_descriptor_match_guided_host)."""
+    return _guided_pair(lib().akz_descriptor_match_guided_host, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind,
+                        radius, distance_threshold, lowes_ratio)
+
+
+def descriptor_match_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind, radius, distance_threshold=10000,
+                            lowes_ratio=0.86, ctx=None):
+    """descriptor_match_guided_host on the GPU (akz_descriptor_match_guided): the same list, bit for bit."""
+    c = ctx or default_context()
+    return _guided_pair(lib().akz_descriptor_match_guided, (c._h,), keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind,
+                        radius, distance_threshold, lowes_ratio)
+
+
+def descriptor_match_guided_pairs(features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86, ctx=None):
+    """Context.descriptor_match_guided_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).descriptor_match_guided_pairs(features, pairs, models, kind, radius, distance_threshold,
+                                                                    lowes_ratio)
+
+
+def match_features_homography_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                                     ransac_epsilon_inliers, guided_radius, guided_lowes_ratio, ctx=None):
+    """match_features_homography, then the guided scan with the H it found (akz_match_features_homography_guided) ->
+    (matches, H or None): with an H the guided list, without one the list of match_features_homography."""
+    c = ctx or default_context()
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
+    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
+    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
+    n = C.c_uint64()
+    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
+    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
+    if nb0 is not None and nb1 is not None and nb0 != nb1:
+        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
+    h = np.zeros(9, np.float32)
+    found = C.c_int()
+    _check(lib().akz_match_features_homography_guided(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p),
+                                                      len(d0), k1.ctypes.data_as(C.c_void_p), len(k1), d1.ctypes.data_as(C.c_void_p),
+                                                      len(d1), nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                      guided_radius, guided_lowes_ratio, out.ctypes.data_as(C.c_void_p), C.byref(n),
+                                                      h.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
+    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+
+
+def match_features_homography_guided_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, guided_radius,
+                                           guided_lowes_ratio, ctx=None):
+    """Context.match_features_homography_guided_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_homography_guided_pairs(features, pairs, lowes_ratio, ransac_trials,
+                                                                             ransac_epsilon_inliers, guided_radius, guided_lowes_ratio)
 
 
 # ------------------------------------------------------------------------------------------

@@ -571,6 +571,63 @@ int akz_match_features_homography_pairs(akz_ctx* ctx, const akz_feature_set* set
                                         float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out /* n_pairs */,
                                         float* h /* 9 x n_pairs */, int* found /* n_pairs */);
 
+/* ---- guided matching (an addition: the reference matches a pair once, blind) -----------------------------------------
+   descriptor_match (feature_matching.rs:37-81) repeated once a model of the pair is known: a train row j competes for a
+   query i only if it lies within `radius` pixels of where the model sends keypoint i -- minimum, second minimum, the lowest
+   index among equal minima, ratio and threshold are taken over those rows alone.  The ratio test of the blind scan compares
+   with the second best of the WHOLE other image, which repeated structure fails although the geometry leaves one candidate.
+   model_kind AKZ_GUIDED_HOMOGRAPHY: model = H, row-major, image 0 onto image 1; the gate is the inlier test of the
+   homography RANSAC above, w > 0 and (U - x1 w)^2 + (V - y1 w)^2 < (radius w)^2 in f32 in that order.
+   model_kind AKZ_GUIDED_FUNDAMENTAL: model = F, row-major, with p1^T F p0 = 0 (the convention of
+   akz_estimate_fundamental_matrix); the gate is the distance of (x1, y1) to the epipolar line of (x0, y0) in PIXELS --
+   l_r = (f[3r] x0 + f[3r+1] y0) + f[3r+2], n = l0 l0 + l1 l1, s = (l0 x1 + l1 y1) + l2, passes iff s s < (radius radius) n,
+   in f32 in that order -- and not the algebraic |p1^T F p0| < epsilon of akz_remove_outliers.
+   Both comparisons are strict: radius 0, F = 0 or a NaN pass nothing.  Model entries are not checked.  Host and GPU form
+   the gate from one source without contraction: the same bits.
+   Only x and y of the first n_descriptors keypoints of a set are read.  Both distances start at distance_threshold (values
+   above 2^31 - 1 count as that); a query is kept iff (double)min < (double)second * lowes_ratio^2 and min < threshold; the
+   list is in index_0 order, index_1 indexes the whole second set.  Every byte of a row is compared (desc_bytes 1..64).
+   Refusals (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written): those of akz_match_features(_pairs), a model_kind
+   other than these two, a NULL model, a radius that is negative or not finite.  n_pairs = 0 and empty sets are AKZ_OK. */
+#define AKZ_GUIDED_HOMOGRAPHY 0
+#define AKZ_GUIDED_FUNDAMENTAL 1
+/* The plain host statement (no GPU call): the loop of feature_matching.rs with the gate at the top of the inner loop. */
+int akz_descriptor_match_guided_host(const akz_keypoint* keypoints_0, uint64_t n_keypoints_0, const uint8_t* descriptors_0,
+                                     uint64_t n_descriptors_0, const akz_keypoint* keypoints_1, uint64_t n_keypoints_1,
+                                     const uint8_t* descriptors_1, uint64_t n_descriptors_1, uint64_t desc_bytes, int model_kind,
+                                     const float* model /* 9 */, float radius, uint64_t distance_threshold, double lowes_ratio,
+                                     akz_match* out /* n_descriptors_0 */, uint64_t* n_out);
+/* The same list from the GPU (the pairs call below with one pair). */
+int akz_descriptor_match_guided(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0, const uint8_t* descriptors_0,
+                                uint64_t n_descriptors_0, const akz_keypoint* keypoints_1, uint64_t n_keypoints_1,
+                                const uint8_t* descriptors_1, uint64_t n_descriptors_1, uint64_t desc_bytes, int model_kind,
+                                const float* model /* 9 */, float radius, uint64_t distance_threshold, double lowes_ratio,
+                                akz_match* out /* n_descriptors_0 */, uint64_t* n_out);
+/* Many pairs in one call, each with its own model (models + 9 p); sets, pairs, the layout of out and the room per pair are
+   those of akz_match_features_pairs.  Each distinct set is uploaded once, all pairs are scanned by one launch; pair p's list
+   is what akz_descriptor_match_guided returns for that pair, bit for bit. */
+int akz_descriptor_match_guided_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                      uint64_t n_pairs, uint64_t desc_bytes, int model_kind, const float* models /* 9 x n_pairs */,
+                                      float radius, uint64_t distance_threshold, double lowes_ratio, akz_match* out,
+                                      uint64_t* n_out /* n_pairs */);
+/* akz_match_features_homography(_pairs) followed by the guided scan with the H it found: per pair exactly what the
+   homography call does (same draws, same H, same found); where found = 1 the returned list is
+   akz_descriptor_match_guided(pair, AKZ_GUIDED_HOMOGRAPHY, H, guided_radius, 10000, guided_lowes_ratio), where found = 0 it
+   is the homography call's list unchanged.  H stays on the device between the two stages and the sets are uploaded once.
+   With guided_radius = ransac_epsilon_inliers and guided_lowes_ratio = lowes_ratio the guided list contains every match the
+   homography call keeps (same index_1, same distance). */
+int akz_match_features_homography_guided(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                         const uint8_t* descriptors_0, uint64_t n_descriptors_0, const akz_keypoint* keypoints_1,
+                                         uint64_t n_keypoints_1, const uint8_t* descriptors_1, uint64_t n_descriptors_1,
+                                         uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                         float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio,
+                                         akz_match* out, uint64_t* n_out, float* h /* 9 */, int* found);
+int akz_match_features_homography_guided_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                               uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                               float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio,
+                                               akz_match* out, uint64_t* n_out /* n_pairs */, float* h /* 9 x n_pairs */,
+                                               int* found /* n_pairs */);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly
