@@ -494,6 +494,10 @@ struct GuidedStage {  // the second stage of akz_match_features_homography_guide
     float radius;
     double ratio;
 };
+struct RefineStage {  // the refit stage of akz_match_features_homography_refined(_pairs): launch::homography_refit after the pick
+    uint32_t max_iterations;
+    uint32_t* iterations;  // one per pair, may be null
+};
 AKZ_LOCAL int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs,
                             const std::vector<uint8_t>& seen);
 AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,

@@ -48,15 +48,21 @@ AKZ_HD bool jacobi_pair(M& m, int p, int q) {
     }
     return true;
 }
-// sweeps over the pairs in row-cyclic order (0,1) (0,2) .. (0,7) (1,2) .. (6,7) until one leaves every pair alone
-template <class M>
-AKZ_HD void jacobi_sweeps(M& m) {
+// sweeps over the pairs of the first ROWS rows in row-cyclic order (0,1) (0,2) .. (0,ROWS-1) (1,2) .. until one leaves every
+// pair alone
+template <int ROWS, class M>
+AKZ_HD void jacobi_sweeps_rows(M& m) {
     for (int sweep = 0; sweep < 60; ++sweep) {
         bool rotated = false;
-        for (int p = 0; p < 8; ++p)
-            for (int q = p + 1; q < 8; ++q) rotated = jacobi_pair(m, p, q) || rotated;
+        for (int p = 0; p < ROWS; ++p)
+            for (int q = p + 1; q < ROWS; ++q) rotated = jacobi_pair(m, p, q) || rotated;
         if (!rotated) break;
     }
+}
+// the 8 x 9 design matrices of the trial models
+template <class M>
+AKZ_HD void jacobi_sweeps(M& m) {
+    jacobi_sweeps_rows<8>(m);
 }
 // after the sweeps: index of the smallest singular value (row norm); *full_rank = all eight exceed epsilon (as f32)
 template <class M>

@@ -86,13 +86,11 @@ AKZ_HD void hom_rows(M& m, int i, double x, double y, double u, double v) {
     }
 }
 
-// the model from the rotated matrix and the normalisation (c0, s0, c1, s1); false: rank < 8 at `epsilon` or H[8] ~ 0
+// the model from 8 orthogonal rows (rows 0..7 of m, all of norm > 0) and the normalisation (c0, s0, c1, s1): the null-vector
+// projection, the denormalisation, the H[8] rule and the rounding to f32; false: H[8] ~ 0.  Shared by the trial model below
+// and by the refit on the inliers (akz_homography_refit.hpp).
 template <class M>
-AKZ_HD bool hom_model_from_rotated(M& m, float epsilon, double c0x, double c0y, double s0, double c1x, double c1y, double s1,
-                                   float (&h)[9]) {
-    bool full = false;
-    (void)smallest_singular(m, epsilon, &full);
-    if (!full) return false;
+AKZ_HD bool hom_model_from_rows(M& m, double c0x, double c0y, double s0, double c1x, double c1y, double s1, float (&h)[9]) {
     // (row by row, the row reloaded per k: the device keeps one row in registers instead of the whole matrix)
     double best[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, best_n = -1.0;
     AKZ_NOUNROLL
@@ -152,6 +150,16 @@ AKZ_HD bool hom_model_from_rotated(M& m, float epsilon, double c0x, double c0y, 
     AKZ_UNROLL
     for (int j = 0; j < 9; ++j) h[j] = (float)(H[j] / H[8]);
     return true;
+}
+
+// the model from the rotated matrix and the normalisation (c0, s0, c1, s1); false: rank < 8 at `epsilon` or H[8] ~ 0
+template <class M>
+AKZ_HD bool hom_model_from_rotated(M& m, float epsilon, double c0x, double c0y, double s0, double c1x, double c1y, double s1,
+                                   float (&h)[9]) {
+    bool full = false;
+    (void)smallest_singular(m, epsilon, &full);
+    if (!full) return false;
+    return hom_model_from_rows(m, c0x, c0y, s0, c1x, c1y, s1, h);
 }
 
 // x0, y0 from keypoints_0 and x1, y1 from keypoints_1 of the four sampled matches -> H (row-major, H[8] = 1)

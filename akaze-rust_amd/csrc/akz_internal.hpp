@@ -385,6 +385,12 @@ void homography_trials(hipStream_t s, const PairJobHost* d_pairs, const uint32_t
 void homography_pick_filter(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                             const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float epsilon_inlier,
                             void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found);
+// the refit stage after homography_pick_filter (akz_homography_refit.hip): per pair with found = 1 and 4 matches or more, the
+// loop of akz_homography_refit.hpp on the raw list from the H at d_h + 9 pair; after an accepted fit H, the kept list and its
+// count are rewritten; d_iterations[pair] = accepted fits (0 for the pairs left alone)
+void homography_refit(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                      const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
+                      void* d_keep, uint64_t* d_keep_cnt, float* d_h, const int32_t* d_found, uint32_t* d_iterations);
 void unpack_pair(hipStream_t s, const uint8_t* dq, uint32_t nq, uint32_t q_pad, uint8_t* outq, uint32_t* popq, uint32_t* bound, uint32_t threshold,
                  const uint8_t* dt, uint32_t nt, uint32_t t_pad, uint8_t* outt, uint32_t* popt, bool fp4);
 uint32_t match_mfma_tile_rows();

@@ -510,11 +510,13 @@ struct HomographyModel {  // akz_match_features_homography(_pairs): k_homography
 // keypoint x / y through pinned staging; the descriptor scans (one multi-set launch per first set, or the pair matcher for
 // rows of 62..64 bytes); k_pair_points; ONE read-back of the match counts; the samples drawn on the calling thread in pair
 // order, in chunks whose trials (Model::trials) run while the next chunk is drawn; Model::pick_filter; ONE read-back of the
-// kept lists (and, for a model that is handed back, every pair's model and found flag).
+// kept lists (and, for a model that is handed back, every pair's model and found flag).  A RefineStage puts the refit kernel
+// between the pick and that read-back: it rewrites H, the kept lists and their counts in place and adds every pair's number of
+// accepted fits to the head that the read-back carries; the guided stage then reads the H table it has rewritten.
 template <class Model>
 int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
                      double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out, float* model_out,
-                     int* found_out, const GuidedStage* guided = nullptr) {
+                     int* found_out, const GuidedStage* guided = nullptr, const RefineStage* refine = nullptr) {
     constexpr int K = Model::K;
     if (n_pairs == 0) return AKZ_OK;
     if (guided && !(guided->radius >= 0.0f && std::isfinite(guided->radius))) {
@@ -631,7 +633,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     const size_t b_mdl = up((size_t)std::max<uint64_t>(n_trials, 1) * 36), b_inl = up((size_t)std::max<uint64_t>(n_trials, 1) * 4);
     // (a model handed back: every pair's 9 floats and found flag between the counts and the kept lists)
     const size_t b_hm = Model::kModelOut ? up((size_t)n_pairs * 36) : 0, b_hf = Model::kModelOut ? up((size_t)n_pairs * 4) : 0;
-    const size_t b_head = b_cnt + b_hm + b_hf;
+    const size_t b_it = Model::kModelOut && refine ? up((size_t)n_pairs * 4) : 0;
+    const size_t b_head = b_cnt + b_hm + b_hf + b_it;
     const size_t b_keep = b_head + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
     AKZ_TRY(ensure(c, c->mp_trials, b_mdl + b_inl));
     AKZ_TRY(ensure(c, c->mp_keep, b_keep));
@@ -645,6 +648,7 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     uint64_t* d_kcnt = (uint64_t*)c->mp_keep.p;
     float* d_hm = (float*)((char*)c->mp_keep.p + b_cnt);
     int32_t* d_hf = (int32_t*)((char*)c->mp_keep.p + b_cnt + b_hm);
+    uint32_t* d_it = (uint32_t*)((char*)c->mp_keep.p + b_cnt + b_hm + b_hf);
     akz_match* d_keep = (akz_match*)((char*)c->mp_keep.p + b_head);
     for (uint64_t p = 0; p < n_pairs; ++p)  // (n_trials of the table: the pair's trials, for the pick)
         if (h_cnt[tab[(size_t)p].cnt_idx] >= (uint64_t)K) tab[(size_t)p].n_trials = ransac_trials;
@@ -700,6 +704,11 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     }
     Model::pick_filter(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep, d_kcnt, d_hm, d_hf);
     AKZ_HIP_TRY(hipGetLastError());
+    if (Model::kModelOut && refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
+        launch::homography_refit(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, Model::kEpsilonModel, ransac_epsilon_inliers,
+                                 refine->max_iterations, d_keep, d_kcnt, d_hm, d_hf, d_it);
+        AKZ_HIP_TRY(hipGetLastError());
+    }
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
     AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_head + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
@@ -761,6 +770,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         if (model_out) std::memcpy(model_out, h_hm, (size_t)n_pairs * 36);
         if (found_out)
             for (uint64_t p = 0; p < n_pairs; ++p) found_out[p] = h_hf[p];
+        if (refine && refine->iterations)
+            std::memcpy(refine->iterations, (const char*)c->mp_pin_out.p + b_cnt + b_hm + b_hf, (size_t)n_pairs * 4);
     }
     if (timed) {
         float ms[6] = {};
@@ -858,5 +869,75 @@ int akz_match_features_homography_guided(akz_ctx* c, const akz_keypoint* kp0, ui
     if (found) *found = fnd;
     if (h && fnd) std::memcpy(h, hm, sizeof(hm));
     return AKZ_OK;
+}
+}  // extern "C"
+
+extern "C" {
+// the homography calls with the refit stage between the pick and the read-back (see the header)
+int akz_match_features_homography_refined_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out, uint64_t* n_out,
+                                                float* h, int* found, uint32_t* iterations) {
+    const RefineStage r{refine_iterations, iterations};
+    return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                             out, n_out, h, found, nullptr, &r);
+}
+int akz_match_features_homography_refined_guided_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                       uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                       float ransac_epsilon_inliers, uint32_t refine_iterations, float guided_radius,
+                                                       double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* h, int* found,
+                                                       uint32_t* iterations) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    const RefineStage r{refine_iterations, iterations};
+    return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                             out, n_out, h, found, &g, &r);
+}
+}  // extern "C"
+namespace {
+// one pair: the pairs call with sets {0, 1} and the pair (0, 1)
+int refined_single(const char* name, akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                   const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, double lowes_ratio,
+                   uint64_t ransac_trials, float ransac_epsilon_inliers, uint32_t refine_iterations, const GuidedStage* g, akz_match* out,
+                   uint64_t* n_out, float* h, int* found, uint32_t* iterations) {
+    if (!n_out) {
+        set_error(std::string(name) + "null n_out");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
+        set_error(std::string(name) + "a feature set has more descriptors than keypoints");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
+    const uint64_t pair[2] = {0, 1};
+    int fnd = 0;
+    float hm[9];
+    uint32_t it = 0;
+    const RefineStage r{refine_iterations, &it};
+    AKZ_TRY(match_pairs_impl<HomographyModel>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out,
+                                              hm, &fnd, g, &r));
+    if (found) *found = fnd;
+    if (h && fnd) std::memcpy(h, hm, sizeof(hm));
+    if (iterations) *iterations = it;
+    return AKZ_OK;
+}
+}  // namespace
+extern "C" {
+int akz_match_features_homography_refined(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                          const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                          double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                          uint32_t refine_iterations, akz_match* out, uint64_t* n_out, float* h, int* found,
+                                          uint32_t* iterations) {
+    return refined_single("match_features_homography_refined: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
+                          ransac_trials, ransac_epsilon_inliers, refine_iterations, nullptr, out, n_out, h, found, iterations);
+}
+int akz_match_features_homography_refined_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                                 const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1,
+                                                 uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                 float ransac_epsilon_inliers, uint32_t refine_iterations, float guided_radius,
+                                                 double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* h, int* found,
+                                                 uint32_t* iterations) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    return refined_single("match_features_homography_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
+                          ransac_trials, ransac_epsilon_inliers, refine_iterations, &g, out, n_out, h, found, iterations);
 }
 }  // extern "C"

@@ -34,6 +34,7 @@
 
 #include "akz_fmatrix.hpp"
 #include "akz_homography.hpp"
+#include "akz_homography_refit.hpp"
 #include "akz_internal.hpp"
 #include "akz_pool.hpp"
 
@@ -380,6 +381,107 @@ extern "C" int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, u
         if (found) *found = 1;
     }
     *n_out = k;
+    return AKZ_OK;
+}
+
+// ---- the refit of a homography on its inliers (akz_homography_refit.hpp) ---------------------------------------
+namespace {
+// the sums of the members' terms in the documented order: lane i mod 256, ascending i from +0.0, then the tree
+template <int K, class Term>
+void lane_tree_sums(uint64_t n, const std::vector<uint8_t>& member, Term term, double (&out)[K]) {
+    static thread_local double p[K][kRefitLanes];
+    for (int k = 0; k < K; ++k)
+        for (int l = 0; l < kRefitLanes; ++l) p[k][l] = 0.0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!member[(size_t)i]) continue;
+        double t[K];
+        term(i, t);
+        for (int k = 0; k < K; ++k) p[k][i % kRefitLanes] = p[k][i % kRefitLanes] + t[k];
+    }
+    for (int k = 0; k < K; ++k) {
+        for (int s = kRefitLanes / 2; s > 0; s >>= 1)
+            for (int l = 0; l < s; ++l) p[k][l] = p[k][l] + p[k][l + s];
+        out[k] = p[k][0];
+    }
+}
+// fit(S) of the statement; false: no model
+bool refit_on_members(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const std::vector<uint8_t>& member,
+                      uint64_t count, float (&h)[9]) {
+    if (count < 4) return false;
+    const double cnt = (double)count;
+    double s1sum[4], s2sum[2], s3sum[kRefitSums3];
+    lane_tree_sums<4>(n, member, [&](uint64_t i, double (&t)[4]) { refit_terms1(x0[i], y0[i], x1[i], y1[i], t); }, s1sum);
+    const double c0x = s1sum[0] / cnt, c0y = s1sum[1] / cnt, c1x = s1sum[2] / cnt, c1y = s1sum[3] / cnt;
+    lane_tree_sums<2>(n, member, [&](uint64_t i, double (&t)[2]) { refit_terms2(x0[i], y0[i], x1[i], y1[i], c0x, c0y, c1x, c1y, t); }, s2sum);
+    double s0 = 0.0, s1 = 0.0;
+    if (!refit_scale(s2sum[0], cnt, s0) || !refit_scale(s2sum[1], cnt, s1)) return false;
+    lane_tree_sums<kRefitSums3>(
+        n, member, [&](uint64_t i, double (&t)[kRefitSums3]) { refit_terms3(x0[i], y0[i], x1[i], y1[i], c0x, c0y, s0, c1x, c1y, s1, t); },
+        s3sum);
+    Mat9x9 m;
+    refit_normal_matrix(m, s3sum);
+    return refit_model_from_normal(m, cnt, AKZ_HOMOGRAPHY_EPSILON_MODEL, c0x, c0y, s0, c1x, c1y, s1, h);
+}
+uint64_t classify(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const float (&h)[9], float eps,
+                  std::vector<uint8_t>& member) {
+    uint64_t c = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        member[(size_t)i] = homography_inlier(h, x0[i], y0[i], x1[i], y1[i], eps) ? 1 : 0;
+        c += member[(size_t)i];
+    }
+    return c;
+}
+}  // namespace
+
+extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                     const akz_match* matches, uint64_t n_matches, const float* h_in, float epsilon_inlier,
+                                     uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* h_out, uint32_t* iterations) {
+    if (!n_out || (n_matches && (!matches || !out))) {
+        set_error("refine_homography: null pointer");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    if (!h_in) {
+        set_error("refine_homography: null h_in");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    if (!(epsilon_inlier > 0.0f && std::isfinite(epsilon_inlier))) {
+        set_error("refine_homography: epsilon_inlier must be finite and > 0");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n_matches; ++i)
+        if (matches[i].index_0 >= n0 || matches[i].index_1 >= n1 || !keypoints_0 || !keypoints_1) {
+            set_error("refine_homography: match index out of range");
+            return AKZ_ERR_INVALID_ARG;
+        }
+    std::vector<float> px0((size_t)n_matches), py0((size_t)n_matches), px1((size_t)n_matches), py1((size_t)n_matches);
+    for (uint64_t i = 0; i < n_matches; ++i) {
+        px0[(size_t)i] = keypoints_0[matches[i].index_0].x; py0[(size_t)i] = keypoints_0[matches[i].index_0].y;
+        px1[(size_t)i] = keypoints_1[matches[i].index_1].x; py1[(size_t)i] = keypoints_1[matches[i].index_1].y;
+    }
+    const float *x0 = px0.data(), *y0 = py0.data(), *x1 = px1.data(), *y1 = py1.data();
+    float h[9];
+    std::memcpy(h, h_in, sizeof(h));
+    std::vector<uint8_t> member((size_t)n_matches), next((size_t)n_matches);
+    uint64_t count = classify(x0, y0, x1, y1, n_matches, h, epsilon_inlier, member);
+    uint32_t done = 0;
+    while (done < max_iterations) {
+        float h2[9];
+        if (!refit_on_members(x0, y0, x1, y1, n_matches, member, count, h2)) break;
+        const uint64_t count2 = classify(x0, y0, x1, y1, n_matches, h2, epsilon_inlier, next);
+        if (count2 < count) break;
+        const bool grew = count2 > count;
+        std::memcpy(h, h2, sizeof(h));
+        member.swap(next);
+        count = count2;
+        ++done;
+        if (!grew) break;
+    }
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < n_matches; ++i)
+        if (member[(size_t)i]) out[k++] = matches[i];
+    *n_out = k;
+    if (h_out) std::memcpy(h_out, h, sizeof(h));
+    if (iterations) *iterations = done;
     return AKZ_OK;
 }
 

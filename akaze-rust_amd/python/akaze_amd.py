@@ -223,6 +223,15 @@ def lib():
         "akz_match_features_homography": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp,
                                            C.POINTER(i32)], i32),
         "akz_match_features_homography_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
+        "akz_refine_homography": ([vp, u64, vp, u64, vp, u64, fp, C.c_float, C.c_uint32, vp, pu64, fp, C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_homography_refined": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64,
+                                                   fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_homography_refined_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64, fp,
+                                                         C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_homography_refined_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32,
+                                                          C.c_float, f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_homography_refined_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, C.c_float, f64,
+                                                                vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
         "akz_descriptor_match_guided_host": ([vp, u64, vp, u64, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_guided_pairs": ([vp, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
@@ -413,6 +422,13 @@ class _PairsArgs:
 
     def lists_and_models(self):
         return [(m, self.h[p].reshape(3, 3).copy() if self.found[p] else None) for p, m in enumerate(self.lists())]
+
+    def refined(self):
+        self.it = np.zeros(max(1, len(self.pr)), np.uint32)
+        return (*self.models(), self.it.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    def lists_models_iterations(self):
+        return [(m, h, int(self.it[p])) for p, (m, h) in enumerate(self.lists_and_models())]
 
 
 # ------------------------------------------------------------------------------------------
@@ -752,6 +768,26 @@ class Context:
         _check(lib().akz_match_features_homography_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                                 guided_radius, guided_lowes_ratio, *a.tail, *a.models()))
         return a.lists_and_models()
+
+    def match_features_homography_refined_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                refine_iterations):
+        """match_features_homography_pairs with the refit of every H found on its inliers
+        (akz_match_features_homography_refined_pairs).  Returns one (matches, H or None, accepted fits) per pair, each equal
+        to what match_features_homography_refined returns for that pair when the pairs are matched in order on this thread."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_homography_refined_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                                 refine_iterations, *a.tail, *a.refined()))
+        return a.lists_models_iterations()
+
+    def match_features_homography_refined_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                       refine_iterations, guided_radius, guided_lowes_ratio):
+        """match_features_homography_refined_pairs, then the guided scan with every REFINED H
+        (akz_match_features_homography_refined_guided_pairs).  Returns one (matches, H or None, accepted fits) per pair."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_homography_refined_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                                        refine_iterations, guided_radius, guided_lowes_ratio, *a.tail,
+                                                                        *a.refined()))
+        return a.lists_models_iterations()
 
     def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
         """Guided matching over many pairs in one call (akz_descriptor_match_guided_pairs): features and pairs as for
@@ -1425,6 +1461,81 @@ def match_features_homography_guided_pairs(features, pairs, lowes_ratio, ransac_
     """Context.match_features_homography_guided_pairs on ctx (default: the default context)."""
     return (ctx or default_context()).match_features_homography_guided_pairs(features, pairs, lowes_ratio, ransac_trials,
                                                                              ransac_epsilon_inliers, guided_radius, guided_lowes_ratio)
+
+
+# ---- the refit of the RANSAC homography on its inliers (an addition; include/akaze_hip.h, DESIGN.md 8) ---------------------
+def refine_homography(keypoints_0, keypoints_1, matches, h, epsilon_inlier, max_iterations):
+    """Local optimisation of the homography h over a raw match list on the host (akz_refine_homography): least-squares refits
+    on the inliers and re-classification until the set stops growing -> (inliers in match order, 3x3 float32 H, accepted
+    fits).  With 0 accepted fits H is h and the list its inliers."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    hin = np.ascontiguousarray(np.asarray(h, np.float32).reshape(9))
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    n = C.c_uint64()
+    hout = np.zeros(9, np.float32)
+    it = C.c_uint32()
+    _check(lib().akz_refine_homography(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                       m.ctypes.data_as(C.c_void_p), len(m), hin.ctypes.data_as(C.POINTER(C.c_float)), epsilon_inlier,
+                                       max_iterations, out.ctypes.data_as(C.c_void_p), C.byref(n),
+                                       hout.ctypes.data_as(C.POINTER(C.c_float)), C.byref(it)))
+    return out[:n.value].copy(), hout.reshape(3, 3), it.value
+
+
+def _refined_pair(fn, extra, keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                  ransac_epsilon_inliers, refine_iterations, ctx):
+    c = ctx or default_context()
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
+    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
+    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
+    n = C.c_uint64()
+    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
+    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
+    if nb0 is not None and nb1 is not None and nb0 != nb1:
+        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
+    h = np.zeros(9, np.float32)
+    found = C.c_int()
+    it = C.c_uint32()
+    _check(fn(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), len(d0), k1.ctypes.data_as(C.c_void_p), len(k1),
+              d1.ctypes.data_as(C.c_void_p), len(d1), nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+              refine_iterations, *extra, out.ctypes.data_as(C.c_void_p), C.byref(n), h.ctypes.data_as(C.POINTER(C.c_float)),
+              C.byref(found), C.byref(it)))
+    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None), it.value
+
+
+def match_features_homography_refined(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                                      ransac_epsilon_inliers, refine_iterations, ctx=None):
+    """match_features_homography with the refit of the H it found as one more stage on the GPU
+    (akz_match_features_homography_refined) -> (matches, H or None, accepted fits): with an H what refine_homography gives on
+    the raw descriptor_match list from the winner, without one the list of match_features_homography."""
+    return _refined_pair(lib().akz_match_features_homography_refined, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1,
+                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, ctx)
+
+
+def match_features_homography_refined_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                                             ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
+    """match_features_homography_refined, then the guided scan with the REFINED H
+    (akz_match_features_homography_refined_guided) -> (matches, H or None, accepted fits)."""
+    return _refined_pair(lib().akz_match_features_homography_refined_guided, (guided_radius, guided_lowes_ratio), keypoints_0,
+                         descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                         refine_iterations, ctx)
+
+
+def match_features_homography_refined_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations,
+                                            ctx=None):
+    """Context.match_features_homography_refined_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_homography_refined_pairs(features, pairs, lowes_ratio, ransac_trials,
+                                                                              ransac_epsilon_inliers, refine_iterations)
+
+
+def match_features_homography_refined_guided_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                   refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
+    """Context.match_features_homography_refined_guided_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_homography_refined_guided_pairs(
+        features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio)
 
 
 # ------------------------------------------------------------------------------------------

@@ -538,7 +538,7 @@ int akz_match_features_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t
    included) or whose triples change orientation between the images give no model.  H is row-major with H[8] = 1 (it maps
    image 0 onto image 1); a match is an inlier iff w = h6 x0 + h7 y0 + h8 > 0 and |H p0 - p1| < epsilon_inlier, evaluated
    without a division as (U - x1 w)^2 + (V - y1 w)^2 < (epsilon_inlier w)^2 in f32.  The returned H is the winning trial's
-   model (no refit on the inliers).  Samples come from the calling thread's default random source, 4 per trial (see
+   model; akz_refine_homography and the _refined calls below refit it on its inliers.  Samples come from the calling thread's default random source, 4 per trial (see
    akz_random_seed).  DESIGN.md 8. */
 /* epsilon_model of the two context calls: every rotated row norm of the normalised 8 x 9 design matrix must exceed it */
 #define AKZ_HOMOGRAPHY_EPSILON_MODEL 1e-6f
@@ -627,6 +627,61 @@ int akz_match_features_homography_guided_pairs(akz_ctx* ctx, const akz_feature_s
                                                float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio,
                                                akz_match* out, uint64_t* n_out /* n_pairs */, float* h /* 9 x n_pairs */,
                                                int* found /* n_pairs */);
+
+/* ---- the refit of the RANSAC homography on its inliers (an addition) -------------------------------------
+   Local optimisation of a homography over a pair's RAW match list (the ratio-test list, so the set can grow):
+       S = { i : inlier(h, i, epsilon_inlier) }  (the inlier test above);  done = 0
+       while done < max_iterations:
+           h' = fit(S)            no model: stop
+           S' = inliers(h')
+           |S'| < |S|: stop       h' is rejected
+           grew = |S'| > |S|;  h, S = h', S';  done += 1
+           not grew: stop
+   The result never has fewer inliers than the input.  fit(S) for |S| >= 4 is the least-squares DLT over all of S: Hartley
+   normalisation of both images (centroid, mean distance d, s = sqrt(2) / d; d = 0: no model), the normal matrix M = A^T A
+   of the design rows of the 4-point model in normalised coordinates, its null vector by the one-sided Jacobi sweeps on the
+   9 rows of M (the row of the smallest norm dropped; every kept norm above AKZ_HOMOGRAPHY_EPSILON_MODEL^2 |S| / 4, else no
+   model), then the denormalisation, the H[8] rule and the rounding of the 4-point model.  All of it in f64 in one order,
+   every sum over S by lanes (element i in lane i mod 256, ascending, from +0.0) and the tree p[l] += p[l + s],
+   s = 128 .. 1: host and GPU give the same bits.
+   akz_refine_homography is the plain host statement (no GPU call).  out must hold n_matches entries; it receives S in
+   match order, h_out (9, may be NULL) the final h, *iterations (may be NULL) the number of accepted fits; with 0 accepted
+   fits that is h_in unchanged and its inliers.  Refusals: those of akz_remove_outliers_homography, a NULL h_in, an
+   epsilon_inlier that is not finite or <= 0. */
+int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                          const akz_match* matches, uint64_t n_matches, const float* h_in /* 9 */, float epsilon_inlier,
+                          uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* h_out /* 9, may be NULL */,
+                          uint32_t* iterations /* may be NULL */);
+/* akz_match_features_homography(_pairs) with the refit as one more stage on the GPU: draws, winner and found are exactly the
+   unrefined call's and the random source ends where that call leaves it; where found = 1 the list and H are those of
+   akz_refine_homography(raw list, winner, ransac_epsilon_inliers, refine_iterations); where found = 0 or a pair has fewer
+   than 4 matches the list is the unrefined call's and iterations is 0.  refine_iterations = 0 is the unrefined call bit for
+   bit.  iterations: one per pair, may be NULL.  Refusals are the unrefined call's, before the first draw and any GPU work. */
+int akz_match_features_homography_refined(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                          const uint8_t* descriptors_0, uint64_t n_descriptors_0, const akz_keypoint* keypoints_1,
+                                          uint64_t n_keypoints_1, const uint8_t* descriptors_1, uint64_t n_descriptors_1,
+                                          uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                          float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out, uint64_t* n_out,
+                                          float* h /* 9 */, int* found, uint32_t* iterations);
+int akz_match_features_homography_refined_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out,
+                                                uint64_t* n_out /* n_pairs */, float* h /* 9 x n_pairs */, int* found /* n_pairs */,
+                                                uint32_t* iterations /* n_pairs */);
+/* The refined call followed by the guided stage of akz_match_features_homography_guided(_pairs), gating with the REFINED H. */
+int akz_match_features_homography_refined_guided(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                                 const uint8_t* descriptors_0, uint64_t n_descriptors_0,
+                                                 const akz_keypoint* keypoints_1, uint64_t n_keypoints_1,
+                                                 const uint8_t* descriptors_1, uint64_t n_descriptors_1, uint64_t desc_bytes,
+                                                 double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                                 uint32_t refine_iterations, float guided_radius, double guided_lowes_ratio,
+                                                 akz_match* out, uint64_t* n_out, float* h /* 9 */, int* found, uint32_t* iterations);
+int akz_match_features_homography_refined_guided_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets,
+                                                       const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio,
+                                                       uint64_t ransac_trials, float ransac_epsilon_inliers, uint32_t refine_iterations,
+                                                       float guided_radius, double guided_lowes_ratio, akz_match* out,
+                                                       uint64_t* n_out /* n_pairs */, float* h /* 9 x n_pairs */,
+                                                       int* found /* n_pairs */, uint32_t* iterations /* n_pairs */);
 
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
