@@ -1,6 +1,6 @@
 // The model of one RANSAC trial -- estimate_fundamental_matrix (akaze/src/ops/estimate_fundamental_matrix.rs:17-69) for
 // exactly eight correspondences -- as ONE piece of source for the host path (akz_ransac.cpp) and for the device kernel
-// that runs the trials of match_features (akz_fmatrix.hip): f64 additions, multiplications, divisions and square roots in
+// that runs the trials of match_features (akz_ransac_kernels.hip): f64 additions, multiplications, divisions and square roots in
 // a fixed order, no contraction (-ffp-contract=off on both sides), so that the two produce the same bits.
 #pragma once
 #include <cmath>
@@ -85,7 +85,7 @@ AKZ_HD int smallest_singular(M& m, float epsilon, bool* full_rank) {
 }
 
 // the design matrix of eight correspondences (:26-40), products in f32 as the reference forms them
-// (row i of one correspondence: the batched trials of akz_fmatrix.hip form the rows of a matrix on several lanes)
+// (row i of one correspondence: the batched trials of akz_ransac_kernels.hip form the rows of a matrix on several lanes)
 template <class M>
 AKZ_HD void design_row(M& m, int i, float x0, float y0, float x1, float y1) {
     const float row[9] = {x0 * x1, x0 * y1, x0, y0 * x1, y0 * y1, y0, x1, y1, 1.0f};
@@ -131,6 +131,20 @@ AKZ_HD float fundamental_error(const float (&f)[9], float x0, float y0, float x1
     const float s = (r0 * x0 + r1 * y0) + r2;
     return fabsf(s);
 }
+
+// The fundamental matrix as a RANSAC model, for ransac_host (akz_ransac.cpp) and the kernels of akz_ransac_kernels.hip alike
+struct FundamentalRansac {
+    static constexpr int K = 8;                           // matches per sample, and the least a call works on
+    static constexpr bool kKeepAllWithoutWinner = false;  // no trial with an inlier: the zero model is evaluated (error 0)
+    static constexpr bool kModelOut = false;              // the call hands back no model
+    static AKZ_HD bool from_sample(const float (&x0)[8], const float (&y0)[8], const float (&x1)[8], const float (&y1)[8], float epsilon,
+                                   float (&f)[9]) {
+        return fundamental_from_8(x0, y0, x1, y1, epsilon, f);
+    }
+    static AKZ_HD bool inlier(const float (&f)[9], float x0, float y0, float x1, float y1, float eps) {
+        return fundamental_error(f, x0, y0, x1, y1) < eps;
+    }
+};
 
 // The gate of guided matching for a fundamental matrix (akz_descriptor_match_guided, model_kind 1): the point
 // (x1, y1) lies closer than `radius` pixels to the epipolar line F (x0, y0, 1)^T, without a division or a square root, in

@@ -1,5 +1,5 @@
 // The model of one homography RANSAC trial -- the 4-point DLT with Hartley normalisation -- as ONE piece of source for the
-// host path (akz_ransac.cpp) and the device kernels (akz_homography.hip), like akz_fmatrix.hpp for the fundamental
+// host path (akz_ransac.cpp) and the device kernels (akz_ransac_kernels.hip), like akz_fmatrix.hpp for the fundamental
 // matrix: f64 arithmetic in a fixed order, no contraction (-ffp-contract=off on both sides), the same bits on both.
 // The reference has no homography; this is an addition.
 //
@@ -183,6 +183,19 @@ AKZ_HD bool homography_inlier(const float (&h)[9], float x0, float y0, float x1,
     const float du = U - x1 * w, dv = V - y1 * w, ew = eps * w;
     return w > 0.0f && du * du + dv * dv < ew * ew;
 }
+// The homography as a RANSAC model (see FundamentalRansac)
+struct HomographyRansac {
+    static constexpr int K = 4;
+    static constexpr bool kKeepAllWithoutWinner = true;  // no trial with an inlier: every match is kept whatever epsilon is
+    static constexpr bool kModelOut = true;              // H and found are handed back (found = 0: H zeros on the device)
+    static AKZ_HD bool from_sample(const float (&x0)[4], const float (&y0)[4], const float (&x1)[4], const float (&y1)[4], float epsilon,
+                                   float (&h)[9]) {
+        return homography_from_4(x0, y0, x1, y1, epsilon, h);
+    }
+    static AKZ_HD bool inlier(const float (&h)[9], float x0, float y0, float x1, float y1, float eps) {
+        return homography_inlier(h, x0, y0, x1, y1, eps);
+    }
+};
 // homography_inlier in two halves for a scan that tests one (x0, y0) against many (x1, y1) (akz_guided.hip): what depends
 // on the query alone is formed once -- the same operations on the same values, so transfer_near(transfer_disc(h, x0, y0,
 // eps), x1, y1) has the bits of homography_inlier(h, x0, y0, x1, y1, eps).

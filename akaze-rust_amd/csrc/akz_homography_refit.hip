@@ -1,11 +1,9 @@
-// The refit stage of akz_match_features_homography_refined(_pairs): after k_homography_pick_filter (akz_homography.hip) has
+// The refit stage of akz_match_features_homography_refined(_pairs): after k_pairs_pick_filter (akz_ransac_kernels.hip) has
 // left every pair's winner, found flag and kept list on the device, this kernel runs the local optimisation of
 // akz_homography_refit.hpp on the pair's RAW list -- the same source as the host statement akz_refine_homography, the same
 // bits -- and rewrites H, the kept list and its count.
-#include <hip/hip_runtime.h>
-
 #include "akz_homography_refit.hpp"
-#include "akz_internal.hpp"
+#include "akz_ransac_device.hpp"
 
 namespace akz {
 namespace {
@@ -13,6 +11,7 @@ namespace {
 using PairJob = launch::PairJobHost;
 
 constexpr int RF = kRefitLanes;  // one thread per lane of the summation order
+static_assert(RF == kGroup, "compact_kept");
 constexpr int RG = 6;            // sums that go through the tree together (LDS: RG x 256 doubles)
 
 // The sums of every thread's v[k] in the order of the statement: p[l] = p[l] + p[l + s] for s = 128, 64 through LDS, then
@@ -69,9 +68,9 @@ __device__ unsigned block_count(const float (&h)[9], const float* x0, const floa
 // Per pair (a workgroup of 256, grid-stride): nothing for a pair without a model, with fewer than 4 matches or with
 // max_iterations == 0 (iterations = 0, H and the kept list stay the pick kernel's); else the loop of the statement.  Element
 // i of the raw list is thread i mod 256's, added in ascending i: the lane sums live in f64 registers (24 in pass 3).  The
-// 9 x 9 decomposition keeps M in LDS, as the trial kernel keeps its 8 x 9: its rotations run on four lanes (see below), the
-// dropped row, the rank rule and the model tail on thread 0.  After at least one accepted fit: H rewritten, the kept list
-// compacted again in match order (the ballot and prefix compaction of k_homography_pick_filter), keep_cnt rewritten.
+// 9 x 9 decomposition keeps M in LDS, as the trial kernel keeps its 8 x 9: its rotations run on four lanes
+// (jacobi_sweep_levels<9>: 15 levels per sweep), the dropped row, the rank rule and the model tail on thread 0.  After at
+// least one accepted fit: H rewritten, the kept list compacted again in match order, keep_cnt rewritten.
 __global__ void __launch_bounds__(RF) k_homography_refit(const PairJob* __restrict__ pairs, unsigned n_pairs, const akz_match* __restrict__ raw,
                                                          const unsigned long long* __restrict__ raw_cnt, const float* __restrict__ pts,
                                                          unsigned long long stride, float epsilon_model, float epsilon_inlier,
@@ -84,11 +83,7 @@ __global__ void __launch_bounds__(RF) k_homography_refit(const PairJob* __restri
     __shared__ float s_h[9];
     __shared__ int s_ok;
     __shared__ unsigned s_wsum[RF / 64];
-    struct LdsMat {
-        double* p;
-        __device__ double& at(int r, int k) { return p[r * 9 + k]; }
-    };
-    const unsigned tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    const unsigned tid = threadIdx.x;
     for (unsigned p = blockIdx.x; p < n_pairs; p += gridDim.x) {
         const PairJob pj = pairs[p];
         const unsigned long long n64 = raw_cnt[pj.cnt_idx];
@@ -148,21 +143,9 @@ __global__ void __launch_bounds__(RF) k_homography_refit(const PairJob* __restri
             if (tid < 64) {  // the first wave: M, the sweeps on its lanes 0 .. 3, the model on lane 0
                 LdsMat m{s_m};
                 if (tid == 0) refit_normal_matrix(m, s_sum);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                // The host's row-cyclic sweep (0,1) (0,2) .. (7,8), level by level: the pairs with p + q = sum touch disjoint
-                // rows, and every earlier pair of the cyclic order that shares a row with (p, q) has a smaller sum, every later
-                // one a larger: the same rotations on the same values.  At most four pairs per level, 15 levels per sweep.
-                for (int sweep = 0; sweep < 60; ++sweep) {
-                    bool rotated = false;
-                    for (int sum = 1; sum <= 15; ++sum) {
-                        const int pp = max(0, sum - 8) + (int)tid, qq = sum - pp;
-                        if (tid < 4 && pp < qq) rotated = jacobi_pair(m, pp, qq) || rotated;
-                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                        __builtin_amdgcn_wave_barrier();
-                    }
-                    if (__ballot(rotated) == 0ull) break;  // the first sweep without a rotation
-                }
+                wave_sync();
+                for (int sweep = 0; sweep < 60; ++sweep)
+                    if (__ballot(jacobi_sweep_levels<9>(m, (int)tid, tid < 4)) == 0ull) break;  // the first sweep without a rotation
                 if (tid == 0) {
                     float h2[9];
                     const bool ok = refit_model_from_rotated(m, count, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, h2);
@@ -196,17 +179,7 @@ __global__ void __launch_bounds__(RF) k_homography_refit(const PairJob* __restri
             for (unsigned base = 0; base < n; base += RF) {
                 const unsigned i = base + tid;
                 const bool kept = i < n && homography_inlier(h, x0[i], y0[i], x1[i], y1[i], epsilon_inlier);
-                const unsigned long long bal = __ballot(kept);
-                if (lane == 0) s_wsum[w] = (unsigned)__popcll(bal);
-                __syncthreads();
-                unsigned before = (unsigned)__popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-                for (unsigned k = 0; k < RF / 64; ++k) {
-                    if (k < w) before += s_wsum[k];
-                    total += s_wsum[k];
-                }
-                if (kept) keep[pj.keep_off + written + before] = raw[pj.raw_off + i];
-                written += total;
-                __syncthreads();
+                compact_kept(kept, raw + pj.raw_off + i, keep + pj.keep_off, written, s_wsum, tid);
             }
             if (tid == 0) keep_cnt[p] = written;
         }

@@ -136,7 +136,7 @@ AKZ_HD bool refit_model_from_rotated(M& m, double count, float epsilon_model, do
     return hom_model_from_rows(m, c0x, c0y, s0, c1x, c1y, s1, h);
 }
 // the model from M: the row-cyclic sweeps over its 9 rows, then the above (the host; the device runs the same rotations level
-// by level on four lanes, see k_homography_refit)
+// by level on four lanes, see jacobi_sweep_levels)
 template <class M>
 AKZ_HD bool refit_model_from_normal(M& m, double count, float epsilon_model, double c0x, double c0y, double s0, double c1x, double c1y,
                                     double s1, float (&h)[9]) {

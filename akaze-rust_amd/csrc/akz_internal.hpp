@@ -17,7 +17,7 @@ void set_error(const std::string& msg);
 unsigned host_cpu_share();
 
 // remove_outliers (estimate_fundamental_matrix.rs:99-165) with the trials optionally run by the caller's hook (akz_ransac.cpp;
-// match_features hands in the device kernel of akz_fmatrix.hip): (x0, y0, x1, y1 of every match, n, 8 sample indices per
+// match_features hands in the device kernel of akz_ransac_kernels.hip): (x0, y0, x1, y1 of every match, n, 8 sample indices per
 // trial, trials, epsilon_model, epsilon_inlier) -> 9 model floats and the inlier count (-1: no model) per trial
 using TrialsOnDevice = std::function<int(const float*, const float*, const float*, const float*, uint32_t, const uint32_t*, uint32_t,
                                          float, float, float*, int32_t*)>;
@@ -352,40 +352,35 @@ uint32_t match_mfma_multi_chunks(uint32_t n0, uint32_t n_sets, uint32_t avg_tile
 void unpack_bits(hipStream_t s, const uint8_t* d, uint32_t n, uint32_t n_pad, bool query, uint8_t* out8, uint32_t* pop,
                  uint32_t* bound, uint32_t threshold, uint32_t n_bound, const uint32_t* d_tiles, bool fp4 = false);
 // both sets of a pair call in one launch (query form with one bound array, train form)
-// one workgroup per RANSAC trial: model of its eight samples (akz_fmatrix.hpp) + inlier count over all matches (akz_fmatrix.hip)
+// one workgroup per RANSAC trial: model of its eight samples (akz_fmatrix.hpp) + inlier count over all matches
+// (akz_ransac_kernels.hip)
 void ransac_trials(hipStream_t s, const float* d_pts, uint32_t n_matches, const uint32_t* d_samples, uint32_t trials, float epsilon_model,
                    float epsilon_inlier, float* d_models, int32_t* d_inliers);
-// akz_match_features_pairs (akz_fmatrix.hip).  Per pair p: its matches at d_raw + raw_off, their count at d_raw_cnt[cnt_idx];
-// its x0 | y0 | x1 | y1 at d_pts + {0, 1, 2, 3} * pts_stride + raw_off; its trials at trial_off .. + n_trials of the call
-struct PairJobHost {  // = PairJob of akz_fmatrix.hip
+// The pairs calls of both models (akz_ransac_kernels.hip).  Per pair p: its matches at d_raw + raw_off, their count at
+// d_raw_cnt[cnt_idx]; its x0 | y0 | x1 | y1 at d_pts + {0, 1, 2, 3} * pts_stride + raw_off; its trials at trial_off .. + n_trials
+// of the call
+struct PairJobHost {
     uint64_t raw_off, kp0_off, kp1_off, trial_off, keep_off, n_trials;
     uint32_t cnt_idx, pad;
 };
 static_assert(sizeof(PairJobHost) == 56, "the device reads 56-byte pair records");
+enum class RansacModel { Fundamental, Homography };  // 8 / 4 matches per sample (FundamentalRansac, HomographyRansac)
 // gathers the keypoint coordinates of every pair's matches (kx / ky: x / y of every uploaded set's keypoints)
 void pair_points(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                  const float* d_kx, const float* d_ky, float* d_pts, uint64_t pts_stride);
-// trials first_trial .. + n_trials of the call: d_trials holds this chunk's 8 sample indices per trial (relative to the
+// trials first_trial .. + n_trials of the call: d_trials holds this chunk's K sample indices per trial (relative to the
 // pair's first match), then the pair of every trial; models / inliers are indexed by the call's trial number
-void ransac_trials_multi(hipStream_t s, const PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
-                         const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier,
-                         float* d_models, int32_t* d_inliers);
-// per pair: the first trial with the most inliers (zero model without one above 0), then the matches it keeps, compacted in
-// order at d_keep + keep_off, their count at d_keep_cnt[pair] (fewer than 8 matches: all of them)
-void ransac_pick_filter(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
-                        const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float epsilon_inlier,
-                        void* d_keep, uint64_t* d_keep_cnt);
-// akz_match_features_homography(_pairs) (akz_homography.hip): the same pair records; d_trials holds this chunk's 4 sample
-// indices per trial, then the pair of every trial
-void homography_trials(hipStream_t s, const PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
-                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier,
-                       float* d_models, int32_t* d_inliers);
-// per pair: the winner (strict `>` from 0 in trial order), its H at d_h + 9 pair and found at d_found[pair] (none: zeros, found
-// 0, every match kept), the kept matches compacted in order at d_keep + keep_off, their count at d_keep_cnt[pair]
-void homography_pick_filter(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
-                            const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float epsilon_inlier,
-                            void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found);
-// the refit stage after homography_pick_filter (akz_homography_refit.hip): per pair with found = 1 and 4 matches or more, the
+void pairs_trials(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial,
+                  uint32_t n_trials, const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float epsilon_model,
+                  float epsilon_inlier, float* d_models, int32_t* d_inliers);
+// per pair: the first trial with the most inliers (strict `>` from 0 in trial order), then the matches it keeps, compacted in
+// order at d_keep + keep_off, their count at d_keep_cnt[pair] (fewer than K matches: all of them).  No trial above 0 -- the
+// fundamental matrix: the zero model filters; the homography: every match kept.  The homography also leaves the winner's H at
+// d_h + 9 pair (none: zeros) and found at d_found[pair]; both are null for the fundamental matrix.
+void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw,
+                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers,
+                       float epsilon_inlier, void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found);
+// the refit stage after the homography's pairs_pick_filter (akz_homography_refit.hip): per pair with found = 1 and 4 matches or more, the
 // loop of akz_homography_refit.hpp on the raw list from the H at d_h + 9 pair; after an accepted fit H, the kept list and its
 // count are rewritten; d_iterations[pair] = accepted fits (0 for the pairs left alone)
 void homography_refit(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,

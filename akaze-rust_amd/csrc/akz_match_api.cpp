@@ -356,7 +356,7 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
     std::vector<akz_match> raw((size_t)std::max<uint64_t>(1, n_d0));
     uint64_t n_raw = 0;
     AKZ_TRY(akz_descriptor_match(c, d0, n_d0, d1, n_d1, desc_bytes, 10000, lowes_ratio, raw.data(), &n_raw));  // lib.rs:261-266
-    // lib.rs:267-274.  The trials run on the device (akz_fmatrix.hip: the host's model source, same bits) when there is
+    // lib.rs:267-274.  The trials run on the device (akz_ransac_kernels.hip: the host's model source, same bits) when there is
     // enough of them to pay for a launch and a round trip (~60 us); the samples, the choice of the winner and the final
     // filter stay on the host.  A 4K pair (8 264 matches, 1 000 trials): 1.3-1.4 ms on 16 host threads -> see DESIGN 6.
     TrialsOnDevice on_device;
@@ -466,50 +466,28 @@ int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint
     }
     return AKZ_OK;
 }
-// The geometric model of the pairs orchestration below: K match indices per sample, the trial and pick / filter kernels, and
-// whether the call hands back a model per pair (H, found).
+// The geometric model of the pairs orchestration below: the kernels' model kind, K match indices per sample, and whether the
+// call hands back a model per pair (H, found).
 namespace {
-struct FundamentalModel {  // akz_match_features_pairs: k_ransac_trials_multi, k_ransac_pick_filter (akz_fmatrix.hip)
+struct FundamentalModel {  // akz_match_features_pairs
+    static constexpr launch::RansacModel kKind = launch::RansacModel::Fundamental;
     static constexpr int K = 8;
     static constexpr bool kModelOut = false;
     static constexpr float kEpsilonModel = 0.05f;
     static constexpr const char* kName = "match_features_pairs: ";
-    static void trials(hipStream_t s, const launch::PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
-                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float eps_model, float eps_inlier, float* d_models,
-                       int32_t* d_inliers) {
-        launch::ransac_trials_multi(s, d_pairs, d_trials, first_trial, n_trials, d_raw_cnt, d_pts, pts_stride, eps_model, eps_inlier, d_models,
-                                    d_inliers);
-    }
-    static void pick_filter(hipStream_t s, const launch::PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
-                            const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float eps_inlier,
-                            void* d_keep, uint64_t* d_keep_cnt, float*, int32_t*) {
-        launch::ransac_pick_filter(s, d_pairs, n_pairs, d_raw, d_raw_cnt, d_pts, pts_stride, d_models, d_inliers, eps_inlier, d_keep,
-                                   d_keep_cnt);
-    }
 };
-struct HomographyModel {  // akz_match_features_homography(_pairs): k_homography_trials, k_homography_pick_filter
+struct HomographyModel {  // akz_match_features_homography(_pairs)
+    static constexpr launch::RansacModel kKind = launch::RansacModel::Homography;
     static constexpr int K = 4;
     static constexpr bool kModelOut = true;
     static constexpr float kEpsilonModel = AKZ_HOMOGRAPHY_EPSILON_MODEL;
     static constexpr const char* kName = "match_features_homography_pairs: ";
-    static void trials(hipStream_t s, const launch::PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial, uint32_t n_trials,
-                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float eps_model, float eps_inlier, float* d_models,
-                       int32_t* d_inliers) {
-        launch::homography_trials(s, d_pairs, d_trials, first_trial, n_trials, d_raw_cnt, d_pts, pts_stride, eps_model, eps_inlier, d_models,
-                                  d_inliers);
-    }
-    static void pick_filter(hipStream_t s, const launch::PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
-                            const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers, float eps_inlier,
-                            void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found) {
-        launch::homography_pick_filter(s, d_pairs, n_pairs, d_raw, d_raw_cnt, d_pts, pts_stride, d_models, d_inliers, eps_inlier, d_keep,
-                                       d_keep_cnt, d_h, d_found);
-    }
 };
 
 // match_features over many pairs (see the header).  Stages, all on the context's stream: every distinct set's 64-byte rows and
 // keypoint x / y through pinned staging; the descriptor scans (one multi-set launch per first set, or the pair matcher for
 // rows of 62..64 bytes); k_pair_points; ONE read-back of the match counts; the samples drawn on the calling thread in pair
-// order, in chunks whose trials (Model::trials) run while the next chunk is drawn; Model::pick_filter; ONE read-back of the
+// order, in chunks whose trials (launch::pairs_trials) run while the next chunk is drawn; launch::pairs_pick_filter; ONE read-back of the
 // kept lists (and, for a model that is handed back, every pair's model and found flag).  A RefineStage puts the refit kernel
 // between the pick and that read-back: it rewrites H, the kept lists and their counts in place and adds every pair's number of
 // accepted fits to the head that the read-back carries; the guided stage then reads the H table it has rewritten.
@@ -540,7 +518,7 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     const size_t b_rows = up((size_t)rows1 * 64), b_xy = up((size_t)rows1 * 4);
     const size_t b_raw = up((size_t)cap1 * sizeof(akz_match)), b_cnt = up((size_t)n_pairs * 8), b_pts = (size_t)cap1 * 16;
     const size_t b_tab = up((size_t)n_pairs * sizeof(launch::PairJobHost));
-    constexpr uint32_t kChunk = 16384;  // trials per launch of k_ransac_trials_multi (and per pinned sample slot)
+    constexpr uint32_t kChunk = 16384;  // trials per launch of k_pairs_trials (and per pinned sample slot)
     const size_t b_smp = (size_t)kChunk * 9 * sizeof(uint32_t);
     AKZ_TRY(ensure(c, c->mp_in, b_rows + 2 * b_xy));
     AKZ_TRY(ensure(c, c->mp_raw, b_raw + b_cnt + b_pts));
@@ -670,8 +648,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         AKZ_HIP_TRY(hipEventRecord(c->mp_smp_ev[slot], st));
         if (timed && !launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         launched = true;
-        Model::trials(st, d_tab, d_smp[slot], chunk_first, fill, d_cnt, d_pts, cap1, Model::kEpsilonModel, ransac_epsilon_inliers, d_mdl,
-                      d_inl);
+        launch::pairs_trials(st, Model::kKind, d_tab, d_smp[slot], chunk_first, fill, d_cnt, d_pts, cap1, Model::kEpsilonModel,
+                             ransac_epsilon_inliers, d_mdl, d_inl);
         AKZ_HIP_TRY(hipGetLastError());
         chunk_first += fill;
         fill = 0;
@@ -702,7 +680,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         if (!launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[4], st));
     }
-    Model::pick_filter(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep, d_kcnt, d_hm, d_hf);
+    launch::pairs_pick_filter(st, Model::kKind, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep,
+                              d_kcnt, Model::kModelOut ? d_hm : nullptr, Model::kModelOut ? d_hf : nullptr);
     AKZ_HIP_TRY(hipGetLastError());
     if (Model::kModelOut && refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
         launch::homography_refit(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, Model::kEpsilonModel, ransac_epsilon_inliers,

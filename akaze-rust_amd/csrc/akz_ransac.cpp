@@ -52,19 +52,58 @@ struct Model {
     float f[9];  // row-major 3 x 3
 };
 
-// estimate_fundamental_matrix (:17-69): the model itself is akz_fmatrix.hpp (shared with the device kernel)
-bool estimate(const akz_keypoint* k0, const akz_keypoint* k1, const akz_match* sample, float epsilon, Model& out) {
-    float x0[8], y0[8], x1[8], y1[8];
-    for (int i = 0; i < 8; ++i) {
-        x0[i] = k0[sample[i].index_0].x; y0[i] = k0[sample[i].index_0].y;
-        x1[i] = k1[sample[i].index_1].x; y1[i] = k1[sample[i].index_1].y;
+// the refusals every call over a list of matches shares; `name` is the call's
+int refuse_bad_matches(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                       const akz_match* matches, uint64_t n_matches, const akz_match* out, const uint64_t* n_out) {
+    if (!n_out || (n_matches && (!matches || !out))) {
+        set_error(std::string(name) + ": null pointer");
+        return AKZ_ERR_INVALID_ARG;
     }
-    return fundamental_from_8(x0, y0, x1, y1, epsilon, out.f);
+    for (uint64_t i = 0; i < n_matches; ++i)
+        if (matches[i].index_0 >= n0 || matches[i].index_1 >= n1 || !keypoints_0 || !keypoints_1) {
+            set_error(std::string(name) + ": match index out of range");
+            return AKZ_ERR_INVALID_ARG;
+        }
+    return AKZ_OK;
 }
 
-// evaluate_model (:79-83): |p_r^T F p_l|
-float model_error(const Model& md, const akz_keypoint& k0, const akz_keypoint& k1) {
-    return fundamental_error(md.f, k0.x, k0.y, k1.x, k1.y);
+// The matched point pairs side by side, x0 | y0 | x1 | y1 with n_matches floats each: the inlier count of a trial -- 8 M
+// evaluations for the 8 000 matches of a 4K pair at 1 000 trials -- is then a streaming loop the compiler vectorises instead
+// of two gathers of 32-byte keypoints per evaluation.
+struct MatchPoints {
+    std::vector<float> v;
+    const float *x0, *y0, *x1, *y1;
+    MatchPoints(const akz_keypoint* keypoints_0, const akz_keypoint* keypoints_1, const akz_match* matches, uint64_t n) : v((size_t)n * 4) {
+        float* p = v.data();
+        x0 = p; y0 = p + n; x1 = p + 2 * n; y1 = p + 3 * n;
+        for (uint64_t i = 0; i < n; ++i) {
+            p[i] = keypoints_0[matches[i].index_0].x; p[n + i] = keypoints_0[matches[i].index_0].y;
+            p[2 * n + i] = keypoints_1[matches[i].index_1].x; p[3 * n + i] = keypoints_1[matches[i].index_1].y;
+        }
+    }
+};
+
+// the model of exactly M::K matches (estimate_fundamental_matrix :17-69 for K = 8): *found = 0 is the reference's `None`
+template <class M>
+int estimate_model(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                   const akz_match* sample, float epsilon, float* model, int* found) {
+    if (!keypoints_0 || !keypoints_1 || !sample || !model || !found) {
+        set_error(std::string(name) + ": null pointer");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < M::K; ++i)
+        if (sample[i].index_0 >= n0 || sample[i].index_1 >= n1) {
+            set_error(std::string(name) + ": match index out of range");
+            return AKZ_ERR_INVALID_ARG;
+        }
+    float x0[M::K], y0[M::K], x1[M::K], y1[M::K], m[9];
+    for (int i = 0; i < M::K; ++i) {
+        x0[i] = keypoints_0[sample[i].index_0].x; y0[i] = keypoints_0[sample[i].index_0].y;
+        x1[i] = keypoints_1[sample[i].index_1].x; y1[i] = keypoints_1[sample[i].index_1].y;
+    }
+    *found = M::from_sample(x0, y0, x1, y1, epsilon, m) ? 1 : 0;
+    if (*found) std::memcpy(model, m, sizeof(m));
+    return AKZ_OK;
 }
 
 // run_trials(lo, hi) over trials 0 .. num_trials on nthreads host threads (one pool for both RANSAC models)
@@ -174,65 +213,57 @@ extern "C" int akz_debug_ransac_samples_k(uint64_t s0, uint64_t s1, uint64_t n_m
     return AKZ_OK;
 }
 
-// trials_on_device (match_features with a context): runs the trials elsewhere -- px0 .. py1 (n_matches floats each), the
-// samples (8 per trial), -> models (9 floats per trial), inliers (-1: no model); AKZ_OK or an error (the host path then
-// takes over)
-int akz::remove_outliers_impl(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
-                              const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
-                              float epsilon_inlier, akz_match* out, uint64_t* n_out, const TrialsOnDevice& trials_on_device) {
-    if (!n_out || (n_matches && (!matches || !out))) {
-        set_error("remove_outliers: null pointer");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    for (uint64_t i = 0; i < n_matches; ++i)
-        if (matches[i].index_0 >= n0 || matches[i].index_1 >= n1 || !keypoints_0 || !keypoints_1) {
-            set_error("remove_outliers: match index out of range");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    if (n_matches < 8) {  // "Not enough points to do RANSAC."
+// RANSAC on the host for either model (M: FundamentalRansac of akz_fmatrix.hpp, HomographyRansac of akz_homography.hpp).
+// The trials are independent once their samples are drawn: the samples come from the thread's random source in trial order
+// (as the sequential loop of :111-147 draws them), the models and inlier counts are computed on a few host threads, the
+// winner is picked in trial order with the reference's strict `>` from 0 -- the same model as the sequential loop returns
+// (12 ms -> 1.5 ms for the 8 000 matches of a 4K pair at 1 000 trials) -- and the final filter runs in match order.  Fewer
+// than M::K matches ("Not enough points to do RANSAC."): returned unchanged, nothing drawn.  No trial with an inlier: the zero
+// model filters, or (M::kKeepAllWithoutWinner) every match is kept; h and found are written for M::kModelOut only.
+// trials_on_device (match_features with a context, the fundamental matrix only): runs the trials elsewhere -- x0 .. y1
+// (n_matches floats each), the samples (8 per trial), -> models (9 floats per trial), inliers (-1: no model); AKZ_OK or an
+// error (the host path then takes over)
+namespace {
+template <class M>
+int ransac_host(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model, float epsilon_inlier, akz_match* out,
+                uint64_t* n_out, float* h, int* found, const TrialsOnDevice& trials_on_device) {
+    constexpr int K = M::K;
+    AKZ_TRY(refuse_bad_matches(name, keypoints_0, n0, keypoints_1, n1, matches, n_matches, out, n_out));
+    if (found) *found = 0;
+    if (n_matches < (uint64_t)K) {
         if (n_matches) std::memcpy(out, matches, n_matches * sizeof(akz_match));
         *n_out = n_matches;
         return AKZ_OK;
     }
-    // The trials are independent once their samples are drawn: the samples come from the thread's random source in trial
-    // order (as the sequential loop of :111-147 draws them), the models and inlier counts are computed on a few host
-    // threads, and the winner is picked in trial order with the reference's strict `>` -- the same model as the
-    // sequential loop returns (12 ms -> 1.5 ms for the 8 000 matches of a 4K pair at 1 000 trials).
-    std::vector<uint64_t> samples((size_t)num_trials * 8);
-    draw_samples<8>(default_source(), n_matches, num_trials, samples.data());
+    std::vector<uint64_t> samples((size_t)num_trials * K);
+    draw_samples<K>(default_source(), n_matches, num_trials, samples.data());
     std::vector<Model> models((size_t)num_trials);
-    std::vector<int64_t> inliers((size_t)num_trials, -1);  // -1: no model (rank-deficient sample)
-    // the matched point pairs side by side (x0, y0, x1, y1 as four arrays): the inlier count of a trial -- model_error over
-    // every match, 8 M evaluations for the 8 000 matches of a 4K pair at 1 000 trials -- is then a streaming loop the
-    // compiler vectorises instead of two gathers of 32-byte keypoints per evaluation.  Same expression per match, same
-    // operation order (pr[2] = pl[2] = 1.0f: the products with them are exact).
-    std::vector<float> px0((size_t)n_matches), py0((size_t)n_matches), px1((size_t)n_matches), py1((size_t)n_matches);
-    for (uint64_t i = 0; i < n_matches; ++i) {
-        px0[(size_t)i] = keypoints_0[matches[i].index_0].x; py0[(size_t)i] = keypoints_0[matches[i].index_0].y;
-        px1[(size_t)i] = keypoints_1[matches[i].index_1].x; py1[(size_t)i] = keypoints_1[matches[i].index_1].y;
-    }
+    std::vector<int64_t> inliers((size_t)num_trials, -1);  // -1: no model (rank-deficient or degenerate sample)
+    const MatchPoints pt(keypoints_0, keypoints_1, matches, n_matches);
+    const float *x0 = pt.x0, *y0 = pt.y0, *x1 = pt.x1, *y1 = pt.y1;
     auto run_trials = [&](uint64_t lo, uint64_t hi) {
-        const float *x0 = px0.data(), *y0 = py0.data(), *x1 = px1.data(), *y1 = py1.data();
         for (uint64_t trial = lo; trial < hi; ++trial) {
-            akz_match sample[8];
-            for (int i = 0; i < 8; ++i) sample[i] = matches[samples[(size_t)trial * 8 + i]];
+            float sx0[K], sy0[K], sx1[K], sy1[K];
+            for (int i = 0; i < K; ++i) {
+                const uint64_t j = samples[(size_t)trial * K + i];
+                sx0[i] = x0[j]; sy0[i] = y0[j]; sx1[i] = x1[j]; sy1[i] = y1[j];
+            }
             Model model;
-            if (!estimate(keypoints_0, keypoints_1, sample, epsilon_model, model)) continue;
+            if (!M::from_sample(sx0, sy0, sx1, sy1, epsilon_model, model.f)) continue;
             int64_t inl = 0;
-            for (uint64_t i = 0; i < n_matches; ++i)  // model_error(model, k0, k1) < epsilon_inlier
-                inl += fundamental_error(model.f, x0[i], y0[i], x1[i], y1[i]) < epsilon_inlier ? 1 : 0;
+            for (uint64_t i = 0; i < n_matches; ++i) inl += M::inlier(model.f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier) ? 1 : 0;
             models[(size_t)trial] = model;
             inliers[(size_t)trial] = inl;
         }
     };
     bool on_device = false;
     if (trials_on_device && num_trials <= 0x7fffffffull && n_matches <= 0x7fffffffull) {
-        std::vector<uint32_t> smp((size_t)num_trials * 8);
-        for (size_t i = 0; i < smp.size(); ++i) smp[i] = (uint32_t)samples[i];
+        std::vector<uint32_t> smp(samples.begin(), samples.end());
         std::vector<float> mdl((size_t)num_trials * 9);
         std::vector<int32_t> inl((size_t)num_trials);
-        if (trials_on_device(px0.data(), py0.data(), px1.data(), py1.data(), (uint32_t)n_matches, smp.data(), (uint32_t)num_trials,
-                             epsilon_model, epsilon_inlier, mdl.data(), inl.data()) == AKZ_OK) {
+        if (trials_on_device(x0, y0, x1, y1, (uint32_t)n_matches, smp.data(), (uint32_t)num_trials, epsilon_model, epsilon_inlier, mdl.data(),
+                             inl.data()) == AKZ_OK) {
             for (uint64_t t = 0; t < num_trials; ++t) {
                 inliers[(size_t)t] = inl[(size_t)t];
                 if (inl[(size_t)t] >= 0) std::memcpy(models[(size_t)t].f, &mdl[(size_t)t * 9], sizeof(float) * 9);
@@ -254,11 +285,22 @@ int akz::remove_outliers_impl(const akz_keypoint* keypoints_0, uint64_t n0, cons
         }
     uint64_t k = 0;
     for (uint64_t i = 0; i < n_matches; ++i)
-        if (model_error(final_model, keypoints_0[matches[i].index_0], keypoints_1[matches[i].index_1]) <
-            epsilon_inlier)
+        if ((M::kKeepAllWithoutWinner && max_inliers == 0) || M::inlier(final_model.f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier))
             out[k++] = matches[i];
     *n_out = k;
+    if (M::kModelOut && max_inliers > 0) {
+        if (h) std::memcpy(h, final_model.f, sizeof(final_model.f));
+        if (found) *found = 1;
+    }
     return AKZ_OK;
+}
+}  // namespace
+
+int akz::remove_outliers_impl(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                              const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
+                              float epsilon_inlier, akz_match* out, uint64_t* n_out, const TrialsOnDevice& trials_on_device) {
+    return ransac_host<FundamentalRansac>("remove_outliers", keypoints_0, n0, keypoints_1, n1, matches, n_matches, num_trials, epsilon_model,
+                                          epsilon_inlier, out, n_out, nullptr, nullptr, trials_on_device);
 }
 
 extern "C" int akz_remove_outliers(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1,
@@ -268,120 +310,23 @@ extern "C" int akz_remove_outliers(const akz_keypoint* keypoints_0, uint64_t n0,
                                      n_out, akz::TrialsOnDevice());
 }
 
-// ops::estimate_fundamental_matrix::estimate_fundamental_matrix (:17-69) for exactly 8 matches: *found = 0 is the
-// reference's `None` (rank < 8 at `epsilon`); f = the 3x3 matrix, row-major
+// ops::estimate_fundamental_matrix::estimate_fundamental_matrix (:17-69) for exactly 8 matches; f = the 3x3 matrix, row-major
 extern "C" int akz_estimate_fundamental_matrix(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1,
                                                uint64_t n1, const akz_match* matches8, float epsilon, float* f, int* found) {
-    if (!keypoints_0 || !keypoints_1 || !matches8 || !f || !found) {
-        set_error("estimate_fundamental_matrix: null pointer");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    for (int i = 0; i < 8; ++i)
-        if (matches8[i].index_0 >= n0 || matches8[i].index_1 >= n1) {
-            set_error("estimate_fundamental_matrix: match index out of range");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    Model md;
-    *found = estimate(keypoints_0, keypoints_1, matches8, epsilon, md) ? 1 : 0;
-    if (*found) std::memcpy(f, md.f, sizeof(md.f));
-    return AKZ_OK;
+    return estimate_model<FundamentalRansac>("estimate_fundamental_matrix", keypoints_0, n0, keypoints_1, n1, matches8, epsilon, f, found);
 }
 
 // ---- the homography (no reference counterpart; akz_homography.hpp) ------------------------------------------
-namespace {
-bool estimate_h(const akz_keypoint* k0, const akz_keypoint* k1, const akz_match* sample, float epsilon, float (&h)[9]) {
-    float x0[4], y0[4], x1[4], y1[4];
-    for (int i = 0; i < 4; ++i) {
-        x0[i] = k0[sample[i].index_0].x; y0[i] = k0[sample[i].index_0].y;
-        x1[i] = k1[sample[i].index_1].x; y1[i] = k1[sample[i].index_1].y;
-    }
-    return homography_from_4(x0, y0, x1, y1, epsilon, h);
-}
-}  // namespace
-
 extern "C" int akz_estimate_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
                                        const akz_match* matches4, float epsilon, float* h, int* found) {
-    if (!keypoints_0 || !keypoints_1 || !matches4 || !h || !found) {
-        set_error("estimate_homography: null pointer");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    for (int i = 0; i < 4; ++i)
-        if (matches4[i].index_0 >= n0 || matches4[i].index_1 >= n1) {
-            set_error("estimate_homography: match index out of range");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    float m[9];
-    *found = estimate_h(keypoints_0, keypoints_1, matches4, epsilon, m) ? 1 : 0;
-    if (*found) std::memcpy(h, m, sizeof(m));
-    return AKZ_OK;
+    return estimate_model<HomographyRansac>("estimate_homography", keypoints_0, n0, keypoints_1, n1, matches4, epsilon, h, found);
 }
 
-// The host path of the homography RANSAC: remove_outliers_impl's structure with 4-point samples -- the samples from the
-// thread's source in trial order, the trials on the host pool, the winner in trial order with a strict `>` from 0, the final
-// filter in match order.  Fewer than 4 matches: returned unchanged, nothing drawn; no model with an inlier: all kept, found 0.
 extern "C" int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
                                               const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
                                               float epsilon_inlier, akz_match* out, uint64_t* n_out, float* h, int* found) {
-    if (!n_out || (n_matches && (!matches || !out))) {
-        set_error("remove_outliers_homography: null pointer");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    for (uint64_t i = 0; i < n_matches; ++i)
-        if (matches[i].index_0 >= n0 || matches[i].index_1 >= n1 || !keypoints_0 || !keypoints_1) {
-            set_error("remove_outliers_homography: match index out of range");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    if (found) *found = 0;
-    if (n_matches < 4) {
-        if (n_matches) std::memcpy(out, matches, n_matches * sizeof(akz_match));
-        *n_out = n_matches;
-        return AKZ_OK;
-    }
-    std::vector<uint64_t> samples((size_t)num_trials * 4);
-    draw_samples<4>(default_source(), n_matches, num_trials, samples.data());
-    std::vector<Model> models((size_t)num_trials);
-    std::vector<int64_t> inliers((size_t)num_trials, -1);
-    std::vector<float> px0((size_t)n_matches), py0((size_t)n_matches), px1((size_t)n_matches), py1((size_t)n_matches);
-    for (uint64_t i = 0; i < n_matches; ++i) {
-        px0[(size_t)i] = keypoints_0[matches[i].index_0].x; py0[(size_t)i] = keypoints_0[matches[i].index_0].y;
-        px1[(size_t)i] = keypoints_1[matches[i].index_1].x; py1[(size_t)i] = keypoints_1[matches[i].index_1].y;
-    }
-    auto run_trials = [&](uint64_t lo, uint64_t hi) {
-        const float *x0 = px0.data(), *y0 = py0.data(), *x1 = px1.data(), *y1 = py1.data();
-        for (uint64_t trial = lo; trial < hi; ++trial) {
-            akz_match sample[4];
-            for (int i = 0; i < 4; ++i) sample[i] = matches[samples[(size_t)trial * 4 + i]];
-            Model model;
-            if (!estimate_h(keypoints_0, keypoints_1, sample, epsilon_model, model.f)) continue;
-            int64_t inl = 0;
-            for (uint64_t i = 0; i < n_matches; ++i) inl += homography_inlier(model.f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier) ? 1 : 0;
-            models[(size_t)trial] = model;
-            inliers[(size_t)trial] = inl;
-        }
-    };
-    const unsigned nthreads = (unsigned)std::min<uint64_t>(std::min(host_cpu_share(), 16u),
-                                                          std::max<uint64_t>(1, num_trials * (n_matches + 9000) / 2000000));
-    run_trials_pooled(num_trials, nthreads, run_trials);
-    int64_t max_inliers = 0;
-    uint64_t best = 0;
-    for (uint64_t trial = 0; trial < num_trials; ++trial)
-        if (inliers[(size_t)trial] > max_inliers) {
-            max_inliers = inliers[(size_t)trial];
-            best = trial;
-        }
-    uint64_t k = 0;
-    if (max_inliers == 0) {  // no model: everything is kept
-        std::memcpy(out, matches, n_matches * sizeof(akz_match));
-        k = n_matches;
-    } else {
-        const Model& md = models[(size_t)best];
-        for (uint64_t i = 0; i < n_matches; ++i)
-            if (homography_inlier(md.f, px0[(size_t)i], py0[(size_t)i], px1[(size_t)i], py1[(size_t)i], epsilon_inlier)) out[k++] = matches[i];
-        if (h) std::memcpy(h, md.f, sizeof(md.f));
-        if (found) *found = 1;
-    }
-    *n_out = k;
-    return AKZ_OK;
+    return ransac_host<HomographyRansac>("remove_outliers_homography", keypoints_0, n0, keypoints_1, n1, matches, n_matches, num_trials,
+                                         epsilon_model, epsilon_inlier, out, n_out, h, found, TrialsOnDevice());
 }
 
 // ---- the refit of a homography on its inliers (akz_homography_refit.hpp) ---------------------------------------
@@ -436,10 +381,7 @@ uint64_t classify(const float* x0, const float* y0, const float* x1, const float
 extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
                                      const akz_match* matches, uint64_t n_matches, const float* h_in, float epsilon_inlier,
                                      uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* h_out, uint32_t* iterations) {
-    if (!n_out || (n_matches && (!matches || !out))) {
-        set_error("refine_homography: null pointer");
-        return AKZ_ERR_INVALID_ARG;
-    }
+    AKZ_TRY(refuse_bad_matches("refine_homography", keypoints_0, n0, keypoints_1, n1, matches, n_matches, out, n_out));
     if (!h_in) {
         set_error("refine_homography: null h_in");
         return AKZ_ERR_INVALID_ARG;
@@ -448,17 +390,8 @@ extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n
         set_error("refine_homography: epsilon_inlier must be finite and > 0");
         return AKZ_ERR_INVALID_ARG;
     }
-    for (uint64_t i = 0; i < n_matches; ++i)
-        if (matches[i].index_0 >= n0 || matches[i].index_1 >= n1 || !keypoints_0 || !keypoints_1) {
-            set_error("refine_homography: match index out of range");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    std::vector<float> px0((size_t)n_matches), py0((size_t)n_matches), px1((size_t)n_matches), py1((size_t)n_matches);
-    for (uint64_t i = 0; i < n_matches; ++i) {
-        px0[(size_t)i] = keypoints_0[matches[i].index_0].x; py0[(size_t)i] = keypoints_0[matches[i].index_0].y;
-        px1[(size_t)i] = keypoints_1[matches[i].index_1].x; py1[(size_t)i] = keypoints_1[matches[i].index_1].y;
-    }
-    const float *x0 = px0.data(), *y0 = py0.data(), *x1 = px1.data(), *y1 = py1.data();
+    const MatchPoints pt(keypoints_0, keypoints_1, matches, n_matches);
+    const float *x0 = pt.x0, *y0 = pt.y0, *x1 = pt.x1, *y1 = pt.y1;
     float h[9];
     std::memcpy(h, h_in, sizeof(h));
     std::vector<uint8_t> member((size_t)n_matches), next((size_t)n_matches);

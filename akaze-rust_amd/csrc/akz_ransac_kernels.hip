@@ -1,0 +1,307 @@
+// The RANSAC of match_features on the GPU, for both models (akaze/src/ops/estimate_fundamental_matrix.rs:99-165, called from
+// akaze/src/lib.rs:267-274; the homography is an addition).  The reference runs num_trials x (model of a sample +
+// inlier count over every match) one after the other on one core; the host port of akz_ransac.cpp spreads the trials over
+// host threads.  Here the models come from the host's source (akz_fmatrix.hpp, akz_homography.hpp: f64 Jacobi rotations on
+// the 8 x 9 matrix, in LDS) through the one skeleton of akz_ransac_device.hpp.  Samples are always drawn on the host from the
+// calling thread's random source in trial order; what is formed here has the bits of the host path.
+//   k_ransac_trials                       akz_match_features: a workgroup per trial of one pair, winner and filter on the host
+//   k_pair_points, k_pairs_trials<Model, NW>, k_pairs_pick_filter<Model>
+//                                         the pairs calls: everything but the draws, over the pair records (PairJobHost)
+#include "akz_homography.hpp"
+#include "akz_ransac_device.hpp"
+
+namespace akz {
+namespace {
+
+using PairJob = launch::PairJobHost;
+
+constexpr int RT = 256;
+
+// pts: x0 | y0 | x1 | y1, n floats each; samples: 8 match indices per trial; out: per trial 9 floats (model) and the
+// inlier count (-1: no model).  The first wave forms the model, its lanes 0 .. 3 the rotations; the 256 threads count.
+__global__ void __launch_bounds__(RT) k_ransac_trials(const float* __restrict__ pts, unsigned n, const unsigned* __restrict__ samples,
+                                                      float epsilon_model, float epsilon_inlier, float* __restrict__ models,
+                                                      int* __restrict__ inliers) {
+    __shared__ float s_f[9];
+    __shared__ int s_ok, s_cnt;
+    __shared__ double s_m[8 * 9];
+    const unsigned trial = blockIdx.x, tid = threadIdx.x;
+    const float *x0 = pts, *y0 = pts + n, *x1 = pts + 2 * (size_t)n, *y1 = pts + 3 * (size_t)n;
+    if (tid < 64) {
+        LdsMat m{s_m};
+        if (tid == 0) {
+            float sx0[8], sy0[8], sx1[8], sy1[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const unsigned j = samples[(size_t)trial * 8 + i];
+                sx0[i] = x0[j]; sy0[i] = y0[j]; sx1[i] = x1[j]; sy1[i] = y1[j];
+            }
+            design_matrix(m, sx0, sy0, sx1, sy1);
+        }
+        wave_sync();
+        for (int sweep = 0; sweep < 60; ++sweep)
+            if (__ballot(jacobi_sweep_levels<8>(m, (int)tid, tid < 4)) == 0ull) break;
+        if (tid == 0) {
+            float f[9];
+            const bool ok = model_from_rotated(m, epsilon_model, f);
+            s_ok = ok ? 1 : 0;
+            s_cnt = 0;
+            if (ok) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    s_f[k] = f[k];
+                    models[(size_t)trial * 9 + k] = f[k];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (!s_ok) {
+        if (tid == 0) inliers[trial] = -1;
+        return;
+    }
+    float f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = s_f[k];
+    int cnt = 0;
+    for (unsigned i = tid; i < n; i += RT) cnt += fundamental_error(f, x0[i], y0[i], x1[i], y1[i]) < epsilon_inlier ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((tid & 63u) == 0) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (tid == 0) inliers[trial] = s_cnt;
+}
+
+// ---- the pairs calls -------------------------------------------------------------------------------------------------------
+// x0 | y0 | x1 | y1 of every match of every pair (the four arrays the host path builds), at the pair's offset of the matches:
+// a workgroup per pair (grid-stride over pairs), a thread per match
+__global__ void __launch_bounds__(256) k_pair_points(const PairJob* __restrict__ pairs, unsigned n_pairs, const akz_match* __restrict__ raw,
+                                                     const unsigned long long* __restrict__ raw_cnt, const float* __restrict__ kx,
+                                                     const float* __restrict__ ky, float* __restrict__ pts, unsigned long long stride) {
+    for (unsigned p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+        const PairJob pj = pairs[p];
+        const unsigned long long n = raw_cnt[pj.cnt_idx];
+        for (unsigned long long i = threadIdx.x; i < n; i += blockDim.x) {
+            const akz_match m = raw[pj.raw_off + i];
+            const size_t o = pj.raw_off + i, a = pj.kp0_off + m.index_0, b = pj.kp1_off + m.index_1;
+            pts[o] = kx[a];
+            pts[stride + o] = ky[a];
+            pts[2 * stride + o] = kx[b];
+            pts[3 * stride + o] = ky[b];
+        }
+    }
+}
+
+// The device half of a model (the host half: FundamentalRansac / HomographyRansac): how the four lanes of a trial write its
+// design rows (false: the sample gives no model, the trial never sweeps), what they keep beside the matrix, and the model
+// from the rotated matrix on one lane.
+struct FundamentalDev : FundamentalRansac {
+    struct Side {};
+    // rows sub and sub + 4; every sample is usable
+    static __device__ bool rows(LdsMat m, Side&, int sub, const unsigned* smp, size_t off, const float* pts, unsigned long long stride) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = sub + 4 * h;
+            const size_t j = off + smp[i];
+            design_row(m, i, pts[j], pts[stride + j], pts[2 * stride + j], pts[3 * stride + j]);
+        }
+        return true;
+    }
+    static __device__ bool model(LdsMat m, const Side&, float epsilon, float (&f)[9]) { return model_from_rotated(m, epsilon, f); }
+};
+struct HomographyDev : HomographyRansac {
+    struct Side {
+        double v[6];  // c0x, c0y, s0, c1x, c1y, s1
+    };
+    // each lane loads the whole sample and forms its normalisation and degeneracy test itself (the same operands in the same
+    // order: the same bits on all four), then writes the two rows of its own correspondence
+    static __device__ bool rows(LdsMat m, Side& side, int sub, const unsigned* smp, size_t off, const float* pts, unsigned long long stride) {
+        float x0[4], y0[4], x1[4], y1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const size_t j = off + smp[i];
+            x0[i] = pts[j]; y0[i] = pts[stride + j]; x1[i] = pts[2 * stride + j]; y1[i] = pts[3 * stride + j];
+        }
+        HomSample hs;
+        if (!hom_prepare(x0, y0, x1, y1, hs)) return false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (i == sub) hom_rows(m, i, hs.x0[i], hs.y0[i], hs.x1[i], hs.y1[i]);
+        if (sub == 0) {
+            side.v[0] = hs.c0x; side.v[1] = hs.c0y; side.v[2] = hs.s0;
+            side.v[3] = hs.c1x; side.v[4] = hs.c1y; side.v[5] = hs.s1;
+        }
+        return true;
+    }
+    static __device__ bool model(LdsMat m, const Side& t, float epsilon, float (&h)[9]) {
+        return hom_model_from_rotated(m, epsilon, t.v[0], t.v[1], t.v[2], t.v[3], t.v[4], t.v[5], h);
+    }
+};
+
+// Trials first_trial .. + n_trials of a pairs call.  TPW trials per wave, four lanes per trial: a batch has ~10^5 trials, and a
+// workgroup per trial with four busy lanes held a few thousand of them on the chip.  The sweeps run on each trial's four
+// lanes, each trial leaving at its own first sweep without a rotation (its four ballot bits); the model is formed on one lane
+// per trial; the wave then counts the inliers of its trials one after the other with all 64 lanes.  Output per trial: the
+// model (9 floats) and the inlier count, or -1 (no model).
+// NW > 1: the workgroup has NW - 1 more waves that only help count (a launch of few trials -- one pair, 1 000 trials, is 63
+// waves -- leaves most of the chip idle while each wave counts 16 trials over every match: single homography calls on 4K pairs
+// took 1.8x the fundamental-matrix call's time with one wave).  Counts are integers: the same for every NW.
+constexpr int TPW = 16;  // trials per wave
+constexpr int TW = 64;
+template <class Model, int NW>
+__global__ void __launch_bounds__(TW * NW) k_pairs_trials(const PairJob* __restrict__ pairs, const unsigned* __restrict__ trials,
+                                                          unsigned long long first_trial, unsigned n_trials,
+                                                          const unsigned long long* __restrict__ raw_cnt, const float* __restrict__ pts,
+                                                          unsigned long long stride, float epsilon_model, float epsilon_inlier,
+                                                          float* __restrict__ models, int* __restrict__ inliers) {
+    constexpr int K = Model::K;
+    __shared__ double s_m[TPW][8 * 9];
+    __shared__ typename Model::Side s_side[TPW];
+    __shared__ float s_f[TPW][9];
+    __shared__ int s_ok[TPW];
+    __shared__ int s_cnt[TPW];
+    const int tid = (int)threadIdx.x, lane = tid & (TW - 1), tw = lane >> 2, sub = lane & 3;
+    const unsigned t0 = blockIdx.x * TPW, tl = t0 + (unsigned)tw;
+    if (NW == 1 || tid < TW) {  // the models: the first wave
+        const bool valid = tl < n_trials;
+        LdsMat m{s_m[tw]};
+        bool usable = false;
+        if (valid) usable = Model::rows(m, s_side[tw], sub, trials + (size_t)tl * K, pairs[trials[(size_t)n_trials * K + tl]].raw_off, pts, stride);
+        wave_sync();
+        bool active = usable;
+        for (int sweep = 0; sweep < 60; ++sweep) {
+            if (__ballot(active) == 0ull) break;
+            const bool rotated = jacobi_sweep_levels<8>(m, sub, active);
+            if (((__ballot(rotated) >> (4 * tw)) & 0xfull) == 0ull) active = false;  // this trial's first sweep without a rotation
+        }
+        if (valid && sub == 0) {
+            float f[9];
+            const bool ok = usable && Model::model(m, s_side[tw], epsilon_model, f);
+            const size_t t = first_trial + tl;
+            s_ok[tw] = ok ? 1 : 0;
+            if (NW > 1) s_cnt[tw] = 0;
+            if (ok) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    s_f[tw][k] = f[k];
+                    models[t * 9 + k] = f[k];
+                }
+            } else {
+                inliers[t] = -1;
+            }
+        }
+    }
+    if (NW == 1) wave_sync();
+    else __syncthreads();
+    for (int u = 0; u < TPW; ++u) {
+        const unsigned t = t0 + (unsigned)u;
+        if (t >= n_trials) break;
+        if (!s_ok[u]) continue;
+        const PairJob pj = pairs[trials[(size_t)n_trials * K + t]];
+        const unsigned n = (unsigned)raw_cnt[pj.cnt_idx];
+        const float *x0 = pts + pj.raw_off, *y0 = x0 + stride, *x1 = y0 + stride, *y1 = x1 + stride;
+        float f[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = s_f[u][k];
+        int cnt = 0;
+        for (unsigned i = (unsigned)tid; i < n; i += TW * NW) cnt += Model::inlier(f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier) ? 1 : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        if (NW == 1) {
+            if (lane == 0) inliers[first_trial + t] = cnt;
+        } else if (lane == 0) {
+            atomicAdd(&s_cnt[u], cnt);
+        }
+    }
+    if (NW > 1) {
+        __syncthreads();
+        if (tid < TPW && t0 + (unsigned)tid < n_trials && s_ok[tid]) inliers[first_trial + t0 + tid] = s_cnt[tid];
+    }
+}
+
+// Per pair (a workgroup, grid-stride): the winner among its trials (pick_winner; fewer than K matches: none), and the matches
+// it keeps (Model::inlier, as the host's final filter), compacted in match order.  Fewer than K matches: all kept.  No winner:
+// the zero model is evaluated, or (kKeepAllWithoutWinner) all kept.  kModelOut: the winner's H or zeros, and found.
+template <class Model>
+__global__ void __launch_bounds__(kGroup) k_pairs_pick_filter(const PairJob* __restrict__ pairs, unsigned n_pairs, const akz_match* __restrict__ raw,
+                                                              const unsigned long long* __restrict__ raw_cnt, const float* __restrict__ pts,
+                                                              unsigned long long stride, const float* __restrict__ models,
+                                                              const int* __restrict__ inliers, float epsilon_inlier, akz_match* __restrict__ keep,
+                                                              unsigned long long* __restrict__ keep_cnt, float* __restrict__ h_out,
+                                                              int* __restrict__ found_out) {
+    __shared__ int s_best[kGroup / 64];
+    __shared__ unsigned long long s_idx[kGroup / 64];
+    __shared__ unsigned s_wsum[kGroup / 64];
+    __shared__ float s_f[9];
+    __shared__ int s_found;
+    const unsigned tid = threadIdx.x;
+    for (unsigned p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+        const PairJob pj = pairs[p];
+        const unsigned long long n = raw_cnt[pj.cnt_idx];
+        const Winner win = pick_winner(inliers, pj.trial_off, pj.n_trials, n >= (unsigned long long)Model::K, s_best, s_idx, tid);
+        if (tid == 0) {
+            const int found = win.best > 0 ? 1 : 0;
+            if (Model::kKeepAllWithoutWinner) s_found = found;
+            for (int k = 0; k < 9; ++k) {
+                s_f[k] = found ? models[(pj.trial_off + win.bidx) * 9 + k] : 0.0f;
+                if (Model::kModelOut) h_out[(size_t)p * 9 + k] = s_f[k];
+            }
+            if (Model::kModelOut) found_out[p] = found;
+        }
+        __syncthreads();
+        const bool all = n < (unsigned long long)Model::K || (Model::kKeepAllWithoutWinner && s_found == 0);
+        float f[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = s_f[k];
+        const float *x0 = pts + pj.raw_off, *y0 = x0 + stride, *x1 = y0 + stride, *y1 = x1 + stride;
+        unsigned long long written = 0;
+        for (unsigned long long base = 0; base < n; base += kGroup) {
+            const unsigned long long i = base + tid;
+            const bool kept = i < n && (all || Model::inlier(f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier));
+            compact_kept(kept, raw + pj.raw_off + i, keep + pj.keep_off, written, s_wsum, tid);
+        }
+        if (tid == 0) keep_cnt[p] = written;
+    }
+}
+
+}  // namespace
+
+namespace launch {
+void pair_points(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+                 const float* d_kx, const float* d_ky, float* d_pts, uint64_t pts_stride) {
+    if (n_pairs == 0) return;
+    hipLaunchKernelGGL(k_pair_points, dim3(std::min<uint32_t>(n_pairs, 8192)), dim3(256), 0, s, d_pairs, n_pairs, (const akz_match*)d_raw,
+                       (const unsigned long long*)d_raw_cnt, d_kx, d_ky, d_pts, (unsigned long long)pts_stride);
+}
+void pairs_trials(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, const uint32_t* d_trials, uint64_t first_trial,
+                  uint32_t n_trials, const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, float epsilon_model,
+                  float epsilon_inlier, float* d_models, int32_t* d_inliers) {
+    if (n_trials == 0) return;
+    // the fundamental matrix: one wave per workgroup, the waves share nothing.  The homography with fewer workgroups than half
+    // the chip's SIMDs (256 CUs x 4): three helper waves per workgroup for the counts
+    const uint32_t blocks = (n_trials + TPW - 1) / TPW;
+    auto k = model == RansacModel::Fundamental ? k_pairs_trials<FundamentalDev, 1>
+             : blocks < 512                    ? k_pairs_trials<HomographyDev, 4>
+                                               : k_pairs_trials<HomographyDev, 1>;
+    const uint32_t nw = model == RansacModel::Homography && blocks < 512 ? 4 : 1;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(TW * nw), 0, s, d_pairs, d_trials, (unsigned long long)first_trial, n_trials,
+                       (const unsigned long long*)d_raw_cnt, d_pts, (unsigned long long)pts_stride, epsilon_model, epsilon_inlier, d_models,
+                       d_inliers);
+}
+void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw,
+                       const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers,
+                       float epsilon_inlier, void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found) {
+    if (n_pairs == 0) return;
+    auto k = model == RansacModel::Fundamental ? k_pairs_pick_filter<FundamentalDev> : k_pairs_pick_filter<HomographyDev>;
+    hipLaunchKernelGGL(k, dim3(std::min<uint32_t>(n_pairs, 8192)), dim3(kGroup), 0, s, d_pairs, n_pairs, (const akz_match*)d_raw,
+                       (const unsigned long long*)d_raw_cnt, d_pts, (unsigned long long)pts_stride, d_models, d_inliers, epsilon_inlier,
+                       (akz_match*)d_keep, (unsigned long long*)d_keep_cnt, d_h, d_found);
+}
+void ransac_trials(hipStream_t s, const float* d_pts, uint32_t n_matches, const uint32_t* d_samples, uint32_t trials, float epsilon_model,
+                   float epsilon_inlier, float* d_models, int32_t* d_inliers) {
+    if (trials == 0) return;
+    hipLaunchKernelGGL(k_ransac_trials, dim3(trials), dim3(RT), 0, s, d_pts, n_matches, d_samples, epsilon_model, epsilon_inlier, d_models,
+                       d_inliers);
+}
+}  // namespace launch
+}  // namespace akz

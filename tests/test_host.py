@@ -377,6 +377,28 @@ def test_remove_outliers_host(amd, ref):
         amd.remove_outliers(k0, k1, bad, 10, 0.05, 3.0)
 
 
+def test_no_winner_rules_of_the_two_models(amd):
+    """No trial with an inlier (here: no trial at all).  The fundamental matrix evaluates the zero model, whose error 0 is
+    below epsilon only if 0 < epsilon; the homography keeps every match whatever epsilon is and reports found = 0.  Neither
+    call draws from the random source."""
+    import ctypes as C
+    def color():
+        rgb = (C.c_uint8 * 3)()
+        assert amd.lib().akz_random_color(rgb) == 0
+        return bytes(rgb)
+    k0, k1, m = _two_view_scene(40, 5, 4)
+    assert len(m) >= 8
+    amd.random_seed(42, 69)
+    fresh = color()
+    amd.random_seed(42, 69)
+    assert len(amd.remove_outliers(k0, k1, m, 0, 0.05, 0.0)) == 0
+    assert np.array_equal(amd.remove_outliers(k0, k1, m, 0, 0.05, 3.0), m)
+    for eps in (0.0, 3.0):
+        kept, h = amd.remove_outliers_homography(k0, k1, m, 0, amd.HOMOGRAPHY_EPSILON_MODEL, eps)
+        assert np.array_equal(kept, m) and h is None, eps
+    assert color() == fresh
+
+
 def test_features_and_matches_file_formats(amd, tmp_path):
     """akaze-util's on-disk formats (akaze-util/src/lib.rs:10-67): bincode 1.x bytes checked against a
     hand-built struct.pack image, serde_json schema checked with the json module, both round-trip."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The homography RANSAC calls against the fundamental-matrix calls, and this build's F path against another build's.
+"""The homography RANSAC calls against the fundamental-matrix calls, and this build's two paths against another build's.
 
     timeout -k 10 900 python tools/homography_ransac.py --baseline OTHER/akaze-rust_amd [--rounds 5] [--out FILE]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/homography_ransac.py --trace
@@ -11,9 +11,10 @@ pairs call (akz_match_features_pairs / akz_match_features_homography_pairs), med
 pairs call's host draw time (akz_debug_match_pairs_split).
 
 Every measurement runs in a child process of one build and one model; a round runs, in this order, the baseline's F, this
-build's F, this build's H and the baseline's F again (the baseline against itself: the spread).  The report holds the
-medians over --rounds rounds, the ratios H / F (this build) and F (this build) / F (baseline), and the spread.  Prints one
-JSON document (and writes it to --out if given).  --trace: one pass of every call of this build, both models."""
+build's F, the baseline's H, this build's H and the baseline's F and H again (the baseline against itself: the spread).  The
+report holds the medians over --rounds rounds, the ratios H / F (this build), F / F and H / H (this build over the baseline),
+and the baseline's spread per model.  Prints one JSON document (and writes it to --out if given).  --trace: one pass of every
+call of this build, both models."""
 import argparse
 import ctypes as C
 import json
@@ -87,7 +88,7 @@ def child(pkg, model, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--baseline", help="akaze-rust_amd directory of the build to compare the F path against")
+    ap.add_argument("--baseline", help="akaze-rust_amd directory of the build to compare against")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -102,7 +103,8 @@ def main():
         child(here, "F", 1)
         child(here, "H", 1)
         return
-    legs = [("base_F", args.baseline, "F"), ("F", here, "F"), ("H", here, "H"), ("base_F_again", args.baseline, "F")]
+    legs = [("base_F", args.baseline, "F"), ("F", here, "F"), ("base_H", args.baseline, "H"), ("H", here, "H"),
+            ("base_F_again", args.baseline, "F"), ("base_H_again", args.baseline, "H")]
     runs = {k: [] for k, _, _ in legs}
     for r in range(args.rounds):
         for key, pkg, model in legs:
@@ -123,8 +125,9 @@ def main():
             if med["H"][wl][m] is None:
                 continue
             row[f"H_over_F_{m}"] = round(med["H"][wl][m] / med["F"][wl][m], 3)
-            row[f"F_over_base_{m}"] = round(med["F"][wl][m] / med["base_F"][wl][m], 3)
-            row[f"base_spread_{m}"] = round(abs(med["base_F_again"][wl][m] / med["base_F"][wl][m] - 1.0), 3)
+            for k in "FH":
+                row[f"{k}_over_base_{m}"] = round(med[k][wl][m] / med[f"base_{k}"][wl][m], 3)
+                row[f"base_{k}_again_over_base_{m}"] = round(med[f"base_{k}_again"][wl][m] / med[f"base_{k}"][wl][m], 3)
         ratios[wl] = row
     import torch
     doc = {"tool": "tools/homography_ransac.py", "device": torch.cuda.get_device_name(0), "trials": TRIALS, "epsilon": EPS,

@@ -2,7 +2,7 @@
 """What the refit stage costs: akz_match_features_homography_refined with 1 and with 8 iterations against
 akz_match_features_homography of the same build, on the same inputs and seed.
 
-    timeout -k 10 1100 python tools/homography_refit.py [--rounds 7] [--reps 5] [--out profiles/r12_homography_refit.json]
+    timeout -k 10 1100 python tools/homography_refit.py [--baseline OTHER/akaze-rust_amd] [--rounds 7] [--reps 5] [--out FILE]
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/homography_refit.py --trace
 
 Workloads of tools/homography_ransac.py (synth_frame features of one scene with shifts; 1 000 trials, epsilon 3.0, ratio
@@ -13,7 +13,8 @@ and for the pairs calls the pick / filter interval of akz_debug_match_pairs_spli
 Every measurement runs in a child process of its own; a round runs, in this order, the unrefined call, 1 iteration, 8
 iterations and the unrefined call again (the baseline against itself: the spread, i.e. the noise floor).  The report holds
 the medians over --rounds rounds, the ratios refined / unrefined and the spread.  Prints one JSON document (and writes it to
---out if given).  --trace: one pass of every call."""
+--out if given).  --baseline: every leg also runs on that build, right before this build's, and the report adds the ratios this
+build / baseline and the baseline's unrefined call against itself.  --trace: one pass of every call."""
 import argparse
 import ctypes as C
 import json
@@ -28,8 +29,8 @@ TRIALS, EPS, RATIO = 1000, 3.0, 0.86
 CASES = ("1 pair 1080p", "4K pairs, single calls", "4K pairs, pairs call", "exhaustive 16 x 1080p")
 
 
-def child(its, reps):
-    sys.path.insert(0, os.path.join(ROOT, "akaze-rust_amd", "python"))
+def child(pkg, its, reps):
+    sys.path.insert(0, os.path.join(pkg, "python"))
     import akaze_amd as A
     import torch
     ctx = A.Context(0, torch.cuda.current_stream().cuda_stream)
@@ -88,24 +89,30 @@ def child(its, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--baseline", help="akaze-rust_amd directory of a build to compare against")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true")
-    ap.add_argument("--child", metavar="ITERATIONS", help=argparse.SUPPRESS)
+    ap.add_argument("--child", nargs=2, metavar=("PKG", "ITERATIONS"), help=argparse.SUPPRESS)
     args = ap.parse_args()
+    here = os.path.join(ROOT, "akaze-rust_amd")
     if args.child:
-        print(json.dumps(child(None if args.child == "none" else int(args.child), args.reps)))
+        print(json.dumps(child(args.child[0], None if args.child[1] == "none" else int(args.child[1]), args.reps)))
         return
     if args.trace:
         for its in (None, 1, 8):
-            child(its, 1)
+            child(here, its, 1)
         return
-    legs = [("unrefined", "none"), ("refined_1", "1"), ("refined_8", "8"), ("unrefined_again", "none")]
-    runs = {k: [] for k, _ in legs}
+    legs = []
+    for key, its in (("unrefined", "none"), ("refined_1", "1"), ("refined_8", "8"), ("unrefined_again", "none")):
+        if args.baseline:
+            legs.append(("base_" + key, args.baseline, its))
+        legs.append((key, here, its))
+    runs = {k: [] for k, _, _ in legs}
     for r in range(args.rounds):
-        for key, its in legs:
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", its, "--reps", str(args.reps)], check=True,
+        for key, pkg, its in legs:
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", pkg, its, "--reps", str(args.reps)], check=True,
                                  capture_output=True, text=True, timeout=300).stdout
             runs[key].append(json.loads(out.strip().splitlines()[-1]))
             print(f"round {r} {key}: {runs[key][-1]}", file=sys.stderr, flush=True)
@@ -118,6 +125,10 @@ def main():
                "unrefined_self_spread": round(abs(med["unrefined_again"][wl]["ms"] / base["ms"] - 1.0), 3)}
         if "pick_filter_refit_ms" in base:
             row["pick_filter_refit_ms"] = {k: round(med[k][wl]["pick_filter_refit_ms"], 4) for k in med}
+        if args.baseline:
+            for k in ("unrefined", "refined_1", "refined_8"):
+                row[f"{k}_over_base"] = round(med[k][wl]["ms"] / med["base_" + k][wl]["ms"], 3)
+            row["base_unrefined_again_over_base"] = round(med["base_unrefined_again"][wl]["ms"] / med["base_unrefined"][wl]["ms"], 3)
         ratios[wl] = row
     import torch
     doc = {"tool": "tools/homography_refit.py", "device": torch.cuda.get_device_name(0), "trials": TRIALS, "epsilon": EPS,
