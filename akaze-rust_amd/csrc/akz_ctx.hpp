@@ -490,11 +490,11 @@ AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::v
 struct GuidedPairSpec {
     uint64_t q_row0, n0, t_row0, n1, out_off;
 };
-struct GuidedStage {  // the second stage of akz_match_features_homography_guided(_pairs)
+struct GuidedStage {  // the second stage of akz_match_features_{homography,fundamental}_guided(_pairs)
     float radius;
     double ratio;
 };
-struct RefineStage {  // the refit stage of akz_match_features_homography_refined(_pairs): launch::homography_refit after the pick
+struct RefineStage {  // the refit stage of akz_match_features_{homography,fundamental}_refined(_pairs): launch::model_refit after the pick
     uint32_t max_iterations;
     uint32_t* iterations;  // one per pair, may be null
 };

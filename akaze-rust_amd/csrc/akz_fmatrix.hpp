@@ -137,6 +137,7 @@ struct FundamentalRansac {
     static constexpr int K = 8;                           // matches per sample, and the least a call works on
     static constexpr bool kKeepAllWithoutWinner = false;  // no trial with an inlier: the zero model is evaluated (error 0)
     static constexpr bool kModelOut = false;              // the call hands back no model
+    static constexpr bool kZeroModelOut = false;          // (with kModelOut: zeros are written where there is no winner)
     static AKZ_HD bool from_sample(const float (&x0)[8], const float (&y0)[8], const float (&x1)[8], const float (&y1)[8], float epsilon,
                                    float (&f)[9]) {
         return fundamental_from_8(x0, y0, x1, y1, epsilon, f);
@@ -144,6 +145,13 @@ struct FundamentalRansac {
     static AKZ_HD bool inlier(const float (&f)[9], float x0, float y0, float x1, float y1, float eps) {
         return fundamental_error(f, x0, y0, x1, y1) < eps;
     }
+};
+
+// The same model for the calls that hand the winner back (akz_remove_outliers_fundamental, akz_match_features_fundamental*):
+// f and found are written; without a winner f is the zero model that was evaluated
+struct FundamentalRansacModelOut : FundamentalRansac {
+    static constexpr bool kModelOut = true;
+    static constexpr bool kZeroModelOut = true;
 };
 
 // The gate of guided matching for a fundamental matrix (akz_descriptor_match_guided, model_kind 1): the point

@@ -188,6 +188,7 @@ struct HomographyRansac {
     static constexpr int K = 4;
     static constexpr bool kKeepAllWithoutWinner = true;  // no trial with an inlier: every match is kept whatever epsilon is
     static constexpr bool kModelOut = true;              // H and found are handed back (found = 0: H zeros on the device)
+    static constexpr bool kZeroModelOut = false;         // (the host leaves h alone where there is no winner)
     static AKZ_HD bool from_sample(const float (&x0)[4], const float (&y0)[4], const float (&x1)[4], const float (&y1)[4], float epsilon,
                                    float (&h)[9]) {
         return homography_from_4(x0, y0, x1, y1, epsilon, h);

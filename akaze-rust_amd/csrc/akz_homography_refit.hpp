@@ -1,6 +1,6 @@
 // Local optimisation of the winning homography: the least-squares refit on its inliers and the re-classification, as ONE
 // piece of source for the host statement (akz_refine_homography, akz_ransac.cpp) and the device kernel
-// (k_homography_refit, akz_homography_refit.hip), like akz_homography.hpp for the trial model: f64 in a fixed order, no
+// (k_refit<HomographyRefit>, akz_homography_refit.hip), like akz_homography.hpp for the trial model: f64 in a fixed order, no
 // contraction, the same bits on both sides.
 //
 // The loop, over a pair's RAW match list (the set can grow):
@@ -135,18 +135,37 @@ AKZ_HD bool refit_model_from_rotated(M& m, double count, float epsilon_model, do
     if (!full) return false;
     return hom_model_from_rows(m, c0x, c0y, s0, c1x, c1y, s1, h);
 }
-// the model from M: the row-cyclic sweeps over its 9 rows, then the above (the host; the device runs the same rotations level
-// by level on four lanes, see jacobi_sweep_levels)
-template <class M>
-AKZ_HD bool refit_model_from_normal(M& m, double count, float epsilon_model, double c0x, double c0y, double s0, double c1x, double c1y,
-                                    double s1, float (&h)[9]) {
-    jacobi_sweeps_rows<9>(m);
-    return refit_model_from_rotated(m, count, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, h);
-}
+// (the sweeps before it: jacobi_sweeps_rows<9> on the host; the device runs the same rotations level by level on four lanes,
+// see jacobi_sweep_levels)
 
 struct Mat9x9 {
     double v[9][9];
     AKZ_HD double& at(int p, int k) { return v[p][k]; }
+};
+
+// The homography as a REFIT model: what the loop above needs from a model, for the host loop (akz_ransac.cpp) and the refit
+// kernel (akz_homography_refit.hip) alike -- the fewest members of a fit (and matches of a pair the stage works on), the
+// inlier rule, the terms of pass 3, M from their sums and the model from the rotated M.  Passes 1 and 2 are the same for
+// every model.  (FundamentalRefit of akz_fundamental_refit.hpp is the other one.)
+struct HomographyRefit {
+    static constexpr int kMin = 4;
+    static constexpr int kSums3 = kRefitSums3;
+    static AKZ_HD bool inlier(const float (&h)[9], float x0, float y0, float x1, float y1, float eps) {
+        return homography_inlier(h, x0, y0, x1, y1, eps);
+    }
+    static AKZ_HD void terms3(float x0, float y0, float x1, float y1, double c0x, double c0y, double s0, double c1x, double c1y, double s1,
+                              double (&t)[kSums3]) {
+        refit_terms3(x0, y0, x1, y1, c0x, c0y, s0, c1x, c1y, s1, t);
+    }
+    template <class M>
+    static AKZ_HD void normal_matrix(M& m, const double* sums) {
+        refit_normal_matrix(m, sums);
+    }
+    template <class M>
+    static AKZ_HD bool model_from_rotated(M& m, double count, float epsilon_model, double c0x, double c0y, double s0, double c1x, double c1y,
+                                          double s1, float (&h)[9]) {
+        return refit_model_from_rotated(m, count, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, h);
+    }
 };
 
 }  // namespace akz

@@ -375,15 +375,16 @@ void pairs_trials(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, 
                   float epsilon_inlier, float* d_models, int32_t* d_inliers);
 // per pair: the first trial with the most inliers (strict `>` from 0 in trial order), then the matches it keeps, compacted in
 // order at d_keep + keep_off, their count at d_keep_cnt[pair] (fewer than K matches: all of them).  No trial above 0 -- the
-// fundamental matrix: the zero model filters; the homography: every match kept.  The homography also leaves the winner's H at
-// d_h + 9 pair (none: zeros) and found at d_found[pair]; both are null for the fundamental matrix.
+// fundamental matrix: the zero model filters; the homography: every match kept.  A call that hands the model back also gets the
+// winner's model at d_h + 9 pair (none: zeros) and found at d_found[pair]; both are null for akz_match_features_pairs.
 void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw,
                        const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers,
                        float epsilon_inlier, void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found);
-// the refit stage after the homography's pairs_pick_filter (akz_homography_refit.hip): per pair with found = 1 and 4 matches or more, the
-// loop of akz_homography_refit.hpp on the raw list from the H at d_h + 9 pair; after an accepted fit H, the kept list and its
-// count are rewritten; d_iterations[pair] = accepted fits (0 for the pairs left alone)
-void homography_refit(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
+// the refit stage after pairs_pick_filter (akz_homography_refit.hip), for a model that was handed back: per pair with found = 1
+// and 4 (the fundamental matrix: 8) matches or more, the loop of akz_homography_refit.hpp (akz_fundamental_refit.hpp) on the raw
+// list from the model at d_h + 9 pair; after an accepted fit the model, the kept list and its count are rewritten;
+// d_iterations[pair] = accepted fits (0 for the pairs left alone).  epsilon_model: that of the model's rank rule
+void model_refit(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                       const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
                       void* d_keep, uint64_t* d_keep_cnt, float* d_h, const int32_t* d_found, uint32_t* d_iterations);
 void unpack_pair(hipStream_t s, const uint8_t* dq, uint32_t nq, uint32_t q_pad, uint8_t* outq, uint32_t* popq, uint32_t* bound, uint32_t threshold,

@@ -474,13 +474,21 @@ struct FundamentalModel {  // akz_match_features_pairs
     static constexpr int K = 8;
     static constexpr bool kModelOut = false;
     static constexpr float kEpsilonModel = 0.05f;
+    static constexpr float kRefitEpsilon = AKZ_FUNDAMENTAL_REFIT_EPSILON;  // the rank rule of the refit stage
+    static constexpr int kGuidedKind = AKZ_GUIDED_FUNDAMENTAL;            // the gate of the guided stage
     static constexpr const char* kName = "match_features_pairs: ";
+};
+struct FundamentalModelOut : FundamentalModel {  // akz_match_features_fundamental*(_pairs): F and found are read back too
+    static constexpr bool kModelOut = true;
+    static constexpr const char* kName = "match_features_fundamental_pairs: ";
 };
 struct HomographyModel {  // akz_match_features_homography(_pairs)
     static constexpr launch::RansacModel kKind = launch::RansacModel::Homography;
     static constexpr int K = 4;
     static constexpr bool kModelOut = true;
     static constexpr float kEpsilonModel = AKZ_HOMOGRAPHY_EPSILON_MODEL;
+    static constexpr float kRefitEpsilon = AKZ_HOMOGRAPHY_EPSILON_MODEL;
+    static constexpr int kGuidedKind = AKZ_GUIDED_HOMOGRAPHY;
     static constexpr const char* kName = "match_features_homography_pairs: ";
 };
 
@@ -488,23 +496,25 @@ struct HomographyModel {  // akz_match_features_homography(_pairs)
 // keypoint x / y through pinned staging; the descriptor scans (one multi-set launch per first set, or the pair matcher for
 // rows of 62..64 bytes); k_pair_points; ONE read-back of the match counts; the samples drawn on the calling thread in pair
 // order, in chunks whose trials (launch::pairs_trials) run while the next chunk is drawn; launch::pairs_pick_filter; ONE read-back of the
-// kept lists (and, for a model that is handed back, every pair's model and found flag).  A RefineStage puts the refit kernel
-// between the pick and that read-back: it rewrites H, the kept lists and their counts in place and adds every pair's number of
-// accepted fits to the head that the read-back carries; the guided stage then reads the H table it has rewritten.
+// kept lists (and, for a model that is handed back, every pair's model and found flag).  A RefineStage puts the refit kernel of
+// the model's kind between the pick and that read-back: it rewrites the models, the kept lists and their counts in place and
+// adds every pair's number of accepted fits to the head that the read-back carries; the guided stage, gating with the model's
+// kind, then reads the model table it has rewritten.  Both stages need a model that is handed back (kModelOut).
 template <class Model>
 int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
                      double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out, float* model_out,
-                     int* found_out, const GuidedStage* guided = nullptr, const RefineStage* refine = nullptr) {
+                     int* found_out, const GuidedStage* guided = nullptr, const RefineStage* refine = nullptr,
+                     const char* name = Model::kName) {  // name: the prefix of the entry point's error texts
     constexpr int K = Model::K;
     if (n_pairs == 0) return AKZ_OK;
     if (guided && !(guided->radius >= 0.0f && std::isfinite(guided->radius))) {
-        set_error(std::string(Model::kName) + "guided_radius must be finite and >= 0");
+        set_error(std::string(name) + "guided_radius must be finite and >= 0");
         return AKZ_ERR_INVALID_ARG;
     }
     std::vector<uint8_t> seen;
     uint64_t cap = 0;
-    AKZ_TRY(pairs_validate(Model::kName, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
-    if (guided) AKZ_TRY(guided_limits(Model::kName, sets, pairs, n_pairs, seen));
+    AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
+    if (guided) AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
     AKZ_TRY(bind(c, true, false));
     const bool timed = c->mp_split_on;
     if (timed)
@@ -684,14 +694,14 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
                               d_kcnt, Model::kModelOut ? d_hm : nullptr, Model::kModelOut ? d_hf : nullptr);
     AKZ_HIP_TRY(hipGetLastError());
     if (Model::kModelOut && refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
-        launch::homography_refit(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, Model::kEpsilonModel, ransac_epsilon_inliers,
-                                 refine->max_iterations, d_keep, d_kcnt, d_hm, d_hf, d_it);
+        launch::model_refit(st, Model::kKind, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, Model::kRefitEpsilon, ransac_epsilon_inliers,
+                            refine->max_iterations, d_keep, d_kcnt, d_hm, d_hf, d_it);
         AKZ_HIP_TRY(hipGetLastError());
     }
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
     AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_head + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
-    // the guided stage: every pair scanned again with the H that the pick kernel left on the device (pairs without one give
+    // the guided stage: every pair scanned again with the model (H or F) that the pick kernel left on the device (pairs without one give
     // empty lists that nobody reads); the sets are those uploaded above
     akz_match* d_gout = nullptr;
     if (guided) {
@@ -706,7 +716,7 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
             spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
             off += sets[a].n_descriptors;
         }
-        AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, AKZ_GUIDED_HOMOGRAPHY, d_hm, d_hf, guided->radius, 10000, guided->ratio, d_gout,
+        AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, Model::kGuidedKind, d_hm, d_hf, guided->radius, 10000, guided->ratio, d_gout,
                                d_gcnt));
         AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_cnt.p, d_gcnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     }
@@ -918,5 +928,105 @@ int akz_match_features_homography_refined_guided(akz_ctx* c, const akz_keypoint*
     const GuidedStage g{guided_radius, guided_lowes_ratio};
     return refined_single("match_features_homography_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
                           ransac_trials, ransac_epsilon_inliers, refine_iterations, &g, out, n_out, h, found, iterations);
+}
+}  // extern "C"
+
+// ---- the fundamental matrix handed back, refitted, and guiding (see the header) ---------------------------------------------
+namespace {
+// one pair: the pairs call with sets {0, 1} and the pair (0, 1); refine_iterations / g: null without that stage
+int fundamental_single(const char* name, akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                       const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, double lowes_ratio,
+                       uint64_t ransac_trials, float ransac_epsilon_inliers, const uint32_t* refine_iterations, const GuidedStage* g,
+                       akz_match* out, uint64_t* n_out, float* f, int* found, uint32_t* iterations) {
+    if (!n_out) {
+        set_error(std::string(name) + "null n_out");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
+        set_error(std::string(name) + "a feature set has more descriptors than keypoints");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
+    const uint64_t pair[2] = {0, 1};
+    int fnd = 0;
+    float fm[9] = {};
+    uint32_t it = 0;
+    const RefineStage r{refine_iterations ? *refine_iterations : 0u, &it};
+    AKZ_TRY(match_pairs_impl<FundamentalModelOut>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out,
+                                                  n_out, fm, &fnd, g, refine_iterations ? &r : nullptr, name));
+    if (found) *found = fnd;
+    if (f) std::memcpy(f, fm, sizeof(fm));  // (zeros without a winner, as akz_remove_outliers_fundamental)
+    if (iterations) *iterations = it;
+    return AKZ_OK;
+}
+}  // namespace
+extern "C" {
+int akz_match_features_fundamental_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                                         uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                         akz_match* out, uint64_t* n_out, float* f, int* found) {
+    return match_pairs_impl<FundamentalModelOut>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials,
+                                                 ransac_epsilon_inliers, out, n_out, f, found);
+}
+int akz_match_features_fundamental_refined_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                 uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                 float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out, uint64_t* n_out,
+                                                 float* f, int* found, uint32_t* iterations) {
+    const RefineStage r{refine_iterations, iterations};
+    return match_pairs_impl<FundamentalModelOut>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials,
+                                                 ransac_epsilon_inliers, out, n_out, f, found, nullptr, &r,
+                                                 "match_features_fundamental_refined_pairs: ");
+}
+int akz_match_features_fundamental_guided_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio, akz_match* out,
+                                                uint64_t* n_out, float* f, int* found) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    return match_pairs_impl<FundamentalModelOut>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials,
+                                                 ransac_epsilon_inliers, out, n_out, f, found, &g, nullptr,
+                                                 "match_features_fundamental_guided_pairs: ");
+}
+int akz_match_features_fundamental_refined_guided_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                        uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                        float ransac_epsilon_inliers, uint32_t refine_iterations, float guided_radius,
+                                                        double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* f, int* found,
+                                                        uint32_t* iterations) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    const RefineStage r{refine_iterations, iterations};
+    return match_pairs_impl<FundamentalModelOut>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials,
+                                                 ransac_epsilon_inliers, out, n_out, f, found, &g, &r,
+                                                 "match_features_fundamental_refined_guided_pairs: ");
+}
+int akz_match_features_fundamental(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                   const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                   double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out,
+                                   float* f, int* found) {
+    return fundamental_single("match_features_fundamental: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
+                              ransac_trials, ransac_epsilon_inliers, nullptr, nullptr, out, n_out, f, found, nullptr);
+}
+int akz_match_features_fundamental_refined(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                           const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                           double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                           uint32_t refine_iterations, akz_match* out, uint64_t* n_out, float* f, int* found,
+                                           uint32_t* iterations) {
+    return fundamental_single("match_features_fundamental_refined: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
+                              ransac_trials, ransac_epsilon_inliers, &refine_iterations, nullptr, out, n_out, f, found, iterations);
+}
+int akz_match_features_fundamental_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                          const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                          double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, float guided_radius,
+                                          double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* f, int* found) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    return fundamental_single("match_features_fundamental_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
+                              ransac_trials, ransac_epsilon_inliers, nullptr, &g, out, n_out, f, found, nullptr);
+}
+int akz_match_features_fundamental_refined_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                                  const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1,
+                                                  uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                  float ransac_epsilon_inliers, uint32_t refine_iterations, float guided_radius,
+                                                  double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* f, int* found,
+                                                  uint32_t* iterations) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    return fundamental_single("match_features_fundamental_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                              lowes_ratio, ransac_trials, ransac_epsilon_inliers, &refine_iterations, &g, out, n_out, f, found, iterations);
 }
 }  // extern "C"

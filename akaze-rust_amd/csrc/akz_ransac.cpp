@@ -34,6 +34,7 @@
 
 #include "akz_fmatrix.hpp"
 #include "akz_homography.hpp"
+#include "akz_fundamental_refit.hpp"
 #include "akz_homography_refit.hpp"
 #include "akz_internal.hpp"
 #include "akz_pool.hpp"
@@ -219,7 +220,9 @@ extern "C" int akz_debug_ransac_samples_k(uint64_t s0, uint64_t s1, uint64_t n_m
 // winner is picked in trial order with the reference's strict `>` from 0 -- the same model as the sequential loop returns
 // (12 ms -> 1.5 ms for the 8 000 matches of a 4K pair at 1 000 trials) -- and the final filter runs in match order.  Fewer
 // than M::K matches ("Not enough points to do RANSAC."): returned unchanged, nothing drawn.  No trial with an inlier: the zero
-// model filters, or (M::kKeepAllWithoutWinner) every match is kept; h and found are written for M::kModelOut only.
+// model filters, or (M::kKeepAllWithoutWinner) every match is kept; h and found are written for M::kModelOut only.  Without a
+// winner (and with fewer than K matches) the two models that hand a model back differ, by M::kZeroModelOut: the homography
+// leaves h untouched (found = 0 says so), the fundamental matrix writes the zero model that it evaluated (found = 0 as well).
 // trials_on_device (match_features with a context, the fundamental matrix only): runs the trials elsewhere -- x0 .. y1
 // (n_matches floats each), the samples (8 per trial), -> models (9 floats per trial), inliers (-1: no model); AKZ_OK or an
 // error (the host path then takes over)
@@ -231,6 +234,7 @@ int ransac_host(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, 
     constexpr int K = M::K;
     AKZ_TRY(refuse_bad_matches(name, keypoints_0, n0, keypoints_1, n1, matches, n_matches, out, n_out));
     if (found) *found = 0;
+    if (M::kModelOut && M::kZeroModelOut && h) std::memset(h, 0, 9 * sizeof(float));
     if (n_matches < (uint64_t)K) {
         if (n_matches) std::memcpy(out, matches, n_matches * sizeof(akz_match));
         *n_out = n_matches;
@@ -288,9 +292,9 @@ int ransac_host(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, 
         if ((M::kKeepAllWithoutWinner && max_inliers == 0) || M::inlier(final_model.f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier))
             out[k++] = matches[i];
     *n_out = k;
-    if (M::kModelOut && max_inliers > 0) {
+    if (M::kModelOut && (max_inliers > 0 || M::kZeroModelOut)) {  // (no winner: final_model is the zero model)
         if (h) std::memcpy(h, final_model.f, sizeof(final_model.f));
-        if (found) *found = 1;
+        if (found) *found = max_inliers > 0 ? 1 : 0;
     }
     return AKZ_OK;
 }
@@ -316,6 +320,14 @@ extern "C" int akz_estimate_fundamental_matrix(const akz_keypoint* keypoints_0, 
     return estimate_model<FundamentalRansac>("estimate_fundamental_matrix", keypoints_0, n0, keypoints_1, n1, matches8, epsilon, f, found);
 }
 
+// akz_remove_outliers with the winner handed back (see the header): the same skeleton, the same draws, the same list
+extern "C" int akz_remove_outliers_fundamental(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                               const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
+                                               float epsilon_inlier, akz_match* out, uint64_t* n_out, float* f, int* found) {
+    return ransac_host<FundamentalRansacModelOut>("remove_outliers_fundamental", keypoints_0, n0, keypoints_1, n1, matches, n_matches,
+                                                  num_trials, epsilon_model, epsilon_inlier, out, n_out, f, found, TrialsOnDevice());
+}
+
 // ---- the homography (no reference counterpart; akz_homography.hpp) ------------------------------------------
 extern "C" int akz_estimate_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
                                        const akz_match* matches4, float epsilon, float* h, int* found) {
@@ -329,7 +341,7 @@ extern "C" int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, u
                                          epsilon_model, epsilon_inlier, out, n_out, h, found, TrialsOnDevice());
 }
 
-// ---- the refit of a homography on its inliers (akz_homography_refit.hpp) ---------------------------------------
+// ---- the refit of a model on its inliers (akz_homography_refit.hpp, akz_fundamental_refit.hpp) -----------------
 namespace {
 // the sums of the members' terms in the documented order: lane i mod 256, ascending i from +0.0, then the tree
 template <int K, class Term>
@@ -349,45 +361,47 @@ void lane_tree_sums(uint64_t n, const std::vector<uint8_t>& member, Term term, d
         out[k] = p[k][0];
     }
 }
-// fit(S) of the statement; false: no model
+// fit(S) of the statement for the refit model R (HomographyRefit, FundamentalRefit); false: no model
+template <class R>
 bool refit_on_members(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const std::vector<uint8_t>& member,
-                      uint64_t count, float (&h)[9]) {
-    if (count < 4) return false;
+                      uint64_t count, float epsilon_model, float (&h)[9]) {
+    if (count < (uint64_t)R::kMin) return false;
     const double cnt = (double)count;
-    double s1sum[4], s2sum[2], s3sum[kRefitSums3];
+    double s1sum[4], s2sum[2], s3sum[R::kSums3];
     lane_tree_sums<4>(n, member, [&](uint64_t i, double (&t)[4]) { refit_terms1(x0[i], y0[i], x1[i], y1[i], t); }, s1sum);
     const double c0x = s1sum[0] / cnt, c0y = s1sum[1] / cnt, c1x = s1sum[2] / cnt, c1y = s1sum[3] / cnt;
     lane_tree_sums<2>(n, member, [&](uint64_t i, double (&t)[2]) { refit_terms2(x0[i], y0[i], x1[i], y1[i], c0x, c0y, c1x, c1y, t); }, s2sum);
     double s0 = 0.0, s1 = 0.0;
     if (!refit_scale(s2sum[0], cnt, s0) || !refit_scale(s2sum[1], cnt, s1)) return false;
-    lane_tree_sums<kRefitSums3>(
-        n, member, [&](uint64_t i, double (&t)[kRefitSums3]) { refit_terms3(x0[i], y0[i], x1[i], y1[i], c0x, c0y, s0, c1x, c1y, s1, t); },
-        s3sum);
+    lane_tree_sums<R::kSums3>(
+        n, member, [&](uint64_t i, double (&t)[R::kSums3]) { R::terms3(x0[i], y0[i], x1[i], y1[i], c0x, c0y, s0, c1x, c1y, s1, t); }, s3sum);
     Mat9x9 m;
-    refit_normal_matrix(m, s3sum);
-    return refit_model_from_normal(m, cnt, AKZ_HOMOGRAPHY_EPSILON_MODEL, c0x, c0y, s0, c1x, c1y, s1, h);
+    R::normal_matrix(m, s3sum);
+    jacobi_sweeps_rows<9>(m);
+    return R::model_from_rotated(m, cnt, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, h);
 }
+template <class R>
 uint64_t classify(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const float (&h)[9], float eps,
                   std::vector<uint8_t>& member) {
     uint64_t c = 0;
     for (uint64_t i = 0; i < n; ++i) {
-        member[(size_t)i] = homography_inlier(h, x0[i], y0[i], x1[i], y1[i], eps) ? 1 : 0;
+        member[(size_t)i] = R::inlier(h, x0[i], y0[i], x1[i], y1[i], eps) ? 1 : 0;
         c += member[(size_t)i];
     }
     return c;
 }
-}  // namespace
-
-extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
-                                     const akz_match* matches, uint64_t n_matches, const float* h_in, float epsilon_inlier,
-                                     uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* h_out, uint32_t* iterations) {
-    AKZ_TRY(refuse_bad_matches("refine_homography", keypoints_0, n0, keypoints_1, n1, matches, n_matches, out, n_out));
+// the loop of the statement, one for both models; `name` is the call's, `what` its model argument
+template <class R>
+int refine_host(const char* name, const char* what, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                const akz_match* matches, uint64_t n_matches, const float* h_in, float epsilon_model, float epsilon_inlier,
+                uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* h_out, uint32_t* iterations) {
+    AKZ_TRY(refuse_bad_matches(name, keypoints_0, n0, keypoints_1, n1, matches, n_matches, out, n_out));
     if (!h_in) {
-        set_error("refine_homography: null h_in");
+        set_error(std::string(name) + ": null " + what);
         return AKZ_ERR_INVALID_ARG;
     }
     if (!(epsilon_inlier > 0.0f && std::isfinite(epsilon_inlier))) {
-        set_error("refine_homography: epsilon_inlier must be finite and > 0");
+        set_error(std::string(name) + ": epsilon_inlier must be finite and > 0");
         return AKZ_ERR_INVALID_ARG;
     }
     const MatchPoints pt(keypoints_0, keypoints_1, matches, n_matches);
@@ -395,12 +409,12 @@ extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n
     float h[9];
     std::memcpy(h, h_in, sizeof(h));
     std::vector<uint8_t> member((size_t)n_matches), next((size_t)n_matches);
-    uint64_t count = classify(x0, y0, x1, y1, n_matches, h, epsilon_inlier, member);
+    uint64_t count = classify<R>(x0, y0, x1, y1, n_matches, h, epsilon_inlier, member);
     uint32_t done = 0;
     while (done < max_iterations) {
         float h2[9];
-        if (!refit_on_members(x0, y0, x1, y1, n_matches, member, count, h2)) break;
-        const uint64_t count2 = classify(x0, y0, x1, y1, n_matches, h2, epsilon_inlier, next);
+        if (!refit_on_members<R>(x0, y0, x1, y1, n_matches, member, count, epsilon_model, h2)) break;
+        const uint64_t count2 = classify<R>(x0, y0, x1, y1, n_matches, h2, epsilon_inlier, next);
         if (count2 < count) break;
         const bool grew = count2 > count;
         std::memcpy(h, h2, sizeof(h));
@@ -416,6 +430,21 @@ extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n
     if (h_out) std::memcpy(h_out, h, sizeof(h));
     if (iterations) *iterations = done;
     return AKZ_OK;
+}
+}  // namespace
+
+extern "C" int akz_refine_homography(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                     const akz_match* matches, uint64_t n_matches, const float* h_in, float epsilon_inlier,
+                                     uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* h_out, uint32_t* iterations) {
+    return refine_host<HomographyRefit>("refine_homography", "h_in", keypoints_0, n0, keypoints_1, n1, matches, n_matches, h_in,
+                                        AKZ_HOMOGRAPHY_EPSILON_MODEL, epsilon_inlier, max_iterations, out, n_out, h_out, iterations);
+}
+
+extern "C" int akz_refine_fundamental_matrix(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                             const akz_match* matches, uint64_t n_matches, const float* f_in, float epsilon_inlier,
+                                             uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* f_out, uint32_t* iterations) {
+    return refine_host<FundamentalRefit>("refine_fundamental_matrix", "f_in", keypoints_0, n0, keypoints_1, n1, matches, n_matches, f_in,
+                                         AKZ_FUNDAMENTAL_REFIT_EPSILON, epsilon_inlier, max_iterations, out, n_out, f_out, iterations);
 }
 
 // random::default().seed([s0, s1]) for the calling thread

@@ -221,7 +221,8 @@ __global__ void __launch_bounds__(TW * NW) k_pairs_trials(const PairJob* __restr
 
 // Per pair (a workgroup, grid-stride): the winner among its trials (pick_winner; fewer than K matches: none), and the matches
 // it keeps (Model::inlier, as the host's final filter), compacted in match order.  Fewer than K matches: all kept.  No winner:
-// the zero model is evaluated, or (kKeepAllWithoutWinner) all kept.  kModelOut: the winner's H or zeros, and found.
+// the zero model is evaluated, or (kKeepAllWithoutWinner) all kept.  h_out / found_out, where the call hands the model back (else
+// null): the winner's model or zeros, and found.
 template <class Model>
 __global__ void __launch_bounds__(kGroup) k_pairs_pick_filter(const PairJob* __restrict__ pairs, unsigned n_pairs, const akz_match* __restrict__ raw,
                                                               const unsigned long long* __restrict__ raw_cnt, const float* __restrict__ pts,
@@ -244,9 +245,9 @@ __global__ void __launch_bounds__(kGroup) k_pairs_pick_filter(const PairJob* __r
             if (Model::kKeepAllWithoutWinner) s_found = found;
             for (int k = 0; k < 9; ++k) {
                 s_f[k] = found ? models[(pj.trial_off + win.bidx) * 9 + k] : 0.0f;
-                if (Model::kModelOut) h_out[(size_t)p * 9 + k] = s_f[k];
+                if (h_out) h_out[(size_t)p * 9 + k] = s_f[k];
             }
-            if (Model::kModelOut) found_out[p] = found;
+            if (found_out) found_out[p] = found;
         }
         __syncthreads();
         const bool all = n < (unsigned long long)Model::K || (Model::kKeepAllWithoutWinner && s_found == 0);

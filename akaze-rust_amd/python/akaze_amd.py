@@ -239,6 +239,23 @@ def lib():
                                                   pu64, fp, C.POINTER(i32)], i32),
         "akz_match_features_homography_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp, pu64, fp,
                                                         C.POINTER(i32)], i32),
+        "akz_remove_outliers_fundamental": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
+        "akz_refine_fundamental_matrix": ([vp, u64, vp, u64, vp, u64, fp, C.c_float, C.c_uint32, vp, pu64, fp, C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_fundamental": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp,
+                                            C.POINTER(i32)], i32),
+        "akz_match_features_fundamental_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
+        "akz_match_features_fundamental_refined": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64,
+                                                    fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_fundamental_refined_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64, fp,
+                                                          C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_fundamental_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp,
+                                                   pu64, fp, C.POINTER(i32)], i32),
+        "akz_match_features_fundamental_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp, pu64, fp,
+                                                         C.POINTER(i32)], i32),
+        "akz_match_features_fundamental_refined_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32,
+                                                           C.c_float, f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_match_features_fundamental_refined_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, C.c_float,
+                                                                 f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
@@ -787,6 +804,45 @@ class Context:
         _check(lib().akz_match_features_homography_refined_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                                         refine_iterations, guided_radius, guided_lowes_ratio, *a.tail,
                                                                         *a.refined()))
+        return a.lists_models_iterations()
+
+    def match_features_fundamental_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
+        """match_features_pairs with the fundamental matrix that filtered every pair (akz_match_features_fundamental_pairs).
+        Returns one (matches, F or None) per pair: the list of match_features_pairs, F the RANSAC winner."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_fundamental_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers, *a.tail,
+                                                          *a.models()))
+        return a.lists_and_models()
+
+    def match_features_fundamental_refined_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                 refine_iterations):
+        """match_features_fundamental_pairs with the refit of every F found on its inliers
+        (akz_match_features_fundamental_refined_pairs).  Returns one (matches, F or None, accepted fits) per pair, each equal
+        to what match_features_fundamental_refined returns for that pair when the pairs are matched in order on this thread."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_fundamental_refined_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                                  refine_iterations, *a.tail, *a.refined()))
+        return a.lists_models_iterations()
+
+    def match_features_fundamental_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                guided_radius, guided_lowes_ratio):
+        """match_features_fundamental_pairs, then the guided scan with every F found
+        (akz_match_features_fundamental_guided_pairs).  Returns one (matches, F or None) per pair: with an F the list of
+        descriptor_match_guided(pair, GUIDED_FUNDAMENTAL, F, guided_radius, 10000, guided_lowes_ratio), without one the list
+        of match_features_fundamental_pairs."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_fundamental_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                                 guided_radius, guided_lowes_ratio, *a.tail, *a.models()))
+        return a.lists_and_models()
+
+    def match_features_fundamental_refined_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                        refine_iterations, guided_radius, guided_lowes_ratio):
+        """match_features_fundamental_refined_pairs, then the guided scan with every REFINED F
+        (akz_match_features_fundamental_refined_guided_pairs).  Returns one (matches, F or None, accepted fits) per pair."""
+        a = _PairsArgs(self, features, pairs)
+        _check(lib().akz_match_features_fundamental_refined_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                                         refine_iterations, guided_radius, guided_lowes_ratio, *a.tail,
+                                                                         *a.refined()))
         return a.lists_models_iterations()
 
     def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
@@ -1485,6 +1541,8 @@ def refine_homography(keypoints_0, keypoints_1, matches, h, epsilon_inlier, max_
 
 def _refined_pair(fn, extra, keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
                   ransac_epsilon_inliers, refine_iterations, ctx):
+    """a single-pair call that hands back (list, model, found[, accepted fits]) -> (matches, model or None[, accepted fits]);
+    refine_iterations None: a call without the refit stage's two arguments"""
     c = ctx or default_context()
     k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
     k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
@@ -1499,11 +1557,13 @@ def _refined_pair(fn, extra, keypoints_0, descriptors_0, keypoints_1, descriptor
     h = np.zeros(9, np.float32)
     found = C.c_int()
     it = C.c_uint32()
+    refit = refine_iterations is not None
     _check(fn(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), len(d0), k1.ctypes.data_as(C.c_void_p), len(k1),
               d1.ctypes.data_as(C.c_void_p), len(d1), nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-              refine_iterations, *extra, out.ctypes.data_as(C.c_void_p), C.byref(n), h.ctypes.data_as(C.POINTER(C.c_float)),
-              C.byref(found), C.byref(it)))
-    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None), it.value
+              *((refine_iterations,) if refit else ()), *extra, out.ctypes.data_as(C.c_void_p), C.byref(n),
+              h.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found), *((C.byref(it),) if refit else ())))
+    res = out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+    return (*res, it.value) if refit else res
 
 
 def match_features_homography_refined(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
@@ -1535,6 +1595,108 @@ def match_features_homography_refined_guided_pairs(features, pairs, lowes_ratio,
                                                    refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
     """Context.match_features_homography_refined_guided_pairs on ctx (default: the default context)."""
     return (ctx or default_context()).match_features_homography_refined_guided_pairs(
+        features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio)
+
+
+# ---- the RANSAC fundamental matrix handed back, refitted and guiding (an addition; include/akaze_hip.h, DESIGN.md 8) ---------
+FUNDAMENTAL_REFIT_EPSILON = 1e-6  # AKZ_FUNDAMENTAL_REFIT_EPSILON: the rank rule of the refit
+
+
+def remove_outliers_fundamental(keypoints_0, keypoints_1, matches, num_trials, epsilon_model, epsilon_inlier):
+    """remove_outliers with the model that filtered (akz_remove_outliers_fundamental; host only) -> (matches kept, F or None):
+    the list and the draws of remove_outliers, F the first trial with the most inliers (3x3 float32, p1^T F p0 = 0)."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    n = C.c_uint64()
+    f = np.zeros(9, np.float32)
+    found = C.c_int()
+    _check(lib().akz_remove_outliers_fundamental(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                                 m.ctypes.data_as(C.c_void_p), len(m), num_trials, epsilon_model, epsilon_inlier,
+                                                 out.ctypes.data_as(C.c_void_p), C.byref(n), f.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 C.byref(found)))
+    return out[:n.value].copy(), (f.reshape(3, 3) if found.value else None)
+
+
+def refine_fundamental_matrix(keypoints_0, keypoints_1, matches, f, epsilon_inlier, max_iterations):
+    """Local optimisation of the fundamental matrix f over a raw match list on the host (akz_refine_fundamental_matrix):
+    normalised least-squares refits on the inliers, rank 2 enforced, and re-classification until the set stops growing ->
+    (inliers in match order, 3x3 float32 F of unit norm, accepted fits).  With 0 accepted fits F is f and the list its inliers."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    fin = np.ascontiguousarray(np.asarray(f, np.float32).reshape(9))
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    n = C.c_uint64()
+    fout = np.zeros(9, np.float32)
+    it = C.c_uint32()
+    _check(lib().akz_refine_fundamental_matrix(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                               m.ctypes.data_as(C.c_void_p), len(m), fin.ctypes.data_as(C.POINTER(C.c_float)),
+                                               epsilon_inlier, max_iterations, out.ctypes.data_as(C.c_void_p), C.byref(n),
+                                               fout.ctypes.data_as(C.POINTER(C.c_float)), C.byref(it)))
+    return out[:n.value].copy(), fout.reshape(3, 3), it.value
+
+
+def match_features_fundamental(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                               ransac_epsilon_inliers, ctx=None):
+    """match_features with the fundamental matrix that filtered (akz_match_features_fundamental) -> (matches kept, F or None);
+    equal to remove_outliers_fundamental(k0, k1, descriptor_match(d0, d1, 10000, ratio), ransac_trials, 0.05,
+    ransac_epsilon_inliers) from the same random state."""
+    return _refined_pair(lib().akz_match_features_fundamental, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio,
+                         ransac_trials, ransac_epsilon_inliers, None, ctx)
+
+
+def match_features_fundamental_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                                      ransac_epsilon_inliers, guided_radius, guided_lowes_ratio, ctx=None):
+    """match_features_fundamental, then the guided scan with the F it found (akz_match_features_fundamental_guided) ->
+    (matches, F or None): with an F the guided list, without one the list of match_features_fundamental."""
+    return _refined_pair(lib().akz_match_features_fundamental_guided, (guided_radius, guided_lowes_ratio), keypoints_0, descriptors_0,
+                         keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers, None, ctx)
+
+
+def match_features_fundamental_refined(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                                       ransac_epsilon_inliers, refine_iterations, ctx=None):
+    """match_features_fundamental with the refit of the F it found as one more stage on the GPU
+    (akz_match_features_fundamental_refined) -> (matches, F or None, accepted fits): with an F what refine_fundamental_matrix
+    gives on the raw descriptor_match list from the winner, without one the list of match_features_fundamental."""
+    return _refined_pair(lib().akz_match_features_fundamental_refined, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1,
+                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, ctx)
+
+
+def match_features_fundamental_refined_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                                              ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
+    """match_features_fundamental_refined, then the guided scan with the REFINED F
+    (akz_match_features_fundamental_refined_guided) -> (matches, F or None, accepted fits)."""
+    return _refined_pair(lib().akz_match_features_fundamental_refined_guided, (guided_radius, guided_lowes_ratio), keypoints_0,
+                         descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                         refine_iterations, ctx)
+
+
+def match_features_fundamental_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
+    """Context.match_features_fundamental_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_fundamental_pairs(features, pairs, lowes_ratio, ransac_trials,
+                                                                       ransac_epsilon_inliers)
+
+
+def match_features_fundamental_refined_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations,
+                                             ctx=None):
+    """Context.match_features_fundamental_refined_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_fundamental_refined_pairs(features, pairs, lowes_ratio, ransac_trials,
+                                                                               ransac_epsilon_inliers, refine_iterations)
+
+
+def match_features_fundamental_guided_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, guided_radius,
+                                            guided_lowes_ratio, ctx=None):
+    """Context.match_features_fundamental_guided_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_fundamental_guided_pairs(features, pairs, lowes_ratio, ransac_trials,
+                                                                              ransac_epsilon_inliers, guided_radius, guided_lowes_ratio)
+
+
+def match_features_fundamental_refined_guided_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                                    refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
+    """Context.match_features_fundamental_refined_guided_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_fundamental_refined_guided_pairs(
         features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio)
 
 

@@ -683,6 +683,107 @@ int akz_match_features_homography_refined_guided_pairs(akz_ctx* ctx, const akz_f
                                                        uint64_t* n_out /* n_pairs */, float* h /* 9 x n_pairs */,
                                                        int* found /* n_pairs */, uint32_t* iterations /* n_pairs */);
 
+/* ---- the RANSAC fundamental matrix handed back, refitted on its inliers, and guiding (an addition) ---------
+   akz_remove_outliers, akz_match_features and akz_match_features_pairs return a list only, as the reference does.  The calls
+   below run the same RANSAC -- the same draws from the calling thread's random source, the same list bit for bit -- and also
+   hand back the model that filtered: f, row-major, with p1^T F p0 = 0 as in akz_estimate_fundamental_matrix, the winner (the
+   first trial with the most inliers); found = 1 iff some trial had a model with more than 0 inliers.  Without a winner the
+   list is still what akz_remove_outliers returns (the zero model is evaluated), f is zeros and found is 0.  Fewer than 8
+   matches: the list is unchanged, f is zeros, found is 0 and nothing is drawn.  f and found may be NULL.
+   akz_remove_outliers_fundamental is the plain host statement (no GPU call; refusals of akz_remove_outliers). */
+int akz_remove_outliers_fundamental(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                    const akz_match* matches, uint64_t n_matches, uint64_t num_trials, float epsilon_model,
+                                    float epsilon_inlier, akz_match* out, uint64_t* n_out, float* f /* 9, may be NULL */,
+                                    int* found /* may be NULL */);
+/* akz_match_features(_pairs) with the model: descriptor_match(d0, d1, 10000, lowes_ratio), then the RANSAC with the reference's
+   epsilon_model 0.05, all on the GPU but the draws; equal to akz_remove_outliers_fundamental on that raw list from the same
+   random state -- list, F bits, found, and the state of the random source afterwards.  f: 9 floats per pair (zeros where found
+   is 0), found: one flag per pair; either may be NULL.  Refusals, the layout of out and every other promise are those of
+   akz_match_features_pairs. */
+int akz_match_features_fundamental(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                   const uint8_t* descriptors_0, uint64_t n_descriptors_0, const akz_keypoint* keypoints_1,
+                                   uint64_t n_keypoints_1, const uint8_t* descriptors_1, uint64_t n_descriptors_1,
+                                   uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                   akz_match* out, uint64_t* n_out, float* f /* 9 */, int* found);
+int akz_match_features_fundamental_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                         uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                         float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out /* n_pairs */,
+                                         float* f /* 9 x n_pairs */, int* found /* n_pairs */);
+/* The refit.  The winner of the RANSAC is the model of ONE 8-point sample in raw pixel coordinates: it is not of rank 2 and it
+   is as noisy as its eight points.  akz_refine_fundamental_matrix runs the loop of akz_refine_homography, unchanged, over a
+   pair's RAW match list with the inlier rule of the RANSAC itself, |p1^T F p0| < epsilon_inlier in f32 in the order of
+   akz_remove_outliers -- so the result never has fewer inliers than the input.  fit(S) for |S| >= 8 (fewer: no model), in f64
+   in one order, every sum over S by lanes and the tree as for the homography:
+     1. Hartley normalisation of both images as for the homography (a mean distance of 0: no model);
+     2. with p = (x, y, 1), q = (u, v, 1) normalised, a = {x x, x y, x, y y, y, 1} and b the same six products of q, the 36 sums
+        of a[k] b[l]: the normal matrix M = A^T A of the design rows of the 8-point model (entry 3 i + j is p_i q_j),
+        M[3 i + j][3 k + l] = sum p_i p_k q_j q_l;
+     3. the null vector by the one-sided Jacobi sweeps on the 9 rows of M: the row of the smallest norm (the first among
+        equals), normalised; every other row norm must exceed AKZ_FUNDAMENTAL_REFIT_EPSILON^2 |S| / 8, else no model;
+     4. rank 2: the same rotations on the three rows of F^; with r the row of the smallest norm afterwards and v3 = r / |r|
+        (|r| = 0: nothing to remove), F' = F^ - (F^ v3) v3^T;
+     5. F = T1^T F' T0, scaled to unit Frobenius norm -- the trial models have it, and epsilon_inlier only means anything at
+        that scale -- and rounded to f32; a norm that is zero or not finite: no model.
+   out must hold n_matches entries; it receives S in match order, f_out (9, may be NULL) the final f, *iterations (may be NULL)
+   the number of accepted fits; with 0 accepted fits that is f_in unchanged and its inliers.  Refusals are those of
+   akz_refine_homography (a NULL f_in, an epsilon_inlier that is not finite or <= 0, an index past a keypoint array, ...);
+   nothing is written after one. */
+#define AKZ_FUNDAMENTAL_REFIT_EPSILON 1e-6f
+int akz_refine_fundamental_matrix(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                  const akz_match* matches, uint64_t n_matches, const float* f_in /* 9 */, float epsilon_inlier,
+                                  uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* f_out /* 9, may be NULL */,
+                                  uint32_t* iterations /* may be NULL */);
+/* akz_match_features_fundamental(_pairs) with the refit and / or the guided scan as further stages on the GPU, with the
+   arguments and promises of the homography family above.  Draws, winner and found are exactly the unrefined call's and the
+   random source ends where that call leaves it.  _refined: where found = 1 the list and F are those of
+   akz_refine_fundamental_matrix(raw list, winner, ransac_epsilon_inliers, refine_iterations); refine_iterations = 0 is the
+   unrefined call bit for bit.  _guided: where found = 1 the returned list is akz_descriptor_match_guided(pair,
+   AKZ_GUIDED_FUNDAMENTAL, F, guided_radius, 10000, guided_lowes_ratio) -- with the REFINED F in the _refined_guided forms; F
+   stays on the device between the stages and the sets are uploaded once.  Where found = 0 or a pair has fewer than 8
+   matches the list is the unrefined call's, iterations is 0 and the guided stage is skipped.
+   There is NO superset promise here, unlike the homography's guided call: the guided gate is a distance to the epipolar
+   line in pixels, the RANSAC's rule is the algebraic |p1^T F p0| -- a match the RANSAC keeps can lie outside the band, and
+   the other way round.  iterations: one per pair, may be NULL.  Refusals are the unrefined call's (and the guided call's
+   radius rule), before the first draw and any GPU work.  So a ransac_epsilon_inliers that akz_refine_fundamental_matrix
+   refuses (not finite, or <= 0) is NOT refused here, as the unrefined call does not refuse it: the stage runs the same loop
+   with it (+infinity: every match with a finite error is an inlier; NaN, 0 or less: none is, and nothing is fitted), and
+   the equality with the host statement is promised for the epsilons that statement accepts. */
+int akz_match_features_fundamental_refined(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                           const uint8_t* descriptors_0, uint64_t n_descriptors_0, const akz_keypoint* keypoints_1,
+                                           uint64_t n_keypoints_1, const uint8_t* descriptors_1, uint64_t n_descriptors_1,
+                                           uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                           float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out, uint64_t* n_out,
+                                           float* f /* 9 */, int* found, uint32_t* iterations);
+int akz_match_features_fundamental_refined_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                 uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                 float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out,
+                                                 uint64_t* n_out /* n_pairs */, float* f /* 9 x n_pairs */, int* found /* n_pairs */,
+                                                 uint32_t* iterations /* n_pairs */);
+int akz_match_features_fundamental_guided(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                          const uint8_t* descriptors_0, uint64_t n_descriptors_0, const akz_keypoint* keypoints_1,
+                                          uint64_t n_keypoints_1, const uint8_t* descriptors_1, uint64_t n_descriptors_1,
+                                          uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                          float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio,
+                                          akz_match* out, uint64_t* n_out, float* f /* 9 */, int* found);
+int akz_match_features_fundamental_guided_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                                uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                                                float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio,
+                                                akz_match* out, uint64_t* n_out /* n_pairs */, float* f /* 9 x n_pairs */,
+                                                int* found /* n_pairs */);
+int akz_match_features_fundamental_refined_guided(akz_ctx* ctx, const akz_keypoint* keypoints_0, uint64_t n_keypoints_0,
+                                                  const uint8_t* descriptors_0, uint64_t n_descriptors_0,
+                                                  const akz_keypoint* keypoints_1, uint64_t n_keypoints_1,
+                                                  const uint8_t* descriptors_1, uint64_t n_descriptors_1, uint64_t desc_bytes,
+                                                  double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                                  uint32_t refine_iterations, float guided_radius, double guided_lowes_ratio,
+                                                  akz_match* out, uint64_t* n_out, float* f /* 9 */, int* found, uint32_t* iterations);
+int akz_match_features_fundamental_refined_guided_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets,
+                                                        const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio,
+                                                        uint64_t ransac_trials, float ransac_epsilon_inliers, uint32_t refine_iterations,
+                                                        float guided_radius, double guided_lowes_ratio, akz_match* out,
+                                                        uint64_t* n_out /* n_pairs */, float* f /* 9 x n_pairs */,
+                                                        int* found /* n_pairs */, uint32_t* iterations /* n_pairs */);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly
