@@ -484,6 +484,10 @@ AKZ_LOCAL uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, con
                                std::vector<uint64_t>& set_row, std::vector<uint64_t>& used);
 AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint64_t>& used, const std::vector<uint64_t>& set_row,
                            uint64_t rows, uint64_t desc_bytes, size_t b_rows, size_t b_xy);
+// akz_match_api.cpp: the descriptor scans of every pair over the uploaded sets; fills the pair records' raw_off, kp0_off, kp1_off, cnt_idx
+AKZ_LOCAL int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
+                          double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
+                          std::vector<launch::PairJobHost>& tab);
 // akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device (rows of 64 bytes, x, y), enqueued on the
 // context's stream -- scan, merge, ratio test and ordered compaction; pair p's list goes to d_out + spec[p].out_off, its
 // length to d_cnt[p].  d_models: 9 floats per pair ON THE DEVICE; d_found (optional): pairs whose flag is 0 give empty lists.

@@ -54,6 +54,26 @@ DefaultSource& default_source();
 template <int K, class T>
 void draw_samples(DefaultSource& src, uint64_t n_matches, uint64_t trials, T* out);
 
+// the refusals every call over a list of matches shares (akz_ransac.cpp); `name` is the call's
+int refuse_bad_matches(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                       const akz_match* matches, uint64_t n_matches, const akz_match* out, const uint64_t* n_out);
+// The matched point pairs side by side, x0 | y0 | x1 | y1 with n_matches floats each: the inlier count of a trial -- 8 M
+// evaluations for the 8 000 matches of a 4K pair at 1 000 trials -- is then a streaming loop the compiler vectorises instead
+// of two gathers of 32-byte keypoints per evaluation.
+struct MatchPoints {
+    std::vector<float> v;
+    const float *x0, *y0, *x1, *y1;
+    MatchPoints(const akz_keypoint* keypoints_0, const akz_keypoint* keypoints_1, const akz_match* matches, uint64_t n) : v((size_t)n * 4) {
+        float* p = v.data();
+        x0 = p; y0 = p + n; x1 = p + 2 * n; y1 = p + 3 * n;
+        for (uint64_t i = 0; i < n; ++i) {
+            p[i] = keypoints_0[matches[i].index_0].x; p[n + i] = keypoints_0[matches[i].index_0].y;
+            p[2 * n + i] = keypoints_1[matches[i].index_1].x; p[3 * n + i] = keypoints_1[matches[i].index_1].y;
+        }
+    }
+};
+
+
 #define AKZ_TRY(expr)            \
     do {                         \
         int _s = (expr);         \
@@ -387,6 +407,17 @@ void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pa
 void model_refit(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                       const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
                       void* d_keep, uint64_t* d_keep_cnt, float* d_h, const int32_t* d_found, uint32_t* d_iterations);
+// The seeded pairs call (akz_match_seeded_api.cpp; the statement: akz_ransac_seeded.hpp).  seeded_round: round `round` of every pair
+// with d_done[pair] == 0 -- its trials draw their own samples from (k1, stream_base + pair, trial) -- into the pair's ring of
+// 128 models and counts.  seeded_update: per running pair the round's first maximum against d_best_inl / d_best_mdl (strictly
+// greater replaces), d_trials_run, d_done from d_need[pair * need_stride + need_index] (null: no stopping rule) or the last round, and
+// the pairs that go on counted in d_running[round].
+void seeded_round(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const uint32_t* d_done, uint64_t k1,
+                  uint64_t stream_base, uint32_t round, uint32_t max_trials, const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride,
+                  float epsilon_model, float epsilon_inlier, float* d_ring_mdl, int32_t* d_ring_inl);
+void seeded_update(hipStream_t s, uint32_t n_pairs, uint32_t round, uint32_t max_trials, const uint32_t* d_need, uint32_t need_stride,
+                   uint32_t need_index, const float* d_ring_mdl, const int32_t* d_ring_inl, uint32_t* d_done, int32_t* d_best_inl, float* d_best_mdl,
+                   uint32_t* d_trials_run, uint32_t* d_running);
 void unpack_pair(hipStream_t s, const uint8_t* dq, uint32_t nq, uint32_t q_pad, uint8_t* outq, uint32_t* popq, uint32_t* bound, uint32_t threshold,
                  const uint8_t* dt, uint32_t nt, uint32_t t_pad, uint8_t* outt, uint32_t* popt, bool fp4);
 uint32_t match_mfma_tile_rows();

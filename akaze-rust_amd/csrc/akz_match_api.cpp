@@ -466,6 +466,67 @@ int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint
     }
     return AKZ_OK;
 }
+// The scans of the pairs calls, enqueued on the context's stream over the sets that pairs_upload placed: pair p's raw list goes to
+// d_raw + tab[p].raw_off, its count to d_cnt[tab[p].cnt_idx] (zeroed here) -- one multi-set launch per first set, or the pair
+// matcher for rows of 62..64 bytes.  tab: one record per pair, raw_off, kp0_off, kp1_off and cnt_idx filled in.
+int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
+                double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
+                std::vector<launch::PairJobHost>& tab) {
+    hipStream_t st = c->stream;
+    tab.assign((size_t)n_pairs, launch::PairJobHost{});
+    AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_pairs * 8, st));
+    uint64_t raw_base = 0;
+    if (desc_bytes > 61) {  // every byte of a row counts: the pair matcher of akz_descriptor_match
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1], na = sets[a].n_descriptors;
+            tab[(size_t)p] = launch::PairJobHost{raw_base, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0, (uint32_t)p, 0};
+            if (na)
+                AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)a] * 64, na, d_rows + set_row[(size_t)b] * 64, sets[b].n_descriptors,
+                                          10000, lowes_ratio, d_raw + raw_base, d_cnt + p, false));
+            raw_base += na;
+        }
+    } else {  // one multi-set launch per first set over its second sets (split at the matcher's limits)
+        std::vector<std::vector<uint64_t>> groups;
+        std::vector<int64_t> group_of((size_t)n_sets, -1);
+        for (uint64_t p = 0; p < n_pairs; ++p) {
+            const uint64_t a = pairs[2 * p];
+            if (group_of[(size_t)a] < 0) {
+                group_of[(size_t)a] = (int64_t)groups.size();
+                groups.emplace_back();
+            }
+            groups[(size_t)group_of[(size_t)a]].push_back(p);
+        }
+        uint32_t cnt_base = 0;
+        std::vector<uint64_t> first, nrows;
+        for (const auto& g : groups) {
+            const uint64_t a = pairs[2 * g[0]], n0 = sets[a].n_descriptors;
+            const uint64_t max_sets = std::max<uint64_t>(1, std::min<uint64_t>(65535, n0 ? 0x7fffffffull / launch::match_mfma_rows((uint32_t)n0, true) : 65535));
+            for (size_t i = 0; i < g.size();) {
+                first.clear();
+                nrows.clear();
+                uint64_t train = 0;
+                const size_t i0 = i;
+                while (i < g.size() && first.size() < max_sets) {
+                    const uint64_t b = pairs[2 * g[i] + 1], nb = sets[b].n_descriptors;
+                    if (!first.empty() && train + nb > 0x7fffffffull) break;
+                    first.push_back(set_row[(size_t)b]);
+                    nrows.push_back(nb);
+                    train += nb;
+                    const uint64_t p = g[i];
+                    tab[(size_t)p] = launch::PairJobHost{raw_base + (i - i0) * n0, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0,
+                                                                   cnt_base + (uint32_t)(i - i0), 0};
+                    ++i;
+                }
+                if (n0)
+                    AKZ_TRY(match_sets_at(c, d_rows + set_row[(size_t)a] * 64, n0, d_rows, first.data(), nrows.data(), first.size(), 10000,
+                                          lowes_ratio, d_raw + raw_base, d_cnt + cnt_base, nullptr, nullptr));
+                raw_base += first.size() * n0;
+                cnt_base += (uint32_t)first.size();
+            }
+        }
+    }
+    return AKZ_OK;
+}
 // The geometric model of the pairs orchestration below: the kernels' model kind, K match indices per sample, and whether the
 // call hands back a model per pair (H, found).
 namespace {
@@ -546,58 +607,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     AKZ_TRY(pairs_upload(c, sets, used, set_row, rows, desc_bytes, b_rows, b_xy));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
     // the scans: pair p's raw list at raw_off, its count at d_cnt[cnt_idx]
-    std::vector<launch::PairJobHost> tab((size_t)n_pairs);
-    AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_pairs * 8, st));
-    uint64_t raw_base = 0;
-    if (desc_bytes > 61) {  // every byte of a row counts: the pair matcher of akz_descriptor_match
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1], na = sets[a].n_descriptors;
-            tab[(size_t)p] = launch::PairJobHost{raw_base, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0, (uint32_t)p, 0};
-            if (na)
-                AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)a] * 64, na, d_rows + set_row[(size_t)b] * 64, sets[b].n_descriptors,
-                                          10000, lowes_ratio, d_raw + raw_base, d_cnt + p, false));
-            raw_base += na;
-        }
-    } else {  // one multi-set launch per first set over its second sets (split at the matcher's limits)
-        std::vector<std::vector<uint64_t>> groups;
-        std::vector<int64_t> group_of((size_t)n_sets, -1);
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            const uint64_t a = pairs[2 * p];
-            if (group_of[(size_t)a] < 0) {
-                group_of[(size_t)a] = (int64_t)groups.size();
-                groups.emplace_back();
-            }
-            groups[(size_t)group_of[(size_t)a]].push_back(p);
-        }
-        uint32_t cnt_base = 0;
-        std::vector<uint64_t> first, nrows;
-        for (const auto& g : groups) {
-            const uint64_t a = pairs[2 * g[0]], n0 = sets[a].n_descriptors;
-            const uint64_t max_sets = std::max<uint64_t>(1, std::min<uint64_t>(65535, n0 ? 0x7fffffffull / launch::match_mfma_rows((uint32_t)n0, true) : 65535));
-            for (size_t i = 0; i < g.size();) {
-                first.clear();
-                nrows.clear();
-                uint64_t train = 0;
-                const size_t i0 = i;
-                while (i < g.size() && first.size() < max_sets) {
-                    const uint64_t b = pairs[2 * g[i] + 1], nb = sets[b].n_descriptors;
-                    if (!first.empty() && train + nb > 0x7fffffffull) break;
-                    first.push_back(set_row[(size_t)b]);
-                    nrows.push_back(nb);
-                    train += nb;
-                    const uint64_t p = g[i];
-                    tab[(size_t)p] = launch::PairJobHost{raw_base + (i - i0) * n0, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0,
-                                                                   cnt_base + (uint32_t)(i - i0), 0};
-                    ++i;
-                }
-                if (n0)
-                    AKZ_TRY(match_sets_at(c, d_rows + set_row[(size_t)a] * 64, n0, d_rows, first.data(), nrows.data(), first.size(), 10000,
-                                          lowes_ratio, d_raw + raw_base, d_cnt + cnt_base, nullptr, nullptr));
-                raw_base += first.size() * n0;
-                cnt_base += (uint32_t)first.size();
-            }
-        }
-    }
+    std::vector<launch::PairJobHost> tab;
+    AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, set_row, d_rows, d_raw, d_cnt, tab));
     launch::PairJobHost* h_tab = (launch::PairJobHost*)c->mp_pin_tab.p;
     uint64_t* h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
     std::memcpy(h_tab, tab.data(), (size_t)n_pairs * sizeof(launch::PairJobHost));

@@ -47,12 +47,6 @@ DefaultSource& default_source() {
     return src;
 }
 
-namespace {
-
-struct Model {
-    float f[9];  // row-major 3 x 3
-};
-
 // the refusals every call over a list of matches shares; `name` is the call's
 int refuse_bad_matches(const char* name, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
                        const akz_match* matches, uint64_t n_matches, const akz_match* out, const uint64_t* n_out) {
@@ -68,20 +62,10 @@ int refuse_bad_matches(const char* name, const akz_keypoint* keypoints_0, uint64
     return AKZ_OK;
 }
 
-// The matched point pairs side by side, x0 | y0 | x1 | y1 with n_matches floats each: the inlier count of a trial -- 8 M
-// evaluations for the 8 000 matches of a 4K pair at 1 000 trials -- is then a streaming loop the compiler vectorises instead
-// of two gathers of 32-byte keypoints per evaluation.
-struct MatchPoints {
-    std::vector<float> v;
-    const float *x0, *y0, *x1, *y1;
-    MatchPoints(const akz_keypoint* keypoints_0, const akz_keypoint* keypoints_1, const akz_match* matches, uint64_t n) : v((size_t)n * 4) {
-        float* p = v.data();
-        x0 = p; y0 = p + n; x1 = p + 2 * n; y1 = p + 3 * n;
-        for (uint64_t i = 0; i < n; ++i) {
-            p[i] = keypoints_0[matches[i].index_0].x; p[n + i] = keypoints_0[matches[i].index_0].y;
-            p[2 * n + i] = keypoints_1[matches[i].index_1].x; p[3 * n + i] = keypoints_1[matches[i].index_1].y;
-        }
-    }
+namespace {
+
+struct Model {
+    float f[9];  // row-major 3 x 3
 };
 
 // the model of exactly M::K matches (estimate_fundamental_matrix :17-69 for K = 8): *found = 0 is the reference's `None`

@@ -7,8 +7,12 @@
 //   k_ransac_trials                       akz_match_features: a workgroup per trial of one pair, winner and filter on the host
 //   k_pair_points, k_pairs_trials<Model, NW>, k_pairs_pick_filter<Model>
 //                                         the pairs calls: everything but the draws, over the pair records (PairJobHost)
+//   k_seeded_round<Model, NW>, k_seeded_update
+//                                         the seeded pairs call: rounds of trials that draw their own samples, and the per-pair
+//                                         best, stopping rule and trial count after each round
 #include "akz_homography.hpp"
 #include "akz_ransac_device.hpp"
+#include "akz_ransac_seeded.hpp"
 
 namespace akz {
 namespace {
@@ -219,6 +223,138 @@ __global__ void __launch_bounds__(TW * NW) k_pairs_trials(const PairJob* __restr
     }
 }
 
+// ---- the seeded pairs call (akz_match_features_seeded_pairs; the statement: akz_ransac_seeded.hpp) ---------------------------------
+// One round of AKZ_RANSAC_ROUND trials of every pair that still runs: workgroup 8 p + w has trials 128 round + 16 w .. + 16 of
+// pair p, in the layout of k_pairs_trials (four lanes per trial, the wave counts with all lanes, NW - 1 helper waves that
+// only count).  A workgroup whose pair is done, or whose trials lie at or past max_trials, leaves at once.  Each trial forms its
+// own sample from (seed key k1, stream stream_base + p, trial) on its first lane -- no sample buffer, no host draw -- and hands
+// it to its four lanes through LDS.  Models and counts go to slot (trial mod 128) of the pair's ring; no model: the count -1.
+constexpr unsigned WPR = AKZ_RANSAC_ROUND / TPW;  // workgroups per pair and round
+template <class Model, int NW>
+__global__ void __launch_bounds__(TW * NW) k_seeded_round(const PairJob* __restrict__ pairs, const unsigned* __restrict__ done,
+                                                          unsigned long long k1, unsigned long long stream_base, unsigned round,
+                                                          unsigned max_trials, const unsigned long long* __restrict__ raw_cnt,
+                                                          const float* __restrict__ pts, unsigned long long stride, float epsilon_model,
+                                                          float epsilon_inlier, float* __restrict__ ring_mdl, int* __restrict__ ring_inl) {
+    constexpr int K = Model::K;
+    __shared__ double s_m[TPW][8 * 9];
+    __shared__ typename Model::Side s_side[TPW];
+    __shared__ float s_f[TPW][9];
+    __shared__ unsigned s_smp[TPW][8];
+    __shared__ int s_ok[TPW];
+    __shared__ int s_cnt[TPW];
+    const int tid = (int)threadIdx.x, lane = tid & (TW - 1), tw = lane >> 2, sub = lane & 3;
+    const unsigned p = blockIdx.x / WPR, slot0 = (blockIdx.x % WPR) * TPW, t0 = round * AKZ_RANSAC_ROUND + slot0;
+    if (done[p] != 0u || t0 >= max_trials) return;  // (the same for the whole workgroup)
+    const unsigned here = min((unsigned)TPW, max_trials - t0);  // trials of this workgroup
+    const PairJob pj = pairs[p];
+    const unsigned n = (unsigned)raw_cnt[pj.cnt_idx];
+    float* mdl = ring_mdl + (size_t)p * AKZ_RANSAC_ROUND * 9;
+    int* inl = ring_inl + (size_t)p * AKZ_RANSAC_ROUND;
+    const unsigned long long ks = seeded_stream_key(k1, stream_base + p);  // (uniform: the pair's stream)
+    if (NW == 1 || tid < TW) {  // the models: the first wave
+        const bool valid = (unsigned)tw < here;
+        LdsMat m{s_m[tw]};
+        if (valid && sub == 0) {
+            unsigned smp[K];
+            seeded_sample<K>(ks, (unsigned long long)t0 + (unsigned)tw, n, smp);
+#pragma unroll
+            for (int i = 0; i < K; ++i) s_smp[tw][i] = smp[i];
+        }
+        wave_sync();
+        bool usable = false;
+        if (valid) usable = Model::rows(m, s_side[tw], sub, s_smp[tw], pj.raw_off, pts, stride);
+        wave_sync();
+        bool active = usable;
+        for (int sweep = 0; sweep < 60; ++sweep) {
+            if (__ballot(active) == 0ull) break;
+            const bool rotated = jacobi_sweep_levels<8>(m, sub, active);
+            if (((__ballot(rotated) >> (4 * tw)) & 0xfull) == 0ull) active = false;  // this trial's first sweep without a rotation
+        }
+        if (valid && sub == 0) {
+            float f[9];
+            const bool ok = usable && Model::model(m, s_side[tw], epsilon_model, f);
+            const unsigned slot = slot0 + (unsigned)tw;
+            s_ok[tw] = ok ? 1 : 0;
+            if (NW > 1) s_cnt[tw] = 0;
+            if (ok) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    s_f[tw][k] = f[k];
+                    mdl[slot * 9 + k] = f[k];
+                }
+            } else {
+                inl[slot] = -1;
+            }
+        }
+    }
+    if (NW == 1) wave_sync();
+    else __syncthreads();
+    const float *x0 = pts + pj.raw_off, *y0 = x0 + stride, *x1 = y0 + stride, *y1 = x1 + stride;
+    for (unsigned u = 0; u < here; ++u) {
+        if (!s_ok[u]) continue;
+        float f[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f[k] = s_f[u][k];
+        int cnt = 0;
+        for (unsigned i = (unsigned)tid; i < n; i += TW * NW) cnt += Model::inlier(f, x0[i], y0[i], x1[i], y1[i], epsilon_inlier) ? 1 : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        if (NW == 1) {
+            if (lane == 0) inl[slot0 + u] = cnt;
+        } else if (lane == 0) {
+            atomicAdd(&s_cnt[u], cnt);
+        }
+    }
+    if (NW > 1) {
+        __syncthreads();
+        if ((unsigned)tid < here && s_ok[tid]) inl[slot0 + (unsigned)tid] = s_cnt[tid];
+    }
+}
+
+// After a round, one wave per pair that still runs: the round's first maximum (the largest count, the lowest trial among
+// equals) replaces the pair's running best only if it is strictly greater -- a later tie never does -- and its model goes to the
+// pair's best slot; trials_run = the trials done so far, T; the pair is done if best >= need[need_index] (need: the host's table
+// of seeded_need for the rounds of one window, need_stride entries per pair; null: no stopping rule) or T == max_trials; else it
+// counts in running[round].
+__global__ void __launch_bounds__(TW) k_seeded_update(unsigned round, unsigned max_trials, const unsigned* __restrict__ need,
+                                                      unsigned need_stride, unsigned need_index,
+                                                      const float* __restrict__ ring_mdl, const int* __restrict__ ring_inl,
+                                                      unsigned* __restrict__ done, int* __restrict__ best_inl, float* __restrict__ best_mdl,
+                                                      unsigned* __restrict__ trials_run, unsigned* __restrict__ running) {
+    const unsigned p = blockIdx.x, lane = threadIdx.x;
+    if (done[p] != 0u) return;
+    const unsigned t0 = round * AKZ_RANSAC_ROUND, cnt = min(AKZ_RANSAC_ROUND, max_trials - t0);  // (a running pair has t0 < max_trials)
+    const int* inl = ring_inl + (size_t)p * AKZ_RANSAC_ROUND;
+    int best = 0;
+    unsigned bidx = ~0u;
+    for (unsigned i = lane; i < cnt; i += TW) {
+        const int v = inl[i];
+        if (v > best) {
+            best = v;
+            bidx = i;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int ob = __shfl_xor(best, o, 64);
+        const unsigned oi = __shfl_xor(bidx, o, 64);
+        if (ob > best || (ob == best && oi < bidx)) {
+            best = ob;
+            bidx = oi;
+        }
+    }
+    const int before = best_inl[p];
+    if (best > before && lane < 9) best_mdl[(size_t)p * 9 + lane] = ring_mdl[((size_t)p * AKZ_RANSAC_ROUND + bidx) * 9 + lane];
+    if (lane == 0) {
+        const unsigned T = t0 + cnt, now = (unsigned)max(best, before);
+        if (best > before) best_inl[p] = best;
+        trials_run[p] = T;
+        if (T == max_trials || (need && now >= need[(size_t)p * need_stride + need_index])) done[p] = 1u;
+        else atomicAdd(running + round, 1u);
+    }
+}
+
 // Per pair (a workgroup, grid-stride): the winner among its trials (pick_winner; fewer than K matches: none), and the matches
 // it keeps (Model::inlier, as the host's final filter), compacted in match order.  Fewer than K matches: all kept.  No winner:
 // the zero model is evaluated, or (kKeepAllWithoutWinner) all kept.  h_out / found_out, where the call hands the model back (else
@@ -288,6 +424,28 @@ void pairs_trials(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, 
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TW * nw), 0, s, d_pairs, d_trials, (unsigned long long)first_trial, n_trials,
                        (const unsigned long long*)d_raw_cnt, d_pts, (unsigned long long)pts_stride, epsilon_model, epsilon_inlier, d_models,
                        d_inliers);
+}
+void seeded_round(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const uint32_t* d_done, uint64_t k1,
+                  uint64_t stream_base, uint32_t round, uint32_t max_trials, const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride,
+                  float epsilon_model, float epsilon_inlier, float* d_ring_mdl, int32_t* d_ring_inl) {
+    if (n_pairs == 0) return;
+    // Helper waves, as k_pairs_trials has them for small launches, here for both models: a round is 8 workgroups per pair by
+    // construction, so below 64 pairs (512 workgroups: half the chip's SIMDs) a lone wave per workgroup would count its 16
+    // trials over every match with most of the chip idle.  Counts are integers: the same for every NW.
+    const uint32_t blocks = n_pairs * WPR;
+    const bool helpers = blocks < 512;
+    auto k = model == RansacModel::Fundamental ? (helpers ? k_seeded_round<FundamentalDev, 4> : k_seeded_round<FundamentalDev, 1>)
+                                               : (helpers ? k_seeded_round<HomographyDev, 4> : k_seeded_round<HomographyDev, 1>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(TW * (helpers ? 4 : 1)), 0, s, d_pairs, d_done, (unsigned long long)k1,
+                       (unsigned long long)stream_base, round, max_trials, (const unsigned long long*)d_raw_cnt, d_pts,
+                       (unsigned long long)pts_stride, epsilon_model, epsilon_inlier, d_ring_mdl, d_ring_inl);
+}
+void seeded_update(hipStream_t s, uint32_t n_pairs, uint32_t round, uint32_t max_trials, const uint32_t* d_need, uint32_t need_stride,
+                   uint32_t need_index, const float* d_ring_mdl, const int32_t* d_ring_inl, uint32_t* d_done, int32_t* d_best_inl, float* d_best_mdl,
+                   uint32_t* d_trials_run, uint32_t* d_running) {
+    if (n_pairs == 0) return;
+    hipLaunchKernelGGL(k_seeded_update, dim3(n_pairs), dim3(TW), 0, s, round, max_trials, d_need, need_stride, need_index, d_ring_mdl, d_ring_inl, d_done,
+                       d_best_inl, d_best_mdl, d_trials_run, d_running);
 }
 void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw,
                        const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers,

@@ -113,6 +113,37 @@ class FeatureSet(C.Structure):
     _fields_ = [("keypoints", C.c_void_p), ("n_keypoints", C.c_uint64), ("descriptors", C.c_void_p),
                 ("n_descriptors", C.c_uint64)]
 
+class RansacOptions(C.Structure):
+    """akz_ransac_options: the options of the seeded RANSAC (remove_outliers_seeded, match_features_seeded(_pairs)).  A new
+    object holds akz_ransac_options_default -- fundamental matrix, ratio 0.86, 1 000 trials, epsilon_inliers 0.02, confidence
+    0.99, seed (42, 69), stream_base 0, no refit, no guided stage -- then the keyword arguments (seed: a pair)."""
+    _fields_ = [("struct_size", C.c_uint32), ("model_kind", C.c_int32), ("lowes_ratio", C.c_double), ("max_trials", C.c_uint64),
+                ("epsilon_inliers", C.c_float), ("refine_iterations", C.c_uint32), ("confidence", C.c_double),
+                ("seed", C.c_uint64 * 2), ("stream_base", C.c_uint64), ("guided", C.c_int32), ("guided_radius", C.c_float),
+                ("guided_lowes_ratio", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().akz_ransac_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k == "seed":
+                self.seed[0], self.seed[1] = v
+            elif k not in dict(self._fields_):
+                raise TypeError(f"no option {k!r}")
+            else:
+                setattr(self, k, v)
+
+    def copy(self, **kw):
+        o = RansacOptions()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(self))
+        for k, v in kw.items():
+            if k == "seed":
+                o.seed[0], o.seed[1] = v
+            else:
+                setattr(o, k, v)
+        return o
+
+
 _lib = None
 
 
@@ -256,6 +287,13 @@ def lib():
                                                            C.c_float, f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
         "akz_match_features_fundamental_refined_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, C.c_float,
                                                                  f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
+        "akz_ransac_options_default": ([C.POINTER(RansacOptions)], None),
+        "akz_draw_sample_seeded": ([u64, u64, u64, u64, u64, i32, pu64], i32),
+        "akz_ransac_required_inliers": ([u64, i32, u64, f64, pu64], i32),
+        "akz_remove_outliers_seeded": ([vp, u64, vp, u64, vp, u64, C.POINTER(RansacOptions), u64, vp, pu64, fp, C.POINTER(i32),
+                                        C.POINTER(C.c_uint32), pu64], i32),
+        "akz_match_features_seeded_pairs": ([vp, vp, u64, vp, u64, u64, C.POINTER(RansacOptions), vp, pu64, fp, C.POINTER(i32),
+                                             C.POINTER(C.c_uint32), pu64], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
@@ -844,6 +882,18 @@ class Context:
                                                                          refine_iterations, guided_radius, guided_lowes_ratio, *a.tail,
                                                                          *a.refined()))
         return a.lists_models_iterations()
+
+    def match_features_seeded_pairs(self, features, pairs, options=None):
+        """match_features over many pairs with the seeded RANSAC (akz_match_features_seeded_pairs): the trial kernel draws its
+        own samples from (options.seed, options.stream_base + pair, trial) and options.confidence stops a pair's trials on the
+        device; the thread's random source is not touched.  Returns one (matches, model or None, accepted fits, trials run) per
+        pair, each equal to remove_outliers_seeded on that pair's raw list with stream = stream_base + pair (then the guided
+        scan, if options.guided)."""
+        a = _PairsArgs(self, features, pairs)
+        opt = options if options is not None else RansacOptions()
+        tr = np.zeros(max(1, len(a.pr)), np.uint64)
+        _check(lib().akz_match_features_seeded_pairs(*a.head, C.byref(opt), *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
 
     def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
         """Guided matching over many pairs in one call (akz_descriptor_match_guided_pairs): features and pairs as for
@@ -1698,6 +1748,57 @@ def match_features_fundamental_refined_guided_pairs(features, pairs, lowes_ratio
     """Context.match_features_fundamental_refined_guided_pairs on ctx (default: the default context)."""
     return (ctx or default_context()).match_features_fundamental_refined_guided_pairs(
         features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio)
+
+
+# ---- seeded RANSAC: samples drawn on the GPU, trials stopped by confidence (an addition; include/akaze_hip.h, DESIGN.md 8) ------
+RANSAC_ROUND = 128            # AKZ_RANSAC_ROUND: trials per round of the seeded RANSAC
+RANSAC_MAX_TRIALS = 1 << 24   # the largest max_trials it accepts
+
+
+def draw_sample_seeded(seed0, seed1, stream, trial, n_matches, k):
+    """The sample of trial `trial` of `stream` over n_matches matches (akz_draw_sample_seeded): k (4 or 8) ascending indices."""
+    out = np.zeros(8, np.uint64)
+    _check(lib().akz_draw_sample_seeded(seed0, seed1, stream, trial, n_matches, k, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out[:k].copy()
+
+
+def ransac_required_inliers(n_matches, k, trials, confidence):
+    """The inlier count that stops a pair of n_matches matches after `trials` trials (akz_ransac_required_inliers)."""
+    need = C.c_uint64()
+    _check(lib().akz_ransac_required_inliers(n_matches, k, trials, confidence, C.byref(need)))
+    return need.value
+
+
+def remove_outliers_seeded(keypoints_0, keypoints_1, matches, options=None, stream=0):
+    """The seeded RANSAC on the host (akz_remove_outliers_seeded; no GPU call) -> (matches kept, model or None, accepted fits,
+    trials run): rounds of 128 trials whose samples are a function of (options.seed, stream, trial), stopped by
+    options.confidence, then the filter and, with options.refine_iterations, the refit."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    opt = options if options is not None else RansacOptions()
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    n = C.c_uint64()
+    f = np.zeros(9, np.float32)
+    found = C.c_int()
+    it = C.c_uint32()
+    tr = C.c_uint64()
+    _check(lib().akz_remove_outliers_seeded(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                            m.ctypes.data_as(C.c_void_p), len(m), C.byref(opt), stream, out.ctypes.data_as(C.c_void_p),
+                                            C.byref(n), f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found), C.byref(it), C.byref(tr)))
+    return out[:n.value].copy(), (f.reshape(3, 3) if found.value else None), it.value, tr.value
+
+
+def match_features_seeded_pairs(features, pairs, options=None, ctx=None):
+    """Context.match_features_seeded_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_seeded_pairs(features, pairs, options)
+
+
+def match_features_seeded(keypoints_0, descriptors_0, keypoints_1, descriptors_1, options=None, ctx=None):
+    """One pair through match_features_seeded_pairs (its stream: options.stream_base) -> (matches, model or None, accepted
+    fits, trials run)."""
+    return (ctx or default_context()).match_features_seeded_pairs([(keypoints_0, descriptors_0), (keypoints_1, descriptors_1)],
+                                                                  [(0, 1)], options)[0]
 
 
 # ------------------------------------------------------------------------------------------

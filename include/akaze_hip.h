@@ -784,6 +784,78 @@ int akz_match_features_fundamental_refined_guided_pairs(akz_ctx* ctx, const akz_
                                                         uint64_t* n_out /* n_pairs */, float* f /* 9 x n_pairs */,
                                                         int* found /* n_pairs */, uint32_t* iterations /* n_pairs */);
 
+/* ---- seeded RANSAC: samples drawn on the GPU, trials stopped by confidence (an addition) ------------------------
+   Every call above draws its samples on the calling thread from the thread's random source, in pair order, and runs exactly
+   ransac_trials trials.  The calls below use a counter-based generator instead: the sample of trial t of a pair is a pure
+   function of (seed, stream, t), so the trial kernel draws it itself, pairs do not depend on each other, and a confidence
+   stops a pair's trials on the device.  The calling thread's random source is neither read nor advanced by any of them.
+   The statement (csrc/akz_ransac_seeded.hpp; u64 arithmetic wraps):
+     G = 0x9E3779B97F4A7C15;  mix64(z): z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31
+     k0 = mix64(seed[0] + G), k1 = mix64(seed[1] ^ k0), ks = mix64(k1 + G (stream + 1)),
+     v(t, i) = mix64(ks + G (8 t + i + 1)) for draw i < K of trial t; K = 8 (fundamental matrix) or 4 (homography).
+   Sample of trial t over n >= K matches (Floyd: K draws, no rejection, every K-subset equally likely): for i = 0 .. K-1 with
+   j = n - K + i, r = the high 64 bits of v(t, i) (j + 1); j is inserted if r is in the set already, else r; the K indices in
+   ascending order.  The model of a sample and the inlier rule are those of akz_remove_outliers_fundamental (epsilon_model
+   0.05) / akz_remove_outliers_homography (AKZ_HOMOGRAPHY_EPSILON_MODEL).  Trials run in rounds of 128 (the last may be
+   shorter); after each round, with T trials done and best the largest inlier count so far (the first trial that reached it is
+   the winner: a later tie does not replace it), a pair with confidence > 0 stops iff best >= need(n, K, T, confidence), the
+   smallest b in 1 .. n with powi(1 - powi(b / n, K), T) <= 1 - confidence in f64 -- powi(w, K) by K - 1 successive
+   multiplications by w, powi(q, T) by binary exponentiation (res = 1; while T: if T & 1: res *= q; T >>= 1; if T: q *= q),
+   no contraction --; otherwise it stops at T = max_trials.  confidence = 0 switches the rule off: exactly max_trials run.
+   Per pair: trials_run; found = best > 0; the model of the winner (zeros where found is 0, for both models); the list by the
+   rules of the calls above -- fewer than K matches: unchanged, nothing run, trials_run 0; no winner: the zero model is
+   evaluated (fundamental) or every match is kept (homography); max_trials = 0 as ransac_trials = 0.  Where found = 1 and
+   refine_iterations > 0, the list, the model and iterations are those of akz_refine_fundamental_matrix / akz_refine_homography
+   on the raw list from the winner with epsilon_inliers. */
+typedef struct akz_ransac_options {
+    uint32_t struct_size;       /* sizeof(akz_ransac_options) */
+    int32_t model_kind;         /* AKZ_GUIDED_HOMOGRAPHY or AKZ_GUIDED_FUNDAMENTAL */
+    double lowes_ratio;         /* of the descriptor scan (GPU call only) */
+    uint64_t max_trials;        /* <= 1 << 24; the GPU call enqueues 2 launches per round of 128 and, per window of 8 rounds
+                                   still running, computes 8 need() values per pair on the calling thread */
+    float epsilon_inliers;
+    uint32_t refine_iterations; /* 0: the refit is off */
+    double confidence;          /* 0: off; otherwise 0 < c < 1 */
+    uint64_t seed[2];
+    uint64_t stream_base;       /* pair p of a call uses stream stream_base + p */
+    int32_t guided;             /* != 0: the guided stage (GPU call only) */
+    float guided_radius;
+    double guided_lowes_ratio;
+} akz_ransac_options;
+/* fundamental matrix, ratio 0.86, 1 000 trials, confidence 0.99, seed {42, 69}, stream_base 0, the refit and the guided stage off (its
+   radius 3 px and ratio 0.86 are set for a caller who switches it on); epsilon_inliers 0.02, the value tools/fundamental_refit.py
+   measures with: |p1^T F p0| at unit norm, 1 .. 5 px on 1080p two-view scenes -- a homography wants pixels, set it */
+void akz_ransac_options_default(akz_ransac_options* options);
+/* the sample alone: out receives the k (4 or 8) ascending indices of trial `trial` of `stream` over n_matches >= k matches */
+int akz_draw_sample_seeded(uint64_t seed0, uint64_t seed1, uint64_t stream, uint64_t trial, uint64_t n_matches, int k,
+                           uint64_t* out /* k */);
+/* need(n_matches, k, trials, confidence) of the statement; k 4 or 8, n_matches and trials >= 1, 0 < confidence < 1 */
+int akz_ransac_required_inliers(uint64_t n_matches, int k, uint64_t trials, double confidence, uint64_t* need);
+/* The host statement: rounds, winner, filter and refit over one raw match list with stream `stream`.  No GPU call and no
+   descriptor work: lowes_ratio and the guided fields are ignored.  out must hold n_matches entries; model (9), found, iterations
+   and trials_run may be NULL.  Refusals (AKZ_ERR_INVALID_ARG, nothing written): those of akz_remove_outliers, and of the
+   options -- NULL, a struct_size other than sizeof(akz_ransac_options), an unknown model_kind, max_trials > 1 << 24, a confidence
+   that is negative, NaN or >= 1 -- and, with refine_iterations > 0, an epsilon_inliers that akz_refine_homography refuses. */
+int akz_remove_outliers_seeded(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                               const akz_match* matches, uint64_t n_matches, const akz_ransac_options* options, uint64_t stream,
+                               akz_match* out, uint64_t* n_out, float* model /* 9 */, int* found, uint32_t* iterations,
+                               uint64_t* trials_run);
+/* match_features over many pairs with the seeded RANSAC, all on the GPU: sets, pairs, the layout of out and the fixed room per
+   pair are those of akz_match_features_pairs.  Pair p's result equals akz_remove_outliers_seeded on that pair's raw list
+   descriptor_match(d0, d1, 10000, lowes_ratio) with stream = stream_base + p, bit for bit: the list, the model bits, found,
+   iterations and trials_run.  With guided != 0, where found = 1 the returned list is akz_descriptor_match_guided(pair,
+   model_kind, the final model, guided_radius, 10000, guided_lowes_ratio), exactly as in the _guided forms above.  A pair's result
+   therefore does not depend on the other pairs of the call: the batch equals the loop of one-pair calls with stream_base + p.
+   model: 9 floats per pair, found / iterations / trials_run: one per pair; each may be NULL.
+   Refusals (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written): everything akz_match_features_pairs refuses, the
+   options' refusals above, n_pairs >= 1 << 28, and with guided the guided call's radius rule (finite, >= 0) and limits.
+   epsilon_inliers is NOT refused here, whatever refine_iterations is: the rule stated for the _refined forms above applies,
+   and the equality with the host statement is promised for the epsilons that statement accepts. */
+int akz_match_features_seeded_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                    uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out,
+                                    uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
+                                    uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly
