@@ -2,8 +2,10 @@
 // k_pairs_pick_filter (akz_ransac_kernels.hip) has left every pair's winner, found flag and kept list on the device, this
 // kernel runs the local optimisation of akz_homography_refit.hpp on the pair's RAW list -- the same source as the host
 // statements akz_refine_homography and akz_refine_fundamental_matrix, the same bits -- and rewrites the model, the kept list
-// and its count.  One loop, two models: k_refit<R> with R = HomographyRefit (akz_homography_refit.hpp) or FundamentalRefit
-// (akz_fundamental_refit.hpp).
+// and its count.  One loop for every model: k_refit<R> with R = HomographyRefit (akz_homography_refit.hpp), FundamentalRefit
+// (akz_fundamental_refit.hpp) or, for the seeded call's third kind, FundamentalNormalisedRefit (akz_fmatrix_normalised.hpp:
+// FundamentalRefit with the Sampson rule).
+#include "akz_fmatrix_normalised.hpp"
 #include "akz_fundamental_refit.hpp"
 #include "akz_homography_refit.hpp"
 #include "akz_ransac_device.hpp"
@@ -201,7 +203,9 @@ void model_refit(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, u
                       const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
                       void* d_keep, uint64_t* d_keep_cnt, float* d_h, const int32_t* d_found, uint32_t* d_iterations) {
     if (n_pairs == 0) return;
-    auto k = model == RansacModel::Fundamental ? k_refit<FundamentalRefit> : k_refit<HomographyRefit>;
+    auto k = model == RansacModel::Fundamental  ? k_refit<FundamentalRefit>
+             : model == RansacModel::Homography ? k_refit<HomographyRefit>
+                                                : k_refit<FundamentalNormalisedRefit>;
     hipLaunchKernelGGL(k, dim3(std::min<uint32_t>(n_pairs, 8192)), dim3(RF), 0, s, d_pairs, n_pairs, (const akz_match*)d_raw,
                        (const unsigned long long*)d_raw_cnt, d_pts, (unsigned long long)pts_stride, epsilon_model, epsilon_inlier,
                        max_iterations, (akz_match*)d_keep, (unsigned long long*)d_keep_cnt, d_h, d_found, d_iterations);

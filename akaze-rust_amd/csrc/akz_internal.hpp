@@ -384,7 +384,9 @@ struct PairJobHost {
     uint32_t cnt_idx, pad;
 };
 static_assert(sizeof(PairJobHost) == 56, "the device reads 56-byte pair records");
-enum class RansacModel { Fundamental, Homography };  // 8 / 4 matches per sample (FundamentalRansac, HomographyRansac)
+// 8 / 4 / 8 matches per sample (FundamentalRansac, HomographyRansac, FundamentalNormalisedRansac: the seeded calls only --
+// seeded_round, pairs_pick_filter over the best slots, model_refit)
+enum class RansacModel { Fundamental, Homography, FundamentalNormalised };
 // gathers the keypoint coordinates of every pair's matches (kx / ky: x / y of every uploaded set's keypoints)
 void pair_points(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                  const float* d_kx, const float* d_ky, float* d_pts, uint64_t pts_stride);

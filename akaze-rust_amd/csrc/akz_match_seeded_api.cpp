@@ -44,10 +44,15 @@ extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set
     AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
     if (opt.guided) AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
     AKZ_TRY(bind(c, true, false));
-    const bool fundamental = opt.model_kind == AKZ_GUIDED_FUNDAMENTAL;
-    const launch::RansacModel kind = fundamental ? launch::RansacModel::Fundamental : launch::RansacModel::Homography;
+    // (the normalised kind: a fundamental matrix too -- K = 8, the refit's rank rule for both stages, the epipolar band when guiding)
+    const bool normalised = opt.model_kind == AKZ_RANSAC_FUNDAMENTAL_NORMALISED;
+    const bool fundamental = opt.model_kind == AKZ_GUIDED_FUNDAMENTAL || normalised;
+    const launch::RansacModel kind = normalised    ? launch::RansacModel::FundamentalNormalised
+                                     : fundamental ? launch::RansacModel::Fundamental
+                                                   : launch::RansacModel::Homography;
+    const int guided_kind = fundamental ? AKZ_GUIDED_FUNDAMENTAL : AKZ_GUIDED_HOMOGRAPHY;
     const uint64_t K = fundamental ? 8 : 4;
-    const float epsilon_model = fundamental ? 0.05f : AKZ_HOMOGRAPHY_EPSILON_MODEL;
+    const float epsilon_model = normalised ? AKZ_FUNDAMENTAL_REFIT_EPSILON : fundamental ? 0.05f : AKZ_HOMOGRAPHY_EPSILON_MODEL;
     const float refit_epsilon = fundamental ? AKZ_FUNDAMENTAL_REFIT_EPSILON : AKZ_HOMOGRAPHY_EPSILON_MODEL;
     const uint32_t max_trials = (uint32_t)opt.max_trials, n_rounds = (max_trials + AKZ_RANSAC_ROUND - 1) / AKZ_RANSAC_ROUND;
     const bool stopping = opt.confidence > 0.0;
@@ -194,7 +199,7 @@ extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set
             spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
             off += sets[a].n_descriptors;
         }
-        AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, opt.model_kind, d_hm, d_hf, opt.guided_radius, 10000, opt.guided_lowes_ratio, d_gout,
+        AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, guided_kind, d_hm, d_hf, opt.guided_radius, 10000, opt.guided_lowes_ratio, d_gout,
                                d_gcnt));
         AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_cnt.p, d_gcnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     }

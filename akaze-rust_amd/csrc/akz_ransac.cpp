@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "akz_fmatrix.hpp"
+#include "akz_fmatrix_normalised.hpp"
 #include "akz_homography.hpp"
 #include "akz_fundamental_refit.hpp"
 #include "akz_homography_refit.hpp"
@@ -429,6 +430,23 @@ extern "C" int akz_refine_fundamental_matrix(const akz_keypoint* keypoints_0, ui
                                              uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* f_out, uint32_t* iterations) {
     return refine_host<FundamentalRefit>("refine_fundamental_matrix", "f_in", keypoints_0, n0, keypoints_1, n1, matches, n_matches, f_in,
                                          AKZ_FUNDAMENTAL_REFIT_EPSILON, epsilon_inlier, max_iterations, out, n_out, f_out, iterations);
+}
+
+// ---- the normalised 8-point model of the seeded family (akz_fmatrix_normalised.hpp) -----------------------------
+// one sample: fit(S) of the refit over exactly eight matches, in ascending order
+extern "C" int akz_estimate_fundamental_normalised(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                                   const akz_match* matches8, float* f, int* found) {
+    return estimate_model<FundamentalNormalisedRansac>("estimate_fundamental_normalised", keypoints_0, n0, keypoints_1, n1, matches8,
+                                                       AKZ_FUNDAMENTAL_REFIT_EPSILON, f, found);
+}
+
+// akz_refine_fundamental_matrix with the Sampson rule of that model
+extern "C" int akz_refine_fundamental_normalised(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                                 const akz_match* matches, uint64_t n_matches, const float* f_in, float epsilon_inlier,
+                                                 uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* f_out, uint32_t* iterations) {
+    return refine_host<FundamentalNormalisedRefit>("refine_fundamental_normalised", "f_in", keypoints_0, n0, keypoints_1, n1, matches,
+                                                   n_matches, f_in, AKZ_FUNDAMENTAL_REFIT_EPSILON, epsilon_inlier, max_iterations, out, n_out,
+                                                   f_out, iterations);
 }
 
 // random::default().seed([s0, s1]) for the calling thread

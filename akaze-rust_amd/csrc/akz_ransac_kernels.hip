@@ -10,6 +10,7 @@
 //   k_seeded_round<Model, NW>, k_seeded_update
 //                                         the seeded pairs call: rounds of trials that draw their own samples, and the per-pair
 //                                         best, stopping rule and trial count after each round
+#include "akz_fmatrix_normalised.hpp"
 #include "akz_homography.hpp"
 #include "akz_ransac_device.hpp"
 #include "akz_ransac_seeded.hpp"
@@ -100,6 +101,7 @@ __global__ void __launch_bounds__(256) k_pair_points(const PairJob* __restrict__
 // design rows (false: the sample gives no model, the trial never sweeps), what they keep beside the matrix, and the model
 // from the rotated matrix on one lane.
 struct FundamentalDev : FundamentalRansac {
+    static constexpr int kRows = 8;  // rows of the trial's matrix in LDS
     struct Side {};
     // rows sub and sub + 4; every sample is usable
     static __device__ bool rows(LdsMat m, Side&, int sub, const unsigned* smp, size_t off, const float* pts, unsigned long long stride) {
@@ -114,6 +116,7 @@ struct FundamentalDev : FundamentalRansac {
     static __device__ bool model(LdsMat m, const Side&, float epsilon, float (&f)[9]) { return model_from_rotated(m, epsilon, f); }
 };
 struct HomographyDev : HomographyRansac {
+    static constexpr int kRows = 8;
     struct Side {
         double v[6];  // c0x, c0y, s0, c1x, c1y, s1
     };
@@ -139,6 +142,77 @@ struct HomographyDev : HomographyRansac {
     }
     static __device__ bool model(LdsMat m, const Side& t, float epsilon, float (&h)[9]) {
         return hom_model_from_rotated(m, epsilon, t.v[0], t.v[1], t.v[2], t.v[3], t.v[4], t.v[5], h);
+    }
+};
+
+// The normalised 8-point model (akz_fmatrix_normalised.hpp; the seeded kernels only): the 9 x 9 normal matrix of the refit.
+// Lane j of the trial's four takes elements j and j + 4 of every sum over the sample (sum8_part) and the four parts combine
+// by two exchanges inside the quad in the order of sum8_join -- IEEE addition commutes, so all four lanes hold the bits of the
+// host's sum, and with them the same centroids and scales.  The 36 sums of pass 3 thus cost each lane two points, not eight,
+// and stay in registers; lane 0 writes M from them.  The rank-2 step and the denormalisation run on one lane (model).
+// (the exchanges are DPP quad permutes, register to register: __shfl_xor would send the 144 of pass 3 through the LDS crossbar)
+template <int QUAD_PERM>
+__device__ inline double quad_permute(double v) {
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, QUAD_PERM, 0xf, 0xf, false),
+                            __builtin_amdgcn_update_dpp(lo, lo, QUAD_PERM, 0xf, 0xf, false));
+}
+template <int N>
+__device__ inline void quad_join(double (&v)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        v[k] = v[k] + quad_permute<0x4e>(v[k]);  // lane ^ 2 (quad_perm [2, 3, 0, 1]): lanes 0, 2: p0 + p2; lanes 1, 3: p1 + p3
+        v[k] = v[k] + quad_permute<0xb1>(v[k]);  // lane ^ 1 (quad_perm [1, 0, 3, 2]): (p0 + p2) + (p1 + p3)
+    }
+}
+struct FundamentalNormalisedDev : FundamentalNormalisedRansac {
+    static constexpr int kRows = 9;
+    using Side = HomographyDev::Side;
+    // (the four lanes of a trial are all here or none is, and leave together: they decide on the same bits; inlined by force --
+    // left to itself the compiler calls it, and a call costs the kernel the registers of the calling convention)
+    static __device__ __forceinline__ bool rows(LdsMat m, Side& side, int sub, const unsigned* smp, size_t off, const float* pts, unsigned long long stride) {
+        const size_t ja = off + smp[sub], jb = off + smp[sub + 4];
+        const float ax0 = pts[ja], ay0 = pts[stride + ja], ax1 = pts[2 * stride + ja], ay1 = pts[3 * stride + ja];
+        const float bx0 = pts[jb], by0 = pts[stride + jb], bx1 = pts[2 * stride + jb], by1 = pts[3 * stride + jb];
+        double c[4];
+        {
+            double a[4], b[4];
+            refit_terms1(ax0, ay0, ax1, ay1, a);
+            refit_terms1(bx0, by0, bx1, by1, b);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[k] = sum8_part(a[k], b[k]);
+            quad_join(c);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[k] = c[k] / 8.0;
+        }
+        double s0 = 0.0, s1 = 0.0;
+        {
+            double a[2], b[2], d[2];
+            refit_terms2(ax0, ay0, ax1, ay1, c[0], c[1], c[2], c[3], a);
+            refit_terms2(bx0, by0, bx1, by1, c[0], c[1], c[2], c[3], b);
+            d[0] = sum8_part(a[0], b[0]);
+            d[1] = sum8_part(a[1], b[1]);
+            quad_join(d);
+            if (!refit_scale(d[0], 8.0, s0) || !refit_scale(d[1], 8.0, s1)) return false;
+        }
+        double sums[kFundRefitSums3];
+        {
+            double b[kFundRefitSums3];
+            fund_refit_terms3(ax0, ay0, ax1, ay1, c[0], c[1], s0, c[2], c[3], s1, sums);
+            fund_refit_terms3(bx0, by0, bx1, by1, c[0], c[1], s0, c[2], c[3], s1, b);
+#pragma unroll
+            for (int k = 0; k < kFundRefitSums3; ++k) sums[k] = sum8_part(sums[k], b[k]);
+            quad_join(sums);
+        }
+        if (sub == 0) {
+            fund_refit_normal_matrix(m, sums);
+            side.v[0] = c[0]; side.v[1] = c[1]; side.v[2] = s0;
+            side.v[3] = c[2]; side.v[4] = c[3]; side.v[5] = s1;
+        }
+        return true;
+    }
+    static __device__ bool model(LdsMat m, const Side& t, float epsilon, float (&f)[9]) {
+        return fund_refit_model_from_rotated(m, 8.0, epsilon, t.v[0], t.v[1], t.v[2], t.v[3], t.v[4], t.v[5], f);
     }
 };
 
@@ -236,8 +310,8 @@ __global__ void __launch_bounds__(TW * NW) k_seeded_round(const PairJob* __restr
                                                           unsigned max_trials, const unsigned long long* __restrict__ raw_cnt,
                                                           const float* __restrict__ pts, unsigned long long stride, float epsilon_model,
                                                           float epsilon_inlier, float* __restrict__ ring_mdl, int* __restrict__ ring_inl) {
-    constexpr int K = Model::K;
-    __shared__ double s_m[TPW][8 * 9];
+    constexpr int K = Model::K, ROWS = Model::kRows;
+    __shared__ double s_m[TPW][ROWS * 9];
     __shared__ typename Model::Side s_side[TPW];
     __shared__ float s_f[TPW][9];
     __shared__ unsigned s_smp[TPW][8];
@@ -268,7 +342,7 @@ __global__ void __launch_bounds__(TW * NW) k_seeded_round(const PairJob* __restr
         bool active = usable;
         for (int sweep = 0; sweep < 60; ++sweep) {
             if (__ballot(active) == 0ull) break;
-            const bool rotated = jacobi_sweep_levels<8>(m, sub, active);
+            const bool rotated = jacobi_sweep_levels<ROWS>(m, sub, active);
             if (((__ballot(rotated) >> (4 * tw)) & 0xfull) == 0ull) active = false;  // this trial's first sweep without a rotation
         }
         if (valid && sub == 0) {
@@ -435,7 +509,9 @@ void seeded_round(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, 
     const uint32_t blocks = n_pairs * WPR;
     const bool helpers = blocks < 512;
     auto k = model == RansacModel::Fundamental ? (helpers ? k_seeded_round<FundamentalDev, 4> : k_seeded_round<FundamentalDev, 1>)
-                                               : (helpers ? k_seeded_round<HomographyDev, 4> : k_seeded_round<HomographyDev, 1>);
+             : model == RansacModel::Homography
+                 ? (helpers ? k_seeded_round<HomographyDev, 4> : k_seeded_round<HomographyDev, 1>)
+                 : (helpers ? k_seeded_round<FundamentalNormalisedDev, 4> : k_seeded_round<FundamentalNormalisedDev, 1>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TW * (helpers ? 4 : 1)), 0, s, d_pairs, d_done, (unsigned long long)k1,
                        (unsigned long long)stream_base, round, max_trials, (const unsigned long long*)d_raw_cnt, d_pts,
                        (unsigned long long)pts_stride, epsilon_model, epsilon_inlier, d_ring_mdl, d_ring_inl);
@@ -451,7 +527,9 @@ void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pa
                        const uint64_t* d_raw_cnt, const float* d_pts, uint64_t pts_stride, const float* d_models, const int32_t* d_inliers,
                        float epsilon_inlier, void* d_keep, uint64_t* d_keep_cnt, float* d_h, int32_t* d_found) {
     if (n_pairs == 0) return;
-    auto k = model == RansacModel::Fundamental ? k_pairs_pick_filter<FundamentalDev> : k_pairs_pick_filter<HomographyDev>;
+    auto k = model == RansacModel::Fundamental  ? k_pairs_pick_filter<FundamentalDev>
+             : model == RansacModel::Homography ? k_pairs_pick_filter<HomographyDev>
+                                                : k_pairs_pick_filter<FundamentalNormalisedDev>;
     hipLaunchKernelGGL(k, dim3(std::min<uint32_t>(n_pairs, 8192)), dim3(kGroup), 0, s, d_pairs, n_pairs, (const akz_match*)d_raw,
                        (const unsigned long long*)d_raw_cnt, d_pts, (unsigned long long)pts_stride, d_models, d_inliers, epsilon_inlier,
                        (akz_match*)d_keep, (unsigned long long*)d_keep_cnt, d_h, d_found);

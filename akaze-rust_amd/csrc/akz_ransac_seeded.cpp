@@ -2,14 +2,17 @@
 // akz_match_features_seeded_pairs equals bit for bit.  Samples are a pure function of (seed, stream, trial)
 // (akz_ransac_seeded.hpp), trials run in rounds of AKZ_RANSAC_ROUND, and a pair stops after the round in which its best inlier
 // count reaches need(n, K, trials so far, confidence).  Models and inlier counts are those of akz_ransac.cpp (from_sample and
-// inlier of akz_fmatrix.hpp / akz_homography.hpp); the refit is akz_refine_homography / akz_refine_fundamental_matrix.  One
-// thread, in trial order: this is the definition, not a fast path.  The calling thread's default random source is not touched.
+// inlier of akz_fmatrix.hpp / akz_homography.hpp); the refit is akz_refine_homography / akz_refine_fundamental_matrix.  The
+// third kind, AKZ_RANSAC_FUNDAMENTAL_NORMALISED, is this family's alone: the normalised 8-point model and the Sampson rule of
+// akz_fmatrix_normalised.hpp, refitted by akz_refine_fundamental_normalised.  One thread, in trial order: this is the
+// definition, not a fast path.  The calling thread's default random source is not touched.
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "akz_fmatrix.hpp"
+#include "akz_fmatrix_normalised.hpp"
 #include "akz_homography.hpp"
 #include "akz_internal.hpp"
 #include "akz_ransac_seeded.hpp"
@@ -24,7 +27,9 @@ int seeded_refuse_options(const char* name, const akz_ransac_options* opt) {
     };
     if (!opt) return refuse("null options");
     if (opt->struct_size != sizeof(akz_ransac_options)) return refuse("options.struct_size is not sizeof(akz_ransac_options)");
-    if (opt->model_kind != AKZ_GUIDED_HOMOGRAPHY && opt->model_kind != AKZ_GUIDED_FUNDAMENTAL) return refuse("unknown options.model_kind");
+    if (opt->model_kind != AKZ_GUIDED_HOMOGRAPHY && opt->model_kind != AKZ_GUIDED_FUNDAMENTAL &&
+        opt->model_kind != AKZ_RANSAC_FUNDAMENTAL_NORMALISED)
+        return refuse("unknown options.model_kind");
     if (opt->max_trials > kSeededMaxTrials) return refuse("options.max_trials must be <= 1 << 24");
     if (!(opt->confidence >= 0.0 && opt->confidence < 1.0)) return refuse("options.confidence must be 0 (off) or 0 < c < 1");
     return AKZ_OK;
@@ -32,8 +37,9 @@ int seeded_refuse_options(const char* name, const akz_ransac_options* opt) {
 
 namespace {
 
-template <class M>
-int seeded_host(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1, const akz_match* matches,
+// `refine`: the refit of the model kind (akz_refine_homography and its kin)
+template <class M, class Refine>
+int seeded_host(Refine refine, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1, const akz_match* matches,
                 uint64_t n_matches, const akz_ransac_options& opt, uint64_t stream, float epsilon_model, akz_match* out, uint64_t* n_out,
                 float* model_out, int* found_out, uint32_t* iterations_out, uint64_t* trials_out) {
     constexpr int K = M::K;
@@ -74,7 +80,6 @@ int seeded_host(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint
             if ((M::kKeepAllWithoutWinner && best == 0) || M::inlier(best_model, x0[i], y0[i], x1[i], y1[i], opt.epsilon_inliers))
                 out[kept++] = matches[i];
         if (best > 0 && opt.refine_iterations > 0) {  // the list, the model and the accepted fits are the refit's
-            auto refine = K == 8 ? akz_refine_fundamental_matrix : akz_refine_homography;
             const float winner[9] = {best_model[0], best_model[1], best_model[2], best_model[3], best_model[4],
                                      best_model[5], best_model[6], best_model[7], best_model[8]};
             AKZ_TRY(refine(keypoints_0, n0, keypoints_1, n1, matches, n_matches, winner, opt.epsilon_inliers, opt.refine_iterations, out, &kept,
@@ -149,11 +154,15 @@ int akz_remove_outliers_seeded(const akz_keypoint* keypoints_0, uint64_t n0, con
         set_error("remove_outliers_seeded: with refine_iterations > 0, epsilon_inliers must be finite and > 0");
         return AKZ_ERR_INVALID_ARG;
     }
+    if (options->model_kind == AKZ_RANSAC_FUNDAMENTAL_NORMALISED)
+        return seeded_host<FundamentalNormalisedRansac>(akz_refine_fundamental_normalised, keypoints_0, n0, keypoints_1, n1, matches, n_matches,
+                                                        *options, stream, AKZ_FUNDAMENTAL_REFIT_EPSILON, out, n_out, model, found, iterations,
+                                                        trials_run);
     if (options->model_kind == AKZ_GUIDED_FUNDAMENTAL)
-        return seeded_host<FundamentalRansac>(keypoints_0, n0, keypoints_1, n1, matches, n_matches, *options, stream, 0.05f, out, n_out, model,
-                                              found, iterations, trials_run);
-    return seeded_host<HomographyRansac>(keypoints_0, n0, keypoints_1, n1, matches, n_matches, *options, stream, AKZ_HOMOGRAPHY_EPSILON_MODEL,
-                                         out, n_out, model, found, iterations, trials_run);
+        return seeded_host<FundamentalRansac>(akz_refine_fundamental_matrix, keypoints_0, n0, keypoints_1, n1, matches, n_matches, *options,
+                                              stream, 0.05f, out, n_out, model, found, iterations, trials_run);
+    return seeded_host<HomographyRansac>(akz_refine_homography, keypoints_0, n0, keypoints_1, n1, matches, n_matches, *options, stream,
+                                         AKZ_HOMOGRAPHY_EPSILON_MODEL, out, n_out, model, found, iterations, trials_run);
 }
 
 }  // extern "C"

@@ -292,6 +292,9 @@ def lib():
         "akz_ransac_required_inliers": ([u64, i32, u64, f64, pu64], i32),
         "akz_remove_outliers_seeded": ([vp, u64, vp, u64, vp, u64, C.POINTER(RansacOptions), u64, vp, pu64, fp, C.POINTER(i32),
                                         C.POINTER(C.c_uint32), pu64], i32),
+        "akz_estimate_fundamental_normalised": ([vp, u64, vp, u64, vp, fp, C.POINTER(i32)], i32),
+        "akz_refine_fundamental_normalised": ([vp, u64, vp, u64, vp, u64, fp, C.c_float, C.c_uint32, vp, pu64, fp,
+                                               C.POINTER(C.c_uint32)], i32),
         "akz_match_features_seeded_pairs": ([vp, vp, u64, vp, u64, u64, C.POINTER(RansacOptions), vp, pu64, fp, C.POINTER(i32),
                                              C.POINTER(C.c_uint32), pu64], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
@@ -1753,6 +1756,45 @@ def match_features_fundamental_refined_guided_pairs(features, pairs, lowes_ratio
 # ---- seeded RANSAC: samples drawn on the GPU, trials stopped by confidence (an addition; include/akaze_hip.h) ------
 RANSAC_ROUND = 128            # AKZ_RANSAC_ROUND: trials per round of the seeded RANSAC
 RANSAC_MAX_TRIALS = 1 << 24   # the largest max_trials it accepts
+
+
+# AKZ_RANSAC_FUNDAMENTAL_NORMALISED: the third model_kind of the seeded calls (the guided calls refuse it) -- the normalised
+# 8-point model with rank 2 enforced, epsilon_inliers a Sampson distance in pixels
+RANSAC_FUNDAMENTAL_NORMALISED = 3
+
+
+def estimate_fundamental_normalised(keypoints_0, keypoints_1, matches8):
+    """The normalised 8-point fundamental matrix of exactly 8 matches, given in ascending order of their position in the list
+    they were sampled from (akz_estimate_fundamental_normalised): 3x3 float32 F of unit norm and rank 2 with p1^T F p0 = 0, or
+    None.  It equals one fit of refine_fundamental_matrix over those eight, bit for bit."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches8, MATCH_DTYPE)
+    if len(m) != 8:
+        raise ValueError("exactly 8 matches")
+    f = np.zeros(9, np.float32)
+    found = C.c_int()
+    _check(lib().akz_estimate_fundamental_normalised(k0.ctypes.data, len(k0), k1.ctypes.data, len(k1), m.ctypes.data,
+                                                     f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
+    return f.reshape(3, 3) if found.value else None
+
+
+def refine_fundamental_normalised(keypoints_0, keypoints_1, matches, f, epsilon_inlier, max_iterations):
+    """refine_fundamental_matrix with the inlier rule of RANSAC_FUNDAMENTAL_NORMALISED: a Sampson distance below epsilon_inlier
+    pixels (akz_refine_fundamental_normalised) -> (inliers in match order, 3x3 float32 F, accepted fits)."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    fin = np.ascontiguousarray(np.asarray(f, np.float32).reshape(9))
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    n = C.c_uint64()
+    fout = np.zeros(9, np.float32)
+    it = C.c_uint32()
+    _check(lib().akz_refine_fundamental_normalised(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                                   m.ctypes.data_as(C.c_void_p), len(m), fin.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   epsilon_inlier, max_iterations, out.ctypes.data_as(C.c_void_p), C.byref(n),
+                                                   fout.ctypes.data_as(C.POINTER(C.c_float)), C.byref(it)))
+    return out[:n.value].copy(), fout.reshape(3, 3), it.value
 
 
 def draw_sample_seeded(seed0, seed1, stream, trial, n_matches, k):

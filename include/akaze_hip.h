@@ -807,9 +807,37 @@ int akz_match_features_fundamental_refined_guided_pairs(akz_ctx* ctx, const akz_
    evaluated (fundamental) or every match is kept (homography); max_trials = 0 as ransac_trials = 0.  Where found = 1 and
    refine_iterations > 0, the list, the model and iterations are those of akz_refine_fundamental_matrix / akz_refine_homography
    on the raw list from the winner with epsilon_inliers. */
+/* A third model kind, for the seeded calls alone (akz_remove_outliers_seeded, akz_match_features_seeded_pairs; the guided calls
+   refuse it, as they refuse 2): the Hartley-normalised 8-point algorithm with rank 2 enforced, judged in pixels.  The kind
+   above keeps the reference's trial model -- the raw-pixel design matrix, no rank-2 step, the algebraic |p1^T F p0| -- because
+   every call that promises the reference's bits must; the seeded calls promise none, and this is the model to use with them.
+     model of a sample: fit(S) of akz_refine_fundamental_matrix over the eight matches in ascending order (steps 1 - 5 above
+       with |S| = 8 and AKZ_FUNDAMENTAL_REFIT_EPSILON), every sum over e0 .. e7 as ((e0 + e4) + (e2 + e6)) + ((e1 + e5) +
+       (e3 + e7)), each element from +0.0 -- what the 256-lane tree does to eight members.  So it equals one fit of
+       akz_refine_fundamental_matrix(those eight, any f, an epsilon that keeps all eight, 1), bit for bit.  No model: a mean
+       distance of 0 in either image, the rank rule, a norm that is zero or not finite.
+     inlier rule (the Sampson distance below epsilon_inliers PIXELS, without a division; f32 in this order):
+       l0 = (f0 x0 + f1 y0) + f2;  l1 = (f3 x0 + f4 y0) + f5;  l2 = (f6 x0 + f7 y0) + f8;  s = (l0 x1 + l1 y1) + l2
+       m0 = (f0 x1 + f3 y1) + f6;  m1 = (f1 x1 + f4 y1) + f7;  d = ((l0 l0 + l1 l1) + m0 m0) + m1 m1
+       inlier iff s s < (eps eps) d.  Strict: a zero model or a NaN passes nothing -- so without a winner the list is EMPTY
+       (the zero model is evaluated, as for the other fundamental kind), the model is zeros and found is 0.
+     refit: akz_refine_fundamental_normalised, which is akz_refine_fundamental_matrix with that inlier rule.
+     guided stage: the epipolar band of AKZ_GUIDED_FUNDAMENTAL with the returned F.
+   Fewer than 8 matches: the list is unchanged and trials_run is 0.  The value is 3: 2 stays refused. */
+#define AKZ_RANSAC_FUNDAMENTAL_NORMALISED 3
+/* The model of exactly 8 matches (given in ascending order of their position in the list they were sampled from): *found = 0
+   where there is no model; f receives F (unit Frobenius norm, rank 2, p1^T F p0 = 0) where there is one. */
+int akz_estimate_fundamental_normalised(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                        const akz_match* matches8, float* f /* 9 */, int* found);
+/* akz_refine_fundamental_matrix with the Sampson rule above in place of |p1^T F p0| < epsilon_inlier: epsilon_inlier is a
+   distance in pixels.  Arguments, results and refusals are those of akz_refine_fundamental_matrix. */
+int akz_refine_fundamental_normalised(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                                      const akz_match* matches, uint64_t n_matches, const float* f_in /* 9 */, float epsilon_inlier,
+                                      uint32_t max_iterations, akz_match* out, uint64_t* n_out, float* f_out /* 9, may be NULL */,
+                                      uint32_t* iterations /* may be NULL */);
 typedef struct akz_ransac_options {
     uint32_t struct_size;       /* sizeof(akz_ransac_options) */
-    int32_t model_kind;         /* AKZ_GUIDED_HOMOGRAPHY or AKZ_GUIDED_FUNDAMENTAL */
+    int32_t model_kind;         /* AKZ_GUIDED_HOMOGRAPHY, AKZ_GUIDED_FUNDAMENTAL or AKZ_RANSAC_FUNDAMENTAL_NORMALISED */
     double lowes_ratio;         /* of the descriptor scan (GPU call only) */
     uint64_t max_trials;        /* <= 1 << 24; the GPU call enqueues 2 launches per round of 128 and, per window of 8 rounds
                                    still running, computes 8 need() values per pair on the calling thread */
