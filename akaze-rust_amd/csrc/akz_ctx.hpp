@@ -137,6 +137,8 @@ struct akz_ctx {
     // guided matching (akz_guided_api.cpp): pair table | models, chunk records, lists of a call; pinned: table | models, counts
     DevBuf gd_tab, gd_rec, gd_out;
     DevBuf gd_pin_tab, gd_pin_cnt, gd_pin_out;
+    // the cross-check (akz_cross_api.cpp): reverse lists | their counts | cross records of a call; pinned: the records
+    DevBuf cx_rev, cx_pin_tab;
     hipEvent_t mp_smp_ev[2] = {nullptr, nullptr};
     hipEvent_t mp_split_ev[7] = {};          // akz_debug_match_pairs_split: stage boundaries of a timed call
     bool mp_split_on = false;
@@ -485,9 +487,11 @@ AKZ_LOCAL uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, con
 AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint64_t>& used, const std::vector<uint64_t>& set_row,
                            uint64_t rows, uint64_t desc_bytes, size_t b_rows, size_t b_xy);
 // akz_match_api.cpp: the descriptor scans of every pair over the uploaded sets; fills the pair records' raw_off, kp0_off, kp1_off, cnt_idx
+// -- and, given `cross`, the opposite direction of every pair to d_rev / d_rcnt with the records of launch::pairs_cross_filter
 AKZ_LOCAL int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
                           double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
-                          std::vector<launch::PairJobHost>& tab);
+                          std::vector<launch::PairJobHost>& tab, akz_match* d_rev = nullptr, uint64_t* d_rcnt = nullptr,
+                          std::vector<launch::CrossJobHost>* cross = nullptr, uint64_t distance_threshold = 10000);
 // akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device (rows of 64 bytes, x, y), enqueued on the
 // context's stream -- scan, merge, ratio test and ordered compaction; pair p's list goes to d_out + spec[p].out_off, its
 // length to d_cnt[p].  d_models: 9 floats per pair ON THE DEVICE; d_found (optional): pairs whose flag is 0 give empty lists.
@@ -507,5 +511,9 @@ AKZ_LOCAL int guided_limits(const char* name, const akz_feature_set* sets, const
 AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
                              int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
                              double lowes_ratio, akz_match* d_out, uint64_t* d_cnt);
+// akz_match_seeded_api.cpp: the seeded pairs call; cross: with cross(A, B) as every pair's raw list (akz_cross_api.cpp)
+AKZ_LOCAL int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                      uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
+                                      float* model, int* found, uint32_t* iterations, uint64_t* trials_run);
 // akz_extract_finish.cpp
 AKZ_LOCAL int device_libm_mode(akz_ctx* c);  // 0: host libm; 1 / 2: the device's FMA / SSE2 forms reproduce it (akz_libm.hpp)

@@ -468,6 +468,20 @@ uint32_t match_guided_block();
 void match_guided(hipStream_t s, int kind, const uint8_t* d_rows, const float* d_kx, const float* d_ky, const GuidedPairHost* d_tab,
                   uint32_t n_tab, uint32_t n_workgroups, const float* d_models, const int32_t* d_found, float radius,
                   uint32_t threshold, MatchRec* d_rec);
+// the cross-check (akz_cross.hip, k_pairs_cross_filter): per pair the forward list at d_fwd + fwd_off (its count at
+// d_fwd_cnt[fwd_cnt_idx]) is rewritten in place, in order, to the records m for which the reverse list at d_rev + rev_off (count
+// at d_rev_cnt[rev_cnt_idx], ascending index_0) holds r with r.index_0 == m.index_1 and r.index_1 == m.index_0; the count follows.
+// fwd_cap / rev_cap: the room of the two lists (a count above it is cut to it).  One workgroup per pair.
+struct CrossJobHost {
+    uint64_t fwd_off, rev_off;
+    uint32_t fwd_cnt_idx, rev_cnt_idx, fwd_cap, rev_cap;
+};
+static_assert(sizeof(CrossJobHost) == 32, "the device reads 32-byte cross records");
+void pairs_cross_filter(hipStream_t s, const CrossJobHost* d_tab, uint32_t n_pairs, akz_match* d_fwd, uint64_t* d_fwd_cnt,
+                        const akz_match* d_rev, const uint64_t* d_rev_cnt);
+// the same for one pair whose record travels with the launch (no table on the device)
+void pair_cross_filter(hipStream_t s, const CrossJobHost& job, akz_match* d_fwd, uint64_t* d_fwd_cnt, const akz_match* d_rev,
+                       const uint64_t* d_rev_cnt);
 }  // namespace launch
 
 // ---- host keypoint logic (akz_keypoints.cpp) ---------------------------------------------

@@ -469,20 +469,36 @@ int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint
 // The scans of the pairs calls, enqueued on the context's stream over the sets that pairs_upload placed: pair p's raw list goes to
 // d_raw + tab[p].raw_off, its count to d_cnt[tab[p].cnt_idx] (zeroed here) -- one multi-set launch per first set, or the pair
 // matcher for rows of 62..64 bytes.  tab: one record per pair, raw_off, kp0_off, kp1_off and cnt_idx filled in.
+// cross (optional, with d_rev and d_rcnt): the opposite direction too -- pair p's descriptor_match(second set, first set) goes to
+// d_rev + (*cross)[p].rev_off (room for the second set's rows; the sum of those over the pairs is the room of d_rev), its count
+// to d_rcnt[tab[p].cnt_idx] (zeroed here); (*cross)[p] is the pair's record for launch::pairs_cross_filter.  From the same
+// multi-set launch on the FP4 matcher, a second scan with the sets exchanged otherwise.  distance_threshold: 10000 for match_features.
 int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
                 double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
-                std::vector<launch::PairJobHost>& tab) {
+                std::vector<launch::PairJobHost>& tab, akz_match* d_rev, uint64_t* d_rcnt, std::vector<launch::CrossJobHost>* cross, uint64_t distance_threshold) {
     hipStream_t st = c->stream;
     tab.assign((size_t)n_pairs, launch::PairJobHost{});
     AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_pairs * 8, st));
-    uint64_t raw_base = 0;
+    if (cross) {
+        cross->assign((size_t)n_pairs, launch::CrossJobHost{});
+        AKZ_HIP_TRY(hipMemsetAsync(d_rcnt, 0, (size_t)n_pairs * 8, st));
+    }
+    uint64_t raw_base = 0, rev_base = 0;
     if (desc_bytes > 61) {  // every byte of a row counts: the pair matcher of akz_descriptor_match
         for (uint64_t p = 0; p < n_pairs; ++p) {
             const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1], na = sets[a].n_descriptors;
             tab[(size_t)p] = launch::PairJobHost{raw_base, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0, (uint32_t)p, 0};
             if (na)
                 AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)a] * 64, na, d_rows + set_row[(size_t)b] * 64, sets[b].n_descriptors,
-                                          10000, lowes_ratio, d_raw + raw_base, d_cnt + p, false));
+                                          distance_threshold, lowes_ratio, d_raw + raw_base, d_cnt + p, false));
+            if (cross) {
+                const uint64_t nb = sets[b].n_descriptors;
+                (*cross)[(size_t)p] = launch::CrossJobHost{raw_base, rev_base, (uint32_t)p, (uint32_t)p, (uint32_t)na, (uint32_t)nb};
+                if (na && nb)
+                    AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)b] * 64, nb, d_rows + set_row[(size_t)a] * 64, na, distance_threshold, lowes_ratio,
+                                              d_rev + rev_base, d_rcnt + p, false));
+                rev_base += nb;
+            }
             raw_base += na;
         }
     } else {  // one multi-set launch per first set over its second sets (split at the matcher's limits)
@@ -515,11 +531,16 @@ int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const 
                     const uint64_t p = g[i];
                     tab[(size_t)p] = launch::PairJobHost{raw_base + (i - i0) * n0, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0,
                                                                    cnt_base + (uint32_t)(i - i0), 0};
+                    if (cross)  // (the launch puts set k's reverse list behind those of the sets before it)
+                        (*cross)[(size_t)p] = launch::CrossJobHost{raw_base + (i - i0) * n0, rev_base + (train - nb), cnt_base + (uint32_t)(i - i0),
+                                                                   cnt_base + (uint32_t)(i - i0), (uint32_t)n0, (uint32_t)nb};
                     ++i;
                 }
                 if (n0)
-                    AKZ_TRY(match_sets_at(c, d_rows + set_row[(size_t)a] * 64, n0, d_rows, first.data(), nrows.data(), first.size(), 10000,
-                                          lowes_ratio, d_raw + raw_base, d_cnt + cnt_base, nullptr, nullptr));
+                    AKZ_TRY(match_sets_at(c, d_rows + set_row[(size_t)a] * 64, n0, d_rows, first.data(), nrows.data(), first.size(), distance_threshold,
+                                          lowes_ratio, d_raw + raw_base, d_cnt + cnt_base, cross && train ? d_rev + rev_base : nullptr,
+                                          cross && train ? d_rcnt + cnt_base : nullptr));  // (no train row: both directions are empty)
+                rev_base += train;
                 raw_base += first.size() * n0;
                 cnt_base += (uint32_t)first.size();
             }

@@ -1,4 +1,5 @@
-// akz_match_features_seeded_pairs (an addition; include/akaze_hip.h): match_features over many pairs with the seeded
+// akz_match_features_seeded_pairs and, with the cross-check in front, akz_match_features_seeded_cross_pairs (additions;
+// include/akaze_hip.h): match_features over many pairs with the seeded
 // RANSAC of akz_ransac_seeded.hpp -- the trial kernel draws its own samples, the stopping rule runs per pair on the device, and
 // the calling thread's random source is never touched.  Stages, all on the context's stream: upload, scans, k_pair_points and the
 // ONE read-back of the match counts as in match_pairs_impl (akz_match_api.cpp: pairs_validate, pairs_place, pairs_upload,
@@ -23,10 +24,12 @@ int seeded_refuse_options(const char* name, const akz_ransac_options* opt);  // 
 }
 using namespace akz;
 
-extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                                               uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                                               float* model, int* found, uint32_t* iterations, uint64_t* trials_run) {
-    const char* name = "match_features_seeded_pairs: ";
+// cross: every pair's raw list is cross(A, B) (akz_match_features_seeded_cross_pairs, akz_cross_api.cpp) -- pairs_scans also
+// writes the opposite direction and launch::pairs_cross_filter rewrites d_raw / d_cnt before anything reads them; clear, the call
+// enqueues what it always did.
+int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                            uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
+                            float* model, int* found, uint32_t* iterations, uint64_t* trials_run) {
     constexpr uint32_t kWindow = 8;  // rounds enqueued between two looks at the pairs still running
     AKZ_TRY(seeded_refuse_options(name, options));
     const akz_ransac_options& opt = *options;
@@ -96,7 +99,24 @@ extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set
     AKZ_TRY(pairs_upload(c, sets, used, set_row, rows, desc_bytes, b_rows, b_xy));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
     std::vector<launch::PairJobHost> tab;
-    AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, set_row, d_rows, d_raw, d_cnt, tab));
+    if (cross) {  // the reverse lists (room: every pair's second set), their counts and the filter's records
+        uint64_t cap_rev = 0;
+        for (uint64_t p = 0; p < n_pairs; ++p) cap_rev += sets[pairs[2 * p + 1]].n_descriptors;
+        const size_t b_rev = up((size_t)std::max<uint64_t>(cap_rev, 1) * sizeof(akz_match)), b_xtab = up((size_t)n_pairs * sizeof(launch::CrossJobHost));
+        AKZ_TRY(ensure(c, c->cx_rev, b_rev + b_cnt + b_xtab));
+        AKZ_TRY(ensure_pinned(c, c->cx_pin_tab, b_xtab));
+        akz_match* d_rev = (akz_match*)c->cx_rev.p;
+        uint64_t* d_rcnt = (uint64_t*)((char*)c->cx_rev.p + b_rev);
+        launch::CrossJobHost* d_xtab = (launch::CrossJobHost*)((char*)c->cx_rev.p + b_rev + b_cnt);
+        std::vector<launch::CrossJobHost> xtab;
+        AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, set_row, d_rows, d_raw, d_cnt, tab, d_rev, d_rcnt, &xtab));
+        std::memcpy(c->cx_pin_tab.p, xtab.data(), (size_t)n_pairs * sizeof(launch::CrossJobHost));
+        AKZ_HIP_TRY(hipMemcpyAsync(d_xtab, c->cx_pin_tab.p, (size_t)n_pairs * sizeof(launch::CrossJobHost), hipMemcpyHostToDevice, st));
+        launch::pairs_cross_filter(st, d_xtab, (uint32_t)n_pairs, d_raw, d_cnt, d_rev, d_rcnt);
+        AKZ_HIP_TRY(hipGetLastError());
+    } else {
+        AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, set_row, d_rows, d_raw, d_cnt, tab));
+    }
     launch::PairJobHost* h_tab = (launch::PairJobHost*)c->mp_pin_tab.p;
     uint64_t* h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
     uint32_t* h_done = (uint32_t*)((char*)c->mp_pin_tab.p + b_tab + b_cnt);  // | need, as on the device
@@ -256,4 +276,11 @@ extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set
         c->mp_split_ms[2] = t_need;
     }
     return AKZ_OK;
+}
+
+extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                                               uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
+                                               float* model, int* found, uint32_t* iterations, uint64_t* trials_run) {
+    return match_seeded_pairs_impl("match_features_seeded_pairs: ", false, c, sets, n_sets, pairs, n_pairs, desc_bytes, options, out, n_out, model,
+                                   found, iterations, trials_run);
 }

@@ -297,7 +297,13 @@ def lib():
                                                C.POINTER(C.c_uint32)], i32),
         "akz_match_features_seeded_pairs": ([vp, vp, u64, vp, u64, u64, C.POINTER(RansacOptions), vp, pu64, fp, C.POINTER(i32),
                                              C.POINTER(C.c_uint32), pu64], i32),
+        "akz_match_features_seeded_cross_pairs": ([vp, vp, u64, vp, u64, u64, C.POINTER(RansacOptions), vp, pu64, fp, C.POINTER(i32),
+                                                   C.POINTER(C.c_uint32), pu64], i32),
+        "akz_descriptor_match_cross_host": ([vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
+        "akz_descriptor_match_cross": ([vp, vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
+        "akz_descriptor_match_cross_device": ([vp, vp, u64, vp, u64, u64, f64, vp, vp], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
+        "akz_debug_match_tile_rows": ([C.POINTER(C.c_uint32)], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
         "akz_write_matches": ([C.c_char_p, vp, u64], i32),
@@ -886,16 +892,19 @@ class Context:
                                                                          *a.refined()))
         return a.lists_models_iterations()
 
-    def match_features_seeded_pairs(self, features, pairs, options=None):
+    def match_features_seeded_pairs(self, features, pairs, options=None, cross_check=False):
         """match_features over many pairs with the seeded RANSAC (akz_match_features_seeded_pairs): the trial kernel draws its
         own samples from (options.seed, options.stream_base + pair, trial) and options.confidence stops a pair's trials on the
         device; the thread's random source is not touched.  Returns one (matches, model or None, accepted fits, trials run) per
         pair, each equal to remove_outliers_seeded on that pair's raw list with stream = stream_base + pair (then the guided
-        scan, if options.guided)."""
+        scan, if options.guided).  cross_check: the raw list is descriptor_match_cross_host(pair, 10000, options.lowes_ratio)
+        -- a match must be the best in both directions -- (akz_match_features_seeded_cross_pairs); the guided scan stays
+        one-directional."""
         a = _PairsArgs(self, features, pairs)
         opt = options if options is not None else RansacOptions()
         tr = np.zeros(max(1, len(a.pr)), np.uint64)
-        _check(lib().akz_match_features_seeded_pairs(*a.head, C.byref(opt), *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
+        fn = lib().akz_match_features_seeded_cross_pairs if cross_check else lib().akz_match_features_seeded_pairs
+        _check(fn(*a.head, C.byref(opt), *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
         return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
 
     def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
@@ -947,6 +956,23 @@ class Context:
             distance_threshold, lowes_ratio, C.c_void_p(out.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(cout.data_ptr()),
             C.c_void_p(ccnt.data_ptr())))
         return out, cnt[:ns], cout[:tot], ccnt[:ns]
+
+    def descriptor_match_cross(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
+        """Cross-checked descriptor_match (akz_descriptor_match_cross): the records of descriptor_match(d0, d1) whose train row,
+        matched the other way round, comes back to the same query row.  Equal to descriptor_match_cross_host."""
+        return _cross_pair(lib().akz_descriptor_match_cross, (self._h,), d0, d1, distance_threshold, lowes_ratio)
+
+    def descriptor_match_cross_device(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
+        """descriptor_match_cross on torch CUDA uint8 tensors of 64-byte descriptor rows (akz_descriptor_match_cross_device);
+        returns (matches tensor view, count) as descriptor_match_device does."""
+        import torch
+        n0, n1 = d0.shape[0], d1.shape[0]
+        out = torch.empty((max(n0, 1), 24), dtype=torch.uint8, device=d0.device)
+        cnt = torch.zeros(1, dtype=torch.int64, device=d0.device)
+        _check(lib().akz_descriptor_match_cross_device(self._h, C.c_void_p(d0.data_ptr()), n0, C.c_void_p(d1.data_ptr()),
+                                                       n1, distance_threshold, lowes_ratio, C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(cnt.data_ptr())))
+        return out, cnt
 
     def descriptor_match_device(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """Same on torch CUDA uint8 tensors of 64-byte descriptor rows; returns (matches tensor view, count)."""
@@ -1831,16 +1857,36 @@ def remove_outliers_seeded(keypoints_0, keypoints_1, matches, options=None, stre
     return out[:n.value].copy(), (f.reshape(3, 3) if found.value else None), it.value, tr.value
 
 
-def match_features_seeded_pairs(features, pairs, options=None, ctx=None):
+def match_features_seeded_pairs(features, pairs, options=None, ctx=None, cross_check=False):
     """Context.match_features_seeded_pairs on ctx (default: the default context)."""
-    return (ctx or default_context()).match_features_seeded_pairs(features, pairs, options)
+    return (ctx or default_context()).match_features_seeded_pairs(features, pairs, options, cross_check=cross_check)
 
 
-def match_features_seeded(keypoints_0, descriptors_0, keypoints_1, descriptors_1, options=None, ctx=None):
+def match_features_seeded(keypoints_0, descriptors_0, keypoints_1, descriptors_1, options=None, ctx=None, cross_check=False):
     """One pair through match_features_seeded_pairs (its stream: options.stream_base) -> (matches, model or None, accepted
     fits, trials run)."""
     return (ctx or default_context()).match_features_seeded_pairs([(keypoints_0, descriptors_0), (keypoints_1, descriptors_1)],
-                                                                  [(0, 1)], options)[0]
+                                                                  [(0, 1)], options, cross_check=cross_check)[0]
+
+
+def _cross_pair(fn, first, d0, d1, distance_threshold, lowes_ratio):
+    d0 = np.ascontiguousarray(d0, np.uint8)
+    d1 = np.ascontiguousarray(d1, np.uint8)
+    nb = d0.shape[1] if d0.ndim == 2 and d0.shape[0] else (d1.shape[1] if d1.ndim == 2 else 61)
+    n0 = d0.shape[0] if d0.ndim == 2 else 0
+    n1 = d1.shape[0] if d1.ndim == 2 else 0
+    out = np.zeros(max(n0, 1), MATCH_DTYPE)
+    n = C.c_uint64()
+    _check(fn(*first, d0.ctypes.data_as(C.c_void_p), n0, d1.ctypes.data_as(C.c_void_p), n1, nb, distance_threshold, lowes_ratio,
+              out.ctypes.data_as(C.c_void_p), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def descriptor_match_cross_host(d0, d1, distance_threshold=10000, lowes_ratio=0.86):
+    """The cross-check on the host (akz_descriptor_match_cross_host; no GPU call): m of descriptor_match(d0, d1) is kept iff
+    descriptor_match(d1, d0) holds the record with index_0 == m.index_1 and index_1 == m.index_0.  The statement that
+    Context.descriptor_match_cross and the cross_check of the seeded calls are held to."""
+    return _cross_pair(lib().akz_descriptor_match_cross_host, (), d0, d1, distance_threshold, lowes_ratio)
 
 
 # ------------------------------------------------------------------------------------------

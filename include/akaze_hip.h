@@ -884,6 +884,43 @@ int akz_match_features_seeded_pairs(akz_ctx* ctx, const akz_feature_set* sets, u
                                     uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
                                     uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */);
 
+/* ---- cross-checked matching: a match is kept only if both directions agree (additions) ------------------------------
+   For descriptor sets A (n0 rows) and B (n1 rows), a distance_threshold and a lowes_ratio:
+     fwd = descriptor_match(A, B, distance_threshold, lowes_ratio)    feature_matching.rs:23-94; index_0 a row of A
+     rev = descriptor_match(B, A, distance_threshold, lowes_ratio)    arguments exchanged; index_0 a row of B
+     cross(A, B) = [ m in fwd, in fwd's order : rev contains r with r.index_0 == m.index_1 and r.index_1 == m.index_0 ]
+   Both directions follow the rules of descriptor_match: the minimum must be below the threshold, the test is
+   (double)min < (double)second * lowes_ratio^2, ties go to the lowest index among equal minima.  A kept record is the forward
+   record unchanged (its distance equals the reverse one: hamming is symmetric).  The result is never longer than fwd: out
+   needs room for n0 records.  A lowes_ratio above 1 makes the ratio test nearly vacuous and leaves plain mutual nearest
+   neighbours; it is accepted wherever descriptor_match accepts it.  cross(A, A) follows from the same statement, and an empty
+   set on either side gives an empty result. */
+/* The host statement: two scans and a lookup, no GPU call, no context.  Refusals (AKZ_ERR_INVALID_ARG, nothing written): those
+   of akz_descriptor_match -- a NULL n_out, desc_bytes outside 1..64, NULL rows or out where there are rows. */
+int akz_descriptor_match_cross_host(const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes,
+                                    uint64_t distance_threshold, double lowes_ratio, akz_match* out, uint64_t* n_out);
+/* The same list from the GPU for host arrays; arguments and refusals are those of akz_descriptor_match.  On the FP4 matcher (the
+   default) and rows of at most 61 bytes both directions come from ONE pass over the distances
+   (akz_descriptor_match_sets_mutual_device); rows of 62..64 bytes and the other matcher kernels scan twice.  The intersection
+   runs on the device (k_pairs_cross_filter): one list comes back. */
+int akz_descriptor_match_cross(akz_ctx* ctx, const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes,
+                               uint64_t distance_threshold, double lowes_ratio, akz_match* out, uint64_t* n_out);
+/* The same on device-resident 64-byte rows, as akz_descriptor_match_device (bytes 61..63 are padding and NOT compared): d_out
+   holds n0 records, compacted in index_0 order, *d_n_out (device uint64) receives the count.  The call enqueues on the context's
+   stream and returns; the scratch for the reverse list comes from the context. */
+int akz_descriptor_match_cross_device(akz_ctx* ctx, const uint8_t* d_d0, uint64_t n0, const uint8_t* d_d1, uint64_t n1,
+                                      uint64_t distance_threshold, double lowes_ratio, akz_match* d_out, uint64_t* d_n_out);
+/* akz_match_features_seeded_pairs with cross(A, B, 10000, options->lowes_ratio) in place of descriptor_match(A, B) as each pair's
+   raw list: the signature, the layout of out, the refusals and the promises are those of that call.  Pair p's result equals
+   akz_remove_outliers_seeded on akz_descriptor_match_cross_host(pair p) with stream = stream_base + p, bit for bit -- the list,
+   the model, found, iterations and trials_run -- so the batch still equals the loop of one-pair calls.
+   The cross-check applies to the list RANSAC sees.  The guided stage, where switched on, stays what it is: a one-directional
+   scan gated by the returned model, which is NOT cross-checked. */
+int akz_match_features_seeded_cross_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
+                                          uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out,
+                                          uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
+                                          uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly

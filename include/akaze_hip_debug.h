@@ -27,6 +27,9 @@ const char* akz_detector_kernel_name(void);
    pair call, `set_chunks` (1..16) per set of a multi-set call; 0 = automatic (the default).  Results are identical for
    every value -- which is what the tests that use this check. */
 int akz_debug_set_match_chunks(akz_ctx* ctx, uint32_t pair_chunks, uint32_t set_chunks);
+/* Test hook: the train rows per LDS tile of the matrix-core matcher (launch::match_mfma_tile_rows()), so that tests can place
+   their set sizes one below, at and one above it.  No GPU call, no context. */
+int akz_debug_match_tile_rows(uint32_t* rows);
 /* Measurement hook: schedule variants of a large batch (results are identical).  key 0: where the early stages
    (level-0 blur, contrast factor) of a batch whose input is complete run: 0 = the copy stream if the context's
    stream-placement probe found it a hardware queue and a pipe of its own (default), 1 = the copy stream regardless, 2 = a
