@@ -450,12 +450,23 @@ int akz_debug_march_bands(int kind, uint32_t w, uint32_t h, uint32_t n, int half
     *n_bands = launch::march_band_rows(kind, w, h, n, half_width, rows, cap);
     return AKZ_OK;
 }
+int akz_debug_detector_set_cells(int half_width, const uint32_t* w, const uint32_t* h, uint32_t n_entries, uint32_t n, int32_t* cells,
+                                 uint32_t cap, int32_t* grids, uint32_t* n_workgroups) {
+    if (!n_workgroups || !w || !h || !grids || (cap && !cells) || n_entries < 1 || n_entries > launch::detector_march_set_max() || n == 0 ||
+        half_width < 1 || half_width > 4)
+        return AKZ_ERR_INVALID_ARG;
+    for (uint32_t e = 0; e < n_entries; ++e)
+        if (w[e] < 4u * (uint32_t)half_width + 8u || h[e] < 4u * (uint32_t)half_width + 8u) return AKZ_ERR_INVALID_ARG;
+    *n_workgroups = launch::detector_set_cells(half_width, w, h, n_entries, n, cells, cap, grids);
+    return AKZ_OK;
+}
 const char* akz_detector_kernel_name(void) { return "detector (k_detector_march + k_detector_tiled)"; }
 int akz_debug_set_schedule(akz_ctx* c, int key, int value) {
-    if (!c || key < 0 || key > 10) return AKZ_ERR_INVALID_ARG;
+    if (!c || key < 0 || key > 11) return AKZ_ERR_INVALID_ARG;
     AKZ_TRY(bind(c));
     c->sched[key] = value;
     if (key == 7 || key == 8) launch::march_min_band_rows(c->sched[7], c->sched[8]);  // (process-wide: measurement)
+    if (key == 11) launch::detector_set_waves(value >= 11 && value <= 14 ? value - 10 : 0);  // (process-wide: the kDetSetWaves sweep)
     if (key == 4) {
         c->big_px_sync = value > 0 ? (uint64_t)value * 1000u : gates::kBigPxSync;
         c->big_px_async = value > 0 ? (uint64_t)value * 1000u : gates::kBigPxAsync;

@@ -203,8 +203,9 @@ struct akz_ctx {
     // schedule variants (akz_debug_set_schedule): [0] where the early stages of a batch run -- 0 the copy stream if the
     // placement probe found it a queue and a pipe of its own (below), 1 the copy stream regardless, 2 a stream of their own
     // (a fifth busy stream), 3 the context's stream (no running ahead); [1] early stages held back until the batch before
-    // has finished its fine-level diffusion (default) or not; [2] no placement probe
-    int sched[11] = {0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // has finished its fine-level diffusion (default) or not; [2] no placement probe; [11] 1 = one column-march detector launch
+    // per level instead of one per set of levels (the others: include/akaze_hip_debug.h)
+    int sched[12] = {0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t big_px = gates::kBigPxAsync;  // the gate of the job being begun (set by extract_begin from the two below; the begin half's helpers read it)
     uint64_t big_px_sync = gates::kBigPxSync, big_px_async = gates::kBigPxAsync;  // (sched[4] sets both: measurement)
     uint64_t lane_px = gates::kLanePx;  // jobs below it go to the lanes, if the context has any (sched[4] sets it too)

@@ -367,15 +367,26 @@ int run_levels(BeginState& b, size_t lo, size_t hi) {
 // saturates the store path on its own; with only the half-resolution octave's detectors on the side stream it is
 // still -5 %: removed).
 // levels whose detector is the one-kernel tiled form are grouped by sigma_size: one launch per group
+// Column-march levels are grouped the same way (sigma_size and the width's parity, which the kernel is compiled for; the kept planes and
+// the extrema test are the job's): one launch per set of up to launch::detector_march_set_max() levels, largest first, when
+// sched[11] asks for it (kDetSetsByDefault: DESIGN.md 4; sched[11] = 1: one launch per level, 2 / 11 .. 14: sets)
+constexpr bool kDetSetsByDefault = true;
 int detectors(BeginState& b, size_t lo, size_t hi, hipStream_t on) {
     akz_ctx* c = b.c;
     const akz_config& cfg = b.r->cfg;
     const uint32_t n = b.n;
     std::map<uint32_t, std::vector<launch::DetLevelDesc>> sets;
+    std::map<std::pair<uint32_t, uint32_t>, std::vector<launch::DetLevelDesc>> march_sets;
+    const bool by_sets = c->sched[11] == 0 ? kDetSetsByDefault : c->sched[11] != 1;
     for (size_t l = lo; l < hi; ++l) {
         if (b.det_done[l]) continue;  // (sched[5]: enqueued behind its level kernel already)
         const LevelPlan& lv = b.r->plan[l];
         const float thr = (float)cfg.detector_threshold, bm = border_margin(lv, cfg);
+        if (by_sets && b.rt.lv[l].det == Det::March) {
+            march_sets[{lv.det_sigma, lv.w & 1u}].push_back(launch::DetLevelDesc{b.P(l, AKZ_LSMOOTH), b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX),
+                                                                                 b.P(l, AKZ_LYY), b.P(l, AKZ_LXY), b.P(l, AKZ_LDET), lv.w, lv.h, (uint32_t)l, bm});
+            continue;
+        }
         if (b.rt.lv[l].det == Det::TiledSet) {
             sets[lv.det_sigma].push_back(launch::DetLevelDesc{b.P(l, AKZ_LSMOOTH), b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX),
                                                              b.P(l, AKZ_LYY), b.P(l, AKZ_LXY), b.P(l, AKZ_LDET), lv.w, lv.h, (uint32_t)l, bm});
@@ -389,6 +400,23 @@ int detectors(BeginState& b, size_t lo, size_t hi, hipStream_t on) {
         }
         StageTimer st(c, AKZ_ST_NMS);
         launch::nms(on, b.P(l, AKZ_LDET), lv.w, lv.h, n, (uint64_t)lv.w * lv.h, (uint32_t)l, thr, bm, b.d_cand, b.cap, b.d_count);
+    }
+    for (auto& kv : march_sets) {
+        std::vector<launch::DetLevelDesc>& v = kv.second;
+        std::stable_sort(v.begin(), v.end(), [](const launch::DetLevelDesc& x, const launch::DetLevelDesc& y) { return (uint64_t)x.w * x.h > (uint64_t)y.w * y.h; });
+        const uint32_t maxn = launch::detector_march_set_max();
+        for (size_t i = 0; i < v.size(); i += maxn) {
+            const uint32_t cnt = (uint32_t)std::min<size_t>(maxn, v.size() - i);
+            StageTimer st(c, AKZ_ST_DETECTOR, on);
+            if (c->profiling) {
+                c->prof.det_launches += 1;
+                uint64_t set_px = 0;
+                for (size_t j = i; j < i + cnt; ++j) set_px += (uint64_t)v[j].w * v[j].h * n;
+                c->prof.det_px += set_px;
+                st.kernel(AKZ_KR_DETECTOR_MARCH, kv.first.first, v[i].w, v[i].h, n, 1, set_px);  // (the largest level's shape, as the tiled sets)
+            }
+            launch::detector_march_set(on, kv.first.first, v.data() + i, cnt, n, (float)cfg.detector_threshold, b.d_cand, b.cap, b.d_count);
+        }
     }
     for (auto& kv : sets) {
         const uint32_t maxn = launch::detector_tiled_set_max();

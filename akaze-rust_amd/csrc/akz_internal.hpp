@@ -248,6 +248,14 @@ bool detector_march_supported(uint32_t sigma, uint32_t w, uint32_t h, float bord
 void detector_march(hipStream_t s, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy,
                     float* lxy, float* ldet_out, uint32_t w, uint32_t h, uint32_t n, uint32_t level, float thr,
                     float border_m, Candidate* d_cand, uint32_t cap, uint32_t* d_count);
+// the same kernel over a set of levels that share sigma_size, the width's parity and the kept planes: one launch whose cells
+// are shared among the levels in proportion to their strip-rows (largest level first)
+uint32_t detector_march_set_max();
+void detector_march_set(hipStream_t s, uint32_t sigma, const DetLevelDesc* levels, uint32_t nlevels, uint32_t n, float thr,
+                        Candidate* d_cand, uint32_t cap, uint32_t* d_count);
+void detector_set_waves(int waves);  // measurement hook (process-wide): 0 = kDetSetWaves
+uint32_t detector_set_cells(int S, const uint32_t* w, const uint32_t* h, uint32_t nlv, uint32_t n, int32_t* cells, uint32_t cap,
+                            int32_t* grids);  // test hook
 // level preparation + the first n_steps <= 4 diffusion steps of a level in one launch (akz_march.hip, k_level_march)
 bool head_fused_supported(uint32_t w, uint32_t h, uint32_t ntaps0, uint32_t ntaps1);
 // (d_zero_word: a 32-bit word the kernel clears -- the job's candidate counter -- or NULL)

@@ -101,6 +101,64 @@ struct MarchNms {
     unsigned* count;
 };
 
+// ---- a detector launch over a SET of levels -------------------------------------------------------------------------
+// Levels of one sigma_size (and width parity, keep / NMS flags) share one launch of k_detector_march: their cells neither
+// start nor end together, so one cell's ring warm-up (4S+3 rows that store nothing) runs under other cells' stores, and
+// only the last level's tail is left.  A single level is a set of one.
+constexpr int kDetSetMax = 4;
+struct DetMarchEntry {
+    const float* ls;
+    float *lx, *ly, *ldet, *lxx, *lyy, *lxy;
+    int w, h;
+    MarchGrid g;
+    unsigned level;          // the level's part of MarchNms
+    int xlo, xhi, ylo, yhi;
+    int first;               // the entry's first cell within every XCD's walk (unused entries: INT_MAX)
+};
+struct DetMarchSet {
+    DetMarchEntry e[kDetSetMax];
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+#define AKZ_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)  // (integer division runs on the vector ALU: back to a scalar register)
+#else
+#define AKZ_UNIFORM(x) (x)
+#endif
+// Workgroup `wg` of `nwg` -> (entry, image, band, strip); false: padding, no work.  The one place the kernel and the
+// host-side check (launch::detector_set_cells) get it from.  Every entry's cell count is rounded up to a multiple of 8 and
+// each XCD (wg & 7) walks a contiguous eighth of EVERY entry, entries in the order given (largest first): a contiguous
+// eighth of the concatenation would give some XCDs full-resolution cells only and others half-resolution cells only.
+// Within an entry: (image, band, strip), strips fastest -- workgroups that run side by side work on the same rows of an
+// image.  The entry is picked by a compare chain on scalars with static indices into the kernel arguments: a computed
+// index would send the whole struct through scratch memory (k_mldb, tab.lv[...]).
+__host__ __device__ __forceinline__ bool det_set_cell(const DetMarchSet& set, int wg, int nwg, DetMarchEntry* E, int* entry, int* img,
+                                                      int* band, int* strip) {
+#if AKZ_MARCH_XCD
+    const int xcd = wg & 7, j = wg >> 3;
+    (void)nwg;
+#else
+    const int xcd = wg / (nwg >> 3), j = wg - xcd * (nwg >> 3);
+#endif
+    DetMarchEntry X = set.e[0];
+    int e = 0, jl = j;  // jl: the cell within the XCD's eighth of the entry
+    const int f1 = set.e[1].first, f2 = set.e[2].first, f3 = set.e[3].first;
+    if (j >= f1) { X = set.e[1]; e = 1; jl = j - f1; }
+    if (j >= f2) { X = set.e[2]; e = 2; jl = j - f2; }
+    if (j >= f3) { X = set.e[3]; e = 3; jl = j - f3; }
+    static_assert(kDetSetMax == 4, "compare chain");
+    const int cell = AKZ_UNIFORM(xcd * ((X.g.total + 7) >> 3) + jl);
+    if (cell >= X.g.total) return false;
+    const int per = X.g.nbands * X.g.nstrips;
+    const int i = AKZ_UNIFORM(cell / per);
+    const int rem = cell - i * per;
+    const int b = AKZ_UNIFORM(rem / X.g.nstrips);
+    *E = X;
+    *entry = e;
+    *img = i;
+    *band = b;
+    *strip = rem - b * X.g.nstrips;
+    return true;
+}
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ f2 tap_main(f2 a, f2 b, f2 c, float kn, float kwn) {
     const f2 z = {0.0f, 0.0f};
@@ -257,9 +315,8 @@ __device__ __forceinline__ void store_filled(const __amdgpu_buffer_rsrc_t (&plan
 
 template <int S, bool NMS, bool KEEP, bool ODDW>
 __global__ void __launch_bounds__(MT, 3)
-k_detector_march(const float* __restrict__ ls, float* __restrict__ lx_out, float* __restrict__ ly_out,
-                 float* __restrict__ lxx_out, float* __restrict__ lyy_out, float* __restrict__ lxy_out,
-                 float* __restrict__ ldet_out, int w, int h, MarchGrid g, float kn, float kwn, float quat, MarchNms nms) {
+k_detector_march(DetMarchSet set, float kn, float kwn, float quat, float thr, Candidate* __restrict__ cand, unsigned cap,
+                 unsigned* __restrict__ count) {
     constexpr int P = 2 * S + 1, NOUT = KEEP ? 4 : 1;
     static_assert(2 * S + 2 <= HALO, "strip halo");
     // input rows in flight ahead of the arithmetic; they sit in a ring of R slots, R a divisor of the unroll count P
@@ -273,15 +330,21 @@ k_detector_march(const float* __restrict__ ls, float* __restrict__ lx_out, float
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     Candidate* const cbuf = s_cands[NMS ? wv : 0];
     unsigned cnum = 0;
-    // (image, band, strip), strips fastest: workgroups that run side by side work on the same rows of the image
-    // (integer division runs on the vector ALU: readfirstlane moves the uniform results back to scalar registers, so
-    // that row addresses, loop bounds and branches derived from them stay scalar)
-    const int per = g.nbands * g.nstrips;
-    const int cell = march_cell();
-    if (cell >= g.total) return;
-    const int img = __builtin_amdgcn_readfirstlane(cell / per);
-    const int rem = cell - img * per;
-    const int band = __builtin_amdgcn_readfirstlane(rem / g.nstrips), strip = rem - band * g.nstrips;
+    // workgroup -> (entry, image, band, strip) of the set: det_set_cell.  Everything taken from the entry is uniform and
+    // stays in scalar registers, as the kernel arguments of a one-level launch did.
+    DetMarchEntry E;
+    int entry, img, band, strip;
+    if (!det_set_cell(set, (int)blockIdx.x, (int)gridDim.x, &E, &entry, &img, &band, &strip)) return;
+    const float* __restrict__ const ls = E.ls;
+    float* __restrict__ const lx_out = E.lx;
+    float* __restrict__ const ly_out = E.ly;
+    float* __restrict__ const lxx_out = E.lxx;
+    float* __restrict__ const lyy_out = E.lyy;
+    float* __restrict__ const lxy_out = E.lxy;
+    float* __restrict__ const ldet_out = E.ldet;
+    const int w = E.w, h = E.h;
+    const MarchGrid g = E.g;
+    const MarchNms nms{E.level, thr, E.xlo, E.xhi, E.ylo, E.yhi, cand, cap, count};
     int cs, ce;  // interior rows of this band
     uniform_band_rows(g, band, S, h, &cs, &ce);
     if (cs >= ce) return;
@@ -1002,7 +1065,7 @@ using launch::g_det_min_rows;
 using launch::g_lvl_min_rows;
 using launch::g_head_min_rows;
 
-inline MarchGrid plan_level_march(uint32_t w, uint32_t h, uint32_t n, dim3* grid, int fill_wg = 3, int min_band_rows = 64) {
+inline int march_cus() {
     static int cus = 0;
     if (!cus) {
         int dev = 0;
@@ -1010,6 +1073,10 @@ inline MarchGrid plan_level_march(uint32_t w, uint32_t h, uint32_t n, dim3* grid
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
         if (cus <= 0) cus = 256;
     }
+    return cus;
+}
+inline MarchGrid plan_level_march(uint32_t w, uint32_t h, uint32_t n, dim3* grid, int fill_wg = 3, int min_band_rows = 64) {
+    const int cus = march_cus();
     const int fill = fill_wg, min_rows = min_band_rows;  // (level kernels: 3 / 64, swept in round 2: flat within +-1.5 % around these)
     MarchGrid g;
     g.nstrips = (int)((w + USE - 1) / USE);
@@ -1040,13 +1107,7 @@ inline MarchGrid plan_level_march(uint32_t w, uint32_t h, uint32_t n, dim3* grid
 }
 
 inline MarchGrid plan_march(uint32_t w, uint32_t h, uint32_t n, int S, dim3* grid, int fill_wg = 3, int min_band_rows = 64) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
+    const int cus = march_cus();
     // Bands: each one re-warms the rings (4S+3 extra rows), so they are as tall as the machine allows — enough
     // workgroups for `fill` resident workgroups per CU, never shorter than min_rows interior rows.
     const int fill = fill_wg, min_rows = min_band_rows;
@@ -1091,64 +1152,148 @@ bool detector_march_supported(uint32_t sigma, uint32_t w, uint32_t h, float bord
 }
 
 
-template <int S, bool NMS, bool KEEP>
-static void launch_detector_march(hipStream_t s, const float* lsmooth, float* lx, float* ly, float* lxx, float* lyy, float* lxy,
-                                  float* ldet_out, uint32_t w, uint32_t h, uint32_t n, float kn, float kwn, float quat,
-                                  const MarchNms& na) {
-    dim3 gr;
 #ifndef AKZ_DET_FILL
 #define AKZ_DET_FILL 3
 #endif
-    // (bands of at least 40 interior rows: only a small job is cut that fine -- a lone 4K frame into 53 bands x 8 strips instead
-    // of 33 x 8, one workgroup per compute unit and each marching 80 rows one after the other: 100 -> 70 us per launch; with 64
-    // rows, the rule until round 6, a lone 4K call took 1.62 ms, with 40 or 32 1.55, with 24 or 16 1.60.  Batches are cut by the
-    // fill target long before.)
+// (bands of at least 40 interior rows: only a small job is cut that fine -- a lone 4K frame into 53 bands x 8 strips instead
+// of 33 x 8, one workgroup per compute unit and each marching 80 rows one after the other: 100 -> 70 us per launch; with 64
+// rows, the rule until round 6, a lone 4K call took 1.62 ms, with 40 or 32 1.55, with 24 or 16 1.60.  Batches are cut by the
+// fill target long before.)
 #ifndef AKZ_DET_MINROWS
 #define AKZ_DET_MINROWS 40
 #endif
-    // (... and 24 where the job is four strip columns or fewer -- a lone 1080p frame, a batch-path job since the end of round 6:
-    // 0.613 -> 0.596 ms per call, 0.441 -> 0.416 per streamed frame; from five columns on 40 and 32 measure the same, 24 worse)
-    const int few_cols_rows = (uint64_t)n * ((w + USE - 1) / USE) <= 4 ? 24 : AKZ_DET_MINROWS;
-    const MarchGrid mg = plan_march(w, h, n, S, &gr, AKZ_DET_FILL, g_det_min_rows > 0 ? g_det_min_rows : few_cols_rows);
-    if (w & 1u)
-        hipLaunchKernelGGL((k_detector_march<S, NMS, KEEP, true>), gr, dim3(MT), 0, s, lsmooth, lx, ly, lxx, lyy, lxy, ldet_out,
-                           (int)w, (int)h, mg, kn, kwn, quat, na);
-    else
-        hipLaunchKernelGGL((k_detector_march<S, NMS, KEEP, false>), gr, dim3(MT), 0, s, lsmooth, lx, ly, lxx, lyy, lxy, ldet_out,
-                           (int)w, (int)h, mg, kn, kwn, quat, na);
+// (... and 24 where the job is four strip columns or fewer -- a lone 1080p frame, a batch-path job since the end of round 6:
+// 0.613 -> 0.596 ms per call, 0.441 -> 0.416 per streamed frame; from five columns on 40 and 32 measure the same, 24 worse)
+static int det_min_band_rows(uint32_t w, uint32_t n) {
+    if (g_det_min_rows > 0) return g_det_min_rows;
+    return (uint64_t)n * ((w + USE - 1) / USE) <= 4 ? 24 : AKZ_DET_MINROWS;
 }
-#define AKZ_MARCH(S)                                                                                              \
-    case S: {                                                                                                     \
-        if (d_cand && keep)                                                                                       \
-            launch_detector_march<S, true, true>(s, lsmooth, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n, kn, kwn, quat, na);   \
-        else if (d_cand)                                                                                          \
-            launch_detector_march<S, true, false>(s, lsmooth, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n, kn, kwn, quat, na);  \
-        else if (keep)                                                                                            \
-            launch_detector_march<S, false, true>(s, lsmooth, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n, kn, kwn, quat, na);  \
-        else                                                                                                      \
-            launch_detector_march<S, false, false>(s, lsmooth, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n, kn, kwn, quat, na); \
+// A launch over a set of levels is cut into about kDetSetWaves x AKZ_DET_FILL x CUs cells (a planning constant like
+// AKZ_DET_FILL, chosen by measurement among 1 .. 4: profiles/r17_detector_sets.txt; akz_debug_set_schedule key 11,
+// values 11 .. 14, overrides it for that sweep).
+constexpr int kDetSetWaves = 1;
+static int g_det_set_waves = 0;
+void detector_set_waves(int waves) { g_det_set_waves = waves >= 1 && waves <= 4 ? waves : 0; }
+
+// plan_march for a set: the set's cells are shared among its levels in proportion to their strip-rows, i.e. level e gets
+// target x rows_e / sum(strip-rows) bands -- never shorter than det_min_band_rows, never more than its rows allow.  A set of
+// one level is planned by plan_march itself, exactly as a one-level launch always was.
+static void plan_march_set(const DetLevelDesc* lv, uint32_t nlv, uint32_t n, int S, MarchGrid* grids) {
+    if (nlv == 1) {
+        dim3 gr;
+        grids[0] = plan_march(lv[0].w, lv[0].h, n, S, &gr, AKZ_DET_FILL, det_min_band_rows(lv[0].w, n));
+        return;
+    }
+    uint64_t strip_rows = 0;
+    for (uint32_t e = 0; e < nlv; ++e) strip_rows += (uint64_t)n * ((lv[e].w + USE - 1) / USE) * (lv[e].h - 2 * (uint32_t)S);
+    const uint64_t target = (uint64_t)march_cus() * AKZ_DET_FILL * (uint64_t)(g_det_set_waves ? g_det_set_waves : kDetSetWaves);
+    for (uint32_t e = 0; e < nlv; ++e) {
+        MarchGrid g;
+        g.nstrips = (int)((lv[e].w + USE - 1) / USE);
+        const long rows = (long)lv[e].h - 2 * S;
+        const long want = (long)((target * (uint64_t)rows + strip_rows - 1) / strip_rows);
+        const long nb = std::max<long>(1, std::min<long>(want, std::max<long>(1, rows / det_min_band_rows(lv[e].w, n))));
+        g.band_rows = (int)((rows + nb - 1) / nb);
+        g.edge_rows = g.band_rows;
+        g.nbands = (int)((rows + g.band_rows - 1) / g.band_rows);
+        g.total = (int)((long)n * g.nstrips * g.nbands);
+        grids[e] = g;
+    }
+}
+// the kernel argument of a set (planes, geometry, admissible candidate range and first cell per entry); returns the grid size
+static unsigned make_det_set(const DetLevelDesc* lv, uint32_t nlv, uint32_t n, int S, bool nms, DetMarchSet* set) {
+    MarchGrid grids[kDetSetMax];
+    plan_march_set(lv, nlv, n, S, grids);
+    int first = 0;
+    for (uint32_t e = 0; e < (uint32_t)kDetSetMax; ++e) {
+        DetMarchEntry& E = set->e[e];
+        if (e >= nlv) {
+            E = DetMarchEntry{};
+            E.first = 0x7fffffff;
+            continue;
+        }
+        E = DetMarchEntry{lv[e].lsmooth, lv[e].lx, lv[e].ly, lv[e].ldet, lv[e].lxx, lv[e].lyy, lv[e].lxy, (int)lv[e].w, (int)lv[e].h,
+                          grids[e], lv[e].level, 0, -1, 0, -1, first};
+        if (nms) {
+            admissible_range(lv[e].w, lv[e].border_m, &E.xlo, &E.xhi);
+            admissible_range(lv[e].h, lv[e].border_m, &E.ylo, &E.yhi);
+        }
+        first += (grids[e].total + 7) / 8;
+    }
+    return (unsigned)first * 8u;
+}
+
+template <int S, bool NMS, bool KEEP>
+static void launch_detector_march(hipStream_t s, const DetMarchSet& set, unsigned nwg, bool oddw, float kn, float kwn, float quat, float thr,
+                                  Candidate* d_cand, uint32_t cap, uint32_t* d_count) {
+    if (oddw)
+        hipLaunchKernelGGL((k_detector_march<S, NMS, KEEP, true>), dim3(nwg), dim3(MT), 0, s, set, kn, kwn, quat, thr, d_cand, cap, d_count);
+    else
+        hipLaunchKernelGGL((k_detector_march<S, NMS, KEEP, false>), dim3(nwg), dim3(MT), 0, s, set, kn, kwn, quat, thr, d_cand, cap, d_count);
+}
+#define AKZ_MARCH(S)                                                                                               \
+    case S: {                                                                                                      \
+        const unsigned nwg = make_det_set(levels, nlevels, n, S, d_cand != nullptr, &set);                         \
+        if (d_cand && keep) launch_detector_march<S, true, true>(s, set, nwg, oddw, kn, kwn, quat, thr, d_cand, cap, d_count);    \
+        else if (d_cand) launch_detector_march<S, true, false>(s, set, nwg, oddw, kn, kwn, quat, thr, d_cand, cap, d_count);      \
+        else if (keep) launch_detector_march<S, false, true>(s, set, nwg, oddw, kn, kwn, quat, thr, d_cand, cap, d_count);        \
+        else launch_detector_march<S, false, false>(s, set, nwg, oddw, kn, kwn, quat, thr, d_cand, cap, d_count);                 \
     } break;
 
-// One level's detector response (+ extrema candidates when d_cand is given) in one launch of k_detector_march.
-// lxx / lyy / lxy may be null together (the planes are then not written).
-void detector_march(hipStream_t s, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy,
-                    float* lxy, float* ldet_out, uint32_t w, uint32_t h, uint32_t n, uint32_t level, float thr,
-                    float border_m, Candidate* d_cand, uint32_t cap, uint32_t* d_count) {
+// The detector response (+ extrema candidates when d_cand is given) of up to detector_march_set_max() levels of one
+// sigma_size in ONE launch of k_detector_march.  The levels share the width's parity and whether lxx / lyy / lxy are
+// given (null together: the planes are then not written); the caller orders them largest first.
+uint32_t detector_march_set_max() { return (uint32_t)kDetSetMax; }
+void detector_march_set(hipStream_t s, uint32_t sigma, const DetLevelDesc* levels, uint32_t nlevels, uint32_t n, float thr,
+                        Candidate* d_cand, uint32_t cap, uint32_t* d_count) {
+    if (nlevels == 0 || nlevels > (uint32_t)kDetSetMax) return;
     const Taps m = taps_scharr_main(sigma);
     const float kn = m.wgt[0], kwn = m.wgt[1];
     const float quat = (float)(sigma * sigma * sigma * sigma);
-    const bool keep = lxx && lyy && lxy;
-    MarchNms na{level, thr, 0, -1, 0, -1, d_cand, cap, d_count};
-    if (d_cand) {
-        admissible_range(w, border_m, &na.xlo, &na.xhi);
-        admissible_range(h, border_m, &na.ylo, &na.yhi);
-    }
+    const bool keep = levels[0].lxx && levels[0].lyy && levels[0].lxy;
+    const bool oddw = (levels[0].w & 1u) != 0;
+    DetMarchSet set;
     switch (sigma) {
         AKZ_MARCH(1) AKZ_MARCH(2) AKZ_MARCH(3) AKZ_MARCH(4)
         default: break;
     }
 }
 #undef AKZ_MARCH
+// One level: a set of one.
+void detector_march(hipStream_t s, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy,
+                    float* lxy, float* ldet_out, uint32_t w, uint32_t h, uint32_t n, uint32_t level, float thr,
+                    float border_m, Candidate* d_cand, uint32_t cap, uint32_t* d_count) {
+    const DetLevelDesc one{lsmooth, lx, ly, lxx, lyy, lxy, ldet_out, w, h, level, border_m};
+    detector_march_set(s, sigma, &one, 1, n, thr, d_cand, cap, d_count);
+}
+// Test hook (CPU): the cells of a planned set of nlv levels (w[e] x h[e], n images each, kernel half width S) as the kernel
+// decodes them -- cells[4 i ..] = (entry, image, band, strip) of workgroup i, entry -1 for padding; grids[3 e ..] =
+// (strips, bands, band rows) of entry e.  Returns the grid size; writes up to cap workgroups.
+uint32_t detector_set_cells(int S, const uint32_t* w, const uint32_t* h, uint32_t nlv, uint32_t n, int32_t* cells, uint32_t cap,
+                            int32_t* grids) {
+    DetLevelDesc lv[kDetSetMax] = {};
+    for (uint32_t e = 0; e < nlv; ++e) {
+        lv[e].w = w[e];
+        lv[e].h = h[e];
+    }
+    DetMarchSet set;
+    const unsigned nwg = make_det_set(lv, nlv, n, S, false, &set);
+    for (uint32_t e = 0; e < nlv; ++e) {
+        grids[3 * e] = set.e[e].g.nstrips;
+        grids[3 * e + 1] = set.e[e].g.nbands;
+        grids[3 * e + 2] = set.e[e].g.band_rows;
+    }
+    for (unsigned i = 0; i < nwg && i < cap; ++i) {
+        DetMarchEntry E;
+        int entry = -1, img = -1, band = -1, strip = -1;
+        if (!det_set_cell(set, (int)i, (int)nwg, &E, &entry, &img, &band, &strip)) entry = img = band = strip = -1;
+        cells[4 * i] = entry;
+        cells[4 * i + 1] = img;
+        cells[4 * i + 2] = band;
+        cells[4 * i + 3] = strip;
+    }
+    return nwg;
+}
 
 // 5-tap gaussian_blur as a march (u8 input: rows of even width are 2-byte aligned, which the 16-bit loads need)
 bool blur5_march_supported(uint32_t w, uint32_t h, uint32_t ntaps) {

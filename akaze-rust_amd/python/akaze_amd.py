@@ -241,6 +241,7 @@ def lib():
         "akz_debug_set_select": ([vp, i32], i32),
         "akz_debug_select_info": ([vp, C.POINTER(C.c_int)], i32),
         "akz_debug_set_schedule": ([vp, i32, i32], i32),
+        "akz_debug_detector_set_cells": ([i32, pu32, pu32, u32, u32, C.POINTER(i32), u32, C.POINTER(i32), pu32], i32),
         "akz_debug_stream_placement": ([vp, C.POINTER(i32)], i32),
         "akz_detector_kernel_name": ([], C.c_char_p),
         "akz_remove_outliers": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64], i32),

@@ -20,6 +20,13 @@ int akz_ctx_graph_probe(akz_ctx* ctx, const uint8_t* d_imgs, uint32_t w, uint32_
    to rows, the number of bands to *n_bands.  Used by the CPU tests to check that the bands tile the rows exactly. */
 int akz_debug_march_bands(int kind, uint32_t w, uint32_t h, uint32_t n, int half_width, int32_t* rows, uint32_t cap,
                           uint32_t* n_bands);
+/* Diagnostics (host only, no GPU work): one k_detector_march launch over a SET of n_entries <= 4 levels (w[e] x h[e], n
+   images each, largest first) as the planner cuts it and as the kernel's prologue decodes it.  cells[4 i ..] = (entry, image,
+   band, strip) of workgroup i, all -1 for a padding workgroup (every entry's cell count is rounded up to a multiple of 8;
+   XCD i & 7 walks a contiguous eighth of every entry); up to `cap` workgroups are written.  grids[3 e ..] = (strips, bands,
+   interior rows per band) of entry e; *n_workgroups = the grid size.  Used by the CPU tests. */
+int akz_debug_detector_set_cells(int half_width, const uint32_t* w, const uint32_t* h, uint32_t n_entries, uint32_t n, int32_t* cells,
+                                 uint32_t cap, int32_t* grids, uint32_t* n_workgroups);
 /* names of the default FED kernel and of the detector kernel that large launches take (for bench / profiles) */
 const char* akz_fed_kernel_name(void);
 const char* akz_detector_kernel_name(void);
@@ -49,7 +56,11 @@ int akz_debug_match_tile_rows(uint32_t* rows);
    in order behind its detectors, when its chain ended there);
    key 10: 1 = level 0 of a tiled-family job as separate launches -- blur, clearing of the contrast scratch, blur, maximum,
    histogram, percentile, and level 1's preparation as a k_prep launch (default 0: k_head + k_contrast_hist_final, and
-   level 1's Lflow from k_head's Scharr pair). */
+   level 1's Lflow from k_head's Scharr pair);
+   key 11: how the column-march detectors of a range of levels are launched: 1 = one launch per level; 2 = one launch per
+   set of up to four levels that share sigma_size, the width's parity and the kept planes (largest first); 0 = the default
+   (which of the two it is, and why); 11 .. 14 = sets, cut into 1 .. 4 x 3 x CUs cells instead of kDetSetWaves x
+   (process-wide: the sweep behind that constant). */
 int akz_debug_set_schedule(akz_ctx* ctx, int key, int value);
 /* What the stream-placement probe of the context's first large batch found: info[0] = it has run, info[1] = early stages on
    the context's stream (0) or the copy stream (2), info[2] = streams it re-created because they shared a hardware queue
