@@ -139,6 +139,9 @@ struct akz_ctx {
     DevBuf gd_pin_tab, gd_pin_cnt, gd_pin_out;
     // the cross-check (akz_cross_api.cpp): reverse lists | their counts | cross records of a call; pinned: the records
     DevBuf cx_rev, cx_pin_tab;
+    // k-nearest-neighbour matching (akz_knn_api.cpp): the partial lists of a scan; rows | records | counts of a host-array call
+    DevBuf kn_part, kn_io;
+    uint32_t dbg_knn_chunks = 0;             // akz_debug_set_knn_chunks (0: automatic)
     hipEvent_t mp_smp_ev[2] = {nullptr, nullptr};
     hipEvent_t mp_split_ev[7] = {};          // akz_debug_match_pairs_split: stage boundaries of a timed call
     bool mp_split_on = false;

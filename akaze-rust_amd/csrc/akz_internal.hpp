@@ -490,6 +490,14 @@ void pairs_cross_filter(hipStream_t s, const CrossJobHost* d_tab, uint32_t n_pai
 // the same for one pair whose record travels with the launch (no table on the device)
 void pair_cross_filter(hipStream_t s, const CrossJobHost& job, akz_match* d_fwd, uint64_t* d_fwd_cnt, const akz_match* d_rev,
                        const uint64_t* d_rev_cnt);
+// k-nearest-neighbour matching (akz_knn.hip): q4 / t4 are the FP4 images of unpack_pair(fp4); `chunks` from knn_chunks (forced: the
+// test hook, 0 = automatic; never fewer than the row field of a key allows); d_part: knn_part_bytes bytes of partial lists.
+// Writes k records per query and its count (all padding for n1 == 0); false: arguments or a retuned tile the kernel was not built for.
+uint32_t knn_list_len(uint32_t k);  // k rounded up to the list length the kernel is built for (1, 2, 4, 8)
+uint32_t knn_chunks(uint32_t n0, uint32_t n1, uint32_t forced = 0);
+size_t knn_part_bytes(uint32_t n0, uint32_t chunks, uint32_t k);
+bool knn(hipStream_t s, const uint8_t* q4, uint32_t n0, const uint8_t* t4, uint32_t n1, uint32_t threshold, uint32_t chunks, uint32_t k,
+         uint32_t* d_part, akz_match* d_out, uint32_t* d_counts);
 }  // namespace launch
 
 // ---- host keypoint logic (akz_keypoints.cpp) ---------------------------------------------

@@ -303,6 +303,10 @@ def lib():
         "akz_descriptor_match_cross_host": ([vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross": ([vp, vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross_device": ([vp, vp, u64, vp, u64, u64, f64, vp, vp], i32),
+        "akz_descriptor_match_knn_host": ([vp, u64, vp, u64, u64, u64, u64, vp, vp], i32),
+        "akz_descriptor_match_knn": ([vp, vp, u64, vp, u64, u64, u64, u64, vp, vp], i32),
+        "akz_descriptor_match_knn_device": ([vp, vp, u64, vp, u64, u64, u64, vp, vp], i32),
+        "akz_debug_set_knn_chunks": ([vp, u32], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_debug_match_tile_rows": ([C.POINTER(C.c_uint32)], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
@@ -974,6 +978,30 @@ class Context:
                                                        n1, distance_threshold, lowes_ratio, C.c_void_p(out.data_ptr()),
                                                        C.c_void_p(cnt.data_ptr())))
         return out, cnt
+
+    def descriptor_match_knn(self, d0, d1, k, distance_threshold=10000):
+        """k-nearest-neighbour matching on the GPU (akz_descriptor_match_knn): for every row of d0 its k nearest rows of d1 below
+        the threshold, ordered by (distance, index) -> (records of shape (n0, k) in MATCH_DTYPE, counts of shape (n0,) uint32).
+        Slots beyond a row's count hold index_1 = 2^64 - 1 and distance = inf.  Equal to descriptor_match_knn_host; rows of at
+        most 61 bytes."""
+        return _knn_pair(lib().akz_descriptor_match_knn, (self._h,), d0, d1, k, distance_threshold)
+
+    def descriptor_match_knn_device(self, d0, d1, k, distance_threshold=10000):
+        """descriptor_match_knn on torch CUDA uint8 tensors of 64-byte descriptor rows (akz_descriptor_match_knn_device; bytes
+        61..63 are not compared) -> (records: uint8 tensor (n0, k, 24), one akz_match per slot; counts: int32 tensor (n0,) holding
+        the uint32 counts), both on the device, enqueued on the context's stream."""
+        import torch
+        n0, n1 = d0.shape[0], d1.shape[0]
+        out = torch.empty((n0, int(k), 24), dtype=torch.uint8, device=d0.device)
+        cnt = torch.empty((n0,), dtype=torch.int32, device=d0.device)
+        _check(lib().akz_descriptor_match_knn_device(self._h, C.c_void_p(d0.data_ptr()) if n0 else None, n0,
+                                                     C.c_void_p(d1.data_ptr()) if n1 else None, n1, int(k), distance_threshold,
+                                                     C.c_void_p(out.data_ptr()), C.c_void_p(cnt.data_ptr())))
+        return out, cnt
+
+    def set_knn_chunks(self, n=0):
+        """akz_debug_set_knn_chunks (include/akaze_hip_debug.h): force the train chunks of the k-NN scan; 0 = automatic."""
+        _check(lib().akz_debug_set_knn_chunks(self._h, int(n)))
 
     def descriptor_match_device(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """Same on torch CUDA uint8 tensors of 64-byte descriptor rows; returns (matches tensor view, count)."""
@@ -1881,6 +1909,30 @@ def _cross_pair(fn, first, d0, d1, distance_threshold, lowes_ratio):
     _check(fn(*first, d0.ctypes.data_as(C.c_void_p), n0, d1.ctypes.data_as(C.c_void_p), n1, nb, distance_threshold, lowes_ratio,
               out.ctypes.data_as(C.c_void_p), C.byref(n)))
     return out[:n.value].copy()
+
+
+def _knn_pair(fn, first, d0, d1, k, distance_threshold):
+    d0 = np.ascontiguousarray(d0, np.uint8)
+    d1 = np.ascontiguousarray(d1, np.uint8)
+    nb = d0.shape[1] if d0.ndim == 2 and d0.shape[0] else (d1.shape[1] if d1.ndim == 2 else 61)
+    n0 = d0.shape[0] if d0.ndim == 2 else 0
+    n1 = d1.shape[0] if d1.ndim == 2 else 0
+    k = int(k)
+    out = np.zeros((n0, max(k, 0)), MATCH_DTYPE)
+    counts = np.zeros(n0, np.uint32)
+    pad_out = out if out.size else np.zeros(1, MATCH_DTYPE)        # (never written: there is no row to write for)
+    pad_cnt = counts if counts.size else np.zeros(1, np.uint32)
+    _check(fn(*first, d0.ctypes.data_as(C.c_void_p) if n0 else None, n0, d1.ctypes.data_as(C.c_void_p) if n1 else None, n1, nb, k,
+              distance_threshold, pad_out.ctypes.data_as(C.c_void_p), pad_cnt.ctypes.data_as(C.c_void_p)))
+    return out, counts
+
+
+def descriptor_match_knn_host(d0, d1, k, distance_threshold=10000):
+    """k-nearest-neighbour matching on the host (akz_descriptor_match_knn_host; no GPU call): for every row of d0 the rows of d1
+    with hamming distance < distance_threshold, ordered by (distance, index), the first k of them -> (records (n0, k) in
+    MATCH_DTYPE, counts (n0,) uint32); unused slots hold index_1 = 2^64 - 1 and distance = inf.  The statement that
+    Context.descriptor_match_knn and descriptor_match_knn_device are held to."""
+    return _knn_pair(lib().akz_descriptor_match_knn_host, (), d0, d1, k, distance_threshold)
 
 
 def descriptor_match_cross_host(d0, d1, distance_threshold=10000, lowes_ratio=0.86):

@@ -921,6 +921,37 @@ int akz_match_features_seeded_cross_pairs(akz_ctx* ctx, const akz_feature_set* s
                                           uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
                                           uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */);
 
+/* ---- k-nearest-neighbour matching: the k best train rows of every query, with their distances (additions) -----------
+   For descriptor sets A (n0 rows) and B (n1 rows), 1 <= k <= AKZ_KNN_MAX_K and a distance_threshold, knn(A, B, k, threshold) is,
+   for every row i of A:
+     * take all rows j of B with d(i, j) = hamming(A_i, B_j) < distance_threshold (strict, the threshold of descriptor_match; any
+       threshold above 8 * desc_bytes therefore means none);
+     * order them by (d, j) ascending -- among equal distances the lowest train index first, descriptor_match's tie rule
+       extended to k -- and keep the first k;
+     * counts[i] = the number kept, 0 .. min(k, n1);
+     * out[i * k + r], r < counts[i]  = {index_0 = i, index_1 = j_r, distance = (double)d_r};
+     * out[i * k + r], r >= counts[i] = {index_0 = i, index_1 = UINT64_MAX, distance = +infinity}: every slot is defined, whole
+       buffers can be compared.
+   No ratio test is applied: descriptor_match(A, B, thr, ratio) keeps query i iff, with min = d_0 (thr if counts[i] < 1) and
+   second = d_1 (thr if counts[i] < 2) of knn(A, B, 2, thr), (double)min < (double)second * ratio^2 and min < thr -- and then
+   names j_0.  out holds n0 * k records, counts n0 values.  n1 == 0: every count is 0 and every slot padding; n0 == 0: nothing
+   is written.  Refusals (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written): k == 0 or k > AKZ_KNN_MAX_K, desc_bytes
+   outside 1..64, a NULL out or counts, NULL rows where there are rows, n0 or n1 above 0x7fffffff. */
+#define AKZ_KNN_MAX_K 8
+/* The host statement: a popcount scan with a sorted insertion, no GPU call, no context.  Every one of the desc_bytes bytes counts. */
+int akz_descriptor_match_knn_host(const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes, uint64_t k,
+                                  uint64_t distance_threshold, akz_match* out, uint32_t* counts);
+/* The same buffers from the GPU for host arrays, complete on return: the distances come from the FP4 matrix instruction
+   (k_knn_fp4), exact integers, so the result equals the statement bit for bit.  desc_bytes 1..61; rows of 62..64 bytes return
+   AKZ_ERR_UNSUPPORTED with nothing written (the FP4 image carries 488 columns, and there is no popcount form of this call). */
+int akz_descriptor_match_knn(akz_ctx* ctx, const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes, uint64_t k,
+                             uint64_t distance_threshold, akz_match* out, uint32_t* counts);
+/* The same on device-resident 64-byte rows, as akz_descriptor_match_device (bytes 61..63 are padding and NOT compared): d_out
+   receives n0 * k records, d_counts n0 values, both on the device.  The call enqueues on the context's stream and returns
+   without synchronising; the scratch for the partial lists comes from the context. */
+int akz_descriptor_match_knn_device(akz_ctx* ctx, const uint8_t* d_d0, uint64_t n0, const uint8_t* d_d1, uint64_t n1, uint64_t k,
+                                    uint64_t distance_threshold, akz_match* d_out, uint32_t* d_counts);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly

@@ -37,6 +37,10 @@ int akz_debug_set_match_chunks(akz_ctx* ctx, uint32_t pair_chunks, uint32_t set_
 /* Test hook: the train rows per LDS tile of the matrix-core matcher (launch::match_mfma_tile_rows()), so that tests can place
    their set sizes one below, at and one above it.  No GPU call, no context. */
 int akz_debug_match_tile_rows(uint32_t* rows);
+/* Test hook: force the number of train chunks of the k-nearest-neighbour scan (akz_descriptor_match_knn*), so that tests reach
+   the merge of the chunks' partial lists at a few hundred rows; 0 = automatic (the default).  The counterpart of pair_chunks
+   above.  Results are identical for every value. */
+int akz_debug_set_knn_chunks(akz_ctx* ctx, uint32_t chunks);
 /* Measurement hook: schedule variants of a large batch (results are identical).  key 0: where the early stages
    (level-0 blur, contrast factor) of a batch whose input is complete run: 0 = the copy stream if the context's
    stream-placement probe found it a hardware queue and a pipe of its own (default), 1 = the copy stream regardless, 2 = a
