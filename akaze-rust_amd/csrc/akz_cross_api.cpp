@@ -86,8 +86,7 @@ int akz_descriptor_match_cross_device(akz_ctx* c, const uint8_t* d_d0, uint64_t 
         AKZ_HIP_TRY(hipMemsetAsync(d_n_out, 0, sizeof(uint64_t), st));
         return AKZ_OK;
     }
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t b_rev = up((size_t)n1 * sizeof(akz_match));
+    const size_t b_rev = up256((size_t)n1 * sizeof(akz_match));
     AKZ_TRY(ensure(c, c->cx_rev, b_rev + 256));
     akz_match* d_rev = (akz_match*)c->cx_rev.p;
     uint64_t* d_rcnt = (uint64_t*)((char*)c->cx_rev.p + b_rev);
@@ -110,11 +109,10 @@ int akz_descriptor_match_cross(akz_ctx* c, const uint8_t* d0, uint64_t n0, const
     if (n0 == 0 || n1 == 0) return AKZ_OK;
     // both sets as 64-byte rows in one block (A, then B); the lists and their counts beside them
     hipStream_t st = c->stream;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     std::vector<uint8_t> rows((size_t)(n0 + n1) * 64, 0);
     for (uint64_t i = 0; i < n0; ++i) std::memcpy(&rows[(size_t)i * 64], d0 + i * desc_bytes, (size_t)desc_bytes);
     for (uint64_t i = 0; i < n1; ++i) std::memcpy(&rows[(size_t)(n0 + i) * 64], d1 + i * desc_bytes, (size_t)desc_bytes);
-    const size_t b_fwd = up((size_t)n0 * sizeof(akz_match)), b_rev = up((size_t)n1 * sizeof(akz_match));
+    const size_t b_fwd = up256((size_t)n0 * sizeof(akz_match)), b_rev = up256((size_t)n1 * sizeof(akz_match));
     AKZ_TRY(ensure(c, c->match_a, rows.size()));
     AKZ_TRY(ensure(c, c->match_out, b_fwd + 256));
     AKZ_TRY(ensure(c, c->cx_rev, b_rev + 256));

@@ -373,6 +373,7 @@ AKZ_LOCAL inline hipError_t sync_all_streams(akz_ctx* c, unsigned which = kSyncA
         if ((which & kSyncSide) && s) wait(s);
     return first;
 }
+AKZ_LOCAL inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }  // the parts of one buffer start on 256 bytes
 AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return AKZ_OK;
     if (b.p) {
@@ -483,22 +484,7 @@ AKZ_LOCAL int place_streams(akz_ctx* c);
 // akz_match_api.cpp: the tail of every scan of one train set -- merge of the chunk records, ratio test, ordered compaction
 AKZ_LOCAL int match_finish(akz_ctx* c, MatchRec* rec, uint32_t n0, uint32_t chunks, uint32_t thr, double lowes_ratio, akz_match* d_out,
                            uint64_t* d_n_out);
-// akz_match_api.cpp: what the pairs calls share -- the refusals, the placement of every distinct set and its upload to c->mp_in
-AKZ_LOCAL int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                             uint64_t desc_bytes, const void* out, const void* n_out, std::vector<uint8_t>& seen, uint64_t& cap);
-AKZ_LOCAL uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, std::vector<uint8_t>& seen,
-                               std::vector<uint64_t>& set_row, std::vector<uint64_t>& used);
-AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint64_t>& used, const std::vector<uint64_t>& set_row,
-                           uint64_t rows, uint64_t desc_bytes, size_t b_rows, size_t b_xy);
-// akz_match_api.cpp: the descriptor scans of every pair over the uploaded sets; fills the pair records' raw_off, kp0_off, kp1_off, cnt_idx
-// -- and, given `cross`, the opposite direction of every pair to d_rev / d_rcnt with the records of launch::pairs_cross_filter
-AKZ_LOCAL int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
-                          double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
-                          std::vector<launch::PairJobHost>& tab, akz_match* d_rev = nullptr, uint64_t* d_rcnt = nullptr,
-                          std::vector<launch::CrossJobHost>* cross = nullptr, uint64_t distance_threshold = 10000);
-// akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device (rows of 64 bytes, x, y), enqueued on the
-// context's stream -- scan, merge, ratio test and ordered compaction; pair p's list goes to d_out + spec[p].out_off, its
-// length to d_cnt[p].  d_models: 9 floats per pair ON THE DEVICE; d_found (optional): pairs whose flag is 0 give empty lists.
+// ---- the pairs calls (akz_match_api.cpp, akz_match_seeded_api.cpp, akz_guided_api.cpp) -----------------------------------
 struct GuidedPairSpec {
     uint64_t q_row0, n0, t_row0, n1, out_off;
 };
@@ -510,8 +496,73 @@ struct RefineStage {  // the refit stage of akz_match_features_{homography,funda
     uint32_t max_iterations;
     uint32_t* iterations;  // one per pair, may be null
 };
+// What the opening of a pairs call leaves to the rest of it.  pairs_open fills the first group, pairs_front the second.
+struct AKZ_LOCAL PairsFront {
+    std::vector<uint64_t> set_row, used;  // first row of every set a pair names; those sets in order of first use
+    uint64_t rows = 0, cap1 = 0;          // rows of all used sets; the room of `out` (sum of the first sets' descriptors), at least 1
+    size_t b_rows = 0, b_xy = 0, b_cnt = 0;
+    uint8_t* d_rows = nullptr;  // c->mp_in = rows | x | y
+    float *d_kx = nullptr, *d_ky = nullptr;
+
+    bool timed = false;                    // akz_debug_match_pairs_split is on
+    std::vector<launch::PairJobHost> tab;  // one record per pair; raw_off, kp0_off, kp1_off and cnt_idx filled in
+    akz_match* d_raw = nullptr;            // c->mp_raw = raw lists | counts | points
+    uint64_t* d_cnt = nullptr;
+    float* d_pts = nullptr;
+    launch::PairJobHost *d_tab = nullptr, *h_tab = nullptr;  // c->mp_tab = table | the caller's bytes; c->mp_pin_tab = table | counts | the caller's
+    uint64_t* h_cnt = nullptr;                               // (read back; valid after the caller's synchronise)
+    char *d_own = nullptr, *h_own = nullptr;
+};
+// The head of c->mp_keep and of its pinned image c->mp_pin_out: kept counts | models | found | accepted fits | trials run, then the
+// kept lists.  The caller sets the four byte counts (0: the field is absent), pairs_keep the rest.
+struct PairsKeep {
+    size_t b_model, b_found, b_fits, b_trials;
+    size_t b_head = 0;
+    uint64_t n_keep = 0;
+    uint64_t* d_kcnt = nullptr;
+    float* d_hm = nullptr;
+    int32_t* d_hf = nullptr;
+    uint32_t *d_it = nullptr, *d_tr = nullptr;
+    akz_match* d_keep = nullptr;
+};
+// akz_match_api.cpp.  pairs_open: the refusals (guided: those of the guided scan too), bind, the placement of every distinct set and
+// the room for its rows.  pairs_front: pairs_open, the upload, the scans (cross: both directions and launch::pairs_cross_filter), the
+// table, launch::pair_points and the enqueued read-back of the counts -- it does not synchronise.  b_dev_own / b_pin_own: the caller's
+// bytes behind the table in c->mp_tab and behind the counts in c->mp_pin_tab.
+AKZ_LOCAL int pairs_open(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                         uint64_t desc_bytes, const void* out, const void* n_out, bool guided, PairsFront& f);
+AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const PairsFront& f);
+AKZ_LOCAL int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                          uint64_t desc_bytes, double lowes_ratio, const void* out, const void* n_out, bool guided, bool cross, size_t b_dev_own,
+                          size_t b_pin_own, PairsFront& f);
+AKZ_LOCAL int pairs_table_upload(akz_ctx* c, PairsFront& f);  // f.tab -> f.d_tab through f.h_tab
+AKZ_LOCAL int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k);
+// pairs_tail: launch::pairs_pick_filter over the trials' models and counts (d_mdl, d_inl), launch::model_refit given `refine`, the ONE
+// read-back of head and kept lists, the guided stage given `guided`, the synchronise, the copy-out and the intervals of a timed call
+// (t_host: the caller's host time, interval 2).  model .. trials_run: one per pair, each may be null.
+AKZ_LOCAL int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const PairsFront& f, const PairsKeep& k,
+                         launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine,
+                         float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host, akz_match* out, uint64_t* n_out,
+                         float* model, int* found, uint32_t* fits, uint64_t* trials_run);
+// the lists of a pairs call to out / n_out: pair p's guided list (h_gcnt[p] records at its fixed place in d_gout, fetched by ONE read-back
+// of the span such lists occupy) where h_gcnt is given and h_found is null or h_found[p] set, else its kept list (h_kcnt, h_keep, tab)
+AKZ_LOCAL int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const uint64_t* h_gcnt,
+                             const int32_t* h_found, const akz_match* d_gout, const uint64_t* h_kcnt, const akz_match* h_keep,
+                             const launch::PairJobHost* tab, akz_match* out, uint64_t* n_out);
+// akz_match_api.cpp: the descriptor scans of every pair over the uploaded sets; fills the pair records' raw_off, kp0_off, kp1_off, cnt_idx
+// -- and, given `cross`, the opposite direction of every pair to d_rev / d_rcnt with the records of launch::pairs_cross_filter
+AKZ_LOCAL int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
+                          double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
+                          std::vector<launch::PairJobHost>& tab, akz_match* d_rev = nullptr, uint64_t* d_rcnt = nullptr,
+                          std::vector<launch::CrossJobHost>* cross = nullptr, uint64_t distance_threshold = 10000);
+// akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device (rows of 64 bytes, x, y), enqueued on the
+// context's stream -- scan, merge, ratio test and ordered compaction; pair p's list goes to d_out + spec[p].out_off, its
+// length to d_cnt[p].  d_models: 9 floats per pair ON THE DEVICE; d_found (optional): pairs whose flag is 0 give empty lists.
+// guided_specs: every pair's rows as placed by pairs_open, its list at the fixed place out / d_out give it.
 AKZ_LOCAL int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs,
                             const std::vector<uint8_t>& seen);
+AKZ_LOCAL std::vector<GuidedPairSpec> guided_specs(const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs,
+                                                   const std::vector<uint64_t>& set_row);
 AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
                              int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
                              double lowes_ratio, akz_match* d_out, uint64_t* d_cnt);

@@ -1,5 +1,6 @@
-// C ABI of libakaze_hip.so, part 5: guided matching -- the host statement, the pair call and the pairs call
-// (the composite with the homography RANSAC is the last stage of match_pairs_impl, akz_match_api.cpp).
+// C ABI of libakaze_hip.so, part 5: guided matching -- the host statement, the pair call and the pairs call, which opens as every
+// pairs call does (pairs_open) and closes with the copy-out they share (pairs_copy_out); guided_specs and guided_enqueue are also
+// the guided stage of the RANSAC pairs calls (pairs_tail, akz_match_api.cpp).
 #include "akz_ctx.hpp"
 #include "akz_homography.hpp"
 
@@ -53,6 +54,17 @@ int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t*
         return AKZ_ERR_INVALID_ARG;
     }
     return AKZ_OK;
+}
+
+std::vector<GuidedPairSpec> guided_specs(const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const std::vector<uint64_t>& set_row) {
+    std::vector<GuidedPairSpec> spec((size_t)n_pairs);
+    uint64_t off = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1];
+        spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
+        off += sets[a].n_descriptors;
+    }
+    return spec;
 }
 
 int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
@@ -153,58 +165,25 @@ int akz_descriptor_match_guided_pairs(akz_ctx* c, const akz_feature_set* sets, u
     const char* name = "descriptor_match_guided_pairs: ";
     if (n_pairs == 0) return AKZ_OK;
     if (!guided_args_ok(name, model_kind, models, radius)) return AKZ_ERR_INVALID_ARG;
-    std::vector<uint8_t> seen;
-    uint64_t cap = 0;
-    AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
-    AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
-    AKZ_TRY(bind(c, true, false));
+    PairsFront f;
+    AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, true, f));
     hipStream_t st = c->stream;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    std::vector<uint64_t> set_row, used;
-    const uint64_t rows = pairs_place(sets, n_sets, pairs, n_pairs, seen, set_row, used);
-    const uint64_t rows1 = std::max<uint64_t>(rows, 1), cap1 = std::max<uint64_t>(cap, 1);
-    const size_t b_rows = up((size_t)rows1 * 64), b_xy = up((size_t)rows1 * 4), b_cnt = up((size_t)n_pairs * 8);
-    const size_t b_mdl = up((size_t)n_pairs * 36);
-    AKZ_TRY(ensure(c, c->mp_in, b_rows + 2 * b_xy));
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, b_rows + 2 * b_xy));
-    AKZ_TRY(ensure(c, c->gd_out, b_cnt + b_mdl + (size_t)cap1 * sizeof(akz_match)));
-    AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, b_cnt + b_mdl));
-    const uint8_t* d_rows = (const uint8_t*)c->mp_in.p;
-    const float *d_kx = (const float*)(d_rows + b_rows), *d_ky = (const float*)(d_rows + b_rows + b_xy);
+    const size_t b_mdl = up256((size_t)n_pairs * 36);
+    AKZ_TRY(ensure(c, c->gd_out, f.b_cnt + b_mdl + (size_t)f.cap1 * sizeof(akz_match)));
+    AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, f.b_cnt + b_mdl));
     uint64_t* d_cnt = (uint64_t*)c->gd_out.p;
-    float* d_models = (float*)((char*)c->gd_out.p + b_cnt);
-    akz_match* d_out = (akz_match*)((char*)c->gd_out.p + b_cnt + b_mdl);
+    float* d_models = (float*)((char*)c->gd_out.p + f.b_cnt);
+    akz_match* d_out = (akz_match*)((char*)c->gd_out.p + f.b_cnt + b_mdl);
     uint64_t* h_cnt = (uint64_t*)c->gd_pin_cnt.p;
-    float* h_models = (float*)((char*)c->gd_pin_cnt.p + b_cnt);
-    AKZ_TRY(pairs_upload(c, sets, used, set_row, rows, desc_bytes, b_rows, b_xy));
+    float* h_models = (float*)((char*)c->gd_pin_cnt.p + f.b_cnt);
+    AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));
     std::memcpy(h_models, models, (size_t)n_pairs * 36);
     AKZ_HIP_TRY(hipMemcpyAsync(d_models, h_models, (size_t)n_pairs * 36, hipMemcpyHostToDevice, st));
-    std::vector<GuidedPairSpec> spec((size_t)n_pairs);
-    uint64_t off = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1];
-        spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
-        off += sets[a].n_descriptors;
-    }
-    AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, model_kind, d_models, nullptr, radius, distance_threshold, lowes_ratio, d_out, d_cnt));
+    AKZ_TRY(guided_enqueue(c, guided_specs(sets, pairs, n_pairs, f.set_row), f.d_rows, f.d_kx, f.d_ky, model_kind, d_models, nullptr, radius,
+                           distance_threshold, lowes_ratio, d_out, d_cnt));
     AKZ_HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     AKZ_HIP_TRY(hipStreamSynchronize(st));
-    // ONE read-back of the span the lists occupy (fixed room per pair), through pinned staging
-    uint64_t span = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        if (h_cnt[p]) span = spec[(size_t)p].out_off + h_cnt[p];
-    if (span) {
-        AKZ_TRY(ensure_pinned(c, c->gd_pin_out, (size_t)span * sizeof(akz_match)));
-        AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_out.p, d_out, (size_t)span * sizeof(akz_match), hipMemcpyDeviceToHost, st));
-        AKZ_HIP_TRY(hipStreamSynchronize(st));
-    }
-    const akz_match* h_out = (const akz_match*)c->gd_pin_out.p;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint64_t k = h_cnt[p], at = spec[(size_t)p].out_off;
-        if (k) std::memcpy(out + at, h_out + at, (size_t)k * sizeof(akz_match));
-        n_out[p] = k;
-    }
-    return AKZ_OK;
+    return pairs_copy_out(c, sets, pairs, n_pairs, h_cnt, nullptr, d_out, nullptr, nullptr, nullptr, out, n_out);  // every pair's guided list
 }
 
 // one pair: the pairs call with sets {0, 1} and the pair (0, 1)

@@ -1,4 +1,6 @@
-// C ABI of libakaze_hip.so, part 4: descriptor_match (pair, multi-set, both directions), match_features.
+// C ABI of libakaze_hip.so, part 4: descriptor_match (pair, multi-set, both directions), match_features, and the RANSAC pairs calls:
+// what they all share (pairs_validate .. pairs_scans, the front and the tail: pairs_front, pairs_keep, pairs_tail), the call that draws
+// its samples on the host between the two (match_pairs_impl<Model>), and its entry points for both models, one pair or many.
 #include "akz_ctx.hpp"
 
 // Merge of a query set's chunk records (rec[chunk][query], then room for n0 merged records), ratio test and ordered
@@ -366,24 +368,23 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
             AKZ_TRY(bind(c, true, false));
             const size_t b_pts = (size_t)n * 4 * sizeof(float), b_smp = (size_t)trials * 8 * sizeof(uint32_t);
             const size_t b_mdl = (size_t)trials * 9 * sizeof(float), b_inl = (size_t)trials * sizeof(int32_t);
-            auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-            const size_t in_bytes = up(b_pts) + up(b_smp), out_bytes = up(b_mdl) + up(b_inl);
+            const size_t in_bytes = up256(b_pts) + up256(b_smp), out_bytes = up256(b_mdl) + up256(b_inl);
             AKZ_TRY(ensure(c, c->ransac_dev, in_bytes + out_bytes));
             AKZ_TRY(ensure_pinned(c, c->ransac_pin, in_bytes + out_bytes));
             char* h = (char*)c->ransac_pin.p;
             char* d = (char*)c->ransac_dev.p;
             std::memcpy(h, x0, (size_t)n * 4); std::memcpy(h + (size_t)n * 4, y0, (size_t)n * 4);
             std::memcpy(h + (size_t)n * 8, x1, (size_t)n * 4); std::memcpy(h + (size_t)n * 12, y1, (size_t)n * 4);
-            std::memcpy(h + up(b_pts), samples, b_smp);
+            std::memcpy(h + up256(b_pts), samples, b_smp);
             hipStream_t st = c->stream;
             AKZ_HIP_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
-            launch::ransac_trials(st, (const float*)d, n, (const uint32_t*)(d + up(b_pts)), trials, eps_model, eps_inlier,
-                                  (float*)(d + in_bytes), (int32_t*)(d + in_bytes + up(b_mdl)));
+            launch::ransac_trials(st, (const float*)d, n, (const uint32_t*)(d + up256(b_pts)), trials, eps_model, eps_inlier,
+                                  (float*)(d + in_bytes), (int32_t*)(d + in_bytes + up256(b_mdl)));
             AKZ_HIP_TRY(hipGetLastError());
             AKZ_HIP_TRY(hipMemcpyAsync(h + in_bytes, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, st));
             AKZ_HIP_TRY(hipStreamSynchronize(st));
             std::memcpy(models, h + in_bytes, b_mdl);
-            std::memcpy(inliers, h + in_bytes + up(b_mdl), b_inl);
+            std::memcpy(inliers, h + in_bytes + up256(b_mdl), b_inl);
             return AKZ_OK;
         };
     return remove_outliers_impl(kp0, n_kp0, kp1, n_kp1, raw.data(), n_raw, ransac_trials, 0.05f, ransac_epsilon_inliers, out, n_out,
@@ -394,8 +395,8 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
 
 // The refusals of the pairs calls (akz_match_features_pairs, its homography form, akz_descriptor_match_guided_pairs), all
 // before any GPU work: seen[k] = 1 for every set a pair names, cap = the room of `out` (sum of the first sets' descriptors).
-int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                        uint64_t desc_bytes, const void* out, const void* n_out, std::vector<uint8_t>& seen, uint64_t& cap) {
+static int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                          uint64_t desc_bytes, const void* out, const void* n_out, std::vector<uint8_t>& seen, uint64_t& cap) {
     auto refuse = [name](const std::string& msg) {
         set_error(name + msg);
         return AKZ_ERR_INVALID_ARG;
@@ -424,8 +425,8 @@ int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, ui
 }
 // every distinct set once, in order of first use: rows (and x / y of its first n_descriptors keypoints, the only ones a
 // match can name) from row set_row[k]; returns the rows of all used sets
-uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, std::vector<uint8_t>& seen,
-                          std::vector<uint64_t>& set_row, std::vector<uint64_t>& used) {
+static uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, std::vector<uint8_t>& seen,
+                            std::vector<uint64_t>& set_row, std::vector<uint64_t>& used) {
     set_row.assign((size_t)n_sets, 0);
     used.clear();
     uint64_t rows = 0;
@@ -441,29 +442,25 @@ uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_
     return rows;
 }
 // every used set's rows (padded to 64 bytes) and the x / y of its first n_descriptors keypoints: through pinned staging to
-// c->mp_in = rows | x | y (b_rows, b_xy: the sizes of the parts), on the context's stream
-int pairs_upload(akz_ctx* c, const akz_feature_set* sets, const std::vector<uint64_t>& used, const std::vector<uint64_t>& set_row,
-                      uint64_t rows, uint64_t desc_bytes, size_t b_rows, size_t b_xy) {
+// c->mp_in = rows | x | y, on the context's stream
+int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const PairsFront& f) {
     hipStream_t st = c->stream;
-    uint8_t* d_rows = (uint8_t*)c->mp_in.p;
-    float *d_kx = (float*)(d_rows + b_rows), *d_ky = (float*)(d_rows + b_rows + b_xy);
-    {
-        uint8_t* h = (uint8_t*)c->mp_pin_in.p;
-        float *hx = (float*)(h + b_rows), *hy = (float*)(h + b_rows + b_xy);
-        for (uint64_t k : used) {
-            const akz_feature_set& f = sets[k];
-            uint8_t* r = h + set_row[(size_t)k] * 64;
-            for (uint64_t i = 0; i < f.n_descriptors; ++i) {
-                std::memcpy(r + i * 64, f.descriptors + i * desc_bytes, (size_t)desc_bytes);
-                if (desc_bytes < 64) std::memset(r + i * 64 + desc_bytes, 0, (size_t)(64 - desc_bytes));
-                hx[set_row[(size_t)k] + i] = f.keypoints[i].x;
-                hy[set_row[(size_t)k] + i] = f.keypoints[i].y;
-            }
+    uint8_t* h = (uint8_t*)c->mp_pin_in.p;
+    float *hx = (float*)(h + f.b_rows), *hy = (float*)(h + f.b_rows + f.b_xy);
+    for (uint64_t k : f.used) {
+        const akz_feature_set& s = sets[k];
+        const uint64_t row0 = f.set_row[(size_t)k];
+        uint8_t* r = h + row0 * 64;
+        for (uint64_t i = 0; i < s.n_descriptors; ++i) {
+            std::memcpy(r + i * 64, s.descriptors + i * desc_bytes, (size_t)desc_bytes);
+            if (desc_bytes < 64) std::memset(r + i * 64 + desc_bytes, 0, (size_t)(64 - desc_bytes));
+            hx[row0 + i] = s.keypoints[i].x;
+            hy[row0 + i] = s.keypoints[i].y;
         }
-        AKZ_HIP_TRY(hipMemcpyAsync(d_rows, h, (size_t)rows * 64, hipMemcpyHostToDevice, st));
-        AKZ_HIP_TRY(hipMemcpyAsync(d_kx, hx, (size_t)rows * 4, hipMemcpyHostToDevice, st));
-        AKZ_HIP_TRY(hipMemcpyAsync(d_ky, hy, (size_t)rows * 4, hipMemcpyHostToDevice, st));
     }
+    AKZ_HIP_TRY(hipMemcpyAsync(f.d_rows, h, (size_t)f.rows * 64, hipMemcpyHostToDevice, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(f.d_kx, hx, (size_t)f.rows * 4, hipMemcpyHostToDevice, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(f.d_ky, hy, (size_t)f.rows * 4, hipMemcpyHostToDevice, st));
     return AKZ_OK;
 }
 // The scans of the pairs calls, enqueued on the context's stream over the sets that pairs_upload placed: pair p's raw list goes to
@@ -548,6 +545,175 @@ int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const 
     }
     return AKZ_OK;
 }
+// The opening every pairs call shares (akz_ctx.hpp): no GPU work before the last refusal.
+int pairs_open(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+               uint64_t desc_bytes, const void* out, const void* n_out, bool guided, PairsFront& f) {
+    std::vector<uint8_t> seen;
+    uint64_t cap = 0;
+    AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
+    if (guided) AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
+    AKZ_TRY(bind(c, true, false));
+    f.rows = pairs_place(sets, n_sets, pairs, n_pairs, seen, f.set_row, f.used);
+    f.cap1 = std::max<uint64_t>(cap, 1);
+    const uint64_t rows1 = std::max<uint64_t>(f.rows, 1);
+    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4), f.b_cnt = up256((size_t)n_pairs * 8);
+    AKZ_TRY(ensure(c, c->mp_in, f.b_rows + 2 * f.b_xy));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, f.b_rows + 2 * f.b_xy));
+    f.d_rows = (uint8_t*)c->mp_in.p;
+    f.d_kx = (float*)(f.d_rows + f.b_rows), f.d_ky = (float*)(f.d_rows + f.b_rows + f.b_xy);
+    return AKZ_OK;
+}
+int pairs_table_upload(akz_ctx* c, PairsFront& f) {
+    std::memcpy(f.h_tab, f.tab.data(), f.tab.size() * sizeof(launch::PairJobHost));
+    AKZ_HIP_TRY(hipMemcpyAsync(f.d_tab, f.h_tab, f.tab.size() * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, c->stream));
+    return AKZ_OK;
+}
+// The front of the RANSAC pairs calls, all on the context's stream: every distinct set's 64-byte rows and keypoint x / y through pinned
+// staging; the descriptor scans (pairs_scans; cross: the opposite direction too, and the filter that rewrites raw lists and counts before
+// anything reads them); the pair table; k_pair_points; the read-back of the match counts, which the caller waits for.
+int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                uint64_t desc_bytes, double lowes_ratio, const void* out, const void* n_out, bool guided, bool cross, size_t b_dev_own,
+                size_t b_pin_own, PairsFront& f) {
+    AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, guided, f));
+    f.timed = c->mp_split_on;
+    if (f.timed)
+        for (hipEvent_t& e : c->mp_split_ev)
+            if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
+    hipStream_t st = c->stream;
+    const size_t b_raw = up256((size_t)f.cap1 * sizeof(akz_match)), b_tab = up256((size_t)n_pairs * sizeof(launch::PairJobHost));
+    AKZ_TRY(ensure(c, c->mp_raw, b_raw + f.b_cnt + (size_t)f.cap1 * 16));
+    AKZ_TRY(ensure(c, c->mp_tab, b_tab + b_dev_own));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_tab, b_tab + f.b_cnt + b_pin_own));
+    f.d_raw = (akz_match*)c->mp_raw.p;
+    f.d_cnt = (uint64_t*)((char*)c->mp_raw.p + b_raw);
+    f.d_pts = (float*)((char*)c->mp_raw.p + b_raw + f.b_cnt);
+    f.d_tab = (launch::PairJobHost*)c->mp_tab.p;
+    f.d_own = (char*)c->mp_tab.p + b_tab;
+    f.h_tab = (launch::PairJobHost*)c->mp_pin_tab.p;
+    f.h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
+    f.h_own = (char*)c->mp_pin_tab.p + b_tab + f.b_cnt;
+    if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
+    AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));
+    if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
+    if (cross) {  // the reverse lists (room: every pair's second set), their counts and the filter's records
+        uint64_t cap_rev = 0;
+        for (uint64_t p = 0; p < n_pairs; ++p) cap_rev += sets[pairs[2 * p + 1]].n_descriptors;
+        const size_t b_rev = up256((size_t)std::max<uint64_t>(cap_rev, 1) * sizeof(akz_match)), b_xtab = up256((size_t)n_pairs * sizeof(launch::CrossJobHost));
+        AKZ_TRY(ensure(c, c->cx_rev, b_rev + f.b_cnt + b_xtab));
+        AKZ_TRY(ensure_pinned(c, c->cx_pin_tab, b_xtab));
+        akz_match* d_rev = (akz_match*)c->cx_rev.p;
+        uint64_t* d_rcnt = (uint64_t*)((char*)c->cx_rev.p + b_rev);
+        launch::CrossJobHost* d_xtab = (launch::CrossJobHost*)((char*)c->cx_rev.p + b_rev + f.b_cnt);
+        std::vector<launch::CrossJobHost> xtab;
+        AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, f.set_row, f.d_rows, f.d_raw, f.d_cnt, f.tab, d_rev, d_rcnt, &xtab));
+        std::memcpy(c->cx_pin_tab.p, xtab.data(), (size_t)n_pairs * sizeof(launch::CrossJobHost));
+        AKZ_HIP_TRY(hipMemcpyAsync(d_xtab, c->cx_pin_tab.p, (size_t)n_pairs * sizeof(launch::CrossJobHost), hipMemcpyHostToDevice, st));
+        launch::pairs_cross_filter(st, d_xtab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, d_rev, d_rcnt);
+        AKZ_HIP_TRY(hipGetLastError());
+    } else {
+        AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, f.set_row, f.d_rows, f.d_raw, f.d_cnt, f.tab));
+    }
+    AKZ_TRY(pairs_table_upload(c, f));
+    launch::pair_points(st, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_kx, f.d_ky, f.d_pts, f.cap1);
+    AKZ_HIP_TRY(hipGetLastError());
+    AKZ_HIP_TRY(hipMemcpyAsync(f.h_cnt, f.d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+    return AKZ_OK;
+}
+// room for the head and the kept lists of n_keep matches (PairsKeep, akz_ctx.hpp) on the device and in pinned memory
+int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k) {
+    k.n_keep = n_keep;
+    k.b_head = f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials;
+    const size_t b_keep = k.b_head + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
+    AKZ_TRY(ensure(c, c->mp_keep, b_keep));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_out, b_keep));
+    char* d = (char*)c->mp_keep.p;
+    k.d_kcnt = (uint64_t*)d;
+    k.d_hm = (float*)(d + f.b_cnt);
+    k.d_hf = (int32_t*)(d + f.b_cnt + k.b_model);
+    k.d_it = (uint32_t*)(d + f.b_cnt + k.b_model + k.b_found);
+    k.d_tr = (uint32_t*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits);
+    k.d_keep = (akz_match*)(d + k.b_head);
+    return AKZ_OK;
+}
+int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const uint64_t* h_gcnt, const int32_t* h_found,
+                   const akz_match* d_gout, const uint64_t* h_kcnt, const akz_match* h_keep, const launch::PairJobHost* tab, akz_match* out,
+                   uint64_t* n_out) {
+    auto guided = [&](uint64_t p) { return h_gcnt && (!h_found || h_found[p] != 0); };
+    uint64_t span = 0, off = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        if (guided(p) && h_gcnt[p]) span = off + h_gcnt[p];
+        off += sets[pairs[2 * p]].n_descriptors;
+    }
+    if (span) {  // through pinned staging
+        AKZ_TRY(ensure_pinned(c, c->gd_pin_out, (size_t)span * sizeof(akz_match)));
+        AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_out.p, d_gout, (size_t)span * sizeof(akz_match), hipMemcpyDeviceToHost, c->stream));
+        AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    const akz_match* h_gout = (const akz_match*)c->gd_pin_out.p;
+    uint64_t at = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        const uint64_t n = guided(p) ? h_gcnt[p] : h_kcnt[p];  // found: the guided list replaces the filtered one
+        if (n) std::memcpy(out + at, guided(p) ? h_gout + at : h_keep + tab[p].keep_off, (size_t)n * sizeof(akz_match));
+        n_out[p] = n;
+        at += sets[pairs[2 * p]].n_descriptors;
+    }
+    return AKZ_OK;
+}
+// The tail of the RANSAC pairs calls (akz_ctx.hpp).  launch::model_refit rewrites the models, the kept lists and their counts in place and
+// adds every pair's number of accepted fits to the head; the guided stage then scans every pair again with the model (H or F) that is on
+// the device (pairs without one give empty lists that nobody reads) over the sets the front uploaded.  Both stages need the head's models.
+int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const PairsFront& f, const PairsKeep& k,
+               launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine,
+               float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host, akz_match* out, uint64_t* n_out, float* model,
+               int* found, uint32_t* fits, uint64_t* trials_run) {
+    hipStream_t st = c->stream;
+    launch::pairs_pick_filter(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, d_mdl, d_inl, epsilon_inliers, k.d_keep, k.d_kcnt,
+                              k.b_model ? k.d_hm : nullptr, k.b_found ? k.d_hf : nullptr);
+    AKZ_HIP_TRY(hipGetLastError());
+    if (refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
+        launch::model_refit(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, refit_epsilon, epsilon_inliers,
+                            refine->max_iterations, k.d_keep, k.d_kcnt, k.d_hm, k.d_hf, k.d_it);
+        AKZ_HIP_TRY(hipGetLastError());
+    }
+    if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
+    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, k.b_head + (size_t)k.n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
+    if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
+    akz_match* d_gout = nullptr;
+    if (guided) {
+        AKZ_TRY(ensure(c, c->gd_out, f.b_cnt + (size_t)f.cap1 * sizeof(akz_match)));
+        AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, f.b_cnt));
+        uint64_t* d_gcnt = (uint64_t*)c->gd_out.p;
+        d_gout = (akz_match*)((char*)c->gd_out.p + f.b_cnt);
+        AKZ_TRY(guided_enqueue(c, guided_specs(sets, pairs, n_pairs, f.set_row), f.d_rows, f.d_kx, f.d_ky, guided_kind, k.d_hm, k.d_hf, guided->radius,
+                               10000, guided->ratio, d_gout, d_gcnt));
+        AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_cnt.p, d_gcnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+    }
+    AKZ_HIP_TRY(hipStreamSynchronize(st));
+    const char* head = (const char*)c->mp_pin_out.p;
+    const float* h_hm = (const float*)(head + f.b_cnt);
+    const int32_t* h_hf = (const int32_t*)(head + f.b_cnt + k.b_model);
+    const uint32_t* h_it = (const uint32_t*)(head + f.b_cnt + k.b_model + k.b_found);
+    const uint32_t* h_tr = (const uint32_t*)(head + f.b_cnt + k.b_model + k.b_found + k.b_fits);
+    AKZ_TRY(pairs_copy_out(c, sets, pairs, n_pairs, guided ? (const uint64_t*)c->gd_pin_cnt.p : nullptr, h_hf, d_gout, (const uint64_t*)head,
+                           (const akz_match*)(head + k.b_head), f.tab.data(), out, n_out));
+    if (model) std::memcpy(model, h_hm, (size_t)n_pairs * 36);
+    for (uint64_t p = 0; p < n_pairs; ++p) {
+        if (found) found[p] = h_hf[p];
+        if (fits) fits[p] = h_it[p];
+        if (trials_run) trials_run[p] = h_tr[p];
+    }
+    if (f.timed) {  // akz_debug_match_pairs_split: [3] is the trials or the rounds, between the caller's events 3 and 4
+        float ms[6] = {};
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[0], c->mp_split_ev[0], c->mp_split_ev[1]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[1], c->mp_split_ev[1], c->mp_split_ev[2]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[3], c->mp_split_ev[3], c->mp_split_ev[4]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[4], c->mp_split_ev[4], c->mp_split_ev[5]));
+        AKZ_HIP_TRY(hipEventElapsedTime(&ms[5], c->mp_split_ev[5], c->mp_split_ev[6]));
+        for (int i = 0; i < 6; ++i) c->mp_split_ms[i] = ms[i];
+        c->mp_split_ms[2] = t_host;
+    }
+    return AKZ_OK;
+}
 // The geometric model of the pairs orchestration below: the kernels' model kind, K match indices per sample, and whether the
 // call hands back a model per pair (H, found).
 namespace {
@@ -574,14 +740,9 @@ struct HomographyModel {  // akz_match_features_homography(_pairs)
     static constexpr const char* kName = "match_features_homography_pairs: ";
 };
 
-// match_features over many pairs (see the header).  Stages, all on the context's stream: every distinct set's 64-byte rows and
-// keypoint x / y through pinned staging; the descriptor scans (one multi-set launch per first set, or the pair matcher for
-// rows of 62..64 bytes); k_pair_points; ONE read-back of the match counts; the samples drawn on the calling thread in pair
-// order, in chunks whose trials (launch::pairs_trials) run while the next chunk is drawn; launch::pairs_pick_filter; ONE read-back of the
-// kept lists (and, for a model that is handed back, every pair's model and found flag).  A RefineStage puts the refit kernel of
-// the model's kind between the pick and that read-back: it rewrites the models, the kept lists and their counts in place and
-// adds every pair's number of accepted fits to the head that the read-back carries; the guided stage, gating with the model's
-// kind, then reads the model table it has rewritten.  Both stages need a model that is handed back (kModelOut).
+// match_features over many pairs (see the header), the samples drawn on the host: between pairs_front and pairs_tail the samples
+// of every pair with K matches or more are drawn on the calling thread in pair order, in chunks whose trials (launch::pairs_trials)
+// run while the next chunk is drawn.  A RefineStage or a GuidedStage needs a model that is handed back (kModelOut).
 template <class Model>
 int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
                      double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out, float* model_out,
@@ -593,87 +754,39 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         set_error(std::string(name) + "guided_radius must be finite and >= 0");
         return AKZ_ERR_INVALID_ARG;
     }
-    std::vector<uint8_t> seen;
-    uint64_t cap = 0;
-    AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
-    if (guided) AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
-    AKZ_TRY(bind(c, true, false));
-    const bool timed = c->mp_split_on;
-    if (timed)
-        for (hipEvent_t& e : c->mp_split_ev)
-            if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
-    hipStream_t st = c->stream;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    std::vector<uint64_t> set_row, used;
-    const uint64_t rows = pairs_place(sets, n_sets, pairs, n_pairs, seen, set_row, used);
-    const uint64_t rows1 = std::max<uint64_t>(rows, 1), cap1 = std::max<uint64_t>(cap, 1);
-    const size_t b_rows = up((size_t)rows1 * 64), b_xy = up((size_t)rows1 * 4);
-    const size_t b_raw = up((size_t)cap1 * sizeof(akz_match)), b_cnt = up((size_t)n_pairs * 8), b_pts = (size_t)cap1 * 16;
-    const size_t b_tab = up((size_t)n_pairs * sizeof(launch::PairJobHost));
+    if (!Model::kModelOut) refine = nullptr;
     constexpr uint32_t kChunk = 16384;  // trials per launch of k_pairs_trials (and per pinned sample slot)
     const size_t b_smp = (size_t)kChunk * 9 * sizeof(uint32_t);
-    AKZ_TRY(ensure(c, c->mp_in, b_rows + 2 * b_xy));
-    AKZ_TRY(ensure(c, c->mp_raw, b_raw + b_cnt + b_pts));
-    AKZ_TRY(ensure(c, c->mp_tab, b_tab + 2 * b_smp));
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, b_rows + 2 * b_xy));
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_tab, b_tab + b_cnt));
-    uint8_t* d_rows = (uint8_t*)c->mp_in.p;
-    float *d_kx = (float*)(d_rows + b_rows), *d_ky = (float*)(d_rows + b_rows + b_xy);
-    akz_match* d_raw = (akz_match*)c->mp_raw.p;
-    uint64_t* d_cnt = (uint64_t*)((char*)c->mp_raw.p + b_raw);
-    float* d_pts = (float*)((char*)c->mp_raw.p + b_raw + b_cnt);
-    launch::PairJobHost* d_tab = (launch::PairJobHost*)c->mp_tab.p;
-    uint32_t* d_smp[2] = {(uint32_t*)((char*)c->mp_tab.p + b_tab), (uint32_t*)((char*)c->mp_tab.p + b_tab + b_smp)};
-    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
-    AKZ_TRY(pairs_upload(c, sets, used, set_row, rows, desc_bytes, b_rows, b_xy));
-    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
-    // the scans: pair p's raw list at raw_off, its count at d_cnt[cnt_idx]
-    std::vector<launch::PairJobHost> tab;
-    AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, set_row, d_rows, d_raw, d_cnt, tab));
-    launch::PairJobHost* h_tab = (launch::PairJobHost*)c->mp_pin_tab.p;
-    uint64_t* h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
-    std::memcpy(h_tab, tab.data(), (size_t)n_pairs * sizeof(launch::PairJobHost));
-    AKZ_HIP_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)n_pairs * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, st));
-    launch::pair_points(st, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_kx, d_ky, d_pts, cap1);
-    AKZ_HIP_TRY(hipGetLastError());
-    AKZ_HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
-    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[2], st));
+    PairsFront f;
+    AKZ_TRY(pairs_front(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, out, n_out, guided != nullptr, false, 2 * b_smp, 0, f));
+    hipStream_t st = c->stream;
+    uint32_t* d_smp[2] = {(uint32_t*)f.d_own, (uint32_t*)(f.d_own + b_smp)};
+    if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[2], st));
     AKZ_HIP_TRY(hipStreamSynchronize(st));
     // the trials of every pair with 8 matches or more, in pair order; the kept lists side by side
     uint64_t n_trials = 0, n_keep = 0;
     for (uint64_t p = 0; p < n_pairs; ++p) {
-        launch::PairJobHost& j = tab[(size_t)p];
-        const uint64_t n = h_cnt[j.cnt_idx];
+        launch::PairJobHost& j = f.tab[(size_t)p];
+        const uint64_t n = f.h_cnt[j.cnt_idx];
         j.trial_off = n_trials;
-        j.n_trials = 0;
+        j.n_trials = n >= (uint64_t)K ? ransac_trials : 0;  // (the pair's trials, for the pick)
         j.keep_off = n_keep;
         n_keep += n;
-        if (n >= (uint64_t)K) n_trials += ransac_trials;
+        n_trials += j.n_trials;
     }
-    const size_t b_mdl = up((size_t)std::max<uint64_t>(n_trials, 1) * 36), b_inl = up((size_t)std::max<uint64_t>(n_trials, 1) * 4);
+    const size_t b_mdl = up256((size_t)std::max<uint64_t>(n_trials, 1) * 36), b_inl = up256((size_t)std::max<uint64_t>(n_trials, 1) * 4);
     // (a model handed back: every pair's 9 floats and found flag between the counts and the kept lists)
-    const size_t b_hm = Model::kModelOut ? up((size_t)n_pairs * 36) : 0, b_hf = Model::kModelOut ? up((size_t)n_pairs * 4) : 0;
-    const size_t b_it = Model::kModelOut && refine ? up((size_t)n_pairs * 4) : 0;
-    const size_t b_head = b_cnt + b_hm + b_hf + b_it;
-    const size_t b_keep = b_head + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
+    PairsKeep keep{Model::kModelOut ? up256((size_t)n_pairs * 36) : 0, Model::kModelOut ? up256((size_t)n_pairs * 4) : 0,
+                   refine ? up256((size_t)n_pairs * 4) : 0, 0};
     AKZ_TRY(ensure(c, c->mp_trials, b_mdl + b_inl));
-    AKZ_TRY(ensure(c, c->mp_keep, b_keep));
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_out, b_keep));
-    for (int k = 0; k < 2; ++k) {
-        AKZ_TRY(ensure_pinned(c, c->mp_pin_smp[k], b_smp));
-        if (!c->mp_smp_ev[k]) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->mp_smp_ev[k], hipEventDisableTiming));
+    AKZ_TRY(pairs_keep(c, f, n_keep, keep));
+    for (int i = 0; i < 2; ++i) {
+        AKZ_TRY(ensure_pinned(c, c->mp_pin_smp[i], b_smp));
+        if (!c->mp_smp_ev[i]) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->mp_smp_ev[i], hipEventDisableTiming));
     }
     float* d_mdl = (float*)c->mp_trials.p;
     int32_t* d_inl = (int32_t*)((char*)c->mp_trials.p + b_mdl);
-    uint64_t* d_kcnt = (uint64_t*)c->mp_keep.p;
-    float* d_hm = (float*)((char*)c->mp_keep.p + b_cnt);
-    int32_t* d_hf = (int32_t*)((char*)c->mp_keep.p + b_cnt + b_hm);
-    uint32_t* d_it = (uint32_t*)((char*)c->mp_keep.p + b_cnt + b_hm + b_hf);
-    akz_match* d_keep = (akz_match*)((char*)c->mp_keep.p + b_head);
-    for (uint64_t p = 0; p < n_pairs; ++p)  // (n_trials of the table: the pair's trials, for the pick)
-        if (h_cnt[tab[(size_t)p].cnt_idx] >= (uint64_t)K) tab[(size_t)p].n_trials = ransac_trials;
-    std::memcpy(h_tab, tab.data(), (size_t)n_pairs * sizeof(launch::PairJobHost));
-    AKZ_HIP_TRY(hipMemcpyAsync(d_tab, h_tab, (size_t)n_pairs * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, st));
+    AKZ_TRY(pairs_table_upload(c, f));
     // draws on this thread, in pair order; a full slot goes to the device and its trials start while the next one fills
     double t_draw = 0.0;
     DefaultSource& src = default_source();
@@ -688,9 +801,9 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         std::memmove(hs + (size_t)fill * K, hs + (size_t)kChunk * K, (size_t)fill * 4);
         AKZ_HIP_TRY(hipMemcpyAsync(d_smp[slot], hs, (size_t)fill * (K + 1) * 4, hipMemcpyHostToDevice, st));
         AKZ_HIP_TRY(hipEventRecord(c->mp_smp_ev[slot], st));
-        if (timed && !launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
+        if (f.timed && !launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         launched = true;
-        launch::pairs_trials(st, Model::kKind, d_tab, d_smp[slot], chunk_first, fill, d_cnt, d_pts, cap1, Model::kEpsilonModel,
+        launch::pairs_trials(st, Model::kKind, f.d_tab, d_smp[slot], chunk_first, fill, f.d_cnt, f.d_pts, f.cap1, Model::kEpsilonModel,
                              ransac_epsilon_inliers, d_mdl, d_inl);
         AKZ_HIP_TRY(hipGetLastError());
         chunk_first += fill;
@@ -700,7 +813,7 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         return AKZ_OK;
     };
     for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint64_t n = h_cnt[tab[(size_t)p].cnt_idx];
+        const uint64_t n = f.h_cnt[f.tab[(size_t)p].cnt_idx];
         if (n < (uint64_t)K) continue;
         for (uint64_t left = ransac_trials; left;) {
             if (!hs) {  // the slot's previous copy must be done before it is written again
@@ -718,92 +831,40 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         }
     }
     AKZ_TRY(flush());
-    if (timed) {
+    if (f.timed) {
         if (!launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[4], st));
     }
-    launch::pairs_pick_filter(st, Model::kKind, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, d_mdl, d_inl, ransac_epsilon_inliers, d_keep,
-                              d_kcnt, Model::kModelOut ? d_hm : nullptr, Model::kModelOut ? d_hf : nullptr);
-    AKZ_HIP_TRY(hipGetLastError());
-    if (Model::kModelOut && refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
-        launch::model_refit(st, Model::kKind, d_tab, (uint32_t)n_pairs, d_raw, d_cnt, d_pts, cap1, Model::kRefitEpsilon, ransac_epsilon_inliers,
-                            refine->max_iterations, d_keep, d_kcnt, d_hm, d_hf, d_it);
-        AKZ_HIP_TRY(hipGetLastError());
+    return pairs_tail(c, sets, pairs, n_pairs, f, keep, Model::kKind, d_mdl, d_inl, ransac_epsilon_inliers, refine, Model::kRefitEpsilon, guided,
+                      Model::kGuidedKind, t_draw, out, n_out, model_out, found_out, refine ? refine->iterations : nullptr, nullptr);
+}
+// One pair: the pairs call with sets {0, 1} and the pair (0, 1).  refine_iterations / g: null without that stage.  H is copied out only
+// when found; F always (zeros without a winner, as akz_remove_outliers_fundamental), and its refusals inside the pairs call carry `name`.
+template <class Model>
+int match_single(const char* name, akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0, const akz_keypoint* kp1,
+                 uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
+                 float ransac_epsilon_inliers, const uint32_t* refine_iterations, const GuidedStage* g, akz_match* out, uint64_t* n_out, float* m,
+                 int* found, uint32_t* iterations) {
+    constexpr bool homography = Model::kKind == launch::RansacModel::Homography;
+    if (!n_out) {
+        set_error(std::string(name) + "null n_out");
+        return AKZ_ERR_INVALID_ARG;
     }
-    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
-    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, b_head + (size_t)n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
-    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
-    // the guided stage: every pair scanned again with the model (H or F) that the pick kernel left on the device (pairs without one give
-    // empty lists that nobody reads); the sets are those uploaded above
-    akz_match* d_gout = nullptr;
-    if (guided) {
-        AKZ_TRY(ensure(c, c->gd_out, b_cnt + (size_t)cap1 * sizeof(akz_match)));
-        AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, b_cnt));
-        uint64_t* d_gcnt = (uint64_t*)c->gd_out.p;
-        d_gout = (akz_match*)((char*)c->gd_out.p + b_cnt);
-        std::vector<GuidedPairSpec> spec((size_t)n_pairs);
-        uint64_t off = 0;
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1];
-            spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
-            off += sets[a].n_descriptors;
-        }
-        AKZ_TRY(guided_enqueue(c, spec, d_rows, d_kx, d_ky, Model::kGuidedKind, d_hm, d_hf, guided->radius, 10000, guided->ratio, d_gout,
-                               d_gcnt));
-        AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_cnt.p, d_gcnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
+    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
+        set_error(std::string(name) + "a feature set has more descriptors than keypoints");
+        return AKZ_ERR_INVALID_ARG;
     }
-    AKZ_HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t* h_kcnt = (const uint64_t*)c->mp_pin_out.p;
-    const akz_match* h_keep = (const akz_match*)((const char*)c->mp_pin_out.p + b_head);
-    // the guided lists of the pairs with a model: ONE read-back of the span they occupy, through pinned staging
-    const int32_t* h_found = (const int32_t*)((const char*)c->mp_pin_out.p + b_cnt + b_hm);
-    const akz_match* h_gout = nullptr;
-    if (guided) {
-        uint64_t span = 0, off = 0;
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            if (h_found[p] && ((const uint64_t*)c->gd_pin_cnt.p)[p]) span = off + ((const uint64_t*)c->gd_pin_cnt.p)[p];
-            off += sets[pairs[2 * p]].n_descriptors;
-        }
-        if (span) {
-            AKZ_TRY(ensure_pinned(c, c->gd_pin_out, (size_t)span * sizeof(akz_match)));
-            AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_out.p, d_gout, (size_t)span * sizeof(akz_match), hipMemcpyDeviceToHost, st));
-            AKZ_HIP_TRY(hipStreamSynchronize(st));
-            h_gout = (const akz_match*)c->gd_pin_out.p;
-        }
-    }
-    uint64_t at = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint64_t k = h_kcnt[p];
-        const bool take_guided = guided && h_found[p] != 0;
-        if (take_guided) {  // found: the guided list replaces the filtered one
-            const uint64_t g = ((const uint64_t*)c->gd_pin_cnt.p)[p];
-            if (g) std::memcpy(out + at, h_gout + at, (size_t)g * sizeof(akz_match));
-            n_out[p] = g;
-        } else {
-            if (k) std::memcpy(out + at, h_keep + tab[(size_t)p].keep_off, (size_t)k * sizeof(akz_match));
-            n_out[p] = k;
-        }
-        at += sets[pairs[2 * p]].n_descriptors;
-    }
-    if (Model::kModelOut) {
-        const float* h_hm = (const float*)((const char*)c->mp_pin_out.p + b_cnt);
-        const int32_t* h_hf = (const int32_t*)((const char*)c->mp_pin_out.p + b_cnt + b_hm);
-        if (model_out) std::memcpy(model_out, h_hm, (size_t)n_pairs * 36);
-        if (found_out)
-            for (uint64_t p = 0; p < n_pairs; ++p) found_out[p] = h_hf[p];
-        if (refine && refine->iterations)
-            std::memcpy(refine->iterations, (const char*)c->mp_pin_out.p + b_cnt + b_hm + b_hf, (size_t)n_pairs * 4);
-    }
-    if (timed) {
-        float ms[6] = {};
-        AKZ_HIP_TRY(hipEventElapsedTime(&ms[0], c->mp_split_ev[0], c->mp_split_ev[1]));
-        AKZ_HIP_TRY(hipEventElapsedTime(&ms[1], c->mp_split_ev[1], c->mp_split_ev[2]));
-        AKZ_HIP_TRY(hipEventElapsedTime(&ms[3], c->mp_split_ev[3], c->mp_split_ev[4]));
-        AKZ_HIP_TRY(hipEventElapsedTime(&ms[4], c->mp_split_ev[4], c->mp_split_ev[5]));
-        AKZ_HIP_TRY(hipEventElapsedTime(&ms[5], c->mp_split_ev[5], c->mp_split_ev[6]));
-        for (int k = 0; k < 6; ++k) c->mp_split_ms[k] = ms[k];
-        c->mp_split_ms[2] = t_draw;
-    }
+    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
+    const uint64_t pair[2] = {0, 1};
+    int fnd = 0;
+    float mdl[9] = {};
+    uint32_t it = 0;
+    const RefineStage r{refine_iterations ? *refine_iterations : 0u, &it};
+    AKZ_TRY(match_pairs_impl<Model>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out, mdl, &fnd, g,
+                                    refine_iterations ? &r : nullptr, homography ? Model::kName : name));
+    if (found) *found = fnd;
+    if (m && (fnd || !homography)) std::memcpy(m, mdl, sizeof(mdl));
+    if (iterations) *iterations = it;
     return AKZ_OK;
 }
 }  // namespace
@@ -814,35 +875,6 @@ int akz_match_features_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n
                              akz_match* out, uint64_t* n_out) {
     return match_pairs_impl<FundamentalModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                               out, n_out, nullptr, nullptr);
-}
-
-// the homography RANSAC over many pairs (see the header): the orchestration above with 4-point samples
-int akz_match_features_homography_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                                        uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
-                                        akz_match* out, uint64_t* n_out, float* h, int* found) {
-    return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                             out, n_out, h, found);
-}
-
-// one pair: the pairs call with sets {0, 1} and the pair (0, 1); refusals are those of akz_match_features
-int akz_match_features_homography(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
-                                  const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
-                                  double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out,
-                                  uint64_t* n_out, float* h, int* found) {
-    if (!n_out) return AKZ_ERR_INVALID_ARG;
-    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
-        set_error("match_features_homography: a feature set has more descriptors than keypoints");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
-    const uint64_t pair[2] = {0, 1};
-    int fnd = 0;
-    float hm[9];
-    AKZ_TRY(match_pairs_impl<HomographyModel>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out,
-                                              hm, &fnd));
-    if (found) *found = fnd;
-    if (h && fnd) std::memcpy(h, hm, sizeof(hm));
-    return AKZ_OK;
 }
 
 int akz_debug_match_pairs_split(akz_ctx* c, int enable, double* ms) {
@@ -856,10 +888,13 @@ int akz_debug_match_pairs_split(akz_ctx* c, int enable, double* ms) {
     return AKZ_OK;
 }
 
-}  // extern "C"
-
-extern "C" {
-// the homography call, then the guided scan with the H it found (see the header): the orchestration above with its last stage
+// ---- the homography RANSAC (see the header): 4-point samples; with the guided scan as the last stage; with the refit stage ----
+int akz_match_features_homography_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
+                                        uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
+                                        akz_match* out, uint64_t* n_out, float* h, int* found) {
+    return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                                             out, n_out, h, found);
+}
 int akz_match_features_homography_guided_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
                                                uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
                                                float ransac_epsilon_inliers, float guided_radius, double guided_lowes_ratio, akz_match* out,
@@ -868,33 +903,6 @@ int akz_match_features_homography_guided_pairs(akz_ctx* c, const akz_feature_set
     return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                              out, n_out, h, found, &g);
 }
-int akz_match_features_homography_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
-                                         const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
-                                         double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, float guided_radius,
-                                         double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* h, int* found) {
-    if (!n_out) {
-        set_error("match_features_homography_guided: null n_out");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
-        set_error("match_features_homography_guided: a feature set has more descriptors than keypoints");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
-    const uint64_t pair[2] = {0, 1};
-    const GuidedStage g{guided_radius, guided_lowes_ratio};
-    int fnd = 0;
-    float hm[9];
-    AKZ_TRY(match_pairs_impl<HomographyModel>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out,
-                                              hm, &fnd, &g));
-    if (found) *found = fnd;
-    if (h && fnd) std::memcpy(h, hm, sizeof(hm));
-    return AKZ_OK;
-}
-}  // extern "C"
-
-extern "C" {
-// the homography calls with the refit stage between the pick and the read-back (see the header)
 int akz_match_features_homography_refined_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
                                                 uint64_t n_pairs, uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials,
                                                 float ransac_epsilon_inliers, uint32_t refine_iterations, akz_match* out, uint64_t* n_out,
@@ -913,43 +921,31 @@ int akz_match_features_homography_refined_guided_pairs(akz_ctx* c, const akz_fea
     return match_pairs_impl<HomographyModel>(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                              out, n_out, h, found, &g, &r);
 }
-}  // extern "C"
-namespace {
-// one pair: the pairs call with sets {0, 1} and the pair (0, 1)
-int refined_single(const char* name, akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
-                   const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, double lowes_ratio,
-                   uint64_t ransac_trials, float ransac_epsilon_inliers, uint32_t refine_iterations, const GuidedStage* g, akz_match* out,
-                   uint64_t* n_out, float* h, int* found, uint32_t* iterations) {
-    if (!n_out) {
-        set_error(std::string(name) + "null n_out");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
-        set_error(std::string(name) + "a feature set has more descriptors than keypoints");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
-    const uint64_t pair[2] = {0, 1};
-    int fnd = 0;
-    float hm[9];
-    uint32_t it = 0;
-    const RefineStage r{refine_iterations, &it};
-    AKZ_TRY(match_pairs_impl<HomographyModel>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out, n_out,
-                                              hm, &fnd, g, &r));
-    if (found) *found = fnd;
-    if (h && fnd) std::memcpy(h, hm, sizeof(hm));
-    if (iterations) *iterations = it;
-    return AKZ_OK;
+// (refusals are those of akz_match_features: a null n_out sets no text)
+int akz_match_features_homography(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                  const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                  double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out,
+                                  uint64_t* n_out, float* h, int* found) {
+    if (!n_out) return AKZ_ERR_INVALID_ARG;
+    return match_single<HomographyModel>("match_features_homography: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
+                                         ransac_trials, ransac_epsilon_inliers, nullptr, nullptr, out, n_out, h, found, nullptr);
 }
-}  // namespace
-extern "C" {
+int akz_match_features_homography_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
+                                         const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
+                                         double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, float guided_radius,
+                                         double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* h, int* found) {
+    const GuidedStage g{guided_radius, guided_lowes_ratio};
+    return match_single<HomographyModel>("match_features_homography_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, nullptr, &g, out, n_out, h, found, nullptr);
+}
 int akz_match_features_homography_refined(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
                                           const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
                                           double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
                                           uint32_t refine_iterations, akz_match* out, uint64_t* n_out, float* h, int* found,
                                           uint32_t* iterations) {
-    return refined_single("match_features_homography_refined: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
-                          ransac_trials, ransac_epsilon_inliers, refine_iterations, nullptr, out, n_out, h, found, iterations);
+    return match_single<HomographyModel>("match_features_homography_refined: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, &refine_iterations, nullptr, out, n_out, h, found,
+                                         iterations);
 }
 int akz_match_features_homography_refined_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
                                                  const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1,
@@ -958,41 +954,12 @@ int akz_match_features_homography_refined_guided(akz_ctx* c, const akz_keypoint*
                                                  double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* h, int* found,
                                                  uint32_t* iterations) {
     const GuidedStage g{guided_radius, guided_lowes_ratio};
-    return refined_single("match_features_homography_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
-                          ransac_trials, ransac_epsilon_inliers, refine_iterations, &g, out, n_out, h, found, iterations);
+    return match_single<HomographyModel>("match_features_homography_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, &refine_iterations, &g, out, n_out, h, found,
+                                         iterations);
 }
-}  // extern "C"
 
 // ---- the fundamental matrix handed back, refitted, and guiding (see the header) ---------------------------------------------
-namespace {
-// one pair: the pairs call with sets {0, 1} and the pair (0, 1); refine_iterations / g: null without that stage
-int fundamental_single(const char* name, akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
-                       const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes, double lowes_ratio,
-                       uint64_t ransac_trials, float ransac_epsilon_inliers, const uint32_t* refine_iterations, const GuidedStage* g,
-                       akz_match* out, uint64_t* n_out, float* f, int* found, uint32_t* iterations) {
-    if (!n_out) {
-        set_error(std::string(name) + "null n_out");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    if (n_d0 > n_kp0 || n_d1 > n_kp1) {
-        set_error(std::string(name) + "a feature set has more descriptors than keypoints");
-        return AKZ_ERR_INVALID_ARG;
-    }
-    const akz_feature_set sets[2] = {{kp0, n_kp0, d0, n_d0}, {kp1, n_kp1, d1, n_d1}};
-    const uint64_t pair[2] = {0, 1};
-    int fnd = 0;
-    float fm[9] = {};
-    uint32_t it = 0;
-    const RefineStage r{refine_iterations ? *refine_iterations : 0u, &it};
-    AKZ_TRY(match_pairs_impl<FundamentalModelOut>(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, ransac_trials, ransac_epsilon_inliers, out,
-                                                  n_out, fm, &fnd, g, refine_iterations ? &r : nullptr, name));
-    if (found) *found = fnd;
-    if (f) std::memcpy(f, fm, sizeof(fm));  // (zeros without a winner, as akz_remove_outliers_fundamental)
-    if (iterations) *iterations = it;
-    return AKZ_OK;
-}
-}  // namespace
-extern "C" {
 int akz_match_features_fundamental_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                                          uint64_t desc_bytes, double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
                                          akz_match* out, uint64_t* n_out, float* f, int* found) {
@@ -1032,24 +999,24 @@ int akz_match_features_fundamental(akz_ctx* c, const akz_keypoint* kp0, uint64_t
                                    const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
                                    double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, akz_match* out, uint64_t* n_out,
                                    float* f, int* found) {
-    return fundamental_single("match_features_fundamental: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
-                              ransac_trials, ransac_epsilon_inliers, nullptr, nullptr, out, n_out, f, found, nullptr);
+    return match_single<FundamentalModelOut>("match_features_fundamental: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                             lowes_ratio, ransac_trials, ransac_epsilon_inliers, nullptr, nullptr, out, n_out, f, found, nullptr);
 }
 int akz_match_features_fundamental_refined(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
                                            const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
                                            double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers,
                                            uint32_t refine_iterations, akz_match* out, uint64_t* n_out, float* f, int* found,
                                            uint32_t* iterations) {
-    return fundamental_single("match_features_fundamental_refined: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
-                              ransac_trials, ransac_epsilon_inliers, &refine_iterations, nullptr, out, n_out, f, found, iterations);
+    return match_single<FundamentalModelOut>("match_features_fundamental_refined: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                             lowes_ratio, ransac_trials, ransac_epsilon_inliers, &refine_iterations, nullptr, out, n_out, f, found, iterations);
 }
 int akz_match_features_fundamental_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
                                           const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1, uint64_t desc_bytes,
                                           double lowes_ratio, uint64_t ransac_trials, float ransac_epsilon_inliers, float guided_radius,
                                           double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* f, int* found) {
     const GuidedStage g{guided_radius, guided_lowes_ratio};
-    return fundamental_single("match_features_fundamental_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes, lowes_ratio,
-                              ransac_trials, ransac_epsilon_inliers, nullptr, &g, out, n_out, f, found, nullptr);
+    return match_single<FundamentalModelOut>("match_features_fundamental_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                             lowes_ratio, ransac_trials, ransac_epsilon_inliers, nullptr, &g, out, n_out, f, found, nullptr);
 }
 int akz_match_features_fundamental_refined_guided(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, const uint8_t* d0, uint64_t n_d0,
                                                   const akz_keypoint* kp1, uint64_t n_kp1, const uint8_t* d1, uint64_t n_d1,
@@ -1058,7 +1025,7 @@ int akz_match_features_fundamental_refined_guided(akz_ctx* c, const akz_keypoint
                                                   double guided_lowes_ratio, akz_match* out, uint64_t* n_out, float* f, int* found,
                                                   uint32_t* iterations) {
     const GuidedStage g{guided_radius, guided_lowes_ratio};
-    return fundamental_single("match_features_fundamental_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
-                              lowes_ratio, ransac_trials, ransac_epsilon_inliers, &refine_iterations, &g, out, n_out, f, found, iterations);
+    return match_single<FundamentalModelOut>("match_features_fundamental_refined_guided: ", c, kp0, n_kp0, d0, n_d0, kp1, n_kp1, d1, n_d1, desc_bytes,
+                                             lowes_ratio, ransac_trials, ransac_epsilon_inliers, &refine_iterations, &g, out, n_out, f, found, iterations);
 }
 }  // extern "C"
