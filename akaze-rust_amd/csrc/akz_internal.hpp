@@ -439,7 +439,7 @@ void match_mfma_multi(hipStream_t s, const uint8_t* q8, const uint32_t* qpop, ui
                       const void* d_table, uint32_t n_chunks, uint32_t threshold, uint32_t* bound, MatchRec* d_out, bool fp4 = false);
 void match_mfma(hipStream_t s, const uint8_t* q8, const uint32_t* qpop, uint32_t n0, const uint8_t* t8, uint32_t n1,
                 uint32_t threshold, uint32_t* bound, uint32_t chunks, MatchRec* d_rec, bool fp4 = false);
-// both directions of a multi-set launch (FP4 form): see k_match_fp4<.., COLS> in akz_match.hip
+// both directions of a multi-set launch (FP4 form): see k_match_fp4<COLS> in akz_match.hip
 struct MatchColSetHost {  // = ColSet of akz_match.hip
     uint32_t row0, rows, out0;
 };

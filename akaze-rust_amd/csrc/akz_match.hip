@@ -28,12 +28,12 @@
 #include <climits>
 #include <cstdlib>
 
+#include "akz_fp4_scan.hpp"
 #include "akz_internal.hpp"
 
 namespace akz {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int KB = 512;            // int8 columns per descriptor (64 bytes x 8 bits)
@@ -332,11 +332,7 @@ __global__ void __launch_bounds__(MM_NT) k_match_mfma(const uint8_t* __restrict_
                 int top = acc[b][0];
 #pragma unroll
                 for (int i = 1; i < 16; ++i) top = max(top, acc[b][i]);
-                #ifdef AKZ_MM_NOSLOW
-                if (partial) {
-#else
                 if (partial || (int)pq[b] - top < (int)limit[b]) {  // rare: see `limit`
-#endif
                     // exact update from the tile's two smallest distances and the first row of the smallest: keys
                     // (acc << 4 | 15 - i) order by accumulator, then by ascending row; top two keys by max3 / med3
                     int key[16];
@@ -399,48 +395,17 @@ __global__ void __launch_bounds__(MM_NT) k_match_mfma(const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same scan on the block-scaled FP4 matrix instruction (gfx950: v_mfma_scale_f32_32x32x64_f8f6f4, twice the K per
-// instruction and per operand byte of the int8 form at the same issue cost).  Operands are the +-1 images of
-// k_unpack_bits(fp4): e2m1 holds +-1 exactly, the block scales are 1 (E8M0 127), and a dot product of 488 terms of +-1 is
-// an integer of magnitude <= 488: the f32 accumulators are exact.  hamming = (488 - dot) / 2.  Structure, tie rule and
-// output are those of k_match_mfma; a train row is 256 bytes, a wave's query operands 32 registers.  What differs since
-// round 4: the exact top-2 update costs what the case needs (see `The exact update` in the kernel), the second-distance
-// bound shared between workgroups is off (AKZ_MM4_BOUND), the one-direction form takes two tiles per barrier (AKZ_MM4_STEP),
-// and a staged half tile goes to LDS before the chain's accumulators are looked at.
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-constexpr int KB4 = KB / 2;           // bytes per unpacked row
-constexpr int MM_PITCH4 = KB4 + 16;   // LDS row pitch: 16-byte operand reads of 16 consecutive rows fall into different banks
-constexpr int kBits = 488;            // columns that carry +-1 (61 bytes)
-constexpr float kPadAcc = -1.0e30f;   // accumulator given to the padding rows of a partial tile (a real one is >= -488)
-constexpr float kPadKey = -1.0e5f;    // ... and what tells their keys 16 acc + (15 - i) from real ones (>= -7808)
+// The same scan on the block-scaled FP4 matrix instruction: the walk of akz_fp4_scan.hpp (operands, tiles, staging and the
+// matrix chain are described there) with the top-2 state of k_match_mfma as its visitor.  hamming = (488 - dot) / 2;
+// structure of the chunks, tie rule and output are those of k_match_mfma.  What differs since round 4: the exact top-2
+// update costs what the case needs (see `The exact update`), and the second-distance bound that the workgroups of a query
+// share in k_match_mfma is not used: with the exact update at that cost it pays only for very large sets (89 816 x 89 816:
+// 1551 -> 1495 us); a 4K pair (61 against 64 us), the multi-set launch of the all-pairs step (478 against 491 us) and the
+// step itself do better without the atomics and the re-reads (profiles/r04_match_mutual.txt).  The `bound` parameter stays
+// in the kernel's signature, unused.
+static_assert(fp4::TR == MM_TR && fp4::QB == MM_QB && fp4::ROW == KB / 2, "both matrix forms share the padded images and the chunk tables");
+constexpr float kPadKey = -1.0e5f;  // tells the keys 16 acc + (15 - i) of padding rows (fp4::kPadAcc) from real ones (>= -7808)
 
-// NB: 32-query blocks per wave.  1 (used): 16 waves of 32 queries (1024 threads); 2: 8 waves of 64 queries (512 threads),
-// every train operand read from LDS feeding two matrix instructions -- measured 30 % SLOWER at 90 K rows (2.36 against
-// 1.80 ms, profiles/r03_match_variants.txt), as for the int8 form: the loop needs its 16 waves.
-#ifndef AKZ_MM4_NB
-#define AKZ_MM4_NB 1
-#endif
-#ifndef AKZ_MM4_NT
-#define AKZ_MM4_NT 1024
-#endif
-// AKZ_MM4_STEP: tiles per barrier of the one-direction form (two LDS buffers of STEP tiles each).
-// AKZ_MM4_BOUND = 1: the workgroups that scan for a query share an upper bound of its second distance (bound[q], as in
-// k_match_mfma; pushed once per tile).  With the exact update at its round-4 cost that pays only for very large sets
-// (89 816 x 89 816: 1551 -> 1495 us); a 4K pair (61 against 64 us), the multi-set launch of the all-pairs step (478 against
-// 491 us) and the step itself do better without the atomics and the re-reads, so it is off (profiles/r04_match_mutual.txt).
-#ifndef AKZ_MM4_STEP
-#define AKZ_MM4_STEP 2
-#endif
-// AKZ_MM4_RING: tiles staged ahead in the both-direction form, one barrier per that many tiles (2: 7.32 -> 7.17 ms for the
-// all-pairs step of 16 x 4K 5x5 frames; the limits a lane compares with are then two tiles old instead of one).
-#ifndef AKZ_MM4_RING
-#define AKZ_MM4_RING 2
-#endif
-#ifndef AKZ_MM4_BOUND
-#define AKZ_MM4_BOUND 0
-#endif
-constexpr int MM4_QB = (AKZ_MM4_NT / 64) * 32 * AKZ_MM4_NB;  // queries per workgroup of the FP4 kernel
 // BOTH DIRECTIONS of a block in one pass (COLS; akz_descriptor_match_sets_mutual_device): hamming is symmetric, so the
 // distances of the queries to a train set are also the distances of that set's rows to the queries, and the match list
 // of the opposite direction (feature_matching.rs:23-94 with the two sets exchanged) needs, for every TRAIN row, the two
@@ -450,7 +415,7 @@ constexpr int MM4_QB = (AKZ_MM4_NT / 64) * 32 * AKZ_MM4_NB;  // queries per work
 //     old = atomicMin(cbest, mine);  atomicMin(csecond, max(old, mine) >> 32)
 // (the second smallest distance is the smallest among the losers of the first exchange; the packed minimum keeps the lowest
 // query among equal distances).  Elements ABOVE the row's current csecond cannot be one of its final two and are skipped:
-// the rows' bounds travel with the tile -- staged one tile ahead into LDS as accumulator limits 488 - 2 csecond (stale
+// the rows' bounds travel with the tile -- staged with it into LDS as accumulator limits 488 - 2 csecond (stale
 // values are only looser) -- and every lane compares its 16 accumulators with the limits of its 16 rows (four 16-byte LDS
 // reads that a whole half-wave shares); only a true candidate leaves the straight-line path.  The state starts from the
 // exact result over the first col_q0 queries (a separate small launch of this kernel with the roles exchanged,
@@ -458,56 +423,182 @@ constexpr int MM4_QB = (AKZ_MM4_NT / 64) * 32 * AKZ_MM4_NB;  // queries per work
 // (Measured on the way, 16 x 4K 5x5 frames, 120 blocks: gate on the loosest bound of a sub-tile + per-candidate bound loads
 // 58 ms; bulk bound loads, chunks rotated against the query blocks, 2048 seed rows 18.5 ms -- of which 7 ms the bound loads
 // and 1.6 ms the atomics; limits in LDS 13.1 ms; compares OR-ed on the scalar unit 12.5 ms; candidates found by scalar
-// masks, losers settled after the next commit 8.8 ms; lead images on two streams 7.3 ms.  A third of the sub-tiles hold a
-// candidate -- 3.3 per train row and lead image, as 2 ln(rows / seed rows) says -- and what one costs is the time its wave
-// keeps the workgroup waiting at the tile's barrier: profiles/r04_match_mutual.txt.)
-template <int NB, int NT, bool COLS = false>
-__global__ void __launch_bounds__(NT) k_match_fp4(const uint8_t* __restrict__ q4, unsigned n0, const uint8_t* __restrict__ t4,
-                                                  unsigned n1, unsigned chunk_tiles, unsigned threshold,
-                                                  unsigned* __restrict__ bound, MatchRec* __restrict__ out,
-                                                  const MatchChunk* __restrict__ table,
-                                                  unsigned long long* __restrict__ cbest = nullptr,
-                                                  unsigned* __restrict__ csecond = nullptr, unsigned col_q0 = 0) {
-    constexpr int QB = (NT / 64) * 32 * NB;
-    // (12 waves -- NT = 768, one or two query blocks per wave -- measured in round 4: 2.68 / 2.44 ms against 1.80 at 90 K rows,
-    //  profiles/r04_match_mutual.txt: the loop wants its 16 waves; that form is not maintained)
-    static_assert(MM_SUB == 4 && (NB == 1 || NB == 2) && (NT == 512 || NT == 1024), "staging below: two 64-row parts per 128-row tile");
-    static_assert(!COLS || NB == 1, "the opposite direction's pending exchange: one query per lane");
-    // Two buffers of STEP tiles each: one barrier per STEP tiles (4 STEP sub-tiles).  The waves of a workgroup meet at that
-    // barrier, so a step takes what its slowest wave takes, and what differs between the waves -- exact updates, candidates of
-    // the opposite direction -- averages out over more sub-tiles (round 4, profiles/r04_match_mutual.txt).
-    // (two tiles per step: 89 816 x 89 816 1596 -> 1557 us, multi-set launch 481 -> 470 us; with the opposite direction one
-    //  tile -- its limits are a step old when they are used, and two tiles cost it 11 spilled registers: 8.8 -> 9.6 ms)
-    constexpr int STEP = (COLS || NT < 1024) ? 1 : AKZ_MM4_STEP, SUBS = MM_SUB * STEP;  // (two 512-thread workgroups per CU: one tile each)
-    // AHEAD (the both-direction form): steps staged ahead in a ring of 2 AHEAD buffers, one barrier per AHEAD steps -- the same
-    // halving of the barriers without the doubled loop body (AKZ_MM4_RING)
-    constexpr int AHEAD = (COLS && STEP == 1 && NT == 1024) ? AKZ_MM4_RING : 1, NBUF = 2 * AHEAD;
-    __shared__ __attribute__((aligned(16))) uint8_t s_tile[NBUF][STEP * MM_TR * MM_PITCH4];
-    __shared__ __attribute__((aligned(16))) float s_lim[NBUF][COLS ? STEP * MM_TR : 4];  // COLS: accumulator limits of the rows
+// masks, losers settled after the next commit 8.8 ms; lead images on two streams 7.3 ms.  Of the 7.3 ms the pass without the
+// candidates takes 6.7 and without the compares too 6.55: the 16 compares + scalar ORs are 0.14 ms.  A third of the
+// sub-tiles hold a candidate -- 3.3 per train row and lead image, as 2 ln(rows / seed rows) says -- and what one costs is the
+// time its wave keeps the workgroup waiting at the tile's barrier: profiles/r04_match_mutual.txt.)
+constexpr int kColsStep = 1, kColsNbuf = 2 * fp4::kRingBothWays;
+
+// What the both-direction visitor holds beyond the top-2 state (nothing in the one-direction form).
+template <bool COLS>
+struct ColsState {};
+template <>
+struct ColsState<true> {
+    float (*s_lim)[kColsStep * fp4::TR];  // accumulator limits of the rows of every LDS buffer
+    unsigned long long* cbest;
+    unsigned* csecond;
+    unsigned tid, h, q, n0, col_q0, row0, n1;  // (the hooks and the candidates need the lane and the chunk: the walk hands them only j0)
+    unsigned long long lim_lo, lim_hi;  // csecond of rows 4 tid .. 4 tid + 3 of the tile being staged (tid < 32)
+    // the lane's last exchange with a train row's cbest whose loser has not been entered in csecond yet
+    unsigned long long pend_old;
+    unsigned pend_d, pend_row;
+};
+
+// The walk's visitor: a lane's top-2 over its rows of the chunk and, with COLS, the opposite direction's candidates.
+template <bool COLS>
+struct Top2 : fp4::Visitor {
+    unsigned threshold, min_d, second, min_j;
+    unsigned limit;  // always equals `second` without the shared bound; kept apart because folding it changes the instruction stream
+    ColsState<COLS> c;
+
+    __device__ __forceinline__ void settle() {
+        if constexpr (COLS) {
+            if (c.pend_row != 0xffffffffu) {
+                const unsigned long long mine = ((unsigned long long)c.pend_d << 32) | c.q;
+                const unsigned loser = (unsigned)((c.pend_old > mine ? c.pend_old : mine) >> 32);
+                if (loser < threshold) atomicMin(c.csecond + c.pend_row, loser);
+                c.pend_row = 0xffffffffu;
+            }
+        }
+    }
+    __device__ __forceinline__ void committed() { settle(); }
+    __device__ __forceinline__ void tile_fetch(unsigned tile, int part) {  // the bounds of a tile's 128 rows come with its first part
+        if constexpr (COLS) {
+            if (c.tid < 32u) {
+                const unsigned long long* src =
+                    reinterpret_cast<const unsigned long long*>(c.csecond + (size_t)tile * fp4::TR + 64u * part + 4u * c.tid);
+                c.lim_lo = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                c.lim_hi = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+    __device__ __forceinline__ void tile_commit(int buf, int part, unsigned tile) {
+        if constexpr (COLS) {
+            if (c.tid < 32u) {
+                const unsigned sec[4] = {(unsigned)c.lim_lo, (unsigned)(c.lim_lo >> 32), (unsigned)c.lim_hi, (unsigned)(c.lim_hi >> 32)};
+                float4 lim;
+                float* lp = &lim.x;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned row = tile * fp4::TR + 64u * part - c.row0 + 4u * c.tid + (unsigned)k;  // row of the set: padding rows never take part
+                    lp[k] = row < c.n1 ? (float)(fp4::kBits - 2 * (int)min(sec[k], 1000u)) : 1e9f;
+                }
+                *reinterpret_cast<float4*>(&c.s_lim[buf][64u * part + 4u * c.tid]) = lim;
+            }
+        }
+    }
+    __device__ __forceinline__ void sub_tile(const v16f& acc, unsigned j0, int buf, int sub) {
+        float topf = acc[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) topf = fmaxf(topf, acc[i]);
+        // the smallest distance of the lane's 16 rows (the accumulators are 488 - 2 d: the half is exact; as a float, so
+        // that 16 padding rows stay above any threshold)
+        const float bestf = ((float)fp4::kBits - topf) * 0.5f;
+        if constexpr (COLS) {
+            // the limits of the lane's 16 rows (four groups of four consecutive rows, shared by the half-wave)
+            const float* lp = &c.s_lim[buf][32 * sub + 4 * c.h];
+            float lim[16];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const float4 v = *reinterpret_cast<const float4*>(lp + 8 * g4);
+                lim[4 * g4] = v.x; lim[4 * g4 + 1] = v.y; lim[4 * g4 + 2] = v.z; lim[4 * g4 + 3] = v.w;
+            }
+            // One compare per accumulator; the 16 lane masks stay on the scalar unit.  A sub-tile with a candidate
+            // (30..60 % of them: 1024 pairs at 2 / samples-so-far each) is then scanned mask by mask with scalar
+            // branches, and only the accumulator that holds one is looked at by its lanes.  (Round 4: as a per-lane
+            // loop over the 16 accumulators -- compare, branch, execution mask each -- the scan was 2.5 ms of the
+            // 10.3 ms all-pairs step; `hit = hit || ...` had the compiler build a 16-bit mask per lane out of ~50
+            // vector instructions on every sub-tile.)
+            unsigned long long hit[16], any = 0ull;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                hit[i] = __ballot(acc[i] >= lim[i]);
+                any |= hit[i];
+            }
+            const bool q_live = c.q >= c.col_q0 && c.q < c.n0;
+            const unsigned p0 = c.row0 + j0;  // j0 as a row of the padded image
+            const unsigned long long live = __ballot(q_live);
+            if ((any & live) != 0ull) {  // a row of the sub-tile may take one of the wave's queries as one of its two nearest
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    // (wave-uniform tests, four accumulators at a time first: a scan of sixteen dependent scalar
+                    //  compare-and-branch steps was ~300 cycles that the wave's workgroup then waited for at the barrier)
+                    if (((hit[4 * g4] | hit[4 * g4 + 1] | hit[4 * g4 + 2] | hit[4 * g4 + 3]) & live) == 0ull) continue;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = 4 * g4 + k;
+                        if ((hit[i] & live) == 0ull) continue;
+                        if (acc[i] >= lim[i] && q_live) {
+                            const unsigned d = (unsigned)((fp4::kBits - (int)acc[i]) >> 1);
+                            if (d < threshold) {
+                                const unsigned prow = p0 + fp4::lane_row(i);
+                                // (the exchange's answer is looked at after the next commit, or when the lane's next
+                                //  candidate comes first: a wave that waited for it here held its workgroup at the barrier)
+                                if (__ballot(c.pend_row != 0xffffffffu) != 0ull) settle();
+                                const unsigned long long mine = ((unsigned long long)d << 32) | c.q;
+                                c.pend_old = atomicMin(c.cbest + prow, mine);
+                                c.pend_d = d;
+                                c.pend_row = prow;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        // The exact update.  best < limit <= second: the lane's 16 rows improve its second distance at least (a sub-tile
+        // whose best distance is >= limit changes nothing that matters).  Unless they also hold a new minimum that is all
+        // there is to do; a new minimum needs the row of the first largest accumulator and the second largest one: keys
+        // 16 acc + (15 - i), exact in fp32, through a top-2 network of v_max3 / v_med3 (~58 instructions, for about a third
+        // of the sub-tiles).  The SIMD's vector issue is what the loop runs out of next to its matrix instructions (one
+        // MFMA holds it for 8 of its 32 cycles, every other instruction for 4): the former body -- integer keys and the
+        // padding tests of a partial tile on every entry, ~110 instructions for 47..95 % of the sub-tiles -- cost 12 % of
+        // the kernel at 89 816 x 89 816 and 22 % in the multi-set launch (round 4, profiles/r04_match_mutual.txt).
+        if (bestf < (float)limit) {
+            const unsigned tb = (unsigned)bestf, before = second;
+            if (tb < min_d) {
+                float key[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) key[i] = __builtin_fmaf(acc[i], 16.0f, (float)(15 - i));
+                float M = __builtin_fmaxf(key[0], key[1]), S = __builtin_fminf(key[0], key[1]);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float ka = key[2 + 3 * g], kb = key[3 + 3 * g], kc = key[4 + 3 * g];
+                    const float gm = __builtin_fmaxf(ka, __builtin_fmaxf(kb, kc)), gs = __builtin_amdgcn_fmed3f(ka, kb, kc);
+                    S = __builtin_fmaxf(__builtin_fminf(M, gm), __builtin_fmaxf(S, gs));
+                    M = __builtin_fmaxf(M, gm);
+                }
+                {
+                    const float gm = __builtin_fmaxf(key[14], key[15]), gs = __builtin_fminf(key[14], key[15]);
+                    S = __builtin_fmaxf(__builtin_fminf(M, gm), __builtin_fmaxf(S, gs));
+                    M = __builtin_fmaxf(M, gm);
+                }
+                const int i1 = 15 - ((int)M & 15);
+                const unsigned ts = S < kPadKey ? 0xffffffffu : (unsigned)((fp4::kBits - ((int)S >> 4)) >> 1);
+                second = min(min_d, ts);
+                min_d = tb;
+                min_j = j0 + fp4::lane_row(i1);
+            } else {
+                second = tb;
+            }
+            if (second < before) limit = min(limit, second);
+        }
+    }
+};
+
+// blockIdx.x: 512 queries; blockIdx.y: a chunk, as for k_match_mfma (whose records it writes); q4 / t4: the FP4 images.
+template <bool COLS = false>
+__global__ void __launch_bounds__(fp4::NT) k_match_fp4(const uint8_t* __restrict__ q4, unsigned n0, const uint8_t* __restrict__ t4,
+                                                       unsigned n1, unsigned chunk_tiles, unsigned threshold,
+                                                       unsigned* __restrict__ bound, MatchRec* __restrict__ out,
+                                                       const MatchChunk* __restrict__ table,
+                                                       unsigned long long* __restrict__ cbest = nullptr,
+                                                       unsigned* __restrict__ csecond = nullptr, unsigned col_q0 = 0) {
+    __shared__ __attribute__((aligned(16))) float s_lim[COLS ? kColsNbuf : 1][kColsStep * fp4::TR];
     const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const unsigned r = lane & 31u, h = lane >> 5;
-    const unsigned q_first = blockIdx.x * QB + wave * 32u * NB;
-    auto op = [](v4i x) { return v8i{x.x, x.y, x.z, x.w, 0, 0, 0, 0}; };  // FP4 operands occupy the first four registers
-
-    v4i bq[NB][8];  // B operands: the wave's queries, eight K-steps of 64 columns, resident for the whole chunk
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const uint8_t* row = q4 + (size_t)(q_first + 32 * b + r) * KB4 + 16 * h;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) bq[b][s] = *reinterpret_cast<const v4i*>(row + 32 * s);
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int s = 0; s < 8; ++s) asm volatile("" : "+v"(bq[b][s]));
-    unsigned min_d[NB], second[NB], limit[NB], b_seen[NB], pushed[NB], min_j[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        min_d[b] = second[b] = limit[b] = b_seen[b] = pushed[b] = threshold;
-        min_j[b] = 0u;
-    }
-    (void)pushed;
-    (void)bound;  // (AKZ_MM4_BOUND 0)
+    const unsigned q = blockIdx.x * fp4::QB + wave * 32u + r;
+    const fp4::Queries bq = fp4::load_queries(q4, q, h);
+    (void)bound;
 
     unsigned t_begin, t_end, row0 = 0u, record = blockIdx.y;
     if (table) {
@@ -516,290 +607,37 @@ __global__ void __launch_bounds__(NT) k_match_fp4(const uint8_t* __restrict__ q4
         const unsigned chunk = COLS ? (blockIdx.y + blockIdx.x * 7u) % gridDim.y : blockIdx.y;
         const MatchChunk ck = table[chunk];
         t_begin = ck.t_begin; t_end = ck.t_end; row0 = ck.row0; n1 = ck.n_rows; record = ck.record;
-        bound += ck.bound_off;
     } else {
         const unsigned tiles_total = (n1 + MM_TR - 1) / MM_TR;
         t_begin = blockIdx.y * chunk_tiles;
         t_end = min(tiles_total, t_begin + chunk_tiles);
     }
-    // staging: the next step's tiles arrive in 64-row parts (1024 sixteen-byte pieces each) through one register stage:
-    // part p requested before chain 2 p, handed to the other LDS buffer after chain 2 p + 1 has been issued
-    constexpr int PIECES = (1024 + NT - 1) / NT;
-    constexpr bool EXACT = PIECES * NT == 1024;  // (768 threads: the second piece exists for the first 256 only)
-    unsigned st_src[PIECES], st_dst[PIECES];
-#pragma unroll
-    for (int p = 0; p < PIECES; ++p) {
-        const unsigned idx = min(tid + (unsigned)p * NT, 1023u);  // (a surplus thread repeats piece 1023: same bytes, same place)
-        st_src[p] = (idx >> 4) * KB4 + (idx & 15u) * 16u;
-        st_dst[p] = (idx >> 4) * MM_PITCH4 + (idx & 15u) * 16u;
+    Top2<COLS> v;
+    v.threshold = v.min_d = v.second = v.limit = threshold;
+    v.min_j = 0u;
+    if constexpr (COLS) {
+        v.c.s_lim = s_lim; v.c.cbest = cbest; v.c.csecond = csecond;
+        v.c.tid = tid; v.c.h = h; v.c.q = q; v.c.n0 = n0; v.c.col_q0 = col_q0; v.c.row0 = row0; v.c.n1 = n1;
+        v.c.lim_lo = v.c.lim_hi = v.c.pend_old = 0ull;
+        v.c.pend_d = 0u; v.c.pend_row = 0xffffffffu;
     }
-    (void)EXACT;
-    uint4 stage[PIECES];
-    unsigned long long lim_lo = 0, lim_hi = 0;  // COLS: csecond of rows 4 tid .. 4 tid + 3 of the tile being staged (tid < 32)
-    // COLS: the lane's last exchange with a train row's cbest whose loser has not been entered in csecond yet
-    unsigned long long pend_old = 0ull;
-    unsigned pend_d = 0u, pend_row = 0xffffffffu;
-#ifdef AKZ_MM_COUNT
-    __shared__ unsigned s_count[4];
-    if (tid < 4) s_count[tid] = 0;
-#endif
-    auto settle = [&]() {
-        if constexpr (COLS) {
-            if (pend_row != 0xffffffffu) {
-#ifdef AKZ_MM_COUNT
-                if (pend_old > (((unsigned long long)pend_d << 32) | (q_first + r))) atomicAdd(&s_count[2], 1u);
-#endif
-                const unsigned long long mine = ((unsigned long long)pend_d << 32) | (q_first + r);
-                const unsigned loser = (unsigned)((pend_old > mine ? pend_old : mine) >> 32);
-                if (loser < threshold) atomicMin(csecond + pend_row, loser);
-                pend_row = 0xffffffffu;
-            }
-        }
-    };
-    auto fetch = [&](unsigned tile, int part) {
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p)
-            stage[p] = *reinterpret_cast<const uint4*>(t4 + ((size_t)tile * MM_TR + 64u * part) * KB4 + st_src[p]);
-        if constexpr (COLS) {
-            if ((part & 1) == 0 && tid < 32u) {  // (the bounds of a tile's 128 rows come with its first part)
-                const unsigned long long* src =
-                    reinterpret_cast<const unsigned long long*>(csecond + (size_t)tile * MM_TR + 64u * part + 4u * tid);
-                lim_lo = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                lim_hi = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    };
-    auto commit = [&](int buf, int part, unsigned tile) {
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p) *reinterpret_cast<uint4*>(&s_tile[buf][64 * part * MM_PITCH4 + st_dst[p]]) = stage[p];
-        if constexpr (COLS) {
-            if ((part & 1) == 0 && tid < 32u) {
-                const unsigned sec[4] = {(unsigned)lim_lo, (unsigned)(lim_lo >> 32), (unsigned)lim_hi, (unsigned)(lim_hi >> 32)};
-                float4 lim;
-                float* lp = &lim.x;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const unsigned row = tile * MM_TR + 64u * part - row0 + 4u * tid + (unsigned)k;  // row of the set: padding rows never take part
-                    lp[k] = row < n1 ? (float)(kBits - 2 * (int)min(sec[k], 1000u)) : 1e9f;
-                }
-                *reinterpret_cast<float4*>(&s_lim[buf][64u * part + 4u * tid]) = lim;
-            }
-        }
-    };
-#pragma unroll
-    for (int ah = 0; ah < AHEAD; ++ah) {
-        const unsigned t0 = t_begin + (unsigned)(ah * STEP);
-        if (t0 < t_end) {
-#pragma unroll
-            for (int part = 0; part < 2 * STEP; ++part) {
-                if (part < 2 * (int)min((unsigned)STEP, t_end - t0)) {
-                    fetch(t0, part);
-                    commit(ah, part, t0);
-                }
-            }
-        }
+    // one direction: two tiles per barrier; both: one tile per step, two staged ahead (see fp4::kStepOneWay, kRingBothWays)
+    fp4::walk<COLS ? kColsStep : fp4::kStepOneWay, COLS ? fp4::kRingBothWays : 1>(bq, t4, fp4::Chunk{t_begin, t_end, row0, n1}, v);
+    v.settle();
+    // the two lanes of a column hold disjoint row sets: order-free merge, then one record per live query
+    const unsigned o_min = __shfl_xor(v.min_d, 32, 64), o_sec = __shfl_xor(v.second, 32, 64), o_j = __shfl_xor(v.min_j, 32, 64);
+    unsigned m = v.min_d, s2 = v.second, j = v.min_j;
+    if (o_min < m || (o_min == m && o_min < threshold && o_j < j)) {
+        s2 = min(o_sec, m);
+        m = o_min;
+        j = o_j;
+    } else {
+        s2 = min(s2, o_min);
     }
-    __syncthreads();
-    for (unsigned tile = t_begin; tile < t_end; tile += STEP) {
-        const unsigned step = (tile - t_begin) / STEP;
-        const int buf = (int)(step % NBUF), buf_to = (int)((step + AHEAD) % NBUF);
-        const unsigned to = tile + AHEAD * STEP;                                                 // the step staged during this one
-        const unsigned here = min((unsigned)STEP, t_end - tile);                                 // tiles of this step
-        const unsigned next = to < t_end ? min((unsigned)STEP, t_end - to) : 0u;                  // ... and of the one being staged
-#if AKZ_MM4_BOUND > 0
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            limit[b] = min(limit[b], min(second[b], b_seen[b] < 0xffffffffu ? b_seen[b] + 1u : b_seen[b]));
-            if (second[b] < min(pushed[b], b_seen[b])) {  // once per tile, and only what the others do not know yet
-                atomicMin(bound + q_first + 32 * b + r, second[b]);
-                pushed[b] = second[b];
-            }
-            b_seen[b] = __hip_atomic_load(bound + q_first + 32 * b + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#endif
-#pragma unroll
-        for (int sub = 0; sub < SUBS; ++sub) {
-            if (sub >= MM_SUB && (unsigned)sub >= MM_SUB * here) break;  // (uniform: the last step of a chunk may be short)
-            const bool more = (unsigned)(sub >> 1) < 2u * next;          // part sub / 2 of the next step exists
-            const bool partial = (tile + (sub / MM_SUB) + 1) * MM_TR - row0 > n1;  // uniform: only the last tile of the set
-            if (more && (sub & 1) == 0) fetch(to, sub >> 1);  // in flight under the MFMA chains below
-            v16f acc[NB];
-#pragma unroll
-            for (int b = 0; b < NB; ++b)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[b][i] = 0.0f;
-            const uint8_t* arow = &s_tile[buf][(32 * sub + r) * MM_PITCH4 + 16 * h];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const v4i a = *reinterpret_cast<const v4i*>(arow + 32 * s);
-#pragma unroll
-                for (int b = 0; b < NB; ++b)
-                    acc[b] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(op(a), op(bq[b][s]), acc[b], 4, 4, 0, 127, 0, 127);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-#pragma unroll
-            for (int s = 0; s < 8 - 3; ++s) {
-                __builtin_amdgcn_sched_group_barrier(0x008, NB, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, 3 * NB, 0);
-            // The half tile requested before the previous chain goes to LDS while this chain runs, BEFORE its accumulators
-            // are looked at: the wait for the loads is a wait for everything the wave has in flight, the atomics of the
-            // opposite direction included (vmcnt counts them for 600..3000 cycles), and here those are a chain or two old.
-            // Their answers are in by then too: settled without another wait.
-            if ((sub & 1) == 1) {
-                if (more) commit(buf_to, sub >> 1, to);
-                settle();
-            }
-            const unsigned j0 = tile * MM_TR - row0 + 32 * sub + 4 * h;  // row index inside the set
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if (partial) {  // uniform, the last tile of a set: padding rows never match
-#pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        if (j0 + (unsigned)((i & 3) + 8 * (i >> 2)) >= n1) acc[b][i] = kPadAcc;
-                }
-                float topf = acc[b][0];
-#pragma unroll
-                for (int i = 1; i < 16; ++i) topf = fmaxf(topf, acc[b][i]);
-                // the smallest distance of the lane's 16 rows (the accumulators are 488 - 2 d: the half is exact; as a float, so
-                // that 16 padding rows stay above any threshold)
-                const float bestf = ((float)kBits - topf) * 0.5f;
-#ifdef AKZ_MM_COLS_NOCMP  // measurement: the pass without the opposite direction's compares
-                if constexpr (false) {
-#else
-                if constexpr (COLS) {
-#endif
-                    // the limits of the lane's 16 rows (four groups of four consecutive rows, shared by the half-wave)
-                    const float* lp = &s_lim[buf][32 * sub + 4 * h];
-                    float lim[16];
-#pragma unroll
-                    for (int g4 = 0; g4 < 4; ++g4) {
-                        const float4 v = *reinterpret_cast<const float4*>(lp + 8 * g4);
-                        lim[4 * g4] = v.x; lim[4 * g4 + 1] = v.y; lim[4 * g4 + 2] = v.z; lim[4 * g4 + 3] = v.w;
-                    }
-                    // One compare per accumulator; the 16 lane masks stay on the scalar unit.  A sub-tile with a candidate
-                    // (30..60 % of them: 1024 pairs at 2 / samples-so-far each) is then scanned mask by mask with scalar
-                    // branches, and only the accumulator that holds one is looked at by its lanes.  (Round 4: as a per-lane
-                    // loop over the 16 accumulators -- compare, branch, execution mask each -- the scan was 2.5 ms of the
-                    // 10.3 ms all-pairs step; `hit = hit || ...` had the compiler build a 16-bit mask per lane out of ~50
-                    // vector instructions on every sub-tile.)
-                    unsigned long long hit[16], any = 0ull;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        hit[i] = __ballot(acc[b][i] >= lim[i]);
-                        any |= hit[i];
-                    }
-                    const unsigned q = q_first + 32 * b + r;
-                    const bool q_live = q >= col_q0 && q < n0;
-                    const unsigned long long live = __ballot(q_live);
-#ifdef AKZ_MM_COLS_NOHIT  // measurement: the pass without the opposite direction's candidates
-                    any = 0ull;
-#endif
-                    if ((any & live) != 0ull) {  // a row of the sub-tile may take one of the wave's queries as one of its two nearest
-#ifdef AKZ_MM_COUNT
-                        if (lane == 0) atomicAdd(&s_count[0], 1u);
-#endif
-#pragma unroll
-                        for (int g4 = 0; g4 < 4; ++g4) {
-                            // (wave-uniform tests, four accumulators at a time first: a scan of sixteen dependent scalar
-                            //  compare-and-branch steps was ~300 cycles that the wave's workgroup then waited for at the barrier)
-                            if (((hit[4 * g4] | hit[4 * g4 + 1] | hit[4 * g4 + 2] | hit[4 * g4 + 3]) & live) == 0ull) continue;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const int i = 4 * g4 + k;
-                                if ((hit[i] & live) == 0ull) continue;
-                                if (acc[b][i] >= lim[i] && q_live) {
-                                    const unsigned d = (unsigned)((kBits - (int)acc[b][i]) >> 1);
-                                    if (d < threshold) {
-                                        const size_t prow = (size_t)tile * MM_TR + 32u * sub + 4u * h + (unsigned)((i & 3) + 8 * (i >> 2));
-#ifdef AKZ_MM_COLS_NOATOMIC  // measurement: candidates found, nothing entered
-                                        if (d == 0xdeadbeefu) csecond[prow] = d;
-#else
-                                        // (the exchange's answer is looked at after the next commit, or when the lane's next
-                                        //  candidate comes first: a wave that waited for it here held its workgroup at the barrier)
-#ifdef AKZ_MM_COUNT
-                                        atomicAdd(&s_count[1], 1u);
-                                        if (d < csecond[prow]) atomicAdd(&s_count[3], 1u);
-#endif
-                                        if (__ballot(pend_row != 0xffffffffu) != 0ull) settle();
-                                        const unsigned long long mine = ((unsigned long long)d << 32) | q;
-                                        pend_old = atomicMin(cbest + prow, mine);
-                                        pend_d = d;
-                                        pend_row = (unsigned)prow;
-#endif
-                                    }
-                                }
-                            }
-                        }
-                    }
-                }
-                // The exact update.  best < limit <= second: the lane's 16 rows improve its second distance at least (see `limit`
-                // in k_match_mfma).  Unless they also hold a new minimum that is all there is to do; a new minimum needs the
-                // row of the first largest accumulator and the second largest one: keys 16 acc + (15 - i), exact in fp32,
-                // through a top-2 network of v_max3 / v_med3 (~58 instructions, for about a third of the sub-tiles).  The
-                // SIMD's vector issue is what the loop runs out of next to its matrix instructions (one MFMA holds it for 8
-                // of its 32 cycles, every other instruction for 4): the former body -- integer keys and the padding tests of
-                // a partial tile on every entry, ~110 instructions for 47..95 % of the sub-tiles -- cost 12 % of the kernel
-                // at 89 816 x 89 816 and 22 % in the multi-set launch (round 4, profiles/r04_match_mutual.txt).
-                if (bestf < (float)limit[b]) {
-                    const unsigned tb = (unsigned)bestf, before = second[b];
-                    if (tb < min_d[b]) {
-                        float key[16];
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) key[i] = __builtin_fmaf(acc[b][i], 16.0f, (float)(15 - i));
-                        float M = __builtin_fmaxf(key[0], key[1]), S = __builtin_fminf(key[0], key[1]);
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const float ka = key[2 + 3 * g], kb = key[3 + 3 * g], kc = key[4 + 3 * g];
-                            const float gm = __builtin_fmaxf(ka, __builtin_fmaxf(kb, kc)), gs = __builtin_amdgcn_fmed3f(ka, kb, kc);
-                            S = __builtin_fmaxf(__builtin_fminf(M, gm), __builtin_fmaxf(S, gs));
-                            M = __builtin_fmaxf(M, gm);
-                        }
-                        {
-                            const float gm = __builtin_fmaxf(key[14], key[15]), gs = __builtin_fminf(key[14], key[15]);
-                            S = __builtin_fmaxf(__builtin_fminf(M, gm), __builtin_fmaxf(S, gs));
-                            M = __builtin_fmaxf(M, gm);
-                        }
-                        const int i1 = 15 - ((int)M & 15);
-                        const unsigned ts = S < kPadKey ? 0xffffffffu : (unsigned)((kBits - ((int)S >> 4)) >> 1);
-                        second[b] = min(min_d[b], ts);
-                        min_d[b] = tb;
-                        min_j[b] = j0 + (unsigned)((i1 & 3) + 8 * (i1 >> 2));
-                    } else {
-                        second[b] = tb;
-                    }
-                    if (second[b] < before) {
-                        limit[b] = min(limit[b], second[b]);
-                    }
-                }
-            }
-        }
-        if (AHEAD == 1 || step % AHEAD == AHEAD - 1 || tile + STEP >= t_end) __syncthreads();  // (uniform)
-    }
-    settle();
-#ifdef AKZ_MM_COUNT
-    __syncthreads();
-    if (COLS && tid == 0)
-        printf("COUNT %u %u %u %u %u\n", (t_end - t_begin) * 4u * 16u, s_count[0], s_count[1], s_count[2], s_count[3]);
-#endif
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const unsigned o_min = __shfl_xor(min_d[b], 32, 64), o_sec = __shfl_xor(second[b], 32, 64), o_j = __shfl_xor(min_j[b], 32, 64);
-        unsigned m = min_d[b], s2 = second[b], j = min_j[b];
-        if (o_min < m || (o_min == m && o_min < threshold && o_j < j)) {
-            s2 = min(o_sec, m);
-            m = o_min;
-            j = o_j;
-        } else {
-            s2 = min(s2, o_min);
-        }
-        const unsigned q = q_first + 32 * b + r;
-        if (h == 0 && q < n0) {
-            MatchRec rec;
-            rec.min_d = m; rec.second_d = s2; rec.min_j = j; rec._pad = 0;
-            out[(size_t)record * n0 + q] = rec;
-        }
+    if (h == 0 && q < n0) {
+        MatchRec rec;
+        rec.min_d = m; rec.second_d = s2; rec.min_j = j; rec._pad = 0;
+        out[(size_t)record * n0 + q] = rec;
     }
 }
 
@@ -881,7 +719,7 @@ namespace launch {
 
 // rows of the unpacked image of a set of n descriptors (queries: whole workgroups; train: whole tiles)
 uint32_t match_mfma_rows(uint32_t n, bool queries) {
-    const uint32_t m = queries ? (uint32_t)std::max(MM_QB, MM4_QB) : (uint32_t)MM_TR;
+    const uint32_t m = queries ? (uint32_t)MM_QB : (uint32_t)MM_TR;
     return (std::max<uint32_t>(n, 1) + m - 1) / m * m;
 }
 uint32_t match_mfma_chunks(uint32_t n0, uint32_t n1, uint32_t forced) {
@@ -956,7 +794,7 @@ void match_mfma_multi(hipStream_t s, const uint8_t* q8, const uint32_t* qpop, ui
                       const void* d_table, uint32_t n_chunks, uint32_t threshold, uint32_t* bound, MatchRec* d_out, bool fp4) {
     if (n0 == 0 || n_chunks == 0) return;
     if (fp4) {
-        hipLaunchKernelGGL((k_match_fp4<AKZ_MM4_NB, AKZ_MM4_NT>), dim3((n0 + MM4_QB - 1) / MM4_QB, n_chunks), dim3(AKZ_MM4_NT), 0, s, q8, n0, t8, 0u, 0u,
+        hipLaunchKernelGGL((k_match_fp4<>), dim3((n0 + fp4::QB - 1) / fp4::QB, n_chunks), dim3(fp4::NT), 0, s, q8, n0, t8, 0u, 0u,
                            threshold, bound, d_out, reinterpret_cast<const MatchChunk*>(d_table));
         return;
     }
@@ -975,11 +813,8 @@ void match_cols_seed(hipStream_t s, const uint8_t* q4, uint32_t n0, const uint8_
                      uint32_t* d_bound, MatchRec* d_seed, unsigned long long* cbest, uint32_t* csecond) {
     const uint32_t seed = match_cols_seed_rows(n0);
     if (t_rows == 0) return;
-#if AKZ_MM4_BOUND
-    (void)hipMemsetAsync(d_bound, 0xff, (size_t)match_mfma_rows(t_rows, true) * sizeof(uint32_t), s);  // no pruning bound yet
-#endif
     const uint32_t tiles = (std::max<uint32_t>(seed, 1) + MM_TR - 1) / MM_TR;
-    hipLaunchKernelGGL((k_match_fp4<AKZ_MM4_NB, AKZ_MM4_NT>), dim3((t_rows + MM4_QB - 1) / MM4_QB, 1), dim3(AKZ_MM4_NT), 0, s, t4, t_rows, q4,
+    hipLaunchKernelGGL((k_match_fp4<>), dim3((t_rows + fp4::QB - 1) / fp4::QB, 1), dim3(fp4::NT), 0, s, t4, t_rows, q4,
                        seed, tiles, threshold, d_bound, d_seed, (const MatchChunk*)nullptr, (unsigned long long*)nullptr,
                        (unsigned*)nullptr, 0u);
     hipLaunchKernelGGL(k_cols_init, dim3((t_rows + 255) / 256), dim3(256), 0, s, d_seed, t_rows, cbest, csecond);
@@ -988,7 +823,7 @@ void match_cols_seed(hipStream_t s, const uint8_t* q4, uint32_t n0, const uint8_
 void match_fp4_multi_mutual(hipStream_t s, const uint8_t* q4, uint32_t n0, const uint8_t* t4, const void* d_table, uint32_t n_chunks,
                             uint32_t threshold, uint32_t* bound, MatchRec* d_out, unsigned long long* cbest, uint32_t* csecond) {
     if (n0 == 0 || n_chunks == 0) return;
-    hipLaunchKernelGGL((k_match_fp4<AKZ_MM4_NB, AKZ_MM4_NT, true>), dim3((n0 + MM4_QB - 1) / MM4_QB, n_chunks), dim3(AKZ_MM4_NT), 0, s, q4, n0,
+    hipLaunchKernelGGL((k_match_fp4<true>), dim3((n0 + fp4::QB - 1) / fp4::QB, n_chunks), dim3(fp4::NT), 0, s, q4, n0,
                        t4, 0u, 0u, threshold, bound, d_out, reinterpret_cast<const MatchChunk*>(d_table), cbest, csecond,
                        match_cols_seed_rows(n0));
 }
@@ -1005,7 +840,7 @@ void match_mfma(hipStream_t s, const uint8_t* q8, const uint32_t* qpop, uint32_t
     const uint32_t tiles = (std::max<uint32_t>(n1, 1) + MM_TR - 1) / MM_TR;
     const uint32_t chunk_tiles = (tiles + chunks - 1) / chunks;
     if (fp4) {
-        hipLaunchKernelGGL((k_match_fp4<AKZ_MM4_NB, AKZ_MM4_NT>), dim3((n0 + MM4_QB - 1) / MM4_QB, chunks), dim3(AKZ_MM4_NT), 0, s, q8, n0, t8, n1,
+        hipLaunchKernelGGL((k_match_fp4<>), dim3((n0 + fp4::QB - 1) / fp4::QB, chunks), dim3(fp4::NT), 0, s, q8, n0, t8, n1,
                            chunk_tiles, threshold, bound, d_rec, (const MatchChunk*)nullptr);
         return;
     }
