@@ -998,6 +998,47 @@ ref_result* ref_extract_u8(const uint8_t* img, int w, int h, const ref_config* c
     for (size_t i = 0; i < im.px.size(); ++i) im.px[i] = float(img[i]) * 1.0f / 255.0f;
     return akref::extract(im, to_cfg(cfg), threads);
 }
+// the plane size of level lvl of allocate_evolutions(w, h, cfg) with the chained half_size of lib.rs:80-90; -1 beyond the last
+int ref_plan_level_size(int w, int h, const ref_config* cfg, uint64_t lvl, uint32_t* lw, uint32_t* lh) {
+    std::vector<akref::Evolution> ev;
+    if (!akref::allocate_evolutions(uint32_t(w), uint32_t(h), to_cfg(cfg), ev) || lvl >= ev.size()) return -1;
+    *lw = uint32_t(w) >> ev[size_t(lvl)].octave;
+    *lh = uint32_t(h) >> ev[size_t(lvl)].octave;
+    return 0;
+}
+// detect_keypoints + extract_descriptors on evolutions the CALLER holds [ref: scale_space_extrema.rs:199-203,
+// descriptors.rs:14-27]: planes = n_levels x 10 pointers in the plane order below (row-major f32 of the level's size,
+// NULL where the caller has nothing; Lt, Lx, Ly, Ldet of every level are required), the table of akz_extract_from_planes.
+ref_result* ref_detect_from_planes(int w, int h, const ref_config* cfg, const float* const* planes, uint64_t n_levels) {
+    auto* r = new akref::Result;
+    r->cfg = to_cfg(cfg);
+    if (!planes || !akref::allocate_evolutions(uint32_t(w), uint32_t(h), r->cfg, r->ev) || r->ev.size() != n_levels) {
+        delete r;
+        return nullptr;
+    }
+    int lw = w, lh = h;
+    for (size_t l = 0; l < r->ev.size(); ++l) {
+        auto& e = r->ev[l];
+        if (l > 0 && e.octave > r->ev[l - 1].octave) {  // the chained half_size of lib.rs:80-90
+            lw /= 2;
+            lh /= 2;
+        }
+        akref::Image* im[10] = {&e.Lt, &e.Lsmooth, &e.Lx, &e.Ly, &e.Lxx, &e.Lyy, &e.Lxy, &e.Lflow, &e.Lstep, &e.Ldet};
+        for (int p = 0; p < 10; ++p)
+            if (planes[l * 10 + p]) *im[p] = to_img(planes[l * 10 + p], lw, lh);
+        if (e.Lt.px.empty() || e.Lx.px.empty() || e.Ly.px.empty() || e.Ldet.px.empty()) {
+            delete r;
+            return nullptr;
+        }
+    }
+    std::vector<akref::Keypoint> ext = akref::find_scale_space_extrema(r->ev, r->cfg);
+    r->n_extrema = ext.size();
+    r->kps = akref::do_subpixel_refinement(ext, r->ev);
+    const size_t nb = akref::descriptor_bytes(r->cfg);
+    r->desc.assign(r->kps.size() * nb, 0);
+    for (size_t i = 0; i < r->kps.size(); ++i) akref::get_mldb_descriptor(r->kps[i], r->ev, r->cfg, &r->desc[i * nb]);
+    return r;
+}
 void ref_result_free(ref_result* r) { delete r; }
 uint64_t ref_result_num_levels(const ref_result* r) { return r->ev.size(); }
 uint64_t ref_result_num_keypoints(const ref_result* r) { return r->kps.size(); }

@@ -282,6 +282,33 @@ def extract(img, cfg=None, threads=1):
     return RefResult(hdl)
 
 
+def detect_from_planes(w, h, planes, cfg=None):
+    """detect_keypoints + extract_descriptors on evolutions the caller holds: planes[level][name] -> 2-D float32 array (names
+    of PLANES; missing ones are skipped; Lt, Lx, Ly and Ldet are required), as akaze_amd.Context.extract_from_planes takes them."""
+    cfg = cfg or default_config()
+    keep = []
+    tab = (C.c_void_p * (len(planes) * 10))()
+    size = lib().ref_plan_level_size
+    size.argtypes = [C.c_int, C.c_int, C.POINTER(RefConfig), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    for l, lv in enumerate(planes):
+        lw, lh = C.c_uint32(), C.c_uint32()
+        if size(w, h, C.byref(cfg), l, C.byref(lw), C.byref(lh)) != 0:
+            raise ValueError(f"level {l}: more evolutions than allocate_evolutions gives")
+        for p, name in enumerate(PLANES):
+            a = lv.get(name)
+            if a is None or a.size == 0:
+                continue
+            a = np.ascontiguousarray(a, np.float32)
+            if a.shape != (lh.value, lw.value):  # (the library copies lw * lh floats from it)
+                raise ValueError(f"level {l} plane {name}: shape {a.shape}, the level is {(lh.value, lw.value)}")
+            keep.append(a)
+            tab[l * 10 + p] = a.ctypes.data
+    fn = lib().ref_detect_from_planes
+    fn.argtypes = [C.c_int, C.c_int, C.POINTER(RefConfig), C.POINTER(C.c_void_p), C.c_uint64]
+    fn.restype = C.c_void_p
+    return RefResult(fn(w, h, C.byref(cfg), tab, len(planes)))
+
+
 def descriptor_match(d0, d1, distance_threshold=10000, lowes_ratio=0.86):
     d0 = np.ascontiguousarray(d0, np.uint8)
     d1 = np.ascontiguousarray(d1, np.uint8)
