@@ -1,5 +1,7 @@
 // C ABI of libakaze_hip.so (declared in include/akaze_hip.h), part 1: context lifecycle, device memory helpers, host-side
 // planning, profile, mode setters and measurement hooks.  See akz_ctx.hpp for how the ABI is split over translation units.
+#include <cstdio>
+
 #include "akz_ctx.hpp"
 
 // Host cores this process can count on: the affinity mask, cut down by the cgroup CPU quota, divided among the ranks
@@ -511,6 +513,62 @@ int akz_debug_set_host_sort(akz_ctx* c, int on) {
     if (!c) return AKZ_ERR_INVALID_ARG;
     c->dbg_host_sort = on < 0 ? -1 : (on != 0);
     for (akz_ctx* l : c->lanes) l->dbg_host_sort = c->dbg_host_sort;
+    return AKZ_OK;
+}
+int akz_debug_set_alloc_fill(akz_ctx* c, int on) {
+    if (!c) return AKZ_ERR_INVALID_ARG;
+    c->dbg_alloc_fill = on != 0;
+    for (akz_ctx* l : c->lanes) l->dbg_alloc_fill = c->dbg_alloc_fill;
+    return AKZ_OK;
+}
+// One context's raised claims against the device: up to three rows behind out[*k].  Read-only: copies, no launch, no claim changes.
+static int audit_one(akz_ctx* c, const char* prefix, akz_scratch_audit* out, uint32_t cap, uint32_t* k) {
+    AKZ_HIP_TRY(sync_all_streams(c));
+    struct Claim {
+        const char* name;
+        const DevBuf* buf;
+        size_t bytes;
+        bool epochs;
+    };
+    const Claim claims[3] = {{"small", &c->small, c->small_zero_p == c->small.p ? c->small_zero : 0, false},
+                             {"bucket_scratch", &c->bucket_scratch, c->bucket_zero, false},
+                             {"match_state", &c->match_state, c->match_state_known, true}};
+    std::vector<uint64_t> host;
+    for (const Claim& cl : claims) {
+        akz_scratch_audit row{};
+        std::snprintf(row.name, sizeof(row.name), "%s%s", prefix, cl.name);
+        row.claimed_bytes = cl.bytes;
+        row.first_bad = -1;
+        if (cl.bytes > cl.buf->bytes || (cl.bytes && !cl.buf->p)) {  // a claim past its buffer is an offence of the bookkeeping itself
+            row.first_bad = (int64_t)cl.buf->bytes;
+        } else if (cl.bytes) {
+            host.assign((cl.bytes + 7) / 8, 0);
+            AKZ_HIP_TRY(hipMemcpy(host.data(), cl.buf->p, cl.bytes, hipMemcpyDeviceToHost));
+            if (cl.epochs) {  // words of epoch << 32 | count
+                for (size_t i = 0; i < cl.bytes / 8 && row.first_bad < 0; ++i)
+                    if ((uint32_t)(host[i] >> 32) > c->match_epoch) row.first_bad = (int64_t)(i * 8);
+            } else {
+                const uint8_t* b = (const uint8_t*)host.data();
+                for (size_t i = 0; i < cl.bytes && row.first_bad < 0; ++i)
+                    if (b[i] != 0) row.first_bad = (int64_t)i;
+            }
+        }
+        if (*k < cap) out[*k] = row;
+        ++*k;
+    }
+    return AKZ_OK;
+}
+int akz_debug_audit_scratch(akz_ctx* c, akz_scratch_audit* out, uint32_t cap, uint32_t* n_rows) {
+    AKZ_TRY(bind(c));
+    if (!n_rows || (cap && !out)) return AKZ_ERR_INVALID_ARG;
+    uint32_t k = 0;
+    AKZ_TRY(audit_one(c, "", out, cap, &k));
+    for (size_t i = 0; i < c->lanes.size(); ++i) {
+        char prefix[16];
+        std::snprintf(prefix, sizeof(prefix), "lane%u.", (unsigned)i);
+        AKZ_TRY(audit_one(c->lanes[i], prefix, out, cap, &k));
+    }
+    *n_rows = k;
     return AKZ_OK;
 }
 int akz_debug_set_device_libm(akz_ctx* c, int mode) {

@@ -109,14 +109,19 @@ struct akz_ctx {
     DevBuf scratch[6];                       // f32 plane temporaries (largest level x batch)
     DevBuf scratch_coarse;                   // the coarse chain's own diffusion scratch: it outlives the batch's join (see extract_begin)
     DevBuf lazy[6];                          // one-image planes of akz_fetch_plane's recomputation (never shared with scratch users)
+    // Scratch CLAIMS: three buffers are read by a job for what an earlier job left in them, so that no clearing
+    // launch is needed.  What is known of each is stated here and nowhere else: ensure() drops the claim of a buffer it
+    // (re)allocates, the launch code drops it before it enqueues anything that dirties the range and raises it once the memset /
+    // the launches that restore the content are enqueued, and akz_debug_audit_scratch checks every raised claim on the device.
     DevBuf small;                            // hmax bits / histogram / counters
-    void* small_zero_p = nullptr;            // ... of which the first small_zero bytes are known to be zero (head_impl: its histogram
+    void* small_zero_p = nullptr;            // claim: the first small_zero bytes of `small` are zero (head_impl: its histogram
     size_t small_zero = 0;                   //     pass leaves them so; 0: not known)
     DevBuf cand;                             // NMS candidates
     DevBuf cand_sorted, sort_scratch;        // the list in scan order (device sort of extract_finish) and the sort's scratch
     DevBuf rel_scratch;                      // the selection's neighbour lists (launch::candidate_relations)
     DevBuf sel_scratch, sel_recs;            // the selection on the device (launch::select_device): its scratch, the selected keypoints
-    DevBuf bucket_scratch;                   // launch::sort_candidates_buckets (its counters are zero between jobs)
+    DevBuf bucket_scratch;                   // launch::sort_candidates_buckets
+    size_t bucket_zero = 0;                  // claim: the first bucket_zero bytes of bucket_scratch (its counters) are zero; 0: not known
     int dbg_select = -1;                     // akz_debug_set_select: 2 / 1 / 0 force the device / the neighbour-list / the grid selection, -1 automatic
     std::atomic<uint32_t> last_total_kp{0};  // keypoints of the previous finished job (speculative fetch size of the device selection)
     std::atomic<int> sel_last_mode{-1};      // akz_debug_select_info: how the last finished job was selected (0 grids, 1 lists, 2 device), the
@@ -129,6 +134,7 @@ struct akz_ctx {
     DevBuf match_state;                      // k_match_merge_compact's per-workgroup counts (zeroed when allocated, then told apart by epoch);
                                              // single-stream: only ever touched by launches on `stream` (see match_device_impl)
     uint32_t match_epoch = 0;
+    size_t match_state_known = 0;            // claim: no word of the first match_state_known bytes carries an epoch beyond match_epoch
     DevBuf ransac_dev, ransac_pin;           // match_features: the trials' inputs and outputs on the device / pinned staging of both
     // akz_match_features_pairs: the sets' rows and x / y; raw lists, their counts and points; pair table and two slots of
     // trial samples; models and inlier counts; kept lists with their counts -- and the pinned staging of each
@@ -167,6 +173,7 @@ struct akz_ctx {
     int dbg_device_libm = -1;   // akz_debug_set_device_libm: 0 = the host's libm always, -1 = automatic (device_libm_mode)
     int libm_last = 0;          // how the last finished job got its angles: 0 host libm, 1 / 2 the device's FMA / SSE2 forms
     int dbg_host_sort = -1;                            // akz_debug_set_host_sort: 1 / 0 force the host / the device sort, -1 automatic
+    bool dbg_alloc_fill = false;                       // akz_debug_set_alloc_fill: fresh device memory is filled with kAllocFillByte
     DevBuf cosi;                             // (cos, sin) per keypoint
     DevBuf pin[PIN_COUNT_];                  // pinned host staging (enum Pin)
     std::vector<std::pair<size_t, void*>> slab_pool;  // freed device blocks (pyramid slabs, descriptor rows)
@@ -274,6 +281,28 @@ struct akz_ctx {
 // akz_debug_kernel_rows stage of the JPEG rows: the reconstruction has no akz_profile stage of its own
 constexpr int kStageIngest = 10;
 
+// akz_debug_kernel_rows stage of the candidate sort's rows (extract_finish): counted, never timed -- no events, no akz_profile stage
+constexpr int kStageSort = 11;
+// the row of kernel variant (kind, param) on launches of shape (w, h, n) in c->rows, created on first use (under c->ev_m)
+AKZ_LOCAL inline int kernel_row_locked(akz_ctx* c, int stage, uint32_t kind, uint32_t param, uint32_t w, uint32_t h, uint32_t n) {
+    for (size_t i = 0; i < c->rows.size(); ++i) {
+        const akz_kernel_row& r = c->rows[i];
+        if (r.stage == (uint32_t)stage && r.kind == kind && r.param == param && r.w == w && r.h == h && r.n == n) return (int)i;
+    }
+    akz_kernel_row r{};
+    r.stage = (uint32_t)stage, r.kind = kind, r.param = param, r.w = w, r.h = h, r.n = n;
+    c->rows.push_back(r);
+    return (int)c->rows.size() - 1;
+}
+// launches that are counted without a span (profiling on): which sort a job's candidates took
+AKZ_LOCAL inline void kernel_row_count(akz_ctx* c, int stage, uint32_t kind, uint32_t w, uint32_t h, uint32_t n, uint64_t launches, uint64_t px) {
+    if (!c->profiling) return;
+    std::lock_guard<std::mutex> lk(c->ev_m);
+    akz_kernel_row& r = c->rows[(size_t)kernel_row_locked(c, stage, kind, 0, w, h, n)];
+    r.launches += launches;
+    r.px += px;
+}
+
 // RAII stage timer: device stages bracket the enqueued work with two events on the stream; they
 // are resolved (hipEventElapsedTime) at the end of the extract call, after the final sync.
 struct StageTimer {
@@ -308,16 +337,7 @@ struct StageTimer {
     void kernel(uint32_t kind, uint32_t param, uint32_t w, uint32_t h, uint32_t n, uint64_t launches, uint64_t px, uint64_t px_steps = 0) {
         if (!on) return;
         std::lock_guard<std::mutex> lk(c->ev_m);
-        for (size_t i = 0; i < c->rows.size() && row < 0; ++i) {
-            const akz_kernel_row& r = c->rows[i];
-            if (r.stage == (uint32_t)stage && r.kind == kind && r.param == param && r.w == w && r.h == h && r.n == n) row = (int)i;
-        }
-        if (row < 0) {
-            akz_kernel_row r{};
-            r.stage = (uint32_t)stage, r.kind = kind, r.param = param, r.w = w, r.h = h, r.n = n;
-            c->rows.push_back(r);
-            row = (int)c->rows.size() - 1;
-        }
+        if (row < 0) row = kernel_row_locked(c, stage, kind, param, w, h, n);
         c->rows[(size_t)row].launches += launches;
         c->rows[(size_t)row].px += px;
         c->rows[(size_t)row].px_steps += px_steps;
@@ -374,6 +394,13 @@ AKZ_LOCAL inline hipError_t sync_all_streams(akz_ctx* c, unsigned which = kSyncA
     return first;
 }
 AKZ_LOCAL inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }  // the parts of one buffer start on 256 bytes
+// akz_debug_set_alloc_fill: what hipMalloc returned holds 0xA5 bytes before anybody sees it (a debug mode: a fill and a wait)
+constexpr int kAllocFillByte = 0xA5;
+AKZ_LOCAL inline hipError_t alloc_fill(const akz_ctx* c, void* p, size_t bytes) {
+    if (!c->dbg_alloc_fill) return hipSuccess;
+    const hipError_t e = hipMemset(p, kAllocFillByte, bytes);
+    return e != hipSuccess ? e : hipDeviceSynchronize();
+}
 AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return AKZ_OK;
     if (b.p) {
@@ -386,9 +413,12 @@ AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
         c->small_zero_p = nullptr;
         c->small_zero = 0;
     }
+    if (&b == &c->bucket_scratch) c->bucket_zero = 0;
+    if (&b == &c->match_state) c->match_state_known = 0;
     const size_t want = bytes + bytes / 8 + 256;
     AKZ_HIP_TRY(hipMalloc(&b.p, want));
     b.bytes = want;
+    AKZ_HIP_TRY(alloc_fill(c, b.p, want));
     return AKZ_OK;
 }
 AKZ_LOCAL inline int ensure_pinned(akz_ctx* c, DevBuf& b, size_t bytes) {

@@ -210,6 +210,7 @@ int akz_ctx_set_lanes(akz_ctx* c, uint32_t lanes) {
         l->dbg_set_chunks = c->dbg_set_chunks;
         l->dbg_host_sort = c->dbg_host_sort;
         l->dbg_select = c->dbg_select;
+        l->dbg_alloc_fill = c->dbg_alloc_fill;
         c->lanes.push_back(l);
     }
     c->next_lane = 0;

@@ -293,16 +293,20 @@ int enqueue_device_side(FinishState& f) {
     f.sorted = rows_sort;
     bool buckets_sort = false;
     if (!f.sorted) {  // several images or a longer list: the same sort in four launches, if the job has few enough rows
-        const size_t before = c->bucket_scratch.bytes;  // (a buffer that has just been (re)allocated: its counters are not zero yet)
+        // (whether its counters are zero is the claim c->bucket_zero: ensure() drops it with the buffer, the sort keeps it)
         AKZ_TRY(ensure(c, c->bucket_scratch, launch::sort_candidates_buckets_scratch(cap)));
         buckets_sort = launch::sort_candidates_buckets(s, f.d_unsorted(), cap, f.d_count, lw.data(), lh.data(), L, n, c->bucket_scratch.p,
-                                                       c->bucket_scratch.bytes != before, d_sorted, d_zero, want_lists ? c->rel_scratch.p : nullptr);
+                                                       &c->bucket_zero, d_sorted, d_zero, want_lists ? c->rel_scratch.p : nullptr);
         f.sorted = buckets_sort;
     }
     if (!f.sorted) {
         AKZ_TRY(ensure(c, c->sort_scratch, launch::sort_candidates_scratch(cap, max_px, L, n)));
         f.sorted = launch::sort_candidates_device(s, f.d_unsorted(), cap, f.d_count, max_px, L, n, c->sort_scratch.p, d_sorted, d_zero);
     }
+    // (akz_debug_kernel_rows: which of the three sorts the job took)
+    if (f.sorted)
+        kernel_row_count(c, kStageSort, rows_sort ? AKZ_KR_SORT_ROWS : (buckets_sort ? AKZ_KR_SORT_BUCKETS : AKZ_KR_SORT_RADIX), r->plan[0].w,
+                         r->plan[0].h, n, rows_sort ? 1 : (buckets_sort ? 4 : 3), cap);
     AKZ_HIP_TRY(hipGetLastError());
     if (!f.sorted || !want_lists) return AKZ_OK;
     launch::candidate_relations(s, d_sorted, cap, f.d_count, f.lsize.data(), f.lratio.data(), lw.data(), lh.data(), L, n, c->rel_scratch.p,

@@ -19,12 +19,19 @@ int match_finish(akz_ctx* c, MatchRec* rec, uint32_t n0, uint32_t chunks, uint32
     //   * match_state (told apart by epoch) belongs to ONE stream: this function, like every user of the context's matcher
     //     scratch (match_rec, mm_q8, mm_t8, mm_pop), enqueues on c->stream only -- launches of two epochs never overlap.
     if (n0 >= gates::kMergeCompactMinRows && n0 <= gates::kMergeCompactMaxRows) {
+        // (the claim c->match_state_known: how much of the state holds no epoch beyond match_epoch -- dropped by ensure() with the
+        // buffer, and when the epoch wraps: words of 2^32 calls ago would read as published)
         const size_t need = launch::match_merge_compact_state_bytes(n0);
-        if (c->match_state.bytes < need) {
-            AKZ_TRY(ensure(c, c->match_state, need * 2));
-            AKZ_HIP_TRY(hipMemsetAsync(c->match_state.p, 0, c->match_state.bytes, c->stream));
+        if (++c->match_epoch == 0) {
+            c->match_epoch = 1;
+            c->match_state_known = 0;
         }
-        if (++c->match_epoch == 0) ++c->match_epoch;
+        if (c->match_state_known < need) {
+            if (c->match_state.bytes < need) AKZ_TRY(ensure(c, c->match_state, need * 2));
+            c->match_state_known = 0;
+            AKZ_HIP_TRY(hipMemsetAsync(c->match_state.p, 0, c->match_state.bytes, c->stream));
+            c->match_state_known = c->match_state.bytes;
+        }
         launch::match_merge_compact(c->stream, rec, n0, chunks, thr, lowes_ratio * lowes_ratio, d_out,
                                     (unsigned long long*)d_n_out, c->match_state.p, c->match_epoch);
         AKZ_HIP_TRY(hipGetLastError());

@@ -14,6 +14,7 @@ int slab_acquire(akz_ctx* c, size_t bytes, void** p, size_t* got) {
         }
     bytes += bytes / 8;  // head-room so that the next, slightly larger request can reuse the block
     AKZ_HIP_TRY(hipMalloc(p, bytes));
+    AKZ_HIP_TRY(alloc_fill(c, *p, bytes));
     *got = bytes;
     return AKZ_OK;
 }

@@ -947,9 +947,11 @@ bool sort_candidates_rows(hipStream_t s, const Candidate* d_cand, uint32_t cap, 
 size_t sort_candidates_buckets_scratch(uint32_t cap) {
     return up256((size_t)(SORT_BUCKETS_MAX + 1) * 4) * 2 + up256((size_t)cap * 4) * 3 + 256;
 }
+size_t sort_candidates_buckets_counters() { return up256((size_t)(SORT_BUCKETS_MAX + 1) * 4); }
 bool sort_candidates_buckets(hipStream_t s, const Candidate* d_cand, uint32_t cap, const uint32_t* d_count, const uint32_t* level_w,
-                             const uint32_t* level_h, uint32_t n_levels, uint32_t n_images, void* scratch, bool scratch_is_new,
+                             const uint32_t* level_h, uint32_t n_levels, uint32_t n_images, void* scratch, size_t* counters_zero,
                              Candidate* d_sorted, uint32_t* d_zero, void* rel_scratch) {
+    // (a job that is refused touches nothing: the claim stays as it was)
     if (n_levels == 0 || n_levels > (uint32_t)kMaxLevels || cap == 0) return false;
     const uint64_t nb64 = (uint64_t)n_images * rows_per_image(level_h, n_levels);
     if (nb64 > SORT_BUCKETS_MAX) return false;
@@ -964,7 +966,9 @@ bool sort_candidates_buckets(hipStream_t s, const Candidate* d_cand, uint32_t ca
     unsigned* bucket_of = (unsigned*)(p + 2 * cb);
     unsigned* slot_of = (unsigned*)(p + 2 * cb + lb);
     unsigned* row_keys = (unsigned*)(p + 2 * cb + 2 * lb);
-    if (scratch_is_new) (void)hipMemsetAsync(cnt, 0, cb, s);  // (afterwards k_bucket_scan leaves them zero)
+    const bool known_zero = *counters_zero >= cb;
+    *counters_zero = 0;  // (k_bucket_count dirties them; until every launch below is enqueued nothing is known)
+    if (!known_zero && hipMemsetAsync(cnt, 0, cb, s) != hipSuccess) return false;  // (afterwards k_bucket_scan leaves them zero)
     unsigned *offs = nullptr, *flags = nullptr;
     if (rel_scratch) {  // (candidate_relations' layout: its row table holds the bucket starts)
         const size_t offs_b = up256((size_t)n_images * (n_levels + 1) * 4), flags_b = up256((size_t)n_images * 4),
@@ -980,6 +984,7 @@ bool sort_candidates_buckets(hipStream_t s, const Candidate* d_cand, uint32_t ca
                        (const unsigned*)slot_of, row_keys);
     hipLaunchKernelGGL(k_bucket_rank, dim3(gb), dim3(256), 0, s, d_cand, cap, d_count, (const unsigned*)start, (const unsigned*)bucket_of,
                        (const unsigned*)row_keys, d_sorted, d_zero);
+    if (hipPeekAtLastError() == hipSuccess) *counters_zero = cb;  // (k_bucket_scan has cleared every counter k_bucket_count bumped)
     return true;
 }
 size_t sort_candidates_scratch(uint32_t cap, uint64_t max_px, uint32_t n_levels, uint32_t n_images) {

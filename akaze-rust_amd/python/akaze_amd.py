@@ -69,7 +69,12 @@ class KernelRow(C.Structure):
 
 
 KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march",
-                    6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d"}
+                    6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d", 9: "k_sort_rows", 10: "k_bucket_sort", 11: "rocprim_radix_sort"}
+
+
+class ScratchAudit(C.Structure):
+    """akz_scratch_audit (akaze_hip_debug.h)"""
+    _fields_ = [("name", C.c_char * 32), ("claimed_bytes", C.c_uint64), ("first_bad", C.c_int64)]
 
 
 class Gate(C.Structure):
@@ -238,6 +243,8 @@ def lib():
         "akz_ctx_set_host_threads": ([vp, u32], i32),
         "akz_debug_set_match_chunks": ([vp, u32, u32], i32),
         "akz_debug_set_host_sort": ([vp, i32], i32),
+        "akz_debug_set_alloc_fill": ([vp, i32], i32),
+        "akz_debug_audit_scratch": ([vp, vp, u32, pu32], i32),
         "akz_debug_set_select": ([vp, i32], i32),
         "akz_debug_select_info": ([vp, C.POINTER(C.c_int)], i32),
         "akz_debug_set_schedule": ([vp, i32, i32], i32),
@@ -648,6 +655,19 @@ class Context:
     def debug_set_host_sort(self, on):
         """akz_debug_set_host_sort: candidates bucketed and sorted on the host instead of the device sort."""
         _check(lib().akz_debug_set_host_sort(self._h, -1 if on is None else (1 if on else 0)))
+
+    def debug_set_alloc_fill(self, on=True):
+        """akz_debug_set_alloc_fill: every device allocation of the context from now on is filled with 0xA5 bytes (identical results)."""
+        _check(lib().akz_debug_set_alloc_fill(self._h, int(bool(on))))
+
+    def debug_audit_scratch(self):
+        """akz_debug_audit_scratch: every raised scratch claim checked on the device -> [dict(name, claimed_bytes, first_bad)],
+        first_bad None where the claimed range holds what the claim says (or nothing is claimed)."""
+        n = C.c_uint32()
+        rows = (ScratchAudit * 32)()
+        _check(lib().akz_debug_audit_scratch(self._h, C.cast(rows, C.c_void_p), 32, C.byref(n)))
+        return [dict(name=r.name.decode(), claimed_bytes=int(r.claimed_bytes), first_bad=None if r.first_bad < 0 else int(r.first_bad))
+                for r in rows[:min(n.value, 32)]]
 
     def debug_set_match_chunks(self, pair_chunks=0, set_chunks=0):
         """akz_debug_set_match_chunks (include/akaze_hip_debug.h): force the matcher's chunk counts; 0 = automatic."""

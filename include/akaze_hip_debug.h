@@ -117,9 +117,13 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    akz_profile; reset != 0 zeroes the figures.  *n_rows = rows there are (may exceed cap).
    JPEG reconstruction (akz_extract_features_file / _files, akz_image_load_luma_device) adds rows of stage 10, which no
    akz_profile stage counts: k_jpeg_idct (px = coefficients), k_jpeg_luma (px = output pixels) and the coefficient upload
-   (px = bytes copied), each with param = components and (w, h, 1) = the frame. */
+   (px = bytes copied), each with param = components and (w, h, 1) = the frame.
+   The device sort of a job's extrema candidates adds one row of stage 11 per job, counted and never timed (ms stays 0; any
+   profiling level): k_sort_rows (one launch), the four k_bucket_* launches, or the key / radix sort / gather chain around
+   rocPRIM -- param 0, (w, h, n) = the frame and the batch, px = the list's capacity. */
 enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5,
-       AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8 };
+       AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8, AKZ_KR_SORT_ROWS = 9, AKZ_KR_SORT_BUCKETS = 10,
+       AKZ_KR_SORT_RADIX = 11 };
 typedef struct akz_kernel_row {
     uint32_t stage, kind, param, w, h, n;
     uint64_t launches, px, px_steps;
@@ -143,6 +147,24 @@ int akz_debug_set_select(akz_ctx* ctx, int mode);
    an image took on the device, info[2] = images that sent the job back to the host's selection, info[3] = candidates,
    info[4 .. 7] = 10 ns ticks of k_select's phases on image 0 (first states, turns, second pass, output).  info: 8 ints. */
 int akz_debug_select_info(akz_ctx* ctx, int* info);
+
+/* Test hooks for the scratch that one job leaves in a known state for the next (the claimed buffers).
+   akz_debug_set_alloc_fill(ctx, on != 0): every device allocation the context (and its lanes) makes from now on -- scratch, slabs
+   of results -- is filled with bytes 0xA5 before the allocating call returns (a fill and a wait: a debug mode), so that "fresh
+   memory is not zero" is a fact and not luck.  Results are identical.
+   akz_debug_audit_scratch: waits for the context's streams, then copies the range of every claim that is raised to the host and
+   checks it against what the claim says: `small` (contrast scratch: zero), `bucket_scratch` (the bucket sort's counters: zero),
+   `match_state` (the look-back words of the merging compaction: none carries an epoch beyond the context's).  Three rows per
+   context, the lanes' behind the context's own ("lane0.small", ...): the claimed bytes (0: nothing claimed, nothing checked) and
+   the offset of the first offending byte / word, -1 for none.  Read-only: it launches nothing and changes no claim.  *n_rows = rows
+   there are (may exceed cap). */
+typedef struct akz_scratch_audit {
+    char name[32];
+    uint64_t claimed_bytes;
+    int64_t first_bad;
+} akz_scratch_audit;
+int akz_debug_set_alloc_fill(akz_ctx* ctx, int on);
+int akz_debug_audit_scratch(akz_ctx* ctx, akz_scratch_audit* out, uint32_t cap, uint32_t* n_rows);
 
 /* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
    source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */

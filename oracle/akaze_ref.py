@@ -282,6 +282,18 @@ def extract(img, cfg=None, threads=1):
     return RefResult(hdl)
 
 
+def plan_level_size(w, h, lvl, cfg=None):
+    """(width, height) of evolution `lvl` of a w x h frame as allocate_evolutions and the chained half_size give it; None past
+    the last level."""
+    cfg = cfg or default_config()
+    size = lib().ref_plan_level_size
+    size.argtypes = [C.c_int, C.c_int, C.POINTER(RefConfig), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lw, lh = C.c_uint32(), C.c_uint32()
+    if size(w, h, C.byref(cfg), lvl, C.byref(lw), C.byref(lh)) != 0:
+        return None
+    return lw.value, lh.value
+
+
 def detect_from_planes(w, h, planes, cfg=None):
     """detect_keypoints + extract_descriptors on evolutions the caller holds: planes[level][name] -> 2-D float32 array (names
     of PLANES; missing ones are skipped; Lt, Lx, Ly and Ldet are required), as akaze_amd.Context.extract_from_planes takes them."""
