@@ -89,7 +89,7 @@ int akz_ctx_create(int device, void* stream, akz_ctx** out) {
     }
     std::unique_ptr<akz_ctx> c(new akz_ctx);
     c->device = device;
-    c->stream = c->main = (hipStream_t)stream;  // NULL == the default stream
+    c->stream = (hipStream_t)stream;  // NULL == the default stream
     *out = c.release();
     return AKZ_OK;
 }
@@ -226,7 +226,7 @@ int akz_ctx_synchronize(akz_ctx* c) {
     if (c->copy) AKZ_HIP_TRY(hipStreamSynchronize(c->copy));
     return AKZ_OK;
 }
-void* akz_ctx_stream(akz_ctx* c) { return c ? (void*)c->main : nullptr; }
+void* akz_ctx_stream(akz_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int akz_device_malloc(akz_ctx* c, size_t bytes, void** d_out) {
     AKZ_TRY(bind(c));

@@ -102,9 +102,7 @@ enum Pin {
 };
 struct akz_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;            // the stream the enqueueing helpers use: the caller's stream, except while extract_begin
-                                             // puts a batch's early stages or its coarse chain on a stream of their own
-    hipStream_t main = nullptr;              // the caller's stream (never changes; what other threads synchronise with)
+    hipStream_t stream = nullptr;            // the caller's stream (set at creation, a lane's again by place_lanes; what other threads synchronise with)
     bool own_stream = false;
     DevBuf scratch[6];                       // f32 plane temporaries (largest level x batch)
     DevBuf scratch_coarse;                   // the coarse chain's own diffusion scratch: it outlives the batch's join (see extract_begin)
@@ -216,14 +214,8 @@ struct akz_ctx {
     // has finished its fine-level diffusion (default) or not; [2] no placement probe; [11] 1 = one column-march detector launch
     // per level instead of one per set of levels (the others: include/akaze_hip_debug.h)
     int sched[12] = {0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t big_px = gates::kBigPxAsync;  // the gate of the job being begun (set by extract_begin from the two below; the begin half's helpers read it)
     uint64_t big_px_sync = gates::kBigPxSync, big_px_async = gates::kBigPxAsync;  // (sched[4] sets both: measurement)
     uint64_t lane_px = gates::kLanePx;  // jobs below it go to the lanes, if the context has any (sched[4] sets it too)
-    // pixels per LAUNCH (level w*h*n) from which the blur, the contrast passes and the detectors take their column-march
-    // form: 8 Mpx (a 32 x 480x270 level: 41 us tiled against 66 for the march, which would run one strip per image row);
-    // inside a batch-path job smaller than that, the job's own size -- its full-resolution launches march, the rest is tiled
-    static constexpr uint64_t kLaunchMarchPx = gates::kMarchPx;
-    uint64_t launch_min_px = kLaunchMarchPx;
     // Stream placement (place_streams): the runtime multiplexes a process's streams onto a few in-order hardware queues
     // (GPU_MAX_HW_QUEUES, 4 by default); two busy streams of a context on one queue serialise the whole pipeline, so the
     // first large batch measures which of the context's streams actually run side by side and replaces those that do not
@@ -278,6 +270,19 @@ struct akz_ctx {
     DevBuf jpeg_coef, jpeg_plane, jpeg_frames;
     std::mutex jpeg_m;
 };
+// What a job decides for the launch helpers (akz_ops.cpp) it shares with the per-op entry points and the lazy recomputations.
+// Everything else they depend on (fed_mode, det_mode, stream_min_px, sched[], profiling) is a context setting no job overrides.
+struct JobForm {
+    hipStream_t stream;     // the stream to enqueue on
+    int prep_mode;          // the preparation mode in force (akz_ctx::prep_mode; extract_begin: 0 for jobs below gates::kTiledPrepPx)
+    // pixels per LAUNCH (level w*h*n) from which the blur, the contrast passes and the detectors take their column-march
+    // form: 8 Mpx (a 32 x 480x270 level: 41 us tiled against 66 for the march, which would run one strip per image row);
+    // inside a batch-path job smaller than that, the job's own size -- its full-resolution launches march, the rest is tiled
+    uint64_t march_min_px;
+};
+// outside a job: the context's stream, the mode as the user set it, the 8 Mpx gate
+AKZ_LOCAL inline JobForm no_job_form(const akz_ctx* c) { return JobForm{c->stream, c->prep_mode, gates::kMarchPx}; }
+
 // akz_debug_kernel_rows stage of the JPEG rows: the reconstruction has no akz_profile stage of its own
 constexpr int kStageIngest = 10;
 
@@ -325,7 +330,7 @@ struct StageTimer {
     bool on;
     hipStream_t s;
     int row = -1;
-    StageTimer(akz_ctx* ctx, int st, hipStream_t stream = nullptr) : c(ctx), stage(st), s(stream ? stream : ctx->stream) {
+    StageTimer(akz_ctx* ctx, int st, hipStream_t stream) : c(ctx), stage(st), s(stream) {
         on = c->profiling >= 2 || (c->profiling == 1 && (st == AKZ_ST_FED || st == AKZ_ST_DETECTOR));
         if (!on) return;
         a = get(c);
@@ -387,7 +392,7 @@ AKZ_LOCAL inline hipError_t sync_all_streams(akz_ctx* c, unsigned which = kSyncA
         const hipError_t e = hipStreamSynchronize(s);
         if (first == hipSuccess) first = e;
     };
-    if (which & kSyncMain) wait(c->main);
+    if (which & kSyncMain) wait(c->stream);
     if ((which & kSyncAux) && c->aux) wait(c->aux);
     for (hipStream_t s : {c->coarse, c->pre, c->copy})
         if ((which & kSyncSide) && s) wait(s);
@@ -492,22 +497,22 @@ AKZ_LOCAL int level_info_out(const std::vector<LevelPlan>& plan, uint64_t level,
                    double* tau, uint64_t tau_cap);
 // akz_ops.cpp: the launch helpers behind the per-op entry points, which the extraction pipeline calls as well
 template <typename T>
-AKZ_LOCAL int gaussian_blur_impl(akz_ctx* c, const T* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n, float sigma);
+AKZ_LOCAL int gaussian_blur_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n, float sigma);
 // level 0 of a small job in two launches (k_head, k_contrast_hist_final); *fused = false: not this job (the separate stages follow)
 template <typename T>
-AKZ_LOCAL int head_impl(akz_ctx* c, const T* d_in, float* d_lt0, float* d_blurred, float* d_gx, float* d_gy, uint32_t w, uint32_t h, uint32_t n,
+AKZ_LOCAL int head_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_lt0, float* d_blurred, float* d_gx, float* d_gy, uint32_t w, uint32_t h, uint32_t n,
                         float sigma0, double percentile, double gscale, uint64_t nbins, double* d_k_out, bool* fused, uint32_t* d_zero_word = nullptr);
-AKZ_LOCAL int contrast_impl(akz_ctx* c, const float* d_in, uint32_t w, uint32_t h, uint32_t n, double percentile, double gscale, uint64_t nbins,
+AKZ_LOCAL int contrast_impl(akz_ctx* c, const JobForm& f, const float* d_in, uint32_t w, uint32_t h, uint32_t n, double percentile, double gscale, uint64_t nbins,
                   double* d_k_out);
 AKZ_LOCAL uint32_t fed_max_fuse(const akz_ctx* c, uint32_t w, uint32_t h, uint32_t n);
 AKZ_LOCAL uint32_t fed_num_launches(const akz_ctx* c, uint32_t n_tau, uint32_t w, uint32_t h, uint32_t n);
 AKZ_LOCAL float* fed_dst(uint32_t launches, uint32_t k /*1-based*/, float* A, float* B);
 // next / next_done: the last launch may also prepare the NEXT level (launch::fed_fused's epilogue); *next_done says whether it did
-AKZ_LOCAL int fed_impl(akz_ctx* c, const float* in, float* A, float* B, const float* lflow, float* lstep, uint32_t w, uint32_t h, uint32_t n,
+AKZ_LOCAL int fed_impl(akz_ctx* c, const JobForm& f, const float* in, float* A, float* B, const float* lflow, float* lstep, uint32_t w, uint32_t h, uint32_t n,
              const double* taus, uint32_t n_tau, const launch::FedNextPrep* next = nullptr, bool* next_done = nullptr);
-AKZ_LOCAL int detector_family(const akz_ctx* c, uint32_t sigma, uint32_t w, uint32_t h, uint32_t n, float border_m, bool keep_second,
+AKZ_LOCAL int detector_family(const akz_ctx* c, const JobForm& f, uint32_t sigma, uint32_t w, uint32_t h, uint32_t n, float border_m,
                     bool nms = true);
-AKZ_LOCAL int detector_impl(akz_ctx* c, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy, float* lxy,
+AKZ_LOCAL int detector_impl(akz_ctx* c, const JobForm& f, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy, float* lxy,
                   float* ldet_out, uint32_t w, uint32_t h, uint32_t n);
 // akz_place.cpp
 AKZ_LOCAL int place_streams(akz_ctx* c);

@@ -21,7 +21,6 @@ enum class Det : uint8_t {  // detector_family's 0 split in two, 4 and 5
 // preparation rode on the previous level's last diffusion launch (BeginState::prepared, reported by fed_impl).
 struct BeginRoute {
     bool big = false;           // the job takes the batch path (column marches, forked coarse chain, resident tail)
-    int prep_mode = 0;          // the preparation mode in force (c->prep_mode as this begin half has swapped it)
     int pre_on = 0;             // level 0 runs ahead on: 0 nothing (the context's stream), 2 the copy stream, 1 a stream of its own
     bool level1_clone = false;  // level 1 continues level 0's octave: k_head can leave its Lsmooth and the Scharr pair
     size_t res_first = 0;       // first level of the resident tail (L: none)
@@ -38,17 +37,16 @@ struct BeginRoute {
     std::vector<Level> lv;
 };
 
-// No HIP call, nothing mutated.  Reads c->prep_mode, c->launch_min_px and c->big_px as extract_begin has set them for this job
-// (detector_family and the preparation gates below depend on them).
-BeginRoute begin_route(const akz_ctx* c, const std::vector<LevelPlan>& plan, const akz_config& cfg, uint32_t w, uint32_t h, uint32_t n,
-                       uint32_t flags, bool input_ready, bool big) {
+// No HIP call, nothing mutated.  What the job decided comes as `f` (its stream is not looked at) and `big`; of the context only
+// settings that no job overrides are read.
+BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<LevelPlan>& plan, const akz_config& cfg, uint32_t w, uint32_t h,
+                       uint32_t n, uint32_t flags, bool input_ready, bool big) {
     const size_t L = plan.size();
     BeginRoute rt;
     rt.big = big;
-    rt.prep_mode = c->prep_mode;
     rt.lv.resize(L);
     const int pre_mode = c->sched[0] == 0 ? c->pre_mode : c->sched[0] == 1 ? 2 : c->sched[0] == 2 ? 1 : 0;  // (1: a stream of its own, measurement only)
-    if ((input_ready || (flags & AKZ_INPUT_READY)) && pre_mode != 0 && c->profiling < 2 && c->prep_mode == 2 && big &&
+    if ((input_ready || (flags & AKZ_INPUT_READY)) && pre_mode != 0 && c->profiling < 2 && f.prep_mode == 2 && big &&
         launch::blur5_march_supported(w, h, (uint32_t)gaussian_kernel_size((float)cfg.base_scale_offset)) &&
         launch::contrast_march_supported(w, h, (uint32_t)gaussian_kernel_size(1.0f), (uint32_t)cfg.contrast_factor_num_bins))
         rt.pre_on = pre_mode;
@@ -68,7 +66,7 @@ BeginRoute begin_route(const akz_ctx* c, const std::vector<LevelPlan>& plan, con
     // against 0.32 ms resident); a batch that forks its coarse chain onto the second stream hides that latency under
     // the fine detectors and gains what the 17 small launches cost those detectors (5.9 -> 5.3 ms per 32-frame step).
     rt.res_first = L;
-    if (c->fed_mode == 2 && (c->prep_mode == 3 || (c->prep_mode == 2 && big))) {
+    if (c->fed_mode == 2 && (f.prep_mode == 3 || (f.prep_mode == 2 && big))) {
         size_t f = 1;
         while (f < L && !launch::octave_resident_supported(plan[f].w, plan[f].h)) ++f;
         f = std::max(f, L > (size_t)launch::kResidentMaxLevels ? L - (size_t)launch::kResidentMaxLevels : (size_t)1);
@@ -100,7 +98,7 @@ BeginRoute begin_route(const akz_ctx* c, const std::vector<LevelPlan>& plan, con
     for (size_t l = 0; l < L; ++l) {
         const LevelPlan& lv = plan[l];
         BeginRoute::Level& q = rt.lv[l];
-        const int fam = detector_family(c, lv.det_sigma, lv.w, lv.h, n, border_margin(lv, cfg), (flags & AKZ_KEEP_ALL_PLANES) != 0);
+        const int fam = detector_family(c, f, lv.det_sigma, lv.w, lv.h, n, border_margin(lv, cfg));
         q.det = fam == 5 ? Det::March : fam == 4 ? Det::TiledSet : launch::detector_nms_fused_supported(lv.det_sigma) ? Det::NmsFused : Det::Fallback;
         if (l >= rt.fork_level && q.det == Det::Fallback) rt.own_kernels = false;
         if (l == 0) continue;
@@ -110,15 +108,15 @@ BeginRoute begin_route(const akz_ctx* c, const std::vector<LevelPlan>& plan, con
         if (l >= rt.res_first) {
             q.prep = Prep::Resident;
         } else if (!lv.tau.empty() && c->fed_mode == 2 && launch::level_march_supported(lv.w, lv.h) &&
-                   (c->prep_mode == 3 || (c->prep_mode == 2 && lpx >= gates::kLevelMarchPx))) {
+                   (f.prep_mode == 3 || (f.prep_mode == 2 && lpx >= gates::kLevelMarchPx))) {
             q.prep = Prep::LevelMarch;
             q.n1 = std::min<uint32_t>((uint32_t)lv.tau.size(), 4u);
             q.rem = (uint32_t)lv.tau.size() - q.n1;
             // a new octave: the 2x2 mean of the previous Lt is formed inside the level kernel where the widths allow it
             // (one launch and one plane round trip less per octave), materialised first otherwise
             q.fold_half = half && launch::level_march_half_supported(lv.w, lv.h, pv.w, pv.h, q.n1);
-        } else if (c->prep_mode != 0 && launch::prep_stream_supported(lv.w, lv.h) &&
-                   (c->prep_mode == 1 || (c->prep_mode >= 2 && !half && lpx >= c->stream_min_px))) {
+        } else if (f.prep_mode != 0 && launch::prep_stream_supported(lv.w, lv.h) &&
+                   (f.prep_mode == 1 || (f.prep_mode >= 2 && !half && lpx >= c->stream_min_px))) {
             // measured on MI355X: the streaming kernel is ~2x faster for cloned levels of a batch (a single
             // frame is launch-latency bound and stays on the tiled kernel); for the first
             // level of an octave (2x2 mean of a 4x larger input) the two are equal, the tiled one stays
@@ -138,8 +136,8 @@ struct BeginState {
     const BeginRoute& rt;
     uint32_t n;
     bool keep_all;
-    hipStream_t s;   // the caller's stream
-    hipStream_t ls;  // the stream the level chain enqueues on (s, or the coarse stream behind the fork)
+    JobForm form;    // what the job decided; form.stream is the caller's stream
+    JobForm chain;   // ... as the level chain enqueues: form, or with the coarse stream behind the fork
     uint64_t seq;    // published (c->begin_seq) when this job's fed_ev has been recorded
     // One append list for the whole batch (image id stored per candidate): a single D2H later.
     Candidate* d_cand;
@@ -175,7 +173,7 @@ bool detector_one_pass(BeginState& b, size_t l, hipStream_t on) {
 // sched[5] (measurement, profiles/r06_interleave.txt): the detector of a fine level right behind the kernel that wrote its
 // Lsmooth instead of after the whole fine chain -- does the detector then find (part of) the plane in the Infinity Cache?
 void interleave_detector(BeginState& b, size_t l) {
-    if (b.c->sched[5] && l < b.rt.fork_level && !b.det_done[l] && b.rt.lv[l].det == Det::March && detector_one_pass(b, l, b.ls)) b.det_done[l] = 1;
+    if (b.c->sched[5] && l < b.rt.fork_level && !b.det_done[l] && b.rt.lv[l].det == Det::March && detector_one_pass(b, l, b.chain.stream)) b.det_done[l] = 1;
 }
 
 // ---- level 0: Lt0 = gaussian_blur(img, base_scale_offset); contrast factor (lib.rs:56-69) ----
@@ -197,6 +195,7 @@ int level0(BeginState& b, const T* d_imgs, hipEvent_t input_ready) {
     const akz_config& cfg = r->cfg;
     const uint32_t w = r->w, h = r->h, n = b.n;
     const bool early = b.rt.pre_on != 0;
+    JobForm f = b.form;  // (on the early stream where the job runs ahead)
     if (early) {
         hipStream_t& ps = b.rt.pre_on == 2 ? c->copy : c->pre;
         if (!ps) AKZ_HIP_TRY(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
@@ -206,33 +205,30 @@ int level0(BeginState& b, const T* d_imgs, hipEvent_t input_ready) {
         // (VALU-bound) diffusion launches to its (bandwidth-bound) detectors: that is what they are meant to run under
         if (c->sched[1] && b.seq > 1)
             AKZ_HIP_TRY(hipStreamWaitEvent(ps, (c->sched[1] == 2 ? c->pre_ev : c->fed_ev)[(b.seq - 1) % akz_ctx::kFedRing], 0));
-        c->stream = ps;
+        f.stream = ps;
     }
     // the job's candidate counter is cleared on the stream of its first stage (every detector launch comes behind that):
     // by that stage's kernel itself where it is k_head, by a fill otherwise
     // (a small job: both stages in two launches -- akz_ops.cpp: head_impl; level 1, where it continues the octave, finds its Lsmooth
     // written -- the contrast factor's blur of Lt0 is the same image -- and the Scharr pair of it in level 0's Lx / Ly planes)
-    AKZ_TRY(head_impl<T>(c, d_imgs, b.P(0, AKZ_LT), b.rt.level1_clone ? b.P(1, AKZ_LSMOOTH) : nullptr, b.P(0, AKZ_LX), b.P(0, AKZ_LY), w, h, n,
+    AKZ_TRY(head_impl<T>(c, f, d_imgs, b.P(0, AKZ_LT), b.rt.level1_clone ? b.P(1, AKZ_LSMOOTH) : nullptr, b.P(0, AKZ_LX), b.P(0, AKZ_LY), w, h, n,
                          (float)cfg.base_scale_offset, cfg.contrast_percentile, 1.0, cfg.contrast_factor_num_bins, r->d_k, &b.head_fused, b.d_count));
     if (!b.head_fused) {
-        AKZ_HIP_TRY(hipMemsetAsync(b.d_count, 0, sizeof(uint32_t), c->stream));
+        AKZ_HIP_TRY(hipMemsetAsync(b.d_count, 0, sizeof(uint32_t), f.stream));
         {
-            StageTimer st(c, AKZ_ST_BLUR0);
-            AKZ_TRY(gaussian_blur_impl<T>(c, d_imgs, b.P(0, AKZ_LT), w, h, n, (float)cfg.base_scale_offset));
+            StageTimer st(c, AKZ_ST_BLUR0, f.stream);
+            AKZ_TRY(gaussian_blur_impl<T>(c, f, d_imgs, b.P(0, AKZ_LT), w, h, n, (float)cfg.base_scale_offset));
         }
         {
-            StageTimer st(c, AKZ_ST_CONTRAST);
-            AKZ_TRY(contrast_impl(c, b.P(0, AKZ_LSMOOTH), w, h, n, cfg.contrast_percentile, 1.0, cfg.contrast_factor_num_bins, r->d_k));
+            StageTimer st(c, AKZ_ST_CONTRAST, f.stream);
+            AKZ_TRY(contrast_impl(c, f, b.P(0, AKZ_LSMOOTH), w, h, n, cfg.contrast_percentile, 1.0, cfg.contrast_factor_num_bins, r->d_k));
         }
     }
     // every job marks the end of its level-0 stages (the last use of the context's contrast scratch): a later job that
     // runs ahead waits for exactly that, whichever stream it was recorded on
     if (!c->pre_done) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->pre_done, hipEventDisableTiming));
-    AKZ_HIP_TRY(hipEventRecord(c->pre_done, c->stream));
-    if (early) {
-        c->stream = b.s;
-        AKZ_HIP_TRY(hipStreamWaitEvent(b.s, c->pre_done, 0));
-    }
+    AKZ_HIP_TRY(hipEventRecord(c->pre_done, f.stream));
+    if (early) AKZ_HIP_TRY(hipStreamWaitEvent(b.form.stream, c->pre_done, 0));
     return AKZ_OK;
 }
 
@@ -251,9 +247,9 @@ int resident_tail(BeginState& b, size_t i) {
                                            (uint32_t)plan[l].tau.size(), ht[l].data(), plan[l].octave});
         px_steps += (uint64_t)plan[l].w * plan[l].h * b.n * plan[l].tau.size();
     }
-    StageTimer st(c, AKZ_ST_FED);
+    StageTimer st(c, AKZ_ST_FED, b.chain.stream);
     st.kernel(AKZ_KR_OCTAVE_RESIDENT, (uint32_t)rl.size(), plan[i].w, plan[i].h, b.n, 1, 0, px_steps);
-    launch::octave_resident(b.ls, b.P(i - 1, AKZ_LT), plan[i - 1].w, plan[i - 1].h, b.n, rl.data(), (uint32_t)rl.size(), b.g1.data(), b.r->d_k);
+    launch::octave_resident(b.chain.stream, b.P(i - 1, AKZ_LT), plan[i - 1].w, plan[i - 1].h, b.n, rl.data(), (uint32_t)rl.size(), b.g1.data(), b.r->d_k);
     if (c->profiling) {
         c->prof.fed_launches += 1;
         c->prof.fed_px_steps += px_steps;
@@ -277,18 +273,18 @@ int level_by_march(BeginState& b, size_t i, float* A, float* B) {
     float* d1 = fed_dst(rest + 1, 1, A, B);
     const float* level_in = b.P(i - 1, AKZ_LT);
     if (half && !q.fold_half) {
-        StageTimer st(c, AKZ_ST_PREP);
+        StageTimer st(c, AKZ_ST_PREP, b.chain.stream);
         float* hb = d1 == A ? B : A;
-        launch::half_size(b.ls, b.P(i - 1, AKZ_LT), hb, pv.w, pv.h, n);
+        launch::half_size(b.chain.stream, b.P(i - 1, AKZ_LT), hb, pv.w, pv.h, n);
         level_in = hb;
     }
     float ht[4];
     for (uint32_t j = 0; j < n1; ++j) ht[j] = 0.5f * (float)lv.tau[j];
     {
-        StageTimer st(c, AKZ_ST_FED);
+        StageTimer st(c, AKZ_ST_FED, b.chain.stream);
         st.kernel(AKZ_KR_LEVEL_MARCH, n1 | (q.fold_half ? 16u : 0u) | ((rem == 0 && b.keep_all) ? 32u : 0u), lv.w, lv.h, n, 1,
                   (uint64_t)lv.w * lv.h * n, (uint64_t)lv.w * lv.h * n * n1);
-        launch::level_march(b.ls, level_in, b.P(i, AKZ_LSMOOTH), b.P(i, AKZ_LFLOW), d1,
+        launch::level_march(b.chain.stream, level_in, b.P(i, AKZ_LSMOOTH), b.P(i, AKZ_LFLOW), d1,
                             (rem == 0 && b.keep_all) ? b.P(i, AKZ_LSTEP) : nullptr, lv.w, lv.h, n, b.g1.data(), b.r->d_k,
                             lv.octave, ht, n1, q.fold_half ? pv.w : 0u, q.fold_half ? pv.h : 0u);
         if (c->profiling) {
@@ -298,9 +294,9 @@ int level_by_march(BeginState& b, size_t i, float* A, float* B) {
         }
     }
     if (rem) {  // (a span of its own: the rows of akz_debug_kernel_rows tell the two kernels apart)
-        StageTimer st(c, AKZ_ST_FED);
+        StageTimer st(c, AKZ_ST_FED, b.chain.stream);
         st.kernel(AKZ_KR_FED_OWN, rem, lv.w, lv.h, n, rest, 0, (uint64_t)lv.w * lv.h * n * rem);
-        AKZ_TRY(fed_impl(c, d1, A, B, b.P(i, AKZ_LFLOW), b.keep_all ? b.P(i, AKZ_LSTEP) : nullptr, lv.w, lv.h, n, lv.tau.data() + n1, rem));
+        AKZ_TRY(fed_impl(c, b.chain, d1, A, B, b.P(i, AKZ_LFLOW), b.keep_all ? b.P(i, AKZ_LSTEP) : nullptr, lv.w, lv.h, n, lv.tau.data() + n1, rem));
     }
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
@@ -325,27 +321,27 @@ int level_by_launches(BeginState& b, size_t i, float* A, float* B) {
         fed_in = half_buf;
     }
     if (i == 1 && b.head_fused && b.rt.level1_clone) {  // Lsmooth is k_head's; Lflow = pm_g2 of the Scharr pair k_head left in level 0's Lx / Ly
-        StageTimer st(c, AKZ_ST_PREP);
-        launch::flow_from_pair(b.ls, b.P(0, AKZ_LX), b.P(0, AKZ_LY), b.P(1, AKZ_LFLOW), lv.w, lv.h, n, b.r->d_k, lv.octave);
+        StageTimer st(c, AKZ_ST_PREP, b.chain.stream);
+        launch::flow_from_pair(b.chain.stream, b.P(0, AKZ_LX), b.P(0, AKZ_LY), b.P(1, AKZ_LFLOW), lv.w, lv.h, n, b.r->d_k, lv.octave);
     } else if (!b.prepared[i]) {
-        StageTimer st(c, AKZ_ST_PREP);
+        StageTimer st(c, AKZ_ST_PREP, b.chain.stream);
         (b.rt.lv[i].prep == Prep::Stream ? launch::prep_stream : launch::prep_fused)(
-            b.ls, b.P(i - 1, AKZ_LT), half, half_buf, b.P(i, AKZ_LSMOOTH), b.P(i, AKZ_LFLOW), lv.w, lv.h, pv.w, pv.h, n, b.g1.data(), b.r->d_k, lv.octave);
+            b.chain.stream, b.P(i - 1, AKZ_LT), half, half_buf, b.P(i, AKZ_LSMOOTH), b.P(i, AKZ_LFLOW), lv.w, lv.h, pv.w, pv.h, n, b.g1.data(), b.r->d_k, lv.octave);
     }
-    if (b.keep_all && n_tau == 0) AKZ_HIP_TRY(hipMemsetAsync(b.P(i, AKZ_LSTEP), 0, plane_bytes(lv.w, lv.h, n), b.ls));
+    if (b.keep_all && n_tau == 0) AKZ_HIP_TRY(hipMemsetAsync(b.P(i, AKZ_LSTEP), 0, plane_bytes(lv.w, lv.h, n), b.chain.stream));
     launch::FedNextPrep np{};
     const bool ride = i + 1 < b.L() && b.rt.lv[i + 1].may_ride;
     if (ride) np = launch::FedNextPrep{b.P(i + 1, AKZ_LSMOOTH), b.P(i + 1, AKZ_LFLOW), b.g1.data(), b.r->d_k, b.r->plan[i + 1].octave};
     bool rode = false;
-    StageTimer st(c, AKZ_ST_FED);
+    StageTimer st(c, AKZ_ST_FED, b.chain.stream);
     st.kernel(AKZ_KR_FED_OWN, n_tau, lv.w, lv.h, n, fed_num_launches(c, n_tau, lv.w, lv.h, n), 0, (uint64_t)lv.w * lv.h * n * n_tau);
-    AKZ_TRY(fed_impl(c, fed_in, A, B, b.P(i, AKZ_LFLOW), b.keep_all ? b.P(i, AKZ_LSTEP) : nullptr, lv.w, lv.h, n, lv.tau.data(), n_tau,
+    AKZ_TRY(fed_impl(c, b.chain, fed_in, A, B, b.P(i, AKZ_LFLOW), b.keep_all ? b.P(i, AKZ_LSTEP) : nullptr, lv.w, lv.h, n, lv.tau.data(), n_tau,
                      ride ? &np : nullptr, &rode));
     b.prepared[i + 1] = rode ? 1 : 0;
     return AKZ_OK;
 }
 
-// ---- levels [lo, hi) of the chain (lib.rs:78-119) on b.ls (c->stream is b.ls while this runs) ----
+// ---- levels [lo, hi) of the chain (lib.rs:78-119) on b.chain.stream ----
 int run_levels(BeginState& b, size_t lo, size_t hi) {
     akz_ctx* c = b.c;
     const std::vector<LevelPlan>& plan = b.r->plan;
@@ -361,7 +357,26 @@ int run_levels(BeginState& b, size_t lo, size_t hi) {
     return AKZ_OK;
 }
 
-// ---- detectors: levels [lo, hi) on stream `on` (c->stream is `on` while this runs) ----
+// One launch per chunk of up to `maxn` levels of a set (levels of one sigma_size); the kernel row carries the shape of the chunk's
+// first level (the largest, in a march set).
+using DetSetLaunch = void (*)(hipStream_t, uint32_t, const launch::DetLevelDesc*, uint32_t, uint32_t, float, Candidate*, uint32_t, uint32_t*);
+void detector_set(BeginState& b, hipStream_t on, DetSetLaunch go, uint32_t maxn, uint32_t kind, uint32_t sigma, const std::vector<launch::DetLevelDesc>& v) {
+    akz_ctx* c = b.c;
+    for (size_t i = 0; i < v.size(); i += maxn) {
+        const uint32_t cnt = (uint32_t)std::min<size_t>(maxn, v.size() - i);
+        StageTimer st(c, AKZ_ST_DETECTOR, on);
+        if (c->profiling) {
+            c->prof.det_launches += 1;
+            uint64_t set_px = 0;
+            for (size_t j = i; j < i + cnt; ++j) set_px += (uint64_t)v[j].w * v[j].h * b.n;
+            c->prof.det_px += set_px;
+            st.kernel(kind, sigma, v[i].w, v[i].h, b.n, 1, set_px);
+        }
+        go(on, sigma, v.data() + i, cnt, b.n, (float)b.r->cfg.detector_threshold, b.d_cand, b.cap, b.d_count);
+    }
+}
+
+// ---- detectors: levels [lo, hi) on f.stream ----
 // The detector of level l needs only Lsmooth_l; its launches follow the whole diffusion chain on the same stream (running them on
 // a side stream next to the diffusion was +3 % with the round-1 kernels and is -15 % with the column march, which
 // saturates the store path on its own; with only the half-resolution octave's detectors on the side stream it is
@@ -371,10 +386,11 @@ int run_levels(BeginState& b, size_t lo, size_t hi) {
 // the extrema test are the job's): one launch per set of up to launch::detector_march_set_max() levels, largest first, when
 // sched[11] asks for it (kDetSetsByDefault: DESIGN.md 4; sched[11] = 1: one launch per level, 2 / 11 .. 14: sets)
 constexpr bool kDetSetsByDefault = true;
-int detectors(BeginState& b, size_t lo, size_t hi, hipStream_t on) {
+int detectors(BeginState& b, size_t lo, size_t hi, const JobForm& f) {
     akz_ctx* c = b.c;
     const akz_config& cfg = b.r->cfg;
     const uint32_t n = b.n;
+    const hipStream_t on = f.stream;
     std::map<uint32_t, std::vector<launch::DetLevelDesc>> sets;
     std::map<std::pair<uint32_t, uint32_t>, std::vector<launch::DetLevelDesc>> march_sets;
     const bool by_sets = c->sched[11] == 0 ? kDetSetsByDefault : c->sched[11] != 1;
@@ -382,58 +398,29 @@ int detectors(BeginState& b, size_t lo, size_t hi, hipStream_t on) {
         if (b.det_done[l]) continue;  // (sched[5]: enqueued behind its level kernel already)
         const LevelPlan& lv = b.r->plan[l];
         const float thr = (float)cfg.detector_threshold, bm = border_margin(lv, cfg);
-        if (by_sets && b.rt.lv[l].det == Det::March) {
-            march_sets[{lv.det_sigma, lv.w & 1u}].push_back(launch::DetLevelDesc{b.P(l, AKZ_LSMOOTH), b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX),
-                                                                                 b.P(l, AKZ_LYY), b.P(l, AKZ_LXY), b.P(l, AKZ_LDET), lv.w, lv.h, (uint32_t)l, bm});
-            continue;
-        }
-        if (b.rt.lv[l].det == Det::TiledSet) {
-            sets[lv.det_sigma].push_back(launch::DetLevelDesc{b.P(l, AKZ_LSMOOTH), b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX),
-                                                             b.P(l, AKZ_LYY), b.P(l, AKZ_LXY), b.P(l, AKZ_LDET), lv.w, lv.h, (uint32_t)l, bm});
+        const Det det = b.rt.lv[l].det;
+        if ((by_sets && det == Det::March) || det == Det::TiledSet) {
+            (det == Det::March ? march_sets[{lv.det_sigma, lv.w & 1u}] : sets[lv.det_sigma])
+                .push_back(launch::DetLevelDesc{b.P(l, AKZ_LSMOOTH), b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX), b.P(l, AKZ_LYY), b.P(l, AKZ_LXY),
+                                                b.P(l, AKZ_LDET), lv.w, lv.h, (uint32_t)l, bm});
             continue;
         }
         if (detector_one_pass(b, l, on)) continue;
         {
-            StageTimer st(c, AKZ_ST_DETECTOR);
-            AKZ_TRY(detector_impl(c, b.P(l, AKZ_LSMOOTH), lv.det_sigma, b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX),
+            StageTimer st(c, AKZ_ST_DETECTOR, on);
+            AKZ_TRY(detector_impl(c, f, b.P(l, AKZ_LSMOOTH), lv.det_sigma, b.P(l, AKZ_LX), b.P(l, AKZ_LY), b.P(l, AKZ_LXX),
                                   b.P(l, AKZ_LYY), b.P(l, AKZ_LXY), b.P(l, AKZ_LDET), lv.w, lv.h, n));
         }
-        StageTimer st(c, AKZ_ST_NMS);
+        StageTimer st(c, AKZ_ST_NMS, on);
         launch::nms(on, b.P(l, AKZ_LDET), lv.w, lv.h, n, (uint64_t)lv.w * lv.h, (uint32_t)l, thr, bm, b.d_cand, b.cap, b.d_count);
     }
     for (auto& kv : march_sets) {
         std::vector<launch::DetLevelDesc>& v = kv.second;
         std::stable_sort(v.begin(), v.end(), [](const launch::DetLevelDesc& x, const launch::DetLevelDesc& y) { return (uint64_t)x.w * x.h > (uint64_t)y.w * y.h; });
-        const uint32_t maxn = launch::detector_march_set_max();
-        for (size_t i = 0; i < v.size(); i += maxn) {
-            const uint32_t cnt = (uint32_t)std::min<size_t>(maxn, v.size() - i);
-            StageTimer st(c, AKZ_ST_DETECTOR, on);
-            if (c->profiling) {
-                c->prof.det_launches += 1;
-                uint64_t set_px = 0;
-                for (size_t j = i; j < i + cnt; ++j) set_px += (uint64_t)v[j].w * v[j].h * n;
-                c->prof.det_px += set_px;
-                st.kernel(AKZ_KR_DETECTOR_MARCH, kv.first.first, v[i].w, v[i].h, n, 1, set_px);  // (the largest level's shape, as the tiled sets)
-            }
-            launch::detector_march_set(on, kv.first.first, v.data() + i, cnt, n, (float)cfg.detector_threshold, b.d_cand, b.cap, b.d_count);
-        }
+        detector_set(b, on, launch::detector_march_set, launch::detector_march_set_max(), AKZ_KR_DETECTOR_MARCH, kv.first.first, v);
     }
-    for (auto& kv : sets) {
-        const uint32_t maxn = launch::detector_tiled_set_max();
-        for (size_t i = 0; i < kv.second.size(); i += maxn) {
-            StageTimer st(c, AKZ_ST_DETECTOR, on);
-            if (c->profiling) {
-                c->prof.det_launches += 1;
-                uint64_t set_px = 0;
-                for (size_t j = i; j < std::min(kv.second.size(), i + maxn); ++j) set_px += (uint64_t)kv.second[j].w * kv.second[j].h * n;
-                c->prof.det_px += set_px;
-                // one launch over several levels of one sigma_size: the row carries the largest level's shape
-                st.kernel(AKZ_KR_DETECTOR_TILED, kv.first, kv.second[i].w, kv.second[i].h, n, 1, set_px);
-            }
-            launch::detector_tiled_set(on, kv.first, kv.second.data() + i, (uint32_t)std::min<size_t>(maxn, kv.second.size() - i),
-                                       n, (float)cfg.detector_threshold, b.d_cand, b.cap, b.d_count);
-        }
-    }
+    for (auto& kv : sets)  // (plan order)
+        detector_set(b, on, launch::detector_tiled_set, launch::detector_tiled_set_max(), AKZ_KR_DETECTOR_TILED, kv.first, kv.second);
     return AKZ_OK;
 }
 
@@ -447,7 +434,7 @@ int detectors(BeginState& b, size_t lo, size_t hi, hipStream_t on) {
 // *done_on: the stream behind whose work the batch's candidate list is complete
 int fork_and_join(BeginState& b, hipStream_t* done_on) {
     akz_ctx* c = b.c;
-    hipStream_t s = b.s;
+    const hipStream_t s = b.form.stream;
     if (!c->coarse) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->coarse, hipStreamNonBlocking));
     hipEvent_t fine_done = StageTimer::get(c);
     AKZ_HIP_TRY(hipEventRecord(fine_done, s));
@@ -457,12 +444,10 @@ int fork_and_join(BeginState& b, hipStream_t* done_on) {
     // The fine detectors are ENQUEUED first: the coarse chain is dozens of small launches, and a caller that is not
     // ahead of the chip -- one synchronous call on a 4K pair -- kept the main stream idle for the 0.19 ms it took to
     // enqueue them (the two streams run side by side either way).
-    AKZ_TRY(detectors(b, 0, b.rt.fork_level, s));
-    b.ls = c->coarse;
-    c->stream = c->coarse;
+    AKZ_TRY(detectors(b, 0, b.rt.fork_level, b.form));
+    b.chain.stream = c->coarse;
     AKZ_TRY(run_levels(b, b.rt.fork_level, b.L()));
-    AKZ_TRY(detectors(b, b.rt.fork_level, b.L(), c->coarse));
-    c->stream = s;
+    AKZ_TRY(detectors(b, b.rt.fork_level, b.L(), b.chain));
     hipEvent_t ev = StageTimer::get(c);
     if (b.rt.own_kernels) {
         AKZ_HIP_TRY(hipEventRecord(ev, s));
@@ -497,14 +482,7 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     if (!out) return AKZ_ERR_INVALID_ARG;
     *out = nullptr;
     AKZ_TRY(bind(c, true, c && c->is_lane));  // (a lane's finish half shares the lane's one stream: begin waits for it)
-    c->big_px = sync_call ? c->big_px_sync : c->big_px_async;  // (akz_gates.hpp)
-    struct GateRestore {  // the per-op entry points (akz_op_*) use the same helpers: they see the begin / finish interface's gate
-        akz_ctx* c;
-        ~GateRestore() {
-            c->big_px = c->big_px_async;
-            c->launch_min_px = akz_ctx::kLaunchMarchPx;
-        }
-    } gate_restore{c};
+    const uint64_t big_px = sync_call ? c->big_px_sync : c->big_px_async;  // (akz_gates.hpp)
     if (!d_imgs || !cfgp || n == 0) {
         set_error("extract: null image/config or empty batch");
         return AKZ_ERR_INVALID_ARG;
@@ -514,10 +492,10 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     AKZ_TRY(job_open(c, "extract_begin", want_slot, w, h, n, flags, *cfgp, o));
     akz_job* job = o.job.get();
     akz_result* r = job->r.get();
-    r->big_px = c->big_px;  // (the finish half may run on another thread while the next job is begun with another gate)
+    r->big_px = big_px;  // (the finish half may run on another thread while the next job is begun with another gate)
     const size_t L = r->plan.size();
     const bool keep_all = (flags & AKZ_KEEP_ALL_PLANES) != 0;
-    hipStream_t s = c->stream;
+    const hipStream_t s = c->stream;
     AKZ_TRY(job_layout(o, begin_planes(L, keep_all)));
 
     job->t_begin_ms = now_ms();
@@ -538,27 +516,18 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     if (!c->pre_ev[0])
         for (hipEvent_t& e : c->pre_ev) AKZ_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     const uint64_t seq = c->begin_seq.load() + 1;  // published when this job's event has been recorded
-    struct StreamRestore {  // the helpers (gaussian_blur_impl, fed_impl, StageTimer, ...) enqueue on c->stream
-        akz_ctx* c;
-        hipStream_t main;
-        ~StreamRestore() { c->stream = main; }
-    } stream_restore{c, s};
     // Jobs below gates::kTiledPrepPx take the TILED preparation family whatever their launches' sizes -- k_blur, k_contrast_max /
     // _hist, k_prep riding on the previous level's last k_fed_own launch, no resident tail: since that epilogue exists the
     // chain of few-microsecond launches beats the streaming kernels and k_level_march up to ~11 Mpx per job (akz_gates.hpp: kTiledPrepPx; profiles/
-    // r06_lone_libm.txt: 2-6 x 1080p, 4-8 x 720p, lone 2-5 Mpx frames 3-9 % faster per call, 0-9 % as a stream).  The helpers
-    // read c->prep_mode: it is swapped for the duration of this begin half (only the automatic mode 2 is overridden).
-    struct PrepModeRestore {
-        akz_ctx* c;
-        int mode;
-        ~PrepModeRestore() { c->prep_mode = mode; }
-    } prep_mode_restore{c, c->prep_mode};
-    if (c->prep_mode == 2 && c->sched[6] == 0 && (uint64_t)w * h * n < gates::kTiledPrepPx) c->prep_mode = 0;
-    const bool big = (uint64_t)w * h * n >= c->big_px;
-    c->launch_min_px = big ? std::min<uint64_t>(akz_ctx::kLaunchMarchPx, (uint64_t)w * h * n) : akz_ctx::kLaunchMarchPx;
+    // r06_lone_libm.txt: 2-6 x 1080p, 4-8 x 720p, lone 2-5 Mpx frames 3-9 % faster per call, 0-9 % as a stream).  Only the
+    // automatic mode 2 is overridden.  A batch-path job marches from its own size on (JobForm::march_min_px).
+    const uint64_t job_px = (uint64_t)w * h * n;
+    const bool big = job_px >= big_px;
+    const bool tiled_family = c->prep_mode == 2 && c->sched[6] == 0 && job_px < gates::kTiledPrepPx;
+    const JobForm form{s, tiled_family ? 0 : c->prep_mode, big ? std::min<uint64_t>(gates::kMarchPx, job_px) : gates::kMarchPx};
     if (big && !c->placed) AKZ_TRY(place_streams(c));
-    const BeginRoute rt = begin_route(c, r->plan, r->cfg, w, h, n, flags, input_ready != nullptr, big);
-    BeginState b{c, r, rt, n, keep_all, s, s, seq, (Candidate*)c->cand_slot[o.slot].p, (uint32_t*)c->count_slot[o.slot].p, cap,
+    const BeginRoute rt = begin_route(c, form, r->plan, r->cfg, w, h, n, flags, input_ready != nullptr, big);
+    BeginState b{c, r, rt, n, keep_all, form, form, seq, (Candidate*)c->cand_slot[o.slot].p, (uint32_t*)c->count_slot[o.slot].p, cap,
                  {}, std::vector<char>(L, 0), std::vector<char>(L + 1, 0)};
 
     AKZ_TRY(level0<T>(b, d_imgs, input_ready));
@@ -585,7 +554,7 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
 
     hipStream_t done_on = s;
     if (rt.fork_level < L) AKZ_TRY(fork_and_join(b, &done_on));
-    else AKZ_TRY(detectors(b, 0, L, s));
+    else AKZ_TRY(detectors(b, 0, L, form));
     AKZ_HIP_TRY(hipGetLastError());
     job->nms_done = StageTimer::get(c);
     AKZ_HIP_TRY(hipEventRecord(job->nms_done, done_on));

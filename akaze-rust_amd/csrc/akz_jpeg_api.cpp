@@ -88,7 +88,7 @@ int reconstruct(akz_ctx* c, int slot, const Staged& st, uint8_t* d_dst) {
     AKZ_TRY(ensure(c, c->jpeg_plane, f.plane_bytes));
     uint8_t* d_plane = (uint8_t*)c->jpeg_plane.p;
     {
-        StageTimer t(c, kStageIngest);
+        StageTimer t(c, kStageIngest, s);
         t.kernel(AKZ_KR_JPEG_COPY, f.nc, f.width, f.height, 1, 1, coef_bytes);
         AKZ_HIP_TRY(hipMemcpyAsync(c->jpeg_coef.p, c->jpeg_pin[slot].p, coef_bytes, hipMemcpyHostToDevice, s));
     }
@@ -99,12 +99,12 @@ int reconstruct(akz_ctx* c, int slot, const Staged& st, uint8_t* d_dst) {
             AKZ_HIP_TRY(hipMemsetAsync(d_plane + f.c[k].plane_off + blocks, 0, f.c[k].plane_len - blocks, s));
     }
     {
-        StageTimer t(c, kStageIngest);
+        StageTimer t(c, kStageIngest, s);
         t.kernel(AKZ_KR_JPEG_IDCT, f.nc, f.width, f.height, 1, 1, (uint64_t)f.nblocks * 64);
         launch::jpeg_idct(s, f, (const int16_t*)c->jpeg_coef.p, d_plane);
     }
     {
-        StageTimer t(c, kStageIngest);
+        StageTimer t(c, kStageIngest, s);
         t.kernel(AKZ_KR_JPEG_LUMA, f.nc, f.width, f.height, 1, 1, (uint64_t)f.width * f.height);
         launch::jpeg_luma(s, f, d_plane, d_dst);
     }

@@ -18,8 +18,7 @@ static int check_plane_args(const void* a, const void* b, uint32_t w, uint32_t h
 }
 
 template <typename T>
-int gaussian_blur_impl(akz_ctx* c, const T* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n,
-                              float sigma) {
+int gaussian_blur_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n, float sigma) {
     const size_t ks = gaussian_kernel_size(sigma);
     if (ks > (size_t)kMaxTaps || !(sigma > 0.0f)) {
         set_error("gaussian_blur: sigma must be in (0, 6]");
@@ -31,49 +30,48 @@ int gaussian_blur_impl(akz_ctx* c, const T* d_in, float* d_out, uint32_t w, uint
     AKZ_TRY(check_plane_args(d_in, d_out, w, h, n, t.hw));
     constexpr bool is_u8 = std::is_same<T, uint8_t>::value;
     // large batches: the column march (HBM-bound: 0.33 GB of a 32-frame 1080p batch)
-    const uint64_t blur_march_min_px = c->launch_min_px;
-    if ((const void*)d_in != (const void*)d_out && (c->prep_mode == 3 || (c->prep_mode == 2 && (uint64_t)w * h * n >= blur_march_min_px)) &&
+    if ((const void*)d_in != (const void*)d_out && (f.prep_mode == 3 || (f.prep_mode == 2 && (uint64_t)w * h * n >= f.march_min_px)) &&
         launch::blur5_march_supported(w, h, (uint32_t)k.size())) {
-        if constexpr (is_u8) launch::blur5_march_u8(c->stream, d_in, d_out, w, h, n, k.data());
-        else launch::blur5_march_f32(c->stream, d_in, d_out, w, h, n, k.data());
+        if constexpr (is_u8) launch::blur5_march_u8(f.stream, d_in, d_out, w, h, n, k.data());
+        else launch::blur5_march_f32(f.stream, d_in, d_out, w, h, n, k.data());
         AKZ_HIP_TRY(hipGetLastError());
         return AKZ_OK;
     }
-    if ((const void*)d_in != (const void*)d_out && c->prep_mode != 0 &&
+    if ((const void*)d_in != (const void*)d_out && f.prep_mode != 0 &&
         launch::blur5_stream_supported(w, h, (uint32_t)k.size(), is_u8) &&
-        (!is_u8 || ((uintptr_t)d_in & 3u) == 0) && (c->prep_mode == 1 || (uint64_t)w * h * n >= c->stream_min_px)) {
-        if constexpr (is_u8) launch::blur5_stream_u8(c->stream, d_in, d_out, w, h, n, k.data());
-        else launch::blur5_stream_f32(c->stream, d_in, d_out, w, h, n, k.data());
+        (!is_u8 || ((uintptr_t)d_in & 3u) == 0) && (f.prep_mode == 1 || (uint64_t)w * h * n >= c->stream_min_px)) {
+        if constexpr (is_u8) launch::blur5_stream_u8(f.stream, d_in, d_out, w, h, n, k.data());
+        else launch::blur5_stream_f32(f.stream, d_in, d_out, w, h, n, k.data());
         AKZ_HIP_TRY(hipGetLastError());
         return AKZ_OK;
     }
     if (launch::blur_fused_supported((uint32_t)k.size()) && (const void*)d_in != (const void*)d_out) {
         if constexpr (std::is_same<T, uint8_t>::value)
-            launch::blur_fused_u8(c->stream, d_in, d_out, w, h, n, k.data(), (uint32_t)k.size());
+            launch::blur_fused_u8(f.stream, d_in, d_out, w, h, n, k.data(), (uint32_t)k.size());
         else
-            launch::blur_fused_f32(c->stream, d_in, d_out, w, h, n, k.data(), (uint32_t)k.size());
+            launch::blur_fused_f32(f.stream, d_in, d_out, w, h, n, k.data(), (uint32_t)k.size());
         AKZ_HIP_TRY(hipGetLastError());
         return AKZ_OK;
     }
     AKZ_TRY(ensure(c, c->scratch[0], plane_bytes(w, h, n)));
     float* tmp = (float*)c->scratch[0].p;
-    if constexpr (std::is_same<T, uint8_t>::value) launch::filter_h_u8(c->stream, d_in, tmp, w, h, n, t);
-    else launch::filter_h_f32(c->stream, d_in, tmp, w, h, n, t);
-    launch::filter_v_f32(c->stream, tmp, d_out, w, h, n, t);
+    if constexpr (std::is_same<T, uint8_t>::value) launch::filter_h_u8(f.stream, d_in, tmp, w, h, n, t);
+    else launch::filter_h_f32(f.stream, d_in, tmp, w, h, n, t);
+    launch::filter_v_f32(f.stream, tmp, d_out, w, h, n, t);
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
 }
-template int gaussian_blur_impl<float>(akz_ctx*, const float*, float*, uint32_t, uint32_t, uint32_t, float);
-template int gaussian_blur_impl<uint8_t>(akz_ctx*, const uint8_t*, float*, uint32_t, uint32_t, uint32_t, float);
+template int gaussian_blur_impl<float>(akz_ctx*, const JobForm&, const float*, float*, uint32_t, uint32_t, uint32_t, float);
+template int gaussian_blur_impl<uint8_t>(akz_ctx*, const JobForm&, const uint8_t*, float*, uint32_t, uint32_t, uint32_t, float);
 
 // scharr_horizontal / scharr_vertical (derivatives.rs:41-65) through scratch[0]
-static int scharr_impl(akz_ctx* c, const float* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n, bool x_order,
+static int scharr_impl(akz_ctx* c, const JobForm& f, const float* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n, bool x_order,
                        uint32_t sigma) {
     const Taps tm = taps_scharr_main(sigma), to = taps_scharr_off(sigma);
     AKZ_TRY(ensure(c, c->scratch[0], plane_bytes(w, h, n)));
     float* tmp = (float*)c->scratch[0].p;
-    launch::filter_h_f32(c->stream, d_in, tmp, w, h, n, x_order ? tm : to);
-    launch::filter_v_f32(c->stream, tmp, d_out, w, h, n, x_order ? to : tm);
+    launch::filter_h_f32(f.stream, d_in, tmp, w, h, n, x_order ? tm : to);
+    launch::filter_v_f32(f.stream, tmp, d_out, w, h, n, x_order ? to : tm);
     return AKZ_OK;
 }
 
@@ -84,10 +82,10 @@ static int scharr_impl(akz_ctx* c, const float* d_in, float* d_out, uint32_t w, 
 // later); d_blurred: where the contrast factor's blur of Lt0 goes (level 1's Lsmooth, or NULL: context scratch).
 // sched[10] = 1: the separate stages (measurement).
 template <typename T>
-int head_impl(akz_ctx* c, const T* d_in, float* d_lt0, float* d_blurred, float* d_gx, float* d_gy, uint32_t w, uint32_t h, uint32_t n, float sigma0,
+int head_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_lt0, float* d_blurred, float* d_gx, float* d_gy, uint32_t w, uint32_t h, uint32_t n, float sigma0,
               double percentile, double gscale, uint64_t nbins, double* d_k_out, bool* fused, uint32_t* d_zero_word) {
     *fused = false;
-    if (c->prep_mode != 0 || c->sched[10] != 0 || !(sigma0 > 0.0f) || !(gscale > 0.0) || nbins == 0 || nbins > 4096) return AKZ_OK;
+    if (f.prep_mode != 0 || c->sched[10] != 0 || !(sigma0 > 0.0f) || !(gscale > 0.0) || nbins == 0 || nbins > 4096) return AKZ_OK;
     const size_t ks0 = gaussian_kernel_size(sigma0), ks1 = gaussian_kernel_size((float)gscale);
     if (!launch::head_fused_supported(w, h, (uint32_t)ks0, (uint32_t)ks1) || (const void*)d_in == (const void*)d_lt0) return AKZ_OK;
     const std::vector<float> k5 = gaussian_kernel(sigma0, ks0), g3 = gaussian_kernel((float)gscale, ks1);
@@ -99,22 +97,22 @@ int head_impl(akz_ctx* c, const T* d_in, float* d_lt0, float* d_blurred, float* 
     const size_t known_zero = c->small_zero_p == c->small.p ? c->small_zero : 0;
     c->small_zero = 0;  // (until both launches are enqueued: an error in between leaves the scratch in an unknown state)
     if (known_zero < small_bytes)  // (first use, a larger job, or another family used it last)
-        AKZ_HIP_TRY(hipMemsetAsync(c->small.p, 0, small_bytes, c->stream));
+        AKZ_HIP_TRY(hipMemsetAsync(c->small.p, 0, small_bytes, f.stream));
     float* blurred = d_blurred;  // (level 1's Lsmooth where level 1 continues the octave: the same blur of Lt0, lib.rs:92-95)
     if (!blurred) {
         AKZ_TRY(ensure(c, c->scratch[1], plane_bytes(w, h, n)));
         blurred = (float*)c->scratch[1].p;
     }
     {
-        StageTimer st(c, AKZ_ST_BLUR0);
+        StageTimer st(c, AKZ_ST_BLUR0, f.stream);
         if constexpr (std::is_same<T, uint8_t>::value)
-            launch::head_fused_u8(c->stream, d_in, d_lt0, blurred, d_gx, d_gy, w, h, n, k5.data(), g3.data(), d_smax, d_zero_word);
+            launch::head_fused_u8(f.stream, d_in, d_lt0, blurred, d_gx, d_gy, w, h, n, k5.data(), g3.data(), d_smax, d_zero_word);
         else
-            launch::head_fused_f32(c->stream, d_in, d_lt0, blurred, d_gx, d_gy, w, h, n, k5.data(), g3.data(), d_smax, d_zero_word);
+            launch::head_fused_f32(f.stream, d_in, d_lt0, blurred, d_gx, d_gy, w, h, n, k5.data(), g3.data(), d_smax, d_zero_word);
     }
     {
-        StageTimer st(c, AKZ_ST_CONTRAST);
-        launch::contrast_hist_final(c->stream, d_gx, d_gy, w, h, n, d_smax, (uint32_t)nbins, d_hist, d_done, percentile, d_k_out);
+        StageTimer st(c, AKZ_ST_CONTRAST, f.stream);
+        launch::contrast_hist_final(f.stream, d_gx, d_gy, w, h, n, d_smax, (uint32_t)nbins, d_hist, d_done, percentile, d_k_out);
     }
     AKZ_HIP_TRY(hipGetLastError());
     c->small_zero_p = c->small.p;
@@ -122,11 +120,11 @@ int head_impl(akz_ctx* c, const T* d_in, float* d_lt0, float* d_blurred, float* 
     *fused = true;
     return AKZ_OK;
 }
-template int head_impl<float>(akz_ctx*, const float*, float*, float*, float*, float*, uint32_t, uint32_t, uint32_t, float, double, double, uint64_t, double*, bool*, uint32_t*);
-template int head_impl<uint8_t>(akz_ctx*, const uint8_t*, float*, float*, float*, float*, uint32_t, uint32_t, uint32_t, float, double, double, uint64_t, double*, bool*, uint32_t*);
+template int head_impl<float>(akz_ctx*, const JobForm&, const float*, float*, float*, float*, float*, uint32_t, uint32_t, uint32_t, float, double, double, uint64_t, double*, bool*, uint32_t*);
+template int head_impl<uint8_t>(akz_ctx*, const JobForm&, const uint8_t*, float*, float*, float*, float*, uint32_t, uint32_t, uint32_t, float, double, double, uint64_t, double*, bool*, uint32_t*);
 
-int contrast_impl(akz_ctx* c, const float* d_in, uint32_t w, uint32_t h, uint32_t n, double percentile,
-                         double gscale, uint64_t nbins, double* d_k_out) {
+int contrast_impl(akz_ctx* c, const JobForm& f, const float* d_in, uint32_t w, uint32_t h, uint32_t n, double percentile, double gscale,
+                  uint64_t nbins, double* d_k_out) {
     if (nbins == 0 || nbins > 4096) {
         set_error("contrast_factor: num_bins must be in 1..4096");
         return AKZ_ERR_INVALID_ARG;
@@ -143,28 +141,28 @@ int contrast_impl(akz_ctx* c, const float* d_in, uint32_t w, uint32_t h, uint32_
     unsigned long long* d_hmax = (unsigned long long*)c->small.p;
     uint32_t* d_hist = (uint32_t*)((char*)c->small.p + (size_t)n * 8);
     double* d_thr = (double*)((char*)c->small.p + small_bytes);
-    AKZ_HIP_TRY(hipMemsetAsync(c->small.p, 0, small_bytes, c->stream));
+    AKZ_HIP_TRY(hipMemsetAsync(c->small.p, 0, small_bytes, f.stream));
     c->small_zero = 0;  // (these passes do not clean up after themselves)
     const size_t ks = gaussian_kernel_size((float)gscale);
-    const bool stream = c->prep_mode != 0 && gscale > 0.0 && launch::contrast_stream_supported(w, h, (uint32_t)ks, (uint32_t)nbins) &&
-                        (c->prep_mode == 1 || (uint64_t)w * h * n >= c->stream_min_px);
-    const bool march = gscale > 0.0 && (c->prep_mode == 3 || (c->prep_mode == 2 && (uint64_t)w * h * n >= c->launch_min_px)) &&
+    const bool stream = f.prep_mode != 0 && gscale > 0.0 && launch::contrast_stream_supported(w, h, (uint32_t)ks, (uint32_t)nbins) &&
+                        (f.prep_mode == 1 || (uint64_t)w * h * n >= c->stream_min_px);
+    const bool march = gscale > 0.0 && (f.prep_mode == 3 || (f.prep_mode == 2 && (uint64_t)w * h * n >= f.march_min_px)) &&
                        launch::contrast_march_supported(w, h, (uint32_t)ks, (uint32_t)nbins);
     if (march) {
         const std::vector<float> g3 = gaussian_kernel((float)gscale, ks);
-        launch::contrast_march(c->stream, d_in, w, h, n, g3.data(), d_hmax, (uint32_t)nbins, d_hist, d_thr);
+        launch::contrast_march(f.stream, d_in, w, h, n, g3.data(), d_hmax, (uint32_t)nbins, d_hist, d_thr);
     } else if (stream) {
         // both passes recompute blur + Scharr from the input in registers: no blurred plane is written or re-read
         const std::vector<float> g3 = gaussian_kernel((float)gscale, ks);
-        launch::contrast_stream(c->stream, d_in, w, h, n, g3.data(), d_hmax, (uint32_t)nbins, d_hist, d_thr);
+        launch::contrast_stream(f.stream, d_in, w, h, n, g3.data(), d_hmax, (uint32_t)nbins, d_hist, d_thr);
     } else {
         AKZ_TRY(ensure(c, c->scratch[1], plane_bytes(w, h, n)));
         float* blurred = (float*)c->scratch[1].p;
-        AKZ_TRY(gaussian_blur_impl<float>(c, d_in, blurred, w, h, n, (float)gscale));
-        launch::contrast_max(c->stream, blurred, w, h, n, d_hmax);
-        launch::contrast_hist(c->stream, blurred, w, h, n, d_hmax, (uint32_t)nbins, d_hist);
+        AKZ_TRY(gaussian_blur_impl<float>(c, f, d_in, blurred, w, h, n, (float)gscale));
+        launch::contrast_max(f.stream, blurred, w, h, n, d_hmax);
+        launch::contrast_hist(f.stream, blurred, w, h, n, d_hmax, (uint32_t)nbins, d_hist);
     }
-    launch::contrast_final(c->stream, d_hmax, d_hist, (uint32_t)nbins, percentile, n, d_k_out);
+    launch::contrast_final(f.stream, d_hmax, d_hist, (uint32_t)nbins, percentile, n, d_k_out);
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
 }
@@ -189,12 +187,12 @@ uint32_t fed_num_launches(const akz_ctx* c, uint32_t n_tau, uint32_t w, uint32_t
 float* fed_dst(uint32_t launches, uint32_t k /*1-based*/, float* A, float* B) {
     return ((launches - k) % 2 == 0) ? A : B;
 }
-int fed_impl(akz_ctx* c, const float* in, float* A, float* B, const float* lflow, float* lstep, uint32_t w,
-                    uint32_t h, uint32_t n, const double* taus, uint32_t n_tau, const launch::FedNextPrep* next, bool* next_done) {
+int fed_impl(akz_ctx* c, const JobForm& f, const float* in, float* A, float* B, const float* lflow, float* lstep, uint32_t w, uint32_t h,
+             uint32_t n, const double* taus, uint32_t n_tau, const launch::FedNextPrep* next, bool* next_done) {
     if (next_done) *next_done = false;
     const uint32_t launches = fed_num_launches(c, n_tau, w, h, n);
     if (launches == 0) {
-        if (in != A) AKZ_HIP_TRY(hipMemcpyAsync(A, in, plane_bytes(w, h, n), hipMemcpyDeviceToDevice, c->stream));
+        if (in != A) AKZ_HIP_TRY(hipMemcpyAsync(A, in, plane_bytes(w, h, n), hipMemcpyDeviceToDevice, f.stream));
         return AKZ_OK;
     }
     const float* cur = in;
@@ -208,7 +206,7 @@ int fed_impl(akz_ctx* c, const float* in, float* A, float* B, const float* lflow
         if (c->fed_mode == 0) {
             const float half_tau = 0.5f * (float)taus[done];
             done += 1;
-            launch::fed_step(c->stream, cur, lflow, dst, (done == n_tau) ? lstep : nullptr, w, h, n, half_tau);
+            launch::fed_step(f.stream, cur, lflow, dst, (done == n_tau) ? lstep : nullptr, w, h, n, half_tau);
         } else {
             const uint32_t cnt = (n_tau - done + (launches - k + 1) - 1) / (launches - k + 1);  // balanced chunks
             float ht[2 * kFedMaxFuse];
@@ -216,7 +214,7 @@ int fed_impl(akz_ctx* c, const float* in, float* A, float* B, const float* lflow
             done += cnt;
             // the level's last launch may carry the next level's preparation (k_fed_own's epilogue)
             const launch::FedNextPrep* np = (k == launches && next && launch::fed_epilogue_supported(w, h, cnt)) ? next : nullptr;
-            launch::fed_fused(c->stream, cur, lflow, dst, (done == n_tau) ? lstep : nullptr, w, h, n, ht, cnt, np);
+            launch::fed_fused(f.stream, cur, lflow, dst, (done == n_tau) ? lstep : nullptr, w, h, n, ht, cnt, np);
             if (np && next_done) *next_done = true;
         }
         cur = dst;
@@ -235,34 +233,32 @@ int fed_impl(akz_ctx* c, const float* in, float* A, float* B, const float* lflow
 // (k_detector_march, akz_march.hip: large launches).  Measured on MI355X per level of a 32-frame batch, all planes
 // kept (tools/march_probe.py, microseconds, sigma_size 3): 1920x1080 555 / 503 / 350, 960x540 140 / 124 / 82,
 // 480x270 45 / 41 / 66 (pair / tiled / march): the march from 8 Mpx per launch on.
-int detector_family(const akz_ctx* c, uint32_t sigma, uint32_t w, uint32_t h, uint32_t n, float border_m,
-                           bool keep_second, bool nms) {
-    (void)keep_second;
+int detector_family(const akz_ctx* c, const JobForm& f, uint32_t sigma, uint32_t w, uint32_t h, uint32_t n, float border_m, bool nms) {
     if (c->det_mode == 0) return 0;
     if (c->det_mode == 4) return launch::detector_tiled_fused_supported(sigma) ? 4 : 0;
     if (c->det_mode == 5) return launch::detector_march_supported(sigma, w, h, border_m, nms) ? 5 : 0;
-    const uint64_t march_min = c->launch_min_px;
+    const uint64_t march_min = f.march_min_px;
     const uint64_t px = (uint64_t)w * h * n;
     if (px >= march_min && launch::detector_march_supported(sigma, w, h, border_m, nms)) return 5;
     if (px < march_min && launch::detector_tiled_fused_supported(sigma)) return 4;
     return 0;
 }
 
-int detector_impl(akz_ctx* c, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx,
-                         float* lyy, float* lxy, float* ldet_out, uint32_t w, uint32_t h, uint32_t n) {
+int detector_impl(akz_ctx* c, const JobForm& f, const float* lsmooth, uint32_t sigma, float* lx, float* ly, float* lxx, float* lyy,
+                  float* lxy, float* ldet_out, uint32_t w, uint32_t h, uint32_t n) {
     if (sigma == 0 || 2 * sigma + 1 > (uint32_t)kMaxTaps) {
         set_error("detector_response: sigma_size must be in 1..6");
         return AKZ_ERR_INVALID_ARG;
     }
     AKZ_TRY(check_plane_args(lsmooth, ldet_out, w, h, n, (int)sigma));
-    if (const int fam = detector_family(c, sigma, w, h, n, 0.0f, lxx && lyy && lxy, false)) {
+    if (const int fam = detector_family(c, f, sigma, w, h, n, 0.0f, false)) {
         (fam == 5 ? launch::detector_march : launch::detector_tiled_fused)(
-            c->stream, lsmooth, sigma, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n, 0, 0.0f, 0.0f, nullptr, 0, nullptr);
+            f.stream, lsmooth, sigma, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n, 0, 0.0f, 0.0f, nullptr, 0, nullptr);
         AKZ_HIP_TRY(hipGetLastError());
         return AKZ_OK;
     }
     if (launch::detector_fused_supported(sigma)) {
-        launch::detector_fused(c->stream, lsmooth, sigma, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n);
+        launch::detector_fused(f.stream, lsmooth, sigma, lx, ly, lxx, lyy, lxy, ldet_out, w, h, n);
         AKZ_HIP_TRY(hipGetLastError());
         return AKZ_OK;
     }
@@ -270,13 +266,13 @@ int detector_impl(akz_ctx* c, const float* lsmooth, uint32_t sigma, float* lx, f
     if (!lxx) { AKZ_TRY(ensure(c, c->scratch[2], pb)); lxx = (float*)c->scratch[2].p; }
     if (!lyy) { AKZ_TRY(ensure(c, c->scratch[3], pb)); lyy = (float*)c->scratch[3].p; }
     if (!lxy) { AKZ_TRY(ensure(c, c->scratch[4], pb)); lxy = (float*)c->scratch[4].p; }
-    AKZ_TRY(scharr_impl(c, lsmooth, lx, w, h, n, true, sigma));   // Lx  = scharr(Lsmooth, x)
-    AKZ_TRY(scharr_impl(c, lsmooth, ly, w, h, n, false, sigma));  // Ly  = scharr(Lsmooth, y)
-    AKZ_TRY(scharr_impl(c, lx, lxx, w, h, n, true, sigma));       // Lxx = scharr(Lx, x)
-    AKZ_TRY(scharr_impl(c, ly, lyy, w, h, n, false, sigma));      // Lyy = scharr(Ly, y)
-    AKZ_TRY(scharr_impl(c, lx, lxy, w, h, n, false, sigma));      // Lxy = scharr(Lx, y)
+    AKZ_TRY(scharr_impl(c, f, lsmooth, lx, w, h, n, true, sigma));   // Lx  = scharr(Lsmooth, x)
+    AKZ_TRY(scharr_impl(c, f, lsmooth, ly, w, h, n, false, sigma));  // Ly  = scharr(Lsmooth, y)
+    AKZ_TRY(scharr_impl(c, f, lx, lxx, w, h, n, true, sigma));       // Lxx = scharr(Lx, x)
+    AKZ_TRY(scharr_impl(c, f, ly, lyy, w, h, n, false, sigma));      // Lyy = scharr(Ly, y)
+    AKZ_TRY(scharr_impl(c, f, lx, lxy, w, h, n, false, sigma));      // Lxy = scharr(Lx, y)
     const uint32_t quat = sigma * sigma * sigma * sigma;
-    launch::ldet(c->stream, lxx, lyy, lxy, ldet_out, (uint64_t)w * h * n, (float)quat);
+    launch::ldet(f.stream, lxx, lyy, lxy, ldet_out, (uint64_t)w * h * n, (float)quat);
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
 }
@@ -306,12 +302,12 @@ int akz_op_vertical_filter(akz_ctx* c, const float* d_in, float* d_out, uint32_t
 int akz_op_gaussian_blur(akz_ctx* c, const float* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n,
                          float sigma) {
     AKZ_TRY(bind(c));
-    return gaussian_blur_impl<float>(c, d_in, d_out, w, h, n, sigma);
+    return gaussian_blur_impl<float>(c, no_job_form(c), d_in, d_out, w, h, n, sigma);
 }
 int akz_op_gaussian_blur_u8(akz_ctx* c, const uint8_t* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n,
                             float sigma) {
     AKZ_TRY(bind(c));
-    return gaussian_blur_impl<uint8_t>(c, d_in, d_out, w, h, n, sigma);
+    return gaussian_blur_impl<uint8_t>(c, no_job_form(c), d_in, d_out, w, h, n, sigma);
 }
 int akz_op_half_size(akz_ctx* c, const float* d_in, float* d_out, uint32_t w, uint32_t h, uint32_t n) {
     AKZ_TRY(bind(c));
@@ -340,7 +336,7 @@ int akz_op_scharr(akz_ctx* c, const float* d_in, float* d_out, uint32_t w, uint3
     AKZ_TRY(check_plane_args(d_in, d_out, w, h, n, (int)sigma));
     // derivatives.rs:118-122: with both orders the reference takes the HORIZONTAL derivative twice and adds the two
     // images (`sqrt_squared` is `image_1 += image_2`, image.rs:218-231)
-    AKZ_TRY(scharr_impl(c, d_in, d_out, w, h, n, x_order != 0, sigma));
+    AKZ_TRY(scharr_impl(c, no_job_form(c), d_in, d_out, w, h, n, x_order != 0, sigma));
     if (x_order != 0 && y_order != 0) launch::accumulate(c->stream, d_out, d_out, (uint64_t)w * h * n);
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
@@ -358,7 +354,7 @@ int akz_op_contrast_factor(akz_ctx* c, const float* d_in, uint32_t w, uint32_t h
                            double gscale, uint64_t num_bins, double* d_k_out) {
     AKZ_TRY(bind(c));
     if (!d_in || !d_k_out || n == 0) return AKZ_ERR_INVALID_ARG;
-    return contrast_impl(c, d_in, w, h, n, percentile, gscale, num_bins, d_k_out);
+    return contrast_impl(c, no_job_form(c), d_in, w, h, n, percentile, gscale, num_bins, d_k_out);
 }
 int akz_op_flow(akz_ctx* c, const float* d_lsmooth, float* d_lflow, uint32_t w, uint32_t h, uint32_t n,
                 const double* d_k, uint32_t k_scale_pow) {
@@ -380,16 +376,16 @@ int akz_op_fed_steps(akz_ctx* c, float* d_lt, const float* d_lflow, float* d_lst
     float* B = (float*)c->scratch[5].p;
     float* in = (float*)c->scratch[3].p;
     AKZ_HIP_TRY(hipMemcpyAsync(in, d_lt, plane_bytes(w, h, n), hipMemcpyDeviceToDevice, c->stream));
-    StageTimer st(c, AKZ_ST_FED);  // the launches alone, without the copy above (stand-alone roofline legs of bench.py)
+    StageTimer st(c, AKZ_ST_FED, c->stream);  // the launches alone, without the copy above (stand-alone roofline legs of bench.py)
     st.kernel(AKZ_KR_FED_OWN, n_tau, w, h, n, fed_num_launches(c, n_tau, w, h, n), 0, (uint64_t)w * h * n * n_tau);
-    return fed_impl(c, in, d_lt, B, d_lflow, d_lstep, w, h, n, taus, n_tau);
+    return fed_impl(c, no_job_form(c), in, d_lt, B, d_lflow, d_lstep, w, h, n, taus, n_tau);
 }
 int akz_op_detector_response(akz_ctx* c, const float* d_lsmooth, uint32_t sigma_size, float* d_lx, float* d_ly,
                              float* d_lxx, float* d_lyy, float* d_lxy, float* d_ldet, uint32_t w, uint32_t h,
                              uint32_t n) {
     AKZ_TRY(bind(c));
     if (!d_lx || !d_ly) return AKZ_ERR_INVALID_ARG;
-    return detector_impl(c, d_lsmooth, sigma_size, d_lx, d_ly, d_lxx, d_lyy, d_lxy, d_ldet, w, h, n);
+    return detector_impl(c, no_job_form(c), d_lsmooth, sigma_size, d_lx, d_ly, d_lxx, d_lyy, d_lxy, d_ldet, w, h, n);
 }
 
 }  // extern "C"

@@ -147,7 +147,7 @@ int place_streams(akz_ctx* c) {
     // a stream that is being captured into a graph cannot be synchronised or timed: the probe waits for a call outside
     // the capture (akz_ctx_warmup is the place to run it once, up front)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (c->main && hipStreamIsCapturing(c->main, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return AKZ_OK;
+    if (c->stream && hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return AKZ_OK;
     (void)hipGetLastError();
     c->placed = true;
     finisher_drain(c);  // (the finish half uses c->aux)
@@ -158,13 +158,13 @@ int place_streams(akz_ctx* c) {
         c->pre_mode = 2;
         return AKZ_OK;
     }
-    AKZ_HIP_TRY(hipStreamSynchronize(c->main));
+    AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
     AKZ_HIP_TRY(hipStreamSynchronize(c->aux));
     AKZ_HIP_TRY(hipStreamSynchronize(c->coarse));
     AKZ_HIP_TRY(hipStreamSynchronize(c->copy));
     StreamPlacer sp(c);
-    AKZ_TRY(sp.calibrate(c->main));
-    sp.accepted.push_back(c->main);
+    AKZ_TRY(sp.calibrate(c->stream));
+    sp.accepted.push_back(c->stream);
     bool free_coarse = false, free_aux = false, free_copy = false;
     AKZ_TRY(sp.settle(&c->coarse, &free_coarse));
     AKZ_TRY(sp.settle(&c->aux, &free_aux));
@@ -178,16 +178,16 @@ int place_streams(akz_ctx* c) {
 // that order a lane behind the caller's work).  Up to four lanes can have a pipe each.
 int place_lanes(akz_ctx* c) {
     if (c->sched[2] || c->lanes.empty()) return AKZ_OK;
-    for (akz_ctx* l : c->lanes) AKZ_HIP_TRY(hipStreamSynchronize(l->main));
+    for (akz_ctx* l : c->lanes) AKZ_HIP_TRY(hipStreamSynchronize(l->stream));
     StreamPlacer sp(c);
-    AKZ_TRY(sp.calibrate(c->lanes[0]->main));
+    AKZ_TRY(sp.calibrate(c->lanes[0]->stream));
     c->lane_collisions = 0;
     for (akz_ctx* l : c->lanes) {
         bool free = false;
-        hipStream_t st = l->main;
+        hipStream_t st = l->stream;
         AKZ_TRY(sp.settle(&st, &free));
-        if (st != l->main) {  // (the replaced stream is destroyed with the placer's rejects; the lane owns the new one)
-            l->main = l->stream = st;
+        if (st != l->stream) {  // (the replaced stream is destroyed with the placer's rejects; the lane owns the new one)
+            l->stream = st;
         }
         if (!free) ++c->lane_collisions;
     }
@@ -202,13 +202,13 @@ int akz::place_streams_beside(akz_ctx* c, hipStream_t* slots, int n_slots, int* 
     if (still_shared) *still_shared = 0;
     if (c->is_lane || c->sched[2] || n_slots <= 0) return AKZ_OK;
     if (!c->placed) AKZ_TRY(place_streams(c));
-    AKZ_HIP_TRY(hipStreamSynchronize(c->main));
+    AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
     AKZ_HIP_TRY(hipStreamSynchronize(c->coarse));
     AKZ_HIP_TRY(hipStreamSynchronize(c->aux));
     for (int i = 0; i < n_slots; ++i) AKZ_HIP_TRY(hipStreamSynchronize(slots[i]));
     StreamPlacer sp(c);
-    AKZ_TRY(sp.calibrate(c->main));
-    sp.accepted = {c->main, c->coarse, c->aux};
+    AKZ_TRY(sp.calibrate(c->stream));
+    sp.accepted = {c->stream, c->coarse, c->aux};
     for (int i = 0; i < n_slots; ++i) {
         bool free = false;
         AKZ_TRY(sp.settle(&slots[i], &free));

@@ -316,6 +316,7 @@ int akz_result_device_plane(const akz_result* r, uint64_t img, uint64_t level, a
 static int recompute_plane(const akz_result* r, uint64_t img, uint64_t level, akz_plane plane, const float** d_out) {
     akz_ctx* c = r->ctx;
     AKZ_TRY(bind(c));
+    const JobForm f = no_job_form(c);
     const LevelPlan& lv = r->plan[(size_t)level];
     const size_t px = (size_t)lv.w * lv.h, pb = px * sizeof(float);
     auto img_plane = [&](uint64_t l, int p) { return r->planes[(size_t)l][p] + (size_t)img * r->plan[(size_t)l].w * r->plan[(size_t)l].h; };
@@ -324,7 +325,7 @@ static int recompute_plane(const akz_result* r, uint64_t img, uint64_t level, ak
         for (int k = 0; k < 6; ++k) AKZ_TRY(ensure(c, c->lazy[k], pb));
         float* b[6];
         for (int k = 0; k < 6; ++k) b[k] = (float*)c->lazy[k].p;
-        AKZ_TRY(detector_impl(c, img_plane(level, AKZ_LSMOOTH), lv.det_sigma, b[0], b[1], b[2], b[3], b[4], b[5], lv.w, lv.h, 1));
+        AKZ_TRY(detector_impl(c, f, img_plane(level, AKZ_LSMOOTH), lv.det_sigma, b[0], b[1], b[2], b[3], b[4], b[5], lv.w, lv.h, 1));
         *d_out = plane == AKZ_LXX ? b[2] : plane == AKZ_LYY ? b[3] : b[4];
         return AKZ_OK;
     }
@@ -338,7 +339,7 @@ static int recompute_plane(const akz_result* r, uint64_t img, uint64_t level, ak
             in = (const float*)c->lazy[3].p;
         }
         AKZ_HIP_TRY(hipMemsetAsync(step, 0, pb, c->stream));  // a level without diffusion steps keeps the zero plane (lib.rs:107)
-        AKZ_TRY(fed_impl(c, in, A, B, img_plane(level, AKZ_LFLOW), step, lv.w, lv.h, 1, lv.tau.data(), (uint32_t)lv.tau.size()));
+        AKZ_TRY(fed_impl(c, f, in, A, B, img_plane(level, AKZ_LFLOW), step, lv.w, lv.h, 1, lv.tau.data(), (uint32_t)lv.tau.size()));
         *d_out = step;
         return AKZ_OK;
     }
@@ -504,6 +505,7 @@ static int fetch_pyramid(const akz_result* r, uint64_t img, float* const* dst, u
 
     // recomputation k on the context's stream, with the kernels and the argument order of recompute_plane.  Its output
     // set was last read by the downloads of recomputation k - 2, which are queued by then (see the walk below).
+    const JobForm form = no_job_form(c);
     auto recompute = [&](size_t k) -> int {
         const size_t l = rc[k], s = k % 2;
         const LevelPlan& lv = r->plan[l];
@@ -512,7 +514,7 @@ static int fetch_pyramid(const akz_result* r, uint64_t img, float* const* dst, u
                        (float*)c->fetch_out[s][3].p};
         if (k >= 2) AKZ_HIP_TRY(hipStreamWaitEvent(c->stream, c->fetch_free[s], 0));
         if (need_deriv[l])
-            AKZ_TRY(detector_impl(c, img_plane(l, AKZ_LSMOOTH), lv.det_sigma, t[0], t[1], o[0], o[1], o[2], t[2], lv.w, lv.h, 1));
+            AKZ_TRY(detector_impl(c, form, img_plane(l, AKZ_LSMOOTH), lv.det_sigma, t[0], t[1], o[0], o[1], o[2], t[2], lv.w, lv.h, 1));
         if (need_step[l]) {
             const LevelPlan& pv = r->plan[l - 1];
             const float* in = img_plane(l - 1, AKZ_LT);
@@ -522,7 +524,7 @@ static int fetch_pyramid(const akz_result* r, uint64_t img, float* const* dst, u
             }
             if (lv.tau.empty())  // a level without diffusion steps keeps the zero plane (lib.rs:107)
                 AKZ_HIP_TRY(hipMemsetAsync(o[3], 0, px_of(l) * sizeof(float), c->stream));
-            AKZ_TRY(fed_impl(c, in, t[0], t[1], img_plane(l, AKZ_LFLOW), o[3], lv.w, lv.h, 1, lv.tau.data(), (uint32_t)lv.tau.size()));
+            AKZ_TRY(fed_impl(c, form, in, t[0], t[1], img_plane(l, AKZ_LFLOW), o[3], lv.w, lv.h, 1, lv.tau.data(), (uint32_t)lv.tau.size()));
         }
         AKZ_HIP_TRY(hipGetLastError());
         AKZ_HIP_TRY(hipEventRecord(c->fetch_ready[s], c->stream));
