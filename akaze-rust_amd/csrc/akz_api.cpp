@@ -120,7 +120,7 @@ int akz_ctx_destroy(akz_ctx* c) {
                       &c->small, &c->cand, &c->cand_sorted, &c->sort_scratch, &c->rel_scratch, &c->sel_scratch, &c->sel_recs, &c->bucket_scratch, &c->kp_in, &c->kp_out, &c->match_a, &c->match_b, &c->match_rec, &c->match_state,
                       &c->match_out, &c->cosi, &c->mm_q8, &c->mm_t8, &c->mm_pop, &c->mm_tab, &c->mm_cols,
                       &c->ms1.q8, &c->ms1.t8, &c->ms1.pop, &c->ms1.tab, &c->ms1.cols, &c->ms1.rec, &c->ransac_dev,
-                      &c->mp_in, &c->mp_raw, &c->mp_tab, &c->mp_trials, &c->mp_keep, &c->gd_tab, &c->gd_rec, &c->gd_out, &c->cx_rev, &c->kn_part, &c->kn_io};
+                      &c->mp_in, &c->mp_raw, &c->mp_tab, &c->mp_trials, &c->mp_keep, &c->gd_tab, &c->gd_rec, &c->gd_out, &c->cx_rev, &c->kn_part, &c->kn_io, &c->kb_dev};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (DevBuf* b : {&c->jpeg_coef, &c->jpeg_plane, &c->jpeg_frames})
@@ -147,11 +147,13 @@ int akz_ctx_destroy(akz_ctx* c) {
     for (DevBuf& b : c->pin)
         if (b.p) (void)hipHostFree(b.p);
     if (c->ransac_pin.p) (void)hipHostFree(c->ransac_pin.p);
-    for (DevBuf* b : {&c->mp_pin_in, &c->mp_pin_tab, &c->mp_pin_smp[0], &c->mp_pin_smp[1], &c->mp_pin_out, &c->gd_pin_tab, &c->gd_pin_cnt, &c->gd_pin_out, &c->cx_pin_tab})
+    for (DevBuf* b : {&c->mp_pin_in, &c->mp_pin_tab, &c->mp_pin_smp[0], &c->mp_pin_smp[1], &c->mp_pin_out, &c->gd_pin_tab, &c->gd_pin_cnt, &c->gd_pin_out, &c->cx_pin_tab, &c->kb_pin})
         if (b->p) (void)hipHostFree(b->p);
     for (hipEvent_t& e : c->mp_smp_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t& e : c->mp_split_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t& e : c->kb_split_ev)
         if (e) (void)hipEventDestroy(e);
     if (c->tab_ring) (void)hipHostFree(c->tab_ring);
     c->tab_ring = nullptr;

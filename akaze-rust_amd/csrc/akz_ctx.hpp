@@ -146,6 +146,12 @@ struct akz_ctx {
     // k-nearest-neighbour matching (akz_knn_api.cpp): the partial lists of a scan; rows | records | counts of a host-array call
     DevBuf kn_part, kn_io;
     uint32_t dbg_knn_chunks = 0;             // akz_debug_set_knn_chunks (0: automatic)
+    // the keypoint budget (akz_budget_api.cpp): x | y | response | set table | block table, then rank | kept indices | radius2 of a
+    // call; pinned: the upload's image, then kept indices | radius2.  No claim: every call initialises what its kernels accumulate into
+    DevBuf kb_dev, kb_pin;
+    hipEvent_t kb_split_ev[4] = {};          // akz_debug_keypoint_budget_split: stage boundaries of a timed call
+    bool kb_split_on = false;
+    double kb_split_ms[3] = {};
     hipEvent_t mp_smp_ev[2] = {nullptr, nullptr};
     hipEvent_t mp_split_ev[7] = {};          // akz_debug_match_pairs_split: stage boundaries of a timed call
     bool mp_split_on = false;

@@ -502,6 +502,24 @@ uint32_t knn_chunks(uint32_t n0, uint32_t n1, uint32_t forced = 0);
 size_t knn_part_bytes(uint32_t n0, uint32_t chunks, uint32_t k);
 bool knn(hipStream_t s, const uint8_t* q4, uint32_t n0, const uint8_t* t4, uint32_t n1, uint32_t threshold, uint32_t chunks, uint32_t k,
          uint32_t* d_part, akz_match* d_out, uint32_t* d_counts);
+// The keypoint budget (akz_budget.hip; include/akaze_hip.h).  All sets of a call lie packed one after the other: d_x, d_y, d_r hold
+// `total` floats each, set s at [base, base + n).  keep = min(max_keypoints, n); out_off: where the set's kept indices start in d_idx
+// (the sets' lists lie densely one after the other: their lengths are known before the launch).
+struct BudgetSet {
+    uint32_t base, n, keep, out_off;
+};
+// One workgroup of k_budget_walk: queries [q0, q0 + budget_query_tile()) of set `set` against its keypoints [t0, t1)
+struct BudgetBlock {
+    uint32_t set, q0, t0, t1;
+};
+static_assert(sizeof(BudgetSet) == 16 && sizeof(BudgetBlock) == 16, "the device reads 16-byte budget records");
+uint32_t budget_query_tile();   // queries of a workgroup (1024)
+uint32_t budget_train_tile();   // keypoints of one LDS stage (256); a block's [t0, t1) starts on a multiple of it
+// radius2 := +inf, rank := 0 for `total` keypoints; then (spread) the radius pass and the rank pass over the n_blocks records of
+// d_blocks, and the ordered compaction, one workgroup per set: d_idx[out_off + k] = the k-th index i (ascending) with rank_i < keep
+void budget(hipStream_t s, bool spread, float robust, const float* d_x, const float* d_y, const float* d_r, uint32_t total,
+            const BudgetSet* d_sets, uint32_t n_sets, const BudgetBlock* d_blocks, uint32_t n_blocks, float* d_radius2, uint32_t* d_rank,
+            uint32_t* d_idx);
 }  // namespace launch
 
 // ---- host keypoint logic (akz_keypoints.cpp) ---------------------------------------------

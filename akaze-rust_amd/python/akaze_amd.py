@@ -118,6 +118,15 @@ class FeatureSet(C.Structure):
     _fields_ = [("keypoints", C.c_void_p), ("n_keypoints", C.c_uint64), ("descriptors", C.c_void_p),
                 ("n_descriptors", C.c_uint64)]
 
+BUDGET_STRONGEST, BUDGET_SPREAD = 0, 1  # AKZ_BUDGET_*
+
+
+class KeypointBudget(C.Structure):
+    """akz_keypoint_budget: at most max_keypoints of a set, the strongest (BUDGET_STRONGEST) or the best spread (BUDGET_SPREAD:
+    adaptive non-maximal suppression, robust in (0, 1])."""
+    _fields_ = [("max_keypoints", C.c_uint64), ("mode", C.c_uint32), ("robust", C.c_float)]
+
+
 class RansacOptions(C.Structure):
     """akz_ransac_options: the options of the seeded RANSAC (remove_outliers_seeded, match_features_seeded(_pairs)).  A new
     object holds akz_ransac_options_default -- fundamental matrix, ratio 0.86, 1 000 trials, epsilon_inliers 0.02, confidence
@@ -314,6 +323,10 @@ def lib():
         "akz_descriptor_match_knn": ([vp, vp, u64, vp, u64, u64, u64, u64, vp, vp], i32),
         "akz_descriptor_match_knn_device": ([vp, vp, u64, vp, u64, u64, u64, vp, vp], i32),
         "akz_debug_set_knn_chunks": ([vp, u32], i32),
+        "akz_keypoint_budget_host": ([vp, u64, C.POINTER(KeypointBudget), vp, pu64, vp], i32),
+        "akz_keypoint_budget_sets": ([vp, vp, u64, C.POINTER(KeypointBudget), vp, vp, vp], i32),
+        "akz_debug_keypoint_budget_split": ([vp, i32, pf64], i32),
+        "akz_debug_keypoint_budget_tiles": ([pu32, pu32], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_debug_match_tile_rows": ([C.POINTER(C.c_uint32)], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
@@ -1022,6 +1035,35 @@ class Context:
     def set_knn_chunks(self, n=0):
         """akz_debug_set_knn_chunks (include/akaze_hip_debug.h): force the train chunks of the k-NN scan; 0 = automatic."""
         _check(lib().akz_debug_set_knn_chunks(self._h, int(n)))
+
+    def keypoint_budget_sets(self, features, max_keypoints, mode=BUDGET_SPREAD, robust=0.9):
+        """The keypoint budget over many sets in one call on the GPU (akz_keypoint_budget_sets): features as for the pairs calls,
+        a sequence of (keypoints, descriptors) -- only the keypoints are read, a bare keypoint array will do.  Returns one
+        (indices uint64 ascending, radius2 float32 [n] or None in BUDGET_STRONGEST mode) per set, each equal to
+        keypoint_budget_host on that set."""
+        ks = [np.ascontiguousarray(f[0] if isinstance(f, (tuple, list)) else f, KEYPOINT_DTYPE) for f in features]
+        sets = (FeatureSet * max(1, len(ks)))()
+        for i, k in enumerate(ks):
+            sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), None, 0)
+        total = sum(len(k) for k in ks)
+        opt = KeypointBudget(int(max_keypoints), int(mode), float(robust))
+        idx = np.zeros(max(1, total), np.uint64)
+        n = np.zeros(max(1, len(ks)), np.uint64)
+        rad = np.zeros(max(1, total), np.float32) if mode == BUDGET_SPREAD else None
+        _check(lib().akz_keypoint_budget_sets(self._h, C.cast(sets, C.c_void_p), len(ks), C.byref(opt), idx.ctypes.data_as(C.c_void_p),
+                                              n.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p) if rad is not None else None))
+        res, at = [], 0
+        for s, k in enumerate(ks):
+            res.append((idx[at:at + int(n[s])].copy(), rad[at:at + len(k)].copy() if rad is not None else None))
+            at += len(k)
+        return res
+
+    def debug_keypoint_budget_split(self, enable=True):
+        """akz_debug_keypoint_budget_split (include/akaze_hip_debug.h): time the later keypoint_budget_sets calls; returns the last
+        timed call's (upload, kernels, download) in ms."""
+        ms = (C.c_double * 3)()
+        _check(lib().akz_debug_keypoint_budget_split(self._h, int(bool(enable)), ms))
+        return tuple(ms)
 
     def descriptor_match_device(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """Same on torch CUDA uint8 tensors of 64-byte descriptor rows; returns (matches tensor view, count)."""
@@ -1953,6 +1995,41 @@ def descriptor_match_knn_host(d0, d1, k, distance_threshold=10000):
     MATCH_DTYPE, counts (n0,) uint32); unused slots hold index_1 = 2^64 - 1 and distance = inf.  The statement that
     Context.descriptor_match_knn and descriptor_match_knn_device are held to."""
     return _knn_pair(lib().akz_descriptor_match_knn_host, (), d0, d1, k, distance_threshold)
+
+
+def keypoint_budget_host(keypoints, max_keypoints, mode=BUDGET_SPREAD, robust=0.9):
+    """The keypoint budget on the host (akz_keypoint_budget_host; no GPU call): the first min(max_keypoints, n) keypoints in the
+    order (response descending, index ascending) of BUDGET_STRONGEST or (suppression radius descending, response descending,
+    index ascending) of BUDGET_SPREAD, reported in ascending index order -> (indices uint64, radius2 float32 [n] or None in
+    BUDGET_STRONGEST mode).  The statement that Context.keypoint_budget_sets is held to."""
+    k = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE)
+    opt = KeypointBudget(int(max_keypoints), int(mode), float(robust))
+    idx = np.zeros(max(1, len(k)), np.uint64)
+    n = C.c_uint64()
+    rad = np.zeros(max(1, len(k)), np.float32) if mode == BUDGET_SPREAD else None
+    _check(lib().akz_keypoint_budget_host(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), C.byref(opt),
+                                          idx.ctypes.data_as(C.c_void_p), C.byref(n),
+                                          rad.ctypes.data_as(C.c_void_p) if rad is not None else None))
+    return idx[:n.value].copy(), (rad[:len(k)].copy() if rad is not None else None)
+
+
+def keypoint_budget_tiles():
+    """akz_debug_keypoint_budget_tiles: (queries per workgroup, keypoints per LDS stage) of the budget's tile walk."""
+    q, t = C.c_uint32(), C.c_uint32()
+    _check(lib().akz_debug_keypoint_budget_tiles(C.byref(q), C.byref(t)))
+    return q.value, t.value
+
+
+def limit_features(keypoints, descriptors, max_keypoints, mode=BUDGET_SPREAD, robust=0.9, ctx=None):
+    """Cut a feature set to at most max_keypoints with Context.keypoint_budget_sets on ctx (default: the default context) ->
+    (keypoints[idx], descriptors[idx], idx), in the detector's order and ready for every match_features* call."""
+    k = np.ascontiguousarray(keypoints, KEYPOINT_DTYPE)
+    d = np.asarray(descriptors)
+    if len(d) != len(k):
+        raise ValueError(f"{len(k)} keypoints but {len(d)} descriptors")
+    idx, _ = (ctx or default_context()).keypoint_budget_sets([k], max_keypoints, mode, robust)[0]
+    sel = idx.astype(np.int64)
+    return k[sel].copy(), np.ascontiguousarray(d[sel]), idx
 
 
 def descriptor_match_cross_host(d0, d1, distance_threshold=10000, lowes_ratio=0.86):

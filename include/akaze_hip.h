@@ -952,6 +952,45 @@ int akz_descriptor_match_knn(akz_ctx* ctx, const uint8_t* d0, uint64_t n0, const
 int akz_descriptor_match_knn_device(akz_ctx* ctx, const uint8_t* d_d0, uint64_t n0, const uint8_t* d_d1, uint64_t n1, uint64_t k,
                                     uint64_t distance_threshold, akz_match* d_out, uint32_t* d_counts);
 
+/* ---- keypoint budget: at most N keypoints of a set, the strongest or the best spread (additions) -----------------------
+   A stage of its own over feature sets, between extract_features and the matching calls (every matching cost grows with the
+   square of the keypoint count); no extraction or matching call changes.  For one set of n keypoints take x_i, y_i and
+   r_i = response, all f32; every operation below is one IEEE f32 operation, rounded on its own (no contraction, subnormals kept):
+     * AKZ_BUDGET_STRONGEST: the order is (r descending, index ascending).  Responses compare as float values: -0 equals +0.
+     * AKZ_BUDGET_SPREAD (adaptive non-maximal suppression; Brown, Szeliski and Winder 2005):
+         d2(i, j)  = fl(fl(dx * dx) + fl(dy * dy))  with dx = fl(x_i - x_j), dy = fl(y_i - y_j);
+         j dominates i iff r_i < fl(robust * r_j)  (j = i is not excepted: a keypoint with a negative response dominates itself);
+         radius2_i = the minimum of d2(i, j) over all j that dominate i, +infinity where none does;
+         the order is (radius2 descending, r descending, index ascending).
+     * the first min(max_keypoints, n) of the order are kept and reported in ASCENDING index order -- the detector's order is
+       preserved, indices[0 .. *n_out) -- and *n_out is their number.  max_keypoints = 0 keeps nothing and is AKZ_OK.
+     * radius2 (optional, SPREAD only): all n values of the set, every slot defined.
+   The minimum and the place in the order depend on no traversal order, so every tiling gives the same bits.
+   Refusals (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written, the message names the set): NULL options, an unknown mode,
+   SPREAD with robust outside (0, 1] (NaN included), an x, y or response that is not finite, NULL keypoints where n > 0, a NULL
+   indices or n_out, a non-NULL radius2 in STRONGEST mode, a set of more than 2^31 - 1 keypoints. */
+#define AKZ_BUDGET_STRONGEST 0
+#define AKZ_BUDGET_SPREAD 1
+typedef struct akz_keypoint_budget {
+    uint64_t max_keypoints;
+    uint32_t mode;  /* AKZ_BUDGET_* */
+    float robust;   /* SPREAD: 0 < robust <= 1 (0.9 is customary); STRONGEST: not read */
+} akz_keypoint_budget;
+/* The host statement for one set: plain loops and a sort, no GPU call, no context.  indices has room for min(max_keypoints, n)
+   entries, radius2 (may be NULL) for n. */
+int akz_keypoint_budget_host(const akz_keypoint* keypoints, uint64_t n, const akz_keypoint_budget* options, uint64_t* indices,
+                             uint64_t* n_out, float* radius2);
+/* The statement over many sets in one call, on the GPU, bit for bit the host statement per set.  Of every akz_feature_set only
+   keypoints and n_keypoints are read (descriptors may be NULL).  Fixed room per set, as in akz_match_features_pairs: set s writes
+   its indices (n_out[s] of them) and its radius2 values (all n_keypoints) from offset sum_{q<s} sets[q].n_keypoints on; indices
+   and radius2 hold sum_s sets[s].n_keypoints entries, n_out holds n_sets.  Empty sets and n_sets = 0 are AKZ_OK.  Further
+   refusals: a NULL ctx or NULL sets while n_sets > 0, all sets together above 2^31 - 1 keypoints.
+   One upload (x, y, response of all sets and two tables), the all-pairs radius and rank passes (k_budget_walk: a keypoint is kept
+   iff fewer than N others stand before it in the order -- counted, not sorted, exact under ties), one ordered compaction per set
+   and one download, on the context's stream with the context's scratch; complete on return. */
+int akz_keypoint_budget_sets(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, const akz_keypoint_budget* options,
+                             uint64_t* indices, uint64_t* n_out /* n_sets */, float* radius2);
+
 /* ---- on-disk formats of akaze-util ---------------------------------- */
 /* akaze_util::{serialize,deserialize}_{features,matches}_{to,from}_file — akaze-util/src/lib.rs:17-67.
    A path ending in ".json" is serde_json, anything else bincode 1.x (little-endian, u64 lengths), exactly

@@ -175,6 +175,11 @@ int akz_debug_ransac_samples_k(uint64_t s0, uint64_t s1, uint64_t n_matches, uin
    calls (events on its stream); ms (optional, 6 doubles) receives the last timed call's uploads, scans, host draws, trials, pick + filter and read-back
    in ms (the trials: first trial launch to last trial's end, overlapping the draws). */
 int akz_debug_match_pairs_split(akz_ctx* ctx, int enable, double* ms);
+/* The same for akz_keypoint_budget_sets: ms (optional, 3 doubles) receives the last timed call's upload, kernels and download. */
+int akz_debug_keypoint_budget_split(akz_ctx* ctx, int enable, double* ms);
+/* Test hook: the queries per workgroup and the keypoints per LDS stage of k_budget_walk, so that tests can place their set sizes
+   one below, at and one above them.  No GPU call, no context. */
+int akz_debug_keypoint_budget_tiles(uint32_t* query_tile, uint32_t* train_tile);
 
 /* ---- kernel-family selectors and the synthetic frame generator (tests, bench, tools): every mode gives bit-identical
    results; a drop-in host never calls these ---------------------------------------------------------------------- */
