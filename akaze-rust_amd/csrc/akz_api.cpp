@@ -315,8 +315,8 @@ extern "C" {
 int akz_ctx_set_profiling(akz_ctx* c, int on) {
     AKZ_TRY(bind(c));
     if (on < 0 || on > 2) return AKZ_ERR_INVALID_ARG;
-    c->profiling = on == 1 ? 2 : on == 2 ? 1 : 0;  // API: 1 = all stages, 2 = light (FED spans only)
-    for (akz_ctx* l : c->lanes) l->profiling = c->profiling;
+    c->settings.profiling = on == 1 ? 2 : on == 2 ? 1 : 0;  // API: 1 = all stages, 2 = light (FED spans only)
+    push_settings(c);
     return AKZ_OK;
 }
 int akz_ctx_warmup(akz_ctx* c) {
@@ -401,29 +401,32 @@ int akz_write_evolutions(const akz_result* r, uint64_t img, const char* dir) {
 
 int akz_ctx_set_detector_mode(akz_ctx* c, int mode) {
     if (!c || (mode != 0 && mode != 2 && mode != 4 && mode != 5)) return AKZ_ERR_INVALID_ARG;
-    c->det_mode = mode;
-    for (akz_ctx* l : c->lanes) l->det_mode = mode;
+    c->settings.det_mode = mode;
+    push_settings(c);
     return AKZ_OK;
 }
 
 int akz_ctx_set_prep_mode(akz_ctx* c, int mode) {
     if (!c || mode < 0 || mode > 3) return AKZ_ERR_INVALID_ARG;
-    c->prep_mode = mode;
-    for (akz_ctx* l : c->lanes) l->prep_mode = mode;
+    c->settings.prep_mode = mode;
+    push_settings(c);
     return AKZ_OK;
 }
 
 int akz_ctx_set_host_threads(akz_ctx* c, uint32_t threads) {
     AKZ_TRY(bind(c));
     if (threads > 256) return AKZ_ERR_INVALID_ARG;
-    for (int k = 0; k < akz_ctx::kSlots; ++k)
-        if (c->slot_busy[k]) {
-            set_error("akz_ctx_set_host_threads: extractions are in flight on this context");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    c->host_threads = threads;
-    c->workers.reset();  // joins the old pool; the next finish starts the new one
-    for (akz_ctx* l : c->lanes) AKZ_TRY(akz_ctx_set_host_threads(l, threads));
+    std::vector<akz_ctx*> all(c->lanes);
+    all.push_back(c);
+    for (akz_ctx* x : all)
+        for (int k = 0; k < akz_ctx::kSlots; ++k)
+            if (x->slot_busy[k]) {
+                set_error("akz_ctx_set_host_threads: extractions are in flight on this context");
+                return AKZ_ERR_INVALID_ARG;
+            }
+    c->settings.host_threads = threads;
+    push_settings(c);
+    for (akz_ctx* x : all) x->workers.reset();  // joins the old pool; the next finish starts the new one
     return AKZ_OK;
 }
 int akz_ctx_set_candidate_hint(akz_ctx* c, uint32_t per_image) {
@@ -435,15 +438,15 @@ int akz_ctx_set_candidate_hint(akz_ctx* c, uint32_t per_image) {
 int akz_ctx_set_match_mode(akz_ctx* c, int mode) {
     AKZ_TRY(bind(c));
     if (mode < 0 || mode > 3) return AKZ_ERR_INVALID_ARG;
-    c->match_mode = mode;
-    for (akz_ctx* l : c->lanes) l->match_mode = mode;
+    c->settings.match_mode = mode;
+    push_settings(c);
     return AKZ_OK;
 }
 int akz_ctx_set_fed_mode(akz_ctx* c, int mode) {
     AKZ_TRY(bind(c));
     if (mode != 0 && mode != 2) return AKZ_ERR_INVALID_ARG;
-    c->fed_mode = mode;
-    for (akz_ctx* l : c->lanes) l->fed_mode = mode;
+    c->settings.fed_mode = mode;
+    push_settings(c);
     return AKZ_OK;
 }
 const char* akz_fed_kernel_name(void) { return "k_level_march + k_fed_own"; }  // (+ k_octave_resident: same profile group)
@@ -466,20 +469,19 @@ int akz_debug_detector_set_cells(int half_width, const uint32_t* w, const uint32
 }
 const char* akz_detector_kernel_name(void) { return "detector (k_detector_march + k_detector_tiled)"; }
 int akz_debug_set_schedule(akz_ctx* c, int key, int value) {
-    if (!c || key < 0 || key > 11) return AKZ_ERR_INVALID_ARG;
+    if (!c || key < 0 || key >= SCHED_COUNT_) return AKZ_ERR_INVALID_ARG;
     AKZ_TRY(bind(c));
-    c->sched[key] = value;
-    if (key == 7 || key == 8) launch::march_min_band_rows(c->sched[7], c->sched[8]);  // (process-wide: measurement)
-    if (key == 11) launch::detector_set_waves(value >= 11 && value <= 14 ? value - 10 : 0);  // (process-wide: the kDetSetWaves sweep)
-    if (key == 4) {
-        c->big_px_sync = value > 0 ? (uint64_t)value * 1000u : gates::kBigPxSync;
-        c->big_px_async = value > 0 ? (uint64_t)value * 1000u : gates::kBigPxAsync;
-        c->lane_px = value > 0 ? (uint64_t)value * 1000u : gates::kLanePx;
-        for (akz_ctx* l : c->lanes) {  // (a job that is dealt to a lane runs there as a one-stream chain)
-            l->big_px_sync = std::max(c->big_px_sync, c->lane_px);
-            l->big_px_async = std::max(c->big_px_async, c->lane_px);
-        }
+    CtxSettings& s = c->settings;
+    s.sched[key] = value;
+    if (key == SCHED_DET_BAND_ROWS || key == SCHED_LEVEL_BAND_ROWS)
+        launch::march_min_band_rows(s.sched[SCHED_DET_BAND_ROWS], s.sched[SCHED_LEVEL_BAND_ROWS]);  // (process-wide: measurement)
+    if (key == SCHED_DET_SETS) launch::detector_set_waves(value >= 11 && value <= 14 ? value - 10 : 0);  // (process-wide: the kDetSetWaves sweep)
+    if (key == SCHED_JOB_KPX) {
+        s.big_px_sync = value > 0 ? (uint64_t)value * 1000u : gates::kBigPxSync;
+        s.big_px_async = value > 0 ? (uint64_t)value * 1000u : gates::kBigPxAsync;
+        s.lane_px = value > 0 ? (uint64_t)value * 1000u : gates::kLanePx;
     }
+    push_settings(c);
     return AKZ_OK;
 }
 int akz_debug_placement_verdict(float spin_pair_ms, float tiny_pair_ms, float tiny_alone_ms, float spin_ms) {
@@ -507,20 +509,20 @@ int akz_debug_select_info(akz_ctx* c, int* info) {
 }
 int akz_debug_set_select(akz_ctx* c, int mode) {
     if (!c) return AKZ_ERR_INVALID_ARG;
-    c->dbg_select = mode < 0 ? -1 : (mode >= 2 ? 2 : (mode != 0));
-    for (akz_ctx* l : c->lanes) l->dbg_select = c->dbg_select;
+    c->settings.dbg_select = mode < 0 ? -1 : (mode >= 2 ? 2 : (mode != 0));
+    push_settings(c);
     return AKZ_OK;
 }
 int akz_debug_set_host_sort(akz_ctx* c, int on) {
     if (!c) return AKZ_ERR_INVALID_ARG;
-    c->dbg_host_sort = on < 0 ? -1 : (on != 0);
-    for (akz_ctx* l : c->lanes) l->dbg_host_sort = c->dbg_host_sort;
+    c->settings.dbg_host_sort = on < 0 ? -1 : (on != 0);
+    push_settings(c);
     return AKZ_OK;
 }
 int akz_debug_set_alloc_fill(akz_ctx* c, int on) {
     if (!c) return AKZ_ERR_INVALID_ARG;
-    c->dbg_alloc_fill = on != 0;
-    for (akz_ctx* l : c->lanes) l->dbg_alloc_fill = c->dbg_alloc_fill;
+    c->settings.dbg_alloc_fill = on != 0;
+    push_settings(c);
     return AKZ_OK;
 }
 // One context's raised claims against the device: up to three rows behind out[*k].  Read-only: copies, no launch, no claim changes.
@@ -575,8 +577,8 @@ int akz_debug_audit_scratch(akz_ctx* c, akz_scratch_audit* out, uint32_t cap, ui
 }
 int akz_debug_set_device_libm(akz_ctx* c, int mode) {
     if (!c) return AKZ_ERR_INVALID_ARG;
-    c->dbg_device_libm = mode == 0 ? 0 : -1;
-    for (akz_ctx* l : c->lanes) l->dbg_device_libm = c->dbg_device_libm;
+    c->settings.dbg_device_libm = mode == 0 ? 0 : -1;
+    push_settings(c);
     return AKZ_OK;
 }
 int akz_debug_device_libm(akz_ctx* c, int* available, int* last_job) {
@@ -605,15 +607,24 @@ int akz_debug_gates(const akz_gate** rows, uint64_t* n) {
 int akz_debug_kernel_rows(akz_ctx* c, akz_kernel_row* out, uint32_t cap, uint32_t* n_rows, int reset) {
     AKZ_TRY(bind(c));
     if (!n_rows || (cap && !out)) return AKZ_ERR_INVALID_ARG;
-    AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
-    resolve_spans(c);
-    std::lock_guard<std::mutex> lk(c->ev_m);
-    *n_rows = (uint32_t)c->rows.size();
-    for (size_t i = 0; i < c->rows.size() && i < cap; ++i) out[i] = c->rows[i];
-    if (reset) {
-        // spans still in flight keep their row index: the table keeps its rows and only the figures start again
-        for (akz_kernel_row& r : c->rows) r.launches = 0, r.px = 0, r.px_steps = 0, r.ms = 0.0;
+    std::vector<akz_ctx*> all{c};
+    all.insert(all.end(), c->lanes.begin(), c->lanes.end());  // jobs dealt to the lanes are part of this context's rows, as of its profile
+    std::vector<akz_kernel_row> sum;
+    for (akz_ctx* x : all) {
+        AKZ_HIP_TRY(hipStreamSynchronize(x->stream));
+        resolve_spans(x);
+        std::lock_guard<std::mutex> lk(x->ev_m);
+        for (akz_kernel_row& r : x->rows) {
+            auto same = [&](const akz_kernel_row& s) { return s.stage == r.stage && s.kind == r.kind && s.param == r.param && s.w == r.w && s.h == r.h && s.n == r.n; };
+            auto it = std::find_if(sum.begin(), sum.end(), same);
+            if (it == sum.end()) sum.push_back(r);
+            else it->launches += r.launches, it->px += r.px, it->px_steps += r.px_steps, it->ms += r.ms;
+            // spans still in flight keep their row index: the table keeps its rows and only the figures start again
+            if (reset) r.launches = 0, r.px = 0, r.px_steps = 0, r.ms = 0.0;
+        }
     }
+    *n_rows = (uint32_t)sum.size();
+    for (size_t i = 0; i < sum.size() && i < cap; ++i) out[i] = sum[i];
     return AKZ_OK;
 }
 int akz_debug_rcp_f64_to_f32(akz_ctx* c, const double* d_x, float* d_out, uint64_t n) {
@@ -625,12 +636,9 @@ int akz_debug_rcp_f64_to_f32(akz_ctx* c, const double* d_x, float* d_out, uint64
 }
 int akz_debug_set_match_chunks(akz_ctx* c, uint32_t pair_chunks, uint32_t set_chunks) {
     if (!c || set_chunks > 16) return AKZ_ERR_INVALID_ARG;
-    c->dbg_pair_chunks = pair_chunks;
-    c->dbg_set_chunks = set_chunks;
-    for (akz_ctx* l : c->lanes) {
-        l->dbg_pair_chunks = pair_chunks;
-        l->dbg_set_chunks = set_chunks;
-    }
+    c->settings.dbg_pair_chunks = pair_chunks;
+    c->settings.dbg_set_chunks = set_chunks;
+    push_settings(c);
     return AKZ_OK;
 }
 

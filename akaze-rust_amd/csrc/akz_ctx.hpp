@@ -100,7 +100,79 @@ enum Pin {
     PIN_SPARE,          // (no user: the device selection's records carry their orientation sums)
     PIN_COUNT_
 };
+// The keys of akz_debug_set_schedule (include/akaze_hip_debug.h carries the same list): measurement hooks, results are identical.
+//  0 SCHED_EARLY_STREAM     where the early stages (level-0 blur, contrast factor) of a batch whose input is complete run:
+//                           0 = the copy stream if the stream-placement probe found it a hardware queue and a pipe of its own,
+//                           1 = the copy stream regardless, 2 = a stream of their own (a fifth busy stream), 3 = the context's
+//                           stream (no running ahead).  Default 0.
+//  1 SCHED_EARLY_HOLD       what the early stages wait for: 0 = nothing, 1 = the fine-level diffusion of the batch before,
+//                           2 = the first octave's diffusion of the batch before.  Default 1.
+//  2 SCHED_NO_PROBE         1 = no stream-placement probe: streams stay as the runtime placed them.  Default 0.
+//  3 SCHED_FORK_OCTAVE      the octave at which the coarse chain of a batch forks onto its own stream; 0 = octave 2.  Default 0.
+//  4 SCHED_JOB_KPX          the job size in thousands of pixels (w*h*n) from which a job takes the batch path (column-march
+//                           kernels, forked coarse chain, resident tail); the same value replaces lane_px, the size below which a
+//                           context with lanes deals its jobs to them; 0 = the gates of akz_debug_gates (big_px_sync,
+//                           big_px_async, lane_px).  Default 0.
+//  5 SCHED_DET_BEHIND_LEVEL 1 = the column-march detector of a fine level right behind its level kernel, 0 = behind the whole
+//                           fine chain (profiles/r06_interleave.txt).  Default 0.
+//  6 SCHED_PREP_OWN_LAUNCH  1 = every level's preparation as a launch of its own and no tiled preparation family chosen per job,
+//                           0 = on the tiled path the last diffusion launch of a level also prepares the next level of the
+//                           octave (k_fed_own's epilogue).  Default 0.
+//  7 SCHED_DET_BAND_ROWS    process-wide: the least interior rows of a band of the detector march -- how finely a small job's
+//                           column marches are cut into workgroups; 0 = the planner's rule (40).  Default 0.
+//  8 SCHED_LEVEL_BAND_ROWS  process-wide: the same for the level march, plus 1000 x the same for the level-0 marches; 0 = the
+//                           planners' rules (level march: 20 below 48 Mpx per launch).  Default 0.
+//  9 SCHED_FINISH_FORM      bit 0 = the waited-for job's headers, keypoint records and descriptor rows come to the host as three
+//                           copies behind the descriptor kernel, clear = that kernel stores them into the host's pinned buffers
+//                           itself; bit 1 = the keypoint kernels of a job that is alone in the context's hands on the auxiliary
+//                           stream, as every other job's, clear = on the main stream, in order behind its detectors, when its
+//                           chain ended there.  Default 0.
+// 10 SCHED_HEAD_SPLIT       1 = level 0 of a tiled-family job as separate launches (blur, clearing of the contrast scratch, blur,
+//                           maximum, histogram, percentile, and level 1's preparation as a k_prep launch), 0 = k_head +
+//                           k_contrast_hist_final, and level 1's Lflow from k_head's Scharr pair.  Default 0.
+// 11 SCHED_DET_SETS         how the column-march detectors of a range of levels are launched: 1 = one launch per level, 2 = one
+//                           launch per set of up to four levels that share sigma_size, the width's parity and the kept planes
+//                           (largest first), 0 = whichever of the two DESIGN.md 4 names the default, 11 .. 14 = sets, cut into
+//                           1 .. 4 x 3 x CUs cells instead of kDetSetWaves x (process-wide: the sweep behind that constant).
+//                           Default 0.
+enum Sched {
+    SCHED_EARLY_STREAM = 0,
+    SCHED_EARLY_HOLD,
+    SCHED_NO_PROBE,
+    SCHED_FORK_OCTAVE,
+    SCHED_JOB_KPX,
+    SCHED_DET_BEHIND_LEVEL,
+    SCHED_PREP_OWN_LAUNCH,
+    SCHED_DET_BAND_ROWS,
+    SCHED_LEVEL_BAND_ROWS,
+    SCHED_FINISH_FORM,
+    SCHED_HEAD_SPLIT,
+    SCHED_DET_SETS,
+    SCHED_COUNT_
+};
+// What a user sets on a context: one value, written by the setters on the context they are called on and handed to its lanes whole
+// (lane_settings, push_settings below).  State that moves at run time (cand_cap_hint, the claims, the last-job fields) is not here.
+struct CtxSettings {
+    int det_mode = 2;  // 0: tiled pair, 2: auto, 4: one tiled kernel, 5: column march (akz_ctx_set_detector_mode)
+    int prep_mode = 2;  // level preparation: 0 LDS-tiled, 1 streaming, 2 auto (fused with the first diffusion steps for large launches), 3 fused wherever supported
+    int match_mode = 2;  // 0: popcount kernel, 1: matrix cores on int8 operands, 2 (default) / 3: on FP4 operands (akz_ctx_set_match_mode)
+    int fed_mode = 2;  // 0: k_fed_step (1 step/launch), 2: k_fed_own (<= 8 steps/launch; <= 16 for small launches)
+    uint64_t stream_min_px = gates::kStreamPx;  // pixels per launch (w*h*n) from which the streaming kernels pay off
+    uint64_t big_px_sync = gates::kBigPxSync, big_px_async = gates::kBigPxAsync;  // (sched[SCHED_JOB_KPX] sets both: measurement)
+    uint64_t lane_px = gates::kLanePx;  // jobs below it go to the lanes, if the context has any (sched[SCHED_JOB_KPX] sets it too)
+    int profiling = 0;  // 0 off, 1 FED spans + host-clock stages, 2 every stage
+    unsigned host_threads = 0;  // akz_ctx_set_host_threads; 0 = sized by host_cpu_share()
+    uint32_t dbg_pair_chunks = 0, dbg_set_chunks = 0;  // akz_debug_set_match_chunks (0: automatic)
+    uint32_t dbg_knn_chunks = 0;  // akz_debug_set_knn_chunks (0: automatic)
+    int dbg_host_sort = -1;  // akz_debug_set_host_sort: 1 / 0 force the host / the device sort, -1 automatic
+    int dbg_select = -1;  // akz_debug_set_select: 2 / 1 / 0 force the device / the neighbour-list / the grid selection, -1 automatic
+    bool dbg_alloc_fill = false;  // akz_debug_set_alloc_fill: fresh device memory is filled with kAllocFillByte
+    int dbg_device_libm = -1;  // akz_debug_set_device_libm: 0 = the host's libm always, -1 = automatic (device_libm_mode)
+    int sched[SCHED_COUNT_] = {0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // akz_debug_set_schedule, indexed by Sched
+};
+static_assert(std::is_trivially_copyable<CtxSettings>::value, "lanes get the block by plain assignment");
 struct akz_ctx {
+    CtxSettings settings;  // a lane's: lane_settings(its parent's), kept so by push_settings
     int device = 0;
     hipStream_t stream = nullptr;            // the caller's stream (set at creation, a lane's again by place_lanes; what other threads synchronise with)
     bool own_stream = false;
@@ -120,7 +192,6 @@ struct akz_ctx {
     DevBuf sel_scratch, sel_recs;            // the selection on the device (launch::select_device): its scratch, the selected keypoints
     DevBuf bucket_scratch;                   // launch::sort_candidates_buckets
     size_t bucket_zero = 0;                  // claim: the first bucket_zero bytes of bucket_scratch (its counters) are zero; 0: not known
-    int dbg_select = -1;                     // akz_debug_set_select: 2 / 1 / 0 force the device / the neighbour-list / the grid selection, -1 automatic
     std::atomic<uint32_t> last_total_kp{0};  // keypoints of the previous finished job (speculative fetch size of the device selection)
     std::atomic<int> sel_last_mode{-1};      // akz_debug_select_info: how the last finished job was selected (0 grids, 1 lists, 2 device), the
     std::atomic<int> sel_skip{0};            // jobs of shape sel_skip_shape that leave the device's selection out (the last one fell back)
@@ -145,7 +216,6 @@ struct akz_ctx {
     DevBuf cx_rev, cx_pin_tab;
     // k-nearest-neighbour matching (akz_knn_api.cpp): the partial lists of a scan; rows | records | counts of a host-array call
     DevBuf kn_part, kn_io;
-    uint32_t dbg_knn_chunks = 0;             // akz_debug_set_knn_chunks (0: automatic)
     // the keypoint budget (akz_budget_api.cpp): x | y | response | set table | block table, then rank | kept indices | radius2 of a
     // call; pinned: the upload's image, then kept indices | radius2.  No claim: every call initialises what its kernels accumulate into
     DevBuf kb_dev, kb_pin;
@@ -172,12 +242,7 @@ struct akz_ctx {
         uint64_t ring_next = 0;
         hipEvent_t ring_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     } ms1;
-    int match_mode = 2;                      // 0: popcount kernel, 1: matrix cores on int8 operands, 2 (default) / 3: on FP4 operands (akz_ctx_set_match_mode)
-    uint32_t dbg_pair_chunks = 0, dbg_set_chunks = 0;  // akz_debug_set_match_chunks (0: automatic)
-    int dbg_device_libm = -1;   // akz_debug_set_device_libm: 0 = the host's libm always, -1 = automatic (device_libm_mode)
     int libm_last = 0;          // how the last finished job got its angles: 0 host libm, 1 / 2 the device's FMA / SSE2 forms
-    int dbg_host_sort = -1;                            // akz_debug_set_host_sort: 1 / 0 force the host / the device sort, -1 automatic
-    bool dbg_alloc_fill = false;                       // akz_debug_set_alloc_fill: fresh device memory is filled with kAllocFillByte
     DevBuf cosi;                             // (cos, sin) per keypoint
     DevBuf pin[PIN_COUNT_];                  // pinned host staging (enum Pin)
     std::vector<std::pair<size_t, void*>> slab_pool;  // freed device blocks (pyramid slabs, descriptor rows)
@@ -209,19 +274,6 @@ struct akz_ctx {
                                         // akz_extract_begin_* runs on the context's own thread (a lane's on the lane's)
     std::shared_ptr<Finisher> fin;      // (a lane's) finisher thread (shared with its jobs: one may outlive the context), started with its first eager job
     hipEvent_t lane_in = nullptr;       // inputs of the job are ready on the caller's stream
-    // stage profiling (akz_ctx_set_profiling)
-    uint64_t stream_min_px = gates::kStreamPx;  // pixels per launch (w*h*n) from which the streaming kernels pay off
-    int prep_mode = 2;  // level preparation: 0 LDS-tiled, 1 streaming, 2 auto (fused with the first diffusion steps for large launches), 3 fused wherever supported
-    int det_mode = 2;  // 0: tiled pair, 2: auto, 4: one tiled kernel, 5: column march (akz_ctx_set_detector_mode)
-    int fed_mode = 2;  // 0: k_fed_step (1 step/launch), 2: k_fed_own (<= 8 steps/launch; <= 16 for small launches)
-    // schedule variants (akz_debug_set_schedule): [0] where the early stages of a batch run -- 0 the copy stream if the
-    // placement probe found it a queue and a pipe of its own (below), 1 the copy stream regardless, 2 a stream of their own
-    // (a fifth busy stream), 3 the context's stream (no running ahead); [1] early stages held back until the batch before
-    // has finished its fine-level diffusion (default) or not; [2] no placement probe; [11] 1 = one column-march detector launch
-    // per level instead of one per set of levels (the others: include/akaze_hip_debug.h)
-    int sched[12] = {0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t big_px_sync = gates::kBigPxSync, big_px_async = gates::kBigPxAsync;  // (sched[4] sets both: measurement)
-    uint64_t lane_px = gates::kLanePx;  // jobs below it go to the lanes, if the context has any (sched[4] sets it too)
     // Stream placement (place_streams): the runtime multiplexes a process's streams onto a few in-order hardware queues
     // (GPU_MAX_HW_QUEUES, 4 by default); two busy streams of a context on one queue serialise the whole pipeline, so the
     // first large batch measures which of the context's streams actually run side by side and replaces those that do not
@@ -232,7 +284,6 @@ struct akz_ctx {
     int place_retries = 0;       // probe measurements that were repeated because the first answer was "shared" or ambiguous
     int lane_collisions = 0;     // lanes whose stream still shares a queue or a pipe with another lane's
     hipEvent_t probe_ev[2] = {nullptr, nullptr};
-    int profiling = 0;  // 0 off, 1 FED spans + host-clock stages, 2 every stage
     akz_profile prof{};
     struct Span { int stage; hipEvent_t a, b; int row; };
     std::vector<Span> spans;          // recorded, not yet resolved
@@ -248,14 +299,13 @@ struct akz_ctx {
     hipEvent_t fed_ev[kFedRing] = {nullptr, nullptr, nullptr, nullptr};
     // ... and pre_ev[seq % kFedRing] behind the last diffusion launch of its FIRST octave: from there to the detectors the
     // main stream carries the half-resolution octave's launches, which are bound by latency and leave most of the chip's
-    // bandwidth unused -- that is where the next job's blur and contrast passes go (sched[1] = 2)
+    // bandwidth unused -- that is where the next job's blur and contrast passes go (sched[SCHED_EARLY_HOLD] = 2)
     hipEvent_t pre_ev[kFedRing] = {nullptr, nullptr, nullptr, nullptr};
     std::atomic<uint64_t> begin_seq{0};  // sequence number of the job begun last
     std::shared_ptr<std::atomic<int>> in_hand = std::make_shared<std::atomic<int>>(0);  // akz_job::in_hand
     std::unique_ptr<WorkerPool> workers;  // host threads of the finish half (started on first use)
-    unsigned host_threads = 0;            // akz_ctx_set_host_threads; 0 = sized by host_cpu_share()
     WorkerPool& pool() {
-        if (!workers) workers.reset(new WorkerPool(std::min(host_threads ? host_threads : host_cpu_share(), 16u) - 1));
+        if (!workers) workers.reset(new WorkerPool(std::min(settings.host_threads ? settings.host_threads : host_cpu_share(), 16u) - 1));
         return *workers;
     }
     // akz_fetch_pyramid (akz_result.cpp), private to it like `lazy`: the streams its downloads run on, the pinned staging ring
@@ -276,18 +326,29 @@ struct akz_ctx {
     DevBuf jpeg_coef, jpeg_plane, jpeg_frames;
     std::mutex jpeg_m;
 };
+// What a lane runs with: its parent's settings, with the job gates no lower than lane_px (a job that is dealt to a lane runs there
+// as a one-stream chain)
+AKZ_LOCAL inline CtxSettings lane_settings(const CtxSettings& parent) {
+    CtxSettings s = parent;
+    for (uint64_t* big_px : {&s.big_px_sync, &s.big_px_async}) *big_px = std::max(*big_px, s.lane_px);
+    return s;
+}
+// the end of every setter: what was written to c->settings reaches the lanes
+AKZ_LOCAL inline void push_settings(akz_ctx* c) {
+    for (akz_ctx* l : c->lanes) l->settings = lane_settings(c->settings);
+}
 // What a job decides for the launch helpers (akz_ops.cpp) it shares with the per-op entry points and the lazy recomputations.
 // Everything else they depend on (fed_mode, det_mode, stream_min_px, sched[], profiling) is a context setting no job overrides.
 struct JobForm {
     hipStream_t stream;     // the stream to enqueue on
-    int prep_mode;          // the preparation mode in force (akz_ctx::prep_mode; extract_begin: 0 for jobs below gates::kTiledPrepPx)
+    int prep_mode;          // the preparation mode in force (CtxSettings::prep_mode; extract_begin: 0 for jobs below gates::kTiledPrepPx)
     // pixels per LAUNCH (level w*h*n) from which the blur, the contrast passes and the detectors take their column-march
     // form: 8 Mpx (a 32 x 480x270 level: 41 us tiled against 66 for the march, which would run one strip per image row);
     // inside a batch-path job smaller than that, the job's own size -- its full-resolution launches march, the rest is tiled
     uint64_t march_min_px;
 };
 // outside a job: the context's stream, the mode as the user set it, the 8 Mpx gate
-AKZ_LOCAL inline JobForm no_job_form(const akz_ctx* c) { return JobForm{c->stream, c->prep_mode, gates::kMarchPx}; }
+AKZ_LOCAL inline JobForm no_job_form(const akz_ctx* c) { return JobForm{c->stream, c->settings.prep_mode, gates::kMarchPx}; }
 
 // akz_debug_kernel_rows stage of the JPEG rows: the reconstruction has no akz_profile stage of its own
 constexpr int kStageIngest = 10;
@@ -307,7 +368,7 @@ AKZ_LOCAL inline int kernel_row_locked(akz_ctx* c, int stage, uint32_t kind, uin
 }
 // launches that are counted without a span (profiling on): which sort a job's candidates took
 AKZ_LOCAL inline void kernel_row_count(akz_ctx* c, int stage, uint32_t kind, uint32_t w, uint32_t h, uint32_t n, uint64_t launches, uint64_t px) {
-    if (!c->profiling) return;
+    if (!c->settings.profiling) return;
     std::lock_guard<std::mutex> lk(c->ev_m);
     akz_kernel_row& r = c->rows[(size_t)kernel_row_locked(c, stage, kind, 0, w, h, n)];
     r.launches += launches;
@@ -337,7 +398,7 @@ struct StageTimer {
     hipStream_t s;
     int row = -1;
     StageTimer(akz_ctx* ctx, int st, hipStream_t stream) : c(ctx), stage(st), s(stream) {
-        on = c->profiling >= 2 || (c->profiling == 1 && (st == AKZ_ST_FED || st == AKZ_ST_DETECTOR));
+        on = c->settings.profiling >= 2 || (c->settings.profiling == 1 && (st == AKZ_ST_FED || st == AKZ_ST_DETECTOR));
         if (!on) return;
         a = get(c);
         b = get(c);
@@ -408,7 +469,7 @@ AKZ_LOCAL inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }  // th
 // akz_debug_set_alloc_fill: what hipMalloc returned holds 0xA5 bytes before anybody sees it (a debug mode: a fill and a wait)
 constexpr int kAllocFillByte = 0xA5;
 AKZ_LOCAL inline hipError_t alloc_fill(const akz_ctx* c, void* p, size_t bytes) {
-    if (!c->dbg_alloc_fill) return hipSuccess;
+    if (!c->settings.dbg_alloc_fill) return hipSuccess;
     const hipError_t e = hipMemset(p, kAllocFillByte, bytes);
     return e != hipSuccess ? e : hipDeviceSynchronize();
 }

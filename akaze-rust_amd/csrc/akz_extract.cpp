@@ -199,20 +199,10 @@ int akz_ctx_set_lanes(akz_ctx* c, uint32_t lanes) {
         }
         l->own_stream = true;
         l->is_lane = true;
-        l->det_mode = c->det_mode; l->prep_mode = c->prep_mode; l->match_mode = c->match_mode; l->fed_mode = c->fed_mode;
         l->cand_cap_hint = c->cand_cap_hint.load();
-        l->stream_min_px = c->stream_min_px;
-        l->big_px_sync = std::max(c->big_px_sync, c->lane_px);  // (a job that is dealt to a lane runs there as a one-stream chain)
-        l->big_px_async = std::max(c->big_px_async, c->lane_px);
-        l->host_threads = c->host_threads;
-        l->profiling = c->profiling;
-        l->dbg_pair_chunks = c->dbg_pair_chunks;
-        l->dbg_set_chunks = c->dbg_set_chunks;
-        l->dbg_host_sort = c->dbg_host_sort;
-        l->dbg_select = c->dbg_select;
-        l->dbg_alloc_fill = c->dbg_alloc_fill;
         c->lanes.push_back(l);
     }
+    push_settings(c);
     c->next_lane = 0;
     return place_lanes(c);
 }
@@ -227,7 +217,7 @@ int akz_ctx_set_eager_finish(akz_ctx* c, int on) {
 static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint32_t w, uint32_t h, uint32_t n,
                                   const akz_config* cfg, uint32_t flags, akz_job** out, bool on_host = false) {
     akz_ctx* on = c;
-    if (c && !c->lanes.empty() && (uint64_t)w * h * n < c->lane_px) {
+    if (c && !c->lanes.empty() && (uint64_t)w * h * n < c->settings.lane_px) {
         AKZ_TRY(bind(c, false));
         on = c->lanes[c->next_lane++ % c->lanes.size()];
         // the lane starts when the caller's stream has reached this point (its inputs are complete)
@@ -296,12 +286,12 @@ int akz_ctx_calibrate_gates(akz_ctx* c, uint64_t* sync_px, uint64_t* async_px, d
     constexpr int kReps = 5;
     akz_config cfg;
     akz_config_default(&cfg);
-    const uint64_t keep_sync = c->big_px_sync, keep_async = c->big_px_async;
+    const uint64_t keep_sync = c->settings.big_px_sync, keep_async = c->settings.big_px_async;
     struct Restore {
         akz_ctx* c;
         uint64_t s, a;
         bool armed = true;
-        ~Restore() { if (armed) { c->big_px_sync = s; c->big_px_async = a; } }
+        ~Restore() { if (armed) { c->settings.big_px_sync = s; c->settings.big_px_async = a; } }
     } restore{c, keep_sync, keep_async};
     double ms[5][4];
     auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
@@ -314,7 +304,7 @@ int akz_ctx_calibrate_gates(akz_ctx* c, uint64_t* sync_px, uint64_t* async_px, d
         struct Free { akz_ctx* c; void* d; ~Free() { (void)akz_device_free(c, d); } } fr{c, d};
         AKZ_TRY(akz_memcpy_h2d(c, d, frame.data(), frame.size()));
         for (int path = 0; path < 2; ++path) {
-            c->big_px_sync = c->big_px_async = path ? 0 : ~0ull;
+            c->settings.big_px_sync = c->settings.big_px_async = path ? 0 : ~0ull;
             // synchronous call
             std::vector<double> t;
             for (int r = 0; r < kReps + 1; ++r) {
@@ -358,14 +348,11 @@ int akz_ctx_calibrate_gates(akz_ctx* c, uint64_t* sync_px, uint64_t* async_px, d
         return first == 5 ? (uint64_t)kShapes[4][0] * kShapes[4][1] + 1 : (uint64_t)kShapes[first][0] * kShapes[first][1];
     };
     restore.armed = false;
-    c->big_px_sync = gate(0, 1);
-    c->big_px_async = gate(2, 3);
-    for (akz_ctx* l : c->lanes) {  // (a job that is dealt to a lane runs there as a one-stream chain)
-        l->big_px_sync = std::max(c->big_px_sync, c->lane_px);
-        l->big_px_async = std::max(c->big_px_async, c->lane_px);
-    }
-    if (sync_px) *sync_px = c->big_px_sync;
-    if (async_px) *async_px = c->big_px_async;
+    c->settings.big_px_sync = gate(0, 1);
+    c->settings.big_px_async = gate(2, 3);
+    push_settings(c);
+    if (sync_px) *sync_px = c->settings.big_px_sync;
+    if (async_px) *async_px = c->settings.big_px_async;
     if (ms_out)
         for (int si = 0; si < 5; ++si)
             for (int k = 0; k < 4; ++k) ms_out[si * 4 + k] = ms[si][k];
@@ -379,13 +366,13 @@ int akz_ctx_graph_probe(akz_ctx* c, const uint8_t* d_imgs, uint32_t w, uint32_t 
                         uint32_t flags, uint32_t reps, double* ms_graph, double* ms_plain, uint64_t* graph_nodes) {
     AKZ_TRY(bind(c));
     if (!d_imgs || !cfg || !ms_graph || !ms_plain || reps == 0) return AKZ_ERR_INVALID_ARG;
-    if ((uint64_t)w * h * n >= c->big_px_async) {  // such a batch forks its coarse chain and completes on that stream: not one capture
+    if ((uint64_t)w * h * n >= c->settings.big_px_async) {  // such a batch forks its coarse chain and completes on that stream: not one capture
         set_error("akz_ctx_graph_probe: jobs that take the batch path fork onto a second stream and cannot be captured from one");
         return AKZ_ERR_INVALID_ARG;
     }
-    const int prof = c->profiling;
-    c->profiling = 0;
-    struct Restore { akz_ctx* c; int p; ~Restore() { c->profiling = p; } } restore{c, prof};
+    const int prof = c->settings.profiling;
+    c->settings.profiling = 0;
+    struct Restore { akz_ctx* c; int p; ~Restore() { c->settings.profiling = p; } } restore{c, prof};
     // 1. warm: every buffer the chain uses exists afterwards (no allocation may happen while capturing)
     for (int i = 0; i < 2; ++i) {
         akz_result* r = nullptr;

@@ -45,8 +45,8 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
     BeginRoute rt;
     rt.big = big;
     rt.lv.resize(L);
-    const int pre_mode = c->sched[0] == 0 ? c->pre_mode : c->sched[0] == 1 ? 2 : c->sched[0] == 2 ? 1 : 0;  // (1: a stream of its own, measurement only)
-    if ((input_ready || (flags & AKZ_INPUT_READY)) && pre_mode != 0 && c->profiling < 2 && f.prep_mode == 2 && big &&
+    const int pre_mode = c->settings.sched[SCHED_EARLY_STREAM] == 0 ? c->pre_mode : c->settings.sched[SCHED_EARLY_STREAM] == 1 ? 2 : c->settings.sched[SCHED_EARLY_STREAM] == 2 ? 1 : 0;  // (1: a stream of its own, measurement only)
+    if ((input_ready || (flags & AKZ_INPUT_READY)) && pre_mode != 0 && c->settings.profiling < 2 && f.prep_mode == 2 && big &&
         launch::blur5_march_supported(w, h, (uint32_t)gaussian_kernel_size((float)cfg.base_scale_offset)) &&
         launch::contrast_march_supported(w, h, (uint32_t)gaussian_kernel_size(1.0f), (uint32_t)cfg.contrast_factor_num_bins))
         rt.pre_on = pre_mode;
@@ -56,7 +56,7 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
     // chain moves to a second stream when octave fork_octave - 1 is finished, and the main stream goes straight to the
     // detectors of the fine octaves (bandwidth-bound, 2.2 ms): the two run side by side and join before the candidate
     // list is read.  (Running two BIG kernels side by side is a loss -- see extract_begin -- so the fork is at octave 2.)
-    const int fork_octave = c->sched[3] > 0 ? c->sched[3] : 2;  // (forking at octave 3 instead, octave 2 on the main stream: -4 %; sched[3]: measurement)
+    const int fork_octave = c->settings.sched[SCHED_FORK_OCTAVE] > 0 ? c->settings.sched[SCHED_FORK_OCTAVE] : 2;  // (forking at octave 3 instead, octave 2 on the main stream: -4 %; sched[SCHED_FORK_OCTAVE]: measurement)
     // (a lone 1080p frame is a chain of dependent launches either way and only pays for the two events: measured
     // 0.596 -> 0.625 ms per streamed frame; batch-path jobs (gates::kBigPxSync / kBigPxAsync) fork)
     // Resident tail: from the first level whose image fits one compute unit, ALL remaining levels (preparation and
@@ -66,7 +66,7 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
     // against 0.32 ms resident); a batch that forks its coarse chain onto the second stream hides that latency under
     // the fine detectors and gains what the 17 small launches cost those detectors (5.9 -> 5.3 ms per 32-frame step).
     rt.res_first = L;
-    if (c->fed_mode == 2 && (f.prep_mode == 3 || (f.prep_mode == 2 && big))) {
+    if (c->settings.fed_mode == 2 && (f.prep_mode == 3 || (f.prep_mode == 2 && big))) {
         size_t f = 1;
         while (f < L && !launch::octave_resident_supported(plan[f].w, plan[f].h)) ++f;
         f = std::max(f, L > (size_t)launch::kResidentMaxLevels ? L - (size_t)launch::kResidentMaxLevels : (size_t)1);
@@ -85,7 +85,7 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
     }
     // (full stage profiling attributes time to stages: it keeps everything on one stream)
     rt.fork_level = L;
-    if (fork_octave > 0 && c->profiling < 2 && big)
+    if (fork_octave > 0 && c->settings.profiling < 2 && big)
         for (size_t i = 1; i < L && rt.fork_level == L; ++i)
             if ((int)plan[i].octave >= fork_octave) rt.fork_level = i;
     // small frames in a large batch: the resident tail may start before octave 2 -- the chain then forks where the tail
@@ -107,7 +107,7 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
         const uint64_t lpx = (uint64_t)lv.w * lv.h * n;
         if (l >= rt.res_first) {
             q.prep = Prep::Resident;
-        } else if (!lv.tau.empty() && c->fed_mode == 2 && launch::level_march_supported(lv.w, lv.h) &&
+        } else if (!lv.tau.empty() && c->settings.fed_mode == 2 && launch::level_march_supported(lv.w, lv.h) &&
                    (f.prep_mode == 3 || (f.prep_mode == 2 && lpx >= gates::kLevelMarchPx))) {
             q.prep = Prep::LevelMarch;
             q.n1 = std::min<uint32_t>((uint32_t)lv.tau.size(), 4u);
@@ -116,7 +116,7 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
             // (one launch and one plane round trip less per octave), materialised first otherwise
             q.fold_half = half && launch::level_march_half_supported(lv.w, lv.h, pv.w, pv.h, q.n1);
         } else if (f.prep_mode != 0 && launch::prep_stream_supported(lv.w, lv.h) &&
-                   (f.prep_mode == 1 || (f.prep_mode >= 2 && !half && lpx >= c->stream_min_px))) {
+                   (f.prep_mode == 1 || (f.prep_mode >= 2 && !half && lpx >= c->settings.stream_min_px))) {
             // measured on MI355X: the streaming kernel is ~2x faster for cloned levels of a batch (a single
             // frame is launch-latency bound and stays on the tiled kernel); for the first
             // level of an octave (2x2 mean of a 4x larger input) the two are equal, the tiled one stays
@@ -124,8 +124,8 @@ BeginRoute begin_route(const akz_ctx* c, const JobForm& f, const std::vector<Lev
         }
         // The next level of the octave starts from this level's final Lt: where it would take the tiled preparation
         // (k_prep), the last diffusion launch of this level writes its Lsmooth and Lflow as well -- one dependent launch
-        // less per level of a lone frame's chain (sched[6] = 1: a launch of its own, as before)
-        q.may_ride = c->sched[6] == 0 && c->fed_mode == 2 && lv.octave == pv.octave && q.prep == Prep::Tiled;
+        // less per level of a lone frame's chain (sched[SCHED_PREP_OWN_LAUNCH] = 1: a launch of its own, as before)
+        q.may_ride = c->settings.sched[SCHED_PREP_OWN_LAUNCH] == 0 && c->settings.fed_mode == 2 && lv.octave == pv.octave && q.prep == Prep::Tiled;
     }
     return rt;
 }
@@ -144,7 +144,7 @@ struct BeginState {
     uint32_t* d_count;
     uint32_t cap;
     std::vector<float> g1;        // Lsmooth taps (lib.rs:95)
-    std::vector<char> det_done;   // sched[5]: the level's detector was enqueued behind its level kernel already
+    std::vector<char> det_done;   // sched[SCHED_DET_BEHIND_LEVEL]: the level's detector was enqueued behind its level kernel already
     std::vector<char> prepared;   // level l's Lsmooth and Lflow have been written by the last diffusion launch of level l - 1 (k_fed_own's epilogue)
     bool head_fused = false;      // k_head took level 0
     float* P(size_t l, int p) const { return r->planes[l][p]; }
@@ -157,7 +157,7 @@ bool detector_one_pass(BeginState& b, size_t l, hipStream_t on) {
     akz_ctx* c = b.c;
     const LevelPlan& lv = b.r->plan[l];
     const float thr = (float)b.r->cfg.detector_threshold, bm = border_margin(lv, b.r->cfg);
-    if (c->profiling) {
+    if (c->settings.profiling) {
         c->prof.det_launches += 1;
         c->prof.det_px += (uint64_t)lv.w * lv.h * b.n;
     }
@@ -170,10 +170,10 @@ bool detector_one_pass(BeginState& b, size_t l, hipStream_t on) {
         b.P(l, AKZ_LDET), lv.w, lv.h, b.n, (uint32_t)l, thr, bm, b.d_cand, b.cap, b.d_count);
     return true;
 }
-// sched[5] (measurement, profiles/r06_interleave.txt): the detector of a fine level right behind the kernel that wrote its
+// sched[SCHED_DET_BEHIND_LEVEL] (measurement, profiles/r06_interleave.txt): the detector of a fine level right behind the kernel that wrote its
 // Lsmooth instead of after the whole fine chain -- does the detector then find (part of) the plane in the Infinity Cache?
 void interleave_detector(BeginState& b, size_t l) {
-    if (b.c->sched[5] && l < b.rt.fork_level && !b.det_done[l] && b.rt.lv[l].det == Det::March && detector_one_pass(b, l, b.chain.stream)) b.det_done[l] = 1;
+    if (b.c->settings.sched[SCHED_DET_BEHIND_LEVEL] && l < b.rt.fork_level && !b.det_done[l] && b.rt.lv[l].det == Det::March && detector_one_pass(b, l, b.chain.stream)) b.det_done[l] = 1;
 }
 
 // ---- level 0: Lt0 = gaussian_blur(img, base_scale_offset); contrast factor (lib.rs:56-69) ----
@@ -203,8 +203,8 @@ int level0(BeginState& b, const T* d_imgs, hipEvent_t input_ready) {
         if (c->pre_done) AKZ_HIP_TRY(hipStreamWaitEvent(ps, c->pre_done, 0));
         // however early the caller begins this batch, its first two stages start when the batch before goes from its
         // (VALU-bound) diffusion launches to its (bandwidth-bound) detectors: that is what they are meant to run under
-        if (c->sched[1] && b.seq > 1)
-            AKZ_HIP_TRY(hipStreamWaitEvent(ps, (c->sched[1] == 2 ? c->pre_ev : c->fed_ev)[(b.seq - 1) % akz_ctx::kFedRing], 0));
+        if (c->settings.sched[SCHED_EARLY_HOLD] && b.seq > 1)
+            AKZ_HIP_TRY(hipStreamWaitEvent(ps, (c->settings.sched[SCHED_EARLY_HOLD] == 2 ? c->pre_ev : c->fed_ev)[(b.seq - 1) % akz_ctx::kFedRing], 0));
         f.stream = ps;
     }
     // the job's candidate counter is cleared on the stream of its first stage (every detector launch comes behind that):
@@ -250,7 +250,7 @@ int resident_tail(BeginState& b, size_t i) {
     StageTimer st(c, AKZ_ST_FED, b.chain.stream);
     st.kernel(AKZ_KR_OCTAVE_RESIDENT, (uint32_t)rl.size(), plan[i].w, plan[i].h, b.n, 1, 0, px_steps);
     launch::octave_resident(b.chain.stream, b.P(i - 1, AKZ_LT), plan[i - 1].w, plan[i - 1].h, b.n, rl.data(), (uint32_t)rl.size(), b.g1.data(), b.r->d_k);
-    if (c->profiling) {
+    if (c->settings.profiling) {
         c->prof.fed_launches += 1;
         c->prof.fed_px_steps += px_steps;
     }
@@ -287,7 +287,7 @@ int level_by_march(BeginState& b, size_t i, float* A, float* B) {
         launch::level_march(b.chain.stream, level_in, b.P(i, AKZ_LSMOOTH), b.P(i, AKZ_LFLOW), d1,
                             (rem == 0 && b.keep_all) ? b.P(i, AKZ_LSTEP) : nullptr, lv.w, lv.h, n, b.g1.data(), b.r->d_k,
                             lv.octave, ht, n1, q.fold_half ? pv.w : 0u, q.fold_half ? pv.h : 0u);
-        if (c->profiling) {
+        if (c->settings.profiling) {
             c->prof.fed_launches += 1;
             c->prof.fed_px_steps += (uint64_t)lv.w * lv.h * n * n1;
             c->prof.fused_px += (uint64_t)lv.w * lv.h * n;
@@ -365,7 +365,7 @@ void detector_set(BeginState& b, hipStream_t on, DetSetLaunch go, uint32_t maxn,
     for (size_t i = 0; i < v.size(); i += maxn) {
         const uint32_t cnt = (uint32_t)std::min<size_t>(maxn, v.size() - i);
         StageTimer st(c, AKZ_ST_DETECTOR, on);
-        if (c->profiling) {
+        if (c->settings.profiling) {
             c->prof.det_launches += 1;
             uint64_t set_px = 0;
             for (size_t j = i; j < i + cnt; ++j) set_px += (uint64_t)v[j].w * v[j].h * b.n;
@@ -384,7 +384,7 @@ void detector_set(BeginState& b, hipStream_t on, DetSetLaunch go, uint32_t maxn,
 // levels whose detector is the one-kernel tiled form are grouped by sigma_size: one launch per group
 // Column-march levels are grouped the same way (sigma_size and the width's parity, which the kernel is compiled for; the kept planes and
 // the extrema test are the job's): one launch per set of up to launch::detector_march_set_max() levels, largest first, when
-// sched[11] asks for it (kDetSetsByDefault: DESIGN.md 4; sched[11] = 1: one launch per level, 2 / 11 .. 14: sets)
+// sched[SCHED_DET_SETS] asks for it (kDetSetsByDefault: DESIGN.md 4; sched[SCHED_DET_SETS] = 1: one launch per level, 2 / 11 .. 14: sets)
 constexpr bool kDetSetsByDefault = true;
 int detectors(BeginState& b, size_t lo, size_t hi, const JobForm& f) {
     akz_ctx* c = b.c;
@@ -393,9 +393,9 @@ int detectors(BeginState& b, size_t lo, size_t hi, const JobForm& f) {
     const hipStream_t on = f.stream;
     std::map<uint32_t, std::vector<launch::DetLevelDesc>> sets;
     std::map<std::pair<uint32_t, uint32_t>, std::vector<launch::DetLevelDesc>> march_sets;
-    const bool by_sets = c->sched[11] == 0 ? kDetSetsByDefault : c->sched[11] != 1;
+    const bool by_sets = c->settings.sched[SCHED_DET_SETS] == 0 ? kDetSetsByDefault : c->settings.sched[SCHED_DET_SETS] != 1;
     for (size_t l = lo; l < hi; ++l) {
-        if (b.det_done[l]) continue;  // (sched[5]: enqueued behind its level kernel already)
+        if (b.det_done[l]) continue;  // (sched[SCHED_DET_BEHIND_LEVEL]: enqueued behind its level kernel already)
         const LevelPlan& lv = b.r->plan[l];
         const float thr = (float)cfg.detector_threshold, bm = border_margin(lv, cfg);
         const Det det = b.rt.lv[l].det;
@@ -482,7 +482,7 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     if (!out) return AKZ_ERR_INVALID_ARG;
     *out = nullptr;
     AKZ_TRY(bind(c, true, c && c->is_lane));  // (a lane's finish half shares the lane's one stream: begin waits for it)
-    const uint64_t big_px = sync_call ? c->big_px_sync : c->big_px_async;  // (akz_gates.hpp)
+    const uint64_t big_px = sync_call ? c->settings.big_px_sync : c->settings.big_px_async;  // (akz_gates.hpp)
     if (!d_imgs || !cfgp || n == 0) {
         set_error("extract: null image/config or empty batch");
         return AKZ_ERR_INVALID_ARG;
@@ -523,8 +523,8 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     // automatic mode 2 is overridden.  A batch-path job marches from its own size on (JobForm::march_min_px).
     const uint64_t job_px = (uint64_t)w * h * n;
     const bool big = job_px >= big_px;
-    const bool tiled_family = c->prep_mode == 2 && c->sched[6] == 0 && job_px < gates::kTiledPrepPx;
-    const JobForm form{s, tiled_family ? 0 : c->prep_mode, big ? std::min<uint64_t>(gates::kMarchPx, job_px) : gates::kMarchPx};
+    const bool tiled_family = c->settings.prep_mode == 2 && c->settings.sched[SCHED_PREP_OWN_LAUNCH] == 0 && job_px < gates::kTiledPrepPx;
+    const JobForm form{s, tiled_family ? 0 : c->settings.prep_mode, big ? std::min<uint64_t>(gates::kMarchPx, job_px) : gates::kMarchPx};
     if (big && !c->placed) AKZ_TRY(place_streams(c));
     const BeginRoute rt = begin_route(c, form, r->plan, r->cfg, w, h, n, flags, input_ready != nullptr, big);
     BeginState b{c, r, rt, n, keep_all, form, form, seq, (Candidate*)c->cand_slot[o.slot].p, (uint32_t*)c->count_slot[o.slot].p, cap,

@@ -87,7 +87,7 @@ int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const ui
         const GuidedPairSpec& s = spec[p];
         if (!s.n0 || !s.n1) continue;
         const uint32_t tiles = (uint32_t)((s.n1 + block - 1) / block);
-        uint32_t chunks = c->dbg_pair_chunks ? c->dbg_pair_chunks : (uint32_t)std::min<uint64_t>(want, std::max<uint32_t>(1, tiles / 2));
+        uint32_t chunks = c->settings.dbg_pair_chunks ? c->settings.dbg_pair_chunks : (uint32_t)std::min<uint64_t>(want, std::max<uint32_t>(1, tiles / 2));
         chunks = std::max(1u, std::min(std::min(chunks, tiles), 64u));
         const uint32_t chunk_rows = (uint32_t)((s.n1 + chunks - 1) / chunks);
         tab.push_back(launch::GuidedPairHost{rec_total, (uint32_t)s.q_row0, (uint32_t)s.n0, (uint32_t)s.t_row0, (uint32_t)s.n1, (uint32_t)wg,

@@ -31,7 +31,7 @@ bool knn_args_ok(const char* name, const void* d0, uint64_t n0, const void* d1, 
 int knn_enqueue(akz_ctx* c, const uint8_t* d_d0, uint32_t n0, const uint8_t* d_d1, uint32_t n1, uint32_t k, uint64_t distance_threshold,
                 akz_match* d_out, uint32_t* d_counts) {
     const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
-    const uint32_t chunks = launch::knn_chunks(n0, n1, c->dbg_knn_chunks);
+    const uint32_t chunks = launch::knn_chunks(n0, n1, c->settings.dbg_knn_chunks);
     const uint32_t q_rows = launch::match_mfma_rows(n0, true), t_rows = launch::match_mfma_rows(n1, false);
     AKZ_TRY(ensure(c, c->kn_part, launch::knn_part_bytes(n0, chunks, k)));
     if (n1) {  // (the matcher's own images: like every user of them, on c->stream only)
@@ -131,7 +131,8 @@ int akz_descriptor_match_knn(akz_ctx* c, const uint8_t* d0, uint64_t n0, const u
 
 int akz_debug_set_knn_chunks(akz_ctx* c, uint32_t chunks) {  // include/akaze_hip_debug.h
     AKZ_TRY(bind(c));
-    c->dbg_knn_chunks = chunks;
+    c->settings.dbg_knn_chunks = chunks;
+    push_settings(c);
     return AKZ_OK;
 }
 

@@ -62,8 +62,8 @@ static int match_device_impl(akz_ctx* c, const uint8_t* d_d0, uint64_t n0, const
     // the scan runs on the matrix cores (integer GEMM on the unpacked bits, identical records): 24 us against 29 for the
     // popcount kernel at 128 x 128, 35 against 190 at 1024 x 1024, 3.0 ms against 9.9 at 90 K x 90 K; mode 0 keeps the
     // popcount kernel selectable
-    const bool mfma = n0 && n1 && c->match_mode != 0 && rows_le_61;
-    const uint32_t chunks = mfma ? launch::match_mfma_chunks((uint32_t)n0, (uint32_t)n1, c->dbg_pair_chunks)
+    const bool mfma = n0 && n1 && c->settings.match_mode != 0 && rows_le_61;
+    const uint32_t chunks = mfma ? launch::match_mfma_chunks((uint32_t)n0, (uint32_t)n1, c->settings.dbg_pair_chunks)
                                  : launch::match_num_chunks((uint32_t)n0, (uint32_t)n1);
     AKZ_TRY(ensure(c, c->match_rec, std::max<uint64_t>(1, n0) * (chunks + 1) * sizeof(MatchRec)));
     MatchRec* rec = (MatchRec*)c->match_rec.p;  // [chunk][query], then the merged records
@@ -75,7 +75,7 @@ static int match_device_impl(akz_ctx* c, const uint8_t* d_d0, uint64_t n0, const
         uint32_t* qpop = (uint32_t*)c->mm_pop.p;
         uint32_t* bound = qpop + q_rows;
         uint32_t* tpop = bound + q_rows;
-        const bool fp4 = c->match_mode >= 2;
+        const bool fp4 = c->settings.match_mode >= 2;
         launch::unpack_pair(c->stream, d_d0, (uint32_t)n0, q_rows, (uint8_t*)c->mm_q8.p, qpop, bound, thr, d_d1, (uint32_t)n1, t_rows,
                             (uint8_t*)c->mm_t8.p, tpop, fp4);
         launch::match_mfma(c->stream, (const uint8_t*)c->mm_q8.p, qpop, (uint32_t)n0, (const uint8_t*)c->mm_t8.p,
@@ -127,7 +127,7 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
         if (cols) AKZ_HIP_TRY(hipMemsetAsync(d_n_cols, 0, n_sets * sizeof(uint64_t), c->stream));
         return AKZ_OK;
     }
-    if (cols && c->match_mode < 2) {  // both directions ride on the FP4 kernel only: the other kernels match direction by direction
+    if (cols && c->settings.match_mode < 2) {  // both directions ride on the FP4 kernel only: the other kernels match direction by direction
         uint64_t off = 0;
         for (uint64_t k = 0; k < n_sets; ++k) {
             if (set_rows[k] == 0) AKZ_HIP_TRY(hipMemsetAsync(d_n_cols + k, 0, sizeof(uint64_t), c->stream));
@@ -137,14 +137,14 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
             off += set_rows[k];
         }
     }
-    if (c->match_mode == 0) {  // popcount kernel: set by set
+    if (c->settings.match_mode == 0) {  // popcount kernel: set by set
         for (uint64_t k = 0; k < n_sets; ++k)
             AKZ_TRY(match_device_impl(c, d_q, n0, d_train + first[(size_t)k] * 64, set_rows[k], distance_threshold, lowes_ratio,
                                       d_out + k * n0, d_n_out + k, true));
         return AKZ_OK;
     }
     // (side 1: the finish stream and the second scratch set -- akz_match_all_pairs alternates; FP4 forms only)
-    const bool alt = side == 1 && c->match_mode >= 2;
+    const bool alt = side == 1 && c->settings.match_mode >= 2;
     if (alt) AKZ_TRY(ensure_aux(c));
     hipStream_t st = alt ? c->aux : c->stream;
     DevBuf &b_q8 = alt ? c->ms1.q8 : c->mm_q8, &b_t8 = alt ? c->ms1.t8 : c->mm_t8, &b_pop = alt ? c->ms1.pop : c->mm_pop;
@@ -153,7 +153,7 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
     size_t& ring_bytes = alt ? c->ms1.ring_bytes : c->tab_ring_bytes;
     uint64_t& ring_next = alt ? c->ms1.ring_next : c->tab_ring_next;
     hipEvent_t* ring_ev = alt ? c->ms1.ring_ev : c->tab_ring_ev;
-    const bool mutual = cols && c->match_mode >= 2;
+    const bool mutual = cols && c->settings.match_mode >= 2;
     const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
     const uint32_t tr = launch::match_mfma_tile_rows();
     const uint32_t q_rows = launch::match_mfma_rows((uint32_t)n0, true);
@@ -163,7 +163,7 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
     // workgroups fill whole rounds of the chip; the chunks of a set share its pruning bounds
     // (chunks are the launch's gridDim.y: at most 65535 of them)
     const uint32_t cps = std::max(1u, std::min(launch::match_mfma_multi_chunks((uint32_t)n0, (uint32_t)n_sets,
-                                                                               (uint32_t)((total_rows / n_sets + tr - 1) / tr), c->dbg_set_chunks),
+                                                                               (uint32_t)((total_rows / n_sets + tr - 1) / tr), c->settings.dbg_set_chunks),
                                                65535u / (uint32_t)n_sets));
     std::vector<launch::MatchChunkHost> chunks((size_t)n_sets * cps);
     std::vector<launch::MatchColSetHost> colsets(mutual ? (size_t)n_sets : 0);
@@ -233,7 +233,7 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
         AKZ_HIP_TRY(hipMemcpyAsync(d_tiles, stage, need, hipMemcpyHostToDevice, st));
         AKZ_HIP_TRY(hipEventRecord(ring_ev[slot], st));
     }
-    const bool fp4 = c->match_mode >= 2;
+    const bool fp4 = c->settings.match_mode >= 2;
     launch::unpack_bits(st, d_q, (uint32_t)n0, q_rows, true, (uint8_t*)b_q8.p, qpop, bound, thr, (uint32_t)n_sets,
                         nullptr, fp4);
     if (n_tiles)
@@ -264,7 +264,7 @@ int akz::match_sets_at(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const uint8_
                            set_first, side);
 }
 hipStream_t akz::match_side_stream(akz_ctx* c) {
-    if (!c || c->match_mode < 2 || bind(c, true, false) != AKZ_OK || ensure_aux(c) != AKZ_OK) return nullptr;
+    if (!c || c->settings.match_mode < 2 || bind(c, true, false) != AKZ_OK || ensure_aux(c) != AKZ_OK) return nullptr;
     return c->aux;
 }
 extern "C" {

@@ -39,7 +39,7 @@ int gaussian_blur_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_out
     }
     if ((const void*)d_in != (const void*)d_out && f.prep_mode != 0 &&
         launch::blur5_stream_supported(w, h, (uint32_t)k.size(), is_u8) &&
-        (!is_u8 || ((uintptr_t)d_in & 3u) == 0) && (f.prep_mode == 1 || (uint64_t)w * h * n >= c->stream_min_px)) {
+        (!is_u8 || ((uintptr_t)d_in & 3u) == 0) && (f.prep_mode == 1 || (uint64_t)w * h * n >= c->settings.stream_min_px)) {
         if constexpr (is_u8) launch::blur5_stream_u8(f.stream, d_in, d_out, w, h, n, k.data());
         else launch::blur5_stream_f32(f.stream, d_in, d_out, w, h, n, k.data());
         AKZ_HIP_TRY(hipGetLastError());
@@ -80,12 +80,12 @@ static int scharr_impl(akz_ctx* c, const JobForm& f, const float* d_in, float* d
 // (histogram, percentile; leaves the scratch zero) -- instead of six (blur, fill, blur, maximum, histogram, percentile).
 // d_gx / d_gy: two planes for the contrast factor's Scharr pair (the caller's level-0 Lx / Ly, which the detector writes much
 // later); d_blurred: where the contrast factor's blur of Lt0 goes (level 1's Lsmooth, or NULL: context scratch).
-// sched[10] = 1: the separate stages (measurement).
+// sched[SCHED_HEAD_SPLIT] = 1: the separate stages (measurement).
 template <typename T>
 int head_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_lt0, float* d_blurred, float* d_gx, float* d_gy, uint32_t w, uint32_t h, uint32_t n, float sigma0,
               double percentile, double gscale, uint64_t nbins, double* d_k_out, bool* fused, uint32_t* d_zero_word) {
     *fused = false;
-    if (f.prep_mode != 0 || c->sched[10] != 0 || !(sigma0 > 0.0f) || !(gscale > 0.0) || nbins == 0 || nbins > 4096) return AKZ_OK;
+    if (f.prep_mode != 0 || c->settings.sched[SCHED_HEAD_SPLIT] != 0 || !(sigma0 > 0.0f) || !(gscale > 0.0) || nbins == 0 || nbins > 4096) return AKZ_OK;
     const size_t ks0 = gaussian_kernel_size(sigma0), ks1 = gaussian_kernel_size((float)gscale);
     if (!launch::head_fused_supported(w, h, (uint32_t)ks0, (uint32_t)ks1) || (const void*)d_in == (const void*)d_lt0) return AKZ_OK;
     const std::vector<float> k5 = gaussian_kernel(sigma0, ks0), g3 = gaussian_kernel((float)gscale, ks1);
@@ -145,7 +145,7 @@ int contrast_impl(akz_ctx* c, const JobForm& f, const float* d_in, uint32_t w, u
     c->small_zero = 0;  // (these passes do not clean up after themselves)
     const size_t ks = gaussian_kernel_size((float)gscale);
     const bool stream = f.prep_mode != 0 && gscale > 0.0 && launch::contrast_stream_supported(w, h, (uint32_t)ks, (uint32_t)nbins) &&
-                        (f.prep_mode == 1 || (uint64_t)w * h * n >= c->stream_min_px);
+                        (f.prep_mode == 1 || (uint64_t)w * h * n >= c->settings.stream_min_px);
     const bool march = gscale > 0.0 && (f.prep_mode == 3 || (f.prep_mode == 2 && (uint64_t)w * h * n >= f.march_min_px)) &&
                        launch::contrast_march_supported(w, h, (uint32_t)ks, (uint32_t)nbins);
     if (march) {
@@ -174,10 +174,10 @@ int contrast_impl(akz_ctx* c, const JobForm& f, const float* d_in, uint32_t w, u
 static constexpr uint32_t kFedMaxFuse = 8;
 uint32_t fed_max_fuse(const akz_ctx* c, uint32_t w, uint32_t h, uint32_t n) {
     constexpr uint64_t deep_wgs = gates::kFedDeepWorkgroups;
-    return c->fed_mode == 2 && launch::fed_deep_workgroups(w, h, n) <= deep_wgs ? 2 * kFedMaxFuse : kFedMaxFuse;
+    return c->settings.fed_mode == 2 && launch::fed_deep_workgroups(w, h, n) <= deep_wgs ? 2 * kFedMaxFuse : kFedMaxFuse;
 }
 uint32_t fed_num_launches(const akz_ctx* c, uint32_t n_tau, uint32_t w, uint32_t h, uint32_t n) {
-    if (c->fed_mode == 0) return n_tau;
+    if (c->settings.fed_mode == 0) return n_tau;
     const uint32_t fuse = fed_max_fuse(c, w, h, n);
     return (n_tau + fuse - 1) / fuse;
 }
@@ -203,7 +203,7 @@ int fed_impl(akz_ctx* c, const JobForm& f, const float* in, float* A, float* B, 
             set_error("internal: FED ping-pong aliasing");
             return AKZ_ERR_INVALID_ARG;
         }
-        if (c->fed_mode == 0) {
+        if (c->settings.fed_mode == 0) {
             const float half_tau = 0.5f * (float)taus[done];
             done += 1;
             launch::fed_step(f.stream, cur, lflow, dst, (done == n_tau) ? lstep : nullptr, w, h, n, half_tau);
@@ -219,7 +219,7 @@ int fed_impl(akz_ctx* c, const JobForm& f, const float* in, float* A, float* B, 
         }
         cur = dst;
     }
-    if (c->profiling) {
+    if (c->settings.profiling) {
         c->prof.fed_launches += launches;
         c->prof.fed_px_steps += (uint64_t)w * h * n * n_tau;
     }
@@ -234,9 +234,9 @@ int fed_impl(akz_ctx* c, const JobForm& f, const float* in, float* A, float* B, 
 // kept (tools/march_probe.py, microseconds, sigma_size 3): 1920x1080 555 / 503 / 350, 960x540 140 / 124 / 82,
 // 480x270 45 / 41 / 66 (pair / tiled / march): the march from 8 Mpx per launch on.
 int detector_family(const akz_ctx* c, const JobForm& f, uint32_t sigma, uint32_t w, uint32_t h, uint32_t n, float border_m, bool nms) {
-    if (c->det_mode == 0) return 0;
-    if (c->det_mode == 4) return launch::detector_tiled_fused_supported(sigma) ? 4 : 0;
-    if (c->det_mode == 5) return launch::detector_march_supported(sigma, w, h, border_m, nms) ? 5 : 0;
+    if (c->settings.det_mode == 0) return 0;
+    if (c->settings.det_mode == 4) return launch::detector_tiled_fused_supported(sigma) ? 4 : 0;
+    if (c->settings.det_mode == 5) return launch::detector_march_supported(sigma, w, h, border_m, nms) ? 5 : 0;
     const uint64_t march_min = f.march_min_px;
     const uint64_t px = (uint64_t)w * h * n;
     if (px >= march_min && launch::detector_march_supported(sigma, w, h, border_m, nms)) return 5;

@@ -154,7 +154,7 @@ int place_streams(akz_ctx* c) {
     AKZ_TRY(ensure_aux(c));
     if (!c->coarse) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->coarse, hipStreamNonBlocking));
     if (!c->copy) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
-    if (c->sched[2]) {  // (measurement: no probe -- streams as the runtime placed them)
+    if (c->settings.sched[SCHED_NO_PROBE]) {  // (measurement: no probe -- streams as the runtime placed them)
         c->pre_mode = 2;
         return AKZ_OK;
     }
@@ -177,7 +177,7 @@ int place_streams(akz_ctx* c) {
 // side by side -- the same check for the lanes' streams (among themselves: the caller's stream carries only the events
 // that order a lane behind the caller's work).  Up to four lanes can have a pipe each.
 int place_lanes(akz_ctx* c) {
-    if (c->sched[2] || c->lanes.empty()) return AKZ_OK;
+    if (c->settings.sched[SCHED_NO_PROBE] || c->lanes.empty()) return AKZ_OK;
     for (akz_ctx* l : c->lanes) AKZ_HIP_TRY(hipStreamSynchronize(l->stream));
     StreamPlacer sp(c);
     AKZ_TRY(sp.calibrate(c->lanes[0]->stream));
@@ -200,7 +200,7 @@ int place_lanes(akz_ctx* c) {
 int akz::place_streams_beside(akz_ctx* c, hipStream_t* slots, int n_slots, int* still_shared) {
     AKZ_TRY(bind(c));
     if (still_shared) *still_shared = 0;
-    if (c->is_lane || c->sched[2] || n_slots <= 0) return AKZ_OK;
+    if (c->is_lane || c->settings.sched[SCHED_NO_PROBE] || n_slots <= 0) return AKZ_OK;
     if (!c->placed) AKZ_TRY(place_streams(c));
     AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
     AKZ_HIP_TRY(hipStreamSynchronize(c->coarse));

@@ -41,30 +41,42 @@ int akz_debug_match_tile_rows(uint32_t* rows);
    the merge of the chunks' partial lists at a few hundred rows; 0 = automatic (the default).  The counterpart of pair_chunks
    above.  Results are identical for every value. */
 int akz_debug_set_knn_chunks(akz_ctx* ctx, uint32_t chunks);
-/* Measurement hook: schedule variants of a large batch (results are identical).  key 0: where the early stages
-   (level-0 blur, contrast factor) of a batch whose input is complete run: 0 = the copy stream if the context's
-   stream-placement probe found it a hardware queue and a pipe of its own (default), 1 = the copy stream regardless, 2 = a
-   stream of their own (a fifth busy stream), 3 = the context's stream (no running ahead); key 1: they are held back until
-   the batch before has finished its fine-level diffusion (1, default) or start at once (0); key 2: 1 = no placement probe;
-   key 3: octave at which the coarse chain forks (0 = default 2); key 4: the job size in thousands of pixels (w*h*n) from
-   which a job takes the batch path -- column-march kernels, forked coarse chain, resident tail -- 0 = default (1 400 for the synchronous entry points, 300 for the begin / finish interface since the end of round 6;
-   6 000 / 3 000 in round 5; the same value also replaces lane_px, the size below which a context with lanes deals its jobs to them);
-   key 5: 1 = the detector of a fine level right behind its level kernel (profiles/r06_interleave.txt: measured, not the default);
-   key 6: 1 = every level's preparation as a launch of its own (default 0: on the tiled path the last diffusion launch of a level
-   also prepares the next level of the octave -- k_fed_own's epilogue);
-   keys 7, 8 (process-wide): the least interior rows of a band of the detector march / the level march, 0 = the planners' rules
-   (40; 20 below 48 Mpx per launch) -- how finely a small job's column marches are cut into workgroups;
-   key 9: bit 0 = the waited-for job's headers, keypoint records and descriptor rows come to the host as three copies behind the
-   descriptor kernel (default: that kernel stores them into the host's pinned buffers itself); bit 1 = the keypoint kernels of
-   a job that is alone in the context's hands on the auxiliary stream, as every other job's (default: on the main stream,
-   in order behind its detectors, when its chain ended there);
-   key 10: 1 = level 0 of a tiled-family job as separate launches -- blur, clearing of the contrast scratch, blur, maximum,
-   histogram, percentile, and level 1's preparation as a k_prep launch (default 0: k_head + k_contrast_hist_final, and
-   level 1's Lflow from k_head's Scharr pair);
-   key 11: how the column-march detectors of a range of levels are launched: 1 = one launch per level; 2 = one launch per
-   set of up to four levels that share sigma_size, the width's parity and the kept planes (largest first); 0 = the default
-   (which of the two it is, and why); 11 .. 14 = sets, cut into 1 .. 4 x 3 x CUs cells instead of kDetSetWaves x
-   (process-wide: the sweep behind that constant). */
+/* Measurement hook: schedule variants (results are identical).  A context with lanes (akz_ctx_set_lanes) hands every key to them,
+   whichever of the two calls comes first.  Keys outside 0 .. 11 are refused.  The keys (csrc/akz_ctx.hpp carries the same list above its enum Sched):
+    0 SCHED_EARLY_STREAM     where the early stages (level-0 blur, contrast factor) of a batch whose input is complete run:
+                             0 = the copy stream if the stream-placement probe found it a hardware queue and a pipe of its own,
+                             1 = the copy stream regardless, 2 = a stream of their own (a fifth busy stream), 3 = the context's
+                             stream (no running ahead).  Default 0.
+    1 SCHED_EARLY_HOLD       what the early stages wait for: 0 = nothing, 1 = the fine-level diffusion of the batch before,
+                             2 = the first octave's diffusion of the batch before.  Default 1.
+    2 SCHED_NO_PROBE         1 = no stream-placement probe: streams stay as the runtime placed them.  Default 0.
+    3 SCHED_FORK_OCTAVE      the octave at which the coarse chain of a batch forks onto its own stream; 0 = octave 2.  Default 0.
+    4 SCHED_JOB_KPX          the job size in thousands of pixels (w*h*n) from which a job takes the batch path (column-march
+                             kernels, forked coarse chain, resident tail); the same value replaces lane_px, the size below which a
+                             context with lanes deals its jobs to them; 0 = the gates of akz_debug_gates (big_px_sync,
+                             big_px_async, lane_px).  Default 0.
+    5 SCHED_DET_BEHIND_LEVEL 1 = the column-march detector of a fine level right behind its level kernel, 0 = behind the whole
+                             fine chain (profiles/r06_interleave.txt).  Default 0.
+    6 SCHED_PREP_OWN_LAUNCH  1 = every level's preparation as a launch of its own and no tiled preparation family chosen per job,
+                             0 = on the tiled path the last diffusion launch of a level also prepares the next level of the
+                             octave (k_fed_own's epilogue).  Default 0.
+    7 SCHED_DET_BAND_ROWS    process-wide: the least interior rows of a band of the detector march -- how finely a small job's
+                             column marches are cut into workgroups; 0 = the planner's rule (40).  Default 0.
+    8 SCHED_LEVEL_BAND_ROWS  process-wide: the same for the level march, plus 1000 x the same for the level-0 marches; 0 = the
+                             planners' rules (level march: 20 below 48 Mpx per launch).  Default 0.
+    9 SCHED_FINISH_FORM      bit 0 = the waited-for job's headers, keypoint records and descriptor rows come to the host as three
+                             copies behind the descriptor kernel, clear = that kernel stores them into the host's pinned buffers
+                             itself; bit 1 = the keypoint kernels of a job that is alone in the context's hands on the auxiliary
+                             stream, as every other job's, clear = on the main stream, in order behind its detectors, when its
+                             chain ended there.  Default 0.
+   10 SCHED_HEAD_SPLIT       1 = level 0 of a tiled-family job as separate launches (blur, clearing of the contrast scratch, blur,
+                             maximum, histogram, percentile, and level 1's preparation as a k_prep launch), 0 = k_head +
+                             k_contrast_hist_final, and level 1's Lflow from k_head's Scharr pair.  Default 0.
+   11 SCHED_DET_SETS         how the column-march detectors of a range of levels are launched: 1 = one launch per level, 2 = one
+                             launch per set of up to four levels that share sigma_size, the width's parity and the kept planes
+                             (largest first), 0 = whichever of the two DESIGN.md 4 names the default, 11 .. 14 = sets, cut into
+                             1 .. 4 x 3 x CUs cells instead of kDetSetWaves x (process-wide: the sweep behind that constant).
+                             Default 0. */
 int akz_debug_set_schedule(akz_ctx* ctx, int key, int value);
 /* What the stream-placement probe of the context's first large batch found: info[0] = it has run, info[1] = early stages on
    the context's stream (0) or the copy stream (2), info[2] = streams it re-created because they shared a hardware queue
@@ -114,7 +126,8 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    covered by a group of k_fed_own launches, levels inside a k_octave_resident launch, sigma_size of a detector launch;
    (w, h, n): the launch's level size and batch (the largest level of a k_detector_tiled launch over several levels);
    launches, px = level pixels x batch, px_steps = pixel-steps advanced, ms = sum of the spans.  Rows accumulate like
-   akz_profile; reset != 0 zeroes the figures.  *n_rows = rows there are (may exceed cap).
+   akz_profile; reset != 0 zeroes the figures.  *n_rows = rows there are (may exceed cap).  The rows of a context with lanes
+   (akz_ctx_set_lanes) include its lanes', summed per kernel variant and shape, as its profile does.
    JPEG reconstruction (akz_extract_features_file / _files, akz_image_load_luma_device) adds rows of stage 10, which no
    akz_profile stage counts: k_jpeg_idct (px = coefficients), k_jpeg_luma (px = output pixels) and the coefficient upload
    (px = bytes copied), each with param = components and (w, h, 1) = the frame.

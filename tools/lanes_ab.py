@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A stream of lone frames dealt to 1 .. 4 lanes of one context (akz_ctx_set_lanes), alternated three times; variants are
 akz_debug_set_schedule settings as in tools/lone_ab.py ("name:key=value,...").
+The variants reach the lanes from round 24 on (CtxSettings); before it every column but "1 lane" ran the default schedule.
     python tools/lanes_ab.py [W H] [variants]"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "akaze-rust_amd", "python"))
