@@ -89,7 +89,7 @@ int akz_ctx_create(int device, void* stream, akz_ctx** out) {
     }
     std::unique_ptr<akz_ctx> c(new akz_ctx);
     c->device = device;
-    c->stream = (hipStream_t)stream;  // NULL == the default stream
+    c->stream = Stream::borrow((hipStream_t)stream);  // NULL == the default stream
     *out = c.release();
     return AKZ_OK;
 }
@@ -113,108 +113,9 @@ int akz_ctx_destroy(akz_ctx* c) {
     finisher_stop(c);
     for (akz_ctx* l : c->lanes) (void)akz_ctx_destroy(l);
     c->lanes.clear();
-    if (c->lane_in) { (void)hipEventDestroy(c->lane_in); c->lane_in = nullptr; }
-    (void)hipStreamSynchronize(c->stream);
-    DevBuf* bufs[] = {&c->lazy[0], &c->lazy[1], &c->lazy[2], &c->lazy[3], &c->lazy[4], &c->lazy[5],
-                      &c->scratch[0], &c->scratch[1], &c->scratch[2], &c->scratch[3], &c->scratch[4], &c->scratch[5], &c->scratch_coarse,
-                      &c->small, &c->cand, &c->cand_sorted, &c->sort_scratch, &c->rel_scratch, &c->sel_scratch, &c->sel_recs, &c->bucket_scratch, &c->kp_in, &c->kp_out, &c->match_a, &c->match_b, &c->match_rec, &c->match_state,
-                      &c->match_out, &c->cosi, &c->mm_q8, &c->mm_t8, &c->mm_pop, &c->mm_tab, &c->mm_cols,
-                      &c->ms1.q8, &c->ms1.t8, &c->ms1.pop, &c->ms1.tab, &c->ms1.cols, &c->ms1.rec, &c->ransac_dev,
-                      &c->mp_in, &c->mp_raw, &c->mp_tab, &c->mp_trials, &c->mp_keep, &c->gd_tab, &c->gd_rec, &c->gd_out, &c->cx_rev, &c->kn_part, &c->kn_io, &c->kb_dev};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (DevBuf* b : {&c->jpeg_coef, &c->jpeg_plane, &c->jpeg_frames})
-        if (b->p) (void)hipFree(b->p);
-    for (int k = 0; k < akz_ctx::kJpegSlots; ++k) {
-        if (c->jpeg_up[k]) (void)hipEventDestroy(c->jpeg_up[k]);
-        if (c->jpeg_pin[k].p) (void)hipHostFree(c->jpeg_pin[k].p);
-    }
-    for (DevBuf& b : c->fetch_tmp)
-        if (b.p) (void)hipFree(b.p);
-    for (auto& set : c->fetch_out)
-        for (DevBuf& b : set)
-            if (b.p) (void)hipFree(b.p);
-    if (c->fetch_stage.p) (void)hipHostFree(c->fetch_stage.p);
-    for (hipEvent_t* e : {&c->fetch_chunk[0], &c->fetch_chunk[1], &c->fetch_chunk[2], &c->fetch_chunk[3], &c->fetch_start,
-                          &c->fetch_join, &c->fetch_ready[0], &c->fetch_ready[1], &c->fetch_free[0], &c->fetch_free[1]}) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-    for (hipStream_t& s : c->fetch) {
-        if (s) (void)hipStreamDestroy(s);
-        s = nullptr;
-    }
-    for (DevBuf& b : c->pin)
-        if (b.p) (void)hipHostFree(b.p);
-    if (c->ransac_pin.p) (void)hipHostFree(c->ransac_pin.p);
-    for (DevBuf* b : {&c->mp_pin_in, &c->mp_pin_tab, &c->mp_pin_smp[0], &c->mp_pin_smp[1], &c->mp_pin_out, &c->gd_pin_tab, &c->gd_pin_cnt, &c->gd_pin_out, &c->cx_pin_tab, &c->kb_pin})
-        if (b->p) (void)hipHostFree(b->p);
-    for (hipEvent_t& e : c->mp_smp_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t& e : c->mp_split_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t& e : c->kb_split_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->tab_ring) (void)hipHostFree(c->tab_ring);
-    c->tab_ring = nullptr;
-    if (c->ms1.ring) (void)hipHostFree(c->ms1.ring);
-    c->ms1.ring = nullptr;
-    for (hipEvent_t& e : c->ms1.ring_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    for (hipEvent_t& e : c->tab_ring_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    if (c->copy) {
-        (void)hipStreamSynchronize(c->copy);
-        (void)hipStreamDestroy(c->copy);
-        c->copy = nullptr;
-    }
-    for (int i = 0; i < akz_ctx::kSlots; ++i) {
-        if (c->cand_slot[i].p) (void)hipFree(c->cand_slot[i].p);
-        if (c->count_slot[i].p) (void)hipFree(c->count_slot[i].p);
-        if (c->stage[i].p) (void)hipFree(c->stage[i].p);
-        if (c->staged[i]) (void)hipEventDestroy(c->staged[i]);
-        c->staged[i] = nullptr;
-    }
-    if (c->aux) {
-        (void)hipStreamSynchronize(c->aux);
-        (void)hipStreamDestroy(c->aux);
-    }
-    if (c->coarse) {
-        (void)hipStreamSynchronize(c->coarse);
-        (void)hipStreamDestroy(c->coarse);
-        c->coarse = nullptr;
-    }
-    if (c->pre) {
-        (void)hipStreamSynchronize(c->pre);
-        (void)hipStreamDestroy(c->pre);
-        c->pre = nullptr;
-    }
-    if (c->pre_done) { (void)hipEventDestroy(c->pre_done); c->pre_done = nullptr; }
-    for (auto& s : c->slab_pool) (void)hipFree(s.second);
-    for (auto& sp : c->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    c->slab_pool.clear();
-    c->spans.clear();
-    c->ev_pool.clear();
-    c->aux = nullptr;
-    c->workers.reset();  // joins the host worker threads
-    for (hipEvent_t& e : c->fed_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    for (hipEvent_t& e : c->pre_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    for (hipEvent_t& e : c->probe_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
+    (void)sync_all_streams(c);  // nothing may still run on what goes now
+    c->workers.reset();         // joins the host worker threads
+    static_cast<CtxOwned&>(*c) = CtxOwned();  // every buffer, event and stream of the context: each releases itself
     c->dead = true;  // results that are still alive keep the (now resource-less) struct; see result_delete
     if (c->live_results == 0) delete c;
     return AKZ_OK;
@@ -222,13 +123,10 @@ int akz_ctx_destroy(akz_ctx* c) {
 int akz_ctx_synchronize(akz_ctx* c) {
     AKZ_TRY(bind(c));
     for (akz_ctx* l : c->lanes) AKZ_TRY(akz_ctx_synchronize(l));
-    AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->coarse) AKZ_HIP_TRY(hipStreamSynchronize(c->coarse));
-    if (c->pre) AKZ_HIP_TRY(hipStreamSynchronize(c->pre));
-    if (c->copy) AKZ_HIP_TRY(hipStreamSynchronize(c->copy));
+    AKZ_HIP_TRY(sync_all_streams(c, kSyncMain | kSyncSide));  // (the finish half's stream is waited for by whoever collects a job)
     return AKZ_OK;
 }
-void* akz_ctx_stream(akz_ctx* c) { return c ? (void*)c->stream : nullptr; }
+void* akz_ctx_stream(akz_ctx* c) { return c ? (void*)c->stream.h : nullptr; }
 
 int akz_device_malloc(akz_ctx* c, size_t bytes, void** d_out) {
     AKZ_TRY(bind(c));
@@ -534,9 +432,9 @@ static int audit_one(akz_ctx* c, const char* prefix, akz_scratch_audit* out, uin
         size_t bytes;
         bool epochs;
     };
-    const Claim claims[3] = {{"small", &c->small, c->small_zero_p == c->small.p ? c->small_zero : 0, false},
-                             {"bucket_scratch", &c->bucket_scratch, c->bucket_zero, false},
-                             {"match_state", &c->match_state, c->match_state_known, true}};
+    const Claim claims[3] = {{"small", &c->small, c->small.known, false},
+                             {"bucket_scratch", &c->bucket_scratch, c->bucket_scratch.known, false},
+                             {"match_state", &c->match_state, c->match_state.known, true}};
     std::vector<uint64_t> host;
     for (const Claim& cl : claims) {
         akz_scratch_audit row{};
@@ -573,6 +471,12 @@ int akz_debug_audit_scratch(akz_ctx* c, akz_scratch_audit* out, uint32_t cap, ui
         AKZ_TRY(audit_one(c->lanes[i], prefix, out, cap, &k));
     }
     *n_rows = k;
+    return AKZ_OK;
+}
+int akz_debug_resource_counts(uint64_t out[6]) {
+    if (!out) return AKZ_ERR_INVALID_ARG;
+    static_assert(res::kKinds_ == 6, "akaze_hip_debug.h promises six counters");
+    for (int k = 0; k < res::kKinds_; ++k) out[k] = res::live[k].load(std::memory_order_relaxed);
     return AKZ_OK;
 }
 int akz_debug_set_device_libm(akz_ctx* c, int mode) {

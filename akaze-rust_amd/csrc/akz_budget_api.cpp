@@ -155,8 +155,7 @@ int akz_keypoint_budget_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t n
     AKZ_TRY(ensure_pinned(c, c->kb_pin, b_up + b_idx + b_f));
     const bool timed = c->kb_split_on;
     if (timed)
-        for (hipEvent_t& e : c->kb_split_ev)
-            if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
+        for (Event& e : c->kb_split_ev) AKZ_TRY(e.ensure(hipEventDefault));
     char *d = (char*)c->kb_dev.p, *h = (char*)c->kb_pin.p;
     float *hx = (float*)h, *hy = (float*)(h + b_f), *hr = (float*)(h + 2 * b_f);
     for (uint64_t s = 0; s < n_sets; ++s) {

@@ -50,9 +50,136 @@ static_assert(sizeof(SelKpHost) == 32, "the device writes 32-byte records");
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
+// What the library holds of the runtime -- memory blocks, events, streams -- lives in three move-only owners: each frees its handle
+// when it goes, so a context (CtxOwned below) or a function that declares one has said all there is to say about its lifetime.
+// res::live counts what they hold, process-wide (akz_debug_resource_counts): up on acquire, down on release.
+namespace res {
+enum Kind { kDevBlocks = 0, kDevBytes, kPinBlocks, kPinBytes, kEvents, kStreams, kKinds_ };
+AKZ_LOCAL inline std::atomic<uint64_t> live[kKinds_];
+inline void up(Kind k, uint64_t n = 1) { live[k].fetch_add(n, std::memory_order_relaxed); }
+inline void down(Kind k, uint64_t n = 1) { live[k].fetch_sub(n, std::memory_order_relaxed); }
+}  // namespace res
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    bool pinned = false;  // page-locked host memory (ensure_pinned, the matcher's rings), else device memory
+    size_t known = 0;     // a scratch claim on the first `known` bytes; 0: nothing known, as of every fresh block
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), pinned(o.pinned), known(o.known) { o.forget(); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            (void)release();
+            p = o.p, bytes = o.bytes, pinned = o.pinned, known = o.known;
+            o.forget();
+        }
+        return *this;
+    }
+    ~DevBuf() { (void)release(); }
+    // an empty buffer gets exactly `want` bytes (the growth rules are the callers': ensure, ensure_pinned, the rings, the slabs)
+    hipError_t acquire(size_t want, bool pin) {
+        const hipError_t e = pin ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+        if (e != hipSuccess) return p = nullptr, e;
+        bytes = want, pinned = pin;
+        res::up(pin ? res::kPinBlocks : res::kDevBlocks);
+        res::up(pin ? res::kPinBytes : res::kDevBytes, want);
+        return hipSuccess;
+    }
+    hipError_t release() {
+        if (!p) return hipSuccess;
+        res::down(pinned ? res::kPinBlocks : res::kDevBlocks);
+        res::down(pinned ? res::kPinBytes : res::kDevBytes, bytes);
+        void* gone = p;
+        forget();
+        return pinned ? hipHostFree(gone) : hipFree(gone);
+    }
+    // a device block on its way through raw pointers (a result's slab: akz_result.cpp); it stays counted in between
+    static DevBuf adopt(void* block, size_t block_bytes) {
+        DevBuf b;
+        b.p = block, b.bytes = block_bytes;
+        return b;
+    }
+    void* detach() {
+        void* block = p;
+        forget();
+        return block;
+    }
+
+private:
+    void forget() { p = nullptr, bytes = 0, known = 0; }
+};
+// An event / a stream: converts to the raw handle, so record, wait and launch sites spell it as they would the handle; ensure()
+// creates it on first use.  A Stream may also BORROW a handle (the caller's stream of akz_ctx_create), which it never destroys.
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) reset(), h = o.h, o.h = nullptr;
+        return *this;
+    }
+    ~Event() { reset(); }
+    operator hipEvent_t() const { return h; }
+    int ensure(unsigned flags = hipEventDisableTiming) {
+        if (h) return AKZ_OK;
+        AKZ_HIP_TRY(hipEventCreateWithFlags(&h, flags));
+        res::up(res::kEvents);
+        return AKZ_OK;
+    }
+    void reset() {
+        if (!h) return;
+        (void)hipEventDestroy(h);
+        res::down(res::kEvents);
+        h = nullptr;
+    }
+};
+struct Stream {
+    hipStream_t h = nullptr;
+    bool owned = false;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : h(o.h), owned(o.owned) { o.h = nullptr, o.owned = false; }
+    Stream& operator=(Stream&& o) noexcept {
+        if (this != &o) reset(std::move(o));
+        return *this;
+    }
+    ~Stream() { reset(); }
+    operator hipStream_t() const { return h; }
+    int ensure() {  // (non-blocking, like every stream of the library)
+        if (h) return AKZ_OK;
+        AKZ_HIP_TRY(hipStreamCreateWithFlags(&h, hipStreamNonBlocking));
+        res::up(res::kStreams);
+        owned = true;
+        return AKZ_OK;
+    }
+    static Stream borrow(hipStream_t theirs) {
+        Stream s;
+        s.h = theirs;
+        return s;
+    }
+    // a stream of another component that hands it over for good / takes it back (akz::place_streams_beside)
+    static Stream adopt(hipStream_t theirs) {
+        Stream s;
+        s.h = theirs, s.owned = theirs != nullptr;
+        if (s.owned) res::up(res::kStreams);
+        return s;
+    }
+    hipStream_t detach() {
+        if (h && owned) res::down(res::kStreams);
+        hipStream_t out = h;
+        h = nullptr, owned = false;
+        return out;
+    }
+    void reset() {
+        if (h && owned) {
+            (void)hipStreamDestroy(h);
+            res::down(res::kStreams);
+        }
+        h = nullptr, owned = false;
+    }
+    void reset(Stream&& fresh) {  // destroys what it owns and holds `fresh` from here on
+        reset();
+        h = fresh.h, owned = fresh.owned;
+        fresh.h = nullptr, fresh.owned = false;
+    }
 };
 
 
@@ -171,39 +298,28 @@ struct CtxSettings {
     int sched[SCHED_COUNT_] = {0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // akz_debug_set_schedule, indexed by Sched
 };
 static_assert(std::is_trivially_copyable<CtxSettings>::value, "lanes get the block by plain assignment");
-struct akz_ctx {
-    CtxSettings settings;  // a lane's: lane_settings(its parent's), kept so by push_settings
-    int device = 0;
-    hipStream_t stream = nullptr;            // the caller's stream (set at creation, a lane's again by place_lanes; what other threads synchronise with)
-    bool own_stream = false;
+// Everything a context owns of the runtime, and nothing else: handles only (no mutex, no atomic), so that the whole set is released
+// by assigning an empty one (akz_ctx_destroy) -- a buffer, event or stream added here needs its declaration and nothing more.
+struct CtxOwned {
+    Stream stream;                           // the caller's stream, borrowed (akz_ctx_create); a lane's is its own (akz_ctx_set_lanes, place_lanes); what other threads synchronise with
     DevBuf scratch[6];                       // f32 plane temporaries (largest level x batch)
     DevBuf scratch_coarse;                   // the coarse chain's own diffusion scratch: it outlives the batch's join (see extract_begin)
     DevBuf lazy[6];                          // one-image planes of akz_fetch_plane's recomputation (never shared with scratch users)
     // Scratch CLAIMS: three buffers are read by a job for what an earlier job left in them, so that no clearing
-    // launch is needed.  What is known of each is stated here and nowhere else: ensure() drops the claim of a buffer it
-    // (re)allocates, the launch code drops it before it enqueues anything that dirties the range and raises it once the memset /
-    // the launches that restore the content are enqueued, and akz_debug_audit_scratch checks every raised claim on the device.
-    DevBuf small;                            // hmax bits / histogram / counters
-    void* small_zero_p = nullptr;            // claim: the first small_zero bytes of `small` are zero (head_impl: its histogram
-    size_t small_zero = 0;                   //     pass leaves them so; 0: not known)
+    // launch is needed.  What is known of each is its DevBuf::known and nothing else: every (re)allocation and release starts it at
+    // zero, the launch code drops it before it enqueues anything that dirties the range and raises it once the memset / the launches
+    // that restore the content are enqueued, and akz_debug_audit_scratch checks every raised claim on the device.
+    DevBuf small;                            // hmax bits / histogram / counters; claim: its first `known` bytes are zero (head_impl: its histogram pass leaves them so)
     DevBuf cand;                             // NMS candidates
     DevBuf cand_sorted, sort_scratch;        // the list in scan order (device sort of extract_finish) and the sort's scratch
     DevBuf rel_scratch;                      // the selection's neighbour lists (launch::candidate_relations)
     DevBuf sel_scratch, sel_recs;            // the selection on the device (launch::select_device): its scratch, the selected keypoints
-    DevBuf bucket_scratch;                   // launch::sort_candidates_buckets
-    size_t bucket_zero = 0;                  // claim: the first bucket_zero bytes of bucket_scratch (its counters) are zero; 0: not known
-    std::atomic<uint32_t> last_total_kp{0};  // keypoints of the previous finished job (speculative fetch size of the device selection)
-    std::atomic<int> sel_last_mode{-1};      // akz_debug_select_info: how the last finished job was selected (0 grids, 1 lists, 2 device), the
-    std::atomic<int> sel_skip{0};            // jobs of shape sel_skip_shape that leave the device's selection out (the last one fell back)
-    std::atomic<uint64_t> sel_skip_shape{0};
-    std::atomic<uint32_t> sel_last_ticks[4];
-    std::atomic<uint32_t> sel_last_rounds{0}, sel_last_fallback{0};  // device's longest run of rounds, images that sent it back to the host
+    DevBuf bucket_scratch;                   // launch::sort_candidates_buckets; claim: its first `known` bytes (its counters) are zero
     DevBuf kp_in, kp_out;                    // keypoint params / orientation sums
-    DevBuf match_a, match_b, match_rec, match_out;
+    DevBuf match_a, match_b, match_out;
     DevBuf match_state;                      // k_match_merge_compact's per-workgroup counts (zeroed when allocated, then told apart by epoch);
-                                             // single-stream: only ever touched by launches on `stream` (see match_device_impl)
-    uint32_t match_epoch = 0;
-    size_t match_state_known = 0;            // claim: no word of the first match_state_known bytes carries an epoch beyond match_epoch
+                                             // single-stream: only ever touched by launches on `stream` (see match_device_impl);
+                                             // claim: no word of its first `known` bytes carries an epoch beyond match_epoch
     DevBuf ransac_dev, ransac_pin;           // match_features: the trials' inputs and outputs on the device / pinned staging of both
     // akz_match_features_pairs: the sets' rows and x / y; raw lists, their counts and points; pair table and two slots of
     // trial samples; models and inlier counts; kept lists with their counts -- and the pinned staging of each
@@ -219,51 +335,90 @@ struct akz_ctx {
     // the keypoint budget (akz_budget_api.cpp): x | y | response | set table | block table, then rank | kept indices | radius2 of a
     // call; pinned: the upload's image, then kept indices | radius2.  No claim: every call initialises what its kernels accumulate into
     DevBuf kb_dev, kb_pin;
-    hipEvent_t kb_split_ev[4] = {};          // akz_debug_keypoint_budget_split: stage boundaries of a timed call
-    bool kb_split_on = false;
-    double kb_split_ms[3] = {};
-    hipEvent_t mp_smp_ev[2] = {nullptr, nullptr};
-    hipEvent_t mp_split_ev[7] = {};          // akz_debug_match_pairs_split: stage boundaries of a timed call
-    bool mp_split_on = false;
-    double mp_split_ms[6] = {};
-    DevBuf mm_q8, mm_t8, mm_pop, mm_tab;     // MFMA matcher: unpacked int8 images of the two sets, bit counts, set tables
-    DevBuf mm_cols;                          // both-direction launches: the train rows' (best, second) state, seed records and bound
-    void* tab_ring = nullptr;                // pinned staging ring of the multi-set matcher's tables
-    size_t tab_ring_bytes = 0;
-    uint64_t tab_ring_next = 0;
-    hipEvent_t tab_ring_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // A second set of the multi-set matcher's scratch: akz_match_all_pairs runs the launches of consecutive lead images
-    // alternately on the caller's stream and on the finish stream (akz::match_sets_at, side 1), so that the small launches
-    // around one image's pass (unpack, seed, compactions: 130 us of 550) run under the other's
+    Event kb_split_ev[4];                    // akz_debug_keypoint_budget_split: stage boundaries of a timed call
+    Event mp_smp_ev[2];
+    Event mp_split_ev[7];                    // akz_debug_match_pairs_split: stage boundaries of a timed call
+    // The matcher's scratch, twice.  Side 0 serves every call on the context's stream (descriptor_match, the pairs calls, kNN);
+    // akz_match_all_pairs runs the launches of consecutive lead images alternately there and on the finish stream with side 1
+    // (akz::match_sets_at), so that the small launches around one image's pass (unpack, seed, compactions: 130 us of 550) run
+    // under the other's
     struct MatchSide {
-        DevBuf q8, t8, pop, tab, cols, rec;
-        void* ring = nullptr;
-        size_t ring_bytes = 0;
+        DevBuf q8, t8, pop, tab;             // MFMA matcher: unpacked int8 images of the two sets, bit counts, set tables
+        DevBuf cols;                         // both-direction launches: the train rows' (best, second) state, seed records and bound
+        DevBuf rec;                          // chunk records [chunk][query], then the merged ones
+        static constexpr int kRing = 4;
+        DevBuf ring;                         // pinned staging ring of the multi-set matcher's tables: kRing slots of ring.bytes / kRing
         uint64_t ring_next = 0;
-        hipEvent_t ring_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    } ms1;
-    int libm_last = 0;          // how the last finished job got its angles: 0 host libm, 1 / 2 the device's FMA / SSE2 forms
+        Event ring_ev[kRing];
+    } ms[2];
     DevBuf cosi;                             // (cos, sin) per keypoint
     DevBuf pin[PIN_COUNT_];                  // pinned host staging (enum Pin)
-    std::vector<std::pair<size_t, void*>> slab_pool;  // freed device blocks (pyramid slabs, descriptor rows)
-    std::mutex slab_m;                                // results are freed by the caller while a lane's finisher thread allocates
+    std::vector<DevBuf> slab_pool;           // freed device blocks (pyramid slabs, descriptor rows), guarded by akz_ctx::slab_m
     // extractions in flight (akz_extract_begin_* / akz_extract_finish)
     static constexpr int kSlots = 3;
     DevBuf cand_slot[kSlots], count_slot[kSlots];
+    Stream aux;                         // finish-side copies and keypoint kernels (created under aux_m: the caller's thread and the finisher's may both be first)
+    Stream coarse;                      // the coarse octaves' chain (diffusion + detectors), next to the fine detectors
+    Stream pre;                         // level-0 blur + contrast factor of a batch whose input is known to be complete:
+    Event pre_done;                     // they run ahead, under the kernels of the batch before (extract_begin)
+    Stream copy;                        // uploads of host frames (akz_extract_begin_host_*), under the kernels of the batch before
+    DevBuf stage[kSlots];               // staging buffers of those uploads, one per job slot
+    Event staged[kSlots];
+    Event lane_in;                      // inputs of the job are ready on the caller's stream
+    Event probe_ev[2];                  // stream placement (place_streams)
+    struct Span { int stage; Event a, b; int row; };
+    std::vector<Span> spans;          // recorded, not yet resolved
+    std::vector<Event> ev_pool;       // recycled events (both guarded by akz_ctx::ev_m)
+    // Every extract_begin records, behind its last fine-level diffusion launch, the event fed_ev[seq % kFedRing] of its
+    // sequence number: the keypoint kernels of job i are held back until job i + 1 has passed that point, and the early
+    // stages of job i + 1 until job i has (see extract_begin).  Four slots: at most kSlots jobs are in flight.
+    static constexpr int kFedRing = 4;
+    Event fed_ev[kFedRing];
+    // ... and pre_ev[seq % kFedRing] behind the last diffusion launch of its FIRST octave: from there to the detectors the
+    // main stream carries the half-resolution octave's launches, which are bound by latency and leave most of the chip's
+    // bandwidth unused -- that is where the next job's blur and contrast passes go (sched[SCHED_EARLY_HOLD] = 2)
+    Event pre_ev[kFedRing];
+    // akz_fetch_pyramid (akz_result.cpp), private to it like `lazy`: the streams its downloads run on, the pinned staging ring
+    // pageable destinations are filled through, and the recomputation of lean results -- temporaries that only the
+    // context's stream touches, and two sets of outputs (Lxx, Lyy, Lxy, Lstep) that the downloads read alternately
+    Stream fetch[2];                         // downloads alternate between two streams (two copy engines)
+    DevBuf fetch_stage;                      // pinned: kFetchStageBufs buffers of kFetchStageBytes
+    Event fetch_chunk[4];                    // a staging buffer's download is complete
+    DevBuf fetch_tmp[3], fetch_out[2][4];
+    Event fetch_start, fetch_join, fetch_ready[2], fetch_free[2];
+    // JPEG reconstruction (akz_jpeg_api.cpp): pinned staging the host decoder writes coefficients (or a host-decoded luma
+    // frame) into, one slot per decoding thread, each with the event of the upload that last read it; the device's
+    // coefficients and component planes of the frame being reconstructed, the luma frames of a file-based extraction;
+    // akz_ctx::jpeg_m orders the uploads of a batch's decoding threads on the stream
+    static constexpr int kJpegSlots = 16;
+    DevBuf jpeg_pin[kJpegSlots];
+    Event jpeg_up[kJpegSlots];
+    DevBuf jpeg_coef, jpeg_plane, jpeg_frames;
+};
+static_assert(std::is_nothrow_move_assignable<CtxOwned>::value && !std::is_copy_constructible<CtxOwned>::value, "released by assigning an empty one; never copied");
+struct akz_ctx : CtxOwned {
+    CtxSettings settings;  // a lane's: lane_settings(its parent's), kept so by push_settings
+    int device = 0;
+    std::atomic<uint32_t> last_total_kp{0};  // keypoints of the previous finished job (speculative fetch size of the device selection)
+    std::atomic<int> sel_last_mode{-1};      // akz_debug_select_info: how the last finished job was selected (0 grids, 1 lists, 2 device), the
+    std::atomic<int> sel_skip{0};            // jobs of shape sel_skip_shape that leave the device's selection out (the last one fell back)
+    std::atomic<uint64_t> sel_skip_shape{0};
+    std::atomic<uint32_t> sel_last_ticks[4];
+    std::atomic<uint32_t> sel_last_rounds{0}, sel_last_fallback{0};  // device's longest run of rounds, images that sent it back to the host
+    uint32_t match_epoch = 0;
+    bool kb_split_on = false;
+    double kb_split_ms[3] = {};
+    bool mp_split_on = false;
+    double mp_split_ms[6] = {};
+    int libm_last = 0;          // how the last finished job got its angles: 0 host libm, 1 / 2 the device's FMA / SSE2 forms
+    std::mutex slab_m;                  // guards slab_pool: results are freed by the caller while a lane's finisher thread allocates
     std::atomic<bool> slot_busy[kSlots] = {{false}, {false}, {false}};  // (begin on the caller's thread, finish possibly on the finisher's)
     std::atomic<uint32_t> cand_cap_hint{1u << 15};  // grows to 1.25x the largest candidate count seen
     std::atomic<int> live_results{0};   // akz_result objects (also inside jobs) that still point at this context
     bool dead = false;                  // akz_ctx_destroy was called; the struct lives until the last result is freed
     std::atomic<uint32_t> last_total_cands{0};  // candidates of the previous finished job (speculative fetch size)
     std::atomic<uint64_t> last_cand_shape{0};   // ... and its shape (akz_extract.hpp: shape_key)
-    hipStream_t aux = nullptr;          // finish-side copies and keypoint kernels (created under aux_m: the caller's thread and the finisher's may both be first)
-    std::mutex aux_m;
-    hipStream_t coarse = nullptr;       // the coarse octaves' chain (diffusion + detectors), next to the fine detectors
-    hipStream_t pre = nullptr;          // level-0 blur + contrast factor of a batch whose input is known to be complete:
-    hipEvent_t pre_done = nullptr;      // they run ahead, under the kernels of the batch before (extract_begin)
-    hipStream_t copy = nullptr;         // uploads of host frames (akz_extract_begin_host_*), under the kernels of the batch before
-    DevBuf stage[kSlots];               // staging buffers of those uploads, one per job slot
-    hipEvent_t staged[kSlots] = {nullptr, nullptr, nullptr};
+    std::mutex aux_m;                   // guards the creation of aux
     // Lanes: child contexts (own streams, scratch planes, candidate slots) that small jobs are dealt to in turn, so that
     // the launch chains of consecutive single frames -- 44 back-to-back launches of a few hundred workgroups each --
     // overlap on the chip instead of queueing on one stream (akz_ctx_set_lanes).
@@ -273,7 +428,6 @@ struct akz_ctx {
     bool eager_finish = true;           // akz_ctx_set_eager_finish (default on): the finish half of every job begun through
                                         // akz_extract_begin_* runs on the context's own thread (a lane's on the lane's)
     std::shared_ptr<Finisher> fin;      // (a lane's) finisher thread (shared with its jobs: one may outlive the context), started with its first eager job
-    hipEvent_t lane_in = nullptr;       // inputs of the job are ready on the caller's stream
     // Stream placement (place_streams): the runtime multiplexes a process's streams onto a few in-order hardware queues
     // (GPU_MAX_HW_QUEUES, 4 by default); two busy streams of a context on one queue serialise the whole pipeline, so the
     // first large batch measures which of the context's streams actually run side by side and replaces those that do not
@@ -283,24 +437,11 @@ struct akz_ctx {
     int place_collisions = 0;    // pairs that still share a queue (no free queue was found)
     int place_retries = 0;       // probe measurements that were repeated because the first answer was "shared" or ambiguous
     int lane_collisions = 0;     // lanes whose stream still shares a queue or a pipe with another lane's
-    hipEvent_t probe_ev[2] = {nullptr, nullptr};
     akz_profile prof{};
-    struct Span { int stage; hipEvent_t a, b; int row; };
-    std::vector<Span> spans;          // recorded, not yet resolved
     // akz_debug_kernel_rows: the spans of the two dominant stages by kernel variant and launch shape (what bench.py lists
     // behind roofline.kernel); a span's `row` indexes this table (-1: not broken down)
     std::vector<akz_kernel_row> rows;
-    std::vector<hipEvent_t> ev_pool;  // recycled events
     std::mutex ev_m;                  // guards spans and ev_pool (begin records on the caller's thread while a finish resolves)
-    // Every extract_begin records, behind its last fine-level diffusion launch, the event fed_ev[seq % kFedRing] of its
-    // sequence number: the keypoint kernels of job i are held back until job i + 1 has passed that point, and the early
-    // stages of job i + 1 until job i has (see extract_begin).  Four slots: at most kSlots jobs are in flight.
-    static constexpr int kFedRing = 4;
-    hipEvent_t fed_ev[kFedRing] = {nullptr, nullptr, nullptr, nullptr};
-    // ... and pre_ev[seq % kFedRing] behind the last diffusion launch of its FIRST octave: from there to the detectors the
-    // main stream carries the half-resolution octave's launches, which are bound by latency and leave most of the chip's
-    // bandwidth unused -- that is where the next job's blur and contrast passes go (sched[SCHED_EARLY_HOLD] = 2)
-    hipEvent_t pre_ev[kFedRing] = {nullptr, nullptr, nullptr, nullptr};
     std::atomic<uint64_t> begin_seq{0};  // sequence number of the job begun last
     std::shared_ptr<std::atomic<int>> in_hand = std::make_shared<std::atomic<int>>(0);  // akz_job::in_hand
     std::unique_ptr<WorkerPool> workers;  // host threads of the finish half (started on first use)
@@ -308,23 +449,7 @@ struct akz_ctx {
         if (!workers) workers.reset(new WorkerPool(std::min(settings.host_threads ? settings.host_threads : host_cpu_share(), 16u) - 1));
         return *workers;
     }
-    // akz_fetch_pyramid (akz_result.cpp), private to it like `lazy`: the streams its downloads run on, the pinned staging ring
-    // pageable destinations are filled through, and the recomputation of lean results -- temporaries that only the
-    // context's stream touches, and two sets of outputs (Lxx, Lyy, Lxy, Lstep) that the downloads read alternately
-    hipStream_t fetch[2] = {nullptr, nullptr};  // downloads alternate between two streams (two copy engines)
-    DevBuf fetch_stage;                      // pinned: kFetchStageBufs buffers of kFetchStageBytes
-    hipEvent_t fetch_chunk[4] = {nullptr, nullptr, nullptr, nullptr};  // a staging buffer's download is complete
-    DevBuf fetch_tmp[3], fetch_out[2][4];
-    hipEvent_t fetch_start = nullptr, fetch_join = nullptr, fetch_ready[2] = {nullptr, nullptr}, fetch_free[2] = {nullptr, nullptr};
-    // JPEG reconstruction (akz_jpeg_api.cpp): pinned staging the host decoder writes coefficients (or a host-decoded luma
-    // frame) into, one slot per decoding thread, each with the event of the upload that last read it; the device's
-    // coefficients and component planes of the frame being reconstructed, the luma frames of a file-based extraction;
-    // jpeg_m orders the uploads of a batch's decoding threads on the stream
-    static constexpr int kJpegSlots = 16;
-    DevBuf jpeg_pin[kJpegSlots];
-    hipEvent_t jpeg_up[kJpegSlots] = {};
-    DevBuf jpeg_coef, jpeg_plane, jpeg_frames;
-    std::mutex jpeg_m;
+    std::mutex jpeg_m;                  // orders the uploads of a batch's JPEG decoding threads on the stream
 };
 // What a lane runs with: its parent's settings, with the job gates no lower than lane_px (a job that is dealt to a lane runs there
 // as a one-stream chain)
@@ -380,18 +505,18 @@ AKZ_LOCAL inline void kernel_row_count(akz_ctx* c, int stage, uint32_t kind, uin
 struct StageTimer {
     akz_ctx* c;
     int stage;
-    hipEvent_t a = nullptr, b = nullptr;
-    static hipEvent_t get(akz_ctx* c) {
+    Event a, b;
+    static Event get(akz_ctx* c) {  // a timing event from the context's pool (an empty one if the runtime has none to give)
+        Event e;
         {
             std::lock_guard<std::mutex> lk(c->ev_m);
             if (!c->ev_pool.empty()) {
-                hipEvent_t e = c->ev_pool.back();
+                e = std::move(c->ev_pool.back());
                 c->ev_pool.pop_back();
                 return e;
             }
         }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
+        (void)e.ensure(hipEventDefault);
         return e;
     }
     bool on;
@@ -418,20 +543,20 @@ struct StageTimer {
         if (!on) return;
         (void)hipEventRecord(b, s);
         std::lock_guard<std::mutex> lk(c->ev_m);
-        c->spans.push_back({stage, a, b, row});
+        c->spans.push_back({stage, std::move(a), std::move(b), row});
     }
 };
-AKZ_LOCAL inline void ev_put(akz_ctx* c, hipEvent_t e) {
+AKZ_LOCAL inline void ev_put(akz_ctx* c, Event&& e) {
     if (!e) return;
     std::lock_guard<std::mutex> lk(c->ev_m);
-    c->ev_pool.push_back(e);
+    c->ev_pool.push_back(std::move(e));
 }
 AKZ_LOCAL inline void resolve_spans(akz_ctx* c) {
     std::lock_guard<std::mutex> lk(c->ev_m);
     std::vector<akz_ctx::Span> pending;
     for (auto& sp : c->spans) {
         if (hipEventQuery(sp.b) != hipSuccess) {  // still in flight (a later job): keep for the next call
-            pending.push_back(sp);
+            pending.push_back(std::move(sp));
             continue;
         }
         float ms = 0.0f;
@@ -439,8 +564,8 @@ AKZ_LOCAL inline void resolve_spans(akz_ctx* c) {
             if (sp.stage < kStageIngest) c->prof.ms[sp.stage] += (double)ms;
             if (sp.row >= 0 && (size_t)sp.row < c->rows.size()) c->rows[(size_t)sp.row].ms += (double)ms;
         }
-        c->ev_pool.push_back(sp.a);
-        c->ev_pool.push_back(sp.b);
+        c->ev_pool.push_back(std::move(sp.a));
+        c->ev_pool.push_back(std::move(sp.b));
     }
     c->spans.swap(pending);
 }
@@ -461,7 +586,7 @@ AKZ_LOCAL inline hipError_t sync_all_streams(akz_ctx* c, unsigned which = kSyncA
     };
     if (which & kSyncMain) wait(c->stream);
     if ((which & kSyncAux) && c->aux) wait(c->aux);
-    for (hipStream_t s : {c->coarse, c->pre, c->copy})
+    for (hipStream_t s : {c->coarse.h, c->pre.h, c->copy.h})
         if ((which & kSyncSide) && s) wait(s);
     return first;
 }
@@ -477,19 +602,10 @@ AKZ_LOCAL inline int ensure(akz_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return AKZ_OK;
     if (b.p) {
         AKZ_HIP_TRY(sync_all_streams(c));
-        AKZ_HIP_TRY(hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
+        AKZ_HIP_TRY(b.release());
     }
-    if (&b == &c->small) {  // fresh memory holds nothing known: hipMalloc may hand back the address just freed
-        c->small_zero_p = nullptr;
-        c->small_zero = 0;
-    }
-    if (&b == &c->bucket_scratch) c->bucket_zero = 0;
-    if (&b == &c->match_state) c->match_state_known = 0;
     const size_t want = bytes + bytes / 8 + 256;
-    AKZ_HIP_TRY(hipMalloc(&b.p, want));
-    b.bytes = want;
+    AKZ_HIP_TRY(b.acquire(want, false));  // (fresh memory holds nothing known: b.known is 0)
     AKZ_HIP_TRY(alloc_fill(c, b.p, want));
     return AKZ_OK;
 }
@@ -497,13 +613,9 @@ AKZ_LOCAL inline int ensure_pinned(akz_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes && b.p) return AKZ_OK;
     if (b.p) {  // (the caller's stream and the finish half's only, as ever: every user of pinned staging synchronises its stream before it returns)
         AKZ_HIP_TRY(sync_all_streams(c, kSyncMain | kSyncAux));
-        AKZ_HIP_TRY(hipHostFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
+        AKZ_HIP_TRY(b.release());
     }
-    const size_t want = bytes + bytes / 4 + 4096;
-    AKZ_HIP_TRY(hipHostMalloc(&b.p, want, hipHostMallocDefault));
-    b.bytes = want;
+    AKZ_HIP_TRY(b.acquire(bytes + bytes / 4 + 4096, true));
     return AKZ_OK;
 }
 // The auxiliary stream carries the finish-side copies and the per-keypoint kernels.  (A lowest-priority
@@ -511,8 +623,7 @@ AKZ_LOCAL inline int ensure_pinned(akz_ctx* c, DevBuf& b, size_t bytes) {
 AKZ_LOCAL inline int ensure_aux(akz_ctx* c) {
     // (the matcher's entry points bind without draining the finisher thread, whose finish half creates the stream too)
     std::lock_guard<std::mutex> lk(c->aux_m);
-    if (!c->aux) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-    return AKZ_OK;
+    return c->aux.ensure();
 }
 // wait until the context's finisher thread (if any) has nothing queued or running; a no-op on that thread itself
 AKZ_LOCAL inline void finisher_drain(akz_ctx* c) {

@@ -189,15 +189,11 @@ int akz_ctx_set_lanes(akz_ctx* c, uint32_t lanes) {
         c->lanes.pop_back();
     }
     while (c->lanes.size() < want) {
-        void* st = nullptr;
-        AKZ_TRY(akz_stream_create(c->device, &st));
+        Stream st;  // (the lane's own)
+        AKZ_TRY(st.ensure());
         akz_ctx* l = nullptr;
-        const int rc = akz_ctx_create(c->device, st, &l);
-        if (rc != AKZ_OK) {
-            (void)akz_stream_destroy(c->device, st);
-            return rc;
-        }
-        l->own_stream = true;
+        AKZ_TRY(akz_ctx_create(c->device, nullptr, &l));
+        l->stream = std::move(st);
         l->is_lane = true;
         l->cand_cap_hint = c->cand_cap_hint.load();
         c->lanes.push_back(l);
@@ -221,7 +217,7 @@ static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint
         AKZ_TRY(bind(c, false));
         on = c->lanes[c->next_lane++ % c->lanes.size()];
         // the lane starts when the caller's stream has reached this point (its inputs are complete)
-        if (!c->lane_in) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->lane_in, hipEventDisableTiming));
+        AKZ_TRY(c->lane_in.ensure());
         AKZ_HIP_TRY(hipEventRecord(c->lane_in, c->stream));
         AKZ_HIP_TRY(hipStreamWaitEvent(on->stream, c->lane_in, 0));
     }
@@ -244,14 +240,14 @@ static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint
         }
         const size_t bytes = (size_t)w * h * n * (is_u8 ? 1 : sizeof(float));
         AKZ_TRY(ensure(on, on->stage[slot], bytes));
-        if (!on->copy) AKZ_HIP_TRY(hipStreamCreateWithFlags(&on->copy, hipStreamNonBlocking));
-        if (!on->staged[slot]) AKZ_HIP_TRY(hipEventCreateWithFlags(&on->staged[slot], hipEventDisableTiming));
+        AKZ_TRY(on->copy.ensure());
+        AKZ_TRY(on->staged[slot].ensure());
         AKZ_HIP_TRY(hipMemcpyAsync(on->stage[slot].p, imgs, bytes, hipMemcpyHostToDevice, on->copy));
         AKZ_HIP_TRY(hipEventRecord(on->staged[slot], on->copy));
         AKZ_HIP_TRY(hipStreamWaitEvent(on->stream, on->staged[slot], 0));
         d_imgs = on->stage[slot].p;
     }
-    hipEvent_t ready = on_host ? on->staged[slot] : nullptr;  // frames this library uploaded: complete behind that event
+    hipEvent_t ready = on_host ? on->staged[slot].h : nullptr;  // frames this library uploaded: complete behind that event
     const int rc = is_u8 ? extract_begin<uint8_t>(on, (const uint8_t*)d_imgs, w, h, n, cfg, flags, out, slot, ready)
                          : extract_begin<float>(on, (const float*)d_imgs, w, h, n, cfg, flags, out, slot, ready);
     // a job dealt to a lane is always finished by the lane's own thread (lanes whose jobs wait for the caller's finish call
@@ -380,9 +376,9 @@ int akz_ctx_graph_probe(akz_ctx* c, const uint8_t* d_imgs, uint32_t w, uint32_t 
         result_delete(r);
     }
     AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    AKZ_HIP_TRY(hipEventCreate(&e0));
-    AKZ_HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    AKZ_TRY(e0.ensure(hipEventDefault));
+    AKZ_TRY(e1.ensure(hipEventDefault));
     // 2. plain chain, from an idle stream each time
     double plain = 0.0;
     for (uint32_t i = 0; i < reps; ++i) {
@@ -427,8 +423,6 @@ int akz_ctx_graph_probe(akz_ctx* c, const uint8_t* d_imgs, uint32_t w, uint32_t 
     (void)hipGraphExecDestroy(exec);
     (void)hipGraphDestroy(graph);
     job_destroy(cap);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *ms_graph = gms / reps;
     *ms_plain = plain / reps;
     return AKZ_OK;

@@ -34,7 +34,7 @@ struct akz_job {
     std::unique_ptr<akz_result, ResultDeleter> r;
     int slot = -1;            // candidate / counter buffers used by this job
     uint32_t cap = 0;         // candidate capacity per image
-    hipEvent_t nms_done = nullptr;
+    Event nms_done;
     uint64_t seq = 0;         // position in the context's order of begins (fed_ev ring)
     double t_begin_ms = 0.0;
     // eager finish: the lane's thread runs the finish half and leaves its outcome here (guarded by fin->m)

@@ -197,8 +197,8 @@ int level0(BeginState& b, const T* d_imgs, hipEvent_t input_ready) {
     const bool early = b.rt.pre_on != 0;
     JobForm f = b.form;  // (on the early stream where the job runs ahead)
     if (early) {
-        hipStream_t& ps = b.rt.pre_on == 2 ? c->copy : c->pre;
-        if (!ps) AKZ_HIP_TRY(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
+        Stream& ps = b.rt.pre_on == 2 ? c->copy : c->pre;
+        AKZ_TRY(ps.ensure());
         if (input_ready) AKZ_HIP_TRY(hipStreamWaitEvent(ps, input_ready, 0));
         if (c->pre_done) AKZ_HIP_TRY(hipStreamWaitEvent(ps, c->pre_done, 0));
         // however early the caller begins this batch, its first two stages start when the batch before goes from its
@@ -226,7 +226,7 @@ int level0(BeginState& b, const T* d_imgs, hipEvent_t input_ready) {
     }
     // every job marks the end of its level-0 stages (the last use of the context's contrast scratch): a later job that
     // runs ahead waits for exactly that, whichever stream it was recorded on
-    if (!c->pre_done) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->pre_done, hipEventDisableTiming));
+    AKZ_TRY(c->pre_done.ensure());
     AKZ_HIP_TRY(hipEventRecord(c->pre_done, f.stream));
     if (early) AKZ_HIP_TRY(hipStreamWaitEvent(b.form.stream, c->pre_done, 0));
     return AKZ_OK;
@@ -435,11 +435,11 @@ int detectors(BeginState& b, size_t lo, size_t hi, const JobForm& f) {
 int fork_and_join(BeginState& b, hipStream_t* done_on) {
     akz_ctx* c = b.c;
     const hipStream_t s = b.form.stream;
-    if (!c->coarse) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->coarse, hipStreamNonBlocking));
-    hipEvent_t fine_done = StageTimer::get(c);
+    AKZ_TRY(c->coarse.ensure());
+    Event fine_done = StageTimer::get(c);
     AKZ_HIP_TRY(hipEventRecord(fine_done, s));
     AKZ_HIP_TRY(hipStreamWaitEvent(c->coarse, fine_done, 0));
-    ev_put(c, fine_done);
+    ev_put(c, std::move(fine_done));
     // (holding the chain back until the full-resolution detectors, or all fine detectors, have finished: -2 ... -5 %)
     // The fine detectors are ENQUEUED first: the coarse chain is dozens of small launches, and a caller that is not
     // ahead of the chip -- one synchronous call on a 4K pair -- kept the main stream idle for the 0.19 ms it took to
@@ -448,7 +448,7 @@ int fork_and_join(BeginState& b, hipStream_t* done_on) {
     b.chain.stream = c->coarse;
     AKZ_TRY(run_levels(b, b.rt.fork_level, b.L()));
     AKZ_TRY(detectors(b, b.rt.fork_level, b.L(), b.chain));
-    hipEvent_t ev = StageTimer::get(c);
+    Event ev = StageTimer::get(c);
     if (b.rt.own_kernels) {
         AKZ_HIP_TRY(hipEventRecord(ev, s));
         AKZ_HIP_TRY(hipStreamWaitEvent(c->coarse, ev, 0));
@@ -457,7 +457,7 @@ int fork_and_join(BeginState& b, hipStream_t* done_on) {
         AKZ_HIP_TRY(hipEventRecord(ev, c->coarse));
         AKZ_HIP_TRY(hipStreamWaitEvent(s, ev, 0));
     }
-    ev_put(c, ev);
+    ev_put(c, std::move(ev));
     return AKZ_OK;
 }
 
@@ -511,10 +511,8 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     }
     AKZ_TRY(ensure(c, c->cand_slot[o.slot], (size_t)cap * sizeof(Candidate)));
     AKZ_TRY(ensure(c, c->count_slot[o.slot], 256));
-    if (!c->fed_ev[0])
-        for (hipEvent_t& e : c->fed_ev) AKZ_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!c->pre_ev[0])
-        for (hipEvent_t& e : c->pre_ev) AKZ_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Event& e : c->fed_ev) AKZ_TRY(e.ensure());
+    for (Event& e : c->pre_ev) AKZ_TRY(e.ensure());
     const uint64_t seq = c->begin_seq.load() + 1;  // published when this job's event has been recorded
     // Jobs below gates::kTiledPrepPx take the TILED preparation family whatever their launches' sizes -- k_blur, k_contrast_max /
     // _hist, k_prep riding on the previous level's last k_fed_own launch, no resident tail: since that epilogue exists the

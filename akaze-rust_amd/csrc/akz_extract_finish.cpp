@@ -50,15 +50,15 @@ int device_libm_mode(akz_ctx* c) {
             std::memcpy(&b[i], &v, 4);
         }
     }
-    float *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
+    DevBuf d_a, d_b, d_o;
     std::vector<float> got(3 * kN);
-    const bool ok_dev = hipMalloc((void**)&d_a, kN * 4) == hipSuccess && hipMalloc((void**)&d_b, kN * 4) == hipSuccess &&
-                        hipMalloc((void**)&d_o, 3 * kN * 4) == hipSuccess &&
-                        hipMemcpy(d_a, a.data(), kN * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                        hipMemcpy(d_b, b.data(), kN * 4, hipMemcpyHostToDevice) == hipSuccess;
+    const bool ok_dev = d_a.acquire(kN * 4, false) == hipSuccess && d_b.acquire(kN * 4, false) == hipSuccess &&
+                        d_o.acquire(3 * kN * 4, false) == hipSuccess &&
+                        hipMemcpy(d_a.p, a.data(), kN * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_b.p, b.data(), kN * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (ok_dev) {
-        launch::libm_eval(nullptr, d_a, d_b, d_o, kN, fma, nullptr);
-        const bool ran = hipGetLastError() == hipSuccess && hipMemcpy(got.data(), d_o, 3 * kN * 4, hipMemcpyDeviceToHost) == hipSuccess;
+        launch::libm_eval(nullptr, (const float*)d_a.p, (const float*)d_b.p, (float*)d_o.p, kN, fma, nullptr);
+        const bool ran = hipGetLastError() == hipSuccess && hipMemcpy(got.data(), d_o.p, 3 * kN * 4, hipMemcpyDeviceToHost) == hipSuccess;
         std::atomic<uint64_t> bad{ran ? 0u : 1u};
         if (ran) {
             const size_t pieces = 64;
@@ -76,9 +76,6 @@ int device_libm_mode(akz_ctx* c) {
         if (bad.load() == 0) mode = fma ? 1 : 2;
     }
     (void)hipGetLastError();
-    if (d_a) (void)hipFree(d_a);
-    if (d_b) (void)hipFree(d_b);
-    if (d_o) (void)hipFree(d_o);
 #endif
     return mode;
 }
@@ -293,10 +290,10 @@ int enqueue_device_side(FinishState& f) {
     f.sorted = rows_sort;
     bool buckets_sort = false;
     if (!f.sorted) {  // several images or a longer list: the same sort in four launches, if the job has few enough rows
-        // (whether its counters are zero is the claim c->bucket_zero: ensure() drops it with the buffer, the sort keeps it)
+        // (whether its counters are zero is the claim c->bucket_scratch.known: a fresh block starts without it, the sort keeps it)
         AKZ_TRY(ensure(c, c->bucket_scratch, launch::sort_candidates_buckets_scratch(cap)));
         buckets_sort = launch::sort_candidates_buckets(s, f.d_unsorted(), cap, f.d_count, lw.data(), lh.data(), L, n, c->bucket_scratch.p,
-                                                       &c->bucket_zero, d_sorted, d_zero, want_lists ? c->rel_scratch.p : nullptr);
+                                                       &c->bucket_scratch.known, d_sorted, d_zero, want_lists ? c->rel_scratch.p : nullptr);
         f.sorted = buckets_sort;
     }
     if (!f.sorted) {
@@ -695,8 +692,7 @@ void publish(FinishState& f) {
         c->prof.calls += 1;
         c->prof.pixels += (uint64_t)r->w * r->h * f.n;
     }
-    ev_put(c, f.job->nms_done);
-    f.job->nms_done = nullptr;
+    ev_put(c, std::move(f.job->nms_done));
 }
 }  // namespace
 

@@ -76,7 +76,7 @@ int stage_file(akz_ctx* c, int slot, const char* path, int64_t cap_px, Staged& s
 // kernels (a JPEG), or the frame's upload.  Records the slot's event behind the upload.
 int reconstruct(akz_ctx* c, int slot, const Staged& st, uint8_t* d_dst) {
     hipStream_t s = c->stream;
-    if (!c->jpeg_up[slot]) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->jpeg_up[slot], hipEventDisableTiming));
+    AKZ_TRY(c->jpeg_up[slot].ensure());
     if (!st.jpeg) {
         AKZ_HIP_TRY(hipMemcpyAsync(d_dst, c->jpeg_pin[slot].p, (size_t)st.w * st.h, hipMemcpyHostToDevice, s));
         AKZ_HIP_TRY(hipEventRecord(c->jpeg_up[slot], s));

@@ -35,15 +35,15 @@ int knn_enqueue(akz_ctx* c, const uint8_t* d_d0, uint32_t n0, const uint8_t* d_d
     const uint32_t q_rows = launch::match_mfma_rows(n0, true), t_rows = launch::match_mfma_rows(n1, false);
     AKZ_TRY(ensure(c, c->kn_part, launch::knn_part_bytes(n0, chunks, k)));
     if (n1) {  // (the matcher's own images: like every user of them, on c->stream only)
-        AKZ_TRY(ensure(c, c->mm_q8, (size_t)q_rows * 512));
-        AKZ_TRY(ensure(c, c->mm_t8, (size_t)t_rows * 512));
-        AKZ_TRY(ensure(c, c->mm_pop, ((size_t)2 * q_rows + t_rows) * sizeof(uint32_t)));
-        uint32_t* qpop = (uint32_t*)c->mm_pop.p;
+        AKZ_TRY(ensure(c, c->ms[0].q8, (size_t)q_rows * 512));
+        AKZ_TRY(ensure(c, c->ms[0].t8, (size_t)t_rows * 512));
+        AKZ_TRY(ensure(c, c->ms[0].pop, ((size_t)2 * q_rows + t_rows) * sizeof(uint32_t)));
+        uint32_t* qpop = (uint32_t*)c->ms[0].pop.p;
         uint32_t* tpop = qpop + 2 * (size_t)q_rows;
-        launch::unpack_pair(c->stream, d_d0, n0, q_rows, (uint8_t*)c->mm_q8.p, qpop, nullptr, thr, d_d1, n1, t_rows, (uint8_t*)c->mm_t8.p, tpop,
+        launch::unpack_pair(c->stream, d_d0, n0, q_rows, (uint8_t*)c->ms[0].q8.p, qpop, nullptr, thr, d_d1, n1, t_rows, (uint8_t*)c->ms[0].t8.p, tpop,
                             true);
     }
-    if (!launch::knn(c->stream, (const uint8_t*)c->mm_q8.p, n0, (const uint8_t*)c->mm_t8.p, n1, thr, chunks, k, (uint32_t*)c->kn_part.p, d_out,
+    if (!launch::knn(c->stream, (const uint8_t*)c->ms[0].q8.p, n0, (const uint8_t*)c->ms[0].t8.p, n1, thr, chunks, k, (uint32_t*)c->kn_part.p, d_out,
                      d_counts)) {
         set_error("descriptor_match_knn: the kernel was built for another tile of the matcher");
         return AKZ_ERR_UNSUPPORTED;

@@ -17,20 +17,20 @@ int match_finish(akz_ctx* c, MatchRec* rec, uint32_t n0, uint32_t chunks, uint32
     //     workgroups of 256 threads -- four per compute unit -- i.e. query sets of up to 262 144 rows; larger sets take the
     //     merge + single-workgroup compaction below;
     //   * match_state (told apart by epoch) belongs to ONE stream: this function, like every user of the context's matcher
-    //     scratch (match_rec, mm_q8, mm_t8, mm_pop), enqueues on c->stream only -- launches of two epochs never overlap.
+    //     scratch (side 0: ms[0].rec, q8, t8, pop), enqueues on c->stream only -- launches of two epochs never overlap.
     if (n0 >= gates::kMergeCompactMinRows && n0 <= gates::kMergeCompactMaxRows) {
-        // (the claim c->match_state_known: how much of the state holds no epoch beyond match_epoch -- dropped by ensure() with the
-        // buffer, and when the epoch wraps: words of 2^32 calls ago would read as published)
+        // (the claim c->match_state.known: how much of the state holds no epoch beyond match_epoch -- a fresh block starts without
+        // one, and it is dropped when the epoch wraps: words of 2^32 calls ago would read as published)
         const size_t need = launch::match_merge_compact_state_bytes(n0);
         if (++c->match_epoch == 0) {
             c->match_epoch = 1;
-            c->match_state_known = 0;
+            c->match_state.known = 0;
         }
-        if (c->match_state_known < need) {
+        if (c->match_state.known < need) {
             if (c->match_state.bytes < need) AKZ_TRY(ensure(c, c->match_state, need * 2));
-            c->match_state_known = 0;
+            c->match_state.known = 0;
             AKZ_HIP_TRY(hipMemsetAsync(c->match_state.p, 0, c->match_state.bytes, c->stream));
-            c->match_state_known = c->match_state.bytes;
+            c->match_state.known = c->match_state.bytes;
         }
         launch::match_merge_compact(c->stream, rec, n0, chunks, thr, lowes_ratio * lowes_ratio, d_out,
                                     (unsigned long long*)d_n_out, c->match_state.p, c->match_epoch);
@@ -65,20 +65,20 @@ static int match_device_impl(akz_ctx* c, const uint8_t* d_d0, uint64_t n0, const
     const bool mfma = n0 && n1 && c->settings.match_mode != 0 && rows_le_61;
     const uint32_t chunks = mfma ? launch::match_mfma_chunks((uint32_t)n0, (uint32_t)n1, c->settings.dbg_pair_chunks)
                                  : launch::match_num_chunks((uint32_t)n0, (uint32_t)n1);
-    AKZ_TRY(ensure(c, c->match_rec, std::max<uint64_t>(1, n0) * (chunks + 1) * sizeof(MatchRec)));
-    MatchRec* rec = (MatchRec*)c->match_rec.p;  // [chunk][query], then the merged records
+    AKZ_TRY(ensure(c, c->ms[0].rec, std::max<uint64_t>(1, n0) * (chunks + 1) * sizeof(MatchRec)));
+    MatchRec* rec = (MatchRec*)c->ms[0].rec.p;  // [chunk][query], then the merged records
     if (mfma) {
         const uint32_t q_rows = launch::match_mfma_rows((uint32_t)n0, true), t_rows = launch::match_mfma_rows((uint32_t)n1, false);
-        AKZ_TRY(ensure(c, c->mm_q8, (size_t)q_rows * 512));
-        AKZ_TRY(ensure(c, c->mm_t8, (size_t)t_rows * 512));
-        AKZ_TRY(ensure(c, c->mm_pop, ((size_t)2 * q_rows + t_rows) * sizeof(uint32_t)));
-        uint32_t* qpop = (uint32_t*)c->mm_pop.p;
+        AKZ_TRY(ensure(c, c->ms[0].q8, (size_t)q_rows * 512));
+        AKZ_TRY(ensure(c, c->ms[0].t8, (size_t)t_rows * 512));
+        AKZ_TRY(ensure(c, c->ms[0].pop, ((size_t)2 * q_rows + t_rows) * sizeof(uint32_t)));
+        uint32_t* qpop = (uint32_t*)c->ms[0].pop.p;
         uint32_t* bound = qpop + q_rows;
         uint32_t* tpop = bound + q_rows;
         const bool fp4 = c->settings.match_mode >= 2;
-        launch::unpack_pair(c->stream, d_d0, (uint32_t)n0, q_rows, (uint8_t*)c->mm_q8.p, qpop, bound, thr, d_d1, (uint32_t)n1, t_rows,
-                            (uint8_t*)c->mm_t8.p, tpop, fp4);
-        launch::match_mfma(c->stream, (const uint8_t*)c->mm_q8.p, qpop, (uint32_t)n0, (const uint8_t*)c->mm_t8.p,
+        launch::unpack_pair(c->stream, d_d0, (uint32_t)n0, q_rows, (uint8_t*)c->ms[0].q8.p, qpop, bound, thr, d_d1, (uint32_t)n1, t_rows,
+                            (uint8_t*)c->ms[0].t8.p, tpop, fp4);
+        launch::match_mfma(c->stream, (const uint8_t*)c->ms[0].q8.p, qpop, (uint32_t)n0, (const uint8_t*)c->ms[0].t8.p,
                            (uint32_t)n1, thr, bound, chunks, rec, fp4);
     } else {
         launch::match(c->stream, d_d0, (uint32_t)n0, d_d1, (uint32_t)n1, thr, rows_le_61, chunks, rec);
@@ -147,12 +147,7 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
     const bool alt = side == 1 && c->settings.match_mode >= 2;
     if (alt) AKZ_TRY(ensure_aux(c));
     hipStream_t st = alt ? c->aux : c->stream;
-    DevBuf &b_q8 = alt ? c->ms1.q8 : c->mm_q8, &b_t8 = alt ? c->ms1.t8 : c->mm_t8, &b_pop = alt ? c->ms1.pop : c->mm_pop;
-    DevBuf &b_tab = alt ? c->ms1.tab : c->mm_tab, &b_cols = alt ? c->ms1.cols : c->mm_cols, &b_rec = alt ? c->ms1.rec : c->match_rec;
-    void*& ring = alt ? c->ms1.ring : c->tab_ring;
-    size_t& ring_bytes = alt ? c->ms1.ring_bytes : c->tab_ring_bytes;
-    uint64_t& ring_next = alt ? c->ms1.ring_next : c->tab_ring_next;
-    hipEvent_t* ring_ev = alt ? c->ms1.ring_ev : c->tab_ring_ev;
+    CtxOwned::MatchSide& m = c->ms[alt];
     const bool mutual = cols && c->settings.match_mode >= 2;
     const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
     const uint32_t tr = launch::match_mfma_tile_rows();
@@ -188,69 +183,66 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
     }
     // (both directions: the train image is also read as a QUERY image by the seed launch -- whole query blocks of rows)
     const uint32_t t_rows_q = mutual ? launch::match_mfma_rows(t_rows, true) : t_rows;
-    AKZ_TRY(ensure(c, b_q8, (size_t)q_rows * 512));
-    AKZ_TRY(ensure(c, b_t8, (size_t)t_rows_q * 512));
-    AKZ_TRY(ensure(c, b_pop, ((size_t)q_rows * (1 + n_sets) + t_rows) * sizeof(uint32_t)));
+    AKZ_TRY(ensure(c, m.q8, (size_t)q_rows * 512));
+    AKZ_TRY(ensure(c, m.t8, (size_t)t_rows_q * 512));
+    AKZ_TRY(ensure(c, m.pop, ((size_t)q_rows * (1 + n_sets) + t_rows) * sizeof(uint32_t)));
     const size_t tab_tiles = std::max<size_t>(1, tiles.size()) * sizeof(uint32_t);
     const size_t tab_chunks = chunks.size() * sizeof(launch::MatchChunkHost), tab_cols = colsets.size() * sizeof(launch::MatchColSetHost);
-    AKZ_TRY(ensure(c, b_tab, tab_tiles + tab_chunks + tab_cols));
+    AKZ_TRY(ensure(c, m.tab, tab_tiles + tab_chunks + tab_cols));
     unsigned long long* cbest = nullptr;
     uint32_t *csecond = nullptr, *seed_bound = nullptr;
     MatchRec* seed_rec = nullptr;
     if (mutual) {  // per row of the padded train image: 8 + 4 (state) + 4 + 16 (seed launch) bytes
-        AKZ_TRY(ensure(c, b_cols, (size_t)t_rows_q * 32));
-        cbest = (unsigned long long*)b_cols.p;
-        seed_rec = (MatchRec*)((char*)b_cols.p + (size_t)t_rows_q * 8);
-        csecond = (uint32_t*)((char*)b_cols.p + (size_t)t_rows_q * 24);
+        AKZ_TRY(ensure(c, m.cols, (size_t)t_rows_q * 32));
+        cbest = (unsigned long long*)m.cols.p;
+        seed_rec = (MatchRec*)((char*)m.cols.p + (size_t)t_rows_q * 8);
+        csecond = (uint32_t*)((char*)m.cols.p + (size_t)t_rows_q * 24);
         seed_bound = csecond + t_rows_q;
     }
-    AKZ_TRY(ensure(c, b_rec, std::max<uint64_t>(1, n0) * chunks.size() * sizeof(MatchRec)));
-    uint32_t* qpop = (uint32_t*)b_pop.p;
+    AKZ_TRY(ensure(c, m.rec, std::max<uint64_t>(1, n0) * chunks.size() * sizeof(MatchRec)));
+    uint32_t* qpop = (uint32_t*)m.pop.p;
     uint32_t* bound = qpop + q_rows;
     uint32_t* tpop = bound + (size_t)n_sets * q_rows;
-    uint32_t* d_tiles = (uint32_t*)b_tab.p;
-    void* d_chunks = (char*)b_tab.p + tab_tiles;
+    uint32_t* d_tiles = (uint32_t*)m.tab.p;
+    void* d_chunks = (char*)m.tab.p + tab_tiles;
     // The tables travel through a ring of pinned staging slots, so that the call returns without waiting for its copies
     // (a synchronisation here made every call of an all-pairs loop wait for the previous call's kernel).
     {
-        constexpr int kRing = 4;
+        constexpr int kRing = CtxOwned::MatchSide::kRing;
         const size_t need = tab_tiles + tab_chunks + tab_cols;
-        if (ring_bytes < need) {
+        if (m.ring.bytes / kRing < need) {
             AKZ_HIP_TRY(hipStreamSynchronize(st));
-            if (ring) AKZ_HIP_TRY(hipHostFree(ring));
-            ring = nullptr;
-            ring_bytes = 0;
-            AKZ_HIP_TRY(hipHostMalloc(&ring, (need + need / 2 + 4096) * kRing, hipHostMallocDefault));
-            ring_bytes = need + need / 2 + 4096;
+            AKZ_HIP_TRY(m.ring.release());
+            AKZ_HIP_TRY(m.ring.acquire((need + need / 2 + 4096) * kRing, true));
         }
-        const int slot = (int)(ring_next++ % kRing);
-        if (!ring_ev[slot]) AKZ_HIP_TRY(hipEventCreateWithFlags(&ring_ev[slot], hipEventDisableTiming));
-        else AKZ_HIP_TRY(hipEventSynchronize(ring_ev[slot]));  // the copy that used this slot four calls ago
-        char* stage = (char*)ring + (size_t)slot * ring_bytes;
+        const int slot = (int)(m.ring_next++ % kRing);
+        if (m.ring_ev[slot]) AKZ_HIP_TRY(hipEventSynchronize(m.ring_ev[slot]));  // the copy that used this slot four calls ago
+        else AKZ_TRY(m.ring_ev[slot].ensure());
+        char* stage = (char*)m.ring.p + (size_t)slot * (m.ring.bytes / kRing);
         if (!tiles.empty()) std::memcpy(stage, tiles.data(), tiles.size() * sizeof(uint32_t));
         std::memcpy(stage + tab_tiles, chunks.data(), tab_chunks);
         if (tab_cols) std::memcpy(stage + tab_tiles + tab_chunks, colsets.data(), tab_cols);
         AKZ_HIP_TRY(hipMemcpyAsync(d_tiles, stage, need, hipMemcpyHostToDevice, st));
-        AKZ_HIP_TRY(hipEventRecord(ring_ev[slot], st));
+        AKZ_HIP_TRY(hipEventRecord(m.ring_ev[slot], st));
     }
     const bool fp4 = c->settings.match_mode >= 2;
-    launch::unpack_bits(st, d_q, (uint32_t)n0, q_rows, true, (uint8_t*)b_q8.p, qpop, bound, thr, (uint32_t)n_sets,
+    launch::unpack_bits(st, d_q, (uint32_t)n0, q_rows, true, (uint8_t*)m.q8.p, qpop, bound, thr, (uint32_t)n_sets,
                         nullptr, fp4);
     if (n_tiles)
-        launch::unpack_bits(st, d_train, 0, n_tiles * tr, false, (uint8_t*)b_t8.p, tpop, nullptr, 0, 0, d_tiles, fp4);
+        launch::unpack_bits(st, d_train, 0, n_tiles * tr, false, (uint8_t*)m.t8.p, tpop, nullptr, 0, 0, d_tiles, fp4);
     if (mutual) {
         // the opposite direction rides along: seed the train rows' state from the first rows of the query set, then one pass
-        launch::match_cols_seed(st, (const uint8_t*)b_q8.p, (uint32_t)n0, (const uint8_t*)b_t8.p, n_tiles * tr, thr,
+        launch::match_cols_seed(st, (const uint8_t*)m.q8.p, (uint32_t)n0, (const uint8_t*)m.t8.p, n_tiles * tr, thr,
                                 seed_bound, seed_rec, cbest, csecond);
-        launch::match_fp4_multi_mutual(st, (const uint8_t*)b_q8.p, (uint32_t)n0, (const uint8_t*)b_t8.p, d_chunks,
-                                       (uint32_t)chunks.size(), thr, bound, (MatchRec*)b_rec.p, cbest, csecond);
+        launch::match_fp4_multi_mutual(st, (const uint8_t*)m.q8.p, (uint32_t)n0, (const uint8_t*)m.t8.p, d_chunks,
+                                       (uint32_t)chunks.size(), thr, bound, (MatchRec*)m.rec.p, cbest, csecond);
         launch::match_compact_cols(st, cbest, csecond, (const char*)d_chunks + tab_chunks, (uint32_t)n_sets, thr,
                                    lowes_ratio * lowes_ratio, d_out_cols, (unsigned long long*)d_n_cols);
     } else {
-        launch::match_mfma_multi(st, (const uint8_t*)b_q8.p, qpop, (uint32_t)n0, (const uint8_t*)b_t8.p, d_chunks,
-                                 (uint32_t)chunks.size(), thr, bound, (MatchRec*)b_rec.p, fp4);
+        launch::match_mfma_multi(st, (const uint8_t*)m.q8.p, qpop, (uint32_t)n0, (const uint8_t*)m.t8.p, d_chunks,
+                                 (uint32_t)chunks.size(), thr, bound, (MatchRec*)m.rec.p, fp4);
     }
-    launch::match_compact_sets(st, (const MatchRec*)b_rec.p, (uint32_t)n0, (uint32_t)n_sets, cps, thr,
+    launch::match_compact_sets(st, (const MatchRec*)m.rec.p, (uint32_t)n0, (uint32_t)n_sets, cps, thr,
                                lowes_ratio * lowes_ratio, d_out, (unsigned long long*)d_n_out);
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
@@ -584,8 +576,7 @@ int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint6
     AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, guided, f));
     f.timed = c->mp_split_on;
     if (f.timed)
-        for (hipEvent_t& e : c->mp_split_ev)
-            if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
+        for (Event& e : c->mp_split_ev) AKZ_TRY(e.ensure(hipEventDefault));
     hipStream_t st = c->stream;
     const size_t b_raw = up256((size_t)f.cap1 * sizeof(akz_match)), b_tab = up256((size_t)n_pairs * sizeof(launch::PairJobHost));
     AKZ_TRY(ensure(c, c->mp_raw, b_raw + f.b_cnt + (size_t)f.cap1 * 16));
@@ -789,7 +780,7 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     AKZ_TRY(pairs_keep(c, f, n_keep, keep));
     for (int i = 0; i < 2; ++i) {
         AKZ_TRY(ensure_pinned(c, c->mp_pin_smp[i], b_smp));
-        if (!c->mp_smp_ev[i]) AKZ_HIP_TRY(hipEventCreateWithFlags(&c->mp_smp_ev[i], hipEventDisableTiming));
+        AKZ_TRY(c->mp_smp_ev[i].ensure());
     }
     float* d_mdl = (float*)c->mp_trials.p;
     int32_t* d_inl = (int32_t*)((char*)c->mp_trials.p + b_mdl);

@@ -94,8 +94,8 @@ int head_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_lt0, float* 
     unsigned long long* d_smax = (unsigned long long*)c->small.p;
     uint32_t* d_hist = (uint32_t*)((char*)c->small.p + (size_t)n * 8);
     uint32_t* d_done = d_hist + (size_t)n * nbins;
-    const size_t known_zero = c->small_zero_p == c->small.p ? c->small_zero : 0;
-    c->small_zero = 0;  // (until both launches are enqueued: an error in between leaves the scratch in an unknown state)
+    const size_t known_zero = c->small.known;
+    c->small.known = 0;  // (until both launches are enqueued: an error in between leaves the scratch in an unknown state)
     if (known_zero < small_bytes)  // (first use, a larger job, or another family used it last)
         AKZ_HIP_TRY(hipMemsetAsync(c->small.p, 0, small_bytes, f.stream));
     float* blurred = d_blurred;  // (level 1's Lsmooth where level 1 continues the octave: the same blur of Lt0, lib.rs:92-95)
@@ -115,8 +115,7 @@ int head_impl(akz_ctx* c, const JobForm& f, const T* d_in, float* d_lt0, float* 
         launch::contrast_hist_final(f.stream, d_gx, d_gy, w, h, n, d_smax, (uint32_t)nbins, d_hist, d_done, percentile, d_k_out);
     }
     AKZ_HIP_TRY(hipGetLastError());
-    c->small_zero_p = c->small.p;
-    c->small_zero = std::max(known_zero, small_bytes);  // (the histogram pass leaves what it used zero again)
+    c->small.known = std::max(known_zero, small_bytes);  // (the histogram pass leaves what it used zero again)
     *fused = true;
     return AKZ_OK;
 }
@@ -142,7 +141,7 @@ int contrast_impl(akz_ctx* c, const JobForm& f, const float* d_in, uint32_t w, u
     uint32_t* d_hist = (uint32_t*)((char*)c->small.p + (size_t)n * 8);
     double* d_thr = (double*)((char*)c->small.p + small_bytes);
     AKZ_HIP_TRY(hipMemsetAsync(c->small.p, 0, small_bytes, f.stream));
-    c->small_zero = 0;  // (these passes do not clean up after themselves)
+    c->small.known = 0;  // (these passes do not clean up after themselves)
     const size_t ks = gaussian_kernel_size((float)gscale);
     const bool stream = f.prep_mode != 0 && gscale > 0.0 && launch::contrast_stream_supported(w, h, (uint32_t)ks, (uint32_t)nbins) &&
                         (f.prep_mode == 1 || (uint64_t)w * h * n >= c->settings.stream_min_px);

@@ -82,14 +82,11 @@ static int streams_interfere(akz_ctx* c, hipStream_t a, hipStream_t b, float alo
 struct StreamPlacer {
     akz_ctx* c;
     float alone_ms = 0.0f;
-    std::vector<hipStream_t> accepted, rejected;
+    std::vector<hipStream_t> accepted;
+    std::vector<Stream> rejected;
     explicit StreamPlacer(akz_ctx* ctx) : c(ctx) {}
-    ~StreamPlacer() {
-        for (hipStream_t r : rejected) (void)hipStreamDestroy(r);
-    }
     int calibrate(hipStream_t on) {
-        for (hipEvent_t& e : c->probe_ev)
-            if (!e) AKZ_HIP_TRY(hipEventCreate(&e));
+        for (Event& e : c->probe_ev) AKZ_TRY(e.ensure(hipEventDefault));
         launch::delay(on, 1);  // (the first launch of a kernel loads its code object: not part of a measurement)
         AKZ_HIP_TRY(hipStreamSynchronize(on));
         alone_ms = 1e30f;
@@ -112,30 +109,24 @@ struct StreamPlacer {
         }
         return AKZ_OK;
     }
-    // *slot ends up a stream that interferes with none of `accepted` (and joins them), or keeps its value (free = false)
-    int settle(hipStream_t* slot, bool* free) {
+    // slot ends up a stream that interferes with none of `accepted` (and joins them), or keeps its value (free = false)
+    int settle(Stream& slot, bool* free) {
         bool hit = false;
-        AKZ_TRY(collides(*slot, &hit));
+        AKZ_TRY(collides(slot, &hit));
         for (int attempt = 0; hit && attempt < 8; ++attempt) {
-            hipStream_t fresh = nullptr;
-            AKZ_HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
+            rejected.emplace_back();
+            Stream& fresh = rejected.back();
+            AKZ_TRY(fresh.ensure());
             bool fresh_hit = false;
-            const int st = collides(fresh, &fresh_hit);
-            if (st != AKZ_OK) {
-                rejected.push_back(fresh);
-                return st;
-            }
-            if (!fresh_hit) {
-                rejected.push_back(*slot);
-                *slot = fresh;
+            AKZ_TRY(collides(fresh, &fresh_hit));
+            if (!fresh_hit) {  // (the one that goes takes fresh's place among the rejects)
+                std::swap(slot, fresh);
                 hit = false;
                 ++c->place_replaced;
-            } else {
-                rejected.push_back(fresh);
             }
         }
         *free = !hit;
-        accepted.push_back(*slot);
+        accepted.push_back(slot);
         return AKZ_OK;
     }
 };
@@ -152,8 +143,8 @@ int place_streams(akz_ctx* c) {
     c->placed = true;
     finisher_drain(c);  // (the finish half uses c->aux)
     AKZ_TRY(ensure_aux(c));
-    if (!c->coarse) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->coarse, hipStreamNonBlocking));
-    if (!c->copy) AKZ_HIP_TRY(hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking));
+    AKZ_TRY(c->coarse.ensure());
+    AKZ_TRY(c->copy.ensure());
     if (c->settings.sched[SCHED_NO_PROBE]) {  // (measurement: no probe -- streams as the runtime placed them)
         c->pre_mode = 2;
         return AKZ_OK;
@@ -166,9 +157,9 @@ int place_streams(akz_ctx* c) {
     AKZ_TRY(sp.calibrate(c->stream));
     sp.accepted.push_back(c->stream);
     bool free_coarse = false, free_aux = false, free_copy = false;
-    AKZ_TRY(sp.settle(&c->coarse, &free_coarse));
-    AKZ_TRY(sp.settle(&c->aux, &free_aux));
-    AKZ_TRY(sp.settle(&c->copy, &free_copy));
+    AKZ_TRY(sp.settle(c->coarse, &free_coarse));
+    AKZ_TRY(sp.settle(c->aux, &free_aux));
+    AKZ_TRY(sp.settle(c->copy, &free_copy));
     c->place_collisions = (free_coarse ? 0 : 1) + (free_aux ? 0 : 1) + (free_copy ? 0 : 1);
     c->pre_mode = free_copy ? 2 : 0;
     return AKZ_OK;
@@ -184,11 +175,7 @@ int place_lanes(akz_ctx* c) {
     c->lane_collisions = 0;
     for (akz_ctx* l : c->lanes) {
         bool free = false;
-        hipStream_t st = l->stream;
-        AKZ_TRY(sp.settle(&st, &free));
-        if (st != l->stream) {  // (the replaced stream is destroyed with the placer's rejects; the lane owns the new one)
-            l->stream = st;
-        }
+        AKZ_TRY(sp.settle(l->stream, &free));  // (a replaced stream goes with the placer's rejects; the lane owns the new one)
         if (!free) ++c->lane_collisions;
     }
     return AKZ_OK;
@@ -211,7 +198,10 @@ int akz::place_streams_beside(akz_ctx* c, hipStream_t* slots, int n_slots, int* 
     sp.accepted = {c->stream, c->coarse, c->aux};
     for (int i = 0; i < n_slots; ++i) {
         bool free = false;
-        AKZ_TRY(sp.settle(&slots[i], &free));
+        Stream slot = Stream::adopt(slots[i]);  // (the component's stream for the length of the probe: settle may replace it)
+        const int rc = sp.settle(slot, &free);
+        slots[i] = slot.detach();
+        AKZ_TRY(rc);
         sp.accepted.pop_back();  // (the component's own streams may share among themselves)
         if (!free && still_shared) ++*still_shared;
     }

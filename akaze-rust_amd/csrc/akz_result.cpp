@@ -5,33 +5,34 @@
 int slab_acquire(akz_ctx* c, size_t bytes, void** p, size_t* got) {
     bytes = align_up(std::max<size_t>(bytes, 256), 256);
     std::lock_guard<std::mutex> lk(c->slab_m);
-    for (size_t i = 0; i < c->slab_pool.size(); ++i)
-        if (c->slab_pool[i].first >= bytes && c->slab_pool[i].first <= bytes + bytes / 4 + 65536) {
-            *p = c->slab_pool[i].second;
-            *got = c->slab_pool[i].first;
+    DevBuf b;  // (the block leaves as a raw pointer: a result holds it until slab_release, or until it is freed behind a dead context)
+    for (size_t i = 0; i < c->slab_pool.size() && !b.p; ++i)
+        if (c->slab_pool[i].bytes >= bytes && c->slab_pool[i].bytes <= bytes + bytes / 4 + 65536) {
+            b = std::move(c->slab_pool[i]);
             c->slab_pool.erase(c->slab_pool.begin() + (long)i);
-            return AKZ_OK;
         }
-    bytes += bytes / 8;  // head-room so that the next, slightly larger request can reuse the block
-    AKZ_HIP_TRY(hipMalloc(p, bytes));
-    AKZ_HIP_TRY(alloc_fill(c, *p, bytes));
-    *got = bytes;
+    if (!b.p) {
+        bytes += bytes / 8;  // head-room so that the next, slightly larger request can reuse the block
+        AKZ_HIP_TRY(b.acquire(bytes, false));
+        AKZ_HIP_TRY(alloc_fill(c, b.p, bytes));
+    }
+    *got = b.bytes;
+    *p = b.detach();
     return AKZ_OK;
 }
 void slab_release(akz_ctx* c, void* p, size_t bytes) {
     std::lock_guard<std::mutex> lk(c->slab_m);
     if (c->slab_pool.size() >= 8) {
         (void)sync_all_streams(c);
-        (void)hipFree(c->slab_pool.front().second);
         c->slab_pool.erase(c->slab_pool.begin());
     }
-    c->slab_pool.emplace_back(bytes, p);
+    c->slab_pool.push_back(DevBuf::adopt(p, bytes));
 }
 
 static void result_release_device(akz_result* r) {
     if (r->ctx && r->ctx->dead) {  // the pools went away with the context: hand the blocks back to the runtime
-        if (r->slab) (void)hipFree(r->slab);
-        if (r->d_desc64) (void)hipFree(r->d_desc64);
+        (void)DevBuf::adopt(r->slab, r->slab_bytes).release();
+        (void)DevBuf::adopt(r->d_desc64, r->desc_block_bytes).release();
     } else {
         if (r->slab) slab_release(r->ctx, r->slab, r->slab_bytes);
         if (r->d_desc64) slab_release(r->ctx, r->d_desc64, r->desc_block_bytes);
@@ -57,8 +58,7 @@ void job_release(akz_job* j) {
     (void)sync_all_streams(c, kSyncMain | kSyncSide);
     if (j->slot >= 0) c->slot_busy[j->slot] = false;
     j->slot = -1;
-    ev_put(c, j->nms_done);
-    j->nms_done = nullptr;
+    ev_put(c, std::move(j->nms_done));
     result_release_device(j->r.get());
 }
 // the outcome of an eagerly finished job, once its lane's thread is through with it
@@ -398,11 +398,10 @@ static bool pinned_range(const void* p, size_t bytes) {
 }
 
 static int fetch_events(akz_ctx* c) {
-    for (hipStream_t& s : c->fetch)
-        if (!s) AKZ_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&c->fetch_chunk[0], &c->fetch_chunk[1], &c->fetch_chunk[2], &c->fetch_chunk[3], &c->fetch_start,
-                          &c->fetch_join, &c->fetch_ready[0], &c->fetch_ready[1], &c->fetch_free[0], &c->fetch_free[1]})
-        if (!*e) AKZ_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (Stream& s : c->fetch) AKZ_TRY(s.ensure());
+    for (Event* e : {&c->fetch_chunk[0], &c->fetch_chunk[1], &c->fetch_chunk[2], &c->fetch_chunk[3], &c->fetch_start,
+                     &c->fetch_join, &c->fetch_ready[0], &c->fetch_ready[1], &c->fetch_free[0], &c->fetch_free[1]})
+        AKZ_TRY(e->ensure());
     return AKZ_OK;
 }
 

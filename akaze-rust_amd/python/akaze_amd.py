@@ -254,6 +254,7 @@ def lib():
         "akz_debug_set_host_sort": ([vp, i32], i32),
         "akz_debug_set_alloc_fill": ([vp, i32], i32),
         "akz_debug_audit_scratch": ([vp, vp, u32, pu32], i32),
+        "akz_debug_resource_counts": ([pu64], i32),
         "akz_debug_set_select": ([vp, i32], i32),
         "akz_debug_select_info": ([vp, C.POINTER(C.c_int)], i32),
         "akz_debug_set_schedule": ([vp, i32, i32], i32),
@@ -397,6 +398,14 @@ def lib():
     L._declared = sorted(sig)
     _lib = L
     return L
+
+
+def debug_resource_counts():
+    """akz_debug_resource_counts: what the library holds process-wide -> dict(device_blocks, device_bytes, pinned_blocks,
+    pinned_bytes, events, streams)."""
+    out = (C.c_uint64 * 6)()
+    _check(lib().akz_debug_resource_counts(out))
+    return dict(zip(("device_blocks", "device_bytes", "pinned_blocks", "pinned_bytes", "events", "streams"), map(int, out)))
 
 
 def _check(status):

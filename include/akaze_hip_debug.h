@@ -178,6 +178,12 @@ typedef struct akz_scratch_audit {
 } akz_scratch_audit;
 int akz_debug_set_alloc_fill(akz_ctx* ctx, int on);
 int akz_debug_audit_scratch(akz_ctx* ctx, akz_scratch_audit* out, uint32_t cap, uint32_t* n_rows);
+/* Test hook: what the library holds of the runtime right now, process-wide, over all contexts, jobs and results: out[0] = device
+   blocks, out[1] = their bytes, out[2] = pinned host blocks, out[3] = their bytes, out[4] = events, out[5] = streams (the caller's
+   stream of akz_ctx_create is not the library's and not counted; nor are the objects of akz_comm_*, akz_device_malloc and
+   akz_stream_create).  A context that is created, used and destroyed, its results freed, leaves all six where they were.  No GPU
+   call, no context. */
+int akz_debug_resource_counts(uint64_t out[6]);
 
 /* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
    source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */
