@@ -210,10 +210,13 @@ int akz_ctx_set_eager_finish(akz_ctx* c, int on) {
     c->eager_finish = on != 0;
     return AKZ_OK;
 }
+// `frames`: imgs are device frames in that layout (u8), converted to luma into the job's staging buffer.  sync_call: the
+// begin half of a synchronous call -- on the context itself, finished by the caller right away (extract_impl's form).
 static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint32_t w, uint32_t h, uint32_t n,
-                                  const akz_config* cfg, uint32_t flags, akz_job** out, bool on_host = false) {
+                                  const akz_config* cfg, uint32_t flags, akz_job** out, bool on_host = false,
+                                  const FrameSpec* frames = nullptr, bool sync_call = false) {
     akz_ctx* on = c;
-    if (c && !c->lanes.empty() && (uint64_t)w * h * n < c->settings.lane_px) {
+    if (!sync_call && c && !c->lanes.empty() && (uint64_t)w * h * n < c->settings.lane_px) {
         AKZ_TRY(bind(c, false));
         on = c->lanes[c->next_lane++ % c->lanes.size()];
         // the lane starts when the caller's stream has reached this point (its inputs are complete)
@@ -223,10 +226,15 @@ static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint
     }
     int slot = -1;
     const void* d_imgs = imgs;
-    if (on_host) {
-        // Frames in host memory: upload on the context's copy stream into the staging buffer of the job slot this
-        // extraction will hold (exclusive until its finish); only this job's kernels wait for the copy, so it runs
-        // under whatever the main stream is doing for the batch before.
+    hipEvent_t ready = nullptr;  // frames this library put into the staging buffer on the copy stream: complete behind that event
+    if (on_host || frames) {
+        // Frames in host memory, or device frames in a layout of the caller's: they go into the staging buffer of the job
+        // slot this extraction will hold (exclusive until its finish or abandon, so jobs in flight never share one).
+        // Host frames are uploaded on the context's copy stream; only this job's kernels wait for the copy, so it runs
+        // under whatever the main stream is doing for the batch before.  Device frames are converted to luma
+        // (k_frame_luma): with AKZ_INPUT_READY on the copy stream in exactly that shape; without it they may be the
+        // output of work queued earlier on the caller's stream, so the conversion goes on the job's main stream (a lane's:
+        // behind the lane_in wait above) and no event is handed down.
         if (out) *out = nullptr;
         AKZ_TRY(bind(on, true, on->is_lane));
         if (!imgs || w == 0 || h == 0 || n == 0) {
@@ -240,21 +248,41 @@ static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint
         }
         const size_t bytes = (size_t)w * h * n * (is_u8 ? 1 : sizeof(float));
         AKZ_TRY(ensure(on, on->stage[slot], bytes));
-        AKZ_TRY(on->copy.ensure());
-        AKZ_TRY(on->staged[slot].ensure());
-        AKZ_HIP_TRY(hipMemcpyAsync(on->stage[slot].p, imgs, bytes, hipMemcpyHostToDevice, on->copy));
-        AKZ_HIP_TRY(hipEventRecord(on->staged[slot], on->copy));
-        AKZ_HIP_TRY(hipStreamWaitEvent(on->stream, on->staged[slot], 0));
+        const bool on_copy = on_host || (flags & AKZ_INPUT_READY);
+        if (on_copy) {
+            AKZ_TRY(on->copy.ensure());
+            AKZ_TRY(on->staged[slot].ensure());
+        }
+        if (on_host) AKZ_HIP_TRY(hipMemcpyAsync(on->stage[slot].p, imgs, bytes, hipMemcpyHostToDevice, on->copy));
+        else AKZ_TRY(frames_enqueue(on, on_copy ? on->copy.h : on->stream.h, (const uint8_t*)imgs, *frames, n, (uint8_t*)on->stage[slot].p));
+        if (on_copy) {
+            AKZ_HIP_TRY(hipEventRecord(on->staged[slot], on->copy));
+            AKZ_HIP_TRY(hipStreamWaitEvent(on->stream, on->staged[slot], 0));
+            ready = on->staged[slot].h;
+        }
+        if (frames) flags &= ~(uint32_t)AKZ_INPUT_READY;  // (the promise was about the caller's frames; the luma frames are complete behind `ready`)
         d_imgs = on->stage[slot].p;
     }
-    hipEvent_t ready = on_host ? on->staged[slot].h : nullptr;  // frames this library uploaded: complete behind that event
-    const int rc = is_u8 ? extract_begin<uint8_t>(on, (const uint8_t*)d_imgs, w, h, n, cfg, flags, out, slot, ready)
-                         : extract_begin<float>(on, (const float*)d_imgs, w, h, n, cfg, flags, out, slot, ready);
+    const int rc = is_u8 ? extract_begin<uint8_t>(on, (const uint8_t*)d_imgs, w, h, n, cfg, flags, out, slot, ready, sync_call)
+                         : extract_begin<float>(on, (const float*)d_imgs, w, h, n, cfg, flags, out, slot, ready, sync_call);
     // a job dealt to a lane is always finished by the lane's own thread (lanes whose jobs wait for the caller's finish call
     // measured SLOWER than no lanes: the chains overlap on the chip but the finish halves queue on one host thread)
-    if (rc == AKZ_OK && (c->eager_finish || on != c)) finisher_post(on, *out);
+    if (rc == AKZ_OK && !sync_call && (c->eager_finish || on != c)) finisher_post(on, *out);
     return rc;
 }
+}  // extern "C"
+// akz_extract_device_frames / akz_extract_begin_device_frames (akz_frames_api.cpp, which has checked the layout)
+int extract_begin_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_job** out) {
+    if (fs.packed_gray()) return extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags, out);  // already what the extraction takes
+    return extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags, out, false, &fs);
+}
+int extract_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_result** out) {
+    if (fs.packed_gray()) return extract_impl<uint8_t>(c, d_src, fs.w, fs.h, n, cfg, flags, out);
+    akz_job* job = nullptr;
+    AKZ_TRY(extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags & ~(uint32_t)AKZ_INPUT_READY, &job, false, &fs, /*sync_call=*/true));
+    return extract_finish(job, out);
+}
+extern "C" {
 int akz_extract_begin_host_u8(akz_ctx* c, const uint8_t* h_imgs, uint32_t w, uint32_t h, uint32_t n, const akz_config* cfg,
                               uint32_t flags, akz_job** out) {
     return extract_begin_dispatch(c, h_imgs, true, w, h, n, cfg, flags, out, true);

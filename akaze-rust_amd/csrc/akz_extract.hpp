@@ -2,6 +2,7 @@
 // akz_result.cpp, akz_place.cpp): results and jobs, opening a job, the two halves.  Host only.
 #pragma once
 #include "akz_ctx.hpp"
+#include "akz_frames.hpp"
 
 struct akz_result {
     akz_ctx* ctx = nullptr;
@@ -118,3 +119,8 @@ AKZ_LOCAL int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h,
                             int want_slot = -1, hipEvent_t input_ready = nullptr, bool sync_call = false);
 // The finish half proper.  The job shell stays with the caller; on failure everything the job held is released.
 AKZ_LOCAL int extract_finish_body(akz_job* jobp, akz_result** out);
+// ---- akz_extract.cpp / akz_frames_api.cpp: device frames in a layout of the caller's (akz_frames.hpp) ----
+AKZ_LOCAL int extract_begin_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_job** out);
+AKZ_LOCAL int extract_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_result** out);
+// k_frame_luma on stream s of context c, with its profile row (stage 10)
+AKZ_LOCAL int frames_enqueue(akz_ctx* c, hipStream_t s, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, uint8_t* d_luma);

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "akz_frames.hpp"
 #include "akz_internal.hpp"
 #include "akz_jpeg.hpp"
 
@@ -779,10 +780,7 @@ int load(const char* path, Image& im) {
 void to_luma(const Image& im, std::vector<uint8_t>& out) {
     if (im.ch == 1) { out = im.px; return; }
     out.resize((size_t)im.w * im.h);
-    for (size_t i = 0; i < out.size(); ++i) {
-        const float l = 0.2126f * (float)im.px[3 * i] + 0.7152f * (float)im.px[3 * i + 1] + 0.0722f * (float)im.px[3 * i + 2];
-        out[i] = (uint8_t)l;
-    }
+    for (size_t i = 0; i < out.size(); ++i) out[i] = luma_u8(im.px[3 * i], im.px[3 * i + 1], im.px[3 * i + 2]);
 }
 int load_luma_bytes(const char* path, const std::vector<uint8_t>& d, uint32_t* w, uint32_t* h, std::vector<uint8_t>& luma) {
     Image im;

@@ -5,6 +5,7 @@
 // (-ffp-contract=off), so the bytes equal akz_image_load_luma's for every stream the host accepts.
 #include <hip/hip_runtime.h>
 
+#include "akz_frames.hpp"
 #include "akz_internal.hpp"
 #include "akz_jpeg.hpp"
 
@@ -139,8 +140,7 @@ __global__ void __launch_bounds__(LX) k_jpeg_luma(Frame f, const uint8_t* __rest
     const float g = Y - 0.34414f * cb - 0.71414f * cr;
     const float b = Y + 1.77200f * cb;
     const uint8_t R = clamp_u8((int)(r + 0.5f)), G = clamp_u8((int)(g + 0.5f)), B = clamp_u8((int)(b + 0.5f));
-    const float l = 0.2126f * (float)R + 0.7152f * (float)G + 0.0722f * (float)B;  // img::to_luma
-    *o = (uint8_t)l;
+    *o = luma_u8(R, G, B);  // img::to_luma
 }
 
 }  // namespace

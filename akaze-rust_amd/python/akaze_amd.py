@@ -28,6 +28,10 @@ AKZ_ERR_BUFFER = -7
 
 PLANES = ["Lt", "Lsmooth", "Lx", "Ly", "Lxx", "Lyy", "Lxy", "Lflow", "Lstep", "Ldet"]
 
+# akz_frame_format
+FRAME_GRAY8, FRAME_RGB8, FRAME_BGR8, FRAME_RGBA8, FRAME_BGRA8, FRAME_RGB8_PLANAR = range(6)
+KR_FRAME_LUMA = 12  # akz_kernel_row.kind of k_frame_luma (stage 10)
+
 
 class AkazeError(RuntimeError):
     def __init__(self, status, msg):
@@ -62,6 +66,65 @@ class Config(C.Structure):
 STAGES = ["blur0", "contrast", "prep", "fed", "detector", "nms", "host_kp", "orient", "mldb", "total"]
 
 
+class FrameLayout(C.Structure):
+    """akz_frame_layout: frames as their producer holds them.  Strides in bytes; 0 = tight."""
+    _fields_ = [("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("row_pitch", C.c_uint64),
+                ("frame_stride", C.c_uint64), ("plane_stride", C.c_uint64)]
+
+
+def frame_layout_of(shape, strides, layout="hwc", order="rgb"):
+    """(FrameLayout, n, batched) of a uint8 array / tensor of `shape` whose `strides` are in bytes.  layout: "hw" ([N,]H,W:
+    luma), "hwc" ([N,]H,W,C with C = 3 or 4: interleaved) or "chw" ([N,]3,H,W: planar R, G, B); order: "rgb" or "bgr"
+    (interleaved only).  The innermost pixel must be dense; row, plane and frame strides are free as long as rows, planes and
+    frames do not overlap.  ValueError names the stride the layout cannot express."""
+    rank = {"hw": 2, "hwc": 3, "chw": 3}.get(layout)
+    if rank is None:
+        raise ValueError('layout must be "hw", "hwc" or "chw"')
+    if order not in ("rgb", "bgr"):
+        raise ValueError('order must be "rgb" or "bgr"')
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) not in (rank, rank + 1):
+        raise ValueError(f'layout "{layout}" takes {rank} or {rank + 1} dimensions, got {len(shape)}')
+    batched = len(shape) == rank + 1
+    n, fstride = (shape[0], strides[0]) if batched else (1, 0)
+    dims, st = shape[-rank:], strides[-rank:]
+    if layout == "hw":
+        (h, w), (sh, sw), c, sc, plane = dims, st, 1, 1, 0
+        fmt = FRAME_GRAY8
+    elif layout == "hwc":
+        (h, w, c), (sh, sw, sc), plane = dims, st, 0
+        if c not in (3, 4):
+            raise ValueError(f"interleaved frames have 3 or 4 channels, got {c}")
+        fmt = {(3, "rgb"): FRAME_RGB8, (3, "bgr"): FRAME_BGR8, (4, "rgb"): FRAME_RGBA8, (4, "bgr"): FRAME_BGRA8}[(c, order)]
+    else:
+        (c, h, w), (plane, sh, sw), sc = dims, st, 1
+        if c != 3:
+            raise ValueError(f"planar frames have 3 planes, got {c}")
+        if order != "rgb":
+            raise ValueError("planar frames are R, G, B planes (akz_frame_format has no planar BGR)")
+        fmt, c = FRAME_RGB8_PLANAR, 1
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError("empty frames")
+    if layout == "hwc" and sc != 1:
+        raise ValueError(f"channel stride {sc}: the channels of a pixel must be adjacent bytes")
+    if w > 1 and sw != c:
+        raise ValueError(f"pixel stride {sw}: the pixels of a row must be dense (stride {c})")
+    tight_row = w * c
+    if h > 1 and sh < tight_row:
+        raise ValueError(f"row stride {sh} is smaller than a row ({tight_row} bytes)")
+    row_pitch = sh if h > 1 else tight_row
+    tight_plane = row_pitch * h
+    if layout == "chw":
+        if plane < tight_plane:
+            raise ValueError(f"plane stride {plane} is smaller than a plane ({tight_plane} bytes)")
+        tight_frame = 3 * plane
+    else:
+        tight_frame = tight_plane
+    if n > 1 and fstride < tight_frame:
+        raise ValueError(f"frame stride {fstride} is smaller than a frame ({tight_frame} bytes)")
+    return FrameLayout(fmt, w, h, row_pitch, fstride if n > 1 else 0, plane), n, batched
+
+
 class KernelRow(C.Structure):
     """akz_kernel_row (akaze_hip_debug.h)"""
     _fields_ = [("stage", C.c_uint32), ("kind", C.c_uint32), ("param", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
@@ -69,7 +132,8 @@ class KernelRow(C.Structure):
 
 
 KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march",
-                    6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d", 9: "k_sort_rows", 10: "k_bucket_sort", 11: "rocprim_radix_sort"}
+                    6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d", 9: "k_sort_rows", 10: "k_bucket_sort", 11: "rocprim_radix_sort",
+                    12: "k_frame_luma"}
 
 
 class ScratchAudit(C.Structure):
@@ -222,6 +286,10 @@ def lib():
         "akz_extract_device_f32": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_begin_device_u8": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_begin_device_f32": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
+        "akz_luma_from_frames_host": ([vp, C.POINTER(FrameLayout), u32, vp], i32),
+        "akz_luma_from_frames_device": ([vp, vp, C.POINTER(FrameLayout), u32, vp], i32),
+        "akz_extract_device_frames": ([vp, vp, C.POINTER(FrameLayout), u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
+        "akz_extract_begin_device_frames": ([vp, vp, C.POINTER(FrameLayout), u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_begin_host_u8": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_begin_host_f32": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_finish": ([vp, C.POINTER(vp)], i32),
@@ -815,6 +883,52 @@ class Context:
         _check(fn(self._h, C.c_void_p(t.data_ptr()), w, h, n, C.byref(options), flags, C.byref(job)))
         return Job(self, job, t)
 
+    def _device_frames(self, t, layout, order):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
+            raise ValueError("device frames must be uint8 torch CUDA tensors")
+        return frame_layout_of(t.shape, t.stride(), layout, order)
+
+    def luma_from_frames(self, t, layout="hwc", order="rgb", out=None):
+        """akz_luma_from_frames_device: to_luma of the frames of a uint8 torch CUDA view (frame_layout_of: crops, pitched
+        and non-contiguous batches pass with no copy) as a [N, H, W] uint8 CUDA tensor ([H, W] for one unbatched frame),
+        enqueued on the context's stream.  out: a contiguous uint8 CUDA tensor of N*H*W elements to write instead (any
+        alignment)."""
+        import torch
+        fl, n, batched = self._device_frames(t, layout, order)
+        shape = (n, fl.height, fl.width) if batched else (fl.height, fl.width)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=t.device)
+        elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == n * fl.height * fl.width):
+            raise ValueError("out must be a contiguous uint8 CUDA tensor of N*H*W elements")
+        _check(lib().akz_luma_from_frames_device(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.c_void_p(out.data_ptr())))
+        return out.view(shape)
+
+    def extract_frames(self, t, layout="hwc", order="rgb", options=None, keep_all_planes=True, host_descriptors=True):
+        """akz_extract_device_frames: extract_features on the luma of colour, pitched or cropped device frames -- the
+        result of extract_features(luma_from_frames(t)), bit for bit.  Keypoint coordinates are relative to the view."""
+        options = options or Config()
+        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS)
+        fl, n, _ = self._device_frames(t, layout, order)
+        res = C.c_void_p()
+        _check(lib().akz_extract_device_frames(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.byref(options), flags,
+                                               C.byref(res)))
+        return ExtractResult(self, res)
+
+    def extract_frames_begin(self, t, layout="hwc", order="rgb", options=None, keep_all_planes=True, host_descriptors=True,
+                             input_ready=False):
+        """akz_extract_begin_device_frames: the first half of extract_frames, returning a Job without synchronising.
+        input_ready=True (AKZ_INPUT_READY): the frames are complete in device memory now; the conversion then runs on the
+        context's copy stream, under the kernels of the batch begun before.  The Job keeps the tensor alive."""
+        options = options or Config()
+        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS) | \
+                (AKZ_INPUT_READY if input_ready else 0)
+        fl, n, _ = self._device_frames(t, layout, order)
+        job = C.c_void_p()
+        _check(lib().akz_extract_begin_device_frames(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.byref(options),
+                                                     flags, C.byref(job)))
+        return Job(self, job, t)
+
     def extract_begin_host(self, frames, options=None, keep_all_planes=True, host_descriptors=True):
         """extract_begin for frames in HOST memory (akz_extract_begin_host_*): a numpy array or a torch CPU tensor
         [N, H, W] (uint8 or float32), ideally pinned (torch .pin_memory()): the upload runs on the context's copy
@@ -1392,6 +1506,18 @@ def load_image_rgb(path):
     w, h, px = C.c_uint32(), C.c_uint32(), C.c_void_p()
     _check(lib().akz_image_load_rgb(os.fsencode(path), C.byref(w), C.byref(h), C.byref(px)))
     return _take(px, w.value * h.value * 3).reshape(h.value, w.value, 3)
+
+
+def luma_from_frames_host(array, layout="hwc", order="rgb"):
+    """akz_luma_from_frames_host: to_luma of the frames of a uint8 numpy array or view (frame_layout_of) as a packed
+    [N, H, W] array ([H, W] for one unbatched frame).  No GPU call."""
+    a = np.asarray(array)
+    if a.dtype != np.uint8:
+        raise ValueError("frames must be uint8")
+    fl, n, batched = frame_layout_of(a.shape, a.strides, layout, order)
+    out = np.empty((n, fl.height, fl.width) if batched else (fl.height, fl.width), np.uint8)
+    _check(lib().akz_luma_from_frames_host(C.c_void_p(a.ctypes.data), C.byref(fl), n, C.c_void_p(out.ctypes.data)))
+    return out
 
 
 def save_png(path, pixels):

@@ -243,6 +243,49 @@ int akz_extract_begin_host_f32(akz_ctx* ctx, const float* h_imgs, uint32_t w, ui
 int akz_extract_finish(akz_job* job, akz_result** out);
 int akz_job_abandon(akz_job* job);
 
+/* ---- frames as their producer holds them: colour, pitched, strided, cropped ---------- */
+/* `image::open(path).to_luma()` (akaze/src/lib.rs:171-172) for frames that are already in memory: what a decoder, a torch
+   pipeline or a region of interest hands over, read where it lies.  The luma of a colour pixel is DynamicImage::to_luma's
+   (f32 weights 0.2126 / 0.7152 / 0.0722, unfused, truncated) -- bit for bit the frame akz_image_load_luma gives for the
+   same pixels, so a picture gives the same keypoints through a file and through these calls. */
+typedef enum akz_frame_format {
+    AKZ_FRAME_GRAY8 = 0,        /* 1 byte / px; to_luma of a one-channel image is the identity (an NV12 Y plane is this, with its pitch) */
+    AKZ_FRAME_RGB8 = 1, AKZ_FRAME_BGR8 = 2,      /* interleaved, 3 bytes / px */
+    AKZ_FRAME_RGBA8 = 3, AKZ_FRAME_BGRA8 = 4,    /* interleaved, 4 bytes / px; alpha ignored, as to_luma of an Rgba image drops it */
+    AKZ_FRAME_RGB8_PLANAR = 5                    /* three planes R, G, B (torch [N,3,H,W]) */
+} akz_frame_format;
+/* A crop is the caller's pointer moved to the region's first pixel plus the parent's pitch (no origin fields).  Tight
+   values: row_pitch = width * bytes per pixel (1 for the planar format); plane_stride = row_pitch * height; frame_stride =
+   row_pitch * height, planar 3 * plane_stride.  Only the bytes of the declared rows are ever read, in naturally aligned
+   words of 4 bytes that hold at least one of them: no padding behind the last row is needed. */
+typedef struct akz_frame_layout {
+    uint32_t format, width, height;   /* width x height: the region extracted, in pixels */
+    uint64_t row_pitch;     /* bytes from a row to the next; 0 = tight (width * bytes per pixel) */
+    uint64_t frame_stride;  /* bytes from a frame to the next; 0 = tight */
+    uint64_t plane_stride;  /* planar only: bytes from R to G and G to B; 0 = row_pitch * height */
+} akz_frame_layout;
+/* Refusals of the four calls below, all AKZ_ERR_INVALID_ARG with the field named in akz_last_error, nothing written or
+   enqueued and *out = NULL: a null pointer, n = 0, an unknown format, a zero width or height, a nonzero row_pitch,
+   frame_stride or plane_stride below its tight value.  Frames too small for the stencils: AKZ_ERR_TOO_SMALL, as ever. */
+/* The statement: luma[n][height][width] (packed) of n frames in HOST memory.  No context, no GPU call. */
+int akz_luma_from_frames_host(const uint8_t* src, const akz_frame_layout* layout, uint32_t n, uint8_t* luma);
+/* The same on the device, enqueued on the context's stream (not synchronised).  d_luma may have any alignment; only its
+   n * width * height bytes are written. */
+int akz_luma_from_frames_device(akz_ctx* ctx, const uint8_t* d_src, const akz_frame_layout* layout, uint32_t n, uint8_t* d_luma);
+/* The result of akz_extract_device_u8 on akz_luma_from_frames_device of the frames, bit for bit.  The luma frames go
+   into a staging buffer of the context that belongs to the job (AKZ_FRAME_GRAY8 with tight strides is handed to
+   akz_extract_device_u8 as it is). */
+int akz_extract_device_frames(akz_ctx* ctx, const uint8_t* d_src, const akz_frame_layout* layout, uint32_t n,
+                              const akz_config* cfg, uint32_t flags, akz_result** out);
+/* The two-phase form (akz_extract_begin_device_u8).  Without AKZ_INPUT_READY the frames may be the output of work the
+   caller enqueued on the context's stream before the call: the conversion runs on that stream (for a job dealt to a
+   lane, on the lane's stream once the caller's stream has reached this point).  With AKZ_INPUT_READY the caller promises
+   that the frames are complete NOW: the conversion runs on the context's copy stream, as the upload of
+   akz_extract_begin_host_* does, under the kernels of the batch before.  d_src must stay valid and unchanged until the
+   job is finished or abandoned. */
+int akz_extract_begin_device_frames(akz_ctx* ctx, const uint8_t* d_src, const akz_frame_layout* layout, uint32_t n,
+                                    const akz_config* cfg, uint32_t flags, akz_job** out);
+
 /* ops::scale_space_extrema::detect_keypoints (scale_space_extrema.rs:199-203) and ops::descriptors::extract_descriptors
    (descriptors.rs:14-27) on evolutions the CALLER holds (the reference's `pub mod ops` takes `&[EvolutionStep]` that
    need not come from extract_features): planes = n_levels x 10 host pointers in akz_plane order (row-major f32 of the

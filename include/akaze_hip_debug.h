@@ -133,10 +133,12 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    (px = bytes copied), each with param = components and (w, h, 1) = the frame.
    The device sort of a job's extrema candidates adds one row of stage 11 per job, counted and never timed (ms stays 0; any
    profiling level): k_sort_rows (one launch), the four k_bucket_* launches, or the key / radix sort / gather chain around
-   rocPRIM -- param 0, (w, h, n) = the frame and the batch, px = the list's capacity. */
+   rocPRIM -- param 0, (w, h, n) = the frame and the batch, px = the list's capacity.
+   The conversion of caller-held frames (akz_luma_from_frames_device, akz_extract_*_device_frames) adds one row of stage 10 per
+   launch: k_frame_luma, param = the akz_frame_format, (w, h, n) = the frames, px = output pixels. */
 enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5,
        AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8, AKZ_KR_SORT_ROWS = 9, AKZ_KR_SORT_BUCKETS = 10,
-       AKZ_KR_SORT_RADIX = 11 };
+       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12 };
 typedef struct akz_kernel_row {
     uint32_t stage, kind, param, w, h, n;
     uint64_t launches, px, px_steps;
