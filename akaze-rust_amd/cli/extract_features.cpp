@@ -1,5 +1,33 @@
 // extract_features INPUT OUTPUT [-d DIRECTORY] [-o PATH] — akaze-util/src/bin/extract_features.rs:18-112.
+// [-m PATH] (this build's own): a detection mask, an image of the input's size whose nonzero pixels are where to detect.
 #include "cli_common.hpp"
+
+// cli::extract with a mask: both images through akz_image_load_luma, then akz_extract_gray_u8_masked
+static cli::Features extract_masked(akz_ctx* ctx, const char* path, const char* mask_path, const akz_config& cfg, bool keep_planes, akz_result** keep) {
+    uint32_t w = 0, h = 0, mw = 0, mh = 0;
+    uint8_t *luma = nullptr, *mask = nullptr;
+    CLI_TRY(akz_image_load_luma(path, &w, &h, &luma));
+    CLI_TRY(akz_image_load_luma(mask_path, &mw, &mh, &mask));
+    if (mw != w || mh != h) {
+        fprintf(stderr, "error: the mask %s is %u x %u but the input %s is %u x %u\n", mask_path, mw, mh, path, w, h);
+        exit(1);
+    }
+    akz_result* res = nullptr;
+    CLI_TRY(akz_extract_gray_u8_masked(ctx, luma, mask, w, h, &cfg, keep_planes ? AKZ_KEEP_ALL_PLANES : 0, &res));
+    akz_image_free(luma);
+    akz_image_free(mask);
+    cli::Features f;
+    uint64_t nl = 0, nk = 0;
+    CLI_TRY(akz_result_counts(res, 0, &nl, &nk, &f.desc_bytes));
+    f.keypoints.resize(nk);
+    f.descriptors.resize(nk * f.desc_bytes);
+    if (nk) {
+        CLI_TRY(akz_result_keypoints(res, 0, f.keypoints.data()));
+        CLI_TRY(akz_result_descriptors(res, 0, f.descriptors.data()));
+    }
+    *keep = res;
+    return f;
+}
 
 int main(int argc, char** argv) {
     const cli::Spec spec{
@@ -9,7 +37,8 @@ int main(int argc, char** argv) {
         "Set AKAZE_LOG to debug for more verbose output.",
         {{"INPUT", "The input image."}, {"OUTPUT", "The output extractions. Extension can be JSON or CBOR."}},
         {{'d', "debug_path", "DIRECTORY", "Sets a directory to write debug information to."},
-         {'o', "options", "PATH", "A JSON file containing options."}}};
+         {'o', "options", "PATH", "A JSON file containing options."},
+         {'m', "mask", "PATH", "A mask image of the input's size: features are detected only where it is nonzero."}}};
     const cli::Args a = cli::parse(spec, argc, argv);
     const cli::Timer timer;
     const char* input = a.pos[0].c_str();
@@ -44,7 +73,10 @@ int main(int argc, char** argv) {
     akz_ctx* ctx = cli::open_context();
     const char* debug_dir = a.get("debug_path");
     akz_result* res = nullptr;
-    const cli::Features f = cli::extract(ctx, input, options, debug_dir != nullptr, &res);
+    const char* mask_path = a.get("mask");
+    if (mask_path) CLI_INFO("Detection mask path is %s.", mask_path);
+    const cli::Features f = mask_path ? extract_masked(ctx, input, mask_path, options, debug_dir != nullptr, &res)
+                                      : cli::extract(ctx, input, options, debug_dir != nullptr, &res);
     CLI_TRY(akz_write_features(output, f.keypoints.data(), f.keypoints.size(), f.descriptors.data(), f.desc_bytes));
     CLI_INFO("Done, extracted %zu features.", f.keypoints.size());
     if (debug_dir) {

@@ -357,6 +357,8 @@ struct CtxOwned {
     // extractions in flight (akz_extract_begin_* / akz_extract_finish)
     static constexpr int kSlots = 3;
     DevBuf cand_slot[kSlots], count_slot[kSlots];
+    DevBuf cand_mask_slot[kSlots];      // a masked job's list: what launch::mask_candidates keeps of cand_slot (same capacity; allocated by the first masked job of the slot; no claim)
+    DevBuf mask_up;                     // akz_extract_gray_u8_masked: the host mask on the device for the length of that (synchronous) call; no claim
     Stream aux;                         // finish-side copies and keypoint kernels (created under aux_m: the caller's thread and the finisher's may both be first)
     Stream coarse;                      // the coarse octaves' chain (diffusion + detectors), next to the fine detectors
     Stream pre;                         // level-0 blur + contrast factor of a batch whose input is known to be complete:
@@ -418,6 +420,9 @@ struct akz_ctx : CtxOwned {
     bool dead = false;                  // akz_ctx_destroy was called; the struct lives until the last result is freed
     std::atomic<uint32_t> last_total_cands{0};  // candidates of the previous finished job (speculative fetch size)
     std::atomic<uint64_t> last_cand_shape{0};   // ... and its shape (akz_extract.hpp: shape_key)
+    // akz_debug_mask_counts: the last finished masked job -- candidates before the mask, kept, NMS passes redone -- and when it
+    // finished (a process-wide count: a context with lanes reports the latest of its own and theirs)
+    std::atomic<uint64_t> mask_last[3] = {{0}, {0}, {0}}, mask_stamp{0};
     std::mutex aux_m;                   // guards the creation of aux
     // Lanes: child contexts (own streams, scratch planes, candidate slots) that small jobs are dealt to in turn, so that
     // the launch chains of consecutive single frames -- 44 back-to-back launches of a few hundred workgroups each --

@@ -127,17 +127,17 @@ static int extract_from_planes(akz_ctx* c, uint32_t w, uint32_t h, const akz_con
 
 template <typename T>
 static int extract_impl(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t n, const akz_config* cfgp,
-                        uint32_t flags, akz_result** out) {
+                        uint32_t flags, akz_result** out, const MaskSpec* mask = nullptr) {
     if (!out) return AKZ_ERR_INVALID_ARG;
     *out = nullptr;
     akz_job* job = nullptr;
-    AKZ_TRY(extract_begin<T>(c, d_imgs, w, h, n, cfgp, flags, &job, -1, nullptr, /*sync_call=*/true));
+    AKZ_TRY(extract_begin<T>(c, d_imgs, w, h, n, cfgp, flags, &job, -1, nullptr, /*sync_call=*/true, mask));
     return extract_finish(job, out);
 }
 
 template <typename T>
 static int extract_host(akz_ctx* c, const T* img, uint32_t w, uint32_t h, const akz_config* cfg, uint32_t flags,
-                        akz_result** out) {
+                        akz_result** out, const uint8_t* host_mask = nullptr) {
     AKZ_TRY(bind(c));
     if (!img || w == 0 || h == 0) {
         set_error("extract: null or empty image");
@@ -145,9 +145,15 @@ static int extract_host(akz_ctx* c, const T* img, uint32_t w, uint32_t h, const 
     }
     const size_t bytes = (size_t)w * h * sizeof(T);
     AKZ_TRY(ensure(c, c->scratch[4], bytes));
+    MaskSpec mask;
+    if (host_mask) {  // w * h bytes, tight: uploaded behind the frame; the call is synchronous, so the one buffer serves
+        AKZ_TRY(ensure(c, c->mask_up, (size_t)w * h));
+        AKZ_HIP_TRY(hipMemcpyAsync(c->mask_up.p, host_mask, (size_t)w * h, hipMemcpyHostToDevice, c->stream));
+        mask = MaskSpec{(const uint8_t*)c->mask_up.p, w, 0};
+    }
     AKZ_HIP_TRY(hipMemcpyAsync(c->scratch[4].p, img, bytes, hipMemcpyHostToDevice, c->stream));
     // the frame is consumed by level 0 on the same stream before anything else touches scratch[4]
-    return extract_impl<T>(c, (const T*)c->scratch[4].p, w, h, 1, cfg, flags, out);
+    return extract_impl<T>(c, (const T*)c->scratch[4].p, w, h, 1, cfg, flags, out, host_mask ? &mask : nullptr);
 }
 
 extern "C" {
@@ -155,6 +161,15 @@ extern "C" {
 int akz_extract_gray_u8(akz_ctx* c, const uint8_t* img, uint32_t w, uint32_t h, const akz_config* cfg, uint32_t flags,
                         akz_result** out) {
     return extract_host<uint8_t>(c, img, w, h, cfg, flags, out);
+}
+int akz_extract_gray_u8_masked(akz_ctx* c, const uint8_t* img, const uint8_t* mask, uint32_t w, uint32_t h, const akz_config* cfg, uint32_t flags,
+                               akz_result** out) {
+    if (out) *out = nullptr;
+    if (!mask) {
+        set_error("akz_extract_gray_u8_masked: null mask");
+        return AKZ_ERR_INVALID_ARG;
+    }
+    return extract_host<uint8_t>(c, img, w, h, cfg, flags, out, mask);
 }
 int akz_extract_gray_f32(akz_ctx* c, const float* img, uint32_t w, uint32_t h, const akz_config* cfg, uint32_t flags,
                          akz_result** out) {
@@ -214,7 +229,7 @@ int akz_ctx_set_eager_finish(akz_ctx* c, int on) {
 // begin half of a synchronous call -- on the context itself, finished by the caller right away (extract_impl's form).
 static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint32_t w, uint32_t h, uint32_t n,
                                   const akz_config* cfg, uint32_t flags, akz_job** out, bool on_host = false,
-                                  const FrameSpec* frames = nullptr, bool sync_call = false) {
+                                  const FrameSpec* frames = nullptr, bool sync_call = false, const MaskSpec* mask = nullptr) {
     akz_ctx* on = c;
     if (!sync_call && c && !c->lanes.empty() && (uint64_t)w * h * n < c->settings.lane_px) {
         AKZ_TRY(bind(c, false));
@@ -263,8 +278,9 @@ static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint
         if (frames) flags &= ~(uint32_t)AKZ_INPUT_READY;  // (the promise was about the caller's frames; the luma frames are complete behind `ready`)
         d_imgs = on->stage[slot].p;
     }
-    const int rc = is_u8 ? extract_begin<uint8_t>(on, (const uint8_t*)d_imgs, w, h, n, cfg, flags, out, slot, ready, sync_call)
-                         : extract_begin<float>(on, (const float*)d_imgs, w, h, n, cfg, flags, out, slot, ready, sync_call);
+    // (a mask travels with the job: on a lane its filter runs on the lane's stream, behind the lane_in wait above)
+    const int rc = is_u8 ? extract_begin<uint8_t>(on, (const uint8_t*)d_imgs, w, h, n, cfg, flags, out, slot, ready, sync_call, mask)
+                         : extract_begin<float>(on, (const float*)d_imgs, w, h, n, cfg, flags, out, slot, ready, sync_call, mask);
     // a job dealt to a lane is always finished by the lane's own thread (lanes whose jobs wait for the caller's finish call
     // measured SLOWER than no lanes: the chains overlap on the chip but the finish halves queue on one host thread)
     if (rc == AKZ_OK && !sync_call && (c->eager_finish || on != c)) finisher_post(on, *out);
@@ -272,14 +288,16 @@ static int extract_begin_dispatch(akz_ctx* c, const void* imgs, bool is_u8, uint
 }
 }  // extern "C"
 // akz_extract_device_frames / akz_extract_begin_device_frames (akz_frames_api.cpp, which has checked the layout)
-int extract_begin_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_job** out) {
-    if (fs.packed_gray()) return extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags, out);  // already what the extraction takes
-    return extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags, out, false, &fs);
+int extract_begin_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_job** out,
+                         const MaskSpec* mask) {
+    if (fs.packed_gray()) return extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags, out, false, nullptr, false, mask);  // already what the extraction takes
+    return extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags, out, false, &fs, false, mask);
 }
-int extract_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_result** out) {
-    if (fs.packed_gray()) return extract_impl<uint8_t>(c, d_src, fs.w, fs.h, n, cfg, flags, out);
+int extract_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_result** out,
+                   const MaskSpec* mask) {
+    if (fs.packed_gray()) return extract_impl<uint8_t>(c, d_src, fs.w, fs.h, n, cfg, flags, out, mask);
     akz_job* job = nullptr;
-    AKZ_TRY(extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags & ~(uint32_t)AKZ_INPUT_READY, &job, false, &fs, /*sync_call=*/true));
+    AKZ_TRY(extract_begin_dispatch(c, d_src, true, fs.w, fs.h, n, cfg, flags & ~(uint32_t)AKZ_INPUT_READY, &job, false, &fs, /*sync_call=*/true, mask));
     return extract_finish(job, out);
 }
 extern "C" {

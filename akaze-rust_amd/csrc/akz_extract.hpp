@@ -23,6 +23,12 @@ struct akz_result {
     std::vector<uint64_t> n_extrema;
 };
 
+// A job's detection mask on the device: height x width bytes per image, nonzero = detect here (akz_mask.hip); d == nullptr: none.
+struct MaskSpec {
+    const uint8_t* d = nullptr;
+    uint64_t row_pitch = 0, frame_stride = 0;  // bytes; frame_stride 0: one mask for every image of the batch
+};
+
 // An extraction in flight: everything up to the NMS candidates is enqueued on the context's
 // stream by extract_begin (no host synchronisation); extract_finish picks the candidates up on
 // the auxiliary stream once `nms_done` fires and runs the host keypoint logic, orientation and
@@ -49,6 +55,7 @@ struct akz_job {
     std::shared_ptr<std::atomic<int>> in_hand;
     bool alone_at_begin = true;
     hipStream_t done_stream = nullptr;  // the stream the begin chain ended on (the main stream, or the forked coarse chain's)
+    MaskSpec mask;            // the job's list is then c->cand_mask_slot[slot], what the mask keeps of c->cand_slot[slot]
     ~akz_job() {
         if (in_hand) --*in_hand;
     }
@@ -116,11 +123,16 @@ AKZ_LOCAL int place_lanes(akz_ctx* c);
 // ---- akz_extract_begin.cpp (instantiated for uint8_t and float) / akz_extract_finish.cpp ----
 template <typename T>
 AKZ_LOCAL int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t n, const akz_config* cfgp, uint32_t flags, akz_job** out,
-                            int want_slot = -1, hipEvent_t input_ready = nullptr, bool sync_call = false);
+                            int want_slot = -1, hipEvent_t input_ready = nullptr, bool sync_call = false, const MaskSpec* mask = nullptr);
+// launch::mask_candidates of job r on stream s, with its kernel row (AKZ_KR_MASK_CANDIDATES under AKZ_ST_NMS): c->cand_slot[slot] ->
+// c->cand_mask_slot[slot], which the caller has made `cap` records long
+AKZ_LOCAL int mask_enqueue(akz_ctx* c, hipStream_t s, const akz_result* r, const MaskSpec& m, int slot, uint32_t cap, uint32_t* d_count);
 // The finish half proper.  The job shell stays with the caller; on failure everything the job held is released.
 AKZ_LOCAL int extract_finish_body(akz_job* jobp, akz_result** out);
 // ---- akz_extract.cpp / akz_frames_api.cpp: device frames in a layout of the caller's (akz_frames.hpp) ----
-AKZ_LOCAL int extract_begin_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_job** out);
-AKZ_LOCAL int extract_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_result** out);
+AKZ_LOCAL int extract_begin_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_job** out,
+                                   const MaskSpec* mask = nullptr);
+AKZ_LOCAL int extract_frames(akz_ctx* c, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, const akz_config* cfg, uint32_t flags, akz_result** out,
+                             const MaskSpec* mask = nullptr);
 // k_frame_luma on stream s of context c, with its profile row (stage 10)
 AKZ_LOCAL int frames_enqueue(akz_ctx* c, hipStream_t s, const uint8_t* d_src, const FrameSpec& fs, uint32_t n, uint8_t* d_luma);

@@ -475,10 +475,22 @@ std::vector<std::pair<uint32_t, int>> begin_planes(size_t L, bool keep_all) {
 }
 }  // namespace
 
+int mask_enqueue(akz_ctx* c, hipStream_t s, const akz_result* r, const MaskSpec& m, int slot, uint32_t cap, uint32_t* d_count) {
+    const uint32_t L = (uint32_t)r->plan.size();
+    uint32_t lw[kMaxLevels], lh[kMaxLevels], lo[kMaxLevels];
+    for (uint32_t l = 0; l < L && l < (uint32_t)kMaxLevels; ++l) lw[l] = r->plan[l].w, lh[l] = r->plan[l].h, lo[l] = r->plan[l].octave;
+    StageTimer st(c, AKZ_ST_NMS, s);
+    st.kernel(AKZ_KR_MASK_CANDIDATES, m.frame_stride ? r->n : 1u, r->w, r->h, r->n, 1, cap);
+    launch::mask_candidates(s, (const Candidate*)c->cand_slot[slot].p, (Candidate*)c->cand_mask_slot[slot].p, cap, d_count, m.d, m.row_pitch,
+                            m.frame_stride, lw, lh, lo, L, r->n);
+    AKZ_HIP_TRY(hipGetLastError());
+    return AKZ_OK;
+}
+
 // open -> route -> level 0 -> fine levels -> pre_ev / fed_ev -> fork or not -> nms_done
 template <typename T>
 int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t n, const akz_config* cfgp, uint32_t flags, akz_job** out,
-                  int want_slot, hipEvent_t input_ready, bool sync_call) {
+                  int want_slot, hipEvent_t input_ready, bool sync_call, const MaskSpec* mask) {
     if (!out) return AKZ_ERR_INVALID_ARG;
     *out = nullptr;
     AKZ_TRY(bind(c, true, c && c->is_lane));  // (a lane's finish half shares the lane's one stream: begin waits for it)
@@ -511,6 +523,7 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     }
     AKZ_TRY(ensure(c, c->cand_slot[o.slot], (size_t)cap * sizeof(Candidate)));
     AKZ_TRY(ensure(c, c->count_slot[o.slot], 256));
+    if (mask) AKZ_TRY(ensure(c, c->cand_mask_slot[o.slot], (size_t)cap * sizeof(Candidate)));
     for (Event& e : c->fed_ev) AKZ_TRY(e.ensure());
     for (Event& e : c->pre_ev) AKZ_TRY(e.ensure());
     const uint64_t seq = c->begin_seq.load() + 1;  // published when this job's event has been recorded
@@ -554,6 +567,13 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     if (rt.fork_level < L) AKZ_TRY(fork_and_join(b, &done_on));
     else AKZ_TRY(detectors(b, 0, L, form));
     AKZ_HIP_TRY(hipGetLastError());
+    // The detection mask: the list every consumer reads -- the three sorts, k_relations, k_select, the speculative fetches, the host's
+    // selection -- is what the mask keeps of it, made behind the last detector and in front of the job's event.  (The mask may be the
+    // output of work queued earlier on the caller's stream: this point lies far behind the frames' own wait.)
+    if (mask) {
+        AKZ_TRY(mask_enqueue(c, done_on, r, *mask, o.slot, cap, b.d_count));
+        job->mask = *mask;
+    }
     job->nms_done = StageTimer::get(c);
     AKZ_HIP_TRY(hipEventRecord(job->nms_done, done_on));
     job->done_stream = done_on;
@@ -561,5 +581,5 @@ int extract_begin(akz_ctx* c, const T* d_imgs, uint32_t w, uint32_t h, uint32_t 
     *out = o.keep(cap);
     return AKZ_OK;
 }
-template int extract_begin<uint8_t>(akz_ctx*, const uint8_t*, uint32_t, uint32_t, uint32_t, const akz_config*, uint32_t, akz_job**, int, hipEvent_t, bool);
-template int extract_begin<float>(akz_ctx*, const float*, uint32_t, uint32_t, uint32_t, const akz_config*, uint32_t, akz_job**, int, hipEvent_t, bool);
+template int extract_begin<uint8_t>(akz_ctx*, const uint8_t*, uint32_t, uint32_t, uint32_t, const akz_config*, uint32_t, akz_job**, int, hipEvent_t, bool, const MaskSpec*);
+template int extract_begin<float>(akz_ctx*, const float*, uint32_t, uint32_t, uint32_t, const akz_config*, uint32_t, akz_job**, int, hipEvent_t, bool, const MaskSpec*);

@@ -119,7 +119,9 @@ struct FinishState {
     std::vector<std::pair<const Candidate*, size_t>> span;
     std::vector<std::vector<HostKeypoint>> hk;
     bool host_rows() const { return !(r->flags & AKZ_NO_HOST_DESCRIPTORS); }
-    const Candidate* d_unsorted() const { return (const Candidate*)c->cand_slot[job->slot].p; }
+    // the job's unordered list: the extrema pass's, or what the job's mask kept of it
+    const Candidate* d_unsorted() const { return (const Candidate*)(job->mask.d ? c->cand_mask_slot : c->cand_slot)[job->slot].p; }
+    uint32_t mask_redone = 0;  // NMS passes the overflow path redid for a masked job
 };
 
 // ensure_pinned may move the buffer: what a speculative fetch brought is kept across it
@@ -373,7 +375,9 @@ int fetch_candidates(FinishState& f) {
         AKZ_TRY(ensure_pinned(c, c->pin[PIN_COUNT_SUMS], 256));
         uint32_t* total_p = (uint32_t*)c->pin[PIN_COUNT_SUMS].p;
         const bool dev_fetch = attempt == 0 && f.dev_sel;  // (the device's selection brings the count with its headers)
-        if (!dev_fetch) AKZ_HIP_TRY(hipMemcpyAsync(total_p, f.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        const bool masked = job->mask.d != nullptr;  // (then the count word is the kept count and the next word the list's length before the mask)
+        if (!dev_fetch) AKZ_HIP_TRY(hipMemcpyAsync(total_p, f.d_count, (masked ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        else if (masked) AKZ_HIP_TRY(hipMemcpyAsync(total_p + 1, f.d_count + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         // Small jobs are bound by the latency of these round trips: fetch, with the count, as many candidates as the
         // previous job of this context had (+25 %) and the contrast factors, so that one synchronisation serves all.
         uint32_t spec = 0;
@@ -421,9 +425,17 @@ int fetch_candidates(FinishState& f) {
         }
         f.total_c = *total_p;
         if (attempt == 0) r->k_host.assign((const double*)c->pin[PIN_CONTRAST].p, (const double*)c->pin[PIN_CONTRAST].p + n);
-        c->last_total_cands = f.total_c;
+        // The capacity bookkeeping sees the list BEFORE the mask: that is what the next job's extrema pass appends (a stream of heavily
+        // masked frames would otherwise pick the short list every time and redo every extrema pass)
+        const uint32_t unfiltered = masked ? std::max(total_p[1], f.total_c) : f.total_c;
+        c->last_total_cands = unfiltered;
         c->last_cand_shape = f.shape;
-        c->cand_cap_hint = std::max(c->cand_cap_hint.load(), (uint32_t)((uint64_t)f.total_c * 5 / 4 / n) + 64u);
+        c->cand_cap_hint = std::max(c->cand_cap_hint.load(), (uint32_t)((uint64_t)unfiltered * 5 / 4 / n) + 64u);
+        if (masked) {
+            static std::atomic<uint64_t> stamp{0};
+            c->mask_last[0] = unfiltered, c->mask_last[1] = f.total_c, c->mask_last[2] = f.mask_redone;
+            c->mask_stamp = ++stamp;
+        }
         if (f.total_c > f.cap) {  // overflow: grow and redo the NMS pass alone on the stored Ldet planes (the host sorts that list)
             if (attempt >= 3) {
                 set_error("NMS candidate buffer overflow");
@@ -435,11 +447,16 @@ int fetch_candidates(FinishState& f) {
             f.d_rel = nullptr;  // (the lists belong to the truncated list)
             AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
             AKZ_TRY(ensure(c, c->cand_slot[job->slot], (size_t)f.cap * sizeof(Candidate)));
+            if (masked) AKZ_TRY(ensure(c, c->cand_mask_slot[job->slot], (size_t)f.cap * sizeof(Candidate)));
             AKZ_HIP_TRY(hipMemsetAsync(f.d_count, 0, sizeof(uint32_t), s));
             for (size_t l = 0; l < plan.size(); ++l)
                 launch::nms(s, r->planes[l][AKZ_LDET], plan[l].w, plan[l].h, n, (uint64_t)plan[l].w * plan[l].h, (uint32_t)l,
                             (float)r->cfg.detector_threshold, border_margin(plan[l], r->cfg), (Candidate*)c->cand_slot[job->slot].p, f.cap, f.d_count);
             AKZ_HIP_TRY(hipGetLastError());
+            if (masked) {  // the redone list goes through the mask like the first
+                AKZ_TRY(mask_enqueue(c, s, r, job->mask, job->slot, f.cap, f.d_count));
+                ++f.mask_redone;
+            }
             continue;
         }
         if (f.dev_sel) {

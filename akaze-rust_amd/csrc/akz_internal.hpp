@@ -344,6 +344,13 @@ void select_device(hipStream_t s, const Candidate* d_sorted, uint32_t cap, const
 // candidates of all images are appended to ONE list (d_count is a single counter, cap the list capacity)
 void nms(hipStream_t s, const float* ldet, uint32_t w, uint32_t h, uint32_t n, uint64_t img_stride, uint32_t level,
          float thr, float border_m, Candidate* d_cand, uint32_t cap, uint32_t* d_count);
+// The detection mask (akz_mask.hip): d_out = the records of d_in whose mask byte is nonzero, in any order.  d_cnt: four words, 8-byte aligned --
+// [0] the list's length on entry, the kept count on return (untouched if it exceeds cap: the first cap records are then copied
+// through), [1] the length on entry, [2], [3] the kernel's own (cleared here, in front of the launch).  row_pitch, frame_stride:
+// bytes of the mask; frame_stride 0 = one mask for all images.  d_out holds cap records and is not d_in.
+void mask_candidates(hipStream_t s, const Candidate* d_in, Candidate* d_out, uint32_t cap, uint32_t* d_cnt, const uint8_t* d_mask,
+                     uint64_t row_pitch, uint64_t frame_stride, const uint32_t* level_w, const uint32_t* level_h,
+                     const uint32_t* level_octave, uint32_t n_levels, uint32_t n_images);
 void orientation(hipStream_t s, const LevelTable& lt, const KpParam* d_kp, uint32_t nkp,
                  unsigned long long window_mask, uint32_t n_windows, OrientOut* d_out);
 // the same with the keypoint count still on the device (*d_nkp <= max_kp: the grid is sized for max_kp)

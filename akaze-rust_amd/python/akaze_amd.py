@@ -31,6 +31,7 @@ PLANES = ["Lt", "Lsmooth", "Lx", "Ly", "Lxx", "Lyy", "Lxy", "Lflow", "Lstep", "L
 # akz_frame_format
 FRAME_GRAY8, FRAME_RGB8, FRAME_BGR8, FRAME_RGBA8, FRAME_BGRA8, FRAME_RGB8_PLANAR = range(6)
 KR_FRAME_LUMA = 12  # akz_kernel_row.kind of k_frame_luma (stage 10)
+KR_MASK_CANDIDATES = 13  # ... of k_mask_candidates (stage 5, nms)
 
 
 class AkazeError(RuntimeError):
@@ -133,7 +134,7 @@ class KernelRow(C.Structure):
 
 KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march",
                     6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d", 9: "k_sort_rows", 10: "k_bucket_sort", 11: "rocprim_radix_sort",
-                    12: "k_frame_luma"}
+                    12: "k_frame_luma", 13: "k_mask_candidates"}
 
 
 class ScratchAudit(C.Structure):
@@ -290,6 +291,13 @@ def lib():
         "akz_luma_from_frames_device": ([vp, vp, C.POINTER(FrameLayout), u32, vp], i32),
         "akz_extract_device_frames": ([vp, vp, C.POINTER(FrameLayout), u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_begin_device_frames": ([vp, vp, C.POINTER(FrameLayout), u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
+        "akz_extract_device_frames_masked": ([vp, vp, C.POINTER(FrameLayout), u32, vp, C.POINTER(FrameLayout), u32, C.POINTER(Config), u32,
+                                              C.POINTER(vp)], i32),
+        "akz_extract_begin_device_frames_masked": ([vp, vp, C.POINTER(FrameLayout), u32, vp, C.POINTER(FrameLayout), u32, C.POINTER(Config),
+                                                    u32, C.POINTER(vp)], i32),
+        "akz_extract_gray_u8_masked": ([vp, vp, vp, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
+        "akz_debug_mask_candidates": ([vp, vp, u32, vp, vp, C.POINTER(FrameLayout), u32, u32, u32, C.POINTER(Config), u32, vp], i32),
+        "akz_debug_mask_counts": ([vp, pu64], i32),
         "akz_extract_begin_host_u8": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_begin_host_f32": ([vp, vp, u32, u32, u32, C.POINTER(Config), u32, C.POINTER(vp)], i32),
         "akz_extract_finish": ([vp, C.POINTER(vp)], i32),
@@ -468,6 +476,25 @@ def lib():
     return L
 
 
+def mask_layout_of(mask, n, h, w):
+    """(FrameLayout, n_masks) of a detection mask for n frames of h x w: a uint8 or bool array / torch tensor [H, W] (one mask for
+    every frame) or [N, H, W], any row and frame strides, dense pixels -- frame_layout_of(..., "hw").  ValueError on another dtype
+    or shape."""
+    dtype = str(getattr(mask, "dtype", None)).replace("torch.", "")
+    if dtype not in ("uint8", "bool"):
+        raise ValueError(f"a mask must be uint8 or bool, got {dtype}")
+    shape = tuple(int(v) for v in mask.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"a mask is [H, W] or [N, H, W], got {len(shape)} dimensions")
+    if shape[-2:] != (h, w):
+        raise ValueError(f"the mask is {shape[-1]} x {shape[-2]} but the frames are {w} x {h}")
+    if len(shape) == 3 and shape[0] != n:
+        raise ValueError(f"{shape[0]} masks for {n} frames (give one per frame, or one [H, W] mask for all)")
+    strides = mask.stride() if callable(getattr(mask, "stride", None)) else mask.strides  # (both dtypes have one-byte elements)
+    ml, n_masks, _ = frame_layout_of(shape, strides, "hw")
+    return ml, n_masks
+
+
 def debug_resource_counts():
     """akz_debug_resource_counts: what the library holds process-wide -> dict(device_blocks, device_bytes, pinned_blocks,
     pinned_bytes, events, streams)."""
@@ -529,6 +556,8 @@ def plan_levels(w, h, cfg=None):
 
 CANDIDATE_DTYPE = np.dtype([("level", "<u4"), ("idx", "<u4"), ("v", "<f4"), ("xp", "<f4"), ("xm", "<f4"),
                             ("yp", "<f4"), ("ym", "<f4"), ("_pad", "<u4")])
+# the same 32 bytes with the last word named for what the device's lists hold there: the image of the batch (akz_debug_mask_candidates)
+CANDIDATE_IMG_DTYPE = np.dtype(CANDIDATE_DTYPE.descr[:-1] + [("img", "<u4")])
 
 
 def host_select_keypoints(w, h, cfg, cands):
@@ -904,30 +933,83 @@ class Context:
         _check(lib().akz_luma_from_frames_device(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.c_void_p(out.data_ptr())))
         return out.view(shape)
 
-    def extract_frames(self, t, layout="hwc", order="rgb", options=None, keep_all_planes=True, host_descriptors=True):
+    def _device_mask(self, mask, n, fl):
+        import torch
+        if not (isinstance(mask, torch.Tensor) and mask.is_cuda):
+            raise ValueError("a device mask must be a uint8 or bool torch CUDA tensor")
+        return mask_layout_of(mask, n, fl.height, fl.width)
+
+    def extract_frames(self, t, layout="hwc", order="rgb", options=None, keep_all_planes=True, host_descriptors=True, mask=None):
         """akz_extract_device_frames: extract_features on the luma of colour, pitched or cropped device frames -- the
-        result of extract_features(luma_from_frames(t)), bit for bit.  Keypoint coordinates are relative to the view."""
+        result of extract_features(luma_from_frames(t)), bit for bit.  Keypoint coordinates are relative to the view.
+        mask (akz_extract_device_frames_masked): a uint8 or bool CUDA tensor [H, W] (shared) or [N, H, W], any row and frame
+        strides; nonzero = detect here.  Masked pixels raise no extrema candidates (include/akaze_hip.h)."""
         options = options or Config()
         flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS)
         fl, n, _ = self._device_frames(t, layout, order)
         res = C.c_void_p()
-        _check(lib().akz_extract_device_frames(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.byref(options), flags,
-                                               C.byref(res)))
+        if mask is None:
+            _check(lib().akz_extract_device_frames(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.byref(options), flags,
+                                                   C.byref(res)))
+        else:
+            ml, n_masks = self._device_mask(mask, n, fl)
+            _check(lib().akz_extract_device_frames_masked(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.c_void_p(mask.data_ptr()),
+                                                          C.byref(ml), n_masks, C.byref(options), flags, C.byref(res)))
         return ExtractResult(self, res)
 
     def extract_frames_begin(self, t, layout="hwc", order="rgb", options=None, keep_all_planes=True, host_descriptors=True,
-                             input_ready=False):
+                             input_ready=False, mask=None):
         """akz_extract_begin_device_frames: the first half of extract_frames, returning a Job without synchronising.
-        input_ready=True (AKZ_INPUT_READY): the frames are complete in device memory now; the conversion then runs on the
-        context's copy stream, under the kernels of the batch begun before.  The Job keeps the tensor alive."""
+        input_ready=True (AKZ_INPUT_READY): the frames (and the mask) are complete in device memory now; the conversion then
+        runs on the context's copy stream, under the kernels of the batch begun before.  mask: as extract_frames.  The Job keeps
+        the tensor and the mask alive."""
         options = options or Config()
         flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS) | \
                 (AKZ_INPUT_READY if input_ready else 0)
         fl, n, _ = self._device_frames(t, layout, order)
         job = C.c_void_p()
-        _check(lib().akz_extract_begin_device_frames(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.byref(options),
-                                                     flags, C.byref(job)))
-        return Job(self, job, t)
+        if mask is None:
+            _check(lib().akz_extract_begin_device_frames(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.byref(options),
+                                                         flags, C.byref(job)))
+            return Job(self, job, t)
+        ml, n_masks = self._device_mask(mask, n, fl)
+        _check(lib().akz_extract_begin_device_frames_masked(self._h, C.c_void_p(t.data_ptr()), C.byref(fl), n, C.c_void_p(mask.data_ptr()),
+                                                            C.byref(ml), n_masks, C.byref(options), flags, C.byref(job)))
+        return Job(self, job, (t, mask))
+
+    def extract_features_masked(self, image, mask, options=None, keep_all_planes=True):
+        """akz_extract_gray_u8_masked: extract_features of a HOST uint8 [H, W] image with a host mask of its size (uint8 or bool,
+        nonzero = detect here)."""
+        options = options or Config()
+        img = np.ascontiguousarray(image)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise ValueError("a masked host image must be a uint8 [H, W] array")
+        m = np.asarray(mask)
+        if m.dtype not in (np.uint8, np.bool_):
+            raise ValueError(f"a mask must be uint8 or bool, got {m.dtype}")
+        if m.shape != img.shape:
+            raise ValueError(f"the mask is {m.shape} but the image is {img.shape}")
+        m = np.ascontiguousarray(m).view(np.uint8)
+        res = C.c_void_p()
+        _check(lib().akz_extract_gray_u8_masked(self._h, img.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), img.shape[1],
+                                                img.shape[0], C.byref(options), AKZ_KEEP_ALL_PLANES if keep_all_planes else 0, C.byref(res)))
+        return ExtractResult(self, res)
+
+    def debug_mask_candidates(self, records, capacity, counts, mask, w, h, n, kept, options=None):
+        """akz_debug_mask_candidates: k_mask_candidates alone, enqueued on the context's stream.  records / kept: CUDA tensors of
+        capacity x 32 bytes (CANDIDATE_IMG_DTYPE); counts: a CUDA tensor of four int32 / uint32 words, [0] = the list's length; mask:
+        as extract_frames."""
+        options = options or Config()
+        ml, n_masks = mask_layout_of(mask, n, h, w)
+        _check(lib().akz_debug_mask_candidates(self._h, C.c_void_p(records.data_ptr()), capacity, C.c_void_p(counts.data_ptr()),
+                                               C.c_void_p(mask.data_ptr()), C.byref(ml), n_masks, w, h, C.byref(options), n,
+                                               C.c_void_p(kept.data_ptr())))
+
+    def debug_mask_counts(self):
+        """akz_debug_mask_counts of the last finished masked job -> dict(unfiltered, kept, redone)."""
+        out = (C.c_uint64 * 3)()
+        _check(lib().akz_debug_mask_counts(self._h, out))
+        return dict(unfiltered=int(out[0]), kept=int(out[1]), redone=int(out[2]))
 
     def extract_begin_host(self, frames, options=None, keep_all_planes=True, host_descriptors=True):
         """extract_begin for frames in HOST memory (akz_extract_begin_host_*): a numpy array or a torch CPU tensor
@@ -1578,10 +1660,14 @@ def default_context():
     return _default_ctx
 
 
-def extract_features(image, options=None, ctx=None):
+def extract_features(image, options=None, ctx=None, mask=None):
     """akaze::extract_features(image, options) -> (evolutions, keypoints, descriptors).
     `evolutions` is the ExtractResult (planes fetched lazily), keypoints a structured array,
-    descriptors an [n, 61] uint8 array."""
+    descriptors an [n, 61] uint8 array.  mask: a host uint8 / bool array of the image's size, nonzero = detect here
+    (akz_extract_gray_u8_masked; the image is then a host uint8 array)."""
+    if mask is not None:
+        r = (ctx or default_context()).extract_features_masked(image, mask, options)
+        return r, r.keypoints(0), r.descriptors(0)
     r = (ctx or default_context()).extract_features(image, options)
     return r, r.keypoints(0), r.descriptors(0)
 

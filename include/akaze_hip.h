@@ -286,6 +286,36 @@ int akz_extract_device_frames(akz_ctx* ctx, const uint8_t* d_src, const akz_fram
 int akz_extract_begin_device_frames(akz_ctx* ctx, const uint8_t* d_src, const akz_frame_layout* layout, uint32_t n,
                                     const akz_config* cfg, uint32_t flags, akz_job** out);
 
+/* ---- a detection mask: masked pixels raise no candidates ------------------------------ */
+/* The second argument of detectAndCompute.  A mask is height x width bytes per frame, the frame's own size; nonzero means
+   detect here (a torch bool tensor is this).  The pyramid, the contrast factor and every plane are untouched by it.  An
+   extrema candidate of level l (octave o, r = 1 << o) at level pixel (x, y) exists only if
+       mask[(y << o) + (r >> 1)][(x << o) + (r >> 1)] != 0
+   -- the rounded position the reference gives the unrefined keypoint (x r + 0.5 (r - 1), scale_space_extrema.rs:89-92), always
+   inside the frame.  A masked candidate never reaches the keypoint cache, like one the border test removes; so it suppresses
+   no neighbour, which a filter over the finished keypoints cannot undo.  Everything behind the candidate list is unchanged
+   (cache walk, second pass, sub-pixel step, orientation, descriptors): a keypoint may be refined up to one level pixel into a
+   masked pixel.  Cost: one 12-byte fill and one small launch per job, between the extrema pass and everything that reads
+   its list; calls without a mask enqueue and allocate nothing new.
+   mask_layout: format AKZ_FRAME_GRAY8, the frames' width and height; row_pitch and frame_stride are free, as for frames.
+   n_masks: 1 (one mask for every frame; its frame_stride is not looked at) or n.  d_mask == NULL together with mask_layout ==
+   NULL is the unmasked call.  The mask follows the frames' stream rules: without AKZ_INPUT_READY it may be the output of work
+   queued earlier on the context's stream, with it the promise covers the mask too; it must stay valid and unchanged until the
+   job is finished or abandoned.
+   Refusals (AKZ_ERR_INVALID_ARG, the field named in akz_last_error, nothing enqueued, *out = NULL), besides the frames' own:
+   exactly one of d_mask / mask_layout null; another format; another size; n_masks not 1 or n; a nonzero row_pitch or
+   frame_stride below its tight value.
+   f32 frames, akz_extract_from_planes and the file calls (akz_extract_features_file / _files) have no masked form. */
+int akz_extract_device_frames_masked(akz_ctx* ctx, const uint8_t* d_src, const akz_frame_layout* layout, uint32_t n,
+                                     const uint8_t* d_mask, const akz_frame_layout* mask_layout, uint32_t n_masks,
+                                     const akz_config* cfg, uint32_t flags, akz_result** out);
+int akz_extract_begin_device_frames_masked(akz_ctx* ctx, const uint8_t* d_src, const akz_frame_layout* layout, uint32_t n,
+                                           const uint8_t* d_mask, const akz_frame_layout* mask_layout, uint32_t n_masks,
+                                           const akz_config* cfg, uint32_t flags, akz_job** out);
+/* akz_extract_gray_u8 with a mask in HOST memory: w * h bytes, tight, uploaded with the frame (mask must not be NULL). */
+int akz_extract_gray_u8_masked(akz_ctx* ctx, const uint8_t* img, const uint8_t* mask, uint32_t w, uint32_t h,
+                               const akz_config* cfg, uint32_t flags, akz_result** out);
+
 /* ops::scale_space_extrema::detect_keypoints (scale_space_extrema.rs:199-203) and ops::descriptors::extract_descriptors
    (descriptors.rs:14-27) on evolutions the CALLER holds (the reference's `pub mod ops` takes `&[EvolutionStep]` that
    need not come from extract_features): planes = n_levels x 10 host pointers in akz_plane order (row-major f32 of the

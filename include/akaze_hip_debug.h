@@ -135,10 +135,13 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    profiling level): k_sort_rows (one launch), the four k_bucket_* launches, or the key / radix sort / gather chain around
    rocPRIM -- param 0, (w, h, n) = the frame and the batch, px = the list's capacity.
    The conversion of caller-held frames (akz_luma_from_frames_device, akz_extract_*_device_frames) adds one row of stage 10 per
-   launch: k_frame_luma, param = the akz_frame_format, (w, h, n) = the frames, px = output pixels. */
+   launch: k_frame_luma, param = the akz_frame_format, (w, h, n) = the frames, px = output pixels.
+   A masked extraction (akz_extract_*_masked) adds one row of stage AKZ_ST_NMS (5) per filter launch, timed with every stage
+   (profiling level 2): k_mask_candidates, param = masks (1: shared, else n), (w, h, n) = the frames, px = the list's capacity.
+   One launch per job, one more for every extrema pass the overflow path redid; unmasked jobs leave no such row. */
 enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5,
        AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8, AKZ_KR_SORT_ROWS = 9, AKZ_KR_SORT_BUCKETS = 10,
-       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12 };
+       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12, AKZ_KR_MASK_CANDIDATES = 13 };
 typedef struct akz_kernel_row {
     uint32_t stage, kind, param, w, h, n;
     uint64_t launches, px, px_steps;
@@ -186,6 +189,22 @@ int akz_debug_audit_scratch(akz_ctx* ctx, akz_scratch_audit* out, uint32_t cap, 
    akz_stream_create).  A context that is created, used and destroyed, its results freed, leaves all six where they were.  No GPU
    call, no context. */
 int akz_debug_resource_counts(uint64_t out[6]);
+/* Test hook: the detection mask's kernel alone (k_mask_candidates, csrc/akz_mask.hip), enqueued on the context's stream and not
+   synchronised.  d_records: a device list of the 32-byte records akz_host_select_keypoints documents, {u32 level, u32 flat_idx,
+   f32 v, xp, xm, yp, ym, u32 img}, in a buffer of `capacity` records; d_counts: four u32 on the device, 8-byte aligned, [0] = the
+   list's length on entry.  (w, h, cfg, n) give the level table, (d_mask, mask_layout, n_masks) the mask as akz_extract_device_frames_masked takes
+   it (same refusals; a null mask is refused).  On completion d_kept (capacity records, not d_records) holds the kept records
+   in any order, d_counts[0] the kept count and d_counts[1] the length on entry.  A length above the capacity leaves
+   d_counts[0] as it is, sets d_counts[1] to it and copies the first `capacity` records through unfiltered: the extraction's
+   overflow path then redoes the list with room.  d_counts[2], [3] are the kernel's own and zero afterwards.  A record whose
+   level, image or index lies outside the tables is dropped. */
+int akz_debug_mask_candidates(akz_ctx* ctx, const void* d_records, uint32_t capacity, uint32_t* d_counts, const uint8_t* d_mask,
+                              const akz_frame_layout* mask_layout, uint32_t n_masks, uint32_t w, uint32_t h, const akz_config* cfg,
+                              uint32_t n, void* d_kept);
+/* The last finished masked job of the context (or of its lanes, whichever finished last): out[0] = candidates before the mask,
+   out[1] = candidates kept, out[2] = extrema passes the overflow path redid (each followed by a filter launch of its own).
+   The capacity bookkeeping of the context (the next job's list size) is fed out[0], not out[1]. */
+int akz_debug_mask_counts(akz_ctx* ctx, uint64_t out[3]);
 
 /* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
    source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */
