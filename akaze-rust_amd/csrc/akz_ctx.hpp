@@ -710,6 +710,11 @@ struct GuidedStage {  // the second stage of akz_match_features_{homography,fund
     float radius;
     double ratio;
 };
+struct PoseStage {  // the pose stage of akz_match_features_seeded_pose_pairs: launch::pairs_pose after the refit (akz_pose.hip)
+    const akz_camera* d_cameras;  // two per pair (image 0, image 1), on the device (the front's own bytes)
+    akz_pose* poses;              // one per pair
+    float* points;                // 3 floats per slot of out, may be null
+};
 struct RefineStage {  // the refit stage of akz_match_features_{homography,fundamental}_refined(_pairs): launch::model_refit after the pick
     uint32_t max_iterations;
     uint32_t* iterations;  // one per pair, may be null
@@ -731,16 +736,22 @@ struct AKZ_LOCAL PairsFront {
     uint64_t* h_cnt = nullptr;                               // (read back; valid after the caller's synchronise)
     char *d_own = nullptr, *h_own = nullptr;
 };
-// The head of c->mp_keep and of its pinned image c->mp_pin_out: kept counts | models | found | accepted fits | trials run, then the
-// kept lists.  The caller sets the four byte counts (0: the field is absent), pairs_keep the rest.
+// The head of c->mp_keep and of its pinned image c->mp_pin_out: kept counts | models | found | accepted fits | trials run | poses |
+// points (3 floats per kept record, where want_points), then the kept lists.  The caller sets the five byte counts (0: the field is
+// absent) and want_points, pairs_keep the rest.
 struct PairsKeep {
     size_t b_model, b_found, b_fits, b_trials;
+    size_t b_pose = 0;
+    bool want_points = false;
+    size_t b_points = 0;
     size_t b_head = 0;
     uint64_t n_keep = 0;
     uint64_t* d_kcnt = nullptr;
     float* d_hm = nullptr;
     int32_t* d_hf = nullptr;
     uint32_t *d_it = nullptr, *d_tr = nullptr;
+    akz_pose* d_pose = nullptr;
+    float* d_points = nullptr;
     akz_match* d_keep = nullptr;
 };
 // akz_match_api.cpp.  pairs_open: the refusals (guided: those of the guided scan too), bind, the placement of every distinct set and
@@ -755,13 +766,13 @@ AKZ_LOCAL int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* s
                           size_t b_pin_own, PairsFront& f);
 AKZ_LOCAL int pairs_table_upload(akz_ctx* c, PairsFront& f);  // f.tab -> f.d_tab through f.h_tab
 AKZ_LOCAL int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k);
-// pairs_tail: launch::pairs_pick_filter over the trials' models and counts (d_mdl, d_inl), launch::model_refit given `refine`, the ONE
-// read-back of head and kept lists, the guided stage given `guided`, the synchronise, the copy-out and the intervals of a timed call
+// pairs_tail: launch::pairs_pick_filter over the trials' models and counts (d_mdl, d_inl), launch::model_refit given `refine`,
+// launch::pairs_pose given `pose`, the ONE read-back of head and kept lists, the guided stage given `guided`, the synchronise, the copy-out and the intervals of a timed call
 // (t_host: the caller's host time, interval 2).  model .. trials_run: one per pair, each may be null.
 AKZ_LOCAL int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const PairsFront& f, const PairsKeep& k,
                          launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine,
                          float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host, akz_match* out, uint64_t* n_out,
-                         float* model, int* found, uint32_t* fits, uint64_t* trials_run);
+                         float* model, int* found, uint32_t* fits, uint64_t* trials_run, const PoseStage* pose = nullptr);
 // the lists of a pairs call to out / n_out: pair p's guided list (h_gcnt[p] records at its fixed place in d_gout, fetched by ONE read-back
 // of the span such lists occupy) where h_gcnt is given and h_found is null or h_found[p] set, else its kept list (h_kcnt, h_keep, tab)
 AKZ_LOCAL int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const uint64_t* h_gcnt,
@@ -784,9 +795,15 @@ AKZ_LOCAL std::vector<GuidedPairSpec> guided_specs(const akz_feature_set* sets, 
 AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
                              int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
                              double lowes_ratio, akz_match* d_out, uint64_t* d_cnt);
-// akz_match_seeded_api.cpp: the seeded pairs call; cross: with cross(A, B) as every pair's raw list (akz_cross_api.cpp)
+// akz_match_seeded_api.cpp: the seeded pairs call; cross: with cross(A, B) as every pair's raw list (akz_cross_api.cpp); pose: with the
+// pose stage behind it (akz_pose_api.cpp)
+struct SeededPose {
+    const akz_camera* cameras;  // one per set, the caller's
+    akz_pose* poses;            // one per pair
+    float* points;              // may be null
+};
 AKZ_LOCAL int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
                                       uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                                      float* model, int* found, uint32_t* iterations, uint64_t* trials_run);
+                                      float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose = nullptr);
 // akz_extract_finish.cpp
 AKZ_LOCAL int device_libm_mode(akz_ctx* c);  // 0: host libm; 1 / 2: the device's FMA / SSE2 forms reproduce it (akz_libm.hpp)

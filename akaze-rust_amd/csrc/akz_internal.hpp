@@ -428,6 +428,15 @@ void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pa
 void model_refit(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw, const uint64_t* d_raw_cnt,
                       const float* d_pts, uint64_t pts_stride, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
                       void* d_keep, uint64_t* d_keep_cnt, float* d_h, const int32_t* d_found, uint32_t* d_iterations);
+// the pose stage after model_refit (akz_pose.hip; the statement: akz_pose.hpp), for a fundamental matrix that was handed back: per
+// pair with found = 1 the decomposition of E = K1^T F K0 from the model at d_f + 9 pair and the cameras d_cameras[2 pair] (image 0)
+// and d_cameras[2 pair + 1] (image 1), the cheirality counts of the four candidates over the KEPT list (coordinates from d_kx / d_ky
+// at kp0_off / kp1_off + the records' indices), the pose at d_poses[pair]; with a pose the kept list compacted in place to the matches
+// in front, its count rewritten, and (d_points != null) 3 floats per kept record at d_points + 3 keep_off.  A pair with found = 0
+// is left alone: its pose must be zero already.
+void pairs_pose(hipStream_t s, const PairJobHost* d_pairs, uint32_t n_pairs, const akz_camera* d_cameras,
+                const float* d_kx, const float* d_ky, const float* d_f, const int32_t* d_found, void* d_keep, uint64_t* d_keep_cnt,
+                akz_pose* d_poses, float* d_points);
 // The seeded pairs call (akz_match_seeded_api.cpp; the statement: akz_ransac_seeded.hpp).  seeded_round: round `round` of every pair
 // with d_done[pair] == 0 -- its trials draw their own samples from (k1, stream_base + pair, trial) -- into the pair's ring of
 // 128 models and counts.  seeded_update: per running pair the round's first maximum against d_best_inl / d_best_mdl (strictly

@@ -620,7 +620,8 @@ int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint6
 // room for the head and the kept lists of n_keep matches (PairsKeep, akz_ctx.hpp) on the device and in pinned memory
 int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k) {
     k.n_keep = n_keep;
-    k.b_head = f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials;
+    k.b_points = k.want_points ? up256((size_t)std::max<uint64_t>(n_keep, 1) * 12) : 0;
+    k.b_head = f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials + k.b_pose + k.b_points;
     const size_t b_keep = k.b_head + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
     AKZ_TRY(ensure(c, c->mp_keep, b_keep));
     AKZ_TRY(ensure_pinned(c, c->mp_pin_out, b_keep));
@@ -630,6 +631,8 @@ int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k) {
     k.d_hf = (int32_t*)(d + f.b_cnt + k.b_model);
     k.d_it = (uint32_t*)(d + f.b_cnt + k.b_model + k.b_found);
     k.d_tr = (uint32_t*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits);
+    k.d_pose = (akz_pose*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials);
+    k.d_points = (float*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials + k.b_pose);
     k.d_keep = (akz_match*)(d + k.b_head);
     return AKZ_OK;
 }
@@ -660,10 +663,12 @@ int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pair
 // The tail of the RANSAC pairs calls (akz_ctx.hpp).  launch::model_refit rewrites the models, the kept lists and their counts in place and
 // adds every pair's number of accepted fits to the head; the guided stage then scans every pair again with the model (H or F) that is on
 // the device (pairs without one give empty lists that nobody reads) over the sets the front uploaded.  Both stages need the head's models.
+// launch::pairs_pose, behind the refit, shrinks the kept lists in place to the matches in front of both cameras and fills the head's poses
+// and points (the seeded call alone asks for it, and refuses the guided stage with it).
 int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const PairsFront& f, const PairsKeep& k,
                launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine,
                float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host, akz_match* out, uint64_t* n_out, float* model,
-               int* found, uint32_t* fits, uint64_t* trials_run) {
+               int* found, uint32_t* fits, uint64_t* trials_run, const PoseStage* pose) {
     hipStream_t st = c->stream;
     launch::pairs_pick_filter(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, d_mdl, d_inl, epsilon_inliers, k.d_keep, k.d_kcnt,
                               k.b_model ? k.d_hm : nullptr, k.b_found ? k.d_hf : nullptr);
@@ -671,6 +676,11 @@ int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, u
     if (refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
         launch::model_refit(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, refit_epsilon, epsilon_inliers,
                             refine->max_iterations, k.d_keep, k.d_kcnt, k.d_hm, k.d_hf, k.d_it);
+        AKZ_HIP_TRY(hipGetLastError());
+    }
+    if (pose) {  // (inside the same interval; the kept lists shrink in place, so the one read-back below carries the final ones)
+        launch::pairs_pose(st, f.d_tab, (uint32_t)n_pairs, pose->d_cameras, f.d_kx, f.d_ky, k.d_hm, k.d_hf, k.d_keep, k.d_kcnt, k.d_pose,
+                           pose->points ? k.d_points : nullptr);
         AKZ_HIP_TRY(hipGetLastError());
     }
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
@@ -699,6 +709,18 @@ int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, u
         if (found) found[p] = h_hf[p];
         if (fits) fits[p] = h_it[p];
         if (trials_run) trials_run[p] = h_tr[p];
+    }
+    if (pose) {
+        const char* h_pose = head + f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials;
+        std::memcpy(pose->poses, h_pose, (size_t)n_pairs * sizeof(akz_pose));
+        if (pose->points) {  // (3 floats per kept record at the place of its list, to the place of that list in `out`)
+            const float* h_points = (const float*)(h_pose + k.b_pose);
+            uint64_t at = 0;
+            for (uint64_t p = 0; p < n_pairs; ++p) {
+                if (n_out[p] && pose->poses[p].found) std::memcpy(pose->points + 3 * at, h_points + 3 * f.tab[(size_t)p].keep_off, (size_t)n_out[p] * 12);
+                at += sets[pairs[2 * p]].n_descriptors;
+            }
+        }
     }
     if (f.timed) {  // akz_debug_match_pairs_split: [3] is the trials or the rounds, between the caller's events 3 and 4
         float ms[6] = {};

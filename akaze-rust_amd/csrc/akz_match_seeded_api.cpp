@@ -23,10 +23,12 @@ using namespace akz;
 
 // cross: every pair's raw list is cross(A, B) (akz_match_features_seeded_cross_pairs, akz_cross_api.cpp) -- pairs_scans also
 // writes the opposite direction and launch::pairs_cross_filter rewrites d_raw / d_cnt before anything reads them; clear, the call
-// enqueues what it always did.
+// enqueues what it always did.  pose: akz_match_features_seeded_pose_pairs (akz_pose_api.cpp, which has refused what that call refuses) --
+// the pairs' cameras ride behind done | need, the head carries the poses (zeroed with the fits and the trial counts) and the points, and
+// the tail runs launch::pairs_pose; null, nothing of it is allocated or enqueued.
 int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
                             uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                            float* model, int* found, uint32_t* iterations, uint64_t* trials_run) {
+                            float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose) {
     constexpr uint32_t kWindow = 8;  // rounds enqueued between two looks at the pairs still running
     AKZ_TRY(seeded_refuse_options(name, options));
     const akz_ransac_options& opt = *options;
@@ -53,9 +55,10 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     const bool stopping = opt.confidence > 0.0;
     const size_t b_done = up256((size_t)n_pairs * 4);
     const size_t b_need = stopping ? up256((size_t)n_pairs * kWindow * 4) : 0;  // one window of rounds per pair
-    PairsFront f;  // behind the pair table: done | need, on the device and (+ 256 for the count of pairs still running) in pinned memory
-    AKZ_TRY(pairs_front(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, out, n_out, opt.guided != 0, cross, b_done + b_need,
-                        b_done + b_need + 256, f));
+    const size_t b_cam = pose ? up256((size_t)n_pairs * 2 * sizeof(akz_camera)) : 0;
+    PairsFront f;  // behind the pair table: done | need | cameras, on the device and (+ 256 for the count of pairs still running, in front of the cameras) in pinned memory
+    AKZ_TRY(pairs_front(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, out, n_out, opt.guided != 0, cross,
+                        b_done + b_need + b_cam, b_done + b_need + 256 + b_cam, f));
     hipStream_t st = c->stream;
     // the rounds' state: every pair's best model and count, its ring of a round's models and counts, the running counts per round
     const size_t b_bm = up256((size_t)n_pairs * 36), b_bi = up256((size_t)n_pairs * 4);
@@ -104,10 +107,17 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     if (stopping) fill_need(0);
     double t_need = now_ms() - t_need0;
     PairsKeep keep{up256((size_t)n_pairs * 36), up256((size_t)n_pairs * 4), up256((size_t)n_pairs * 4), up256((size_t)n_pairs * 4)};
+    if (pose) keep.b_pose = up256((size_t)n_pairs * sizeof(akz_pose)), keep.want_points = pose->points != nullptr;
     AKZ_TRY(pairs_keep(c, f, n_keep, keep));
     AKZ_TRY(pairs_table_upload(c, f));
     AKZ_HIP_TRY(hipMemcpyAsync(d_done, h_done, b_done + b_need, hipMemcpyHostToDevice, st));
-    AKZ_HIP_TRY(hipMemsetAsync(keep.d_it, 0, keep.b_fits + keep.b_trials, st));
+    akz_camera* d_cam = (akz_camera*)(f.d_own + b_done + b_need);
+    if (pose) {
+        akz_camera* h_cam = (akz_camera*)(f.h_own + b_done + b_need + 256);
+        for (uint64_t p = 0; p < n_pairs; ++p) h_cam[2 * p] = pose->cameras[pairs[2 * p]], h_cam[2 * p + 1] = pose->cameras[pairs[2 * p + 1]];
+        AKZ_HIP_TRY(hipMemcpyAsync(d_cam, h_cam, (size_t)n_pairs * 2 * sizeof(akz_camera), hipMemcpyHostToDevice, st));
+    }
+    AKZ_HIP_TRY(hipMemsetAsync(keep.d_it, 0, keep.b_fits + keep.b_trials + keep.b_pose, st));  // (the poses: no pose where the stage leaves at once)
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
     const uint64_t k1 = seeded_seed_key(opt.seed[0], opt.seed[1]);
     for (uint32_t r = 0; r < n_rounds && n_running; ++r) {
@@ -130,8 +140,9 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[4], st));
     const RefineStage refine{opt.refine_iterations, nullptr};
     const GuidedStage guided{opt.guided_radius, opt.guided_lowes_ratio};
+    const PoseStage stage{d_cam, pose ? pose->poses : nullptr, pose ? pose->points : nullptr};
     return pairs_tail(c, sets, pairs, n_pairs, f, keep, kind, d_bm, d_bi, opt.epsilon_inliers, opt.refine_iterations > 0 ? &refine : nullptr, refit_epsilon,
-                      opt.guided ? &guided : nullptr, guided_kind, t_need, out, n_out, model, found, iterations, trials_run);
+                      opt.guided ? &guided : nullptr, guided_kind, t_need, out, n_out, model, found, iterations, trials_run, pose ? &stage : nullptr);
 }
 
 extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,

@@ -223,6 +223,49 @@ class RansacOptions(C.Structure):
         return o
 
 
+class Camera(C.Structure):
+    """akz_camera: a pinhole in pixels, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]; no skew, no distortion."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+    def matrix(self):
+        return np.array([[self.fx, 0.0, self.cx], [0.0, self.fy, self.cy], [0.0, 0.0, 1.0]])
+
+    @classmethod
+    def of(cls, k):
+        """a Camera, (fx, fy, cx, cy) or a 3 x 3 K (its skew entry is not read) -> Camera"""
+        if isinstance(k, cls):
+            return k
+        a = np.asarray(k, np.float64)
+        return cls(a[0, 0], a[1, 1], a[0, 2], a[1, 2]) if a.shape == (3, 3) else cls(*[float(v) for v in a.reshape(4)])
+
+
+class Pose(C.Structure):
+    """akz_pose: the relative pose of a pair (x1 = R x0 + t, |t| = 1) with the statement's by-products.  found = 0: no pose --
+    r, t and winner are zero."""
+    _fields_ = [("r", C.c_float * 9), ("t", C.c_float * 3), ("sigma", C.c_float * 3), ("in_front", C.c_uint32 * 4),
+                ("winner", C.c_uint32), ("found", C.c_int32)]
+
+    @property
+    def R(self):
+        return np.ctypeslib.as_array(self.r).reshape(3, 3)
+
+    @property
+    def T(self):
+        return np.ctypeslib.as_array(self.t)
+
+    @property
+    def singular_values(self):
+        return np.ctypeslib.as_array(self.sigma)
+
+    @property
+    def counts(self):
+        return np.ctypeslib.as_array(self.in_front)
+
+    def words(self):
+        """the record as 21 uint32 words (what the GPU call promises bit for bit)"""
+        return np.frombuffer(bytes(self), np.uint32).copy()
+
+
 _lib = None
 
 
@@ -393,6 +436,9 @@ def lib():
                                              C.POINTER(C.c_uint32), pu64], i32),
         "akz_match_features_seeded_cross_pairs": ([vp, vp, u64, vp, u64, u64, C.POINTER(RansacOptions), vp, pu64, fp, C.POINTER(i32),
                                                    C.POINTER(C.c_uint32), pu64], i32),
+        "akz_recover_pose_host": ([vp, u64, vp, u64, vp, u64, fp, C.POINTER(Camera), C.POINTER(Camera), vp, pu64, C.POINTER(Pose), fp], i32),
+        "akz_match_features_seeded_pose_pairs": ([vp, vp, u64, vp, vp, u64, u64, C.POINTER(RansacOptions), i32, vp, pu64, fp,
+                                                  C.POINTER(i32), C.POINTER(C.c_uint32), pu64, vp, fp], i32),
         "akz_descriptor_match_cross_host": ([vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross": ([vp, vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross_device": ([vp, vp, u64, vp, u64, u64, f64, vp, vp], i32),
@@ -1149,6 +1195,33 @@ class Context:
         fn = lib().akz_match_features_seeded_cross_pairs if cross_check else lib().akz_match_features_seeded_pairs
         _check(fn(*a.head, C.byref(opt), *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
         return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
+
+    def match_features_seeded_pose_pairs(self, features, cameras, pairs, options=None, cross_check=False, points=False):
+        """match_features_seeded_pairs with the pose stage behind it (akz_match_features_seeded_pose_pairs): cameras holds one
+        Camera (or (fx, fy, cx, cy), or a 3 x 3 K) per feature set.  Returns one (matches, model or None, accepted fits, trials
+        run, Pose) per pair -- with points=True a sixth entry, the [len(matches), 3] float32 structure in camera 0's frame at
+        |t| = 1, or None without a pose -- each equal to remove_outliers_seeded on that pair's raw list followed, where a model
+        was found, by recover_pose_host with that list and model.  options.guided and the homography kind are refused."""
+        a = _PairsArgs(self, features, pairs)
+        opt = options if options is not None else RansacOptions()
+        cams = (Camera * max(1, len(a.ks)))(*[Camera.of(k) for k in cameras])
+        if len(cameras) != len(a.ks):
+            raise ValueError(f"{len(a.ks)} feature sets but {len(cameras)} cameras")
+        tr = np.zeros(max(1, len(a.pr)), np.uint64)
+        poses = (Pose * max(1, len(a.pr)))()
+        pts = np.zeros((len(a.out), 3), np.float32) if points else None
+        _check(lib().akz_match_features_seeded_pose_pairs(*a.head[:3], C.cast(cams, C.c_void_p), *a.head[3:], C.byref(opt), int(bool(cross_check)),
+                                                          *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                          C.cast(poses, C.c_void_p), pts.ctypes.data_as(C.POINTER(C.c_float)) if points else None))
+        res, at = [], 0
+        for p, (m, h, it) in enumerate(a.lists_models_iterations()):
+            pose = Pose.from_buffer_copy(poses[p])
+            row = (m, h, it, int(tr[p]), pose)
+            if points:
+                row += (pts[at:at + len(m)].copy() if pose.found else None,)
+            res.append(row)
+            at += a.rows[p]
+        return res
 
     def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
         """Guided matching over many pairs in one call (akz_descriptor_match_guided_pairs): features and pairs as for
@@ -2179,6 +2252,42 @@ def match_features_seeded(keypoints_0, descriptors_0, keypoints_1, descriptors_1
     fits, trials run)."""
     return (ctx or default_context()).match_features_seeded_pairs([(keypoints_0, descriptors_0), (keypoints_1, descriptors_1)],
                                                                   [(0, 1)], options, cross_check=cross_check)[0]
+
+
+def recover_pose_host(keypoints_0, keypoints_1, matches, f, camera_0, camera_1, points=False):
+    """The relative pose behind a fundamental matrix on the host (akz_recover_pose_host; no GPU call): E = K1^T F K0, its four
+    (R, t) candidates, the one with the most matches in front of both cameras -> (the matches in front under it, in order -- the
+    input unchanged without a pose --, Pose) and, with points=True, the [kept, 3] float32 structure (None without a pose)."""
+    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    fm = np.ascontiguousarray(np.asarray(f, np.float32).reshape(9))
+    c0, c1 = Camera.of(camera_0), Camera.of(camera_1)
+    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
+    pts = np.zeros((max(1, len(m)), 3), np.float32) if points else None
+    n = C.c_uint64()
+    pose = Pose()
+    _check(lib().akz_recover_pose_host(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
+                                       m.ctypes.data_as(C.c_void_p), len(m), fm.ctypes.data_as(C.POINTER(C.c_float)), C.byref(c0), C.byref(c1),
+                                       out.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(pose),
+                                       pts.ctypes.data_as(C.POINTER(C.c_float)) if points else None))
+    if points:
+        return out[:n.value].copy(), pose, (pts[:n.value].copy() if pose.found else None)
+    return out[:n.value].copy(), pose
+
+
+def match_features_seeded_pose_pairs(features, cameras, pairs, options=None, ctx=None, cross_check=False, points=False):
+    """Context.match_features_seeded_pose_pairs on ctx (default: the default context)."""
+    return (ctx or default_context()).match_features_seeded_pose_pairs(features, cameras, pairs, options, cross_check=cross_check, points=points)
+
+
+def match_features_seeded_pose(keypoints_0, descriptors_0, camera_0, keypoints_1, descriptors_1, camera_1, options=None, ctx=None,
+                               cross_check=False, points=False):
+    """One pair through match_features_seeded_pose_pairs (its stream: options.stream_base) -> (matches, model or None, accepted
+    fits, trials run, Pose[, points])."""
+    return (ctx or default_context()).match_features_seeded_pose_pairs([(keypoints_0, descriptors_0), (keypoints_1, descriptors_1)],
+                                                                       [camera_0, camera_1], [(0, 1)], options, cross_check=cross_check,
+                                                                       points=points)[0]
 
 
 def _cross_pair(fn, first, d0, d1, distance_threshold, lowes_ratio):

@@ -994,6 +994,63 @@ int akz_match_features_seeded_cross_pairs(akz_ctx* ctx, const akz_feature_set* s
                                           uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
                                           uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */);
 
+/* ---- relative pose: R, t and a cheirality filter per pair (additions) ------------------------------------------
+   With known intrinsics, the step after a fundamental matrix: E = K1^T F K0, its four (R, t) candidates, the candidate that
+   puts the matches in front of both cameras, and the matches that are in front.  The statement (csrc/akz_pose.hpp, ONE source
+   for host and device; f64, no contraction, every sum of three terms is (t0 + t1) + t2):
+     camera: a pinhole in pixels, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]; no skew, no distortion.
+     E = K1^T (F K0) with F as every call here returns it (p1^T F p0 = 0 in pixels).
+     decomposition: the Hestenes rotations of the refit's rank-2 step on the three rows of E; the rotated rows are sigma_i v_i^T.
+       Rows ordered by norm descending, the first among equals first: sigma1 >= sigma2 >= sigma3, v1, v2.  No pose if sigma1 is
+       zero or not finite, or if !(sigma2 > AKZ_FUNDAMENTAL_REFIT_EPSILON sigma1) -- a zero model, a rank-1 F, a pure rotation in
+       exact data.  u1 = E v1 / sigma1, u2 = E v2 / sigma2, u3 = u1 x u2, v3 = v1 x v2 (U and V are proper), W = [[0, -1, 0],
+       [1, 0, 0], [0, 0, 1]], Ra = U W V^T, Rb = U W^T V^T, t = u3 / |u3|.  sigma3 is ignored: the unrefitted winner of
+       model_kind 1 is not of rank 2, and sigma[] tells how far off it is.
+     candidates, with x1 = R x0 + t:  0 = (Ra, +t), 1 = (Ra, -t), 2 = (Rb, +t), 3 = (Rb, -t).  (Which of the two rotations the
+       decomposition calls Ra follows from the signs its rotations leave on v1 and v2: another SVD may number the same four
+       candidates 3, 2, 1, 0.)
+     cheirality of a match under (R, t): a = ((x0 - cx0) / fx0, (y0 - cy0) / fy0, 1), b likewise in image 1, c = R a,
+       det = (c.c)(b.b) - (c.b)^2, n0 = (c.b)(b.t) - (c.t)(b.b), n1 = (c.c)(b.t) - (c.b)(c.t); in front iff det > 0 and n0 > 0
+       and n1 > 0 -- the signs of the depths lambda0 = n0 / det, lambda1 = n1 / det at which the two rays meet in the
+       least-squares sense.  A NaN passes nothing.
+     winner: the candidate with the most matches in front, the first among equals; a largest count of 0: no pose.
+     list: with a pose, the input matches in front under the winner, in input order; without one, the input unchanged.
+     points (optional): per kept match X = (lambda0 a + R^T (lambda1 b - t)) / 2 in camera 0's frame at the scale |t| = 1. */
+typedef struct akz_camera {
+    double fx, fy, cx, cy;
+} akz_camera;
+typedef struct akz_pose {
+    float r[9];           /* row-major */
+    float t[3];           /* unit norm */
+    float sigma[3];       /* sigma_i / sigma1 */
+    uint32_t in_front[4]; /* per candidate */
+    uint32_t winner;
+    int32_t found;        /* 0: r, t and winner are zero; sigma and in_front hold what was computed, else zeros */
+} akz_pose;
+/* The host statement: no GPU call, no context.  out must hold n_matches entries; points (3 floats per kept match, in list
+   order) may be NULL and is written only with a pose.  n_matches = 0: AKZ_OK with found 0.  Refusals (AKZ_ERR_INVALID_ARG,
+   nothing written): those of akz_refine_fundamental_matrix for the keypoint and match arguments; a NULL f, camera, pose or
+   n_out; a camera whose fx or fy is zero or whose fields are not finite. */
+int akz_recover_pose_host(const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
+                          const akz_match* matches, uint64_t n_matches, const float* f /* 9 */, const akz_camera* camera_0,
+                          const akz_camera* camera_1, akz_match* out, uint64_t* n_out, akz_pose* pose,
+                          float* points /* 3 x n_matches, may be NULL */);
+/* akz_match_features_seeded_pairs (cross_check != 0: akz_match_features_seeded_cross_pairs) with the pose stage behind it, all
+   on the GPU: ONE more launch in front of the one read-back.  Pair p equals akz_remove_outliers_seeded on its raw list followed,
+   where found = 1, by akz_recover_pose_host with that list, that model and cameras[pairs[2 p]], cameras[pairs[2 p + 1]], bit for
+   bit: the list, the model, found, iterations, trials_run, every field of the pose and the points.  Where found = 0 (fewer than
+   8 matches among them) the seeded call's result stands and the pose is all zeros.  points: 3 floats per slot of out at the
+   same offsets (pair p's k-th kept match at 3 (offset of pair p + k)); may be NULL.
+   Refusals (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written): everything the seeded call refuses; model_kind
+   AKZ_GUIDED_HOMOGRAPHY; guided != 0 (a guided rescan behind a pose is later work); NULL cameras or poses; a camera that
+   akz_recover_pose_host refuses among the n_sets. */
+int akz_match_features_seeded_pose_pairs(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets,
+                                         const akz_camera* cameras /* n_sets */, const uint64_t* pairs, uint64_t n_pairs,
+                                         uint64_t desc_bytes, const akz_ransac_options* options, int cross_check, akz_match* out,
+                                         uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
+                                         uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */,
+                                         akz_pose* poses /* n_pairs */, float* points /* 3 per slot of out, may be NULL */);
+
 /* ---- k-nearest-neighbour matching: the k best train rows of every query, with their distances (additions) -----------
    For descriptor sets A (n0 rows) and B (n1 rows), 1 <= k <= AKZ_KNN_MAX_K and a distance_threshold, knn(A, B, k, threshold) is,
    for every row i of A:
