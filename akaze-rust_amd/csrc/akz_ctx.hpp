@@ -416,7 +416,7 @@ struct akz_ctx : CtxOwned {
     std::mutex slab_m;                  // guards slab_pool: results are freed by the caller while a lane's finisher thread allocates
     std::atomic<bool> slot_busy[kSlots] = {{false}, {false}, {false}};  // (begin on the caller's thread, finish possibly on the finisher's)
     std::atomic<uint32_t> cand_cap_hint{1u << 15};  // grows to 1.25x the largest candidate count seen
-    std::atomic<int> live_results{0};   // akz_result objects (also inside jobs) that still point at this context
+    std::atomic<int> live_results{0};   // akz_result objects (also inside jobs) and akz_bank objects that still point at this context
     bool dead = false;                  // akz_ctx_destroy was called; the struct lives until the last result is freed
     std::atomic<uint32_t> last_total_cands{0};  // candidates of the previous finished job (speculative fetch size)
     std::atomic<uint64_t> last_cand_shape{0};   // ... and its shape (akz_extract.hpp: shape_key)
@@ -754,16 +754,33 @@ struct PairsKeep {
     float* d_points = nullptr;
     akz_match* d_keep = nullptr;
 };
+// A feature bank (akz_bank_api.cpp; include/akaze_hip.h): feature sets resident on the device in the layout the pairs calls scan --
+// `dev` = rows | x | y, the parts on 256 bytes as in c->mp_in, set k's rows and coordinates from row set_row[k] on.  Immutable once
+// created.  It owns `dev` and counts among its context's live objects (akz_ctx::live_results), as a result does.
+struct akz_bank {
+    akz_ctx* ctx = nullptr;
+    uint64_t desc_bytes = 0, rows = 0;
+    std::vector<akz_feature_set> sets;  // the counts of every set; both pointers null
+    std::vector<uint64_t> set_row;
+    DevBuf dev;
+    uint8_t* d_rows = nullptr;
+    float *d_kx = nullptr, *d_ky = nullptr;
+};
 // akz_match_api.cpp.  pairs_open: the refusals (guided: those of the guided scan too), bind, the placement of every distinct set and
 // the room for its rows.  pairs_front: pairs_open, the upload, the scans (cross: both directions and launch::pairs_cross_filter), the
 // table, launch::pair_points and the enqueued read-back of the counts -- it does not synchronise.  b_dev_own / b_pin_own: the caller's
 // bytes behind the table in c->mp_tab and behind the counts in c->mp_pin_tab.
+// bank (pairs_front; `sets` are then the bank's counts): the opening is pairs_open_bank -- the refusals a bank leaves to make, bind, and
+// f's rows, x, y and set_row are the bank's own; nothing is placed or uploaded and c->mp_in / c->mp_pin_in are not touched.  Null: the
+// call enqueues what it always did.
 AKZ_LOCAL int pairs_open(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                          uint64_t desc_bytes, const void* out, const void* n_out, bool guided, PairsFront& f);
+AKZ_LOCAL int pairs_open_bank(const char* name, akz_ctx* c, const akz_bank* bank, const uint64_t* pairs, uint64_t n_pairs, const void* out,
+                              const void* n_out, bool guided, PairsFront& f);
 AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const PairsFront& f);
 AKZ_LOCAL int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                           uint64_t desc_bytes, double lowes_ratio, const void* out, const void* n_out, bool guided, bool cross, size_t b_dev_own,
-                          size_t b_pin_own, PairsFront& f);
+                          size_t b_pin_own, PairsFront& f, const akz_bank* bank = nullptr);
 AKZ_LOCAL int pairs_table_upload(akz_ctx* c, PairsFront& f);  // f.tab -> f.d_tab through f.h_tab
 AKZ_LOCAL int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k);
 // pairs_tail: launch::pairs_pick_filter over the trials' models and counts (d_mdl, d_inl), launch::model_refit given `refine`,
@@ -804,6 +821,10 @@ struct SeededPose {
 };
 AKZ_LOCAL int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
                                       uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                                      float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose = nullptr);
+                                      float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose = nullptr,
+                                      const akz_bank* bank = nullptr);  // bank: sets, n_sets and desc_bytes are the bank's (pairs_front)
+// akz_pose_api.cpp: the refusals of akz_match_features_seeded_pose_pairs that are not the seeded call's
+AKZ_LOCAL int pose_pairs_refusals(const char* name, const akz_ransac_options* options, const akz_camera* cameras, uint64_t n_sets,
+                                  const akz_pose* poses);
 // akz_extract_finish.cpp
 AKZ_LOCAL int device_libm_mode(akz_ctx* c);  // 0: host libm; 1 / 2: the device's FMA / SSE2 forms reproduce it (akz_libm.hpp)

@@ -510,6 +510,16 @@ void pairs_cross_filter(hipStream_t s, const CrossJobHost* d_tab, uint32_t n_pai
 // the same for one pair whose record travels with the launch (no table on the device)
 void pair_cross_filter(hipStream_t s, const CrossJobHost& job, akz_match* d_fwd, uint64_t* d_fwd_cnt, const akz_match* d_rev,
                        const uint64_t* d_rev_cnt);
+// the feature bank's gather (akz_bank.hip, k_bank_gather): n_seg segments of 64-byte rows -- n_rows rows at src_rows to the rows
+// from dst_row0 on of d_dst -- in ONE launch; dst_row0 ascends, segment s + 1 starts where s ends (0-row segments included),
+// total_rows is their sum.  Bytes of a row at or beyond desc_bytes are stored as zero.
+struct BankSeg {
+    const uint8_t* src_rows;
+    uint64_t n_rows, dst_row0;
+};
+static_assert(sizeof(BankSeg) == 24, "the device reads 24-byte segment records");
+constexpr uint64_t kBankMaxRows = 0x7fffffffull * 64;  // (a launch's workgroups, at no fewer than 64 rows each)
+void bank_gather(hipStream_t s, const BankSeg* d_tab, uint32_t n_seg, uint64_t total_rows, uint32_t desc_bytes, uint8_t* d_dst);
 // k-nearest-neighbour matching (akz_knn.hip): q4 / t4 are the FP4 images of unpack_pair(fp4); `chunks` from knn_chunks (forced: the
 // test hook, 0 = automatic; never fewer than the row field of a key allows); d_part: knn_part_bytes bytes of partial lists.
 // Writes k records per query and its count (all padding for n1 == 0); false: arguments or a retuned tile the kernel was not built for.

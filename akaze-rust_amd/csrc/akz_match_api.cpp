@@ -562,6 +562,45 @@ int pairs_open(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64
     f.d_kx = (float*)(f.d_rows + f.b_rows), f.d_ky = (float*)(f.d_rows + f.b_rows + f.b_xy);
     return AKZ_OK;
 }
+// The opening of a bank call (akz_ctx.hpp): what pairs_validate refuses of a set was refused when the bank was made, so the refusals
+// left are the call's own -- no GPU work before the last of them -- and the layout is the bank's, every set placed whether a pair
+// names it or not.
+int pairs_open_bank(const char* name, akz_ctx* c, const akz_bank* bank, const uint64_t* pairs, uint64_t n_pairs, const void* out,
+                    const void* n_out, bool guided, PairsFront& f) {
+    auto refuse = [name](const std::string& msg) {
+        set_error(name + msg);
+        return AKZ_ERR_INVALID_ARG;
+    };
+    if (!bank) return refuse("null bank");
+    if (!pairs || !n_out) return refuse("null pairs or n_out");
+    const uint64_t n_sets = bank->sets.size();
+    std::vector<uint8_t> seen((size_t)n_sets, 0);
+    uint64_t cap = 0;
+    for (uint64_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const uint64_t k = pairs[2 * p + side];
+            if (k >= n_sets)
+                return refuse("pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(n_sets));
+            if (side == 0) cap += bank->sets[(size_t)k].n_descriptors;
+            seen[(size_t)k] = 1;
+        }
+    if (cap && !out) return refuse("null out");
+    if (!c) return refuse("null context");
+    if (bank->ctx != c) return refuse("the bank belongs to another context");
+    if (guided) {
+        AKZ_TRY(guided_limits(name, bank->sets.data(), pairs, n_pairs, seen));
+        if (bank->rows > 0xffffffffull) return refuse("too many rows in the bank for one guided launch");  // (its records carry absolute rows)
+    }
+    AKZ_TRY(bind(c, true, false));
+    f.set_row = bank->set_row;
+    f.used.clear();
+    f.rows = bank->rows;
+    f.cap1 = std::max<uint64_t>(cap, 1);
+    const uint64_t rows1 = std::max<uint64_t>(f.rows, 1);
+    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4), f.b_cnt = up256((size_t)n_pairs * 8);
+    f.d_rows = bank->d_rows, f.d_kx = bank->d_kx, f.d_ky = bank->d_ky;
+    return AKZ_OK;
+}
 int pairs_table_upload(akz_ctx* c, PairsFront& f) {
     std::memcpy(f.h_tab, f.tab.data(), f.tab.size() * sizeof(launch::PairJobHost));
     AKZ_HIP_TRY(hipMemcpyAsync(f.d_tab, f.h_tab, f.tab.size() * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, c->stream));
@@ -572,8 +611,9 @@ int pairs_table_upload(akz_ctx* c, PairsFront& f) {
 // anything reads them); the pair table; k_pair_points; the read-back of the match counts, which the caller waits for.
 int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                 uint64_t desc_bytes, double lowes_ratio, const void* out, const void* n_out, bool guided, bool cross, size_t b_dev_own,
-                size_t b_pin_own, PairsFront& f) {
-    AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, guided, f));
+                size_t b_pin_own, PairsFront& f, const akz_bank* bank) {
+    if (bank) AKZ_TRY(pairs_open_bank(name, c, bank, pairs, n_pairs, out, n_out, guided, f));
+    else AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, guided, f));
     f.timed = c->mp_split_on;
     if (f.timed)
         for (Event& e : c->mp_split_ev) AKZ_TRY(e.ensure(hipEventDefault));
@@ -591,7 +631,7 @@ int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint6
     f.h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
     f.h_own = (char*)c->mp_pin_tab.p + b_tab + f.b_cnt;
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
-    AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));
+    if (!bank) AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));  // (a bank's sets are where the scans read them)
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
     if (cross) {  // the reverse lists (room: every pair's second set), their counts and the filter's records
         uint64_t cap_rev = 0;

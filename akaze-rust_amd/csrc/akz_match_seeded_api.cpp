@@ -25,10 +25,11 @@ using namespace akz;
 // writes the opposite direction and launch::pairs_cross_filter rewrites d_raw / d_cnt before anything reads them; clear, the call
 // enqueues what it always did.  pose: akz_match_features_seeded_pose_pairs (akz_pose_api.cpp, which has refused what that call refuses) --
 // the pairs' cameras ride behind done | need, the head carries the poses (zeroed with the fits and the trial counts) and the points, and
-// the tail runs launch::pairs_pose; null, nothing of it is allocated or enqueued.
+// the tail runs launch::pairs_pose; null, nothing of it is allocated or enqueued.  bank: the sets lie in a feature bank (akz_bank_api.cpp) --
+// the front opens on its buffers and uploads no set; everything else is the same code over the same table.
 int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
                             uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                            float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose) {
+                            float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose, const akz_bank* bank) {
     constexpr uint32_t kWindow = 8;  // rounds enqueued between two looks at the pairs still running
     AKZ_TRY(seeded_refuse_options(name, options));
     const akz_ransac_options& opt = *options;
@@ -58,7 +59,7 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     const size_t b_cam = pose ? up256((size_t)n_pairs * 2 * sizeof(akz_camera)) : 0;
     PairsFront f;  // behind the pair table: done | need | cameras, on the device and (+ 256 for the count of pairs still running, in front of the cameras) in pinned memory
     AKZ_TRY(pairs_front(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, out, n_out, opt.guided != 0, cross,
-                        b_done + b_need + b_cam, b_done + b_need + 256 + b_cam, f));
+                        b_done + b_need + b_cam, b_done + b_need + 256 + b_cam, f, bank));
     hipStream_t st = c->stream;
     // the rounds' state: every pair's best model and count, its ring of a round's models and counts, the running counts per round
     const size_t b_bm = up256((size_t)n_pairs * 36), b_bi = up256((size_t)n_pairs * 4);

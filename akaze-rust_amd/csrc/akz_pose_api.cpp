@@ -72,18 +72,24 @@ extern "C" int akz_recover_pose_host(const akz_keypoint* keypoints_0, uint64_t n
     return AKZ_OK;
 }
 
-extern "C" int akz_match_features_seeded_pose_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_camera* cameras,
-                                                    const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
-                                                    const akz_ransac_options* options, int cross_check, akz_match* out, uint64_t* n_out,
-                                                    float* model, int* found, uint32_t* iterations, uint64_t* trials_run, akz_pose* poses,
-                                                    float* points) {
-    const char* name = "match_features_seeded_pose_pairs: ";
+// what the pose forms of the seeded pairs calls refuse of their own, in front of the seeded call's refusals (the bank form too: akz_bank_api.cpp)
+int pose_pairs_refusals(const char* name, const akz_ransac_options* options, const akz_camera* cameras, uint64_t n_sets, const akz_pose* poses) {
     AKZ_TRY(seeded_refuse_options(name, options));
     if (options->model_kind == AKZ_GUIDED_HOMOGRAPHY) return refuse(std::string(name) + "a pose needs a fundamental matrix (model_kind 1 or 3)");
     if (options->guided != 0) return refuse(std::string(name) + "the guided stage behind a pose is not there yet: guided must be 0");
     if (!cameras || !poses) return refuse(std::string(name) + "null cameras or poses");
     for (uint64_t s = 0; s < n_sets; ++s)
         if (!camera_ok(cameras[s])) return refuse(std::string(name) + "camera " + std::to_string(s) + " needs finite fields and fx, fy != 0");
+    return AKZ_OK;
+}
+
+extern "C" int akz_match_features_seeded_pose_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_camera* cameras,
+                                                    const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
+                                                    const akz_ransac_options* options, int cross_check, akz_match* out, uint64_t* n_out,
+                                                    float* model, int* found, uint32_t* iterations, uint64_t* trials_run, akz_pose* poses,
+                                                    float* points) {
+    const char* name = "match_features_seeded_pose_pairs: ";
+    AKZ_TRY(pose_pairs_refusals(name, options, cameras, n_sets, poses));
     const SeededPose pose{cameras, poses, points};
     return match_seeded_pairs_impl(name, cross_check != 0, c, sets, n_sets, pairs, n_pairs, desc_bytes, options, out, n_out, model, found, iterations,
                                    trials_run, &pose);

@@ -134,7 +134,7 @@ class KernelRow(C.Structure):
 
 KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march",
                     6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d", 9: "k_sort_rows", 10: "k_bucket_sort", 11: "rocprim_radix_sort",
-                    12: "k_frame_luma", 13: "k_mask_candidates"}
+                    12: "k_frame_luma", 13: "k_mask_candidates", 14: "k_bank_gather"}
 
 
 class ScratchAudit(C.Structure):
@@ -439,6 +439,17 @@ def lib():
         "akz_recover_pose_host": ([vp, u64, vp, u64, vp, u64, fp, C.POINTER(Camera), C.POINTER(Camera), vp, pu64, C.POINTER(Pose), fp], i32),
         "akz_match_features_seeded_pose_pairs": ([vp, vp, u64, vp, vp, u64, u64, C.POINTER(RansacOptions), i32, vp, pu64, fp,
                                                   C.POINTER(i32), C.POINTER(C.c_uint32), pu64, vp, fp], i32),
+        "akz_bank_create_from_results": ([vp, C.POINTER(vp), u64, C.POINTER(vp)], i32),
+        "akz_bank_create_from_sets": ([vp, vp, u64, u64, C.POINTER(vp)], i32),
+        "akz_bank_info": ([vp, pu64, pu64, pu64], i32),
+        "akz_bank_set_info": ([vp, u64, pu64, pu64, pu64], i32),
+        "akz_bank_device": ([vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)], i32),
+        "akz_bank_free": ([vp], i32),
+        "akz_match_features_seeded_bank_pairs": ([vp, vp, vp, u64, C.POINTER(RansacOptions), i32, vp, pu64, fp, C.POINTER(i32),
+                                                  C.POINTER(C.c_uint32), pu64], i32),
+        "akz_match_features_seeded_pose_bank_pairs": ([vp, vp, vp, vp, u64, C.POINTER(RansacOptions), i32, vp, pu64, fp, C.POINTER(i32),
+                                                       C.POINTER(C.c_uint32), pu64, vp, fp], i32),
+        "akz_debug_bank_gather": ([vp, vp, u64, u64, vp], i32),
         "akz_descriptor_match_cross_host": ([vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross": ([vp, vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross_device": ([vp, vp, u64, vp, u64, u64, f64, vp, vp], i32),
@@ -628,7 +639,25 @@ class _PairsArgs:
     """What the pairs calls share: the akz_feature_set array, the pair list and the outputs (head: ctx, sets, n_sets, pairs,
     n_pairs, desc_bytes; tail: out, n_out), and the split of `out` into one list per pair afterwards."""
 
-    def __init__(self, ctx, features, pairs):
+    def __init__(self, ctx, features, pairs, bank_ok=False):
+        self.bank = features if isinstance(features, FeatureBank) else None
+        if self.bank is not None and not bank_ok:
+            raise TypeError("this call takes host feature sets; a FeatureBank goes to the seeded pairs calls")
+        if self.bank is not None and self.bank.ctx is not ctx:
+            raise ValueError("the FeatureBank belongs to another context")
+        if self.bank is not None:  # (head: ctx, bank, pairs, n_pairs -- the sets stay where they are)
+            info = self.bank.info()
+            self.n_sets = info["n_sets"]
+            self.pr = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
+            # (an index beyond the bank is the library's to refuse: it gets no room here)
+            self.rows = [info["sets"][int(a)]["n_descriptors"] if int(a) < self.n_sets else 0 for a in self.pr[:, 0]]
+            self.out = np.zeros(max(1, sum(self.rows)), MATCH_DTYPE)
+            self.n = np.zeros(max(1, len(self.pr)), np.uint64)
+            self.head = (ctx._h, self.bank._h, self.pr.ctypes.data_as(C.c_void_p), len(self.pr))
+            self.tail = (self.out.ctypes.data_as(C.c_void_p), self.n.ctypes.data_as(C.POINTER(C.c_uint64)))
+            return
+        if isinstance(features, (str, bytes)) or not hasattr(features, "__iter__"):
+            raise TypeError(f"features must be a FeatureBank or a sequence of (keypoints, descriptors), got {type(features).__name__}")
         self.ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
         self.ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
         nbs = {d.shape[1] for d in self.ds if d.ndim == 2 and len(d)}
@@ -644,6 +673,7 @@ class _PairsArgs:
         if len(self.ks) == 0 and len(self.pr):
             raise IndexError("pair refers to a set that does not exist")
         self.rows = [len(self.ds[int(a)]) if self.ds[int(a)].ndim == 2 else 0 for a in self.pr[:, 0]] if len(self.ks) else []
+        self.n_sets = len(self.ks)
         self.out = np.zeros(max(1, sum(self.rows)), MATCH_DTYPE)
         self.n = np.zeros(max(1, len(self.pr)), np.uint64)
         self.head = (ctx._h, C.cast(self.sets, C.c_void_p), len(self.ks), self.pr.ctypes.data_as(C.c_void_p), len(self.pr), nb)
@@ -1181,6 +1211,47 @@ class Context:
                                                                          *a.refined()))
         return a.lists_models_iterations()
 
+    def feature_bank(self, results_or_features):
+        """A FeatureBank of this context: feature sets kept on the device in the layout the pairs calls scan.  From one
+        ExtractResult or a sequence of them (akz_bank_create_from_results: every image of every result is a set, in order; the
+        descriptor rows never leave the device, and the results may be closed at once), or from a sequence of (keypoints,
+        descriptors) host sets (akz_bank_create_from_sets: packed and uploaded once).  Pass it as `features` to
+        match_features_seeded_pairs / match_features_seeded_pose_pairs; close() it when done."""
+        src = results_or_features
+        if isinstance(src, ExtractResult):
+            src = [src]
+        if isinstance(src, (str, bytes, FeatureBank)) or not hasattr(src, "__len__"):
+            raise TypeError(f"feature_bank takes ExtractResult objects or (keypoints, descriptors) sets, got {type(src).__name__}")
+        h = C.c_void_p()
+        if len(src) and all(isinstance(r, ExtractResult) for r in src):
+            arr = (C.c_void_p * len(src))(*[r._h for r in src])
+            _check(lib().akz_bank_create_from_results(self._h, arr, len(src), C.byref(h)))
+            return FeatureBank(self, h)
+        if any(isinstance(r, ExtractResult) for r in src):
+            raise TypeError("feature_bank takes results or host sets, not a mixture")
+        for f in src:
+            if not (isinstance(f, (tuple, list)) and len(f) == 2):
+                raise TypeError(f"a host set is (keypoints, descriptors), got {type(f).__name__}")
+        ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in src]
+        ds = [np.ascontiguousarray(d, np.uint8) for _, d in src]
+        nbs = {d.shape[1] for d in ds if d.ndim == 2 and len(d)}
+        if len(nbs) > 1:
+            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
+        nb = nbs.pop() if nbs else 61
+        sets = (FeatureSet * max(1, len(ks)))()
+        for i, (k, d) in enumerate(zip(ks, ds)):
+            nd = len(d) if d.ndim == 2 else 0
+            sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), d.ctypes.data_as(C.c_void_p) if nd else None, nd)
+        _check(lib().akz_bank_create_from_sets(self._h, C.cast(sets, C.c_void_p), len(ks), nb, C.byref(h)))
+        return FeatureBank(self, h)
+
+    def debug_bank_gather(self, src, desc_bytes, dst):
+        """akz_debug_bank_gather: k_bank_gather alone over the rows of the torch CUDA uint8 tensor src [rows, 64] into dst (same shape);
+        complete on return."""
+        import torch
+        torch.cuda.current_stream(src.device).synchronize()
+        _check(lib().akz_debug_bank_gather(self._h, C.c_void_p(src.data_ptr()), int(src.shape[0]), int(desc_bytes), C.c_void_p(dst.data_ptr())))
+
     def match_features_seeded_pairs(self, features, pairs, options=None, cross_check=False):
         """match_features over many pairs with the seeded RANSAC (akz_match_features_seeded_pairs): the trial kernel draws its
         own samples from (options.seed, options.stream_base + pair, trial) and options.confidence stops a pair's trials on the
@@ -1188,10 +1259,15 @@ class Context:
         pair, each equal to remove_outliers_seeded on that pair's raw list with stream = stream_base + pair (then the guided
         scan, if options.guided).  cross_check: the raw list is descriptor_match_cross_host(pair, 10000, options.lowes_ratio)
         -- a match must be the best in both directions -- (akz_match_features_seeded_cross_pairs); the guided scan stays
-        one-directional."""
-        a = _PairsArgs(self, features, pairs)
+        one-directional.  features: a list of (keypoints, descriptors) per set, or a FeatureBank of this context
+        (akz_match_features_seeded_bank_pairs: the same results, no set is packed or uploaded)."""
+        a = _PairsArgs(self, features, pairs, bank_ok=True)
         opt = options if options is not None else RansacOptions()
         tr = np.zeros(max(1, len(a.pr)), np.uint64)
+        if a.bank is not None:
+            _check(lib().akz_match_features_seeded_bank_pairs(*a.head, C.byref(opt), int(bool(cross_check)), *a.tail, *a.refined(),
+                                                              tr.ctypes.data_as(C.POINTER(C.c_uint64))))
+            return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
         fn = lib().akz_match_features_seeded_cross_pairs if cross_check else lib().akz_match_features_seeded_pairs
         _check(fn(*a.head, C.byref(opt), *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
         return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
@@ -1201,18 +1277,20 @@ class Context:
         Camera (or (fx, fy, cx, cy), or a 3 x 3 K) per feature set.  Returns one (matches, model or None, accepted fits, trials
         run, Pose) per pair -- with points=True a sixth entry, the [len(matches), 3] float32 structure in camera 0's frame at
         |t| = 1, or None without a pose -- each equal to remove_outliers_seeded on that pair's raw list followed, where a model
-        was found, by recover_pose_host with that list and model.  options.guided and the homography kind are refused."""
-        a = _PairsArgs(self, features, pairs)
+        was found, by recover_pose_host with that list and model.  options.guided and the homography kind are refused.
+        features may be a FeatureBank of this context (akz_match_features_seeded_pose_bank_pairs), with one camera per set of it."""
+        a = _PairsArgs(self, features, pairs, bank_ok=True)
         opt = options if options is not None else RansacOptions()
-        cams = (Camera * max(1, len(a.ks)))(*[Camera.of(k) for k in cameras])
-        if len(cameras) != len(a.ks):
-            raise ValueError(f"{len(a.ks)} feature sets but {len(cameras)} cameras")
+        if len(cameras) != a.n_sets:
+            raise ValueError(f"{a.n_sets} feature sets but {len(cameras)} cameras")
+        cams = (Camera * max(1, a.n_sets))(*[Camera.of(k) for k in cameras])
         tr = np.zeros(max(1, len(a.pr)), np.uint64)
         poses = (Pose * max(1, len(a.pr)))()
         pts = np.zeros((len(a.out), 3), np.float32) if points else None
-        _check(lib().akz_match_features_seeded_pose_pairs(*a.head[:3], C.cast(cams, C.c_void_p), *a.head[3:], C.byref(opt), int(bool(cross_check)),
-                                                          *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                          C.cast(poses, C.c_void_p), pts.ctypes.data_as(C.POINTER(C.c_float)) if points else None))
+        fn, at_cams = (lib().akz_match_features_seeded_pose_bank_pairs, 2) if a.bank is not None else (lib().akz_match_features_seeded_pose_pairs, 3)
+        _check(fn(*a.head[:at_cams], C.cast(cams, C.c_void_p), *a.head[at_cams:], C.byref(opt), int(bool(cross_check)),
+                  *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64)),
+                  C.cast(poses, C.c_void_p), pts.ctypes.data_as(C.POINTER(C.c_float)) if points else None))
         res, at = [], 0
         for p, (m, h, it) in enumerate(a.lists_models_iterations()):
             pose = Pose.from_buffer_copy(poses[p])
@@ -1480,6 +1558,52 @@ class Job:
 
     def __del__(self):
         self.abandon()
+
+
+class FeatureBank:
+    """An akz_bank: feature sets resident on the device (Context.feature_bank).  Immutable; close() returns its device block."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self._h = handle
+
+    def close(self):
+        if self._h:
+            lib().akz_bank_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """dict(n_sets, desc_bytes, rows, sets=[dict(n_keypoints, n_descriptors, row0) per set])"""
+        n, nb, rows = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(lib().akz_bank_info(self._h, C.byref(n), C.byref(nb), C.byref(rows)))
+        sets = []
+        for k in range(n.value):
+            nk, nd, r0 = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            _check(lib().akz_bank_set_info(self._h, k, C.byref(nk), C.byref(nd), C.byref(r0)))
+            sets.append(dict(n_keypoints=nk.value, n_descriptors=nd.value, row0=r0.value))
+        return dict(n_sets=n.value, desc_bytes=nb.value, rows=rows.value, sets=sets)
+
+    def device(self):
+        """(address of the rows [rows, 64] uint8, of x [rows] float32, of y [rows] float32) on the device; read-only, valid until close()."""
+        r, x, y = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().akz_bank_device(self._h, C.byref(r), C.byref(x), C.byref(y)))
+        return r.value, x.value, y.value
+
+    def download(self):
+        """The three device buffers as numpy arrays (rows [rows, 64] uint8, x, y float32): a copy, for inspection."""
+        n = self.info()["rows"]
+        r, x, y = self.device()
+        rows, hx, hy = np.zeros((n, 64), np.uint8), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        if n:
+            for dst, src in ((rows, r), (hx, x), (hy, y)):
+                copy_raw(dst.ctypes.data, src, dst.nbytes, 2)
+        return rows, hx, hy
 
 
 class ExtractResult:
@@ -2242,9 +2366,14 @@ def remove_outliers_seeded(keypoints_0, keypoints_1, matches, options=None, stre
     return out[:n.value].copy(), (f.reshape(3, 3) if found.value else None), it.value, tr.value
 
 
+def _bank_context(features):
+    """the context of a FeatureBank given as `features`, else None"""
+    return features.ctx if isinstance(features, FeatureBank) else None
+
+
 def match_features_seeded_pairs(features, pairs, options=None, ctx=None, cross_check=False):
-    """Context.match_features_seeded_pairs on ctx (default: the default context)."""
-    return (ctx or default_context()).match_features_seeded_pairs(features, pairs, options, cross_check=cross_check)
+    """Context.match_features_seeded_pairs on ctx (default: a FeatureBank's own context, else the default context)."""
+    return (ctx or _bank_context(features) or default_context()).match_features_seeded_pairs(features, pairs, options, cross_check=cross_check)
 
 
 def match_features_seeded(keypoints_0, descriptors_0, keypoints_1, descriptors_1, options=None, ctx=None, cross_check=False):
@@ -2277,8 +2406,9 @@ def recover_pose_host(keypoints_0, keypoints_1, matches, f, camera_0, camera_1, 
 
 
 def match_features_seeded_pose_pairs(features, cameras, pairs, options=None, ctx=None, cross_check=False, points=False):
-    """Context.match_features_seeded_pose_pairs on ctx (default: the default context)."""
-    return (ctx or default_context()).match_features_seeded_pose_pairs(features, cameras, pairs, options, cross_check=cross_check, points=points)
+    """Context.match_features_seeded_pose_pairs on ctx (default: a FeatureBank's own context, else the default context)."""
+    return (ctx or _bank_context(features) or default_context()).match_features_seeded_pose_pairs(features, cameras, pairs, options,
+                                                                                                  cross_check=cross_check, points=points)
 
 
 def match_features_seeded_pose(keypoints_0, descriptors_0, camera_0, keypoints_1, descriptors_1, camera_1, options=None, ctx=None,

@@ -1051,6 +1051,57 @@ int akz_match_features_seeded_pose_pairs(akz_ctx* ctx, const akz_feature_set* se
                                          uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */,
                                          akz_pose* poses /* n_pairs */, float* points /* 3 per slot of out, may be NULL */);
 
+/* ---- feature banks: match pairs over feature sets that stay on the device (additions, not in the reference) -----
+   An akz_bank is a list of feature sets resident on the device in the layout the pairs calls scan: every set's descriptors as
+   64-byte rows (bytes at or beyond desc_bytes are zero) in ONE contiguous buffer, set after set, and the x and y of the
+   keypoints those rows belong to (one float each per row).  It is immutable: nothing is appended or evicted, and no call writes to
+   it.  It belongs to the context it was created on and owns its device block itself (the library's resource counters count it):
+   akz_bank_free returns it.  A bank may outlive akz_ctx_destroy, exactly as an akz_result may: the context's own resources go
+   with akz_ctx_destroy, the bank keeps its block and nothing else until akz_bank_free, and every call that takes the bank and its
+   context is refused from then on.  Free every bank; one context's banks may be created, used and freed in any order. */
+typedef struct akz_bank akz_bank;
+/* The sets are every image of every result, in order: results[0] image 0, 1, ..., results[1] image 0, ...  A set's n_keypoints
+   equals its n_descriptors, the image's keypoint count (0 for an image without keypoints).  The rows never leave the device:
+   one launch (k_bank_gather) copies them from the results' row blocks, whatever the number of results and images, and writes the
+   bytes beyond desc_bytes as zero whatever the source holds; x and y come from the results' host keypoints, one upload each.
+   Complete on return: the results may be freed at once.  The results may belong to other contexts of the same device.
+   Refusals (AKZ_ERR_INVALID_ARG, *out = NULL, before any GPU work and before any allocation): a NULL ctx, results, out or
+   results[i]; n_results = 0; a result on another device than ctx; results whose descriptor sizes differ (descriptor_channels);
+   a result whose finish half has not completed. */
+int akz_bank_create_from_results(akz_ctx* ctx, const akz_result* const* results, uint64_t n_results, akz_bank** out);
+/* The same object from host sets (features read from files; host sets that are matched again then pay the packing and the upload
+   once): set k of the bank is sets[k], its rows packed and uploaded exactly as akz_match_features_pairs uploads a set a pair names
+   -- the x and y of its first n_descriptors keypoints.  n_sets = 0 gives an empty bank.  Refusals (as above): for EVERY set what
+   akz_match_features_pairs refuses for a set a pair names (more descriptors than keypoints, NULL keypoints or descriptors where
+   there are some), desc_bytes outside 1..64, NULL sets while n_sets > 0, a NULL ctx or out. */
+int akz_bank_create_from_sets(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, uint64_t desc_bytes, akz_bank** out);
+/* n_sets, desc_bytes and the rows of all sets; each pointer may be NULL. */
+int akz_bank_info(const akz_bank* bank, uint64_t* n_sets, uint64_t* desc_bytes, uint64_t* rows);
+/* One set's counts and its first row in the bank's buffers; each pointer may be NULL.  A set index >= n_sets is refused. */
+int akz_bank_set_info(const akz_bank* bank, uint64_t set, uint64_t* n_keypoints, uint64_t* n_descriptors, uint64_t* row0);
+/* The bank's device buffers, for callers that read them with their own kernels (torch): rows x 64 bytes, rows floats, rows floats.
+   Read-only, valid until akz_bank_free; each pointer may be NULL. */
+int akz_bank_device(const akz_bank* bank, const uint8_t** d_rows, const float** d_x, const float** d_y);
+int akz_bank_free(akz_bank* bank);
+/* akz_match_features_seeded_pairs (cross_check != 0: akz_match_features_seeded_cross_pairs) over the sets of a bank: for a bank made
+   from sets S -- by either constructor; from results, S is every image's keypoints and descriptors -- the call returns what that
+   call returns over (S, n_sets, desc_bytes), bit for bit: lists, counts, models, found, iterations and trials_run, in the same
+   layout of out, the guided stage included.  No set is packed or uploaded; the bank is not written.  Refusals
+   (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written): those of that call that do not concern a set's pointers, a NULL bank,
+   a bank of another context. */
+int akz_match_features_seeded_bank_pairs(akz_ctx* ctx, const akz_bank* bank, const uint64_t* pairs, uint64_t n_pairs,
+                                         const akz_ransac_options* options, int cross_check, akz_match* out,
+                                         uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
+                                         uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */);
+/* akz_match_features_seeded_pose_pairs over the sets of a bank, one camera per set of the bank; the same promise -- every field of
+   the poses and the points too -- and the same refusals. */
+int akz_match_features_seeded_pose_bank_pairs(akz_ctx* ctx, const akz_bank* bank, const akz_camera* cameras /* n_sets */,
+                                              const uint64_t* pairs, uint64_t n_pairs, const akz_ransac_options* options,
+                                              int cross_check, akz_match* out, uint64_t* n_out /* n_pairs */,
+                                              float* model /* 9 x n_pairs */, int* found /* n_pairs */,
+                                              uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */,
+                                              akz_pose* poses /* n_pairs */, float* points /* 3 per slot of out, may be NULL */);
+
 /* ---- k-nearest-neighbour matching: the k best train rows of every query, with their distances (additions) -----------
    For descriptor sets A (n0 rows) and B (n1 rows), 1 <= k <= AKZ_KNN_MAX_K and a distance_threshold, knn(A, B, k, threshold) is,
    for every row i of A:

@@ -138,10 +138,12 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    launch: k_frame_luma, param = the akz_frame_format, (w, h, n) = the frames, px = output pixels.
    A masked extraction (akz_extract_*_masked) adds one row of stage AKZ_ST_NMS (5) per filter launch, timed with every stage
    (profiling level 2): k_mask_candidates, param = masks (1: shared, else n), (w, h, n) = the frames, px = the list's capacity.
-   One launch per job, one more for every extrema pass the overflow path redid; unmasked jobs leave no such row. */
+   One launch per job, one more for every extrema pass the overflow path redid; unmasked jobs leave no such row.
+   akz_bank_create_from_results adds one row of stage 10 per bank with at least one row: k_bank_gather, ONE launch, param =
+   desc_bytes, w = 64, h = the bank's rows, n = its segments (images), px = rows copied. */
 enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5,
        AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8, AKZ_KR_SORT_ROWS = 9, AKZ_KR_SORT_BUCKETS = 10,
-       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12, AKZ_KR_MASK_CANDIDATES = 13 };
+       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12, AKZ_KR_MASK_CANDIDATES = 13, AKZ_KR_BANK_GATHER = 14 };
 typedef struct akz_kernel_row {
     uint32_t stage, kind, param, w, h, n;
     uint64_t launches, px, px_steps;
@@ -205,6 +207,11 @@ int akz_debug_mask_candidates(akz_ctx* ctx, const void* d_records, uint32_t capa
    out[1] = candidates kept, out[2] = extrema passes the overflow path redid (each followed by a filter launch of its own).
    The capacity bookkeeping of the context (the next job's list size) is fed out[0], not out[1]. */
 int akz_debug_mask_counts(akz_ctx* ctx, uint64_t out[3]);
+/* Test hook: the feature bank's kernel alone (k_bank_gather, csrc/akz_bank.hip) over caller-held device rows: n_rows rows of 64
+   bytes at d_src (16-byte aligned) to d_dst, as a table of three segments -- the first half, an empty segment, the rest -- through
+   the code path akz_bank_create_from_results takes; complete on return.  Bytes of a row at or beyond desc_bytes (1..64) arrive as
+   zero whatever d_src holds there. */
+int akz_debug_bank_gather(akz_ctx* ctx, const uint8_t* d_src, uint64_t n_rows, uint64_t desc_bytes, uint8_t* d_dst);
 
 /* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
    source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */
