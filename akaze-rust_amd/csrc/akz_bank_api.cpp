@@ -4,6 +4,9 @@
 // keypoints through pinned staging, and launch::bank_gather (akz_bank.hip) -- ONE launch -- over the results' device rows.
 // akz_bank_create_from_sets: the packing and the copies of pairs_upload (akz_match_api.cpp) into the bank's block.  The two bank
 // forms of the seeded pairs calls are those calls with the bank handed down to pairs_front (akz_match_seeded_api.cpp).
+// The two constructors under a keypoint budget (bank_create_budgeted): the budget's plan / enqueue half (budget_enqueue,
+// akz_budget_api.cpp) leaves every set's kept indices on the device, and launch::bank_select -- ONE launch -- gathers rows, x and y
+// through them, from the results' row blocks or from the full sets that pairs_upload put into the context's staging.
 #include <cstring>
 #include <memory>
 #include <string>
@@ -34,15 +37,16 @@ uint64_t bank_segments(const akz_result* const* results, uint64_t n_results, std
     }
     return rows;
 }
-// the bank's block for `rows` rows: rows | x | y, every part on 256 bytes
-int bank_alloc(akz_ctx* c, akz_bank* b, uint64_t rows) {
+// the bank's block for `rows` rows: rows | x | y (| src, the source indices of a budgeted bank), every part on 256 bytes
+int bank_alloc(akz_ctx* c, akz_bank* b, uint64_t rows, bool with_src = false) {
     const uint64_t rows1 = std::max<uint64_t>(rows, 1);
     const size_t b_rows = up256((size_t)rows1 * 64), b_xy = up256((size_t)rows1 * 4);
-    AKZ_HIP_TRY(b->dev.acquire(b_rows + 2 * b_xy, false));
+    AKZ_HIP_TRY(b->dev.acquire(b_rows + 2 * b_xy + (with_src ? b_xy : 0), false));
     AKZ_HIP_TRY(alloc_fill(c, b->dev.p, b->dev.bytes));
     b->rows = rows;
     b->d_rows = (uint8_t*)b->dev.p;
     b->d_kx = (float*)(b->d_rows + b_rows), b->d_ky = (float*)(b->d_rows + b_rows + b_xy);
+    if (with_src) b->d_src = (uint32_t*)(b->d_rows + b_rows + 2 * b_xy);
     return AKZ_OK;
 }
 void bank_place(akz_bank* b) {  // every set behind the one before it
@@ -74,16 +78,13 @@ int bank_gather_enqueue(akz_ctx* c, const std::vector<launch::BankSeg>& segs, si
     AKZ_HIP_TRY(hipGetLastError());
     return AKZ_OK;
 }
-}  // namespace
-
-extern "C" {
-
-int akz_bank_create_from_results(akz_ctx* c, const akz_result* const* results, uint64_t n_results, akz_bank** out) {
-    const std::string name = "bank_create_from_results: ";
-    if (out) *out = nullptr;
+// the refusals of the constructors from results (`name` ends in ": "); rows: the keypoints of all images
+int results_refusals(const std::string& name, const akz_ctx* c, const akz_result* const* results, uint64_t n_results, akz_bank** out,
+                     uint64_t& rows) {
     if (!c || !results || !out) return refuse(name + "null context, results or out");
     if (n_results == 0) return refuse(name + "no result (the descriptor size of a bank is that of its results)");
-    uint64_t images = 0, rows = 0;
+    uint64_t images = 0;
+    rows = 0;
     for (uint64_t i = 0; i < n_results; ++i) {
         const akz_result* r = results[i];
         const std::string at = name + "result " + std::to_string(i) + ": ";
@@ -99,6 +100,68 @@ int akz_bank_create_from_results(akz_ctx* c, const akz_result* const* results, u
         for (uint32_t img = 0; img < r->n; ++img) rows += r->kps[img].size();
     }
     if (images > 0xffffffffull || rows > launch::kBankMaxRows) return refuse(name + "too many images or rows for one launch");
+    return AKZ_OK;
+}
+// the selection table through pinned staging (`pin_off` bytes into c->mp_pin_in, as above) to c->mp_tab, then the one launch of
+// k_bank_select, on the context's stream (not synchronised)
+int bank_select_enqueue(akz_ctx* c, const std::vector<launch::BankSel>& tab, size_t pin_off, uint64_t rows, uint64_t desc_bytes,
+                        const uint32_t* d_idx, const float* d_sx, const float* d_sy, uint8_t* d_rows, float* d_x, float* d_y, uint32_t* d_index) {
+    if (tab.empty() || rows == 0) return AKZ_OK;
+    hipStream_t st = c->stream;
+    const size_t b_tab = tab.size() * sizeof(launch::BankSel);
+    AKZ_TRY(ensure(c, c->mp_tab, b_tab));
+    char* h_tab = (char*)c->mp_pin_in.p + pin_off;
+    std::memcpy(h_tab, tab.data(), b_tab);
+    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_tab.p, h_tab, b_tab, hipMemcpyHostToDevice, st));
+    StageTimer t(c, kStageIngest, st);
+    t.kernel(AKZ_KR_BANK_SELECT, (uint32_t)desc_bytes, 64, (uint32_t)std::min<uint64_t>(rows, 0xffffffffull), (uint32_t)tab.size(), 1, rows);
+    launch::bank_select(st, (const launch::BankSel*)c->mp_tab.p, (uint32_t)tab.size(), rows, (uint32_t)desc_bytes, d_idx, d_sx, d_sy, d_rows, d_x,
+                        d_y, d_index);
+    AKZ_HIP_TRY(hipGetLastError());
+    return AKZ_OK;
+}
+// What the two budgeted constructors share, behind their refusals and bind: the bank of min(max_keypoints, n) rows per set, the
+// budget (budget_enqueue: its ONE upload carries x, y and response, so the bank's x / y are gathered, not uploaded again), the one
+// k_bank_select from src_rows[s] (set s's rows on the device, 64 bytes each; `place`, given, enqueues what puts them there), the
+// kept indices to the host and the call's one synchronisation.  sets: only keypoints / n_keypoints are read.  The selection
+// table goes `pin_off` bytes into c->mp_pin_in, which holds at least pin_off + 40 bytes per set.
+template <typename Place>
+int bank_create_budgeted(akz_ctx* c, const std::vector<akz_feature_set>& sets, const std::vector<const uint8_t*>& src_rows, uint64_t desc_bytes,
+                         const akz_keypoint_budget& o, size_t pin_off, Place place, akz_bank** out) {
+    std::unique_ptr<akz_bank> b(new akz_bank);
+    b->desc_bytes = desc_bytes;
+    b->budgeted = true;
+    for (const akz_feature_set& s : sets) {
+        const uint64_t keep = std::min<uint64_t>(o.max_keypoints, s.n_keypoints);
+        b->sets.push_back(akz_feature_set{nullptr, keep, nullptr, keep});
+    }
+    bank_place(b.get());
+    uint64_t rows = 0;
+    for (const akz_feature_set& s : b->sets) rows += s.n_descriptors;
+    AKZ_TRY(bank_alloc(c, b.get(), rows, true));
+    AKZ_TRY(place());
+    BudgetPlan p;
+    AKZ_TRY(budget_enqueue(c, sets.data(), sets.size(), o, p));
+    std::vector<launch::BankSel> tab;
+    for (size_t s = 0; s < sets.size(); ++s)
+        tab.push_back(launch::BankSel{p.tab[s].keep ? src_rows[s] : nullptr, p.tab[s].base, p.tab[s].keep, b->set_row[s], p.tab[s].out_off});
+    AKZ_TRY(bank_select_enqueue(c, tab, pin_off, rows, desc_bytes, p.d_idx, p.d_x, p.d_y, b->d_rows, b->d_kx, b->d_ky, b->d_src));
+    hipStream_t st = c->stream;
+    if (rows) AKZ_HIP_TRY(hipMemcpyAsync(p.h_down, b->d_src, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    AKZ_HIP_TRY(hipStreamSynchronize(st));  // complete on return: the sources may go
+    if (rows) b->src.assign((const uint32_t*)p.h_down, (const uint32_t*)p.h_down + rows);
+    *out = bank_keep(c, b);
+    return AKZ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int akz_bank_create_from_results(akz_ctx* c, const akz_result* const* results, uint64_t n_results, akz_bank** out) {
+    const std::string name = "bank_create_from_results: ";
+    if (out) *out = nullptr;
+    uint64_t rows = 0;
+    AKZ_TRY(results_refusals(name, c, results, n_results, out, rows));
     AKZ_TRY(bind(c));
     std::unique_ptr<akz_bank> b(new akz_bank);
     b->desc_bytes = result_desc_bytes(results[0]);
@@ -158,6 +221,84 @@ int akz_bank_create_from_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t 
     if (rows) AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));
     AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
     *out = bank_keep(c, b);
+    return AKZ_OK;
+}
+
+int akz_bank_create_from_results_budget(akz_ctx* c, const akz_result* const* results, uint64_t n_results, const akz_keypoint_budget* budget,
+                                        akz_bank** out) {
+    const std::string name = "bank_create_from_results_budget: ";
+    if (out) *out = nullptr;
+    if (out && !budget_options_ok(name.c_str(), budget, out, out, nullptr)) return AKZ_ERR_INVALID_ARG;  // (no indices, n_out or radius2 here)
+    uint64_t rows = 0;
+    AKZ_TRY(results_refusals(name, c, results, n_results, out, rows));
+    if (rows > kBudgetMaxKeypoints) return refuse(name + "the results hold more than 2^31 - 1 keypoints together");
+    std::vector<akz_feature_set> sets;
+    std::vector<const uint8_t*> src_rows;
+    for (uint64_t i = 0; i < n_results; ++i) {
+        const akz_result* r = results[i];
+        for (uint32_t img = 0; img < r->n; ++img) {
+            const std::vector<akz_keypoint>& k = r->kps[img];
+            if (!budget_set_ok(name.c_str(), "result " + std::to_string(i) + " image " + std::to_string(img) + ": ", k.data(), k.size()))
+                return AKZ_ERR_INVALID_ARG;
+            sets.push_back(akz_feature_set{k.data(), k.size(), nullptr, 0});
+            src_rows.push_back(k.empty() ? nullptr : r->d_desc64 + r->desc_off[img] * 64);
+        }
+    }
+    AKZ_TRY(bind(c));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, sets.size() * sizeof(launch::BankSel)));
+    return bank_create_budgeted(c, sets, src_rows, result_desc_bytes(results[0]), *budget, 0, [] { return (int)AKZ_OK; }, out);
+}
+
+int akz_bank_create_from_sets_budget(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, uint64_t desc_bytes,
+                                     const akz_keypoint_budget* budget, akz_bank** out) {
+    const std::string name = "bank_create_from_sets_budget: ";
+    if (out) *out = nullptr;
+    if (!out) return refuse(name + "null out");
+    if (desc_bytes == 0 || desc_bytes > 64) return refuse(name + "desc_bytes must be 1..64");
+    if (n_sets && !sets) return refuse(name + "null sets");
+    if (!budget_options_ok(name.c_str(), budget, out, out, nullptr)) return AKZ_ERR_INVALID_ARG;
+    uint64_t rows = 0;
+    for (uint64_t k = 0; k < n_sets; ++k) {
+        const akz_feature_set& s = sets[k];
+        const std::string at = "set " + std::to_string(k) + ": ";
+        if (s.n_descriptors != s.n_keypoints)
+            return refuse(name + at + std::to_string(s.n_descriptors) + " descriptors for " + std::to_string(s.n_keypoints) +
+                          " keypoints (the budget is defined over keypoints that all have a row)");
+        if ((s.n_keypoints && !s.keypoints) || (s.n_descriptors && !s.descriptors)) return refuse(name + at + "null keypoints or descriptors");
+        if (!budget_set_ok(name.c_str(), at, s.keypoints, s.n_keypoints)) return AKZ_ERR_INVALID_ARG;
+        rows += s.n_descriptors;
+        if (rows > kBudgetMaxKeypoints) return refuse(name + at + "the sets of one call hold more than 2^31 - 1 keypoints together");
+    }
+    if (!c) return refuse(name + "null context");
+    AKZ_TRY(bind(c));
+    // the FULL sets to the context's staging, placed as pairs_open places sets that every pair names
+    PairsFront f;
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < n_sets; ++k) {
+        f.set_row.push_back(at);
+        f.used.push_back(k);
+        at += sets[k].n_descriptors;
+    }
+    f.rows = rows;
+    const uint64_t rows1 = std::max<uint64_t>(rows, 1);
+    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4);
+    AKZ_TRY(ensure(c, c->mp_in, f.b_rows + 2 * f.b_xy));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, f.b_rows + 2 * f.b_xy + (size_t)n_sets * sizeof(launch::BankSel)));
+    f.d_rows = (uint8_t*)c->mp_in.p;
+    f.d_kx = (float*)(f.d_rows + f.b_rows), f.d_ky = (float*)(f.d_rows + f.b_rows + f.b_xy);
+    std::vector<const uint8_t*> src_rows;
+    for (uint64_t k = 0; k < n_sets; ++k) src_rows.push_back(f.d_rows + f.set_row[(size_t)k] * 64);
+    const std::vector<akz_feature_set> all(sets, sets + n_sets);
+    return bank_create_budgeted(c, all, src_rows, desc_bytes, *budget, f.b_rows + 2 * f.b_xy,
+                                [&] { return rows ? pairs_upload(c, sets, desc_bytes, f) : (int)AKZ_OK; }, out);
+}
+
+int akz_bank_set_indices(const akz_bank* b, uint64_t set, uint64_t* indices) {
+    if (!b) return refuse("bank_set_indices: null bank");
+    if (set >= b->sets.size()) return refuse("bank_set_indices: set index " + std::to_string(set) + " >= n_sets " + std::to_string(b->sets.size()));
+    const uint64_t n = b->sets[(size_t)set].n_keypoints, row0 = b->set_row[(size_t)set];
+    if (n && !indices) return refuse("bank_set_indices: null indices for a set of " + std::to_string(n) + " keypoints");
+    for (uint64_t t = 0; t < n; ++t) indices[t] = b->budgeted ? b->src[(size_t)(row0 + t)] : t;
     return AKZ_OK;
 }
 
@@ -227,6 +368,45 @@ int akz_debug_bank_gather(akz_ctx* c, const uint8_t* d_src, uint64_t n_rows, uin
     const std::vector<launch::BankSeg> segs = {{d_src, head, 0}, {nullptr, 0, head}, {d_src + head * 64, n_rows - head, head}};
     AKZ_TRY(ensure_pinned(c, c->mp_pin_in, segs.size() * sizeof(launch::BankSeg)));
     AKZ_TRY(bank_gather_enqueue(c, segs, 0, n_rows, desc_bytes, d_dst));
+    AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
+    return AKZ_OK;
+}
+
+int akz_debug_bank_select(akz_ctx* c, const uint8_t* d_src, const float* d_sx, const float* d_sy, uint64_t n_sets, const uint64_t* n,
+                          const uint64_t* keep, const uint32_t* indices, uint64_t desc_bytes, uint8_t* d_rows, float* d_x, float* d_y,
+                          uint32_t* d_index) {
+    const std::string name = "debug_bank_select: ";
+    if (desc_bytes == 0 || desc_bytes > 64) return refuse(name + "desc_bytes must be 1..64");
+    if (n_sets > 0xfffffff0ull || (n_sets && (!n || !keep))) return refuse(name + "null counts, or too many sets");
+    // the table: the caller's sets, their sources packed one behind the other, between two empty records of the hook's own
+    std::vector<launch::BankSel> tab = {{nullptr, 0, 0, 0, 0}};
+    uint64_t base = 0, rows = 0;
+    for (uint64_t s = 0; s < n_sets; ++s) {
+        const std::string at = name + "set " + std::to_string(s) + ": ";
+        if (keep[s] > n[s] || n[s] > 0xffffffffull) return refuse(at + "keep " + std::to_string(keep[s]) + " of " + std::to_string(n[s]) + " rows");
+        if (keep[s] && !indices) return refuse(at + "null indices");
+        for (uint64_t t = 0; t < keep[s]; ++t) {
+            const uint32_t i = indices[rows + t];
+            if (i >= n[s]) return refuse(at + "index " + std::to_string(i) + " reaches the set's " + std::to_string(n[s]) + " rows");
+            if (t && i <= indices[rows + t - 1]) return refuse(at + "the indices do not ascend at entry " + std::to_string(t));
+        }
+        tab.push_back(launch::BankSel{keep[s] ? d_src + base * 64 : nullptr, base, keep[s], rows, rows});
+        base += n[s];
+        rows += keep[s];
+    }
+    tab.push_back(launch::BankSel{nullptr, base, 0, rows, rows});
+    if (rows > launch::kBankMaxRows || (rows && (!d_src || !d_sx || !d_sy || !d_rows || !d_x || !d_y || !d_index)))
+        return refuse(name + "rows need sources and destinations");
+    AKZ_TRY(bind(c));
+    if (rows == 0) return AKZ_OK;
+    // table | indices in pinned memory; the indices pass through the budget's device scratch, where launch::budget leaves its own
+    const size_t b_tab = up256(tab.size() * sizeof(launch::BankSel));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, b_tab + (size_t)rows * 4));
+    AKZ_TRY(ensure(c, c->kb_dev, (size_t)rows * 4));
+    uint32_t* h_idx = (uint32_t*)((char*)c->mp_pin_in.p + b_tab);
+    std::memcpy(h_idx, indices, (size_t)rows * 4);
+    AKZ_HIP_TRY(hipMemcpyAsync(c->kb_dev.p, h_idx, (size_t)rows * 4, hipMemcpyHostToDevice, c->stream));
+    AKZ_TRY(bank_select_enqueue(c, tab, 0, rows, desc_bytes, (const uint32_t*)c->kb_dev.p, d_sx, d_sy, d_rows, d_x, d_y, d_index));
     AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
     return AKZ_OK;
 }

@@ -1,7 +1,8 @@
 // The keypoint budget (additions; include/akaze_hip.h): at most N keypoints of a set, the strongest or -- adaptive
 // non-maximal suppression -- the best spread.  akz_keypoint_budget_host is the statement: plain f32 loops and a sort.
 // akz_keypoint_budget_sets runs it over many sets on the GPU (akz_budget.hip): one upload, the radius and rank passes of
-// k_budget_walk, one compaction per set, one download.  Nothing here touches an extraction or a matching call.
+// k_budget_walk, one compaction per set, one download.  Nothing here touches an extraction or a matching call.  The call is two
+// halves: budget_enqueue (plan, upload, kernels), which the budgeted bank (akz_bank_api.cpp) shares and stops after, and the download.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,10 +11,6 @@
 #include <vector>
 
 #include "akz_ctx.hpp"
-
-namespace {
-
-constexpr uint64_t kMaxSet = 0x7fffffffull;
 
 // every refusal that does not depend on a set's keypoints; `name` ends in ": "
 bool budget_options_ok(const char* name, const akz_keypoint_budget* opt, const void* indices, const void* n_out, const void* radius2) {
@@ -38,7 +35,7 @@ bool budget_options_ok(const char* name, const akz_keypoint_budget* opt, const v
 
 // ... and those of one set; `what` names it ("" or "set 3: ")
 bool budget_set_ok(const char* name, const std::string& what, const akz_keypoint* k, uint64_t n) {
-    if (n > kMaxSet) {
+    if (n > kBudgetMaxKeypoints) {
         set_error(std::string(name) + what + "more than 2^31 - 1 keypoints");
         return false;
     }
@@ -53,6 +50,8 @@ bool budget_set_ok(const char* name, const std::string& what, const akz_keypoint
         }
     return true;
 }
+
+namespace {
 
 // the statement for one checked set
 void budget_statement(const akz_keypoint* k, uint64_t n64, const akz_keypoint_budget& o, uint64_t* indices, uint64_t* n_out, float* radius2) {
@@ -91,41 +90,13 @@ void budget_statement(const akz_keypoint* k, uint64_t n64, const akz_keypoint_bu
 
 }  // namespace
 
-extern "C" {
-
-int akz_keypoint_budget_host(const akz_keypoint* keypoints, uint64_t n, const akz_keypoint_budget* options, uint64_t* indices,
-                             uint64_t* n_out, float* radius2) {
-    const char* name = "keypoint_budget_host: ";
-    if (!budget_options_ok(name, options, indices, n_out, radius2) || !budget_set_ok(name, "", keypoints, n)) return AKZ_ERR_INVALID_ARG;
-    budget_statement(keypoints, n, *options, indices, n_out, radius2);
-    return AKZ_OK;
-}
-
-int akz_keypoint_budget_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_keypoint_budget* options, uint64_t* indices,
-                             uint64_t* n_out, float* radius2) {
-    const char* name = "keypoint_budget_sets: ";
-    if (n_sets == 0) return AKZ_OK;
-    if (!c || !sets) {
-        set_error(std::string(name) + (c ? "null sets" : "null context"));
-        return AKZ_ERR_INVALID_ARG;
-    }
-    if (!budget_options_ok(name, options, indices, n_out, radius2)) return AKZ_ERR_INVALID_ARG;
-    uint64_t total64 = 0;
-    for (uint64_t s = 0; s < n_sets; ++s) {
-        if (!budget_set_ok(name, "set " + std::to_string(s) + ": ", sets[s].keypoints, sets[s].n_keypoints)) return AKZ_ERR_INVALID_ARG;
-        total64 += sets[s].n_keypoints;
-        if (total64 > kMaxSet) {
-            set_error(std::string(name) + "set " + std::to_string(s) + ": the sets of one call hold more than 2^31 - 1 keypoints together");
-            return AKZ_ERR_INVALID_ARG;
-        }
-    }
-    AKZ_TRY(bind(c, true, false));
-    const akz_keypoint_budget o = *options;
+// The plan / enqueue half of akz_keypoint_budget_sets (akz_ctx.hpp), which the budgeted bank stops after
+int budget_enqueue(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_keypoint_budget& o, BudgetPlan& p) {
     const bool spread = o.mode == AKZ_BUDGET_SPREAD;
-    const uint32_t total = (uint32_t)total64;
     // the set table, and the walk's workgroups: every query tile of a set against train chunks of one length for the whole call, as
     // short as fills the chip (about 2 048 workgroups) and a multiple of the LDS stage
-    std::vector<launch::BudgetSet> tab((size_t)n_sets);
+    std::vector<launch::BudgetSet>& tab = p.tab;
+    tab.assign((size_t)n_sets, launch::BudgetSet{});
     const uint32_t qt = launch::budget_query_tile(), tt = launch::budget_train_tile();
     double work = 0.0;
     uint32_t base = 0, kept = 0;
@@ -136,8 +107,9 @@ int akz_keypoint_budget_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t n
         base += n;
         kept += keep;
         work += (double)n * (double)n;
-        n_out[s] = keep;
     }
+    const uint32_t total = base;
+    p.total = total, p.kept = kept;
     if (total == 0) return AKZ_OK;
     const double per_block = std::max((double)qt * tt, work / 2048.0);
     const uint32_t chunk = (uint32_t)std::min<double>(std::ceil(per_block / qt / tt) * tt, 1u << 30);
@@ -150,7 +122,7 @@ int akz_keypoint_budget_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t n
     // device: x | y | r | set table | block table (the upload), rank, then kept indices | radius2 (the download)
     const size_t b_f = up256((size_t)total * 4), b_tab = up256(tab.size() * sizeof(launch::BudgetSet)),
                  b_blk = up256(blocks.size() * sizeof(launch::BudgetBlock)), b_idx = up256((size_t)kept * 4);
-    const size_t b_up = 3 * b_f + b_tab + b_blk, b_down = b_idx + (radius2 ? (size_t)total * 4 : 0);
+    const size_t b_up = 3 * b_f + b_tab + b_blk;
     AKZ_TRY(ensure(c, c->kb_dev, b_up + b_f + b_idx + b_f));
     AKZ_TRY(ensure_pinned(c, c->kb_pin, b_up + b_idx + b_f));
     const bool timed = c->kb_split_on;
@@ -177,16 +149,58 @@ int akz_keypoint_budget_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t n
                    (uint32_t)blocks.size(), d_rad, d_rank, d_idx);
     AKZ_HIP_TRY(hipGetLastError());
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->kb_split_ev[2], st));
-    char* h_down = h + b_up;
-    if (b_down) AKZ_HIP_TRY(hipMemcpyAsync(h_down, d_idx, b_down, hipMemcpyDeviceToHost, st));
+    p.d_x = (const float*)d, p.d_y = (const float*)(d + b_f), p.d_r = (const float*)(d + 2 * b_f);
+    p.d_idx = d_idx, p.b_idx = b_idx;
+    p.h_down = h + b_up;
+    return AKZ_OK;
+}
+
+extern "C" {
+
+int akz_keypoint_budget_host(const akz_keypoint* keypoints, uint64_t n, const akz_keypoint_budget* options, uint64_t* indices,
+                             uint64_t* n_out, float* radius2) {
+    const char* name = "keypoint_budget_host: ";
+    if (!budget_options_ok(name, options, indices, n_out, radius2) || !budget_set_ok(name, "", keypoints, n)) return AKZ_ERR_INVALID_ARG;
+    budget_statement(keypoints, n, *options, indices, n_out, radius2);
+    return AKZ_OK;
+}
+
+int akz_keypoint_budget_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_keypoint_budget* options, uint64_t* indices,
+                             uint64_t* n_out, float* radius2) {
+    const char* name = "keypoint_budget_sets: ";
+    if (n_sets == 0) return AKZ_OK;
+    if (!c || !sets) {
+        set_error(std::string(name) + (c ? "null sets" : "null context"));
+        return AKZ_ERR_INVALID_ARG;
+    }
+    if (!budget_options_ok(name, options, indices, n_out, radius2)) return AKZ_ERR_INVALID_ARG;
+    uint64_t total64 = 0;
+    for (uint64_t s = 0; s < n_sets; ++s) {
+        if (!budget_set_ok(name, "set " + std::to_string(s) + ": ", sets[s].keypoints, sets[s].n_keypoints)) return AKZ_ERR_INVALID_ARG;
+        total64 += sets[s].n_keypoints;
+        if (total64 > kBudgetMaxKeypoints) {
+            set_error(std::string(name) + "set " + std::to_string(s) + ": the sets of one call hold more than 2^31 - 1 keypoints together");
+            return AKZ_ERR_INVALID_ARG;
+        }
+    }
+    AKZ_TRY(bind(c, true, false));
+    BudgetPlan p;
+    AKZ_TRY(budget_enqueue(c, sets, n_sets, *options, p));
+    for (uint64_t s = 0; s < n_sets; ++s) n_out[s] = p.tab[(size_t)s].keep;
+    if (p.total == 0) return AKZ_OK;
+    // the download: kept indices | radius2
+    const bool timed = c->kb_split_on;
+    hipStream_t st = c->stream;
+    const size_t b_down = p.b_idx + (radius2 ? (size_t)p.total * 4 : 0);
+    if (b_down) AKZ_HIP_TRY(hipMemcpyAsync(p.h_down, p.d_idx, b_down, hipMemcpyDeviceToHost, st));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->kb_split_ev[3], st));
     AKZ_HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t* h_idx = (const uint32_t*)h_down;
+    const uint32_t* h_idx = (const uint32_t*)p.h_down;
     for (uint64_t s = 0; s < n_sets; ++s) {
-        const launch::BudgetSet& b = tab[(size_t)s];
+        const launch::BudgetSet& b = p.tab[(size_t)s];
         for (uint32_t t = 0; t < b.keep; ++t) indices[(size_t)b.base + t] = h_idx[(size_t)b.out_off + t];
     }
-    if (radius2) std::memcpy(radius2, h_down + b_idx, (size_t)total * 4);
+    if (radius2) std::memcpy(radius2, p.h_down + p.b_idx, (size_t)p.total * 4);
     if (timed) {
         float ms[3] = {0.0f, 0.0f, 0.0f};
         for (int i = 0; i < 3; ++i) AKZ_HIP_TRY(hipEventElapsedTime(&ms[i], c->kb_split_ev[i], c->kb_split_ev[i + 1]));

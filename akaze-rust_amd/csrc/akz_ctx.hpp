@@ -765,7 +765,31 @@ struct akz_bank {
     DevBuf dev;
     uint8_t* d_rows = nullptr;
     float *d_kx = nullptr, *d_ky = nullptr;
+    // a bank under a keypoint budget (akz_bank_create_from_*_budget): `dev` = rows | x | y | src, d_src[r] = the index in its source
+    // set of the keypoint row r came from, and `src` is its host copy (akz_bank_set_indices).  Both absent otherwise: the identity.
+    bool budgeted = false;
+    uint32_t* d_src = nullptr;
+    std::vector<uint32_t> src;
 };
+// akz_budget_api.cpp: the keypoint budget's refusals and its plan / enqueue half, shared with the budgeted bank (akz_bank_api.cpp).
+// budget_options_ok: every refusal that does not depend on a set's keypoints; budget_set_ok: those of one set, which `what` names
+// ("" or "set 3: "); `name` ends in ": ".  budget_enqueue: over checked sets of at most kBudgetMaxKeypoints keypoints together
+// (only keypoints / n_keypoints are read) -- the set and block tables, the ONE upload of x | y | response and the tables, and
+// launch::budget, on the context's stream; it neither copies back nor synchronises.  Afterwards set s has its x, y and response at
+// [tab[s].base, + n) of d_x, d_y, d_r and its tab[s].keep kept indices, ascending, at d_idx + tab[s].out_off; h_down: b_idx +
+// 4 * total bytes of pinned memory for the caller's read-back (kept indices | radius2).
+constexpr uint64_t kBudgetMaxKeypoints = 0x7fffffffull;
+AKZ_LOCAL bool budget_options_ok(const char* name, const akz_keypoint_budget* opt, const void* indices, const void* n_out, const void* radius2);
+AKZ_LOCAL bool budget_set_ok(const char* name, const std::string& what, const akz_keypoint* k, uint64_t n);
+struct BudgetPlan {
+    std::vector<launch::BudgetSet> tab;
+    uint32_t total = 0, kept = 0;
+    const float *d_x = nullptr, *d_y = nullptr, *d_r = nullptr;
+    uint32_t* d_idx = nullptr;  // `kept` indices, then (b_idx bytes on) the radius2 of all `total` keypoints
+    size_t b_idx = 0;
+    char* h_down = nullptr;
+};
+AKZ_LOCAL int budget_enqueue(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_keypoint_budget& o, BudgetPlan& p);
 // akz_match_api.cpp.  pairs_open: the refusals (guided: those of the guided scan too), bind, the placement of every distinct set and
 // the room for its rows.  pairs_front: pairs_open, the upload, the scans (cross: both directions and launch::pairs_cross_filter), the
 // table, launch::pair_points and the enqueued read-back of the counts -- it does not synchronise.  b_dev_own / b_pin_own: the caller's

@@ -520,6 +520,18 @@ struct BankSeg {
 static_assert(sizeof(BankSeg) == 24, "the device reads 24-byte segment records");
 constexpr uint64_t kBankMaxRows = 0x7fffffffull * 64;  // (a launch's workgroups, at no fewer than 64 rows each)
 void bank_gather(hipStream_t s, const BankSeg* d_tab, uint32_t n_seg, uint64_t total_rows, uint32_t desc_bytes, uint8_t* d_dst);
+// the budgeted bank's gather (akz_bank.hip, k_bank_select): set s sends `keep` of its rows -- those that d_idx[idx_off + t],
+// t < keep, names, ascending and below the set's row count -- to the rows from dst_row0 on, in ONE launch over n_set records laid
+// out as the segments above (dst_row0 ascends, record s + 1 starts where s ends, total_rows is the sum of keep).  Destination row
+// r = dst_row0 + t, with i the index it names, receives row i of src_rows (bytes at or beyond desc_bytes as zero),
+// d_sx / d_sy[src_base + i], and i itself in d_dst_src.
+struct BankSel {
+    const uint8_t* src_rows;
+    uint64_t src_base, keep, dst_row0, idx_off;
+};
+static_assert(sizeof(BankSel) == 40, "the device reads 40-byte selection records");
+void bank_select(hipStream_t s, const BankSel* d_tab, uint32_t n_set, uint64_t total_rows, uint32_t desc_bytes, const uint32_t* d_idx,
+                 const float* d_sx, const float* d_sy, uint8_t* d_dst, float* d_dx, float* d_dy, uint32_t* d_dst_src);
 // k-nearest-neighbour matching (akz_knn.hip): q4 / t4 are the FP4 images of unpack_pair(fp4); `chunks` from knn_chunks (forced: the
 // test hook, 0 = automatic; never fewer than the row field of a key allows); d_part: knn_part_bytes bytes of partial lists.
 // Writes k records per query and its count (all padding for n1 == 0); false: arguments or a retuned tile the kernel was not built for.

@@ -134,7 +134,7 @@ class KernelRow(C.Structure):
 
 KERNEL_ROW_KINDS = {1: "k_level_march", 2: "k_fed_own", 3: "k_octave_resident", 4: "k_detector_tiled", 5: "k_detector_march",
                     6: "k_jpeg_idct", 7: "k_jpeg_luma", 8: "jpeg_coef_h2d", 9: "k_sort_rows", 10: "k_bucket_sort", 11: "rocprim_radix_sort",
-                    12: "k_frame_luma", 13: "k_mask_candidates", 14: "k_bank_gather"}
+                    12: "k_frame_luma", 13: "k_mask_candidates", 14: "k_bank_gather", 15: "k_bank_select"}
 
 
 class ScratchAudit(C.Structure):
@@ -450,6 +450,10 @@ def lib():
         "akz_match_features_seeded_pose_bank_pairs": ([vp, vp, vp, vp, u64, C.POINTER(RansacOptions), i32, vp, pu64, fp, C.POINTER(i32),
                                                        C.POINTER(C.c_uint32), pu64, vp, fp], i32),
         "akz_debug_bank_gather": ([vp, vp, u64, u64, vp], i32),
+        "akz_bank_create_from_results_budget": ([vp, C.POINTER(vp), u64, C.POINTER(KeypointBudget), C.POINTER(vp)], i32),
+        "akz_bank_create_from_sets_budget": ([vp, vp, u64, u64, C.POINTER(KeypointBudget), C.POINTER(vp)], i32),
+        "akz_bank_set_indices": ([vp, u64, pu64], i32),
+        "akz_debug_bank_select": ([vp, vp, vp, vp, u64, pu64, pu64, pu32, u64, vp, vp, vp, vp], i32),
         "akz_descriptor_match_cross_host": ([vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross": ([vp, vp, u64, vp, u64, u64, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_cross_device": ([vp, vp, u64, vp, u64, u64, f64, vp, vp], i32),
@@ -1211,13 +1215,17 @@ class Context:
                                                                          *a.refined()))
         return a.lists_models_iterations()
 
-    def feature_bank(self, results_or_features):
+    def feature_bank(self, results_or_features, budget=None):
         """A FeatureBank of this context: feature sets kept on the device in the layout the pairs calls scan.  From one
         ExtractResult or a sequence of them (akz_bank_create_from_results: every image of every result is a set, in order; the
         descriptor rows never leave the device, and the results may be closed at once), or from a sequence of (keypoints,
         descriptors) host sets (akz_bank_create_from_sets: packed and uploaded once).  Pass it as `features` to
-        match_features_seeded_pairs / match_features_seeded_pose_pairs; close() it when done."""
+        match_features_seeded_pairs / match_features_seeded_pose_pairs; close() it when done.
+        budget: a KeypointBudget cuts every set as keypoint_budget_host would, on the device (akz_bank_create_from_results_budget /
+        _from_sets_budget): the bank equals feature_bank of the sliced host sets, and FeatureBank.indices() names the keypoints kept."""
         src = results_or_features
+        if budget is not None and not isinstance(budget, KeypointBudget):
+            raise TypeError(f"budget must be a KeypointBudget or None, got {type(budget).__name__}")
         if isinstance(src, ExtractResult):
             src = [src]
         if isinstance(src, (str, bytes, FeatureBank)) or not hasattr(src, "__len__"):
@@ -1225,7 +1233,10 @@ class Context:
         h = C.c_void_p()
         if len(src) and all(isinstance(r, ExtractResult) for r in src):
             arr = (C.c_void_p * len(src))(*[r._h for r in src])
-            _check(lib().akz_bank_create_from_results(self._h, arr, len(src), C.byref(h)))
+            if budget is not None:
+                _check(lib().akz_bank_create_from_results_budget(self._h, arr, len(src), C.byref(budget), C.byref(h)))
+            else:
+                _check(lib().akz_bank_create_from_results(self._h, arr, len(src), C.byref(h)))
             return FeatureBank(self, h)
         if any(isinstance(r, ExtractResult) for r in src):
             raise TypeError("feature_bank takes results or host sets, not a mixture")
@@ -1242,7 +1253,10 @@ class Context:
         for i, (k, d) in enumerate(zip(ks, ds)):
             nd = len(d) if d.ndim == 2 else 0
             sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), d.ctypes.data_as(C.c_void_p) if nd else None, nd)
-        _check(lib().akz_bank_create_from_sets(self._h, C.cast(sets, C.c_void_p), len(ks), nb, C.byref(h)))
+        if budget is not None:
+            _check(lib().akz_bank_create_from_sets_budget(self._h, C.cast(sets, C.c_void_p), len(ks), nb, C.byref(budget), C.byref(h)))
+        else:
+            _check(lib().akz_bank_create_from_sets(self._h, C.cast(sets, C.c_void_p), len(ks), nb, C.byref(h)))
         return FeatureBank(self, h)
 
     def debug_bank_gather(self, src, desc_bytes, dst):
@@ -1251,6 +1265,20 @@ class Context:
         import torch
         torch.cuda.current_stream(src.device).synchronize()
         _check(lib().akz_debug_bank_gather(self._h, C.c_void_p(src.data_ptr()), int(src.shape[0]), int(desc_bytes), C.c_void_p(dst.data_ptr())))
+
+    def debug_bank_select(self, src, sx, sy, n, keep, indices, desc_bytes, rows, x, y, index):
+        """akz_debug_bank_select: k_bank_select alone.  src [sum n, 64] uint8, sx, sy [sum n] float32: torch CUDA tensors, the sets'
+        sources packed one behind the other; n, keep: per set; indices: the kept indices of every set one behind the other (the
+        hook refuses lists that do not ascend or reach n).  rows [>= sum keep, 64] uint8, x, y float32 and index int32 /
+        uint32 [>= sum keep]: torch CUDA tensors that receive the selection; complete on return."""
+        import torch
+        torch.cuda.current_stream(src.device).synchronize()
+        n, keep = np.ascontiguousarray(n, np.uint64), np.ascontiguousarray(keep, np.uint64)
+        idx = np.ascontiguousarray(indices, np.uint32)
+        _check(lib().akz_debug_bank_select(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(sx.data_ptr()), C.c_void_p(sy.data_ptr()), len(n),
+                                           n.ctypes.data_as(C.POINTER(C.c_uint64)), keep.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           idx.ctypes.data_as(C.POINTER(C.c_uint32)), int(desc_bytes), C.c_void_p(rows.data_ptr()),
+                                           C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(index.data_ptr())))
 
     def match_features_seeded_pairs(self, features, pairs, options=None, cross_check=False):
         """match_features over many pairs with the seeded RANSAC (akz_match_features_seeded_pairs): the trial kernel draws its
@@ -1588,6 +1616,19 @@ class FeatureBank:
             _check(lib().akz_bank_set_info(self._h, k, C.byref(nk), C.byref(nd), C.byref(r0)))
             sets.append(dict(n_keypoints=nk.value, n_descriptors=nd.value, row0=r0.value))
         return dict(n_sets=n.value, desc_bytes=nb.value, rows=rows.value, sets=sets)
+
+    def indices(self, set=None):
+        """akz_bank_set_indices: for every row of set `set`, the index in its source set of the keypoint it came from, a uint64
+        array -- what keypoint_budget_host kept for a bank made with a budget, arange otherwise; set=None: a list of them, one
+        per set.  It carries a match record's index_0 / index_1 over the bank back to the extraction result."""
+        sets = self.info()["sets"]
+        if set is None:
+            return [self.indices(k) for k in range(len(sets))]
+        if not 0 <= int(set) < len(sets):
+            raise IndexError(f"set index {set} >= n_sets {len(sets)}")
+        out = np.zeros(sets[int(set)]["n_keypoints"], np.uint64)
+        _check(lib().akz_bank_set_indices(self._h, int(set), out.ctypes.data_as(C.POINTER(C.c_uint64)) if len(out) else None))
+        return out
 
     def device(self):
         """(address of the rows [rows, 64] uint8, of x [rows] float32, of y [rows] float32) on the device; read-only, valid until close()."""

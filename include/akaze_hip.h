@@ -1075,6 +1075,34 @@ int akz_bank_create_from_results(akz_ctx* ctx, const akz_result* const* results,
    akz_match_features_pairs refuses for a set a pair names (more descriptors than keypoints, NULL keypoints or descriptors where
    there are some), desc_bytes outside 1..64, NULL sets while n_sets > 0, a NULL ctx or out. */
 int akz_bank_create_from_sets(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, uint64_t desc_bytes, akz_bank** out);
+/* A bank under a keypoint budget (akz_keypoint_budget, below): every set cut by akz_keypoint_budget_host.  With K_s, D_s the
+   n_s keypoints and descriptors of source set s and idx_s what akz_keypoint_budget_host(K_s, n_s, budget, ...) returns, set s of
+   the bank is (K_s[idx_s], D_s[idx_s]) in that ascending order, and the bank is byte for byte the one akz_bank_create_from_sets
+   builds from those sliced host sets -- rows, the zero bytes at or beyond desc_bytes, x, y, akz_bank_info and akz_bank_set_info
+   (n_keypoints = n_descriptors = min(max_keypoints, n_s)) -- so every bank call returns over it the bytes of the sets call over
+   the sliced sets.  max_keypoints >= every n_s gives the bytes of the unbudgeted constructor, max_keypoints = 0 a bank of
+   n_sets empty sets.  akz_bank_set_indices gives idx_s back.
+   From results, the sets are those of akz_bank_create_from_results.  x, y and response of the results' host keypoints are uploaded
+   once, the budget's kernels leave every set's kept indices on the device, and ONE launch (k_bank_select) gathers rows, x and y
+   through them into the bank, whatever the number of sets; the kept indices come to the host with the call's one
+   synchronisation.  No row of a result leaves the device.  Complete on return: the results may be freed at once.
+   Refusals (AKZ_ERR_INVALID_ARG, *out = NULL, before any GPU work and before any allocation; the message names the result and
+   the image): those of akz_bank_create_from_results, and the budget's -- a NULL budget, an unknown mode, SPREAD with robust
+   outside (0, 1], a keypoint whose x, y or response is not finite, more than 2^31 - 1 keypoints in the call. */
+typedef struct akz_keypoint_budget akz_keypoint_budget;
+int akz_bank_create_from_results_budget(akz_ctx* ctx, const akz_result* const* results, uint64_t n_results,
+                                        const akz_keypoint_budget* budget, akz_bank** out);
+/* The same from host sets: the full sets are packed and uploaded to the context's staging as akz_match_features_pairs uploads
+   them, and the same budget and the same launch select from there into the bank.  Refusals: those of akz_bank_create_from_sets,
+   the budget's (the message names the set), and a set with n_descriptors != n_keypoints -- the budget is defined over keypoints
+   that all have a row. */
+int akz_bank_create_from_sets_budget(akz_ctx* ctx, const akz_feature_set* sets, uint64_t n_sets, uint64_t desc_bytes,
+                                     const akz_keypoint_budget* budget, akz_bank** out);
+/* For every row of a set, in order, the index in its source set of the keypoint the row came from, so that the index_0 / index_1
+   of a match record over the bank can be carried back to the extraction result: idx_s for a budgeted bank, the identity
+   0 .. n - 1 for a bank of the two constructors without a budget.  Plain host code: the bank keeps the indices on the host.
+   Refusals: a NULL bank, NULL indices for a set that is not empty, a set index >= n_sets. */
+int akz_bank_set_indices(const akz_bank* bank, uint64_t set, uint64_t* indices /* that set's n_keypoints */);
 /* n_sets, desc_bytes and the rows of all sets; each pointer may be NULL. */
 int akz_bank_info(const akz_bank* bank, uint64_t* n_sets, uint64_t* desc_bytes, uint64_t* rows);
 /* One set's counts and its first row in the bank's buffers; each pointer may be NULL.  A set index >= n_sets is refused. */

@@ -140,10 +140,13 @@ int akz_ctx_calibrate_gates(akz_ctx* ctx, uint64_t* sync_px, uint64_t* async_px,
    (profiling level 2): k_mask_candidates, param = masks (1: shared, else n), (w, h, n) = the frames, px = the list's capacity.
    One launch per job, one more for every extrema pass the overflow path redid; unmasked jobs leave no such row.
    akz_bank_create_from_results adds one row of stage 10 per bank with at least one row: k_bank_gather, ONE launch, param =
-   desc_bytes, w = 64, h = the bank's rows, n = its segments (images), px = rows copied. */
+   desc_bytes, w = 64, h = the bank's rows, n = its segments (images), px = rows copied.
+   akz_bank_create_from_results_budget / _from_sets_budget add, instead, one row of stage 10 per bank with at least one row:
+   k_bank_select, ONE launch, param = desc_bytes, w = 64, h = the bank's rows, n = its sets, px = rows kept. */
 enum { AKZ_KR_LEVEL_MARCH = 1, AKZ_KR_FED_OWN = 2, AKZ_KR_OCTAVE_RESIDENT = 3, AKZ_KR_DETECTOR_TILED = 4, AKZ_KR_DETECTOR_MARCH = 5,
        AKZ_KR_JPEG_IDCT = 6, AKZ_KR_JPEG_LUMA = 7, AKZ_KR_JPEG_COPY = 8, AKZ_KR_SORT_ROWS = 9, AKZ_KR_SORT_BUCKETS = 10,
-       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12, AKZ_KR_MASK_CANDIDATES = 13, AKZ_KR_BANK_GATHER = 14 };
+       AKZ_KR_SORT_RADIX = 11, AKZ_KR_FRAME_LUMA = 12, AKZ_KR_MASK_CANDIDATES = 13, AKZ_KR_BANK_GATHER = 14,
+       AKZ_KR_BANK_SELECT = 15 };
 typedef struct akz_kernel_row {
     uint32_t stage, kind, param, w, h, n;
     uint64_t launches, px, px_steps;
@@ -212,6 +215,16 @@ int akz_debug_mask_counts(akz_ctx* ctx, uint64_t out[3]);
    the code path akz_bank_create_from_results takes; complete on return.  Bytes of a row at or beyond desc_bytes (1..64) arrive as
    zero whatever d_src holds there. */
 int akz_debug_bank_gather(akz_ctx* ctx, const uint8_t* d_src, uint64_t n_rows, uint64_t desc_bytes, uint8_t* d_dst);
+/* Test hook: the budgeted bank's kernel alone (k_bank_select, csrc/akz_bank.hip) on caller-made inputs, through the code path
+   the budgeted constructors take; complete on return.  On the device: the source rows of n_sets sets packed one behind the
+   other (sum of n rows of 64 bytes at d_src, 16-byte aligned) and their x and y (sum of n floats each).  On the host: every
+   set's n and keep, and the keep indices of every set one behind the other -- per set ascending and below n, which the hook
+   checks, refusing otherwise before anything is uploaded or launched.  On the device afterwards, for the sum of keep rows:
+   d_rows (64 bytes each, the bytes at or beyond desc_bytes zero), d_x, d_y and d_index (the u32 source index of every row).
+   The hook's table holds an empty record of its own in front of and behind the caller's sets. */
+int akz_debug_bank_select(akz_ctx* ctx, const uint8_t* d_src, const float* d_sx, const float* d_sy, uint64_t n_sets, const uint64_t* n,
+                          const uint64_t* keep, const uint32_t* indices, uint64_t desc_bytes, uint8_t* d_rows, float* d_x, float* d_y,
+                          uint32_t* d_index);
 
 /* The samples akz_match_features / akz_match_features_pairs draw for `trials` RANSAC trials over n_matches matches, from a
    source of their own seeded [s0, s1] (the calling thread's source is untouched): 8 ascending indices per trial. */
