@@ -3,7 +3,8 @@
 // are placed once.  akz_bank_create_from_results: bank_segments (the table, plain host code), x / y from the results' host
 // keypoints through pinned staging, and launch::bank_gather (akz_bank.hip) -- ONE launch -- over the results' device rows.
 // akz_bank_create_from_sets: the packing and the copies of pairs_upload (akz_match_api.cpp) into the bank's block.  The two bank
-// forms of the seeded pairs calls are those calls with the bank handed down to pairs_front (akz_match_seeded_api.cpp).
+// forms of the seeded pairs calls are those calls with the bank in their PairsCall (akz_match_seeded_api.cpp).  A bank's block and
+// the context's staging are SetsBlocks (akz_pairs_layout.hpp), every set placed in index order.
 // The two constructors under a keypoint budget (bank_create_budgeted): the budget's plan / enqueue half (budget_enqueue,
 // akz_budget_api.cpp) leaves every set's kept indices on the device, and launch::bank_select -- ONE launch -- gathers rows, x and y
 // through them, from the results' row blocks or from the full sets that pairs_upload put into the context's staging.
@@ -37,25 +38,13 @@ uint64_t bank_segments(const akz_result* const* results, uint64_t n_results, std
     }
     return rows;
 }
-// the bank's block for `rows` rows: rows | x | y (| src, the source indices of a budgeted bank), every part on 256 bytes
-int bank_alloc(akz_ctx* c, akz_bank* b, uint64_t rows, bool with_src = false) {
-    const uint64_t rows1 = std::max<uint64_t>(rows, 1);
-    const size_t b_rows = up256((size_t)rows1 * 64), b_xy = up256((size_t)rows1 * 4);
-    AKZ_HIP_TRY(b->dev.acquire(b_rows + 2 * b_xy + (with_src ? b_xy : 0), false));
+// the block of the bank's sets, every set behind the one before it (with_src: with the source indices of a budgeted bank)
+int bank_alloc(akz_ctx* c, akz_bank* b, bool with_src = false) {
+    b->block.place(b->sets.data(), b->sets.size(), index_order(b->sets.size()));
+    AKZ_HIP_TRY(b->dev.acquire(b->block.bytes(with_src), false));
     AKZ_HIP_TRY(alloc_fill(c, b->dev.p, b->dev.bytes));
-    b->rows = rows;
-    b->d_rows = (uint8_t*)b->dev.p;
-    b->d_kx = (float*)(b->d_rows + b_rows), b->d_ky = (float*)(b->d_rows + b_rows + b_xy);
-    if (with_src) b->d_src = (uint32_t*)(b->d_rows + b_rows + 2 * b_xy);
+    b->block.bind(b->dev.p, with_src);
     return AKZ_OK;
-}
-void bank_place(akz_bank* b) {  // every set behind the one before it
-    b->set_row.assign(b->sets.size(), 0);
-    uint64_t rows = 0;
-    for (size_t k = 0; k < b->sets.size(); ++k) {
-        b->set_row[k] = rows;
-        rows += b->sets[k].n_descriptors;
-    }
 }
 akz_bank* bank_keep(akz_ctx* c, std::unique_ptr<akz_bank>& b) {
     b->ctx = c;
@@ -69,9 +58,7 @@ int bank_gather_enqueue(akz_ctx* c, const std::vector<launch::BankSeg>& segs, si
     hipStream_t st = c->stream;
     const size_t b_tab = segs.size() * sizeof(launch::BankSeg);
     AKZ_TRY(ensure(c, c->mp_tab, b_tab));
-    char* h_tab = (char*)c->mp_pin_in.p + pin_off;
-    std::memcpy(h_tab, segs.data(), b_tab);
-    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_tab.p, h_tab, b_tab, hipMemcpyHostToDevice, st));
+    AKZ_TRY(table_upload(c, c->mp_tab.p, (char*)c->mp_pin_in.p + pin_off, segs.data(), b_tab));
     StageTimer t(c, kStageIngest, st);
     t.kernel(AKZ_KR_BANK_GATHER, (uint32_t)desc_bytes, 64, (uint32_t)std::min<uint64_t>(rows, 0xffffffffull), (uint32_t)segs.size(), 1, rows);
     launch::bank_gather(st, (const launch::BankSeg*)c->mp_tab.p, (uint32_t)segs.size(), rows, (uint32_t)desc_bytes, d_dst);
@@ -110,9 +97,7 @@ int bank_select_enqueue(akz_ctx* c, const std::vector<launch::BankSel>& tab, siz
     hipStream_t st = c->stream;
     const size_t b_tab = tab.size() * sizeof(launch::BankSel);
     AKZ_TRY(ensure(c, c->mp_tab, b_tab));
-    char* h_tab = (char*)c->mp_pin_in.p + pin_off;
-    std::memcpy(h_tab, tab.data(), b_tab);
-    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_tab.p, h_tab, b_tab, hipMemcpyHostToDevice, st));
+    AKZ_TRY(table_upload(c, c->mp_tab.p, (char*)c->mp_pin_in.p + pin_off, tab.data(), b_tab));
     StageTimer t(c, kStageIngest, st);
     t.kernel(AKZ_KR_BANK_SELECT, (uint32_t)desc_bytes, 64, (uint32_t)std::min<uint64_t>(rows, 0xffffffffull), (uint32_t)tab.size(), 1, rows);
     launch::bank_select(st, (const launch::BankSel*)c->mp_tab.p, (uint32_t)tab.size(), rows, (uint32_t)desc_bytes, d_idx, d_sx, d_sy, d_rows, d_x,
@@ -135,19 +120,18 @@ int bank_create_budgeted(akz_ctx* c, const std::vector<akz_feature_set>& sets, c
         const uint64_t keep = std::min<uint64_t>(o.max_keypoints, s.n_keypoints);
         b->sets.push_back(akz_feature_set{nullptr, keep, nullptr, keep});
     }
-    bank_place(b.get());
-    uint64_t rows = 0;
-    for (const akz_feature_set& s : b->sets) rows += s.n_descriptors;
-    AKZ_TRY(bank_alloc(c, b.get(), rows, true));
+    AKZ_TRY(bank_alloc(c, b.get(), true));
+    const SetsBlock& blk = b->block;
+    const uint64_t rows = blk.rows;
     AKZ_TRY(place());
     BudgetPlan p;
     AKZ_TRY(budget_enqueue(c, sets.data(), sets.size(), o, p));
     std::vector<launch::BankSel> tab;
     for (size_t s = 0; s < sets.size(); ++s)
-        tab.push_back(launch::BankSel{p.tab[s].keep ? src_rows[s] : nullptr, p.tab[s].base, p.tab[s].keep, b->set_row[s], p.tab[s].out_off});
-    AKZ_TRY(bank_select_enqueue(c, tab, pin_off, rows, desc_bytes, p.d_idx, p.d_x, p.d_y, b->d_rows, b->d_kx, b->d_ky, b->d_src));
+        tab.push_back(launch::BankSel{p.tab[s].keep ? src_rows[s] : nullptr, p.tab[s].base, p.tab[s].keep, blk.set_row[s], p.tab[s].out_off});
+    AKZ_TRY(bank_select_enqueue(c, tab, pin_off, rows, desc_bytes, p.d_idx, p.d_x, p.d_y, blk.d_rows, blk.d_kx, blk.d_ky, blk.d_src));
     hipStream_t st = c->stream;
-    if (rows) AKZ_HIP_TRY(hipMemcpyAsync(p.h_down, b->d_src, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    if (rows) AKZ_HIP_TRY(hipMemcpyAsync(p.h_down, blk.d_src, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
     AKZ_HIP_TRY(hipStreamSynchronize(st));  // complete on return: the sources may go
     if (rows) b->src.assign((const uint32_t*)p.h_down, (const uint32_t*)p.h_down + rows);
     *out = bank_keep(c, b);
@@ -168,10 +152,9 @@ int akz_bank_create_from_results(akz_ctx* c, const akz_result* const* results, u
     std::vector<launch::BankSeg> segs;
     bank_segments(results, n_results, segs);
     for (const launch::BankSeg& s : segs) b->sets.push_back(akz_feature_set{nullptr, s.n_rows, nullptr, s.n_rows});
-    bank_place(b.get());
-    AKZ_TRY(bank_alloc(c, b.get(), rows));
+    AKZ_TRY(bank_alloc(c, b.get()));
     // x | y of every keypoint, then the table, in pinned memory: one copy each
-    const size_t b_xy = up256((size_t)std::max<uint64_t>(rows, 1) * 4);
+    const size_t b_xy = b->block.b_xy;
     AKZ_TRY(ensure_pinned(c, c->mp_pin_in, 2 * b_xy + segs.size() * sizeof(launch::BankSeg)));
     float *hx = (float*)c->mp_pin_in.p, *hy = (float*)((char*)c->mp_pin_in.p + b_xy);
     uint64_t at = 0;
@@ -180,10 +163,10 @@ int akz_bank_create_from_results(akz_ctx* c, const akz_result* const* results, u
             for (const akz_keypoint& k : kps) hx[at] = k.x, hy[at] = k.y, ++at;
     hipStream_t st = c->stream;
     if (rows) {
-        AKZ_HIP_TRY(hipMemcpyAsync(b->d_kx, hx, (size_t)rows * 4, hipMemcpyHostToDevice, st));
-        AKZ_HIP_TRY(hipMemcpyAsync(b->d_ky, hy, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipMemcpyAsync(b->block.d_kx, hx, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+        AKZ_HIP_TRY(hipMemcpyAsync(b->block.d_ky, hy, (size_t)rows * 4, hipMemcpyHostToDevice, st));
     }
-    AKZ_TRY(bank_gather_enqueue(c, segs, 2 * b_xy, rows, b->desc_bytes, b->d_rows));
+    AKZ_TRY(bank_gather_enqueue(c, segs, 2 * b_xy, rows, b->desc_bytes, b->block.d_rows));
     AKZ_HIP_TRY(hipStreamSynchronize(st));  // complete on return: the results may go
     *out = bank_keep(c, b);
     return AKZ_OK;
@@ -195,30 +178,16 @@ int akz_bank_create_from_sets(akz_ctx* c, const akz_feature_set* sets, uint64_t 
     if (!out) return refuse(name + "null out");
     if (desc_bytes == 0 || desc_bytes > 64) return refuse(name + "desc_bytes must be 1..64");
     if (n_sets && !sets) return refuse(name + "null sets");
-    uint64_t rows = 0;
-    for (uint64_t k = 0; k < n_sets; ++k) {
-        const akz_feature_set& s = sets[k];
-        const std::string at = name + "set " + std::to_string(k) + ": ";
-        if (s.n_descriptors > s.n_keypoints) return refuse(at + "more descriptors than keypoints");
-        if ((s.n_keypoints && !s.keypoints) || (s.n_descriptors && !s.descriptors)) return refuse(at + "null keypoints or descriptors");
-        rows += s.n_descriptors;
-    }
+    for (uint64_t k = 0; k < n_sets; ++k)
+        if (const char* why = set_refusal(sets[k])) return refuse(name + "set " + std::to_string(k) + ": " + why);
     if (!c) return refuse(name + "null context");
     AKZ_TRY(bind(c));
     std::unique_ptr<akz_bank> b(new akz_bank);
     b->desc_bytes = desc_bytes;
     for (uint64_t k = 0; k < n_sets; ++k) b->sets.push_back(akz_feature_set{nullptr, sets[k].n_keypoints, nullptr, sets[k].n_descriptors});
-    bank_place(b.get());
-    AKZ_TRY(bank_alloc(c, b.get(), rows));
-    PairsFront f;  // every set, in order, as pairs_open would have placed it had every set been named
-    f.set_row = b->set_row;
-    for (uint64_t k = 0; k < n_sets; ++k) f.used.push_back(k);
-    f.rows = rows;
-    const uint64_t rows1 = std::max<uint64_t>(rows, 1);
-    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4);
-    f.d_rows = b->d_rows, f.d_kx = b->d_kx, f.d_ky = b->d_ky;
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, f.b_rows + 2 * f.b_xy));
-    if (rows) AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));
+    AKZ_TRY(bank_alloc(c, b.get()));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, b->block.bytes(false)));
+    if (b->block.rows) AKZ_TRY(pairs_upload(c, sets, desc_bytes, b->block, index_order(n_sets)));
     AKZ_HIP_TRY(hipStreamSynchronize(c->stream));
     *out = bank_keep(c, b);
     return AKZ_OK;
@@ -264,39 +233,31 @@ int akz_bank_create_from_sets_budget(akz_ctx* c, const akz_feature_set* sets, ui
         if (s.n_descriptors != s.n_keypoints)
             return refuse(name + at + std::to_string(s.n_descriptors) + " descriptors for " + std::to_string(s.n_keypoints) +
                           " keypoints (the budget is defined over keypoints that all have a row)");
-        if ((s.n_keypoints && !s.keypoints) || (s.n_descriptors && !s.descriptors)) return refuse(name + at + "null keypoints or descriptors");
+        if (const char* why = set_refusal(s)) return refuse(name + at + why);  // (null pointers: the counts are equal)
         if (!budget_set_ok(name.c_str(), at, s.keypoints, s.n_keypoints)) return AKZ_ERR_INVALID_ARG;
         rows += s.n_descriptors;
         if (rows > kBudgetMaxKeypoints) return refuse(name + at + "the sets of one call hold more than 2^31 - 1 keypoints together");
     }
     if (!c) return refuse(name + "null context");
     AKZ_TRY(bind(c));
-    // the FULL sets to the context's staging, placed as pairs_open places sets that every pair names
-    PairsFront f;
-    uint64_t at = 0;
-    for (uint64_t k = 0; k < n_sets; ++k) {
-        f.set_row.push_back(at);
-        f.used.push_back(k);
-        at += sets[k].n_descriptors;
-    }
-    f.rows = rows;
-    const uint64_t rows1 = std::max<uint64_t>(rows, 1);
-    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4);
-    AKZ_TRY(ensure(c, c->mp_in, f.b_rows + 2 * f.b_xy));
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, f.b_rows + 2 * f.b_xy + (size_t)n_sets * sizeof(launch::BankSel)));
-    f.d_rows = (uint8_t*)c->mp_in.p;
-    f.d_kx = (float*)(f.d_rows + f.b_rows), f.d_ky = (float*)(f.d_rows + f.b_rows + f.b_xy);
+    // the FULL sets to the context's staging, every set in index order
+    const std::vector<uint64_t> order = index_order(n_sets);
+    SetsBlock full;
+    full.place(sets, n_sets, order);
+    AKZ_TRY(ensure(c, c->mp_in, full.bytes(false)));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, full.bytes(false) + (size_t)n_sets * sizeof(launch::BankSel)));
+    full.bind(c->mp_in.p, false);
     std::vector<const uint8_t*> src_rows;
-    for (uint64_t k = 0; k < n_sets; ++k) src_rows.push_back(f.d_rows + f.set_row[(size_t)k] * 64);
+    for (uint64_t k = 0; k < n_sets; ++k) src_rows.push_back(full.d_rows + full.set_row[(size_t)k] * 64);
     const std::vector<akz_feature_set> all(sets, sets + n_sets);
-    return bank_create_budgeted(c, all, src_rows, desc_bytes, *budget, f.b_rows + 2 * f.b_xy,
-                                [&] { return rows ? pairs_upload(c, sets, desc_bytes, f) : (int)AKZ_OK; }, out);
+    return bank_create_budgeted(c, all, src_rows, desc_bytes, *budget, full.bytes(false),
+                                [&] { return rows ? pairs_upload(c, sets, desc_bytes, full, order) : (int)AKZ_OK; }, out);
 }
 
 int akz_bank_set_indices(const akz_bank* b, uint64_t set, uint64_t* indices) {
     if (!b) return refuse("bank_set_indices: null bank");
     if (set >= b->sets.size()) return refuse("bank_set_indices: set index " + std::to_string(set) + " >= n_sets " + std::to_string(b->sets.size()));
-    const uint64_t n = b->sets[(size_t)set].n_keypoints, row0 = b->set_row[(size_t)set];
+    const uint64_t n = b->sets[(size_t)set].n_keypoints, row0 = b->block.set_row[(size_t)set];
     if (n && !indices) return refuse("bank_set_indices: null indices for a set of " + std::to_string(n) + " keypoints");
     for (uint64_t t = 0; t < n; ++t) indices[t] = b->budgeted ? b->src[(size_t)(row0 + t)] : t;
     return AKZ_OK;
@@ -306,7 +267,7 @@ int akz_bank_info(const akz_bank* b, uint64_t* n_sets, uint64_t* desc_bytes, uin
     if (!b) return refuse("bank_info: null bank");
     if (n_sets) *n_sets = b->sets.size();
     if (desc_bytes) *desc_bytes = b->desc_bytes;
-    if (rows) *rows = b->rows;
+    if (rows) *rows = b->block.rows;
     return AKZ_OK;
 }
 
@@ -315,15 +276,15 @@ int akz_bank_set_info(const akz_bank* b, uint64_t set, uint64_t* n_keypoints, ui
     if (set >= b->sets.size()) return refuse("bank_set_info: set index " + std::to_string(set) + " >= n_sets " + std::to_string(b->sets.size()));
     if (n_keypoints) *n_keypoints = b->sets[(size_t)set].n_keypoints;
     if (n_descriptors) *n_descriptors = b->sets[(size_t)set].n_descriptors;
-    if (row0) *row0 = b->set_row[(size_t)set];
+    if (row0) *row0 = b->block.set_row[(size_t)set];
     return AKZ_OK;
 }
 
 int akz_bank_device(const akz_bank* b, const uint8_t** d_rows, const float** d_x, const float** d_y) {
     if (!b) return refuse("bank_device: null bank");
-    if (d_rows) *d_rows = b->d_rows;
-    if (d_x) *d_x = b->d_kx;
-    if (d_y) *d_y = b->d_ky;
+    if (d_rows) *d_rows = b->block.d_rows;
+    if (d_x) *d_x = b->block.d_kx;
+    if (d_y) *d_y = b->block.d_ky;
     return AKZ_OK;
 }
 
@@ -343,8 +304,8 @@ int akz_match_features_seeded_bank_pairs(akz_ctx* c, const akz_bank* bank, const
                                          int* found, uint32_t* iterations, uint64_t* trials_run) {
     const char* name = "match_features_seeded_bank_pairs: ";
     if (!bank) return refuse(std::string(name) + "null bank");
-    return match_seeded_pairs_impl(name, cross_check != 0, c, bank->sets.data(), bank->sets.size(), pairs, n_pairs, bank->desc_bytes, options, out,
-                                   n_out, model, found, iterations, trials_run, nullptr, bank);
+    return match_seeded_pairs_impl({name, c, bank->sets.data(), bank->sets.size(), pairs, n_pairs, bank->desc_bytes, out, n_out, bank}, cross_check != 0,
+                                   options, model, found, iterations, trials_run);
 }
 
 int akz_match_features_seeded_pose_bank_pairs(akz_ctx* c, const akz_bank* bank, const akz_camera* cameras, const uint64_t* pairs,
@@ -355,8 +316,8 @@ int akz_match_features_seeded_pose_bank_pairs(akz_ctx* c, const akz_bank* bank, 
     if (!bank) return refuse(std::string(name) + "null bank");
     AKZ_TRY(pose_pairs_refusals(name, options, cameras, bank->sets.size(), poses));
     const SeededPose pose{cameras, poses, points};
-    return match_seeded_pairs_impl(name, cross_check != 0, c, bank->sets.data(), bank->sets.size(), pairs, n_pairs, bank->desc_bytes, options, out,
-                                   n_out, model, found, iterations, trials_run, &pose, bank);
+    return match_seeded_pairs_impl({name, c, bank->sets.data(), bank->sets.size(), pairs, n_pairs, bank->desc_bytes, out, n_out, bank}, cross_check != 0,
+                                   options, model, found, iterations, trials_run, &pose);
 }
 
 int akz_debug_bank_gather(akz_ctx* c, const uint8_t* d_src, uint64_t n_rows, uint64_t desc_bytes, uint8_t* d_dst) {

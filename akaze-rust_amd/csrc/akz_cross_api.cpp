@@ -124,10 +124,13 @@ int akz_descriptor_match_cross(akz_ctx* c, const uint8_t* d0, uint64_t n0, const
     AKZ_HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), rows.size(), hipMemcpyHostToDevice, st));
     akz_feature_set sets[2] = {{nullptr, 0, nullptr, n0}, {nullptr, 0, nullptr, n1}};  // (pairs_scans reads the row counts alone)
     const uint64_t pair[2] = {0, 1};
-    const std::vector<uint64_t> set_row = {0, n0};
+    // (pairs_scans reads c, sets, n_sets, pairs, n_pairs and desc_bytes of the call, set_row and d_rows of the block)
+    SetsBlock block;
+    block.place(sets, 2, {0, 1});
+    block.d_rows = d_rows;
     std::vector<launch::PairJobHost> tab;
     std::vector<launch::CrossJobHost> xtab;
-    AKZ_TRY(pairs_scans(c, sets, 2, pair, 1, desc_bytes, lowes_ratio, set_row, d_rows, d_fwd, d_cnt, tab, d_rev, d_rcnt, &xtab, distance_threshold));
+    AKZ_TRY(pairs_scans({"", c, sets, 2, pair, 1, desc_bytes, nullptr, nullptr, nullptr}, lowes_ratio, block, d_fwd, d_cnt, tab, d_rev, d_rcnt, &xtab, distance_threshold));
     launch::pair_cross_filter(st, xtab[0], d_fwd, d_cnt, d_rev, d_rcnt);
     AKZ_HIP_TRY(hipGetLastError());
     uint64_t cnt = 0;
@@ -150,8 +153,8 @@ int akz_debug_match_tile_rows(uint32_t* rows) {  // include/akaze_hip_debug.h
 int akz_match_features_seeded_cross_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                                           uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out, float* model,
                                           int* found, uint32_t* iterations, uint64_t* trials_run) {
-    return match_seeded_pairs_impl("match_features_seeded_cross_pairs: ", true, c, sets, n_sets, pairs, n_pairs, desc_bytes, options, out, n_out,
-                                   model, found, iterations, trials_run);
+    return match_seeded_pairs_impl({"match_features_seeded_cross_pairs: ", c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, nullptr}, true,
+                                   options, model, found, iterations, trials_run);
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include "akz_select.hpp"
 #include "akz_pool.hpp"
 #include "akz_gates.hpp"
+#include "akz_pairs_layout.hpp"
 
 // functions shared by the library's translation units, none of them exported
 #define AKZ_LOCAL __attribute__((visibility("hidden")))
@@ -595,7 +596,6 @@ AKZ_LOCAL inline hipError_t sync_all_streams(akz_ctx* c, unsigned which = kSyncA
         if ((which & kSyncSide) && s) wait(s);
     return first;
 }
-AKZ_LOCAL inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }  // the parts of one buffer start on 256 bytes
 // akz_debug_set_alloc_fill: what hipMalloc returned holds 0xA5 bytes before anybody sees it (a debug mode: a fill and a wait)
 constexpr int kAllocFillByte = 0xA5;
 AKZ_LOCAL inline hipError_t alloc_fill(const akz_ctx* c, void* p, size_t bytes) {
@@ -719,13 +719,25 @@ struct RefineStage {  // the refit stage of akz_match_features_{homography,funda
     uint32_t max_iterations;
     uint32_t* iterations;  // one per pair, may be null
 };
+// The inputs of a pairs call as its entry point got them.  bank: the sets lie in a feature bank; sets, n_sets and desc_bytes are then the
+// bank's (counts alone, both pointers of a set null).  Null: the caller's sets.
+struct PairsCall {
+    const char* name;  // the prefix of the entry point's error texts
+    akz_ctx* c;
+    const akz_feature_set* sets;
+    uint64_t n_sets;
+    const uint64_t* pairs;
+    uint64_t n_pairs, desc_bytes;
+    akz_match* out;
+    uint64_t* n_out;
+    const akz_bank* bank;
+};
 // What the opening of a pairs call leaves to the rest of it.  pairs_open fills the first group, pairs_front the second.
 struct AKZ_LOCAL PairsFront {
-    std::vector<uint64_t> set_row, used;  // first row of every set a pair names; those sets in order of first use
-    uint64_t rows = 0, cap1 = 0;          // rows of all used sets; the room of `out` (sum of the first sets' descriptors), at least 1
-    size_t b_rows = 0, b_xy = 0, b_cnt = 0;
-    uint8_t* d_rows = nullptr;  // c->mp_in = rows | x | y
-    float *d_kx = nullptr, *d_ky = nullptr;
+    SetsBlock block;             // the sets a pair names in c->mp_in, or the bank's block (akz_pairs_layout.hpp)
+    std::vector<uint64_t> used;  // the sets to upload, in order of first use; none over a bank
+    uint64_t cap1 = 0;           // the room of `out` (sum of the first sets' descriptors), at least 1
+    size_t b_cnt = 0;
 
     bool timed = false;                    // akz_debug_match_pairs_split is on
     std::vector<launch::PairJobHost> tab;  // one record per pair; raw_off, kp0_off, kp1_off and cnt_idx filled in
@@ -736,39 +748,19 @@ struct AKZ_LOCAL PairsFront {
     uint64_t* h_cnt = nullptr;                               // (read back; valid after the caller's synchronise)
     char *d_own = nullptr, *h_own = nullptr;
 };
-// The head of c->mp_keep and of its pinned image c->mp_pin_out: kept counts | models | found | accepted fits | trials run | poses |
-// points (3 floats per kept record, where want_points), then the kept lists.  The caller sets the five byte counts (0: the field is
-// absent) and want_points, pairs_keep the rest.
-struct PairsKeep {
-    size_t b_model, b_found, b_fits, b_trials;
-    size_t b_pose = 0;
-    bool want_points = false;
-    size_t b_points = 0;
-    size_t b_head = 0;
-    uint64_t n_keep = 0;
-    uint64_t* d_kcnt = nullptr;
-    float* d_hm = nullptr;
-    int32_t* d_hf = nullptr;
-    uint32_t *d_it = nullptr, *d_tr = nullptr;
-    akz_pose* d_pose = nullptr;
-    float* d_points = nullptr;
-    akz_match* d_keep = nullptr;
-};
+// (PairsKeep, the kept block of c->mp_keep and c->mp_pin_out: akz_pairs_layout.hpp)
 // A feature bank (akz_bank_api.cpp; include/akaze_hip.h): feature sets resident on the device in the layout the pairs calls scan --
-// `dev` = rows | x | y, the parts on 256 bytes as in c->mp_in, set k's rows and coordinates from row set_row[k] on.  Immutable once
-// created.  It owns `dev` and counts among its context's live objects (akz_ctx::live_results), as a result does.
+// `dev` is the SetsBlock `block`, every set placed in index order.  Immutable once created.  It owns `dev` and counts among its
+// context's live objects (akz_ctx::live_results), as a result does.
 struct akz_bank {
     akz_ctx* ctx = nullptr;
-    uint64_t desc_bytes = 0, rows = 0;
+    uint64_t desc_bytes = 0;
     std::vector<akz_feature_set> sets;  // the counts of every set; both pointers null
-    std::vector<uint64_t> set_row;
+    SetsBlock block;
     DevBuf dev;
-    uint8_t* d_rows = nullptr;
-    float *d_kx = nullptr, *d_ky = nullptr;
-    // a bank under a keypoint budget (akz_bank_create_from_*_budget): `dev` = rows | x | y | src, d_src[r] = the index in its source
+    // a bank under a keypoint budget (akz_bank_create_from_*_budget): the block has its src part, block.d_src[r] = the index in its source
     // set of the keypoint row r came from, and `src` is its host copy (akz_bank_set_indices).  Both absent otherwise: the identity.
     bool budgeted = false;
-    uint32_t* d_src = nullptr;
     std::vector<uint32_t> src;
 };
 // akz_budget_api.cpp: the keypoint budget's refusals and its plan / enqueue half, shared with the budgeted bank (akz_bank_api.cpp).
@@ -790,52 +782,54 @@ struct BudgetPlan {
     char* h_down = nullptr;
 };
 AKZ_LOCAL int budget_enqueue(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const akz_keypoint_budget& o, BudgetPlan& p);
-// akz_match_api.cpp.  pairs_open: the refusals (guided: those of the guided scan too), bind, the placement of every distinct set and
-// the room for its rows.  pairs_front: pairs_open, the upload, the scans (cross: both directions and launch::pairs_cross_filter), the
+// akz_match_api.cpp.  set_refusal: what every call refuses of one feature set, without the prefix that says where (null: nothing).
+// table_upload: a host table to the device through pinned staging, on the context's stream.
+// pairs_open: the refusals (guided: those of the guided scan too), bind, the placement of every distinct set in order of first use and
+// the room for its rows.  pairs_front: the opening, the upload, the scans (cross: both directions and launch::pairs_cross_filter), the
 // table, launch::pair_points and the enqueued read-back of the counts -- it does not synchronise.  b_dev_own / b_pin_own: the caller's
 // bytes behind the table in c->mp_tab and behind the counts in c->mp_pin_tab.
-// bank (pairs_front; `sets` are then the bank's counts): the opening is pairs_open_bank -- the refusals a bank leaves to make, bind, and
-// f's rows, x, y and set_row are the bank's own; nothing is placed or uploaded and c->mp_in / c->mp_pin_in are not touched.  Null: the
-// call enqueues what it always did.
-AKZ_LOCAL int pairs_open(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                         uint64_t desc_bytes, const void* out, const void* n_out, bool guided, PairsFront& f);
-AKZ_LOCAL int pairs_open_bank(const char* name, akz_ctx* c, const akz_bank* bank, const uint64_t* pairs, uint64_t n_pairs, const void* out,
-                              const void* n_out, bool guided, PairsFront& f);
-AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const PairsFront& f);
-AKZ_LOCAL int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                          uint64_t desc_bytes, double lowes_ratio, const void* out, const void* n_out, bool guided, bool cross, size_t b_dev_own,
-                          size_t b_pin_own, PairsFront& f, const akz_bank* bank = nullptr);
+// Over a bank (q.bank) the opening is pairs_open_bank -- the refusals a bank leaves to make, bind, and f.block is the bank's own;
+// nothing is placed or uploaded and c->mp_in / c->mp_pin_in are not touched.  Without one the call enqueues what it always did.
+AKZ_LOCAL const char* set_refusal(const akz_feature_set& s);
+AKZ_LOCAL inline int table_upload(akz_ctx* c, void* d_dst, void* h_pin, const void* tab, size_t bytes) {
+    std::memcpy(h_pin, tab, bytes);
+    AKZ_HIP_TRY(hipMemcpyAsync(d_dst, h_pin, bytes, hipMemcpyHostToDevice, c->stream));
+    return AKZ_OK;
+}
+AKZ_LOCAL int pairs_open(const PairsCall& q, bool guided, PairsFront& f);
+AKZ_LOCAL int pairs_open_bank(const PairsCall& q, bool guided, PairsFront& f);
+// the sets `order` names: rows (padded to 64 bytes) and the x / y of their first n_descriptors keypoints, through c->mp_pin_in
+// (laid out as b) to where b is bound
+AKZ_LOCAL int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const SetsBlock& b, const std::vector<uint64_t>& order);
+AKZ_LOCAL int pairs_front(const PairsCall& q, double lowes_ratio, bool guided, bool cross, size_t b_dev_own, size_t b_pin_own, PairsFront& f);
 AKZ_LOCAL int pairs_table_upload(akz_ctx* c, PairsFront& f);  // f.tab -> f.d_tab through f.h_tab
 AKZ_LOCAL int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k);
 // pairs_tail: launch::pairs_pick_filter over the trials' models and counts (d_mdl, d_inl), launch::model_refit given `refine`,
 // launch::pairs_pose given `pose`, the ONE read-back of head and kept lists, the guided stage given `guided`, the synchronise, the copy-out and the intervals of a timed call
 // (t_host: the caller's host time, interval 2).  model .. trials_run: one per pair, each may be null.
-AKZ_LOCAL int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const PairsFront& f, const PairsKeep& k,
-                         launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine,
-                         float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host, akz_match* out, uint64_t* n_out,
-                         float* model, int* found, uint32_t* fits, uint64_t* trials_run, const PoseStage* pose = nullptr);
+AKZ_LOCAL int pairs_tail(const PairsCall& q, const PairsFront& f, const PairsKeep& k, launch::RansacModel kind, const float* d_mdl,
+                         const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine, float refit_epsilon, const GuidedStage* guided,
+                         int guided_kind, double t_host, float* model, int* found, uint32_t* fits, uint64_t* trials_run,
+                         const PoseStage* pose = nullptr);
 // the lists of a pairs call to out / n_out: pair p's guided list (h_gcnt[p] records at its fixed place in d_gout, fetched by ONE read-back
 // of the span such lists occupy) where h_gcnt is given and h_found is null or h_found[p] set, else its kept list (h_kcnt, h_keep, tab)
-AKZ_LOCAL int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const uint64_t* h_gcnt,
-                             const int32_t* h_found, const akz_match* d_gout, const uint64_t* h_kcnt, const akz_match* h_keep,
-                             const launch::PairJobHost* tab, akz_match* out, uint64_t* n_out);
-// akz_match_api.cpp: the descriptor scans of every pair over the uploaded sets; fills the pair records' raw_off, kp0_off, kp1_off, cnt_idx
+AKZ_LOCAL int pairs_copy_out(const PairsCall& q, const uint64_t* h_gcnt, const int32_t* h_found, const akz_match* d_gout, const uint64_t* h_kcnt,
+                             const akz_match* h_keep, const launch::PairJobHost* tab);
+// akz_match_api.cpp: the descriptor scans of every pair over the sets placed in b; fills the pair records' raw_off, kp0_off, kp1_off, cnt_idx
 // -- and, given `cross`, the opposite direction of every pair to d_rev / d_rcnt with the records of launch::pairs_cross_filter
-AKZ_LOCAL int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
-                          double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
+AKZ_LOCAL int pairs_scans(const PairsCall& q, double lowes_ratio, const SetsBlock& b, akz_match* d_raw, uint64_t* d_cnt,
                           std::vector<launch::PairJobHost>& tab, akz_match* d_rev = nullptr, uint64_t* d_rcnt = nullptr,
                           std::vector<launch::CrossJobHost>* cross = nullptr, uint64_t distance_threshold = 10000);
-// akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device (rows of 64 bytes, x, y), enqueued on the
+// akz_guided_api.cpp: the guided scan of many pairs whose sets lie on the device in b, enqueued on the
 // context's stream -- scan, merge, ratio test and ordered compaction; pair p's list goes to d_out + spec[p].out_off, its
 // length to d_cnt[p].  d_models: 9 floats per pair ON THE DEVICE; d_found (optional): pairs whose flag is 0 give empty lists.
-// guided_specs: every pair's rows as placed by pairs_open, its list at the fixed place out / d_out give it.
+// guided_specs: every pair's rows as placed in b, its list at the fixed place out / d_out give it.
 AKZ_LOCAL int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs,
                             const std::vector<uint8_t>& seen);
-AKZ_LOCAL std::vector<GuidedPairSpec> guided_specs(const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs,
-                                                   const std::vector<uint64_t>& set_row);
-AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
-                             int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
-                             double lowes_ratio, akz_match* d_out, uint64_t* d_cnt);
+AKZ_LOCAL std::vector<GuidedPairSpec> guided_specs(const PairsCall& q, const SetsBlock& b);
+AKZ_LOCAL int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const SetsBlock& b, int kind, const float* d_models,
+                             const int32_t* d_found, float radius, uint64_t distance_threshold, double lowes_ratio, akz_match* d_out,
+                             uint64_t* d_cnt);
 // akz_match_seeded_api.cpp: the seeded pairs call; cross: with cross(A, B) as every pair's raw list (akz_cross_api.cpp); pose: with the
 // pose stage behind it (akz_pose_api.cpp)
 struct SeededPose {
@@ -843,10 +837,8 @@ struct SeededPose {
     akz_pose* poses;            // one per pair
     float* points;              // may be null
 };
-AKZ_LOCAL int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
-                                      uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                                      float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose = nullptr,
-                                      const akz_bank* bank = nullptr);  // bank: sets, n_sets and desc_bytes are the bank's (pairs_front)
+AKZ_LOCAL int match_seeded_pairs_impl(const PairsCall& q, bool cross, const akz_ransac_options* options, float* model, int* found,
+                                      uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose = nullptr);
 // akz_pose_api.cpp: the refusals of akz_match_features_seeded_pose_pairs that are not the seeded call's
 AKZ_LOCAL int pose_pairs_refusals(const char* name, const akz_ransac_options* options, const akz_camera* cameras, uint64_t n_sets,
                                   const akz_pose* poses);

@@ -27,8 +27,8 @@ bool pair_args_ok(const char* name, const akz_keypoint* kp0, uint64_t n_kp0, con
     if (!n_out) why = "null n_out";
     else if (desc_bytes == 0 || desc_bytes > 64) why = "desc_bytes must be 1..64";
     else if (n_d0 > n_kp0 || n_d1 > n_kp1) why = "a feature set has more descriptors than keypoints";
-    else if ((n_kp0 && !kp0) || (n_kp1 && !kp1) || (n_d0 && !d0) || (n_d1 && !d1)) why = "null keypoints or descriptors";
-    else if (n_d0 && !out) why = "null out";
+    else if (!(why = set_refusal({kp0, n_kp0, d0, n_d0})) && !(why = set_refusal({kp1, n_kp1, d1, n_d1})) && n_d0 && !out)
+        why = "null out";  // (the counts have passed: set_refusal can only name the pointers, of set 0 first as before)
     if (why) set_error(std::string(name) + why);
     return why == nullptr;
 }
@@ -56,20 +56,19 @@ int guided_limits(const char* name, const akz_feature_set* sets, const uint64_t*
     return AKZ_OK;
 }
 
-std::vector<GuidedPairSpec> guided_specs(const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const std::vector<uint64_t>& set_row) {
-    std::vector<GuidedPairSpec> spec((size_t)n_pairs);
+std::vector<GuidedPairSpec> guided_specs(const PairsCall& q, const SetsBlock& blk) {
+    std::vector<GuidedPairSpec> spec((size_t)q.n_pairs);
     uint64_t off = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1];
-        spec[(size_t)p] = GuidedPairSpec{set_row[(size_t)a], sets[a].n_descriptors, set_row[(size_t)b], sets[b].n_descriptors, off};
-        off += sets[a].n_descriptors;
+    for (uint64_t p = 0; p < q.n_pairs; ++p) {
+        const uint64_t a = q.pairs[2 * p], b = q.pairs[2 * p + 1];
+        spec[(size_t)p] = GuidedPairSpec{blk.set_row[(size_t)a], q.sets[a].n_descriptors, blk.set_row[(size_t)b], q.sets[b].n_descriptors, off};
+        off += q.sets[a].n_descriptors;
     }
     return spec;
 }
 
-int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const uint8_t* d_rows, const float* d_kx, const float* d_ky,
-                        int kind, const float* d_models, const int32_t* d_found, float radius, uint64_t distance_threshold,
-                        double lowes_ratio, akz_match* d_out, uint64_t* d_cnt) {
+int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const SetsBlock& b, int kind, const float* d_models, const int32_t* d_found,
+                   float radius, uint64_t distance_threshold, double lowes_ratio, akz_match* d_out, uint64_t* d_cnt) {
     hipStream_t st = c->stream;
     const uint32_t thr = clamp_threshold(distance_threshold), block = launch::match_guided_block();
     AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, spec.size() * sizeof(uint64_t), st));
@@ -99,10 +98,9 @@ int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const ui
     AKZ_TRY(ensure(c, c->gd_tab, b_tab));
     AKZ_TRY(ensure(c, c->gd_rec, rec_total * sizeof(MatchRec)));
     AKZ_TRY(ensure_pinned(c, c->gd_pin_tab, b_tab));
-    std::memcpy(c->gd_pin_tab.p, tab.data(), b_tab);
-    AKZ_HIP_TRY(hipMemcpyAsync(c->gd_tab.p, c->gd_pin_tab.p, b_tab, hipMemcpyHostToDevice, st));
+    AKZ_TRY(table_upload(c, c->gd_tab.p, c->gd_pin_tab.p, tab.data(), b_tab));
     MatchRec* rec = (MatchRec*)c->gd_rec.p;
-    launch::match_guided(st, kind, d_rows, d_kx, d_ky, (const launch::GuidedPairHost*)c->gd_tab.p, (uint32_t)tab.size(), (uint32_t)wg, d_models,
+    launch::match_guided(st, kind, b.d_rows, b.d_kx, b.d_ky, (const launch::GuidedPairHost*)c->gd_tab.p, (uint32_t)tab.size(), (uint32_t)wg, d_models,
                          d_found, radius, thr, rec);
     AKZ_HIP_TRY(hipGetLastError());
     for (const launch::GuidedPairHost& g : tab)
@@ -165,8 +163,9 @@ int akz_descriptor_match_guided_pairs(akz_ctx* c, const akz_feature_set* sets, u
     const char* name = "descriptor_match_guided_pairs: ";
     if (n_pairs == 0) return AKZ_OK;
     if (!guided_args_ok(name, model_kind, models, radius)) return AKZ_ERR_INVALID_ARG;
+    const PairsCall q{name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, nullptr};
     PairsFront f;
-    AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, true, f));
+    AKZ_TRY(pairs_open(q, true, f));
     hipStream_t st = c->stream;
     const size_t b_mdl = up256((size_t)n_pairs * 36);
     AKZ_TRY(ensure(c, c->gd_out, f.b_cnt + b_mdl + (size_t)f.cap1 * sizeof(akz_match)));
@@ -176,14 +175,12 @@ int akz_descriptor_match_guided_pairs(akz_ctx* c, const akz_feature_set* sets, u
     akz_match* d_out = (akz_match*)((char*)c->gd_out.p + f.b_cnt + b_mdl);
     uint64_t* h_cnt = (uint64_t*)c->gd_pin_cnt.p;
     float* h_models = (float*)((char*)c->gd_pin_cnt.p + f.b_cnt);
-    AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));
-    std::memcpy(h_models, models, (size_t)n_pairs * 36);
-    AKZ_HIP_TRY(hipMemcpyAsync(d_models, h_models, (size_t)n_pairs * 36, hipMemcpyHostToDevice, st));
-    AKZ_TRY(guided_enqueue(c, guided_specs(sets, pairs, n_pairs, f.set_row), f.d_rows, f.d_kx, f.d_ky, model_kind, d_models, nullptr, radius,
-                           distance_threshold, lowes_ratio, d_out, d_cnt));
+    AKZ_TRY(pairs_upload(c, sets, desc_bytes, f.block, f.used));
+    AKZ_TRY(table_upload(c, d_models, h_models, models, (size_t)n_pairs * 36));
+    AKZ_TRY(guided_enqueue(c, guided_specs(q, f.block), f.block, model_kind, d_models, nullptr, radius, distance_threshold, lowes_ratio, d_out, d_cnt));
     AKZ_HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     AKZ_HIP_TRY(hipStreamSynchronize(st));
-    return pairs_copy_out(c, sets, pairs, n_pairs, h_cnt, nullptr, d_out, nullptr, nullptr, nullptr, out, n_out);  // every pair's guided list
+    return pairs_copy_out(q, h_cnt, nullptr, d_out, nullptr, nullptr, nullptr);  // every pair's guided list
 }
 
 // one pair: the pairs call with sets {0, 1} and the pair (0, 1)

@@ -392,63 +392,46 @@ int akz_match_features(akz_ctx* c, const akz_keypoint* kp0, uint64_t n_kp0, cons
 
 }  // extern "C"
 
-// The refusals of the pairs calls (akz_match_features_pairs, its homography form, akz_descriptor_match_guided_pairs), all
-// before any GPU work: seen[k] = 1 for every set a pair names, cap = the room of `out` (sum of the first sets' descriptors).
-static int pairs_validate(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                          uint64_t desc_bytes, const void* out, const void* n_out, std::vector<uint8_t>& seen, uint64_t& cap) {
-    auto refuse = [name](const std::string& msg) {
-        set_error(name + msg);
-        return AKZ_ERR_INVALID_ARG;
-    };
-    if (!pairs || !n_out) return refuse("null pairs or n_out");
-    if (desc_bytes == 0 || desc_bytes > 64) return refuse("desc_bytes must be 1..64");
-    if (n_sets && !sets) return refuse("null sets");
-    seen.assign((size_t)n_sets, 0);  // 1: checked, 2 .. : checked and placed (pairs_upload)
+const char* set_refusal(const akz_feature_set& s) {
+    if (s.n_descriptors > s.n_keypoints) return "more descriptors than keypoints";
+    if ((s.n_keypoints && !s.keypoints) || (s.n_descriptors && !s.descriptors)) return "null keypoints or descriptors";
+    return nullptr;
+}
+static int pairs_refuse(const char* name, const std::string& msg) {
+    set_error(name + msg);
+    return AKZ_ERR_INVALID_ARG;
+}
+// The refusals every opening of a pairs call makes, all before any GPU work, with the one walk over pairs[]: the index bound, seen[k] = 1
+// for every set a pair names, cap = the room of `out` (sum of the first sets' descriptors), and set_refusal of every set when it is
+// first seen.  Over a bank desc_bytes and the sets are the bank's own and were checked when it was made: nothing of them is refused here.
+static int pairs_validate(const PairsCall& q, std::vector<uint8_t>& seen, uint64_t& cap) {
+    if (!q.pairs || !q.n_out) return pairs_refuse(q.name, "null pairs or n_out");
+    if (q.desc_bytes == 0 || q.desc_bytes > 64) return pairs_refuse(q.name, "desc_bytes must be 1..64");
+    if (q.n_sets && !q.sets) return pairs_refuse(q.name, "null sets");
+    seen.assign((size_t)q.n_sets, 0);
     cap = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p)
+    for (uint64_t p = 0; p < q.n_pairs; ++p)
         for (int side = 0; side < 2; ++side) {
-            const uint64_t k = pairs[2 * p + side];
-            if (k >= n_sets)
-                return refuse("pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(n_sets));
-            if (side == 0) cap += sets[k].n_descriptors;
+            const uint64_t k = q.pairs[2 * p + side];
+            if (k >= q.n_sets)
+                return pairs_refuse(q.name, "pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(q.n_sets));
+            if (side == 0) cap += q.sets[k].n_descriptors;
             if (seen[(size_t)k]) continue;
-            const akz_feature_set& f = sets[k];
-            const std::string at = "pair " + std::to_string(p) + ", set " + std::to_string(k) + ": ";
-            if (f.n_descriptors > f.n_keypoints) return refuse(at + "more descriptors than keypoints");
-            if ((f.n_keypoints && !f.keypoints) || (f.n_descriptors && !f.descriptors)) return refuse(at + "null keypoints or descriptors");
+            if (const char* why = q.bank ? nullptr : set_refusal(q.sets[k]))
+                return pairs_refuse(q.name, "pair " + std::to_string(p) + ", set " + std::to_string(k) + ": " + why);
             seen[(size_t)k] = 1;
         }
-    if (cap && !out) return refuse("null out");
-    if (!c) return refuse("null context");
+    if (cap && !q.out) return pairs_refuse(q.name, "null out");
+    if (!q.c) return pairs_refuse(q.name, "null context");
     return AKZ_OK;
 }
-// every distinct set once, in order of first use: rows (and x / y of its first n_descriptors keypoints, the only ones a
-// match can name) from row set_row[k]; returns the rows of all used sets
-static uint64_t pairs_place(const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, std::vector<uint8_t>& seen,
-                            std::vector<uint64_t>& set_row, std::vector<uint64_t>& used) {
-    set_row.assign((size_t)n_sets, 0);
-    used.clear();
-    uint64_t rows = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        for (int side = 0; side < 2; ++side) {
-            const uint64_t k = pairs[2 * p + side];
-            if (seen[(size_t)k] == 2) continue;
-            seen[(size_t)k] = 2;
-            used.push_back(k);
-            set_row[(size_t)k] = rows;
-            rows += sets[k].n_descriptors;
-        }
-    return rows;
-}
-// every used set's rows (padded to 64 bytes) and the x / y of its first n_descriptors keypoints: through pinned staging to
-// c->mp_in = rows | x | y, on the context's stream
-int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const PairsFront& f) {
+int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, const SetsBlock& b, const std::vector<uint64_t>& order) {
     hipStream_t st = c->stream;
     uint8_t* h = (uint8_t*)c->mp_pin_in.p;
-    float *hx = (float*)(h + f.b_rows), *hy = (float*)(h + f.b_rows + f.b_xy);
-    for (uint64_t k : f.used) {
+    float *hx = (float*)(h + b.b_rows), *hy = (float*)(h + b.b_rows + b.b_xy);
+    for (uint64_t k : order) {
         const akz_feature_set& s = sets[k];
-        const uint64_t row0 = f.set_row[(size_t)k];
+        const uint64_t row0 = b.set_row[(size_t)k];
         uint8_t* r = h + row0 * 64;
         for (uint64_t i = 0; i < s.n_descriptors; ++i) {
             std::memcpy(r + i * 64, s.descriptors + i * desc_bytes, (size_t)desc_bytes);
@@ -457,38 +440,40 @@ int pairs_upload(akz_ctx* c, const akz_feature_set* sets, uint64_t desc_bytes, c
             hy[row0 + i] = s.keypoints[i].y;
         }
     }
-    AKZ_HIP_TRY(hipMemcpyAsync(f.d_rows, h, (size_t)f.rows * 64, hipMemcpyHostToDevice, st));
-    AKZ_HIP_TRY(hipMemcpyAsync(f.d_kx, hx, (size_t)f.rows * 4, hipMemcpyHostToDevice, st));
-    AKZ_HIP_TRY(hipMemcpyAsync(f.d_ky, hy, (size_t)f.rows * 4, hipMemcpyHostToDevice, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(b.d_rows, h, (size_t)b.rows * 64, hipMemcpyHostToDevice, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(b.d_kx, hx, (size_t)b.rows * 4, hipMemcpyHostToDevice, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(b.d_ky, hy, (size_t)b.rows * 4, hipMemcpyHostToDevice, st));
     return AKZ_OK;
 }
-// The scans of the pairs calls, enqueued on the context's stream over the sets that pairs_upload placed: pair p's raw list goes to
+// The scans of the pairs calls, enqueued on the context's stream over the sets placed in blk: pair p's raw list goes to
 // d_raw + tab[p].raw_off, its count to d_cnt[tab[p].cnt_idx] (zeroed here) -- one multi-set launch per first set, or the pair
 // matcher for rows of 62..64 bytes.  tab: one record per pair, raw_off, kp0_off, kp1_off and cnt_idx filled in.
 // cross (optional, with d_rev and d_rcnt): the opposite direction too -- pair p's descriptor_match(second set, first set) goes to
 // d_rev + (*cross)[p].rev_off (room for the second set's rows; the sum of those over the pairs is the room of d_rev), its count
 // to d_rcnt[tab[p].cnt_idx] (zeroed here); (*cross)[p] is the pair's record for launch::pairs_cross_filter.  From the same
 // multi-set launch on the FP4 matcher, a second scan with the sets exchanged otherwise.  distance_threshold: 10000 for match_features.
-int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs, uint64_t desc_bytes,
-                double lowes_ratio, const std::vector<uint64_t>& set_row, uint8_t* d_rows, akz_match* d_raw, uint64_t* d_cnt,
-                std::vector<launch::PairJobHost>& tab, akz_match* d_rev, uint64_t* d_rcnt, std::vector<launch::CrossJobHost>* cross, uint64_t distance_threshold) {
+int pairs_scans(const PairsCall& q, double lowes_ratio, const SetsBlock& blk, akz_match* d_raw, uint64_t* d_cnt, std::vector<launch::PairJobHost>& tab,
+                akz_match* d_rev, uint64_t* d_rcnt, std::vector<launch::CrossJobHost>* cross, uint64_t distance_threshold) {
+    akz_ctx* c = q.c;
+    const std::vector<uint64_t>& set_row = blk.set_row;
+    uint8_t* d_rows = blk.d_rows;
     hipStream_t st = c->stream;
-    tab.assign((size_t)n_pairs, launch::PairJobHost{});
-    AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n_pairs * 8, st));
+    tab.assign((size_t)q.n_pairs, launch::PairJobHost{});
+    AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)q.n_pairs * 8, st));
     if (cross) {
-        cross->assign((size_t)n_pairs, launch::CrossJobHost{});
-        AKZ_HIP_TRY(hipMemsetAsync(d_rcnt, 0, (size_t)n_pairs * 8, st));
+        cross->assign((size_t)q.n_pairs, launch::CrossJobHost{});
+        AKZ_HIP_TRY(hipMemsetAsync(d_rcnt, 0, (size_t)q.n_pairs * 8, st));
     }
     uint64_t raw_base = 0, rev_base = 0;
-    if (desc_bytes > 61) {  // every byte of a row counts: the pair matcher of akz_descriptor_match
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            const uint64_t a = pairs[2 * p], b = pairs[2 * p + 1], na = sets[a].n_descriptors;
+    if (q.desc_bytes > 61) {  // every byte of a row counts: the pair matcher of akz_descriptor_match
+        for (uint64_t p = 0; p < q.n_pairs; ++p) {
+            const uint64_t a = q.pairs[2 * p], b = q.pairs[2 * p + 1], na = q.sets[a].n_descriptors;
             tab[(size_t)p] = launch::PairJobHost{raw_base, set_row[(size_t)a], set_row[(size_t)b], 0, 0, 0, (uint32_t)p, 0};
             if (na)
-                AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)a] * 64, na, d_rows + set_row[(size_t)b] * 64, sets[b].n_descriptors,
+                AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)a] * 64, na, d_rows + set_row[(size_t)b] * 64, q.sets[b].n_descriptors,
                                           distance_threshold, lowes_ratio, d_raw + raw_base, d_cnt + p, false));
             if (cross) {
-                const uint64_t nb = sets[b].n_descriptors;
+                const uint64_t nb = q.sets[b].n_descriptors;
                 (*cross)[(size_t)p] = launch::CrossJobHost{raw_base, rev_base, (uint32_t)p, (uint32_t)p, (uint32_t)na, (uint32_t)nb};
                 if (na && nb)
                     AKZ_TRY(match_device_impl(c, d_rows + set_row[(size_t)b] * 64, nb, d_rows + set_row[(size_t)a] * 64, na, distance_threshold, lowes_ratio,
@@ -499,9 +484,9 @@ int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const 
         }
     } else {  // one multi-set launch per first set over its second sets (split at the matcher's limits)
         std::vector<std::vector<uint64_t>> groups;
-        std::vector<int64_t> group_of((size_t)n_sets, -1);
-        for (uint64_t p = 0; p < n_pairs; ++p) {
-            const uint64_t a = pairs[2 * p];
+        std::vector<int64_t> group_of((size_t)q.n_sets, -1);
+        for (uint64_t p = 0; p < q.n_pairs; ++p) {
+            const uint64_t a = q.pairs[2 * p];
             if (group_of[(size_t)a] < 0) {
                 group_of[(size_t)a] = (int64_t)groups.size();
                 groups.emplace_back();
@@ -511,7 +496,7 @@ int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const 
         uint32_t cnt_base = 0;
         std::vector<uint64_t> first, nrows;
         for (const auto& g : groups) {
-            const uint64_t a = pairs[2 * g[0]], n0 = sets[a].n_descriptors;
+            const uint64_t a = q.pairs[2 * g[0]], n0 = q.sets[a].n_descriptors;
             const uint64_t max_sets = std::max<uint64_t>(1, std::min<uint64_t>(65535, n0 ? 0x7fffffffull / launch::match_mfma_rows((uint32_t)n0, true) : 65535));
             for (size_t i = 0; i < g.size();) {
                 first.clear();
@@ -519,7 +504,7 @@ int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const 
                 uint64_t train = 0;
                 const size_t i0 = i;
                 while (i < g.size() && first.size() < max_sets) {
-                    const uint64_t b = pairs[2 * g[i] + 1], nb = sets[b].n_descriptors;
+                    const uint64_t b = q.pairs[2 * g[i] + 1], nb = q.sets[b].n_descriptors;
                     if (!first.empty() && train + nb > 0x7fffffffull) break;
                     first.push_back(set_row[(size_t)b]);
                     nrows.push_back(nb);
@@ -545,75 +530,53 @@ int pairs_scans(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const 
     return AKZ_OK;
 }
 // The opening every pairs call shares (akz_ctx.hpp): no GPU work before the last refusal.
-int pairs_open(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-               uint64_t desc_bytes, const void* out, const void* n_out, bool guided, PairsFront& f) {
+int pairs_open(const PairsCall& q, bool guided, PairsFront& f) {
+    akz_ctx* c = q.c;
     std::vector<uint8_t> seen;
     uint64_t cap = 0;
-    AKZ_TRY(pairs_validate(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, seen, cap));
-    if (guided) AKZ_TRY(guided_limits(name, sets, pairs, n_pairs, seen));
+    AKZ_TRY(pairs_validate(q, seen, cap));
+    if (guided) AKZ_TRY(guided_limits(q.name, q.sets, q.pairs, q.n_pairs, seen));
     AKZ_TRY(bind(c, true, false));
-    f.rows = pairs_place(sets, n_sets, pairs, n_pairs, seen, f.set_row, f.used);
-    f.cap1 = std::max<uint64_t>(cap, 1);
-    const uint64_t rows1 = std::max<uint64_t>(f.rows, 1);
-    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4), f.b_cnt = up256((size_t)n_pairs * 8);
-    AKZ_TRY(ensure(c, c->mp_in, f.b_rows + 2 * f.b_xy));
-    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, f.b_rows + 2 * f.b_xy));
-    f.d_rows = (uint8_t*)c->mp_in.p;
-    f.d_kx = (float*)(f.d_rows + f.b_rows), f.d_ky = (float*)(f.d_rows + f.b_rows + f.b_xy);
-    return AKZ_OK;
-}
-// The opening of a bank call (akz_ctx.hpp): what pairs_validate refuses of a set was refused when the bank was made, so the refusals
-// left are the call's own -- no GPU work before the last of them -- and the layout is the bank's, every set placed whether a pair
-// names it or not.
-int pairs_open_bank(const char* name, akz_ctx* c, const akz_bank* bank, const uint64_t* pairs, uint64_t n_pairs, const void* out,
-                    const void* n_out, bool guided, PairsFront& f) {
-    auto refuse = [name](const std::string& msg) {
-        set_error(name + msg);
-        return AKZ_ERR_INVALID_ARG;
-    };
-    if (!bank) return refuse("null bank");
-    if (!pairs || !n_out) return refuse("null pairs or n_out");
-    const uint64_t n_sets = bank->sets.size();
-    std::vector<uint8_t> seen((size_t)n_sets, 0);
-    uint64_t cap = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p)
-        for (int side = 0; side < 2; ++side) {
-            const uint64_t k = pairs[2 * p + side];
-            if (k >= n_sets)
-                return refuse("pair " + std::to_string(p) + ": set index " + std::to_string(k) + " >= n_sets " + std::to_string(n_sets));
-            if (side == 0) cap += bank->sets[(size_t)k].n_descriptors;
-            seen[(size_t)k] = 1;
-        }
-    if (cap && !out) return refuse("null out");
-    if (!c) return refuse("null context");
-    if (bank->ctx != c) return refuse("the bank belongs to another context");
-    if (guided) {
-        AKZ_TRY(guided_limits(name, bank->sets.data(), pairs, n_pairs, seen));
-        if (bank->rows > 0xffffffffull) return refuse("too many rows in the bank for one guided launch");  // (its records carry absolute rows)
+    for (uint64_t i = 0; i < 2 * q.n_pairs; ++i) {  // every distinct set once, in order of first use (seen 2: listed)
+        uint8_t& s = seen[(size_t)q.pairs[i]];
+        if (s == 1) f.used.push_back(q.pairs[i]);
+        s = 2;
     }
-    AKZ_TRY(bind(c, true, false));
-    f.set_row = bank->set_row;
-    f.used.clear();
-    f.rows = bank->rows;
+    f.block.place(q.sets, q.n_sets, f.used);
     f.cap1 = std::max<uint64_t>(cap, 1);
-    const uint64_t rows1 = std::max<uint64_t>(f.rows, 1);
-    f.b_rows = up256((size_t)rows1 * 64), f.b_xy = up256((size_t)rows1 * 4), f.b_cnt = up256((size_t)n_pairs * 8);
-    f.d_rows = bank->d_rows, f.d_kx = bank->d_kx, f.d_ky = bank->d_ky;
+    f.b_cnt = up256((size_t)q.n_pairs * 8);
+    AKZ_TRY(ensure(c, c->mp_in, f.block.bytes(false)));
+    AKZ_TRY(ensure_pinned(c, c->mp_pin_in, f.block.bytes(false)));
+    f.block.bind(c->mp_in.p, false);
     return AKZ_OK;
 }
-int pairs_table_upload(akz_ctx* c, PairsFront& f) {
-    std::memcpy(f.h_tab, f.tab.data(), f.tab.size() * sizeof(launch::PairJobHost));
-    AKZ_HIP_TRY(hipMemcpyAsync(f.d_tab, f.h_tab, f.tab.size() * sizeof(launch::PairJobHost), hipMemcpyHostToDevice, c->stream));
+// The opening of a bank call (akz_ctx.hpp): what set_refusal refuses of a set was refused when the bank was made, so the refusals
+// left are the call's own -- no GPU work before the last of them -- and the block is the bank's, every set placed whether a pair
+// names it or not.
+int pairs_open_bank(const PairsCall& q, bool guided, PairsFront& f) {
+    std::vector<uint8_t> seen;
+    uint64_t cap = 0;
+    AKZ_TRY(pairs_validate(q, seen, cap));
+    if (q.bank->ctx != q.c) return pairs_refuse(q.name, "the bank belongs to another context");
+    if (guided) {
+        AKZ_TRY(guided_limits(q.name, q.sets, q.pairs, q.n_pairs, seen));
+        if (q.bank->block.rows > 0xffffffffull) return pairs_refuse(q.name, "too many rows in the bank for one guided launch");  // (its records carry absolute rows)
+    }
+    AKZ_TRY(bind(q.c, true, false));
+    f.block = q.bank->block;
+    f.cap1 = std::max<uint64_t>(cap, 1);
+    f.b_cnt = up256((size_t)q.n_pairs * 8);
     return AKZ_OK;
 }
+int pairs_table_upload(akz_ctx* c, PairsFront& f) { return table_upload(c, f.d_tab, f.h_tab, f.tab.data(), f.tab.size() * sizeof(launch::PairJobHost)); }
 // The front of the RANSAC pairs calls, all on the context's stream: every distinct set's 64-byte rows and keypoint x / y through pinned
 // staging; the descriptor scans (pairs_scans; cross: the opposite direction too, and the filter that rewrites raw lists and counts before
 // anything reads them); the pair table; k_pair_points; the read-back of the match counts, which the caller waits for.
-int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
-                uint64_t desc_bytes, double lowes_ratio, const void* out, const void* n_out, bool guided, bool cross, size_t b_dev_own,
-                size_t b_pin_own, PairsFront& f, const akz_bank* bank) {
-    if (bank) AKZ_TRY(pairs_open_bank(name, c, bank, pairs, n_pairs, out, n_out, guided, f));
-    else AKZ_TRY(pairs_open(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, guided, f));
+int pairs_front(const PairsCall& q, double lowes_ratio, bool guided, bool cross, size_t b_dev_own, size_t b_pin_own, PairsFront& f) {
+    if (q.bank) AKZ_TRY(pairs_open_bank(q, guided, f));
+    else AKZ_TRY(pairs_open(q, guided, f));
+    akz_ctx* c = q.c;
+    const uint64_t n_pairs = q.n_pairs;
     f.timed = c->mp_split_on;
     if (f.timed)
         for (Event& e : c->mp_split_ev) AKZ_TRY(e.ensure(hipEventDefault));
@@ -631,11 +594,11 @@ int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint6
     f.h_cnt = (uint64_t*)((char*)c->mp_pin_tab.p + b_tab);
     f.h_own = (char*)c->mp_pin_tab.p + b_tab + f.b_cnt;
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
-    if (!bank) AKZ_TRY(pairs_upload(c, sets, desc_bytes, f));  // (a bank's sets are where the scans read them)
+    if (!q.bank) AKZ_TRY(pairs_upload(c, q.sets, q.desc_bytes, f.block, f.used));  // (a bank's sets are where the scans read them)
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
     if (cross) {  // the reverse lists (room: every pair's second set), their counts and the filter's records
         uint64_t cap_rev = 0;
-        for (uint64_t p = 0; p < n_pairs; ++p) cap_rev += sets[pairs[2 * p + 1]].n_descriptors;
+        for (uint64_t p = 0; p < n_pairs; ++p) cap_rev += q.sets[q.pairs[2 * p + 1]].n_descriptors;
         const size_t b_rev = up256((size_t)std::max<uint64_t>(cap_rev, 1) * sizeof(akz_match)), b_xtab = up256((size_t)n_pairs * sizeof(launch::CrossJobHost));
         AKZ_TRY(ensure(c, c->cx_rev, b_rev + f.b_cnt + b_xtab));
         AKZ_TRY(ensure_pinned(c, c->cx_pin_tab, b_xtab));
@@ -643,47 +606,38 @@ int pairs_front(const char* name, akz_ctx* c, const akz_feature_set* sets, uint6
         uint64_t* d_rcnt = (uint64_t*)((char*)c->cx_rev.p + b_rev);
         launch::CrossJobHost* d_xtab = (launch::CrossJobHost*)((char*)c->cx_rev.p + b_rev + f.b_cnt);
         std::vector<launch::CrossJobHost> xtab;
-        AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, f.set_row, f.d_rows, f.d_raw, f.d_cnt, f.tab, d_rev, d_rcnt, &xtab));
-        std::memcpy(c->cx_pin_tab.p, xtab.data(), (size_t)n_pairs * sizeof(launch::CrossJobHost));
-        AKZ_HIP_TRY(hipMemcpyAsync(d_xtab, c->cx_pin_tab.p, (size_t)n_pairs * sizeof(launch::CrossJobHost), hipMemcpyHostToDevice, st));
+        AKZ_TRY(pairs_scans(q, lowes_ratio, f.block, f.d_raw, f.d_cnt, f.tab, d_rev, d_rcnt, &xtab));
+        AKZ_TRY(table_upload(c, d_xtab, c->cx_pin_tab.p, xtab.data(), (size_t)n_pairs * sizeof(launch::CrossJobHost)));
         launch::pairs_cross_filter(st, d_xtab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, d_rev, d_rcnt);
         AKZ_HIP_TRY(hipGetLastError());
     } else {
-        AKZ_TRY(pairs_scans(c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, f.set_row, f.d_rows, f.d_raw, f.d_cnt, f.tab));
+        AKZ_TRY(pairs_scans(q, lowes_ratio, f.block, f.d_raw, f.d_cnt, f.tab));
     }
     AKZ_TRY(pairs_table_upload(c, f));
-    launch::pair_points(st, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_kx, f.d_ky, f.d_pts, f.cap1);
+    launch::pair_points(st, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.block.d_kx, f.block.d_ky, f.d_pts, f.cap1);
     AKZ_HIP_TRY(hipGetLastError());
     AKZ_HIP_TRY(hipMemcpyAsync(f.h_cnt, f.d_cnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     return AKZ_OK;
 }
-// room for the head and the kept lists of n_keep matches (PairsKeep, akz_ctx.hpp) on the device and in pinned memory
+// room for the head and the kept lists of n_keep matches (PairsKeep, akz_pairs_layout.hpp) on the device and in pinned memory
 int pairs_keep(akz_ctx* c, const PairsFront& f, uint64_t n_keep, PairsKeep& k) {
     k.n_keep = n_keep;
+    k.b_cnt = f.b_cnt;
     k.b_points = k.want_points ? up256((size_t)std::max<uint64_t>(n_keep, 1) * 12) : 0;
-    k.b_head = f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials + k.b_pose + k.b_points;
-    const size_t b_keep = k.b_head + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
+    const size_t b_keep = pairs_head(nullptr, k).bytes + (size_t)std::max<uint64_t>(n_keep, 1) * sizeof(akz_match);
     AKZ_TRY(ensure(c, c->mp_keep, b_keep));
     AKZ_TRY(ensure_pinned(c, c->mp_pin_out, b_keep));
-    char* d = (char*)c->mp_keep.p;
-    k.d_kcnt = (uint64_t*)d;
-    k.d_hm = (float*)(d + f.b_cnt);
-    k.d_hf = (int32_t*)(d + f.b_cnt + k.b_model);
-    k.d_it = (uint32_t*)(d + f.b_cnt + k.b_model + k.b_found);
-    k.d_tr = (uint32_t*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits);
-    k.d_pose = (akz_pose*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials);
-    k.d_points = (float*)(d + f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials + k.b_pose);
-    k.d_keep = (akz_match*)(d + k.b_head);
+    k.d = pairs_head(c->mp_keep.p, k);
     return AKZ_OK;
 }
-int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const uint64_t* h_gcnt, const int32_t* h_found,
-                   const akz_match* d_gout, const uint64_t* h_kcnt, const akz_match* h_keep, const launch::PairJobHost* tab, akz_match* out,
-                   uint64_t* n_out) {
+int pairs_copy_out(const PairsCall& q, const uint64_t* h_gcnt, const int32_t* h_found, const akz_match* d_gout, const uint64_t* h_kcnt,
+                   const akz_match* h_keep, const launch::PairJobHost* tab) {
+    akz_ctx* c = q.c;
     auto guided = [&](uint64_t p) { return h_gcnt && (!h_found || h_found[p] != 0); };
     uint64_t span = 0, off = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
+    for (uint64_t p = 0; p < q.n_pairs; ++p) {
         if (guided(p) && h_gcnt[p]) span = off + h_gcnt[p];
-        off += sets[pairs[2 * p]].n_descriptors;
+        off += q.sets[q.pairs[2 * p]].n_descriptors;
     }
     if (span) {  // through pinned staging
         AKZ_TRY(ensure_pinned(c, c->gd_pin_out, (size_t)span * sizeof(akz_match)));
@@ -692,11 +646,11 @@ int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pair
     }
     const akz_match* h_gout = (const akz_match*)c->gd_pin_out.p;
     uint64_t at = 0;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
+    for (uint64_t p = 0; p < q.n_pairs; ++p) {
         const uint64_t n = guided(p) ? h_gcnt[p] : h_kcnt[p];  // found: the guided list replaces the filtered one
-        if (n) std::memcpy(out + at, guided(p) ? h_gout + at : h_keep + tab[p].keep_off, (size_t)n * sizeof(akz_match));
-        n_out[p] = n;
-        at += sets[pairs[2 * p]].n_descriptors;
+        if (n) std::memcpy(q.out + at, guided(p) ? h_gout + at : h_keep + tab[p].keep_off, (size_t)n * sizeof(akz_match));
+        q.n_out[p] = n;
+        at += q.sets[q.pairs[2 * p]].n_descriptors;
     }
     return AKZ_OK;
 }
@@ -705,26 +659,27 @@ int pairs_copy_out(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pair
 // the device (pairs without one give empty lists that nobody reads) over the sets the front uploaded.  Both stages need the head's models.
 // launch::pairs_pose, behind the refit, shrinks the kept lists in place to the matches in front of both cameras and fills the head's poses
 // and points (the seeded call alone asks for it, and refuses the guided stage with it).
-int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, uint64_t n_pairs, const PairsFront& f, const PairsKeep& k,
-               launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl, float epsilon_inliers, const RefineStage* refine,
-               float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host, akz_match* out, uint64_t* n_out, float* model,
-               int* found, uint32_t* fits, uint64_t* trials_run, const PoseStage* pose) {
+int pairs_tail(const PairsCall& q, const PairsFront& f, const PairsKeep& k, launch::RansacModel kind, const float* d_mdl, const int32_t* d_inl,
+               float epsilon_inliers, const RefineStage* refine, float refit_epsilon, const GuidedStage* guided, int guided_kind, double t_host,
+               float* model, int* found, uint32_t* fits, uint64_t* trials_run, const PoseStage* pose) {
+    akz_ctx* c = q.c;
+    const uint64_t n_pairs = q.n_pairs;
     hipStream_t st = c->stream;
-    launch::pairs_pick_filter(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, d_mdl, d_inl, epsilon_inliers, k.d_keep, k.d_kcnt,
-                              k.b_model ? k.d_hm : nullptr, k.b_found ? k.d_hf : nullptr);
+    launch::pairs_pick_filter(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, d_mdl, d_inl, epsilon_inliers, k.d.keep, k.d.cnt,
+                              k.b_model ? k.d.model : nullptr, k.b_found ? k.d.found : nullptr);
     AKZ_HIP_TRY(hipGetLastError());
     if (refine) {  // (inside the pick / filter interval of akz_debug_match_pairs_split)
         launch::model_refit(st, kind, f.d_tab, (uint32_t)n_pairs, f.d_raw, f.d_cnt, f.d_pts, f.cap1, refit_epsilon, epsilon_inliers,
-                            refine->max_iterations, k.d_keep, k.d_kcnt, k.d_hm, k.d_hf, k.d_it);
+                            refine->max_iterations, k.d.keep, k.d.cnt, k.d.model, k.d.found, k.d.fits);
         AKZ_HIP_TRY(hipGetLastError());
     }
     if (pose) {  // (inside the same interval; the kept lists shrink in place, so the one read-back below carries the final ones)
-        launch::pairs_pose(st, f.d_tab, (uint32_t)n_pairs, pose->d_cameras, f.d_kx, f.d_ky, k.d_hm, k.d_hf, k.d_keep, k.d_kcnt, k.d_pose,
-                           pose->points ? k.d_points : nullptr);
+        launch::pairs_pose(st, f.d_tab, (uint32_t)n_pairs, pose->d_cameras, f.block.d_kx, f.block.d_ky, k.d.model, k.d.found, k.d.keep, k.d.cnt, k.d.pose,
+                           pose->points ? k.d.points : nullptr);
         AKZ_HIP_TRY(hipGetLastError());
     }
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[5], st));
-    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, k.b_head + (size_t)k.n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
+    AKZ_HIP_TRY(hipMemcpyAsync(c->mp_pin_out.p, c->mp_keep.p, k.d.bytes + (size_t)k.n_keep * sizeof(akz_match), hipMemcpyDeviceToHost, st));
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[6], st));
     akz_match* d_gout = nullptr;
     if (guided) {
@@ -732,33 +687,25 @@ int pairs_tail(akz_ctx* c, const akz_feature_set* sets, const uint64_t* pairs, u
         AKZ_TRY(ensure_pinned(c, c->gd_pin_cnt, f.b_cnt));
         uint64_t* d_gcnt = (uint64_t*)c->gd_out.p;
         d_gout = (akz_match*)((char*)c->gd_out.p + f.b_cnt);
-        AKZ_TRY(guided_enqueue(c, guided_specs(sets, pairs, n_pairs, f.set_row), f.d_rows, f.d_kx, f.d_ky, guided_kind, k.d_hm, k.d_hf, guided->radius,
-                               10000, guided->ratio, d_gout, d_gcnt));
+        AKZ_TRY(guided_enqueue(c, guided_specs(q, f.block), f.block, guided_kind, k.d.model, k.d.found, guided->radius, 10000, guided->ratio, d_gout, d_gcnt));
         AKZ_HIP_TRY(hipMemcpyAsync(c->gd_pin_cnt.p, d_gcnt, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, st));
     }
     AKZ_HIP_TRY(hipStreamSynchronize(st));
-    const char* head = (const char*)c->mp_pin_out.p;
-    const float* h_hm = (const float*)(head + f.b_cnt);
-    const int32_t* h_hf = (const int32_t*)(head + f.b_cnt + k.b_model);
-    const uint32_t* h_it = (const uint32_t*)(head + f.b_cnt + k.b_model + k.b_found);
-    const uint32_t* h_tr = (const uint32_t*)(head + f.b_cnt + k.b_model + k.b_found + k.b_fits);
-    AKZ_TRY(pairs_copy_out(c, sets, pairs, n_pairs, guided ? (const uint64_t*)c->gd_pin_cnt.p : nullptr, h_hf, d_gout, (const uint64_t*)head,
-                           (const akz_match*)(head + k.b_head), f.tab.data(), out, n_out));
-    if (model) std::memcpy(model, h_hm, (size_t)n_pairs * 36);
+    const PairsHead h = pairs_head(c->mp_pin_out.p, k);  // the head's pinned image
+    AKZ_TRY(pairs_copy_out(q, guided ? (const uint64_t*)c->gd_pin_cnt.p : nullptr, h.found, d_gout, h.cnt, h.keep, f.tab.data()));
+    if (model) std::memcpy(model, h.model, (size_t)n_pairs * 36);
     for (uint64_t p = 0; p < n_pairs; ++p) {
-        if (found) found[p] = h_hf[p];
-        if (fits) fits[p] = h_it[p];
-        if (trials_run) trials_run[p] = h_tr[p];
+        if (found) found[p] = h.found[p];
+        if (fits) fits[p] = h.fits[p];
+        if (trials_run) trials_run[p] = h.trials[p];
     }
     if (pose) {
-        const char* h_pose = head + f.b_cnt + k.b_model + k.b_found + k.b_fits + k.b_trials;
-        std::memcpy(pose->poses, h_pose, (size_t)n_pairs * sizeof(akz_pose));
+        std::memcpy(pose->poses, h.pose, (size_t)n_pairs * sizeof(akz_pose));
         if (pose->points) {  // (3 floats per kept record at the place of its list, to the place of that list in `out`)
-            const float* h_points = (const float*)(h_pose + k.b_pose);
             uint64_t at = 0;
             for (uint64_t p = 0; p < n_pairs; ++p) {
-                if (n_out[p] && pose->poses[p].found) std::memcpy(pose->points + 3 * at, h_points + 3 * f.tab[(size_t)p].keep_off, (size_t)n_out[p] * 12);
-                at += sets[pairs[2 * p]].n_descriptors;
+                if (q.n_out[p] && pose->poses[p].found) std::memcpy(pose->points + 3 * at, h.points + 3 * f.tab[(size_t)p].keep_off, (size_t)q.n_out[p] * 12);
+                at += q.sets[q.pairs[2 * p]].n_descriptors;
             }
         }
     }
@@ -817,8 +764,9 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
     if (!Model::kModelOut) refine = nullptr;
     constexpr uint32_t kChunk = 16384;  // trials per launch of k_pairs_trials (and per pinned sample slot)
     const size_t b_smp = (size_t)kChunk * 9 * sizeof(uint32_t);
+    const PairsCall q{name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, nullptr};
     PairsFront f;
-    AKZ_TRY(pairs_front(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, lowes_ratio, out, n_out, guided != nullptr, false, 2 * b_smp, 0, f));
+    AKZ_TRY(pairs_front(q, lowes_ratio, guided != nullptr, false, 2 * b_smp, 0, f));
     hipStream_t st = c->stream;
     uint32_t* d_smp[2] = {(uint32_t*)f.d_own, (uint32_t*)(f.d_own + b_smp)};
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[2], st));
@@ -895,8 +843,8 @@ int match_pairs_impl(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, c
         if (!launched) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
         AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[4], st));
     }
-    return pairs_tail(c, sets, pairs, n_pairs, f, keep, Model::kKind, d_mdl, d_inl, ransac_epsilon_inliers, refine, Model::kRefitEpsilon, guided,
-                      Model::kGuidedKind, t_draw, out, n_out, model_out, found_out, refine ? refine->iterations : nullptr, nullptr);
+    return pairs_tail(q, f, keep, Model::kKind, d_mdl, d_inl, ransac_epsilon_inliers, refine, Model::kRefitEpsilon, guided, Model::kGuidedKind, t_draw,
+                      model_out, found_out, refine ? refine->iterations : nullptr, nullptr);
 }
 // One pair: the pairs call with sets {0, 1} and the pair (0, 1).  refine_iterations / g: null without that stage.  H is copied out only
 // when found; F always (zeros without a winner, as akz_remove_outliers_fundamental), and its refusals inside the pairs call carry `name`.

@@ -25,12 +25,14 @@ using namespace akz;
 // writes the opposite direction and launch::pairs_cross_filter rewrites d_raw / d_cnt before anything reads them; clear, the call
 // enqueues what it always did.  pose: akz_match_features_seeded_pose_pairs (akz_pose_api.cpp, which has refused what that call refuses) --
 // the pairs' cameras ride behind done | need, the head carries the poses (zeroed with the fits and the trial counts) and the points, and
-// the tail runs launch::pairs_pose; null, nothing of it is allocated or enqueued.  bank: the sets lie in a feature bank (akz_bank_api.cpp) --
-// the front opens on its buffers and uploads no set; everything else is the same code over the same table.
-int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs,
-                            uint64_t n_pairs, uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
-                            float* model, int* found, uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose, const akz_bank* bank) {
+// the tail runs launch::pairs_pose; null, nothing of it is allocated or enqueued.  q.bank: the sets lie in a feature bank (akz_bank_api.cpp) --
+// the front opens on its block and uploads no set; everything else is the same code over the same table.
+int match_seeded_pairs_impl(const PairsCall& q, bool cross, const akz_ransac_options* options, float* model, int* found, uint32_t* iterations,
+                            uint64_t* trials_run, const SeededPose* pose) {
     constexpr uint32_t kWindow = 8;  // rounds enqueued between two looks at the pairs still running
+    const char* name = q.name;
+    akz_ctx* c = q.c;
+    const uint64_t n_pairs = q.n_pairs;
     AKZ_TRY(seeded_refuse_options(name, options));
     const akz_ransac_options& opt = *options;
     if (opt.guided && !(opt.guided_radius >= 0.0f && std::isfinite(opt.guided_radius))) {
@@ -58,8 +60,7 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     const size_t b_need = stopping ? up256((size_t)n_pairs * kWindow * 4) : 0;  // one window of rounds per pair
     const size_t b_cam = pose ? up256((size_t)n_pairs * 2 * sizeof(akz_camera)) : 0;
     PairsFront f;  // behind the pair table: done | need | cameras, on the device and (+ 256 for the count of pairs still running, in front of the cameras) in pinned memory
-    AKZ_TRY(pairs_front(name, c, sets, n_sets, pairs, n_pairs, desc_bytes, opt.lowes_ratio, out, n_out, opt.guided != 0, cross,
-                        b_done + b_need + b_cam, b_done + b_need + 256 + b_cam, f, bank));
+    AKZ_TRY(pairs_front(q, opt.lowes_ratio, opt.guided != 0, cross, b_done + b_need + b_cam, b_done + b_need + 256 + b_cam, f));
     hipStream_t st = c->stream;
     // the rounds' state: every pair's best model and count, its ring of a round's models and counts, the running counts per round
     const size_t b_bm = up256((size_t)n_pairs * 36), b_bi = up256((size_t)n_pairs * 4);
@@ -115,16 +116,16 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     akz_camera* d_cam = (akz_camera*)(f.d_own + b_done + b_need);
     if (pose) {
         akz_camera* h_cam = (akz_camera*)(f.h_own + b_done + b_need + 256);
-        for (uint64_t p = 0; p < n_pairs; ++p) h_cam[2 * p] = pose->cameras[pairs[2 * p]], h_cam[2 * p + 1] = pose->cameras[pairs[2 * p + 1]];
+        for (uint64_t p = 0; p < n_pairs; ++p) h_cam[2 * p] = pose->cameras[q.pairs[2 * p]], h_cam[2 * p + 1] = pose->cameras[q.pairs[2 * p + 1]];
         AKZ_HIP_TRY(hipMemcpyAsync(d_cam, h_cam, (size_t)n_pairs * 2 * sizeof(akz_camera), hipMemcpyHostToDevice, st));
     }
-    AKZ_HIP_TRY(hipMemsetAsync(keep.d_it, 0, keep.b_fits + keep.b_trials + keep.b_pose, st));  // (the poses: no pose where the stage leaves at once)
+    AKZ_HIP_TRY(hipMemsetAsync(keep.d.fits, 0, (char*)keep.d.points - (char*)keep.d.fits, st));  // fits | trials | poses (no pose where the stage leaves at once)
     if (f.timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));
     const uint64_t k1 = seeded_seed_key(opt.seed[0], opt.seed[1]);
     for (uint32_t r = 0; r < n_rounds && n_running; ++r) {
         launch::seeded_round(st, kind, f.d_tab, (uint32_t)n_pairs, d_done, k1, opt.stream_base, r, max_trials, f.d_cnt, f.d_pts, f.cap1, epsilon_model,
                              opt.epsilon_inliers, d_rm, d_ri);
-        launch::seeded_update(st, (uint32_t)n_pairs, r, max_trials, d_need, kWindow, r % kWindow, d_rm, d_ri, d_done, d_bi, d_bm, keep.d_tr, d_run);
+        launch::seeded_update(st, (uint32_t)n_pairs, r, max_trials, d_need, kWindow, r % kWindow, d_rm, d_ri, d_done, d_bi, d_bm, keep.d.trials, d_run);
         AKZ_HIP_TRY(hipGetLastError());
         if (stopping && (r + 1) % kWindow == 0 && r + 1 < n_rounds) {  // (without the rule every pair runs to max_trials)
             AKZ_HIP_TRY(hipMemcpyAsync(h_run, d_run + r, 4, hipMemcpyDeviceToHost, st));
@@ -142,13 +143,13 @@ int match_seeded_pairs_impl(const char* name, bool cross, akz_ctx* c, const akz_
     const RefineStage refine{opt.refine_iterations, nullptr};
     const GuidedStage guided{opt.guided_radius, opt.guided_lowes_ratio};
     const PoseStage stage{d_cam, pose ? pose->poses : nullptr, pose ? pose->points : nullptr};
-    return pairs_tail(c, sets, pairs, n_pairs, f, keep, kind, d_bm, d_bi, opt.epsilon_inliers, opt.refine_iterations > 0 ? &refine : nullptr, refit_epsilon,
-                      opt.guided ? &guided : nullptr, guided_kind, t_need, out, n_out, model, found, iterations, trials_run, pose ? &stage : nullptr);
+    return pairs_tail(q, f, keep, kind, d_bm, d_bi, opt.epsilon_inliers, opt.refine_iterations > 0 ? &refine : nullptr, refit_epsilon,
+                      opt.guided ? &guided : nullptr, guided_kind, t_need, model, found, iterations, trials_run, pose ? &stage : nullptr);
 }
 
 extern "C" int akz_match_features_seeded_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                                                uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out,
                                                float* model, int* found, uint32_t* iterations, uint64_t* trials_run) {
-    return match_seeded_pairs_impl("match_features_seeded_pairs: ", false, c, sets, n_sets, pairs, n_pairs, desc_bytes, options, out, n_out, model,
-                                   found, iterations, trials_run);
+    return match_seeded_pairs_impl({"match_features_seeded_pairs: ", c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, nullptr}, false, options,
+                                   model, found, iterations, trials_run);
 }

@@ -91,6 +91,6 @@ extern "C" int akz_match_features_seeded_pose_pairs(akz_ctx* c, const akz_featur
     const char* name = "match_features_seeded_pose_pairs: ";
     AKZ_TRY(pose_pairs_refusals(name, options, cameras, n_sets, poses));
     const SeededPose pose{cameras, poses, points};
-    return match_seeded_pairs_impl(name, cross_check != 0, c, sets, n_sets, pairs, n_pairs, desc_bytes, options, out, n_out, model, found, iterations,
-                                   trials_run, &pose);
+    return match_seeded_pairs_impl({name, c, sets, n_sets, pairs, n_pairs, desc_bytes, out, n_out, nullptr}, cross_check != 0, options, model, found,
+                                   iterations, trials_run, &pose);
 }
