@@ -266,6 +266,19 @@ class Pose(C.Structure):
         return np.frombuffer(bytes(self), np.uint32).copy()
 
 
+def _match_name(model, refined, guided, pairs):
+    """akz_match_features{,_homography,_fundamental}{,_refined}{,_guided}{,_pairs}; model: "", "_homography" or "_fundamental"."""
+    return "akz_match_features" + model + "_refined" * bool(refined) + "_guided" * bool(guided) + "_pairs" * bool(pairs)
+
+
+def _match_run(head, scalars, refine, guided, out, model, iterations):
+    """The argument run of those eighteen functions, stated once -- for the ctypes types of lib()'s table and for the values of a
+    call (_match_pair, _match_pairs) alike: the head (a pair's, _PairArgs, or the sets', _PairsArgs), then lowes_ratio,
+    ransac_trials, ransac_epsilon_inliers, [refine_iterations], [guided_radius, guided_lowes_ratio], out, n_out, [model, found],
+    [iterations].  A part in brackets is () where the function has none."""
+    return (*head, *scalars, *refine, *guided, *out, *model, *iterations)
+
+
 _lib = None
 
 
@@ -382,48 +395,16 @@ def lib():
         "akz_detector_kernel_name": ([], C.c_char_p),
         "akz_remove_outliers": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64], i32),
         "akz_estimate_fundamental_matrix": ([vp, u64, vp, u64, vp, C.c_float, fp, C.POINTER(i32)], i32),
-        "akz_match_features": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64], i32),
-        "akz_match_features_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64], i32),
         "akz_debug_ransac_samples": ([u64, u64, u64, u64, pu64], i32),
         "akz_debug_ransac_samples_k": ([u64, u64, u64, u64, i32, pu64], i32),
         "akz_estimate_homography": ([vp, u64, vp, u64, vp, C.c_float, fp, C.POINTER(i32)], i32),
         "akz_remove_outliers_homography": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
-        "akz_match_features_homography": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp,
-                                           C.POINTER(i32)], i32),
-        "akz_match_features_homography_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
         "akz_refine_homography": ([vp, u64, vp, u64, vp, u64, fp, C.c_float, C.c_uint32, vp, pu64, fp, C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_homography_refined": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64,
-                                                   fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_homography_refined_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64, fp,
-                                                         C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_homography_refined_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32,
-                                                          C.c_float, f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_homography_refined_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, C.c_float, f64,
-                                                                vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
         "akz_descriptor_match_guided_host": ([vp, u64, vp, u64, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
         "akz_descriptor_match_guided_pairs": ([vp, vp, u64, vp, u64, u64, i32, fp, C.c_float, u64, f64, vp, pu64], i32),
-        "akz_match_features_homography_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp,
-                                                  pu64, fp, C.POINTER(i32)], i32),
-        "akz_match_features_homography_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp, pu64, fp,
-                                                        C.POINTER(i32)], i32),
         "akz_remove_outliers_fundamental": ([vp, u64, vp, u64, vp, u64, u64, C.c_float, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
         "akz_refine_fundamental_matrix": ([vp, u64, vp, u64, vp, u64, fp, C.c_float, C.c_uint32, vp, pu64, fp, C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_fundamental": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp,
-                                            C.POINTER(i32)], i32),
-        "akz_match_features_fundamental_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, vp, pu64, fp, C.POINTER(i32)], i32),
-        "akz_match_features_fundamental_refined": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64,
-                                                    fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_fundamental_refined_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, vp, pu64, fp,
-                                                          C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_fundamental_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp,
-                                                   pu64, fp, C.POINTER(i32)], i32),
-        "akz_match_features_fundamental_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_float, f64, vp, pu64, fp,
-                                                         C.POINTER(i32)], i32),
-        "akz_match_features_fundamental_refined_guided": ([vp, vp, u64, vp, u64, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32,
-                                                           C.c_float, f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
-        "akz_match_features_fundamental_refined_guided_pairs": ([vp, vp, u64, vp, u64, u64, f64, u64, C.c_float, C.c_uint32, C.c_float,
-                                                                 f64, vp, pu64, fp, C.POINTER(i32), C.POINTER(C.c_uint32)], i32),
         "akz_ransac_options_default": ([C.POINTER(RansacOptions)], None),
         "akz_draw_sample_seeded": ([u64, u64, u64, u64, u64, i32, pu64], i32),
         "akz_ransac_required_inliers": ([u64, i32, u64, f64, pu64], i32),
@@ -528,6 +509,15 @@ def lib():
         "akz_gather_finish": ([vp, C.POINTER(vp), pu64, pu64, pu64], i32),
         "akz_gather_free": ([vp], i32),
     }
+    # the eighteen akz_match_features* rows, from their parts (_match_run): one of two heads, the scalars, the outputs
+    pair_head = (vp, vp, u64, vp, u64, vp, u64, vp, u64, u64)  # ctx, (keypoints, n, descriptors, n) of set 0, of set 1, desc_bytes
+    sets_head = (vp, vp, u64, vp, u64, u64)                    # ctx, sets, n_sets, pairs, n_pairs, desc_bytes
+    for model in ("", "_homography", "_fundamental"):
+        for refined, guided in ((0, 0), (1, 0), (0, 1), (1, 1)) if model else ((0, 0),):
+            for pairs in (0, 1):
+                sig[_match_name(model, refined, guided, pairs)] = (list(_match_run(
+                    sets_head if pairs else pair_head, (f64, u64, C.c_float), (u32,) * refined, (C.c_float, f64) * guided, (vp, pu64),
+                    (fp, C.POINTER(i32)) if model else (), (pu32,) * refined)), i32)
     for name, (args, res) in sig.items():
         fn = getattr(L, name)  # AttributeError here == a symbol of include/akaze_hip.h is missing
         fn.argtypes = args
@@ -639,6 +629,92 @@ def synth_frame(w, h, frame_index=0, shift=(0, 0)):
     return out
 
 
+def _extract_flags(keep_all_planes, host_descriptors=True, input_ready=False):
+    """the AKZ_* flags word of the extract calls"""
+    return (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS) | \
+           (AKZ_INPUT_READY if input_ready else 0)
+
+
+class _OneResult:
+    """The outputs of a call over one pair or one match list -- out (room for `rows` records), n_out, a 9-float model, found,
+    iterations -- and the slice and the reshape afterwards (tail: out, n_out; model_out: model, found)."""
+
+    def __init__(self, rows):
+        self.out = np.zeros(max(1, rows), MATCH_DTYPE)
+        self.n, self.found, self.it = C.c_uint64(), C.c_int(), C.c_uint32()
+        self.model = np.zeros(9, np.float32)
+        self.tail = (self.out.ctypes.data_as(C.c_void_p), C.byref(self.n))
+        self.model_out = (self.model.ctypes.data_as(C.POINTER(C.c_float)), C.byref(self.found))
+
+    def list(self):
+        return self.out[:self.n.value].copy()
+
+    def found_model(self):
+        return self.model.reshape(3, 3) if self.found.value else None
+
+
+class _PairArgs(_OneResult):
+    """One pair of host sets (head: [keypoints_0, n,] descriptors_0, n, [keypoints_1, n,] descriptors_1, n, desc_bytes -- the
+    keypoints unless only the descriptors are given), kept alive here.  A descriptor array has rows only if it is 2-D; desc_bytes
+    is the width of the first one that has rows, else 61; two widths are refused.  null_empty: a side without rows goes as NULL."""
+
+    def __init__(self, descriptors_0, descriptors_1, keypoints_0=None, keypoints_1=None, null_empty=False):
+        if keypoints_0 is not None:
+            self.k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+            self.k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+        self.d0 = np.ascontiguousarray(descriptors_0, np.uint8)
+        self.d1 = np.ascontiguousarray(descriptors_1, np.uint8)
+        self.n0 = len(self.d0) if self.d0.ndim == 2 else 0
+        self.n1 = len(self.d1) if self.d1.ndim == 2 else 0
+        if self.n0 and self.n1 and self.d0.shape[1] != self.d1.shape[1]:
+            raise ValueError(f"descriptor lengths differ: {self.d0.shape[1]} and {self.d1.shape[1]} bytes")
+        self.desc_bytes = self.d0.shape[1] if self.n0 else (self.d1.shape[1] if self.n1 else 61)
+        side0 = (self.d0.ctypes.data_as(C.c_void_p) if self.n0 or not null_empty else None, self.n0)
+        side1 = (self.d1.ctypes.data_as(C.c_void_p) if self.n1 or not null_empty else None, self.n1)
+        if keypoints_0 is not None:
+            side0 = (self.k0.ctypes.data_as(C.c_void_p), len(self.k0), *side0)
+            side1 = (self.k1.ctypes.data_as(C.c_void_p), len(self.k1), *side1)
+        self.head = (*side0, *side1, self.desc_bytes)
+        super().__init__(self.n0)
+
+
+class _MatchList(_OneResult):
+    """What the host calls over (keypoints_0, keypoints_1, matches) share (head: keypoints_0, n, keypoints_1, n, matches,
+    n_matches[, the model given]), kept alive here."""
+
+    def __init__(self, keypoints_0, keypoints_1, matches, model=None):
+        self.k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
+        self.k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
+        self.m = np.ascontiguousarray(matches, MATCH_DTYPE)
+        self.head = (self.k0.ctypes.data_as(C.c_void_p), len(self.k0), self.k1.ctypes.data_as(C.c_void_p), len(self.k1),
+                     self.m.ctypes.data_as(C.c_void_p), len(self.m))
+        if model is not None:
+            self.model_in = np.ascontiguousarray(np.asarray(model, np.float32).reshape(9))
+            self.head += (self.model_in.ctypes.data_as(C.POINTER(C.c_float)),)
+        super().__init__(len(self.m))
+
+
+def _pack_sets(features, keypoints_only=False):
+    """A sequence of (keypoints, descriptors) host sets as an akz_feature_set array -> (the array, the arrays it points into
+    (keypoints, descriptors), the descriptor rows of every set, desc_bytes).  keypoints_only (akz_keypoint_budget_sets): a set may
+    be a bare keypoint array, and no descriptor is read."""
+    if keypoints_only:
+        ks = [np.ascontiguousarray(f[0] if isinstance(f, (tuple, list)) else f, KEYPOINT_DTYPE) for f in features]
+        ds, rows, nb = [None] * len(ks), [0] * len(ks), 61
+    else:
+        ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
+        ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
+        nbs = {d.shape[1] for d in ds if d.ndim == 2 and len(d)}
+        if len(nbs) > 1:
+            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
+        nb = nbs.pop() if nbs else 61
+        rows = [len(d) if d.ndim == 2 else 0 for d in ds]
+    sets = (FeatureSet * max(1, len(ks)))()
+    for i, (k, d, nd) in enumerate(zip(ks, ds, rows)):
+        sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), d.ctypes.data_as(C.c_void_p) if nd else None, nd)
+    return sets, (ks, ds), rows, nb
+
+
 class _PairsArgs:
     """What the pairs calls share: the akz_feature_set array, the pair list and the outputs (head: ctx, sets, n_sets, pairs,
     n_pairs, desc_bytes; tail: out, n_out), and the split of `out` into one list per pair afterwards."""
@@ -662,25 +738,15 @@ class _PairsArgs:
             return
         if isinstance(features, (str, bytes)) or not hasattr(features, "__iter__"):
             raise TypeError(f"features must be a FeatureBank or a sequence of (keypoints, descriptors), got {type(features).__name__}")
-        self.ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in features]
-        self.ds = [np.ascontiguousarray(d, np.uint8) for _, d in features]
-        nbs = {d.shape[1] for d in self.ds if d.ndim == 2 and len(d)}
-        if len(nbs) > 1:
-            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
-        nb = nbs.pop() if nbs else 61
-        self.sets = (FeatureSet * max(1, len(self.ks)))()
-        for i, (k, d) in enumerate(zip(self.ks, self.ds)):
-            nd = len(d) if d.ndim == 2 else 0
-            self.sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k),
-                                      d.ctypes.data_as(C.c_void_p) if nd else None, nd)
+        self.sets, self.keep, set_rows, nb = _pack_sets(features)
         self.pr = np.ascontiguousarray(np.asarray(pairs, np.uint64).reshape(-1, 2))
-        if len(self.ks) == 0 and len(self.pr):
+        if len(set_rows) == 0 and len(self.pr):
             raise IndexError("pair refers to a set that does not exist")
-        self.rows = [len(self.ds[int(a)]) if self.ds[int(a)].ndim == 2 else 0 for a in self.pr[:, 0]] if len(self.ks) else []
-        self.n_sets = len(self.ks)
+        self.rows = [set_rows[int(a)] for a in self.pr[:, 0]] if len(set_rows) else []
+        self.n_sets = len(set_rows)
         self.out = np.zeros(max(1, sum(self.rows)), MATCH_DTYPE)
         self.n = np.zeros(max(1, len(self.pr)), np.uint64)
-        self.head = (ctx._h, C.cast(self.sets, C.c_void_p), len(self.ks), self.pr.ctypes.data_as(C.c_void_p), len(self.pr), nb)
+        self.head = (ctx._h, C.cast(self.sets, C.c_void_p), self.n_sets, self.pr.ctypes.data_as(C.c_void_p), len(self.pr), nb)
         self.tail = (self.out.ctypes.data_as(C.c_void_p), self.n.ctypes.data_as(C.POINTER(C.c_uint64)))
 
     def models(self):
@@ -698,12 +764,27 @@ class _PairsArgs:
     def lists_and_models(self):
         return [(m, self.h[p].reshape(3, 3).copy() if self.found[p] else None) for p, m in enumerate(self.lists())]
 
-    def refined(self):
+    def iterations(self):
         self.it = np.zeros(max(1, len(self.pr)), np.uint32)
-        return (*self.models(), self.it.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return self.it.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def refined(self):
+        return (*self.models(), self.iterations())
 
     def lists_models_iterations(self):
         return [(m, h, int(self.it[p])) for p, (m, h) in enumerate(self.lists_and_models())]
+
+
+def _match_pairs(ctx, model, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations=None, guided=None):
+    """The nine Context.match_features*_pairs calls: akz_match_features{model}[_refined][_guided]_pairs (_match_name) -- _refined
+    with refine_iterations, _guided with guided = (guided_radius, guided_lowes_ratio).  One list per pair for model "", else one
+    (list, model or None) per pair, with refine_iterations one (list, model or None, accepted fits)."""
+    a = _PairsArgs(ctx, features, pairs)
+    refined = refine_iterations is not None
+    fn = getattr(lib(), _match_name(model, refined, guided, True))
+    _check(fn(*_match_run(a.head, (lowes_ratio, ransac_trials, ransac_epsilon_inliers), (refine_iterations,) if refined else (),
+                          guided or (), a.tail, a.models() if model else (), (a.iterations(),) if refined else ())))
+    return a.lists_models_iterations() if refined else a.lists_and_models() if model else a.lists()
 
 
 # ------------------------------------------------------------------------------------------
@@ -888,7 +969,7 @@ class Context:
         """akaze::extract_features on an in-memory luma image (2-D uint8 or float32 numpy array, or a
         torch CUDA tensor of shape [H, W] or [N, H, W]).  Returns an ExtractResult."""
         options = options or Config()
-        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS)
+        flags = _extract_flags(keep_all_planes, host_descriptors)
         res = C.c_void_p()
         L = lib()
         if isinstance(image, np.ndarray):
@@ -924,8 +1005,7 @@ class Context:
         """akaze::extract_features(input_image_path, options) — akaze/src/lib.rs:167-194."""
         cfg = options or Config()
         res = C.c_void_p()
-        _check(lib().akz_extract_features_file(self._h, os.fsencode(path), C.byref(cfg),
-                                               AKZ_KEEP_ALL_PLANES if keep_all_planes else 0, C.byref(res)))
+        _check(lib().akz_extract_features_file(self._h, os.fsencode(path), C.byref(cfg), _extract_flags(keep_all_planes), C.byref(res)))
         return ExtractResult(self, res)
 
     def extract_features_files(self, paths, options=None, keep_all_planes=True):
@@ -933,8 +1013,7 @@ class Context:
         cfg = options or Config()
         arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
         res = C.c_void_p()
-        _check(lib().akz_extract_features_files(self._h, arr, len(paths), C.byref(cfg),
-                                                AKZ_KEEP_ALL_PLANES if keep_all_planes else 0, C.byref(res)))
+        _check(lib().akz_extract_features_files(self._h, arr, len(paths), C.byref(cfg), _extract_flags(keep_all_planes), C.byref(res)))
         return ExtractResult(self, res)
 
     def load_luma_device(self, path):
@@ -979,8 +1058,7 @@ class Context:
         large batch then run ahead, under the kernels of the batch begun before."""
         import torch
         options = options or Config()
-        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS) | \
-                (AKZ_INPUT_READY if input_ready else 0)
+        flags = _extract_flags(keep_all_planes, host_descriptors, input_ready)
         t = frames
         if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()):
             raise ValueError("device images must be contiguous torch CUDA tensors")
@@ -1025,7 +1103,7 @@ class Context:
         mask (akz_extract_device_frames_masked): a uint8 or bool CUDA tensor [H, W] (shared) or [N, H, W], any row and frame
         strides; nonzero = detect here.  Masked pixels raise no extrema candidates (include/akaze_hip.h)."""
         options = options or Config()
-        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS)
+        flags = _extract_flags(keep_all_planes, host_descriptors)
         fl, n, _ = self._device_frames(t, layout, order)
         res = C.c_void_p()
         if mask is None:
@@ -1044,8 +1122,7 @@ class Context:
         runs on the context's copy stream, under the kernels of the batch begun before.  mask: as extract_frames.  The Job keeps
         the tensor and the mask alive."""
         options = options or Config()
-        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS) | \
-                (AKZ_INPUT_READY if input_ready else 0)
+        flags = _extract_flags(keep_all_planes, host_descriptors, input_ready)
         fl, n, _ = self._device_frames(t, layout, order)
         job = C.c_void_p()
         if mask is None:
@@ -1072,7 +1149,7 @@ class Context:
         m = np.ascontiguousarray(m).view(np.uint8)
         res = C.c_void_p()
         _check(lib().akz_extract_gray_u8_masked(self._h, img.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), img.shape[1],
-                                                img.shape[0], C.byref(options), AKZ_KEEP_ALL_PLANES if keep_all_planes else 0, C.byref(res)))
+                                                img.shape[0], C.byref(options), _extract_flags(keep_all_planes), C.byref(res)))
         return ExtractResult(self, res)
 
     def debug_mask_candidates(self, records, capacity, counts, mask, w, h, n, kept, options=None):
@@ -1097,7 +1174,7 @@ class Context:
         stream, under the kernels of the batch begun before.  The Job keeps the frames alive until it is finished."""
         import torch
         options = options or Config()
-        flags = (AKZ_KEEP_ALL_PLANES if keep_all_planes else 0) | (0 if host_descriptors else AKZ_NO_HOST_DESCRIPTORS)
+        flags = _extract_flags(keep_all_planes, host_descriptors)
         t = frames
         if isinstance(t, np.ndarray):
             t = torch.from_numpy(np.ascontiguousarray(t))
@@ -1115,35 +1192,20 @@ class Context:
 
     def descriptor_match(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """ops::feature_matching::descriptor_match (akaze/src/ops/feature_matching.rs:23-94)."""
-        d0 = np.ascontiguousarray(d0, np.uint8)
-        d1 = np.ascontiguousarray(d1, np.uint8)
-        nb = d0.shape[1] if d0.ndim == 2 and d0.shape[0] else (d1.shape[1] if d1.ndim == 2 else 61)
-        n0 = d0.shape[0] if d0.ndim == 2 else 0
-        n1 = d1.shape[0] if d1.ndim == 2 else 0
-        out = np.zeros(max(n0, 1), MATCH_DTYPE)
-        n = C.c_uint64()
-        _check(lib().akz_descriptor_match(self._h, d0.ctypes.data_as(C.c_void_p), n0, d1.ctypes.data_as(C.c_void_p),
-                                          n1, nb, distance_threshold, lowes_ratio, out.ctypes.data_as(C.c_void_p),
-                                          C.byref(n)))
-        return out[:n.value].copy()
+        return _descriptor_pair(lib().akz_descriptor_match, (self._h,), d0, d1, distance_threshold, lowes_ratio)
 
     def match_features_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
         """match_features (lib.rs:252-275) over many pairs in one call (akz_match_features_pairs): features is a list of
         (keypoints, descriptors) arrays (KEYPOINT_DTYPE / uint8 [n, desc_bytes]), pairs a sequence of (first, second) indices
         into it.  Returns one MATCH_DTYPE array per pair, each equal to what match_features returns for that pair when the
         pairs are matched in order on this thread."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers, *a.tail))
-        return a.lists()
+        return _match_pairs(self, "", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers)
 
     def match_features_homography_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
         """match_features_homography over many pairs in one call (akz_match_features_homography_pairs), arguments as for
         match_features_pairs.  Returns one (matches, H or None) per pair, each equal to what match_features_homography returns
         for that pair when the pairs are matched in order on this thread."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_homography_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers, *a.tail,
-                                                         *a.models()))
-        return a.lists_and_models()
+        return _match_pairs(self, "_homography", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers)
 
     def match_features_homography_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                guided_radius, guided_lowes_ratio):
@@ -1151,48 +1213,34 @@ class Context:
         (akz_match_features_homography_guided_pairs).  Returns one (matches, H or None) per pair: with an H the list of
         descriptor_match_guided(pair, GUIDED_HOMOGRAPHY, H, guided_radius, 10000, guided_lowes_ratio), without one the list
         of match_features_homography_pairs."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_homography_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                                guided_radius, guided_lowes_ratio, *a.tail, *a.models()))
-        return a.lists_and_models()
+        return _match_pairs(self, "_homography", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                            guided=(guided_radius, guided_lowes_ratio))
 
     def match_features_homography_refined_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                 refine_iterations):
         """match_features_homography_pairs with the refit of every H found on its inliers
         (akz_match_features_homography_refined_pairs).  Returns one (matches, H or None, accepted fits) per pair, each equal
         to what match_features_homography_refined returns for that pair when the pairs are matched in order on this thread."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_homography_refined_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                                 refine_iterations, *a.tail, *a.refined()))
-        return a.lists_models_iterations()
+        return _match_pairs(self, "_homography", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations)
 
     def match_features_homography_refined_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                        refine_iterations, guided_radius, guided_lowes_ratio):
         """match_features_homography_refined_pairs, then the guided scan with every REFINED H
         (akz_match_features_homography_refined_guided_pairs).  Returns one (matches, H or None, accepted fits) per pair."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_homography_refined_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                                        refine_iterations, guided_radius, guided_lowes_ratio, *a.tail,
-                                                                        *a.refined()))
-        return a.lists_models_iterations()
+        return _match_pairs(self, "_homography", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations,
+                            (guided_radius, guided_lowes_ratio))
 
     def match_features_fundamental_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers):
         """match_features_pairs with the fundamental matrix that filtered every pair (akz_match_features_fundamental_pairs).
         Returns one (matches, F or None) per pair: the list of match_features_pairs, F the RANSAC winner."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_fundamental_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers, *a.tail,
-                                                          *a.models()))
-        return a.lists_and_models()
+        return _match_pairs(self, "_fundamental", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers)
 
     def match_features_fundamental_refined_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                  refine_iterations):
         """match_features_fundamental_pairs with the refit of every F found on its inliers
         (akz_match_features_fundamental_refined_pairs).  Returns one (matches, F or None, accepted fits) per pair, each equal
         to what match_features_fundamental_refined returns for that pair when the pairs are matched in order on this thread."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_fundamental_refined_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                                  refine_iterations, *a.tail, *a.refined()))
-        return a.lists_models_iterations()
+        return _match_pairs(self, "_fundamental", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations)
 
     def match_features_fundamental_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                 guided_radius, guided_lowes_ratio):
@@ -1200,20 +1248,15 @@ class Context:
         (akz_match_features_fundamental_guided_pairs).  Returns one (matches, F or None) per pair: with an F the list of
         descriptor_match_guided(pair, GUIDED_FUNDAMENTAL, F, guided_radius, 10000, guided_lowes_ratio), without one the list
         of match_features_fundamental_pairs."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_fundamental_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                                 guided_radius, guided_lowes_ratio, *a.tail, *a.models()))
-        return a.lists_and_models()
+        return _match_pairs(self, "_fundamental", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                            guided=(guided_radius, guided_lowes_ratio))
 
     def match_features_fundamental_refined_guided_pairs(self, features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
                                                         refine_iterations, guided_radius, guided_lowes_ratio):
         """match_features_fundamental_refined_pairs, then the guided scan with every REFINED F
         (akz_match_features_fundamental_refined_guided_pairs).  Returns one (matches, F or None, accepted fits) per pair."""
-        a = _PairsArgs(self, features, pairs)
-        _check(lib().akz_match_features_fundamental_refined_guided_pairs(*a.head, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                                         refine_iterations, guided_radius, guided_lowes_ratio, *a.tail,
-                                                                         *a.refined()))
-        return a.lists_models_iterations()
+        return _match_pairs(self, "_fundamental", features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations,
+                            (guided_radius, guided_lowes_ratio))
 
     def feature_bank(self, results_or_features, budget=None):
         """A FeatureBank of this context: feature sets kept on the device in the layout the pairs calls scan.  From one
@@ -1243,20 +1286,11 @@ class Context:
         for f in src:
             if not (isinstance(f, (tuple, list)) and len(f) == 2):
                 raise TypeError(f"a host set is (keypoints, descriptors), got {type(f).__name__}")
-        ks = [np.ascontiguousarray(k, KEYPOINT_DTYPE) for k, _ in src]
-        ds = [np.ascontiguousarray(d, np.uint8) for _, d in src]
-        nbs = {d.shape[1] for d in ds if d.ndim == 2 and len(d)}
-        if len(nbs) > 1:
-            raise ValueError(f"descriptor lengths differ: {sorted(nbs)} bytes")
-        nb = nbs.pop() if nbs else 61
-        sets = (FeatureSet * max(1, len(ks)))()
-        for i, (k, d) in enumerate(zip(ks, ds)):
-            nd = len(d) if d.ndim == 2 else 0
-            sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), d.ctypes.data_as(C.c_void_p) if nd else None, nd)
+        sets, keep, rows, nb = _pack_sets(src)
         if budget is not None:
-            _check(lib().akz_bank_create_from_sets_budget(self._h, C.cast(sets, C.c_void_p), len(ks), nb, C.byref(budget), C.byref(h)))
+            _check(lib().akz_bank_create_from_sets_budget(self._h, C.cast(sets, C.c_void_p), len(rows), nb, C.byref(budget), C.byref(h)))
         else:
-            _check(lib().akz_bank_create_from_sets(self._h, C.cast(sets, C.c_void_p), len(ks), nb, C.byref(h)))
+            _check(lib().akz_bank_create_from_sets(self._h, C.cast(sets, C.c_void_p), len(rows), nb, C.byref(h)))
         return FeatureBank(self, h)
 
     def debug_bank_gather(self, src, desc_bytes, dst):
@@ -1292,12 +1326,11 @@ class Context:
         a = _PairsArgs(self, features, pairs, bank_ok=True)
         opt = options if options is not None else RansacOptions()
         tr = np.zeros(max(1, len(a.pr)), np.uint64)
-        if a.bank is not None:
-            _check(lib().akz_match_features_seeded_bank_pairs(*a.head, C.byref(opt), int(bool(cross_check)), *a.tail, *a.refined(),
-                                                              tr.ctypes.data_as(C.POINTER(C.c_uint64))))
-            return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
-        fn = lib().akz_match_features_seeded_cross_pairs if cross_check else lib().akz_match_features_seeded_pairs
-        _check(fn(*a.head, C.byref(opt), *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
+        if a.bank is not None:  # (the bank call takes cross_check as an argument, the host-set calls are two functions)
+            fn, cross = lib().akz_match_features_seeded_bank_pairs, (int(bool(cross_check)),)
+        else:
+            fn, cross = lib().akz_match_features_seeded_cross_pairs if cross_check else lib().akz_match_features_seeded_pairs, ()
+        _check(fn(*a.head, C.byref(opt), *cross, *a.tail, *a.refined(), tr.ctypes.data_as(C.POINTER(C.c_uint64))))
         return [(m, h, it, int(tr[p])) for p, (m, h, it) in enumerate(a.lists_models_iterations())]
 
     def match_features_seeded_pose_pairs(self, features, cameras, pairs, options=None, cross_check=False, points=False):
@@ -1382,19 +1415,12 @@ class Context:
     def descriptor_match_cross(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """Cross-checked descriptor_match (akz_descriptor_match_cross): the records of descriptor_match(d0, d1) whose train row,
         matched the other way round, comes back to the same query row.  Equal to descriptor_match_cross_host."""
-        return _cross_pair(lib().akz_descriptor_match_cross, (self._h,), d0, d1, distance_threshold, lowes_ratio)
+        return _descriptor_pair(lib().akz_descriptor_match_cross, (self._h,), d0, d1, distance_threshold, lowes_ratio)
 
     def descriptor_match_cross_device(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """descriptor_match_cross on torch CUDA uint8 tensors of 64-byte descriptor rows (akz_descriptor_match_cross_device);
         returns (matches tensor view, count) as descriptor_match_device does."""
-        import torch
-        n0, n1 = d0.shape[0], d1.shape[0]
-        out = torch.empty((max(n0, 1), 24), dtype=torch.uint8, device=d0.device)
-        cnt = torch.zeros(1, dtype=torch.int64, device=d0.device)
-        _check(lib().akz_descriptor_match_cross_device(self._h, C.c_void_p(d0.data_ptr()), n0, C.c_void_p(d1.data_ptr()),
-                                                       n1, distance_threshold, lowes_ratio, C.c_void_p(out.data_ptr()),
-                                                       C.c_void_p(cnt.data_ptr())))
-        return out, cnt
+        return self._device_pair(lib().akz_descriptor_match_cross_device, d0, d1, distance_threshold, lowes_ratio)
 
     def descriptor_match_knn(self, d0, d1, k, distance_threshold=10000):
         """k-nearest-neighbour matching on the GPU (akz_descriptor_match_knn): for every row of d0 its k nearest rows of d1 below
@@ -1425,10 +1451,7 @@ class Context:
         a sequence of (keypoints, descriptors) -- only the keypoints are read, a bare keypoint array will do.  Returns one
         (indices uint64 ascending, radius2 float32 [n] or None in BUDGET_STRONGEST mode) per set, each equal to
         keypoint_budget_host on that set."""
-        ks = [np.ascontiguousarray(f[0] if isinstance(f, (tuple, list)) else f, KEYPOINT_DTYPE) for f in features]
-        sets = (FeatureSet * max(1, len(ks)))()
-        for i, k in enumerate(ks):
-            sets[i] = FeatureSet(k.ctypes.data_as(C.c_void_p) if len(k) else None, len(k), None, 0)
+        sets, (ks, _), _, _ = _pack_sets(features, keypoints_only=True)
         total = sum(len(k) for k in ks)
         opt = KeypointBudget(int(max_keypoints), int(mode), float(robust))
         idx = np.zeros(max(1, total), np.uint64)
@@ -1451,13 +1474,15 @@ class Context:
 
     def descriptor_match_device(self, d0, d1, distance_threshold=10000, lowes_ratio=0.86):
         """Same on torch CUDA uint8 tensors of 64-byte descriptor rows; returns (matches tensor view, count)."""
+        return self._device_pair(lib().akz_descriptor_match_device, d0, d1, distance_threshold, lowes_ratio)
+
+    def _device_pair(self, fn, d0, d1, distance_threshold, lowes_ratio):
         import torch
         n0, n1 = d0.shape[0], d1.shape[0]
         out = torch.empty((max(n0, 1), 24), dtype=torch.uint8, device=d0.device)
         cnt = torch.zeros(1, dtype=torch.int64, device=d0.device)
-        _check(lib().akz_descriptor_match_device(self._h, C.c_void_p(d0.data_ptr()), n0, C.c_void_p(d1.data_ptr()),
-                                                 n1, distance_threshold, lowes_ratio, C.c_void_p(out.data_ptr()),
-                                                 C.c_void_p(cnt.data_ptr())))
+        _check(fn(self._h, C.c_void_p(d0.data_ptr()), n0, C.c_void_p(d1.data_ptr()), n1, distance_threshold, lowes_ratio,
+                  C.c_void_p(out.data_ptr()), C.c_void_p(cnt.data_ptr())))
         return out, cnt
 
     # ---- per-op entry points on torch CUDA float32 tensors [N, H, W] or [H, W] -----------
@@ -1946,29 +1971,18 @@ def deserialize_matches_from_file(path):
 
 def estimate_fundamental_matrix(keypoints_0, keypoints_1, matches8, epsilon):
     """ops::estimate_fundamental_matrix::estimate_fundamental_matrix (:17-69): 3x3 float32 matrix or None."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches8, MATCH_DTYPE)
-    if len(m) != 8:
+    a = _MatchList(keypoints_0, keypoints_1, matches8)
+    if len(a.m) != 8:
         raise ValueError("exactly 8 matches")
-    f = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_estimate_fundamental_matrix(k0.ctypes.data, len(k0), k1.ctypes.data, len(k1), m.ctypes.data, epsilon,
-                                                 f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
-    return f.reshape(3, 3) if found.value else None
+    _check(lib().akz_estimate_fundamental_matrix(*a.head[:5], epsilon, *a.model_out))  # (a sample's size is fixed: no n_matches)
+    return a.found_model()
 
 
 def remove_outliers(keypoints_0, keypoints_1, matches, num_trials, epsilon_model, epsilon_inlier):
     """ops::estimate_fundamental_matrix::remove_outliers (estimate_fundamental_matrix.rs:99-165); host only."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    _check(lib().akz_remove_outliers(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                     m.ctypes.data_as(C.c_void_p), len(m), num_trials, epsilon_model, epsilon_inlier,
-                                     out.ctypes.data_as(C.c_void_p), C.byref(n)))
-    return out[:n.value].copy()
+    a = _MatchList(keypoints_0, keypoints_1, matches)
+    _check(lib().akz_remove_outliers(*a.head, num_trials, epsilon_model, epsilon_inlier, *a.tail))
+    return a.list()
 
 
 def match_features(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials=None,
@@ -1979,21 +1993,24 @@ def match_features(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes
     c = ctx or default_context()
     if ransac_trials is None:
         return c.descriptor_match(descriptors_0, descriptors_1, 10000, lowes_ratio)
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
-    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
-    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
-    n = C.c_uint64()
-    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
-    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
-    if nb0 is not None and nb1 is not None and nb0 != nb1:
-        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
-    _check(lib().akz_match_features(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), len(d0),
-                                    k1.ctypes.data_as(C.c_void_p), len(k1), d1.ctypes.data_as(C.c_void_p), len(d1),
-                                    nb0 or nb1 or 61, lowes_ratio, ransac_trials,
-                                    ransac_epsilon_inliers, out.ctypes.data_as(C.c_void_p), C.byref(n)))
-    return out[:n.value].copy()
+    return _match_pair("", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                       ctx=c)
+
+
+def _match_pair(model, keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
+                refine_iterations=None, guided=None, ctx=None):
+    """The nine single-pair calls akz_match_features{model}[_refined][_guided] (_match_name), as _match_pairs states their
+    pairs forms -> matches for model "", else (matches, model or None), with refine_iterations (matches, model or None, accepted
+    fits)."""
+    c = ctx or default_context()
+    a = _PairArgs(descriptors_0, descriptors_1, keypoints_0, keypoints_1)
+    refined = refine_iterations is not None
+    fn = getattr(lib(), _match_name(model, refined, guided, False))
+    _check(fn(*_match_run((c._h, *a.head), (lowes_ratio, ransac_trials, ransac_epsilon_inliers), (refine_iterations,) if refined else (),
+                          guided or (), a.tail, a.model_out if model else (), (C.byref(a.it),) if refined else ())))
+    if not model:
+        return a.list()
+    return (a.list(), a.found_model(), a.it.value) if refined else (a.list(), a.found_model())
 
 
 def match_features_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
@@ -2007,32 +2024,18 @@ HOMOGRAPHY_EPSILON_MODEL = 1e-6  # AKZ_HOMOGRAPHY_EPSILON_MODEL: the epsilon_mod
 
 def estimate_homography(keypoints_0, keypoints_1, matches4, epsilon):
     """The 4-point homography of exactly 4 matches (akz_estimate_homography): 3x3 float32 H with H[2, 2] = 1, or None."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches4, MATCH_DTYPE)
-    if len(m) != 4:
+    a = _MatchList(keypoints_0, keypoints_1, matches4)
+    if len(a.m) != 4:
         raise ValueError("exactly 4 matches")
-    h = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_estimate_homography(k0.ctypes.data, len(k0), k1.ctypes.data, len(k1), m.ctypes.data, epsilon,
-                                         h.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
-    return h.reshape(3, 3) if found.value else None
+    _check(lib().akz_estimate_homography(*a.head[:5], epsilon, *a.model_out))  # (a sample's size is fixed: no n_matches)
+    return a.found_model()
 
 
 def remove_outliers_homography(keypoints_0, keypoints_1, matches, num_trials, epsilon_model, epsilon_inlier):
     """The homography RANSAC on the host (akz_remove_outliers_homography) -> (matches kept, H or None)."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    h = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_remove_outliers_homography(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                                m.ctypes.data_as(C.c_void_p), len(m), num_trials, epsilon_model, epsilon_inlier,
-                                                out.ctypes.data_as(C.c_void_p), C.byref(n), h.ctypes.data_as(C.POINTER(C.c_float)),
-                                                C.byref(found)))
-    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+    a = _MatchList(keypoints_0, keypoints_1, matches)
+    _check(lib().akz_remove_outliers_homography(*a.head, num_trials, epsilon_model, epsilon_inlier, *a.tail, *a.model_out))
+    return a.list(), a.found_model()
 
 
 def match_features_homography(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
@@ -2040,25 +2043,8 @@ def match_features_homography(keypoints_0, descriptors_0, keypoints_1, descripto
     """descriptor_match(d0, d1, 10000, ratio), then the homography RANSAC, all on the GPU (akz_match_features_homography)
     -> (matches kept, H or None); equal to remove_outliers_homography(k0, k1, that list, ransac_trials,
     HOMOGRAPHY_EPSILON_MODEL, ransac_epsilon_inliers) from the same random state."""
-    c = ctx or default_context()
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
-    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
-    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
-    n = C.c_uint64()
-    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
-    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
-    if nb0 is not None and nb1 is not None and nb0 != nb1:
-        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
-    h = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_match_features_homography(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), len(d0),
-                                               k1.ctypes.data_as(C.c_void_p), len(k1), d1.ctypes.data_as(C.c_void_p), len(d1),
-                                               nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                               out.ctypes.data_as(C.c_void_p), C.byref(n), h.ctypes.data_as(C.POINTER(C.c_float)),
-                                               C.byref(found)))
-    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+    return _match_pair("_homography", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, ctx=ctx)
 
 
 def match_features_homography_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
@@ -2074,23 +2060,10 @@ GUIDED_FUNDAMENTAL = 1  # AKZ_GUIDED_FUNDAMENTAL: the model is F, the gate a ban
 
 def _guided_pair(fn, first, keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind, radius, distance_threshold,
                  lowes_ratio):
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
-    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
-    n0 = len(d0) if d0.ndim == 2 else 0
-    n1 = len(d1) if d1.ndim == 2 else 0
-    nb0 = d0.shape[1] if n0 else None
-    nb1 = d1.shape[1] if n1 else None
-    if nb0 is not None and nb1 is not None and nb0 != nb1:
-        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
+    a = _PairArgs(descriptors_0, descriptors_1, keypoints_0, keypoints_1)
     md = np.ascontiguousarray(np.asarray(model, np.float32).reshape(9))
-    out = np.zeros(max(1, n0), MATCH_DTYPE)
-    n = C.c_uint64()
-    _check(fn(*first, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), n0, k1.ctypes.data_as(C.c_void_p), len(k1),
-              d1.ctypes.data_as(C.c_void_p), n1, nb0 or nb1 or 61, int(kind), md.ctypes.data_as(C.POINTER(C.c_float)), radius,
-              distance_threshold, lowes_ratio, out.ctypes.data_as(C.c_void_p), C.byref(n)))
-    return out[:n.value].copy()
+    _check(fn(*first, *a.head, int(kind), md.ctypes.data_as(C.POINTER(C.c_float)), radius, distance_threshold, lowes_ratio, *a.tail))
+    return a.list()
 
 
 def descriptor_match_guided_host(keypoints_0, descriptors_0, keypoints_1, descriptors_1, model, kind, radius,
@@ -2120,25 +2093,8 @@ def match_features_homography_guided(keypoints_0, descriptors_0, keypoints_1, de
                                      ransac_epsilon_inliers, guided_radius, guided_lowes_ratio, ctx=None):
     """match_features_homography, then the guided scan with the H it found (akz_match_features_homography_guided) ->
     (matches, H or None): with an H the guided list, without one the list of match_features_homography."""
-    c = ctx or default_context()
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
-    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
-    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
-    n = C.c_uint64()
-    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
-    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
-    if nb0 is not None and nb1 is not None and nb0 != nb1:
-        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
-    h = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_match_features_homography_guided(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p),
-                                                      len(d0), k1.ctypes.data_as(C.c_void_p), len(k1), d1.ctypes.data_as(C.c_void_p),
-                                                      len(d1), nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                                                      guided_radius, guided_lowes_ratio, out.ctypes.data_as(C.c_void_p), C.byref(n),
-                                                      h.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
-    return out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
+    return _match_pair("_homography", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, guided=(guided_radius, guided_lowes_ratio), ctx=ctx)
 
 
 def match_features_homography_guided_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, guided_radius,
@@ -2153,46 +2109,14 @@ def refine_homography(keypoints_0, keypoints_1, matches, h, epsilon_inlier, max_
     """Local optimisation of the homography h over a raw match list on the host (akz_refine_homography): least-squares refits
     on the inliers and re-classification until the set stops growing -> (inliers in match order, 3x3 float32 H, accepted
     fits).  With 0 accepted fits H is h and the list its inliers."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    hin = np.ascontiguousarray(np.asarray(h, np.float32).reshape(9))
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    hout = np.zeros(9, np.float32)
-    it = C.c_uint32()
-    _check(lib().akz_refine_homography(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                       m.ctypes.data_as(C.c_void_p), len(m), hin.ctypes.data_as(C.POINTER(C.c_float)), epsilon_inlier,
-                                       max_iterations, out.ctypes.data_as(C.c_void_p), C.byref(n),
-                                       hout.ctypes.data_as(C.POINTER(C.c_float)), C.byref(it)))
-    return out[:n.value].copy(), hout.reshape(3, 3), it.value
+    return _refine(lib().akz_refine_homography, keypoints_0, keypoints_1, matches, h, epsilon_inlier, max_iterations)
 
 
-def _refined_pair(fn, extra, keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
-                  ransac_epsilon_inliers, refine_iterations, ctx):
-    """a single-pair call that hands back (list, model, found[, accepted fits]) -> (matches, model or None[, accepted fits]);
-    refine_iterations None: a call without the refit stage's two arguments"""
-    c = ctx or default_context()
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    d0 = np.ascontiguousarray(descriptors_0, np.uint8)
-    d1 = np.ascontiguousarray(descriptors_1, np.uint8)
-    out = np.zeros(max(1, len(d0)), MATCH_DTYPE)
-    n = C.c_uint64()
-    nb0 = d0.shape[1] if d0.ndim == 2 and len(d0) else None
-    nb1 = d1.shape[1] if d1.ndim == 2 and len(d1) else None
-    if nb0 is not None and nb1 is not None and nb0 != nb1:
-        raise ValueError(f"descriptor lengths differ: {nb0} and {nb1} bytes")
-    h = np.zeros(9, np.float32)
-    found = C.c_int()
-    it = C.c_uint32()
-    refit = refine_iterations is not None
-    _check(fn(c._h, k0.ctypes.data_as(C.c_void_p), len(k0), d0.ctypes.data_as(C.c_void_p), len(d0), k1.ctypes.data_as(C.c_void_p), len(k1),
-              d1.ctypes.data_as(C.c_void_p), len(d1), nb0 or nb1 or 61, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-              *((refine_iterations,) if refit else ()), *extra, out.ctypes.data_as(C.c_void_p), C.byref(n),
-              h.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found), *((C.byref(it),) if refit else ())))
-    res = out[:n.value].copy(), (h.reshape(3, 3) if found.value else None)
-    return (*res, it.value) if refit else res
+def _refine(fn, keypoints_0, keypoints_1, matches, model, epsilon_inlier, max_iterations):
+    """a refit on the host -> (inliers in match order, the 3x3 model, accepted fits)"""
+    a = _MatchList(keypoints_0, keypoints_1, matches, model)
+    _check(fn(*a.head, epsilon_inlier, max_iterations, *a.tail, a.model_out[0], C.byref(a.it)))
+    return a.list(), a.model.reshape(3, 3), a.it.value
 
 
 def match_features_homography_refined(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
@@ -2200,17 +2124,16 @@ def match_features_homography_refined(keypoints_0, descriptors_0, keypoints_1, d
     """match_features_homography with the refit of the H it found as one more stage on the GPU
     (akz_match_features_homography_refined) -> (matches, H or None, accepted fits): with an H what refine_homography gives on
     the raw descriptor_match list from the winner, without one the list of match_features_homography."""
-    return _refined_pair(lib().akz_match_features_homography_refined, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1,
-                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, ctx)
+    return _match_pair("_homography", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, refine_iterations, ctx=ctx)
 
 
 def match_features_homography_refined_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
                                              ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
     """match_features_homography_refined, then the guided scan with the REFINED H
     (akz_match_features_homography_refined_guided) -> (matches, H or None, accepted fits)."""
-    return _refined_pair(lib().akz_match_features_homography_refined_guided, (guided_radius, guided_lowes_ratio), keypoints_0,
-                         descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                         refine_iterations, ctx)
+    return _match_pair("_homography", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, refine_iterations, (guided_radius, guided_lowes_ratio), ctx)
 
 
 def match_features_homography_refined_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations,
@@ -2234,37 +2157,16 @@ FUNDAMENTAL_REFIT_EPSILON = 1e-6  # AKZ_FUNDAMENTAL_REFIT_EPSILON: the rank rule
 def remove_outliers_fundamental(keypoints_0, keypoints_1, matches, num_trials, epsilon_model, epsilon_inlier):
     """remove_outliers with the model that filtered (akz_remove_outliers_fundamental; host only) -> (matches kept, F or None):
     the list and the draws of remove_outliers, F the first trial with the most inliers (3x3 float32, p1^T F p0 = 0)."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    f = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_remove_outliers_fundamental(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                                 m.ctypes.data_as(C.c_void_p), len(m), num_trials, epsilon_model, epsilon_inlier,
-                                                 out.ctypes.data_as(C.c_void_p), C.byref(n), f.ctypes.data_as(C.POINTER(C.c_float)),
-                                                 C.byref(found)))
-    return out[:n.value].copy(), (f.reshape(3, 3) if found.value else None)
+    a = _MatchList(keypoints_0, keypoints_1, matches)
+    _check(lib().akz_remove_outliers_fundamental(*a.head, num_trials, epsilon_model, epsilon_inlier, *a.tail, *a.model_out))
+    return a.list(), a.found_model()
 
 
 def refine_fundamental_matrix(keypoints_0, keypoints_1, matches, f, epsilon_inlier, max_iterations):
     """Local optimisation of the fundamental matrix f over a raw match list on the host (akz_refine_fundamental_matrix):
     normalised least-squares refits on the inliers, rank 2 enforced, and re-classification until the set stops growing ->
     (inliers in match order, 3x3 float32 F of unit norm, accepted fits).  With 0 accepted fits F is f and the list its inliers."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    fin = np.ascontiguousarray(np.asarray(f, np.float32).reshape(9))
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    fout = np.zeros(9, np.float32)
-    it = C.c_uint32()
-    _check(lib().akz_refine_fundamental_matrix(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                               m.ctypes.data_as(C.c_void_p), len(m), fin.ctypes.data_as(C.POINTER(C.c_float)),
-                                               epsilon_inlier, max_iterations, out.ctypes.data_as(C.c_void_p), C.byref(n),
-                                               fout.ctypes.data_as(C.POINTER(C.c_float)), C.byref(it)))
-    return out[:n.value].copy(), fout.reshape(3, 3), it.value
+    return _refine(lib().akz_refine_fundamental_matrix, keypoints_0, keypoints_1, matches, f, epsilon_inlier, max_iterations)
 
 
 def match_features_fundamental(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
@@ -2272,16 +2174,16 @@ def match_features_fundamental(keypoints_0, descriptors_0, keypoints_1, descript
     """match_features with the fundamental matrix that filtered (akz_match_features_fundamental) -> (matches kept, F or None);
     equal to remove_outliers_fundamental(k0, k1, descriptor_match(d0, d1, 10000, ratio), ransac_trials, 0.05,
     ransac_epsilon_inliers) from the same random state."""
-    return _refined_pair(lib().akz_match_features_fundamental, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio,
-                         ransac_trials, ransac_epsilon_inliers, None, ctx)
+    return _match_pair("_fundamental", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, ctx=ctx)
 
 
 def match_features_fundamental_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
                                       ransac_epsilon_inliers, guided_radius, guided_lowes_ratio, ctx=None):
     """match_features_fundamental, then the guided scan with the F it found (akz_match_features_fundamental_guided) ->
     (matches, F or None): with an F the guided list, without one the list of match_features_fundamental."""
-    return _refined_pair(lib().akz_match_features_fundamental_guided, (guided_radius, guided_lowes_ratio), keypoints_0, descriptors_0,
-                         keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers, None, ctx)
+    return _match_pair("_fundamental", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, guided=(guided_radius, guided_lowes_ratio), ctx=ctx)
 
 
 def match_features_fundamental_refined(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
@@ -2289,17 +2191,16 @@ def match_features_fundamental_refined(keypoints_0, descriptors_0, keypoints_1, 
     """match_features_fundamental with the refit of the F it found as one more stage on the GPU
     (akz_match_features_fundamental_refined) -> (matches, F or None, accepted fits): with an F what refine_fundamental_matrix
     gives on the raw descriptor_match list from the winner, without one the list of match_features_fundamental."""
-    return _refined_pair(lib().akz_match_features_fundamental_refined, (), keypoints_0, descriptors_0, keypoints_1, descriptors_1,
-                         lowes_ratio, ransac_trials, ransac_epsilon_inliers, refine_iterations, ctx)
+    return _match_pair("_fundamental", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, refine_iterations, ctx=ctx)
 
 
 def match_features_fundamental_refined_guided(keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
                                               ransac_epsilon_inliers, refine_iterations, guided_radius, guided_lowes_ratio, ctx=None):
     """match_features_fundamental_refined, then the guided scan with the REFINED F
     (akz_match_features_fundamental_refined_guided) -> (matches, F or None, accepted fits)."""
-    return _refined_pair(lib().akz_match_features_fundamental_refined_guided, (guided_radius, guided_lowes_ratio), keypoints_0,
-                         descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials, ransac_epsilon_inliers,
-                         refine_iterations, ctx)
+    return _match_pair("_fundamental", keypoints_0, descriptors_0, keypoints_1, descriptors_1, lowes_ratio, ransac_trials,
+                       ransac_epsilon_inliers, refine_iterations, (guided_radius, guided_lowes_ratio), ctx)
 
 
 def match_features_fundamental_pairs(features, pairs, lowes_ratio, ransac_trials, ransac_epsilon_inliers, ctx=None):
@@ -2343,34 +2244,17 @@ def estimate_fundamental_normalised(keypoints_0, keypoints_1, matches8):
     """The normalised 8-point fundamental matrix of exactly 8 matches, given in ascending order of their position in the list
     they were sampled from (akz_estimate_fundamental_normalised): 3x3 float32 F of unit norm and rank 2 with p1^T F p0 = 0, or
     None.  It equals one fit of refine_fundamental_matrix over those eight, bit for bit."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches8, MATCH_DTYPE)
-    if len(m) != 8:
+    a = _MatchList(keypoints_0, keypoints_1, matches8)
+    if len(a.m) != 8:
         raise ValueError("exactly 8 matches")
-    f = np.zeros(9, np.float32)
-    found = C.c_int()
-    _check(lib().akz_estimate_fundamental_normalised(k0.ctypes.data, len(k0), k1.ctypes.data, len(k1), m.ctypes.data,
-                                                     f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found)))
-    return f.reshape(3, 3) if found.value else None
+    _check(lib().akz_estimate_fundamental_normalised(*a.head[:5], *a.model_out))  # (a sample's size is fixed: no n_matches)
+    return a.found_model()
 
 
 def refine_fundamental_normalised(keypoints_0, keypoints_1, matches, f, epsilon_inlier, max_iterations):
     """refine_fundamental_matrix with the inlier rule of RANSAC_FUNDAMENTAL_NORMALISED: a Sampson distance below epsilon_inlier
     pixels (akz_refine_fundamental_normalised) -> (inliers in match order, 3x3 float32 F, accepted fits)."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    fin = np.ascontiguousarray(np.asarray(f, np.float32).reshape(9))
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    fout = np.zeros(9, np.float32)
-    it = C.c_uint32()
-    _check(lib().akz_refine_fundamental_normalised(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                                   m.ctypes.data_as(C.c_void_p), len(m), fin.ctypes.data_as(C.POINTER(C.c_float)),
-                                                   epsilon_inlier, max_iterations, out.ctypes.data_as(C.c_void_p), C.byref(n),
-                                                   fout.ctypes.data_as(C.POINTER(C.c_float)), C.byref(it)))
-    return out[:n.value].copy(), fout.reshape(3, 3), it.value
+    return _refine(lib().akz_refine_fundamental_normalised, keypoints_0, keypoints_1, matches, f, epsilon_inlier, max_iterations)
 
 
 def draw_sample_seeded(seed0, seed1, stream, trial, n_matches, k):
@@ -2391,20 +2275,11 @@ def remove_outliers_seeded(keypoints_0, keypoints_1, matches, options=None, stre
     """The seeded RANSAC on the host (akz_remove_outliers_seeded; no GPU call) -> (matches kept, model or None, accepted fits,
     trials run): rounds of 128 trials whose samples are a function of (options.seed, stream, trial), stopped by
     options.confidence, then the filter and, with options.refine_iterations, the refit."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    a = _MatchList(keypoints_0, keypoints_1, matches)
     opt = options if options is not None else RansacOptions()
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    n = C.c_uint64()
-    f = np.zeros(9, np.float32)
-    found = C.c_int()
-    it = C.c_uint32()
     tr = C.c_uint64()
-    _check(lib().akz_remove_outliers_seeded(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                            m.ctypes.data_as(C.c_void_p), len(m), C.byref(opt), stream, out.ctypes.data_as(C.c_void_p),
-                                            C.byref(n), f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(found), C.byref(it), C.byref(tr)))
-    return out[:n.value].copy(), (f.reshape(3, 3) if found.value else None), it.value, tr.value
+    _check(lib().akz_remove_outliers_seeded(*a.head, C.byref(opt), stream, *a.tail, *a.model_out, C.byref(a.it), C.byref(tr)))
+    return a.list(), a.found_model(), a.it.value, tr.value
 
 
 def _bank_context(features):
@@ -2428,22 +2303,15 @@ def recover_pose_host(keypoints_0, keypoints_1, matches, f, camera_0, camera_1, 
     """The relative pose behind a fundamental matrix on the host (akz_recover_pose_host; no GPU call): E = K1^T F K0, its four
     (R, t) candidates, the one with the most matches in front of both cameras -> (the matches in front under it, in order -- the
     input unchanged without a pose --, Pose) and, with points=True, the [kept, 3] float32 structure (None without a pose)."""
-    k0 = np.ascontiguousarray(keypoints_0, KEYPOINT_DTYPE)
-    k1 = np.ascontiguousarray(keypoints_1, KEYPOINT_DTYPE)
-    m = np.ascontiguousarray(matches, MATCH_DTYPE)
-    fm = np.ascontiguousarray(np.asarray(f, np.float32).reshape(9))
+    a = _MatchList(keypoints_0, keypoints_1, matches, f)
     c0, c1 = Camera.of(camera_0), Camera.of(camera_1)
-    out = np.zeros(max(1, len(m)), MATCH_DTYPE)
-    pts = np.zeros((max(1, len(m)), 3), np.float32) if points else None
-    n = C.c_uint64()
+    pts = np.zeros((len(a.out), 3), np.float32) if points else None
     pose = Pose()
-    _check(lib().akz_recover_pose_host(k0.ctypes.data_as(C.c_void_p), len(k0), k1.ctypes.data_as(C.c_void_p), len(k1),
-                                       m.ctypes.data_as(C.c_void_p), len(m), fm.ctypes.data_as(C.POINTER(C.c_float)), C.byref(c0), C.byref(c1),
-                                       out.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(pose),
+    _check(lib().akz_recover_pose_host(*a.head, C.byref(c0), C.byref(c1), *a.tail, C.byref(pose),
                                        pts.ctypes.data_as(C.POINTER(C.c_float)) if points else None))
     if points:
-        return out[:n.value].copy(), pose, (pts[:n.value].copy() if pose.found else None)
-    return out[:n.value].copy(), pose
+        return a.list(), pose, (pts[:a.n.value].copy() if pose.found else None)
+    return a.list(), pose
 
 
 def match_features_seeded_pose_pairs(features, cameras, pairs, options=None, ctx=None, cross_check=False, points=False):
@@ -2461,32 +2329,21 @@ def match_features_seeded_pose(keypoints_0, descriptors_0, camera_0, keypoints_1
                                                                        points=points)[0]
 
 
-def _cross_pair(fn, first, d0, d1, distance_threshold, lowes_ratio):
-    d0 = np.ascontiguousarray(d0, np.uint8)
-    d1 = np.ascontiguousarray(d1, np.uint8)
-    nb = d0.shape[1] if d0.ndim == 2 and d0.shape[0] else (d1.shape[1] if d1.ndim == 2 else 61)
-    n0 = d0.shape[0] if d0.ndim == 2 else 0
-    n1 = d1.shape[0] if d1.ndim == 2 else 0
-    out = np.zeros(max(n0, 1), MATCH_DTYPE)
-    n = C.c_uint64()
-    _check(fn(*first, d0.ctypes.data_as(C.c_void_p), n0, d1.ctypes.data_as(C.c_void_p), n1, nb, distance_threshold, lowes_ratio,
-              out.ctypes.data_as(C.c_void_p), C.byref(n)))
-    return out[:n.value].copy()
+def _descriptor_pair(fn, first, d0, d1, distance_threshold, lowes_ratio):
+    """descriptor_match and its cross-checked forms over two host descriptor arrays -> the list"""
+    a = _PairArgs(d0, d1)
+    _check(fn(*first, *a.head, distance_threshold, lowes_ratio, *a.tail))
+    return a.list()
 
 
 def _knn_pair(fn, first, d0, d1, k, distance_threshold):
-    d0 = np.ascontiguousarray(d0, np.uint8)
-    d1 = np.ascontiguousarray(d1, np.uint8)
-    nb = d0.shape[1] if d0.ndim == 2 and d0.shape[0] else (d1.shape[1] if d1.ndim == 2 else 61)
-    n0 = d0.shape[0] if d0.ndim == 2 else 0
-    n1 = d1.shape[0] if d1.ndim == 2 else 0
+    a = _PairArgs(d0, d1, null_empty=True)
     k = int(k)
-    out = np.zeros((n0, max(k, 0)), MATCH_DTYPE)
-    counts = np.zeros(n0, np.uint32)
+    out = np.zeros((a.n0, max(k, 0)), MATCH_DTYPE)
+    counts = np.zeros(a.n0, np.uint32)
     pad_out = out if out.size else np.zeros(1, MATCH_DTYPE)        # (never written: there is no row to write for)
     pad_cnt = counts if counts.size else np.zeros(1, np.uint32)
-    _check(fn(*first, d0.ctypes.data_as(C.c_void_p) if n0 else None, n0, d1.ctypes.data_as(C.c_void_p) if n1 else None, n1, nb, k,
-              distance_threshold, pad_out.ctypes.data_as(C.c_void_p), pad_cnt.ctypes.data_as(C.c_void_p)))
+    _check(fn(*first, *a.head, k, distance_threshold, pad_out.ctypes.data_as(C.c_void_p), pad_cnt.ctypes.data_as(C.c_void_p)))
     return out, counts
 
 
@@ -2537,7 +2394,7 @@ def descriptor_match_cross_host(d0, d1, distance_threshold=10000, lowes_ratio=0.
     """The cross-check on the host (akz_descriptor_match_cross_host; no GPU call): m of descriptor_match(d0, d1) is kept iff
     descriptor_match(d1, d0) holds the record with index_0 == m.index_1 and index_1 == m.index_0.  The statement that
     Context.descriptor_match_cross and the cross_check of the seeded calls are held to."""
-    return _cross_pair(lib().akz_descriptor_match_cross_host, (), d0, d1, distance_threshold, lowes_ratio)
+    return _descriptor_pair(lib().akz_descriptor_match_cross_host, (), d0, d1, distance_threshold, lowes_ratio)
 
 
 # ------------------------------------------------------------------------------------------
