@@ -338,7 +338,8 @@ struct CtxOwned {
     DevBuf kb_dev, kb_pin;
     Event kb_split_ev[4];                    // akz_debug_keypoint_budget_split: stage boundaries of a timed call
     Event mp_smp_ev[2];
-    Event mp_split_ev[7];                    // akz_debug_match_pairs_split: stage boundaries of a timed call
+    Event mp_split_ev[7];                    // akz_debug_match_pairs_split: stage boundaries of a timed call; akz_debug_resection_split uses the
+                                             // first five for the resection call's (one call at a time runs on a context's stream)
     // The matcher's scratch, twice.  Side 0 serves every call on the context's stream (descriptor_match, the pairs calls, kNN);
     // akz_match_all_pairs runs the launches of consecutive lead images alternately there and on the finish stream with side 1
     // (akz::match_sets_at), so that the small launches around one image's pass (unpack, seed, compactions: 130 us of 550) run
@@ -397,6 +398,11 @@ struct CtxOwned {
     DevBuf jpeg_pin[kJpegSlots];
     Event jpeg_up[kJpegSlots];
     DevBuf jpeg_coef, jpeg_plane, jpeg_frames;
+    // the resection (akz_resection_api.cpp): problem table | done | need | five planes (the upload), the rounds' state, then
+    // kept counts | fits | trials | poses | kept indices (the read-back); pinned: the upload's image, the running count, the
+    // read-back.  No claim: every call writes or clears what its kernels read.  (Last, and 64 bytes together: every member that
+    // the extraction's threads share keeps its place within its cache line.)
+    DevBuf rs_dev, rs_pin;
 };
 static_assert(std::is_nothrow_move_assignable<CtxOwned>::value && !std::is_copy_constructible<CtxOwned>::value, "released by assigning an empty one; never copied");
 struct akz_ctx : CtxOwned {
@@ -456,6 +462,8 @@ struct akz_ctx : CtxOwned {
         return *workers;
     }
     std::mutex jpeg_m;                  // orders the uploads of a batch's JPEG decoding threads on the stream
+    bool rs_split_on = false;           // akz_debug_resection_split
+    double rs_split_ms[4] = {};
 };
 // What a lane runs with: its parent's settings, with the job gates no lower than lane_px (a job that is dealt to a lane runs there
 // as a one-stream chain)
@@ -842,5 +850,7 @@ AKZ_LOCAL int match_seeded_pairs_impl(const PairsCall& q, bool cross, const akz_
 // akz_pose_api.cpp: the refusals of akz_match_features_seeded_pose_pairs that are not the seeded call's
 AKZ_LOCAL int pose_pairs_refusals(const char* name, const akz_ransac_options* options, const akz_camera* cameras, uint64_t n_sets,
                                   const akz_pose* poses);
+// ... and the one camera rule of every call that takes an akz_camera (akz_recover_pose_host's): finite fields, fx and fy not zero
+AKZ_LOCAL bool camera_ok(const akz_camera& k);
 // akz_extract_finish.cpp
 AKZ_LOCAL int device_libm_mode(akz_ctx* c);  // 0: host libm; 1 / 2: the device's FMA / SSE2 forms reproduce it (akz_libm.hpp)

@@ -25,12 +25,13 @@ struct Mat8x9 {
     double v[8][9];
     AKZ_HD double& at(int p, int k) { return v[p][k]; }
 };
-// one Hestenes rotation of rows p, q (columns of A^T); false: the pair is orthogonal already
-template <class M>
+// one Hestenes rotation of rows p, q (columns of A^T) over their first COLS entries; false: the pair is orthogonal already
+// (COLS: nine for every model of two views; the resection of akz_resection.hpp has twelve)
+template <int COLS = 9, class M>
 AKZ_HD bool jacobi_pair(M& m, int p, int q) {
     double alpha = 0.0, beta = 0.0, gamma = 0.0;
     AKZ_UNROLL
-    for (int k = 0; k < 9; ++k) {
+    for (int k = 0; k < COLS; ++k) {
         const double x = m.at(p, k), y = m.at(q, k);
         alpha += x * x;
         beta += y * y;
@@ -41,7 +42,7 @@ AKZ_HD bool jacobi_pair(M& m, int p, int q) {
     const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
     const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
     AKZ_UNROLL
-    for (int k = 0; k < 9; ++k) {
+    for (int k = 0; k < COLS; ++k) {
         const double x = m.at(p, k), y = m.at(q, k);
         m.at(p, k) = c * x - sn * y;
         m.at(q, k) = sn * x + c * y;
@@ -50,12 +51,12 @@ AKZ_HD bool jacobi_pair(M& m, int p, int q) {
 }
 // sweeps over the pairs of the first ROWS rows in row-cyclic order (0,1) (0,2) .. (0,ROWS-1) (1,2) .. until one leaves every
 // pair alone
-template <int ROWS, class M>
+template <int ROWS, int COLS = 9, class M>
 AKZ_HD void jacobi_sweeps_rows(M& m) {
     for (int sweep = 0; sweep < 60; ++sweep) {
         bool rotated = false;
         for (int p = 0; p < ROWS; ++p)
-            for (int q = p + 1; q < ROWS; ++q) rotated = jacobi_pair(m, p, q) || rotated;
+            for (int q = p + 1; q < ROWS; ++q) rotated = jacobi_pair<COLS>(m, p, q) || rotated;
         if (!rotated) break;
     }
 }

@@ -17,42 +17,7 @@ using PairJob = launch::PairJobHost;
 
 constexpr int RF = kRefitLanes;  // one thread per lane of the summation order
 static_assert(RF == kGroup, "compact_kept");
-constexpr int RG = 6;            // sums that go through the tree together (LDS: RG x 256 doubles)
-
-// The sums of every thread's v[k] in the order of the statement: p[l] = p[l] + p[l + s] for s = 128, 64 through LDS, then
-// s = 32 .. 1 inside the first wave with __shfl_down (lane l receives p[l] + p[l + s]; the lanes that would read past the wave
-// never feed lane 0).  s_out[k] is valid for every thread on return; the caller reads it before its next call.
-template <int K>
-__device__ void block_sums(const double (&v)[K], double* __restrict__ red, double* __restrict__ s_out, unsigned tid) {
-#pragma unroll
-    for (int g = 0; g < K; g += RG) {
-        double a[RG] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < RG; ++k)
-            if (g + k < K) red[k * RF + tid] = v[g + k];
-        __syncthreads();
-        if (tid < 128) {
-#pragma unroll
-            for (int k = 0; k < RG; ++k)
-                if (g + k < K) {
-                    a[k] = red[k * RF + tid] + red[k * RF + tid + 128];
-                    if (tid >= 64) red[k * RF + tid] = a[k];  // (its own slot: nobody else reads it at this level)
-                }
-        }
-        __syncthreads();
-        if (tid < 64) {
-#pragma unroll
-            for (int k = 0; k < RG; ++k)
-                if (g + k < K) {
-                    double s = a[k] + red[k * RF + tid + 64];
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) s = s + __shfl_down(s, o, 64);
-                    if (tid == 0) s_out[g + k] = s;
-                }
-        }
-        __syncthreads();
-    }
-}
+constexpr int RG = kSumGroup;    // sums that go through the tree together (block_sums; LDS: RG x 256 doubles)
 
 // |{ i < n : inlier under h }| for every thread
 template <class R>

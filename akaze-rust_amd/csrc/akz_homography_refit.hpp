@@ -36,12 +36,37 @@
 // matrix has a condition of 1e1 .. 1e3 over its eight non-zero singular values, so the squared 1e6 leaves ten digits in f64:
 // harmless here, unlike the raw pixel coordinates that note speaks of.
 #pragma once
+#include <cstddef>
+#include <cstdint>
+
 #include "akz_homography.hpp"
 
 namespace akz {
 
 constexpr int kRefitLanes = 256;  // lanes of the summation order
 constexpr int kRefitSums3 = 24;   // sums of pass 3
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// The host's form of that order, for every refit (akz_ransac.cpp, akz_resection_api.cpp): the sums of the members' terms -- lane
+// i mod 256, ascending i from +0.0, then the tree.  member: n flags (any indexable); term(i, t) writes element i's K terms.
+template <int K, class Members, class Term>
+inline void lane_tree_sums(uint64_t n, const Members& member, Term term, double (&out)[K]) {
+    static thread_local double p[K][kRefitLanes];
+    for (int k = 0; k < K; ++k)
+        for (int l = 0; l < kRefitLanes; ++l) p[k][l] = 0.0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!member[(size_t)i]) continue;
+        double t[K];
+        term(i, t);
+        for (int k = 0; k < K; ++k) p[k][i % kRefitLanes] = p[k][i % kRefitLanes] + t[k];
+    }
+    for (int k = 0; k < K; ++k) {
+        for (int s = kRefitLanes / 2; s > 0; s >>= 1)
+            for (int l = 0; l < s; ++l) p[k][l] = p[k][l] + p[k][l + s];
+        out[k] = p[k][0];
+    }
+}
+#endif
 
 AKZ_HD void refit_terms1(float x0, float y0, float x1, float y1, double (&t)[4]) {
     t[0] = (double)x0;

@@ -447,7 +447,25 @@ void seeded_round(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, 
                   float epsilon_model, float epsilon_inlier, float* d_ring_mdl, int32_t* d_ring_inl);
 void seeded_update(hipStream_t s, uint32_t n_pairs, uint32_t round, uint32_t max_trials, const uint32_t* d_need, uint32_t need_stride,
                    uint32_t need_index, const float* d_ring_mdl, const int32_t* d_ring_inl, uint32_t* d_done, int32_t* d_best_inl, float* d_best_mdl,
-                   uint32_t* d_trials_run, uint32_t* d_running);
+                   uint32_t* d_trials_run, uint32_t* d_running, uint32_t model_floats = 9 /* or 15: the resection's r | t | sigma */);
+// The resection call (akz_resection.hip; the statement: akz_resection.hpp).  Problem p: its n correspondences at d_planes +
+// {0 .. 4} * stride + off (X | Y | Z | u | v), its camera as the statement's f32 casts, its kept indices at d_kept + off.
+struct ResJobHost {
+    uint64_t off;
+    uint32_t n, pad;
+    float fx, fy, cx, cy;
+};
+static_assert(sizeof(ResJobHost) == 32, "the device reads 32-byte problem records");
+// resection_round: seeded_round for this model -- a ring of 128 models of 15 floats and counts per problem; seeded_update(.., 15)
+// follows it.  resection_finish, after the last round: per problem found = best count > 0, the refit loop from the best model
+// (max_iterations > 0 and found), the kept indices compacted in order, their count, the accepted fits and the akz_resection (zeros
+// where found is 0).
+void resection_round(hipStream_t s, const ResJobHost* d_jobs, uint32_t n_problems, const uint32_t* d_done, uint64_t k1, uint64_t stream_base,
+                     uint32_t round, uint32_t max_trials, const float* d_planes, uint64_t stride, float epsilon_model, float epsilon_inlier,
+                     float* d_ring_mdl, int32_t* d_ring_inl);
+void resection_finish(hipStream_t s, const ResJobHost* d_jobs, uint32_t n_problems, const float* d_planes, uint64_t stride,
+                      const float* d_best_mdl, const int32_t* d_best_inl, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
+                      uint32_t* d_kept, uint32_t* d_n_kept, uint32_t* d_fits, akz_resection* d_poses);
 void unpack_pair(hipStream_t s, const uint8_t* dq, uint32_t nq, uint32_t q_pad, uint8_t* outq, uint32_t* popq, uint32_t* bound, uint32_t threshold,
                  const uint8_t* dt, uint32_t nt, uint32_t t_pad, uint8_t* outt, uint32_t* popt, bool fp4);
 uint32_t match_mfma_tile_rows();

@@ -14,10 +14,10 @@ int seeded_refuse_options(const char* name, const akz_ransac_options* opt);  // 
 }
 using namespace akz;
 
-namespace {
 bool camera_ok(const akz_camera& k) {
     return std::isfinite(k.fx) && std::isfinite(k.fy) && std::isfinite(k.cx) && std::isfinite(k.cy) && k.fx != 0.0 && k.fy != 0.0;
 }
+namespace {
 int refuse(const std::string& what) {
     set_error(what);
     return AKZ_ERR_INVALID_ARG;

@@ -328,24 +328,6 @@ extern "C" int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, u
 
 // ---- the refit of a model on its inliers (akz_homography_refit.hpp, akz_fundamental_refit.hpp) -----------------
 namespace {
-// the sums of the members' terms in the documented order: lane i mod 256, ascending i from +0.0, then the tree
-template <int K, class Term>
-void lane_tree_sums(uint64_t n, const std::vector<uint8_t>& member, Term term, double (&out)[K]) {
-    static thread_local double p[K][kRefitLanes];
-    for (int k = 0; k < K; ++k)
-        for (int l = 0; l < kRefitLanes; ++l) p[k][l] = 0.0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (!member[(size_t)i]) continue;
-        double t[K];
-        term(i, t);
-        for (int k = 0; k < K; ++k) p[k][i % kRefitLanes] = p[k][i % kRefitLanes] + t[k];
-    }
-    for (int k = 0; k < K; ++k) {
-        for (int s = kRefitLanes / 2; s > 0; s >>= 1)
-            for (int l = 0; l < s; ++l) p[k][l] = p[k][l] + p[k][l + s];
-        out[k] = p[k][0];
-    }
-}
 // fit(S) of the statement for the refit model R (HomographyRefit, FundamentalRefit); false: no model
 template <class R>
 bool refit_on_members(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const std::vector<uint8_t>& member,

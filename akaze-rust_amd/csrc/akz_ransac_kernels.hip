@@ -150,21 +150,7 @@ struct HomographyDev : HomographyRansac {
 // by two exchanges inside the quad in the order of sum8_join -- IEEE addition commutes, so all four lanes hold the bits of the
 // host's sum, and with them the same centroids and scales.  The 36 sums of pass 3 thus cost each lane two points, not eight,
 // and stay in registers; lane 0 writes M from them.  The rank-2 step and the denormalisation run on one lane (model).
-// (the exchanges are DPP quad permutes, register to register: __shfl_xor would send the 144 of pass 3 through the LDS crossbar)
-template <int QUAD_PERM>
-__device__ inline double quad_permute(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, QUAD_PERM, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(lo, lo, QUAD_PERM, 0xf, 0xf, false));
-}
-template <int N>
-__device__ inline void quad_join(double (&v)[N]) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        v[k] = v[k] + quad_permute<0x4e>(v[k]);  // lane ^ 2 (quad_perm [2, 3, 0, 1]): lanes 0, 2: p0 + p2; lanes 1, 3: p1 + p3
-        v[k] = v[k] + quad_permute<0xb1>(v[k]);  // lane ^ 1 (quad_perm [1, 0, 3, 2]): (p0 + p2) + (p1 + p3)
-    }
-}
+// (the exchanges: quad_join of akz_ransac_device.hpp)
 struct FundamentalNormalisedDev : FundamentalNormalisedRansac {
     static constexpr int kRows = 9;
     using Side = HomographyDev::Side;
@@ -391,6 +377,7 @@ __global__ void __launch_bounds__(TW * NW) k_seeded_round(const PairJob* __restr
 // pair's best slot; trials_run = the trials done so far, T; the pair is done if best >= need[need_index] (need: the host's table
 // of seeded_need for the rounds of one window, need_stride entries per pair; null: no stopping rule) or T == max_trials; else it
 // counts in running[round].
+template <int MF>  // floats of a model: 9, the resection's 15
 __global__ void __launch_bounds__(TW) k_seeded_update(unsigned round, unsigned max_trials, const unsigned* __restrict__ need,
                                                       unsigned need_stride, unsigned need_index,
                                                       const float* __restrict__ ring_mdl, const int* __restrict__ ring_inl,
@@ -419,7 +406,7 @@ __global__ void __launch_bounds__(TW) k_seeded_update(unsigned round, unsigned m
         }
     }
     const int before = best_inl[p];
-    if (best > before && lane < 9) best_mdl[(size_t)p * 9 + lane] = ring_mdl[((size_t)p * AKZ_RANSAC_ROUND + bidx) * 9 + lane];
+    if (best > before && lane < MF) best_mdl[(size_t)p * MF + lane] = ring_mdl[((size_t)p * AKZ_RANSAC_ROUND + bidx) * MF + lane];
     if (lane == 0) {
         const unsigned T = t0 + cnt, now = (unsigned)max(best, before);
         if (best > before) best_inl[p] = best;
@@ -518,9 +505,10 @@ void seeded_round(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, 
 }
 void seeded_update(hipStream_t s, uint32_t n_pairs, uint32_t round, uint32_t max_trials, const uint32_t* d_need, uint32_t need_stride,
                    uint32_t need_index, const float* d_ring_mdl, const int32_t* d_ring_inl, uint32_t* d_done, int32_t* d_best_inl, float* d_best_mdl,
-                   uint32_t* d_trials_run, uint32_t* d_running) {
+                   uint32_t* d_trials_run, uint32_t* d_running, uint32_t model_floats) {
     if (n_pairs == 0) return;
-    hipLaunchKernelGGL(k_seeded_update, dim3(n_pairs), dim3(TW), 0, s, round, max_trials, d_need, need_stride, need_index, d_ring_mdl, d_ring_inl, d_done,
+    auto k = model_floats == 9 ? k_seeded_update<9> : k_seeded_update<15>;
+    hipLaunchKernelGGL(k, dim3(n_pairs), dim3(TW), 0, s, round, max_trials, d_need, need_stride, need_index, d_ring_mdl, d_ring_inl, d_done,
                        d_best_inl, d_best_mdl, d_trials_run, d_running);
 }
 void pairs_pick_filter(hipStream_t s, RansacModel model, const PairJobHost* d_pairs, uint32_t n_pairs, const void* d_raw,

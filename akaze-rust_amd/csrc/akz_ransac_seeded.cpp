@@ -20,20 +20,23 @@
 namespace akz {
 
 // the refusals that the host statement and the GPU call share: the options alone (see the header)
-int seeded_refuse_options(const char* name, const akz_ransac_options* opt) {
+// resection: the calls of akz_resection_api.cpp, whose one kind is AKZ_RANSAC_RESECTION; every other call keeps refusing it
+int seeded_refuse_options_of(const char* name, const akz_ransac_options* opt, bool resection) {
     auto refuse = [name](const char* msg) {
         set_error(std::string(name) + msg);
         return AKZ_ERR_INVALID_ARG;
     };
     if (!opt) return refuse("null options");
     if (opt->struct_size != sizeof(akz_ransac_options)) return refuse("options.struct_size is not sizeof(akz_ransac_options)");
-    if (opt->model_kind != AKZ_GUIDED_HOMOGRAPHY && opt->model_kind != AKZ_GUIDED_FUNDAMENTAL &&
-        opt->model_kind != AKZ_RANSAC_FUNDAMENTAL_NORMALISED)
-        return refuse("unknown options.model_kind");
+    if (resection ? opt->model_kind != AKZ_RANSAC_RESECTION
+                  : opt->model_kind != AKZ_GUIDED_HOMOGRAPHY && opt->model_kind != AKZ_GUIDED_FUNDAMENTAL &&
+                        opt->model_kind != AKZ_RANSAC_FUNDAMENTAL_NORMALISED)
+        return refuse(resection ? "options.model_kind must be AKZ_RANSAC_RESECTION" : "unknown options.model_kind");
     if (opt->max_trials > kSeededMaxTrials) return refuse("options.max_trials must be <= 1 << 24");
     if (!(opt->confidence >= 0.0 && opt->confidence < 1.0)) return refuse("options.confidence must be 0 (off) or 0 < c < 1");
     return AKZ_OK;
 }
+int seeded_refuse_options(const char* name, const akz_ransac_options* opt) { return seeded_refuse_options_of(name, opt, false); }
 
 namespace {
 
@@ -54,28 +57,20 @@ int seeded_host(Refine refine, const akz_keypoint* keypoints_0, uint64_t n0, con
     } else {
         const MatchPoints pt(keypoints_0, keypoints_1, matches, n_matches);
         const float *x0 = pt.x0, *y0 = pt.y0, *x1 = pt.x1, *y1 = pt.y1;
-        const uint64_t ks = seeded_stream_key(seeded_seed_key(opt.seed[0], opt.seed[1]), stream);
-        while (trials_run < opt.max_trials) {
-            const uint64_t end = std::min<uint64_t>(opt.max_trials, trials_run + AKZ_RANSAC_ROUND);
-            for (uint64_t trial = trials_run; trial < end; ++trial) {
-                uint64_t smp[K];
-                seeded_sample<K>(ks, trial, n_matches, smp);
+        float m[9];  // the model of the trial at hand
+        seeded_rounds<K>(
+            n_matches, opt.seed[0], opt.seed[1], stream, opt.max_trials, opt.confidence,
+            [&](const uint64_t(&smp)[K]) -> int64_t {
                 float sx0[K], sy0[K], sx1[K], sy1[K];
                 for (int i = 0; i < K; ++i) {
                     sx0[i] = x0[smp[i]]; sy0[i] = y0[smp[i]]; sx1[i] = x1[smp[i]]; sy1[i] = y1[smp[i]];
                 }
-                float m[9];
-                if (!M::from_sample(sx0, sy0, sx1, sy1, epsilon_model, m)) continue;
+                if (!M::from_sample(sx0, sy0, sx1, sy1, epsilon_model, m)) return -1;
                 int64_t inl = 0;
                 for (uint64_t i = 0; i < n_matches; ++i) inl += M::inlier(m, x0[i], y0[i], x1[i], y1[i], opt.epsilon_inliers) ? 1 : 0;
-                if (inl > best) {  // (strict: the first trial that reached the count stays the winner)
-                    best = inl;
-                    std::memcpy(best_model, m, sizeof(m));
-                }
-            }
-            trials_run = end;
-            if (opt.confidence > 0.0 && (uint64_t)best >= seeded_need(n_matches, K, trials_run, opt.confidence)) break;
-        }
+                return inl;
+            },
+            [&] { std::memcpy(best_model, m, sizeof(m)); }, best, trials_run);
         for (uint64_t i = 0; i < n_matches; ++i)
             if ((M::kKeepAllWithoutWinner && best == 0) || M::inlier(best_model, x0[i], y0[i], x1[i], y1[i], opt.epsilon_inliers))
                 out[kept++] = matches[i];
@@ -117,14 +112,18 @@ void akz_ransac_options_default(akz_ransac_options* opt) {
 }
 
 int akz_draw_sample_seeded(uint64_t seed0, uint64_t seed1, uint64_t stream, uint64_t trial, uint64_t n_matches, int k, uint64_t* out) {
-    if ((k != 4 && k != 8) || n_matches < (uint64_t)k || !out) {
-        set_error("draw_sample_seeded: bad arguments (k must be 4 or 8, n_matches >= k, out not null)");
+    if ((k != 4 && k != 6 && k != 8) || n_matches < (uint64_t)k || !out) {
+        set_error("draw_sample_seeded: bad arguments (k must be 4, 6 or 8, n_matches >= k, out not null)");
         return AKZ_ERR_INVALID_ARG;
     }
     const uint64_t ks = seeded_stream_key(seeded_seed_key(seed0, seed1), stream);
     if (k == 8) {
         uint64_t s[8];
         seeded_sample<8>(ks, trial, n_matches, s);
+        std::memcpy(out, s, sizeof(s));
+    } else if (k == 6) {
+        uint64_t s[6];
+        seeded_sample<6>(ks, trial, n_matches, s);
         std::memcpy(out, s, sizeof(s));
     } else {
         uint64_t s[4];
@@ -135,8 +134,8 @@ int akz_draw_sample_seeded(uint64_t seed0, uint64_t seed1, uint64_t stream, uint
 }
 
 int akz_ransac_required_inliers(uint64_t n_matches, int k, uint64_t trials, double confidence, uint64_t* need) {
-    if ((k != 4 && k != 8) || n_matches == 0 || trials == 0 || !(confidence > 0.0 && confidence < 1.0) || !need) {
-        set_error("ransac_required_inliers: bad arguments (k must be 4 or 8, n_matches and trials >= 1, 0 < confidence < 1, need not null)");
+    if ((k != 4 && k != 6 && k != 8) || n_matches == 0 || trials == 0 || !(confidence > 0.0 && confidence < 1.0) || !need) {
+        set_error("ransac_required_inliers: bad arguments (k must be 4, 6 or 8, n_matches and trials >= 1, 0 < confidence < 1, need not null)");
         return AKZ_ERR_INVALID_ARG;
     }
     *need = seeded_need(n_matches, k, trials, confidence);

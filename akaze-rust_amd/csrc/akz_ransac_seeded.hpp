@@ -95,6 +95,31 @@ inline uint64_t seeded_need(uint64_t n, int K, uint64_t T, double confidence) {
     }
     return hi;
 }
+// The rounds of the statement over n >= K elements, for every model of the family (seeded_host of akz_ransac_seeded.cpp, the
+// resection of akz_resection_api.cpp): trial(sample) evaluates the model of a sample and returns its inlier count, below 0 where
+// the sample has no model; won() is called when that trial has become the winner -- strictly more inliers than every trial
+// before it, from 0.  Rounds of AKZ_RANSAC_ROUND trials; after each round the stopping rule, where confidence > 0.
+template <int K, class Trial, class Won>
+inline void seeded_rounds(uint64_t n, uint64_t seed0, uint64_t seed1, uint64_t stream, uint64_t max_trials, double confidence, Trial trial,
+                          Won won, int64_t& best, uint64_t& trials_run) {
+    const uint64_t ks = seeded_stream_key(seeded_seed_key(seed0, seed1), stream);
+    best = 0;
+    trials_run = 0;
+    while (trials_run < max_trials) {
+        const uint64_t end = max_trials - trials_run < AKZ_RANSAC_ROUND ? max_trials : trials_run + AKZ_RANSAC_ROUND;
+        for (uint64_t t = trials_run; t < end; ++t) {
+            uint64_t smp[K];
+            seeded_sample<K>(ks, t, n, smp);
+            const int64_t inl = trial(smp);
+            if (inl > best) {  // (strict: the first trial that reached the count stays the winner)
+                best = inl;
+                won();
+            }
+        }
+        trials_run = end;
+        if (confidence > 0.0 && (uint64_t)best >= seeded_need(n, K, trials_run, confidence)) break;
+    }
+}
 #endif
 
 }  // namespace akz

@@ -266,6 +266,70 @@ class Pose(C.Structure):
         return np.frombuffer(bytes(self), np.uint32).copy()
 
 
+class ResectionProblem(C.Structure):
+    """akz_resection_problem: n 2D-3D correspondences (points 3 n floats, pixels 2 n floats) and their camera."""
+    _fields_ = [("points", C.POINTER(C.c_float)), ("pixels", C.POINTER(C.c_float)), ("n", C.c_uint64), ("camera", Camera)]
+
+
+class Resection(C.Structure):
+    """akz_resection: the absolute pose of a camera against known points (x_cam = R X + t).  found = 0: no pose -- every field
+    is zero."""
+    _fields_ = [("r", C.c_float * 9), ("t", C.c_float * 3), ("sigma", C.c_float * 3), ("found", C.c_int32)]
+
+    @property
+    def R(self):
+        return np.ctypeslib.as_array(self.r).reshape(3, 3)
+
+    @property
+    def T(self):
+        return np.ctypeslib.as_array(self.t)
+
+    @property
+    def singular_values(self):
+        return np.ctypeslib.as_array(self.sigma)
+
+    def words(self):
+        """the record as 16 uint32 words (what the GPU call promises bit for bit)"""
+        return np.frombuffer(bytes(self), np.uint32).copy()
+
+
+class _ResectionArgs:
+    """The arguments of the resection calls, stated once: problems -- a list of (points [n, 3], pixels [n, 2], camera) -- as
+    float32 arrays kept alive here and an akz_resection_problem array; the outputs `tail` = kept (uint32, room for every
+    correspondence, problem p's at the sum of the sizes before it), n_kept, poses, iterations, trials_run (one per problem); and
+    results(): per problem (kept indices, Resection, accepted fits, trials run)."""
+
+    def __init__(self, problems):
+        self.arrays = [(np.ascontiguousarray(np.asarray(pts, np.float32).reshape(-1, 3)),
+                        np.ascontiguousarray(np.asarray(pix, np.float32).reshape(-1, 2)), Camera.of(cam)) for pts, pix, cam in problems]
+        for pts, pix, _ in self.arrays:
+            if len(pts) != len(pix):
+                raise ValueError(f"{len(pts)} points but {len(pix)} pixels")
+        n = len(self.arrays)
+        fp = C.POINTER(C.c_float)
+        self.problems = (ResectionProblem * max(1, n))(*[ResectionProblem(pts.ctypes.data_as(fp), pix.ctypes.data_as(fp), len(pts), cam)
+                                                        for pts, pix, cam in self.arrays])
+        self.sizes = [len(pts) for pts, _, _ in self.arrays]
+        self.kept = np.zeros(max(1, sum(self.sizes)), np.uint32)
+        self.n_kept = np.zeros(max(1, n), np.uint64)
+        self.poses = (Resection * max(1, n))()
+        self.its = np.zeros(max(1, n), np.uint32)
+        self.trials = np.zeros(max(1, n), np.uint64)
+
+    def tail(self):
+        """the output pointers in header order: kept, n_kept, poses, iterations, trials_run"""
+        return (C.cast(self.kept.ctypes.data, C.c_void_p), self.n_kept.ctypes.data_as(C.POINTER(C.c_uint64)), C.cast(self.poses, C.c_void_p),
+                self.its.ctypes.data_as(C.POINTER(C.c_uint32)), self.trials.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def results(self):
+        res, off = [], 0
+        for p, n in enumerate(self.sizes):
+            res.append((self.kept[off:off + int(self.n_kept[p])].copy(), Resection.from_buffer_copy(self.poses[p]), int(self.its[p]),
+                        int(self.trials[p])))
+            off += n
+        return res
+
+
 def _match_name(model, refined, guided, pairs):
     """akz_match_features{,_homography,_fundamental}{,_refined}{,_guided}{,_pairs}; model: "", "_homography" or "_fundamental"."""
     return "akz_match_features" + model + "_refined" * bool(refined) + "_guided" * bool(guided) + "_pairs" * bool(pairs)
@@ -420,6 +484,10 @@ def lib():
         "akz_recover_pose_host": ([vp, u64, vp, u64, vp, u64, fp, C.POINTER(Camera), C.POINTER(Camera), vp, pu64, C.POINTER(Pose), fp], i32),
         "akz_match_features_seeded_pose_pairs": ([vp, vp, u64, vp, vp, u64, u64, C.POINTER(RansacOptions), i32, vp, pu64, fp,
                                                   C.POINTER(i32), C.POINTER(C.c_uint32), pu64, vp, fp], i32),
+        "akz_estimate_resection": ([fp, fp, C.POINTER(Camera), C.POINTER(Resection), C.POINTER(i32)], i32),
+        "akz_refine_resection": ([C.POINTER(ResectionProblem), C.POINTER(Resection), C.c_float, u32, vp, pu64, C.POINTER(Resection), pu32], i32),
+        "akz_resection_seeded_host": ([C.POINTER(ResectionProblem), C.POINTER(RansacOptions), u64, vp, pu64, vp, pu32, pu64], i32),
+        "akz_resection_seeded_problems": ([vp, C.POINTER(ResectionProblem), u64, C.POINTER(RansacOptions), vp, pu64, vp, pu32, pu64], i32),
         "akz_bank_create_from_results": ([vp, C.POINTER(vp), u64, C.POINTER(vp)], i32),
         "akz_bank_create_from_sets": ([vp, vp, u64, u64, C.POINTER(vp)], i32),
         "akz_bank_info": ([vp, pu64, pu64, pu64], i32),
@@ -445,6 +513,7 @@ def lib():
         "akz_keypoint_budget_host": ([vp, u64, C.POINTER(KeypointBudget), vp, pu64, vp], i32),
         "akz_keypoint_budget_sets": ([vp, vp, u64, C.POINTER(KeypointBudget), vp, vp, vp], i32),
         "akz_debug_keypoint_budget_split": ([vp, i32, pf64], i32),
+        "akz_debug_resection_split": ([vp, i32, pf64], i32),
         "akz_debug_keypoint_budget_tiles": ([pu32, pu32], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_debug_match_tile_rows": ([C.POINTER(C.c_uint32)], i32),
@@ -1362,6 +1431,15 @@ class Context:
             at += a.rows[p]
         return res
 
+    def resection_seeded(self, problems, options):
+        """Absolute pose by the seeded 6-point resection RANSAC over many problems in one call (akz_resection_seeded_problems):
+        problems is a list of (points [n, 3], pixels [n, 2], camera), options a RansacOptions with model_kind RANSAC_RESECTION and
+        epsilon_inliers in pixels.  Returns one (kept indices ascending, Resection, accepted fits, trials run) per problem, each
+        equal to resection_seeded_host(problem, options, stream=options.stream_base + p) bit for bit."""
+        a = _ResectionArgs(problems)
+        _check(lib().akz_resection_seeded_problems(self._h, a.problems, len(a.sizes), C.byref(options), *a.tail()))
+        return a.results()
+
     def descriptor_match_guided_pairs(self, features, pairs, models, kind, radius, distance_threshold=10000, lowes_ratio=0.86):
         """Guided matching over many pairs in one call (akz_descriptor_match_guided_pairs): features and pairs as for
         match_features_pairs, models one 3x3 (or 9) float32 model per pair, kind GUIDED_HOMOGRAPHY or GUIDED_FUNDAMENTAL.
@@ -2258,7 +2336,7 @@ def refine_fundamental_normalised(keypoints_0, keypoints_1, matches, f, epsilon_
 
 
 def draw_sample_seeded(seed0, seed1, stream, trial, n_matches, k):
-    """The sample of trial `trial` of `stream` over n_matches matches (akz_draw_sample_seeded): k (4 or 8) ascending indices."""
+    """The sample of trial `trial` of `stream` over n_matches matches (akz_draw_sample_seeded): k (4, 6 or 8) ascending indices."""
     out = np.zeros(8, np.uint64)
     _check(lib().akz_draw_sample_seeded(seed0, seed1, stream, trial, n_matches, k, out.ctypes.data_as(C.POINTER(C.c_uint64))))
     return out[:k].copy()
@@ -2327,6 +2405,64 @@ def match_features_seeded_pose(keypoints_0, descriptors_0, camera_0, keypoints_1
     return (ctx or default_context()).match_features_seeded_pose_pairs([(keypoints_0, descriptors_0), (keypoints_1, descriptors_1)],
                                                                        [camera_0, camera_1], [(0, 1)], options, cross_check=cross_check,
                                                                        points=points)[0]
+
+
+# ---- absolute pose: seeded 6-point resection RANSAC (an addition; include/akaze_hip.h) ----------------------------
+# AKZ_RANSAC_RESECTION: the model_kind of the resection calls and of no other -- x_cam = R X + t from 2D-3D correspondences,
+# epsilon_inliers a reprojection error in pixels
+RANSAC_RESECTION = 4
+
+
+def estimate_resection(points6, pixels6, camera):
+    """The resection model of exactly 6 correspondences, given in ascending order of their position in the problem they were
+    sampled from (akz_estimate_resection) -> Resection; found = 0 (all zeros) where the sample has no model -- coplanar points
+    among them: the DLT cannot do a plane."""
+    pts = np.ascontiguousarray(np.asarray(points6, np.float32).reshape(-1, 3))
+    pix = np.ascontiguousarray(np.asarray(pixels6, np.float32).reshape(-1, 2))
+    if len(pts) != 6 or len(pix) != 6:
+        raise ValueError("exactly 6 correspondences")
+    fp, cam, pose = C.POINTER(C.c_float), Camera.of(camera), Resection()
+    _check(lib().akz_estimate_resection(pts.ctypes.data_as(fp), pix.ctypes.data_as(fp), C.byref(cam), C.byref(pose), None))
+    return pose
+
+
+def refine_resection(points, pixels, camera, pose, epsilon, max_iterations):
+    """The refit of a resection on its inliers, on the host (akz_refine_resection): the loop of refine_homography from pose's R
+    and t with epsilon in pixels -> (kept indices ascending, Resection, accepted fits)."""
+    a = _ResectionArgs([(points, pixels, camera)])
+    kept, n_kept, out, its, _ = a.tail()
+    _check(lib().akz_refine_resection(a.problems, C.byref(pose), epsilon, max_iterations, kept, n_kept, C.cast(out, C.POINTER(Resection)), its))
+    return a.results()[0][:3]
+
+
+def resection_seeded_host(points, pixels, camera, options, stream=0):
+    """The seeded resection RANSAC of one problem on the host (akz_resection_seeded_host; no GPU call) -> (kept indices
+    ascending, Resection, accepted fits, trials run)."""
+    a = _ResectionArgs([(points, pixels, camera)])
+    _check(lib().akz_resection_seeded_host(a.problems, C.byref(options), stream, *a.tail()))
+    return a.results()[0]
+
+
+def correspondences_2d3d(matches_ab, points_ab, matches_ac, keypoints_c):
+    """The join that makes the pose call's points usable for a third image: matches_ab and points_ab are the kept matches of a
+    pair (A, B) and their structure (match_features_seeded_pose_pairs(..., points=True)), matches_ac a match list of (A, C) and
+    keypoints_c C's keypoints.  For every record of matches_ac whose index_0 occurs in matches_ab (its FIRST occurrence there),
+    that record's point and C's pixel -> (points [k, 3] float32, pixels [k, 2] float32, the k record indices into matches_ab,
+    the k record indices into matches_ac), in matches_ac's order."""
+    first = {}
+    for i, a in enumerate(np.asarray(matches_ab["index_0"], np.uint64).tolist()):
+        first.setdefault(a, i)
+    ab, ac = [], []
+    for j, a in enumerate(np.asarray(matches_ac["index_0"], np.uint64).tolist()):
+        if a in first:
+            ab.append(first[a])
+            ac.append(j)
+    ab, ac = np.asarray(ab, np.int64), np.asarray(ac, np.int64)
+    kc = np.asarray(keypoints_c)
+    at = np.asarray(matches_ac["index_1"], np.int64)[ac]
+    pix = np.stack([kc["x"][at], kc["y"][at]], axis=1).astype(np.float32) if len(ac) else np.zeros((0, 2), np.float32)
+    pts = np.asarray(points_ab, np.float32).reshape(-1, 3)[ab]
+    return np.ascontiguousarray(pts), np.ascontiguousarray(pix), ab, ac
 
 
 def _descriptor_pair(fn, first, d0, d1, distance_threshold, lowes_ratio):

@@ -910,7 +910,8 @@ int akz_refine_fundamental_normalised(const akz_keypoint* keypoints_0, uint64_t 
                                       uint32_t* iterations /* may be NULL */);
 typedef struct akz_ransac_options {
     uint32_t struct_size;       /* sizeof(akz_ransac_options) */
-    int32_t model_kind;         /* AKZ_GUIDED_HOMOGRAPHY, AKZ_GUIDED_FUNDAMENTAL or AKZ_RANSAC_FUNDAMENTAL_NORMALISED */
+    int32_t model_kind;         /* AKZ_GUIDED_HOMOGRAPHY, AKZ_GUIDED_FUNDAMENTAL or AKZ_RANSAC_FUNDAMENTAL_NORMALISED; the
+                                   resection calls below: AKZ_RANSAC_RESECTION, and nothing else */
     double lowes_ratio;         /* of the descriptor scan (GPU call only) */
     uint64_t max_trials;        /* <= 1 << 24; the GPU call enqueues 2 launches per round of 128 and, per window of 8 rounds
                                    still running, computes 8 need() values per pair on the calling thread */
@@ -927,10 +928,11 @@ typedef struct akz_ransac_options {
    radius 3 px and ratio 0.86 are set for a caller who switches it on); epsilon_inliers 0.02, the value tools/fundamental_refit.py
    measures with: |p1^T F p0| at unit norm, 1 .. 5 px on 1080p two-view scenes -- a homography wants pixels, set it */
 void akz_ransac_options_default(akz_ransac_options* options);
-/* the sample alone: out receives the k (4 or 8) ascending indices of trial `trial` of `stream` over n_matches >= k matches */
+/* the sample alone: out receives the k (4, 8, or the resection's 6) ascending indices of trial `trial` of `stream` over
+   n_matches >= k matches */
 int akz_draw_sample_seeded(uint64_t seed0, uint64_t seed1, uint64_t stream, uint64_t trial, uint64_t n_matches, int k,
                            uint64_t* out /* k */);
-/* need(n_matches, k, trials, confidence) of the statement; k 4 or 8, n_matches and trials >= 1, 0 < confidence < 1 */
+/* need(n_matches, k, trials, confidence) of the statement; k 4, 6 or 8, n_matches and trials >= 1, 0 < confidence < 1 */
 int akz_ransac_required_inliers(uint64_t n_matches, int k, uint64_t trials, double confidence, uint64_t* need);
 /* The host statement: rounds, winner, filter and refit over one raw match list with stream `stream`.  No GPU call and no
    descriptor work: lowes_ratio and the guided fields are ignored.  out must hold n_matches entries; model (9), found, iterations
@@ -1050,6 +1052,102 @@ int akz_match_features_seeded_pose_pairs(akz_ctx* ctx, const akz_feature_set* se
                                          uint64_t* n_out /* n_pairs */, float* model /* 9 x n_pairs */, int* found /* n_pairs */,
                                          uint32_t* iterations /* n_pairs */, uint64_t* trials_run /* n_pairs */,
                                          akz_pose* poses /* n_pairs */, float* points /* 3 per slot of out, may be NULL */);
+
+/* ---- absolute pose: seeded 6-point resection RANSAC over many problems (additions) -----------------------------
+   The call that places a camera against points that exist already: from 2D-3D correspondences -- for instance the `points` of
+   the pose call above joined with the matches of a third image -- R and t with x_cam = R X + t, by the seeded RANSAC of the
+   family above with a fourth model.  The statement (csrc/akz_resection.hpp, ONE source for host and device; f64 unless stated,
+   no contraction):
+     problem: n correspondences, each a point (X, Y, Z) in f32 and a pixel (u, v) in f32, and one akz_camera.  The camera's
+       fields are cast to f32 ONCE per problem; the fit widens those casts to f64 again and the inlier rule uses them as they
+       are.
+     sample: K = 6 distinct indices in ascending order, the seeded statement's sample with K = 6 (draw i of trial t is
+       v(t, i) = mix64(ks + G (8 t + i + 1)), as for 4 and 8).
+     fit(S), the trial model with |S| = 6 and the refit's model with S the inliers:
+       1. a = (u - cx) / fx, b = (v - cy) / fy.
+       2. centroids of (a, b) and of (X, Y, Z); the mean distance of (a, b) from its centroid, sqrt(da da + db db), is scaled
+          to sqrt 2, that of the points, sqrt((dX dX + dY dY) + dZ dZ), to sqrt 3; a mean distance of 0 on either side: no model.
+       3. with Xh = (x, y, z, 1) normalised and q = {xx, xy, xz, x, yy, yz, y, zz, z, 1}: the 40 sums of q[k], a q[k], b q[k],
+          (a a + b b) q[k] -- the blocks of M = A^T A = [[P, 0, -Qa], [0, P, -Qb], [-Qa, -Qb, W]] (12 x 12) for the DLT rows
+          [Xh, 0, -a Xh], [0, Xh, -b Xh].  Every sum over S is formed in the order of akz_refine_homography's tree (element i
+          in lane i mod 256, ascending from +0.0, then s = 128 .. 1); six members: ((e0 + e4) + e2) + ((e1 + e5) + e3) with
+          every e_j entering as 0.0 + e_j and every absent element as + 0.0.
+       4. the one-sided Jacobi sweeps on the 12 rows of M; the row of the smallest norm (the first among equals), normalised,
+          is P~ (3 x 4, row-major); every other row norm must exceed AKZ_FUNDAMENTAL_REFIT_EPSILON^2 |S| / 6, else no model.
+       5. P^ = T2^-1 P~ T3 (both normalisations undone) = s [R | t]; its sign flips if det of its left 3 x 3 block M3 is
+          negative.  The Hestenes rotations of the relative pose's decomposition on the rows of M3 give sigma1 >= sigma2 >=
+          sigma3 and v_i; u_i = M3 v_i / sigma_i; R = U V^T with R[r][c] = (u1[r] v1[c] + u2[r] v2[c]) + u3[r] v3[c], the
+          rotation nearest M3; t = P^[:, 3] / (((sigma1 + sigma2) + sigma3) / 3); both rounded to f32.  No model where sigma1
+          is zero or not finite or where !(sigma3 > AKZ_FUNDAMENTAL_REFIT_EPSILON sigma1).
+       THE DLT CANNOT DO A PLANE: on coplanar points the null space of A has more than one dimension, and the sigma3 rule is
+       what answers "no model" there.  A planar target needs another solver.
+     inlier rule, f32 in this order, no division, with fx, fy, cx, cy the f32 casts:
+       c_r = ((R[r][0] X + R[r][1] Y) + R[r][2] Z) + t[r];  ex = fx c_0 - (u - cx) c_2;  ey = fy c_1 - (v - cy) c_2;
+       inlier iff c_2 > 0 and ex ex + ey ey < (eps eps)(c_2 c_2).  eps = epsilon_inliers is in PIXELS; the test is strict and
+       a NaN passes nothing.
+     rounds, winner, stop: the seeded statement's -- rounds of 128, the first maximum wins, a problem with confidence > 0
+       stops after the round in which best >= need(n, 6, T, confidence).
+     refit (refine_iterations > 0, where there is a winner): the loop of akz_refine_homography unchanged -- S, fit, reclassify,
+       reject if smaller, stop when not grown -- over the problem's correspondences.
+     result per problem: R, t, sigma_i / sigma1 and found; the indices of the kept correspondences, ascending; the fits
+       accepted; trials_run.  found = 0 -- n < 6 (trials_run 0), no trial with a model, or a best count of 0 -- : the kept
+       list is EMPTY and the pose is all zeros.
+   Advice on epsilon_inliers: the 6-point DLT is a linear fit of twelve numbers to six points and its winner is far noisier than
+   its data.  With pixel noise of standard deviation s, set epsilon_inliers to 4 s at the least, better 5 to 6 s, and
+   refine_iterations to 2 or more: measured on 24 scenes of 800 true correspondences and 20 % outliers at s = 0.7 px, 3 px
+   brings the refit to the whole true set at the median but to 48 % on the worst scene, 4 px to the whole set on all 24; at 2 px
+   some winners are too poor for the refit to grow (README, the resection row; profiles/r32_resection.json).
+   akz_ransac_options_default's 0.02 is the fundamental matrix's unit and is WRONG here: set it. */
+#define AKZ_RANSAC_RESECTION 4 /* the resection calls' model_kind; every other call refuses it */
+typedef struct akz_resection_problem {
+    const float* points; /* 3 n: X, Y, Z per correspondence */
+    const float* pixels; /* 2 n: u, v per correspondence */
+    uint64_t n;          /* < 1 << 32 */
+    akz_camera camera;
+} akz_resection_problem;
+typedef struct akz_resection {
+    float r[9];     /* row-major */
+    float t[3];
+    float sigma[3]; /* sigma_i / sigma1 of the left block of P^: how far it was from a scaled rotation */
+    int32_t found;  /* 0: everything above is zero */
+} akz_resection;
+/* fit(S) of exactly six correspondences, given in ascending order of their position in the problem they were sampled from.
+   *found (may be NULL) and pose->found: 0 where there is no model, and the pose is zeros.  Refusals (AKZ_ERR_INVALID_ARG,
+   nothing written): a NULL array, camera or pose; a camera that akz_recover_pose_host refuses. */
+int akz_estimate_resection(const float* points6 /* 18 */, const float* pixels6 /* 12 */, const akz_camera* camera,
+                           akz_resection* pose, int* found);
+/* The refit alone, on the host: the loop above from pose_in's R and t (its sigma and found are not read) with epsilon in
+   pixels.  kept (room for problem->n) receives the indices of the final set, ascending, *n_kept their number; pose_out (may
+   be NULL): the last accepted fit with found = 1, or *pose_in unchanged where none was accepted; *iterations (may be NULL):
+   the fits accepted.  Refusals (nothing written): a NULL problem, pose_in or n_kept; NULL points, pixels or kept where
+   n > 0; n >= 1 << 32; the camera, as above; an epsilon that is not finite and > 0. */
+int akz_refine_resection(const akz_resection_problem* problem, const akz_resection* pose_in, float epsilon,
+                         uint32_t max_iterations, uint32_t* kept, uint64_t* n_kept, akz_resection* pose_out,
+                         uint32_t* iterations);
+/* The host statement: rounds, winner, filter and refit of one problem with stream `stream`.  No GPU call, no context.
+   options: akz_ransac_options as it is, with model_kind = AKZ_RANSAC_RESECTION; lowes_ratio, guided_radius and
+   guided_lowes_ratio are ignored.  kept: room for problem->n indices; iterations and trials_run may be NULL.
+   Refusals (AKZ_ERR_INVALID_ARG, nothing written): the options' refusals of akz_remove_outliers_seeded with "model_kind is not
+   AKZ_RANSAC_RESECTION" in place of the unknown kind; guided != 0; with refine_iterations > 0 an epsilon_inliers that
+   akz_refine_resection refuses; a NULL problem, n_kept or pose; NULL points, pixels or kept where n > 0; n >= 1 << 32; a
+   camera that akz_recover_pose_host refuses. */
+int akz_resection_seeded_host(const akz_resection_problem* problem, const akz_ransac_options* options, uint64_t stream,
+                              uint32_t* kept, uint64_t* n_kept, akz_resection* pose, uint32_t* iterations,
+                              uint64_t* trials_run);
+/* The same over many problems, all on the GPU: one upload (the problems packed into five f32 planes X | Y | Z | u | v behind one
+   table of offsets and f32 cameras), per round of 128 trials two launches for all problems that still run, one launch for the
+   filter and the refit, ONE read-back and one synchronisation.  Problem p uses stream options->stream_base + p and its kept
+   indices (relative to the problem) start at kept[sum of n_q, q < p]; it equals akz_resection_seeded_host(problems + p,
+   options, stream_base + p) bit for bit -- the indices, every word of the pose, iterations and trials_run -- so the batch
+   equals the loop of one-problem calls.  kept beyond a problem's n_kept is not written.  n_kept, poses: one per problem;
+   iterations, trials_run: one per problem, each may be NULL.  Scratch comes from the context and is kept for the next call.
+   Refusals (AKZ_ERR_INVALID_ARG, before any GPU work, nothing written): a NULL ctx; everything akz_resection_seeded_host
+   refuses, of any problem; n_problems >= 1 << 28; correspondences of all problems together >= 1 << 32.
+   n_problems = 0: AKZ_OK, nothing done. */
+int akz_resection_seeded_problems(akz_ctx* ctx, const akz_resection_problem* problems, uint64_t n_problems,
+                                  const akz_ransac_options* options, uint32_t* kept, uint64_t* n_kept /* n_problems */,
+                                  akz_resection* poses /* n_problems */, uint32_t* iterations /* n_problems */,
+                                  uint64_t* trials_run /* n_problems */);
 
 /* ---- feature banks: match pairs over feature sets that stay on the device (additions, not in the reference) -----
    An akz_bank is a list of feature sets resident on the device in the layout the pairs calls scan: every set's descriptors as

@@ -237,6 +237,10 @@ int akz_debug_ransac_samples_k(uint64_t s0, uint64_t s1, uint64_t n_matches, uin
 int akz_debug_match_pairs_split(akz_ctx* ctx, int enable, double* ms);
 /* The same for akz_keypoint_budget_sets: ms (optional, 3 doubles) receives the last timed call's upload, kernels and download. */
 int akz_debug_keypoint_budget_split(akz_ctx* ctx, int enable, double* ms);
+/* The same for akz_resection_seeded_problems: ms (optional, 4 doubles) receives the last timed call's upload (with the clearing
+   memsets), rounds (first round's launch to the last update's end, the window look-ups of a call with confidence > 0 included),
+   filter + refit and read-back. */
+int akz_debug_resection_split(akz_ctx* ctx, int enable, double* ms);
 /* Test hook: the queries per workgroup and the keypoints per LDS stage of k_budget_walk, so that tests can place their set sizes
    one below, at and one above them.  No GPU call, no context. */
 int akz_debug_keypoint_budget_tiles(uint32_t* query_tile, uint32_t* train_tile);
