@@ -847,6 +847,34 @@ struct SeededPose {
 };
 AKZ_LOCAL int match_seeded_pairs_impl(const PairsCall& q, bool cross, const akz_ransac_options* options, float* model, int* found,
                                       uint32_t* iterations, uint64_t* trials_run, const SeededPose* pose = nullptr);
+// akz_match_seeded_api.cpp: the rounds of every seeded call (the pairs calls, akz_resection_seeded_problems) over n entries -- pairs or
+// problems -- with models of model_floats floats.  SeededState is what the rounds keep: on the device every entry's best model and
+// count, its ring of a round's models and counts and the running counts per round (bytes() at place()'s address; clear() enqueues the
+// two memsets), and the caller's tables(): done | need (one window of rounds per entry; none without a stopping rule) on the device
+// and pinned, and a pinned word for the count read back.  d_trials: the trials-run words on the device.
+struct SeededState {
+    static constexpr uint32_t kWindow = 8;  // rounds enqueued between two looks at the entries still running
+    uint64_t n;
+    uint32_t model_floats, max_trials, n_rounds;
+    double confidence;
+    size_t b_bm, b_bi, b_rm, b_ri, b_run, b_done, b_need;
+    float *d_bm = nullptr, *d_rm = nullptr;
+    int32_t *d_bi = nullptr, *d_ri = nullptr;
+    uint32_t *d_run = nullptr, *d_done = nullptr, *d_need = nullptr /* stays null: no stopping rule */, *d_trials = nullptr;
+    uint32_t *h_done = nullptr, *h_need = nullptr, *h_run = nullptr;
+    SeededState(uint64_t n, uint32_t model_floats, const akz_ransac_options& opt);
+    bool stopping() const { return confidence > 0.0; }
+    size_t bytes() const { return b_bm + b_bi + b_rm + b_ri + b_run; }
+    void place(void* d_state);
+    void tables(void* d_done_need, void* h_done_need, void* h_word);
+    int clear(hipStream_t st) const;
+};
+// seeded_rounds_device: need[entry][k] (seeded_need over n_of(entry) elements, samples of K) for the first window of the entries with
+// h_done == 0; upload() -- the caller's: what it enqueues between the tables and the first round, done | need among it --; then while
+// entries run the rounds: round(r) -- the caller's launch into the ring --, launch::seeded_update, and after every window the read of
+// running[r] and the next table.  t_need (optional) grows by the time spent on the tables.
+AKZ_LOCAL int seeded_rounds_device(hipStream_t st, SeededState& s, int K, uint64_t n_running, const std::function<uint64_t(uint64_t)>& n_of,
+                            const std::function<int()>& upload, const std::function<void(uint32_t)>& round, double* t_need = nullptr);
 // akz_pose_api.cpp: the refusals of akz_match_features_seeded_pose_pairs that are not the seeded call's
 AKZ_LOCAL int pose_pairs_refusals(const char* name, const akz_ransac_options* options, const akz_camera* cameras, uint64_t n_sets,
                                   const akz_pose* poses);

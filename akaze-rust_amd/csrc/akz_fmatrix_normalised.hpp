@@ -91,13 +91,14 @@ struct FundamentalNormalisedRansac {
 
 // FundamentalRefit with that inlier rule (akz_refine_fundamental_normalised, k_refit<FundamentalNormalisedRefit>)
 struct FundamentalNormalisedRefit : FundamentalRefit {
-    static AKZ_HD bool inlier(const float (&f)[9], float x0, float y0, float x1, float y1, float eps) {
+    template <class V, class I>
+    static AKZ_HD bool inlier(const float (&f)[9], const V& v, I i, float eps) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        // eps in a vector register: k_refit<FundamentalRefit> sits at the limit of the scalar registers already, and with the rule's
-        // uniform operands all held there this instantiation spilled 22 of them into vector lanes (the arithmetic is the same)
+        // eps in a vector register, as in FundamentalRefit::inlier and for its reason: this instantiation spilled 22 scalar registers
+        // into vector lanes with the rule's uniform operands all held there (the arithmetic is the same)
         asm("" : "+v"(eps));
 #endif
-        return sampson_inlier(f, x0, y0, x1, y1, eps);
+        return sampson_inlier(f, v.x0[i], v.y0[i], v.x1[i], v.y1[i], eps);
     }
 };
 

@@ -160,25 +160,30 @@ AKZ_HD bool fund_refit_model_from_rotated(M& m, double count, float epsilon_mode
     return true;
 }
 
-// The fundamental matrix as a refit model (see HomographyRefit)
-struct FundamentalRefit {
+// The fundamental matrix as a refit model (see TwoViewRefit)
+struct FundamentalRefit : TwoViewRefit {
     static constexpr int kMin = 8;
     static constexpr int kSums3 = kFundRefitSums3;
-    static AKZ_HD bool inlier(const float (&f)[9], float x0, float y0, float x1, float y1, float eps) {
-        return fundamental_error(f, x0, y0, x1, y1) < eps;
+    template <class V, class I>
+    static AKZ_HD bool inlier(const float (&f)[9], const V& v, I i, float eps) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // eps in a vector register: k_refit<FundamentalRefit> sits at the limit of the scalar registers, and with the rule's uniform
+        // operands all held there it spilled 22 of them into vector lanes and two vector registers to scratch (the same arithmetic)
+        asm("" : "+v"(eps));
+#endif
+        return fundamental_error(f, v.x0[i], v.y0[i], v.x1[i], v.y1[i]) < eps;
     }
-    static AKZ_HD void terms3(float x0, float y0, float x1, float y1, double c0x, double c0y, double s0, double c1x, double c1y, double s1,
-                              double (&t)[kSums3]) {
-        fund_refit_terms3(x0, y0, x1, y1, c0x, c0y, s0, c1x, c1y, s1, t);
+    template <class V, class I>
+    static AKZ_HD void terms3(const V& v, I i, const double (&c)[4], double s0, double s1, double (&t)[kSums3]) {
+        fund_refit_terms3(v.x0[i], v.y0[i], v.x1[i], v.y1[i], c[0], c[1], s0, c[2], c[3], s1, t);
     }
     template <class M>
     static AKZ_HD void normal_matrix(M& m, const double* sums) {
         fund_refit_normal_matrix(m, sums);
     }
     template <class M>
-    static AKZ_HD bool model_from_rotated(M& m, double count, float epsilon_model, double c0x, double c0y, double s0, double c1x, double c1y,
-                                          double s1, float (&f)[9]) {
-        return fund_refit_model_from_rotated(m, count, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, f);
+    static AKZ_HD bool model_from_rotated(M& m, double count, float epsilon_model, const double (&c)[4], double s0, double s1, float (&f)[9]) {
+        return fund_refit_model_from_rotated(m, count, epsilon_model, c[0], c[1], s0, c[2], c[3], s1, f);
     }
 };
 

@@ -38,6 +38,10 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <cstring>
+#include <vector>
+#endif
 
 #include "akz_homography.hpp"
 
@@ -45,28 +49,6 @@ namespace akz {
 
 constexpr int kRefitLanes = 256;  // lanes of the summation order
 constexpr int kRefitSums3 = 24;   // sums of pass 3
-
-#if !defined(__HIP_DEVICE_COMPILE__)
-// The host's form of that order, for every refit (akz_ransac.cpp, akz_resection_api.cpp): the sums of the members' terms -- lane
-// i mod 256, ascending i from +0.0, then the tree.  member: n flags (any indexable); term(i, t) writes element i's K terms.
-template <int K, class Members, class Term>
-inline void lane_tree_sums(uint64_t n, const Members& member, Term term, double (&out)[K]) {
-    static thread_local double p[K][kRefitLanes];
-    for (int k = 0; k < K; ++k)
-        for (int l = 0; l < kRefitLanes; ++l) p[k][l] = 0.0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (!member[(size_t)i]) continue;
-        double t[K];
-        term(i, t);
-        for (int k = 0; k < K; ++k) p[k][i % kRefitLanes] = p[k][i % kRefitLanes] + t[k];
-    }
-    for (int k = 0; k < K; ++k) {
-        for (int s = kRefitLanes / 2; s > 0; s >>= 1)
-            for (int l = 0; l < s; ++l) p[k][l] = p[k][l] + p[k][l + s];
-        out[k] = p[k][0];
-    }
-}
-#endif
 
 AKZ_HD void refit_terms1(float x0, float y0, float x1, float y1, double (&t)[4]) {
     t[0] = (double)x0;
@@ -168,28 +150,113 @@ struct Mat9x9 {
     AKZ_HD double& at(int p, int k) { return v[p][k]; }
 };
 
-// The homography as a REFIT model: what the loop above needs from a model, for the host loop (akz_ransac.cpp) and the refit
-// kernel (akz_homography_refit.hip) alike -- the fewest members of a fit (and matches of a pair the stage works on), the
-// inlier rule, the terms of pass 3, M from their sums and the model from the rotated M.  Passes 1 and 2 are the same for
-// every model.  (FundamentalRefit of akz_fundamental_refit.hpp is the other one.)
-struct HomographyRefit {
+#if !defined(__HIP_DEVICE_COMPILE__)
+// The host's form of that order, for every refit (akz_ransac.cpp, akz_resection_api.cpp): the sums of the members' terms -- lane
+// i mod 256, ascending i from +0.0, then the tree.  member: n flags (any indexable); term(i, t) writes element i's K terms.
+template <int K, class Members, class Term>
+inline void lane_tree_sums(uint64_t n, const Members& member, Term term, double (&out)[K]) {
+    static thread_local double p[K][kRefitLanes];
+    for (int k = 0; k < K; ++k)
+        for (int l = 0; l < kRefitLanes; ++l) p[k][l] = 0.0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!member[(size_t)i]) continue;
+        double t[K];
+        term(i, t);
+        for (int k = 0; k < K; ++k) p[k][i % kRefitLanes] = p[k][i % kRefitLanes] + t[k];
+    }
+    for (int k = 0; k < K; ++k) {
+        for (int s = kRefitLanes / 2; s > 0; s >>= 1)
+            for (int l = 0; l < s; ++l) p[k][l] = p[k][l] + p[k][l + s];
+        out[k] = p[k][0];
+    }
+}
+
+// The loop of the statement on the host for every refit model R (the concept: below) over a view v of n elements -- the one place
+// where the host classifies, fits and applies the accept / grew / stop rule; the device's is refit_loop of akz_ransac_device.hpp.
+// h: the model to start from, the last accepted one on return; member (n flags): the final set; -> the fits accepted.
+template <class R, class View>
+inline uint32_t refit_loop_host(const View& v, uint64_t n, float (&h)[R::kFloats], float epsilon_model, float epsilon_inlier,
+                                uint32_t max_iterations, std::vector<uint8_t>& member) {
+    auto classify = [&](const float (&m)[R::kFloats], std::vector<uint8_t>& set) {
+        uint64_t c = 0;
+        for (uint64_t i = 0; i < n; ++i) c += set[(size_t)i] = R::inlier(m, v, i, epsilon_inlier) ? 1 : 0;
+        return c;
+    };
+    // fit(S) over the members, |S| = count, in the tree's order; false: no model
+    auto fit = [&](const std::vector<uint8_t>& set, uint64_t count, float (&h2)[R::kFloats]) {
+        if (count < (uint64_t)R::kMin) return false;
+        const double cnt = (double)count;
+        double sum1[R::kSums1], sum2[2], sum3[R::kSums3], c[R::kSums1];
+        lane_tree_sums<R::kSums1>(n, set, [&](uint64_t i, double (&t)[R::kSums1]) { R::terms1(v, i, t); }, sum1);
+        for (int k = 0; k < R::kSums1; ++k) c[k] = sum1[k] / cnt;
+        lane_tree_sums<2>(n, set, [&](uint64_t i, double (&t)[2]) { R::terms2(v, i, c, t); }, sum2);
+        double s0 = 0.0, s1 = 0.0;
+        if (!refit_scale(sum2[0], cnt, s0) || !R::scale2(sum2[1], cnt, s1)) return false;
+        lane_tree_sums<R::kSums3>(n, set, [&](uint64_t i, double (&t)[R::kSums3]) { R::terms3(v, i, c, s0, s1, t); }, sum3);
+        typename R::Mat m;
+        R::normal_matrix(m, sum3);
+        jacobi_sweeps_rows<R::kRows, R::kRows>(m);
+        return R::model_from_rotated(m, cnt, epsilon_model, c, s0, s1, h2);
+    };
+    std::vector<uint8_t> next((size_t)n);
+    uint64_t count = classify(h, member);
+    uint32_t done = 0;
+    while (done < max_iterations) {
+        float h2[R::kFloats];
+        if (!fit(member, count, h2)) break;
+        const uint64_t count2 = classify(h2, next);
+        if (count2 < count) break;  // h2 is rejected
+        const bool grew = count2 > count;
+        std::memcpy(h, h2, sizeof(h2));
+        member.swap(next);
+        count = count2;
+        ++done;
+        if (!grew) break;
+    }
+    return done;
+}
+#endif
+
+// A REFIT model (HomographyRefit, FundamentalRefit, ResectionRefit of akz_resection.hpp): what refit_loop_host and the device's
+// refit_loop need from a model, over a view v of the elements and an index i into it:
+//   kMin, kFloats           the fewest members of a fit (and elements the stage works on); the floats of a model
+//   kSums1, kSums3          the sums of passes 1 and 3; pass 2 has two, the first scaled by refit_scale, the second by scale2
+//   kRows, Mat              M is kRows x kRows; the host's matrix type
+//   inlier(h, v, i, eps), terms1(v, i, t), terms2(v, i, c, t), terms3(v, i, c, s0, s1, t)      (c: the kSums1 centroids)
+//   normal_matrix(m, sums), model_from_rotated(m, count, epsilon_model, c, s0, s1, h)
+// Every model of two views (a view: x0 | y0 | x1 | y1) has the passes 1 and 2 of the statement above and a 9 x 9 M:
+struct TwoViewRefit {
+    static constexpr int kSums1 = 4, kRows = 9, kFloats = 9;
+    using Mat = Mat9x9;
+    template <class V, class I>
+    static AKZ_HD void terms1(const V& v, I i, double (&t)[4]) {
+        refit_terms1(v.x0[i], v.y0[i], v.x1[i], v.y1[i], t);
+    }
+    template <class V, class I>
+    static AKZ_HD void terms2(const V& v, I i, const double (&c)[4], double (&t)[2]) {
+        refit_terms2(v.x0[i], v.y0[i], v.x1[i], v.y1[i], c[0], c[1], c[2], c[3], t);
+    }
+    static AKZ_HD bool scale2(double sum_d, double count, double& s) { return refit_scale(sum_d, count, s); }
+};
+// the homography (FundamentalRefit of akz_fundamental_refit.hpp is the other one of two views)
+struct HomographyRefit : TwoViewRefit {
     static constexpr int kMin = 4;
     static constexpr int kSums3 = kRefitSums3;
-    static AKZ_HD bool inlier(const float (&h)[9], float x0, float y0, float x1, float y1, float eps) {
-        return homography_inlier(h, x0, y0, x1, y1, eps);
+    template <class V, class I>
+    static AKZ_HD bool inlier(const float (&h)[9], const V& v, I i, float eps) {
+        return homography_inlier(h, v.x0[i], v.y0[i], v.x1[i], v.y1[i], eps);
     }
-    static AKZ_HD void terms3(float x0, float y0, float x1, float y1, double c0x, double c0y, double s0, double c1x, double c1y, double s1,
-                              double (&t)[kSums3]) {
-        refit_terms3(x0, y0, x1, y1, c0x, c0y, s0, c1x, c1y, s1, t);
+    template <class V, class I>
+    static AKZ_HD void terms3(const V& v, I i, const double (&c)[4], double s0, double s1, double (&t)[kSums3]) {
+        refit_terms3(v.x0[i], v.y0[i], v.x1[i], v.y1[i], c[0], c[1], s0, c[2], c[3], s1, t);
     }
     template <class M>
     static AKZ_HD void normal_matrix(M& m, const double* sums) {
         refit_normal_matrix(m, sums);
     }
     template <class M>
-    static AKZ_HD bool model_from_rotated(M& m, double count, float epsilon_model, double c0x, double c0y, double s0, double c1x, double c1y,
-                                          double s1, float (&h)[9]) {
-        return refit_model_from_rotated(m, count, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, h);
+    static AKZ_HD bool model_from_rotated(M& m, double count, float epsilon_model, const double (&c)[4], double s0, double s1, float (&h)[9]) {
+        return refit_model_from_rotated(m, count, epsilon_model, c[0], c[1], s0, c[2], c[3], s1, h);
     }
 };
 

@@ -328,36 +328,7 @@ extern "C" int akz_remove_outliers_homography(const akz_keypoint* keypoints_0, u
 
 // ---- the refit of a model on its inliers (akz_homography_refit.hpp, akz_fundamental_refit.hpp) -----------------
 namespace {
-// fit(S) of the statement for the refit model R (HomographyRefit, FundamentalRefit); false: no model
-template <class R>
-bool refit_on_members(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const std::vector<uint8_t>& member,
-                      uint64_t count, float epsilon_model, float (&h)[9]) {
-    if (count < (uint64_t)R::kMin) return false;
-    const double cnt = (double)count;
-    double s1sum[4], s2sum[2], s3sum[R::kSums3];
-    lane_tree_sums<4>(n, member, [&](uint64_t i, double (&t)[4]) { refit_terms1(x0[i], y0[i], x1[i], y1[i], t); }, s1sum);
-    const double c0x = s1sum[0] / cnt, c0y = s1sum[1] / cnt, c1x = s1sum[2] / cnt, c1y = s1sum[3] / cnt;
-    lane_tree_sums<2>(n, member, [&](uint64_t i, double (&t)[2]) { refit_terms2(x0[i], y0[i], x1[i], y1[i], c0x, c0y, c1x, c1y, t); }, s2sum);
-    double s0 = 0.0, s1 = 0.0;
-    if (!refit_scale(s2sum[0], cnt, s0) || !refit_scale(s2sum[1], cnt, s1)) return false;
-    lane_tree_sums<R::kSums3>(
-        n, member, [&](uint64_t i, double (&t)[R::kSums3]) { R::terms3(x0[i], y0[i], x1[i], y1[i], c0x, c0y, s0, c1x, c1y, s1, t); }, s3sum);
-    Mat9x9 m;
-    R::normal_matrix(m, s3sum);
-    jacobi_sweeps_rows<9>(m);
-    return R::model_from_rotated(m, cnt, epsilon_model, c0x, c0y, s0, c1x, c1y, s1, h);
-}
-template <class R>
-uint64_t classify(const float* x0, const float* y0, const float* x1, const float* y1, uint64_t n, const float (&h)[9], float eps,
-                  std::vector<uint8_t>& member) {
-    uint64_t c = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        member[(size_t)i] = R::inlier(h, x0[i], y0[i], x1[i], y1[i], eps) ? 1 : 0;
-        c += member[(size_t)i];
-    }
-    return c;
-}
-// the loop of the statement, one for both models; `name` is the call's, `what` its model argument
+// the loop of the statement (refit_loop_host) over a list of matches; `name` is the call's, `what` its model argument
 template <class R>
 int refine_host(const char* name, const char* what, const akz_keypoint* keypoints_0, uint64_t n0, const akz_keypoint* keypoints_1, uint64_t n1,
                 const akz_match* matches, uint64_t n_matches, const float* h_in, float epsilon_model, float epsilon_inlier,
@@ -372,24 +343,10 @@ int refine_host(const char* name, const char* what, const akz_keypoint* keypoint
         return AKZ_ERR_INVALID_ARG;
     }
     const MatchPoints pt(keypoints_0, keypoints_1, matches, n_matches);
-    const float *x0 = pt.x0, *y0 = pt.y0, *x1 = pt.x1, *y1 = pt.y1;
     float h[9];
     std::memcpy(h, h_in, sizeof(h));
-    std::vector<uint8_t> member((size_t)n_matches), next((size_t)n_matches);
-    uint64_t count = classify<R>(x0, y0, x1, y1, n_matches, h, epsilon_inlier, member);
-    uint32_t done = 0;
-    while (done < max_iterations) {
-        float h2[9];
-        if (!refit_on_members<R>(x0, y0, x1, y1, n_matches, member, count, epsilon_model, h2)) break;
-        const uint64_t count2 = classify<R>(x0, y0, x1, y1, n_matches, h2, epsilon_inlier, next);
-        if (count2 < count) break;
-        const bool grew = count2 > count;
-        std::memcpy(h, h2, sizeof(h));
-        member.swap(next);
-        count = count2;
-        ++done;
-        if (!grew) break;
-    }
+    std::vector<uint8_t> member((size_t)n_matches);
+    const uint32_t done = refit_loop_host<R>(pt, n_matches, h, epsilon_model, epsilon_inlier, max_iterations, member);
     uint64_t k = 0;
     for (uint64_t i = 0; i < n_matches; ++i)
         if (member[(size_t)i]) out[k++] = matches[i];

@@ -1,7 +1,8 @@
 // The device skeleton of every RANSAC kernel (akz_ransac_kernels.hip, akz_homography_refit.hip, akz_resection.hip; included by
 // .hip files only): the matrix in LDS, one Jacobi sweep level by level on four lanes, the quad exchange of a trial's sums, the
-// 256-lane tree of the refits, the winner pick and the ordered compaction of a 256-thread workgroup.  The arithmetic is the host's source (akz_fmatrix.hpp, akz_homography.hpp); what is here only moves
-// loops and reductions around it.
+// 256-lane tree of the refits, the winner pick, the ordered compaction of a 256-thread workgroup, and refit_loop with block_count:
+// the refit loop of every model (the statement and the refit concept: akz_homography_refit.hpp).  The arithmetic is the host's
+// source (akz_fmatrix.hpp, akz_homography.hpp, akz_resection.hpp); what is here only moves loops and reductions around it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,6 +71,24 @@ __device__ inline void quad_join(double (&v)[N]) {
         v[k] = v[k] + quad_permute<0xb1>(v[k]);  // lane ^ 1 (quad_perm [1, 0, 3, 2]): (p0 + p2) + (p1 + p3)
     }
 }
+
+// One pair's points as every model of two views reads them, and the pairs calls' table that yields it: x0 | y0 | x1 | y1 at the
+// pair's offset of the matches (k_pair_points), the count of its raw list
+struct PairView {
+    const float *x0, *y0, *x1, *y1;
+    unsigned n;
+};
+struct PairTable {
+    const launch::PairJobHost* pairs;
+    const unsigned long long* raw_cnt;
+    const float* pts;
+    unsigned long long stride;
+    __device__ PairView view(unsigned p) const {
+        const launch::PairJobHost pj = pairs[p];
+        const float* x0 = pts + pj.raw_off;
+        return PairView{x0, x0 + stride, x0 + 2 * stride, x0 + 3 * stride, (unsigned)raw_cnt[pj.cnt_idx]};
+    }
+};
 
 // The winner among trials trial_off .. + n_trials of a 256-thread workgroup: the first trial with the most inliers, strict `>`
 // from 0 in trial order (the largest count, the lowest trial among equals); best = 0: none.  Valid on thread 0 only;
@@ -166,6 +185,126 @@ __device__ void block_sums(const double (&v)[K], double* __restrict__ red, doubl
         }
         __syncthreads();
     }
+}
+
+// |{ i < v.n : inlier under h }| for every thread of the 256
+template <class R, class View>
+__device__ unsigned block_count(const float (&h)[R::kFloats], const View& v, float eps, unsigned* s_wsum, unsigned tid) {
+    unsigned cnt = 0;
+    for (unsigned i = tid; i < v.n; i += kGroup) cnt += R::inlier(h, v, i, eps) ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((tid & 63u) == 0) s_wsum[tid >> 6] = cnt;
+    __syncthreads();
+    unsigned total = 0;
+#pragma unroll
+    for (int k = 0; k < kGroup / 64; ++k) total += s_wsum[k];
+    __syncthreads();
+    return total;
+}
+
+// The loop of the refit's statement (akz_homography_refit.hpp) for the refit model R over the view v, by a workgroup of 256 and the
+// same for all its threads: h is the model to start from and the last accepted one on return; -> the fits accepted.  Element i is
+// thread i mod 256's, added in ascending i: the lane sums live in f64 registers and go through the tree six at a time
+// (block_sums).  M stays in LDS, as the trial wave keeps its own: its rotations run on four lanes of the first wave
+// (jacobi_sweep_levels); the smallest row, the rank rule and the model tail on thread 0.  The caller passes a __syncthreads before
+// the next call (s_ok, s_h, s_sum).  s_wsum: kGroup / 64 counters, the caller's (its compaction uses them too).
+// (The compiler simplifies this function on its own before it inlines it, and the two-view kernels sit at 256 registers: the view by
+// value and the model in a local array keep both out of memory that the LDS stores might alias there; `static` keeps the LDS arrays
+// laid out as a kernel's own.  Without either an instance spills or pads its LDS.)
+template <class R, class View>
+static __device__ __forceinline__ unsigned refit_loop(const View v, float (&h_io)[R::kFloats], float epsilon_model, float epsilon_inlier,
+                                                      unsigned max_iterations, unsigned* s_wsum, unsigned tid) {
+    static_assert(kRefitLanes == kGroup, "block_sums");
+    constexpr int MF = R::kFloats, S1 = R::kSums1, S3 = R::kSums3, ROWS = R::kRows;
+    __shared__ double s_red[kSumGroup * kGroup];
+    __shared__ double s_sum[S3];
+    __shared__ double s_m[ROWS * ROWS];
+    __shared__ float s_h[MF];
+    __shared__ int s_ok;
+    float h[MF];
+#pragma unroll
+    for (int k = 0; k < MF; ++k) h[k] = h_io[k];
+    unsigned cnt = block_count<R>(h, v, epsilon_inlier, s_wsum, tid);
+    unsigned done = 0;
+    while (done < max_iterations) {
+        if (cnt < (unsigned)R::kMin) break;
+        const double count = (double)cnt;
+        double c[S1], s0 = 0.0, s1 = 0.0;
+        {
+            double a[S1];
+#pragma unroll
+            for (int k = 0; k < S1; ++k) a[k] = 0.0;
+            for (unsigned i = tid; i < v.n; i += kGroup)
+                if (R::inlier(h, v, i, epsilon_inlier)) {
+                    double t[S1];
+                    R::terms1(v, i, t);
+#pragma unroll
+                    for (int k = 0; k < S1; ++k) a[k] = a[k] + t[k];
+                }
+            block_sums<S1>(a, s_red, s_sum, tid);
+#pragma unroll
+            for (int k = 0; k < S1; ++k) c[k] = s_sum[k] / count;
+        }
+        {
+            double a[2] = {0.0, 0.0};
+            for (unsigned i = tid; i < v.n; i += kGroup)
+                if (R::inlier(h, v, i, epsilon_inlier)) {
+                    double t[2];
+                    R::terms2(v, i, c, t);
+                    a[0] = a[0] + t[0];
+                    a[1] = a[1] + t[1];
+                }
+            block_sums<2>(a, s_red, s_sum, tid);
+            const double d0 = s_sum[0], d1 = s_sum[1];
+            if (!refit_scale(d0, count, s0) || !R::scale2(d1, count, s1)) break;  // (the same for every thread)
+        }
+        {
+            double a[S3];
+#pragma unroll
+            for (int k = 0; k < S3; ++k) a[k] = 0.0;
+            for (unsigned i = tid; i < v.n; i += kGroup)
+                if (R::inlier(h, v, i, epsilon_inlier)) {
+                    double t[S3];
+                    R::terms3(v, i, c, s0, s1, t);
+#pragma unroll
+                    for (int k = 0; k < S3; ++k) a[k] = a[k] + t[k];
+                }
+            block_sums<S3>(a, s_red, s_sum, tid);
+        }
+        if (tid < 64) {  // the first wave: M, the sweeps on its lanes 0 .. 3, the model on lane 0
+            LdsMatT<ROWS> m{s_m};
+            if (tid == 0) R::normal_matrix(m, s_sum);
+            wave_sync();
+            for (int sweep = 0; sweep < 60; ++sweep)
+                if (__ballot(jacobi_sweep_levels<ROWS, ROWS>(m, (int)tid, tid < 4)) == 0ull) break;  // the first sweep without a rotation
+            if (tid == 0) {
+                float h2[MF];
+                const bool ok = R::model_from_rotated(m, count, epsilon_model, c, s0, s1, h2);
+                s_ok = ok ? 1 : 0;
+                if (ok) {
+#pragma unroll
+                    for (int k = 0; k < MF; ++k) s_h[k] = h2[k];
+                }
+            }
+        }
+        __syncthreads();
+        if (s_ok == 0) break;
+        float h2[MF];
+#pragma unroll
+        for (int k = 0; k < MF; ++k) h2[k] = s_h[k];
+        const unsigned cnt2 = block_count<R>(h2, v, epsilon_inlier, s_wsum, tid);
+        if (cnt2 < cnt) break;  // h2 is rejected
+        const bool grew = cnt2 > cnt;
+#pragma unroll
+        for (int k = 0; k < MF; ++k) h[k] = h2[k];
+        cnt = cnt2;
+        ++done;
+        if (!grew) break;
+    }
+#pragma unroll
+    for (int k = 0; k < MF; ++k) h_io[k] = h[k];
+    return done;
 }
 
 // ... of a match list: thread tid's match *raw_src goes to keep_dst[its place] if `kept`

@@ -1,8 +1,7 @@
 // The seeded resection RANSAC on the GPU (akz_resection_seeded_problems; the statement: akz_resection.hpp, included here as the
-// host includes it -- the same source, the same bits).  Siblings of the seeded pairs call's kernels (akz_ransac_kernels.hip,
-// akz_homography_refit.hip) over problems of five planes X | Y | Z | u | v and models of 15 floats; what those kernels and these
-// share is stated once in akz_ransac_device.hpp (the level-ordered sweeps, the quad exchange, the 256-lane tree, the compaction)
-// and in k_seeded_update<15>, which holds the winner and the stopping rule for every model of the family.
+// host includes it -- the same source, the same bits).  The round kernel has the shape of k_seeded_round (akz_ransac_kernels.hip)
+// over problems of five planes X | Y | Z | u | v and models of 15 floats; k_seeded_update<15> follows it: the winner and the stopping
+// rule of every model of the family.  The refit is refit_loop<ResectionRefit> of akz_ransac_device.hpp, the loop of every model.
 //   k_resection_round<NW>   a round of 128 trials of every problem that still runs
 //   k_resection_finish      per problem: found, the refit loop, the kept indices, the pose
 #include "akz_ransac_device.hpp"
@@ -172,135 +171,48 @@ __global__ void __launch_bounds__(TW * NW) k_resection_round(const ResJob* __res
     }
 }
 
-// |{ i < n : inlier under h }| for every thread of the 256
-__device__ unsigned res_block_count(const float (&h)[MF], const ResCamera& cam, const Planes& pl, unsigned n, float eps, unsigned* s_wsum,
-                                    unsigned tid) {
-    unsigned cnt = 0;
-    for (unsigned i = tid; i < n; i += kGroup) cnt += res_inlier(h, cam, pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], eps) ? 1u : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((tid & 63u) == 0) s_wsum[tid >> 6] = cnt;
-    __syncthreads();
-    unsigned total = 0;
-#pragma unroll
-    for (int k = 0; k < kGroup / 64; ++k) total += s_wsum[k];
-    __syncthreads();
-    return total;
-}
+// one problem's correspondences, camera and count (the view of ResectionRefit), and the table that yields it
+struct ResView : Planes {
+    ResCamera cam;
+    unsigned n;
+};
+struct ResTable {
+    const ResJob* jobs;
+    const float* planes;
+    unsigned long long stride;
+    __device__ ResView view(unsigned p) const {
+        const ResJob pj = jobs[p];
+        return ResView{planes_of(planes, stride, pj.off), ResCamera{pj.fx, pj.fy, pj.cx, pj.cy}, pj.n};
+    }
+};
 
 // After the last round, per problem (a workgroup of 256, grid-stride): found = its best count > 0; with a winner and
-// max_iterations > 0 the refit loop of akz_homography_refit.hpp in the shape of k_refit -- element i is thread i mod 256's, added
-// in ascending i, the lane sums (5, 2, then 40 in f64 registers) go through block_sums six at a time, M and its sweeps in LDS on
-// the first four lanes, the model on thread 0 --; then the kept indices under the final model compacted in order, their count,
-// the accepted fits and the pose.  found = 0: no index, a pose of zeros.
-__global__ void __launch_bounds__(kGroup) k_resection_finish(const ResJob* __restrict__ jobs, unsigned n_problems, const float* __restrict__ planes,
-                                                             unsigned long long stride, const float* __restrict__ best_mdl,
+// max_iterations > 0 refit_loop<ResectionRefit> (lane sums of 5, 2, then 40); then the kept indices under the final model compacted
+// in order, their count, the accepted fits and the pose.  found = 0: no index, a pose of zeros.
+__global__ void __launch_bounds__(kGroup) k_resection_finish(ResTable table, unsigned n_problems, const float* __restrict__ best_mdl,
                                                              const int* __restrict__ best_inl, float epsilon_model, float epsilon_inlier,
                                                              unsigned max_iterations, unsigned* __restrict__ kept_out,
                                                              unsigned* __restrict__ n_kept, unsigned* __restrict__ fits,
                                                              akz_resection* __restrict__ poses) {
-    static_assert(kRefitLanes == kGroup, "block_sums, compact_slot");
     static_assert(sizeof(akz_resection) == (MF + 1) * 4, "r | t | sigma | found");
-    __shared__ double s_red[kSumGroup * kGroup];
-    __shared__ double s_sum[kResSums3];
-    __shared__ double s_m[kResRows * kResRows];
-    __shared__ float s_h[MF];
-    __shared__ int s_ok;
     __shared__ unsigned s_wsum[kGroup / 64];
     const unsigned tid = threadIdx.x;
     for (unsigned p = blockIdx.x; p < n_problems; p += gridDim.x) {
-        const ResJob pj = jobs[p];
-        const unsigned n = pj.n;
-        const ResCamera cam{pj.fx, pj.fy, pj.cx, pj.cy};
-        const Planes pl = planes_of(planes, stride, pj.off);
+        const ResView q = table.view(p);
         const bool found = best_inl[p] > 0;  // (the same for the whole workgroup)
         float h[MF];
 #pragma unroll
         for (int k = 0; k < MF; ++k) h[k] = found ? best_mdl[(size_t)p * MF + k] : 0.0f;
         unsigned done = 0;
-        if (found && max_iterations > 0) {
-            unsigned cnt = res_block_count(h, cam, pl, n, epsilon_inlier, s_wsum, tid);
-            while (done < max_iterations) {
-                if (cnt < (unsigned)kResK) break;
-                const double count = (double)cnt;
-                double c[kResSums1], s2 = 0.0, s3 = 0.0;
-                {
-                    double v[kResSums1] = {0.0, 0.0, 0.0, 0.0, 0.0};
-                    for (unsigned i = tid; i < n; i += kGroup)
-                        if (res_inlier(h, cam, pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], epsilon_inlier)) {
-                            double t[kResSums1];
-                            res_terms1(pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], cam, t);
-#pragma unroll
-                            for (int k = 0; k < kResSums1; ++k) v[k] = v[k] + t[k];
-                        }
-                    block_sums<kResSums1>(v, s_red, s_sum, tid);
-#pragma unroll
-                    for (int k = 0; k < kResSums1; ++k) c[k] = s_sum[k] / count;
-                }
-                {
-                    double v[2] = {0.0, 0.0};
-                    for (unsigned i = tid; i < n; i += kGroup)
-                        if (res_inlier(h, cam, pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], epsilon_inlier)) {
-                            double t[2];
-                            res_terms2(pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], cam, c, t);
-                            v[0] = v[0] + t[0];
-                            v[1] = v[1] + t[1];
-                        }
-                    block_sums<2>(v, s_red, s_sum, tid);
-                    const double d2 = s_sum[0], d3 = s_sum[1];
-                    if (!refit_scale(d2, count, s2) || !res_scale3(d3, count, s3)) break;  // (the same for every thread)
-                }
-                {
-                    double v[kResSums3];
-#pragma unroll
-                    for (int k = 0; k < kResSums3; ++k) v[k] = 0.0;
-                    for (unsigned i = tid; i < n; i += kGroup)
-                        if (res_inlier(h, cam, pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], epsilon_inlier)) {
-                            double t[kResSums3];
-                            res_terms3(pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], cam, c, s2, s3, t);
-#pragma unroll
-                            for (int k = 0; k < kResSums3; ++k) v[k] = v[k] + t[k];
-                        }
-                    block_sums<kResSums3>(v, s_red, s_sum, tid);
-                }
-                if (tid < 64) {  // the first wave: M, the sweeps on its lanes 0 .. 3, the model on lane 0
-                    ResMat m{s_m};
-                    if (tid == 0) res_normal_matrix(m, s_sum);
-                    wave_sync();
-                    for (int sweep = 0; sweep < 60; ++sweep)
-                        if (__ballot(jacobi_sweep_levels<kResRows, kResRows>(m, (int)tid, tid < 4)) == 0ull) break;
-                    if (tid == 0) {
-                        float h2[MF];
-                        const bool ok = res_model_from_rotated(m, count, epsilon_model, c, s2, s3, h2);
-                        s_ok = ok ? 1 : 0;
-                        if (ok) {
-#pragma unroll
-                            for (int k = 0; k < MF; ++k) s_h[k] = h2[k];
-                        }
-                    }
-                }
-                __syncthreads();
-                if (s_ok == 0) break;
-                float h2[MF];
-#pragma unroll
-                for (int k = 0; k < MF; ++k) h2[k] = s_h[k];
-                const unsigned cnt2 = res_block_count(h2, cam, pl, n, epsilon_inlier, s_wsum, tid);
-                if (cnt2 < cnt) break;  // h2 is rejected
-                const bool grew = cnt2 > cnt;
-#pragma unroll
-                for (int k = 0; k < MF; ++k) h[k] = h2[k];
-                cnt = cnt2;
-                ++done;
-                if (!grew) break;
-            }
-        }
+        if (found && max_iterations > 0) done = refit_loop<ResectionRefit>(q, h, epsilon_model, epsilon_inlier, max_iterations, s_wsum, tid);
+        const unsigned long long off = table.jobs[p].off;
         unsigned long long written = 0;
         if (found)
-            for (unsigned base = 0; base < n; base += kGroup) {
+            for (unsigned base = 0; base < q.n; base += kGroup) {
                 const unsigned i = base + tid;
-                const bool kept = i < n && res_inlier(h, cam, pl.X[i], pl.Y[i], pl.Z[i], pl.u[i], pl.v[i], epsilon_inlier);
+                const bool kept = i < q.n && ResectionRefit::inlier(h, q, i, epsilon_inlier);
                 const unsigned long long at = compact_slot(kept, written, s_wsum, tid);
-                if (kept) kept_out[pj.off + at] = i;
+                if (kept) kept_out[off + at] = i;
             }
         if (tid == 0) {
             n_kept[p] = (unsigned)written;
@@ -316,7 +228,7 @@ __global__ void __launch_bounds__(kGroup) k_resection_finish(const ResJob* __res
             out.found = found ? 1 : 0;
             poses[p] = out;
         }
-        __syncthreads();  // (s_ok, s_h, s_sum, s_wsum: the next problem's)
+        __syncthreads();  // (refit_loop's LDS, s_wsum: the next problem's)
     }
 }
 
@@ -338,9 +250,8 @@ void resection_finish(hipStream_t s, const ResJobHost* d_jobs, uint32_t n_proble
                       const float* d_best_mdl, const int32_t* d_best_inl, float epsilon_model, float epsilon_inlier, uint32_t max_iterations,
                       uint32_t* d_kept, uint32_t* d_n_kept, uint32_t* d_fits, akz_resection* d_poses) {
     if (n_problems == 0) return;
-    hipLaunchKernelGGL(k_resection_finish, dim3(std::min<uint32_t>(n_problems, 8192)), dim3(kGroup), 0, s, d_jobs, n_problems, d_planes,
-                       (unsigned long long)stride, d_best_mdl, d_best_inl, epsilon_model, epsilon_inlier, max_iterations, d_kept, d_n_kept, d_fits,
-                       d_poses);
+    hipLaunchKernelGGL(k_resection_finish, dim3(std::min<uint32_t>(n_problems, 8192)), dim3(kGroup), 0, s, ResTable{d_jobs, d_planes, stride},
+                       n_problems, d_best_mdl, d_best_inl, epsilon_model, epsilon_inlier, max_iterations, d_kept, d_n_kept, d_fits, d_poses);
 }
 }  // namespace launch
 }  // namespace akz

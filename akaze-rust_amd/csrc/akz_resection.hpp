@@ -248,6 +248,39 @@ AKZ_HD bool res_inlier(const float (&m)[kResModelFloats], const ResCamera& k, fl
     return c2 > 0.0f && ex * ex + ey * ey < (eps * eps) * (c2 * c2);
 }
 
+// The resection as a refit model (the concept: akz_homography_refit.hpp), for refit_loop_host and the device's refit_loop.  A view:
+// X[i] .. v[i] of the problem's correspondences and its camera `cam`.
+struct ResectionRefit {
+    static constexpr int kMin = kResK, kSums1 = kResSums1, kSums3 = kResSums3, kRows = kResRows, kFloats = kResModelFloats;
+    using Mat = Mat12x12;
+    template <class V, class I>
+    static AKZ_HD bool inlier(const float (&m)[kFloats], const V& q, I i, float eps) {
+        return res_inlier(m, q.cam, q.X[i], q.Y[i], q.Z[i], q.u[i], q.v[i], eps);
+    }
+    template <class V, class I>
+    static AKZ_HD void terms1(const V& q, I i, double (&t)[kSums1]) {
+        res_terms1(q.X[i], q.Y[i], q.Z[i], q.u[i], q.v[i], q.cam, t);
+    }
+    template <class V, class I>
+    static AKZ_HD void terms2(const V& q, I i, const double (&c)[kSums1], double (&t)[2]) {
+        res_terms2(q.X[i], q.Y[i], q.Z[i], q.u[i], q.v[i], q.cam, c, t);
+    }
+    static AKZ_HD bool scale2(double sum_d, double count, double& s) { return res_scale3(sum_d, count, s); }
+    template <class V, class I>
+    static AKZ_HD void terms3(const V& q, I i, const double (&c)[kSums1], double s2, double s3, double (&t)[kSums3]) {
+        res_terms3(q.X[i], q.Y[i], q.Z[i], q.u[i], q.v[i], q.cam, c, s2, s3, t);
+    }
+    template <class M>
+    static AKZ_HD void normal_matrix(M& m, const double* sums) {
+        res_normal_matrix(m, sums);
+    }
+    template <class M>
+    static AKZ_HD bool model_from_rotated(M& m, double count, float epsilon_model, const double (&c)[kSums1], double s2, double s3,
+                                          float (&mdl)[kFloats]) {
+        return res_model_from_rotated(m, count, epsilon_model, c, s2, s3, mdl);
+    }
+};
+
 // The model of one sample: six correspondences in ascending order of their position in the problem.  Part j of a sum holds
 // elements j and j + 4; parts 2 and 3 have no second element.
 AKZ_HD bool resection_from_6(const float (&X)[kResK], const float (&Y)[kResK], const float (&Z)[kResK], const float (&u)[kResK],

@@ -1,9 +1,10 @@
 // Absolute pose by the seeded resection RANSAC (additions; include/akaze_hip.h).  akz_estimate_resection,
 // akz_refine_resection and akz_resection_seeded_host are the statement of akz_resection.hpp run on the host -- one thread, in
-// trial order, no GPU call, no context: the definition, not a fast path.  akz_resection_seeded_problems runs it over many problems
-// on the GPU (akz_resection.hip: the same source on the device): one upload, two launches per round in windows of kWindow rounds
-// as the seeded pairs call enqueues them (akz_match_seeded_api.cpp), one launch for filter and refit, one read-back.  The rounds,
-// the winner and the stopping rule are seeded_rounds / seeded_need on the host and k_seeded_update on the device: the family's.
+// trial order, no GPU call, no context: the definition, not a fast path; their refit is refit_loop_host<ResectionRefit>, the loop of
+// every model.  akz_resection_seeded_problems runs it over many problems on the GPU (akz_resection.hip: the same source on the
+// device): one upload, the rounds by seeded_rounds_device (akz_match_seeded_api.cpp: the driver of every seeded call, which launches this
+// model's round through launch::resection_round), one launch for filter and refit, one read-back.  The winner and the stopping rule
+// are seeded_rounds<K> / seeded_need in the host statement and k_seeded_update on the device: the family's.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -27,20 +28,20 @@ int refuse(const std::string& what) {
     return AKZ_ERR_INVALID_ARG;
 }
 
-// one problem as the statement reads it
+// one problem as the statement reads it (the host's view of ResectionRefit): X[i] .. v[i] out of the interleaved arrays
+struct Strided {
+    const float* p;
+    int step;
+    float operator[](uint64_t i) const { return p[step * i]; }
+};
 struct Problem {
-    const float* pts;
-    const float* px;
+    Strided X, Y, Z, u, v;
     uint64_t n;
     ResCamera cam;
-    float X(uint64_t i) const { return pts[3 * i]; }
-    float Y(uint64_t i) const { return pts[3 * i + 1]; }
-    float Z(uint64_t i) const { return pts[3 * i + 2]; }
-    float u(uint64_t i) const { return px[2 * i]; }
-    float v(uint64_t i) const { return px[2 * i + 1]; }
-    bool inlier(const float (&m)[MF], uint64_t i, float eps) const { return res_inlier(m, cam, X(i), Y(i), Z(i), u(i), v(i), eps); }
 };
-Problem problem_of(const akz_resection_problem& q) { return Problem{q.points, q.pixels, q.n, res_camera(q.camera)}; }
+Problem problem_of(const akz_resection_problem& q) {
+    return Problem{{q.points, 3}, {q.points + 1, 3}, {q.points + 2, 3}, {q.pixels, 2}, {q.pixels + 1, 2}, q.n, res_camera(q.camera)};
+}
 
 // what every call refuses of a problem; `name` ends in ": ", `what` names the problem ("" or "problem 3: ")
 int refuse_problem(const char* name, const std::string& what, const akz_resection_problem& q) {
@@ -65,50 +66,6 @@ void pose_out(const float (&m)[MF], bool found, akz_resection& out) {
     out.found = found ? 1 : 0;
 }
 
-// fit(S) over the members, |S| = count, in the tree's order
-bool fit_members(const Problem& q, const std::vector<uint8_t>& member, uint64_t count, float (&mdl)[MF]) {
-    if (count < (uint64_t)kResK) return false;
-    const double cnt = (double)count;
-    double sum1[kResSums1], sum2[2], sum3[kResSums3], c[kResSums1];
-    lane_tree_sums<kResSums1>(
-        q.n, member, [&](uint64_t i, double(&t)[kResSums1]) { res_terms1(q.X(i), q.Y(i), q.Z(i), q.u(i), q.v(i), q.cam, t); }, sum1);
-    for (int k = 0; k < kResSums1; ++k) c[k] = sum1[k] / cnt;
-    lane_tree_sums<2>(
-        q.n, member, [&](uint64_t i, double(&t)[2]) { res_terms2(q.X(i), q.Y(i), q.Z(i), q.u(i), q.v(i), q.cam, c, t); }, sum2);
-    double s2 = 0.0, s3 = 0.0;
-    if (!refit_scale(sum2[0], cnt, s2) || !res_scale3(sum2[1], cnt, s3)) return false;
-    lane_tree_sums<kResSums3>(
-        q.n, member, [&](uint64_t i, double(&t)[kResSums3]) { res_terms3(q.X(i), q.Y(i), q.Z(i), q.u(i), q.v(i), q.cam, c, s2, s3, t); },
-        sum3);
-    Mat12x12 m;
-    res_normal_matrix(m, sum3);
-    jacobi_sweeps_rows<kResRows, kResRows>(m);
-    return res_model_from_rotated(m, cnt, AKZ_FUNDAMENTAL_REFIT_EPSILON, c, s2, s3, mdl);
-}
-uint64_t classify(const Problem& q, const float (&m)[MF], float eps, std::vector<uint8_t>& member) {
-    uint64_t c = 0;
-    for (uint64_t i = 0; i < q.n; ++i) c += member[(size_t)i] = q.inlier(m, i, eps) ? 1 : 0;
-    return c;
-}
-// the loop of akz_homography_refit.hpp from h; member: the final set; -> the fits accepted
-uint32_t refit_loop(const Problem& q, float (&h)[MF], float eps, uint32_t max_iterations, std::vector<uint8_t>& member) {
-    std::vector<uint8_t> next((size_t)q.n);
-    uint64_t count = classify(q, h, eps, member);
-    uint32_t done = 0;
-    while (done < max_iterations) {
-        float h2[MF];
-        if (!fit_members(q, member, count, h2)) break;
-        const uint64_t count2 = classify(q, h2, eps, next);
-        if (count2 < count) break;
-        const bool grew = count2 > count;
-        std::memcpy(h, h2, sizeof(h2));
-        member.swap(next);
-        count = count2;
-        ++done;
-        if (!grew) break;
-    }
-    return done;
-}
 uint64_t write_kept(const std::vector<uint8_t>& member, uint32_t* kept) {
     uint64_t k = 0;
     for (size_t i = 0; i < member.size(); ++i)
@@ -129,17 +86,16 @@ void seeded_statement(const Problem& q, const akz_ransac_options& opt, uint64_t 
             q.n, opt.seed[0], opt.seed[1], stream, opt.max_trials, opt.confidence,
             [&](const uint64_t(&smp)[kResK]) -> int64_t {
                 float X[kResK], Y[kResK], Z[kResK], u[kResK], v[kResK];
-                for (int i = 0; i < kResK; ++i) X[i] = q.X(smp[i]), Y[i] = q.Y(smp[i]), Z[i] = q.Z(smp[i]), u[i] = q.u(smp[i]), v[i] = q.v(smp[i]);
+                for (int i = 0; i < kResK; ++i) X[i] = q.X[smp[i]], Y[i] = q.Y[smp[i]], Z[i] = q.Z[smp[i]], u[i] = q.u[smp[i]], v[i] = q.v[smp[i]];
                 if (!resection_from_6(X, Y, Z, u, v, q.cam, AKZ_FUNDAMENTAL_REFIT_EPSILON, m)) return -1;
                 int64_t inl = 0;
-                for (uint64_t i = 0; i < q.n; ++i) inl += q.inlier(m, i, opt.epsilon_inliers) ? 1 : 0;
+                for (uint64_t i = 0; i < q.n; ++i) inl += ResectionRefit::inlier(m, q, i, opt.epsilon_inliers) ? 1 : 0;
                 return inl;
             },
             [&] { std::memcpy(best_model, m, sizeof(m)); }, best, run);
         if (best > 0) {
             std::vector<uint8_t> member((size_t)q.n);
-            if (opt.refine_iterations > 0) fits = refit_loop(q, best_model, opt.epsilon_inliers, opt.refine_iterations, member);
-            else classify(q, best_model, opt.epsilon_inliers, member);
+            fits = refit_loop_host<ResectionRefit>(q, q.n, best_model, AKZ_FUNDAMENTAL_REFIT_EPSILON, opt.epsilon_inliers, opt.refine_iterations, member);  // (no iteration: the classification alone)
             k = write_kept(member, kept);
         }
     }
@@ -177,7 +133,7 @@ int akz_refine_resection(const akz_resection_problem* problem, const akz_resecti
     for (int k = 0; k < 9; ++k) h[k] = pose_in->r[k];
     for (int k = 0; k < 3; ++k) h[9 + k] = pose_in->t[k], h[12 + k] = pose_in->sigma[k];
     std::vector<uint8_t> member((size_t)q.n);
-    const uint32_t done = refit_loop(q, h, epsilon, max_iterations, member);
+    const uint32_t done = refit_loop_host<ResectionRefit>(q, q.n, h, AKZ_FUNDAMENTAL_REFIT_EPSILON, epsilon, max_iterations, member);
     *n_kept = write_kept(member, kept);
     if (pose_out_) {
         if (done > 0) pose_out(h, true, *pose_out_);
@@ -200,7 +156,6 @@ int akz_resection_seeded_host(const akz_resection_problem* problem, const akz_ra
 
 int akz_resection_seeded_problems(akz_ctx* c, const akz_resection_problem* problems, uint64_t n_problems, const akz_ransac_options* options,
                                   uint32_t* kept, uint64_t* n_kept, akz_resection* poses, uint32_t* iterations, uint64_t* trials_run) {
-    constexpr uint32_t kWindow = 8;  // rounds enqueued between two looks at the problems still running
     const char* name = "resection_seeded_problems: ";
     if (!c) return refuse(std::string(name) + "null context");
     AKZ_TRY(refuse_options(name, options));
@@ -215,8 +170,7 @@ int akz_resection_seeded_problems(akz_ctx* c, const akz_resection_problem* probl
     }
     if (total && !kept) return refuse(std::string(name) + "null kept");
     const akz_ransac_options& opt = *options;
-    const uint32_t max_trials = (uint32_t)opt.max_trials, n_rounds = (max_trials + AKZ_RANSAC_ROUND - 1) / AKZ_RANSAC_ROUND;
-    const bool stopping = opt.confidence > 0.0;
+    const uint32_t max_trials = (uint32_t)opt.max_trials;
     uint64_t n_running = 0;
     for (uint64_t p = 0; p < n_problems; ++p) n_running += problems[p].n >= (uint64_t)kResK && max_trials > 0 ? 1 : 0;
     if (n_running == 0) {  // nothing to try anywhere: the statement's zeros, and no GPU work
@@ -233,18 +187,18 @@ int akz_resection_seeded_problems(akz_ctx* c, const akz_resection_problem* probl
     // the upload: problem table | done | need (one window of rounds per problem) | X | Y | Z | u | v
     const size_t np = (size_t)n_problems;
     const uint64_t stride = (total + 63) / 64 * 64;
-    const size_t b_job = up256(np * sizeof(launch::ResJobHost)), b_done = up256(np * 4), b_need = stopping ? up256(np * kWindow * 4) : 0;
+    SeededState s(n_problems, MF, opt);
+    const size_t b_job = up256(np * sizeof(launch::ResJobHost)), b_done = s.b_done, b_need = s.b_need;
     const size_t b_pl = up256((size_t)stride * 4 * 5), b_up = b_job + b_done + b_need + b_pl;
-    // the rounds' state: every problem's best model and count, its ring of a round's models and counts, the running counts per round
-    const size_t b_bm = up256(np * MF * 4), b_bi = up256(np * 4), b_rm = up256(np * AKZ_RANSAC_ROUND * MF * 4), b_ri = up256(np * AKZ_RANSAC_ROUND * 4);
-    const size_t b_run = up256((size_t)n_rounds * 4), b_state = b_bm + b_bi + b_rm + b_ri + b_run;
+    const size_t b_state = s.bytes();  // the rounds' state, behind the upload
     // the read-back: kept counts | fits | trials | poses | kept indices
     const size_t b_w = up256(np * 4), b_pose = up256(np * sizeof(akz_resection)), b_down = 3 * b_w + b_pose + up256((size_t)total * 4);
     AKZ_TRY(ensure(c, c->rs_dev, b_up + b_state + b_down));
     AKZ_TRY(ensure_pinned(c, c->rs_pin, b_up + 256 + b_down));
     char *d = (char*)c->rs_dev.p, *h = (char*)c->rs_pin.p;
     launch::ResJobHost* h_job = (launch::ResJobHost*)h;
-    uint32_t *h_done = (uint32_t*)(h + b_job), *h_need = (uint32_t*)(h + b_job + b_done), *h_run = (uint32_t*)(h + b_up);
+    s.tables(d + b_job, h + b_job, h + b_up);
+    uint32_t* h_done = s.h_done;
     float* h_pl = (float*)(h + b_job + b_done + b_need);
     uint64_t off = 0;
     for (size_t p = 0; p < np; ++p) {
@@ -263,56 +217,35 @@ int akz_resection_seeded_problems(akz_ctx* c, const akz_resection_problem* probl
     }
     for (int k = 0; k < 5; ++k)  // (the padding goes up too)
         for (uint64_t i = total; i < stride; ++i) h_pl[k * stride + i] = 0.0f;
-    // need[problem][k] for rounds first .. first + kWindow of the problems that run: filled when the window is about to be launched
-    auto fill_need = [&](uint32_t first) {
-        for (size_t p = 0; p < np; ++p)
-            for (uint32_t k = 0; k < kWindow; ++k) {
-                const uint64_t T = std::min<uint64_t>(max_trials, ((uint64_t)first + k + 1) * AKZ_RANSAC_ROUND);
-                h_need[p * kWindow + k] = h_done[p] == 0u && first + k < n_rounds ? (uint32_t)seeded_need(problems[p].n, kResK, T, opt.confidence) : 0u;
-            }
-    };
-    if (stopping) fill_need(0);
     const launch::ResJobHost* d_job = (const launch::ResJobHost*)d;
-    uint32_t* d_done = (uint32_t*)(d + b_job);
-    uint32_t* d_need = stopping ? (uint32_t*)(d + b_job + b_done) : nullptr;
     const float* d_pl = (const float*)(d + b_job + b_done + b_need);
-    float* d_bm = (float*)(d + b_up);
-    int32_t* d_bi = (int32_t*)(d + b_up + b_bm);
-    float* d_rm = (float*)(d + b_up + b_bm + b_bi);
-    int32_t* d_ri = (int32_t*)(d + b_up + b_bm + b_bi + b_rm);
-    uint32_t* d_run = (uint32_t*)(d + b_up + b_bm + b_bi + b_rm + b_ri);
+    s.place(d + b_up);
     char* d_down = d + b_up + b_state;
     uint32_t *d_nk = (uint32_t*)d_down, *d_fits = (uint32_t*)(d_down + b_w), *d_trials = (uint32_t*)(d_down + 2 * b_w);
+    s.d_trials = d_trials;
     akz_resection* d_pose = (akz_resection*)(d_down + 3 * b_w);
     uint32_t* d_kept = (uint32_t*)(d_down + 3 * b_w + b_pose);
     const bool timed = c->rs_split_on;
-    if (timed) {
-        for (Event& e : c->mp_split_ev) AKZ_TRY(e.ensure(hipEventDefault));
-        AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
-    }
-    AKZ_HIP_TRY(hipMemcpyAsync(d, h, b_up, hipMemcpyHostToDevice, st));
-    AKZ_HIP_TRY(hipMemsetAsync(d_bm, 0, b_bm + b_bi, st));  // no winner yet: count 0, the zero model
-    AKZ_HIP_TRY(hipMemsetAsync(d_run, 0, b_run, st));
-    AKZ_HIP_TRY(hipMemsetAsync(d_trials, 0, b_w, st));      // (a problem that never runs: 0 trials)
-    if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
     const uint64_t k1 = seeded_seed_key(opt.seed[0], opt.seed[1]);
-    for (uint32_t r = 0; r < n_rounds && n_running; ++r) {
-        launch::resection_round(st, d_job, (uint32_t)np, d_done, k1, opt.stream_base, r, max_trials, d_pl, stride, AKZ_FUNDAMENTAL_REFIT_EPSILON,
-                                opt.epsilon_inliers, d_rm, d_ri);
-        launch::seeded_update(st, (uint32_t)np, r, max_trials, d_need, kWindow, r % kWindow, d_rm, d_ri, d_done, d_bi, d_bm, d_trials, d_run, MF);
-        AKZ_HIP_TRY(hipGetLastError());
-        if (stopping && (r + 1) % kWindow == 0 && r + 1 < n_rounds) {  // (without the rule every problem runs to max_trials)
-            AKZ_HIP_TRY(hipMemcpyAsync(h_run, d_run + r, 4, hipMemcpyDeviceToHost, st));
-            AKZ_HIP_TRY(hipStreamSynchronize(st));
-            n_running = *h_run;
-            if (n_running) {  // the next window's table (the stream is idle: the pinned table is free to rewrite)
-                fill_need(r + 1);
-                AKZ_HIP_TRY(hipMemcpyAsync(d_need, h_need, b_need, hipMemcpyHostToDevice, st));
+    AKZ_TRY(seeded_rounds_device(
+        st, s, kResK, n_running, [&](uint64_t p) { return problems[p].n; },
+        [&]() -> int {
+            if (timed) {
+                for (Event& e : c->mp_split_ev) AKZ_TRY(e.ensure(hipEventDefault));
+                AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[0], st));
             }
-        }
-    }
+            AKZ_HIP_TRY(hipMemcpyAsync(d, h, b_up, hipMemcpyHostToDevice, st));
+            AKZ_TRY(s.clear(st));
+            AKZ_HIP_TRY(hipMemsetAsync(d_trials, 0, b_w, st));  // (a problem that never runs: 0 trials)
+            if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[1], st));
+            return AKZ_OK;
+        },
+        [&](uint32_t r) {
+            launch::resection_round(st, d_job, (uint32_t)np, s.d_done, k1, opt.stream_base, r, max_trials, d_pl, stride,
+                                    AKZ_FUNDAMENTAL_REFIT_EPSILON, opt.epsilon_inliers, s.d_rm, s.d_ri);
+        }));
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[2], st));
-    launch::resection_finish(st, d_job, (uint32_t)np, d_pl, stride, d_bm, d_bi, AKZ_FUNDAMENTAL_REFIT_EPSILON, opt.epsilon_inliers,
+    launch::resection_finish(st, d_job, (uint32_t)np, d_pl, stride, s.d_bm, s.d_bi, AKZ_FUNDAMENTAL_REFIT_EPSILON, opt.epsilon_inliers,
                              opt.refine_iterations, d_kept, d_nk, d_fits, d_pose);
     AKZ_HIP_TRY(hipGetLastError());
     if (timed) AKZ_HIP_TRY(hipEventRecord(c->mp_split_ev[3], st));

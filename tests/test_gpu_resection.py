@@ -85,6 +85,23 @@ def test_twelve_problems_equal_the_host_statement(ctx, amd, problems, max_trials
         assert any(e[2] > 0 for e in exp)
 
 
+@pytest.mark.parametrize("max_trials", [1025, 2177])   # one trial past a window of eight rounds, and past two windows
+@pytest.mark.parametrize("confidence", [0.0, 0.99])
+def test_past_a_window_of_rounds(ctx, amd, problems, max_trials, confidence):
+    """The rounds driver's window path, which 200 trials never reach: after eight rounds the host reads the count of problems still
+    running and uploads the next window's need table.  With the stopping rule one call holds problems that cross the window (the
+    outliers and the plane have no winner, so the rule never stops them) and scenes that finished before it."""
+    sub = [problems[p] for p in (2, 4, 5, 8, 9)]   # 7, 256 and 257 correspondences, the plane, the outliers
+    opt = options(amd, max_trials, confidence, 2)
+    exp = host(amd, sub, opt)
+    same(ctx.resection_seeded(sub, opt), exp, (max_trials, confidence))
+    trials = [e[3] for e in exp]
+    if confidence:
+        assert trials[4] == max_trials and any(t < 1024 for t in trials[:3]), trials
+    else:
+        assert trials == [max_trials] * 5, trials
+
+
 def test_nothing_written_beyond_the_counts_or_by_a_refused_call(ctx, amd, problems):
     L = amd.lib()
     opt = options(amd, 200, 0.0, 2)
