@@ -362,8 +362,8 @@ struct Decoder {
             fc.cwpx = (uint32_t)cwpx; fc.chpx = (uint32_t)chpx; fc.blk0 = f.nblocks;
             f.nblocks += fc.bw * fc.bh;
             fc.plane_off = f.plane_bytes;
-            fc.plane_len = std::max<uint64_t>((uint64_t)fc.pw * fc.bh * 8, (uint64_t)fc.pw * (height - 1) + width);
-            f.plane_bytes += (fc.plane_len + 7) & ~(uint64_t)7;
+            fc.plane_len = (uint64_t)fc.pw * fc.bh * 8;
+            f.plane_bytes += fc.plane_len;
         }
         int st = AKZ_OK;
         int16_t* store = (*alloc)(f, &st);
@@ -673,7 +673,9 @@ void reconstruct_host(const Frame& f, const int16_t* coef, uint32_t* ch, std::ve
         for (int y = 0; y < height; ++y) memcpy(&px[(size_t)y * width], &planes[0][(size_t)y * pw], width);
         return;
     }
-    // chroma upsampling (triangle filter for 2x, nearest otherwise) + YCbCr -> RGB
+    // upsampling + YCbCr -> RGB.  A component at the frame's own factors is copied; one at half the horizontal factor and
+    // the same or half the vertical one goes through the triangle filter; every other one, a factor that does not divide
+    // the maximum included (h = 2 of hmax = 3), gives the nearest sample by position.
     *ch = 3;
     px.resize((size_t)width * height * 3);
     std::vector<std::vector<uint8_t>> rows(3, std::vector<uint8_t>((size_t)width + 16));
@@ -685,7 +687,7 @@ void reconstruct_host(const Frame& f, const int16_t* coef, uint32_t* ch, std::ve
             const int sh = hmax / (int)c.h, sv = vmax / (int)c.v;
             const int cwpx = (int)c.cwpx, chpx = (int)c.chpx;
             uint8_t* o = rows[ci].data();
-            if (sh == 1 && sv == 1) {
+            if ((int)c.h == hmax && (int)c.v == vmax) {
                 memcpy(o, &plane[(size_t)y * pw], width);
             } else if (sh == 2 && (sv == 1 || sv == 2) && hmax % (int)c.h == 0 && vmax % (int)c.v == 0) {
                 int yn = y, yf = y;

@@ -2,7 +2,9 @@
 // blocks into padded component planes, k_jpeg_luma upsamples the chroma, converts to RGB and to luma in one pass per output
 // pixel.  Both are the host decoder's arithmetic (akz_image.cpp: idct, reconstruct_host) operation for operation: the same
 // 64-bit integer IDCT, the same branches of the upsampler and the same unfused f32 colour and luma expressions
-// (-ffp-contract=off), so the bytes equal akz_image_load_luma's for every stream the host accepts.
+// (-ffp-contract=off), so the bytes equal akz_image_load_luma's for every stream the host accepts.  The upsampler copies a
+// component only at the frame's own factors (h == hmax and v == vmax), filters one at half the horizontal factor, and
+// takes the nearest sample by position for every other, a factor that does not divide the maximum included.
 #include <hip/hip_runtime.h>
 
 #include "akz_frames.hpp"
@@ -95,7 +97,7 @@ __global__ void __launch_bounds__(IT) k_jpeg_idct(Frame f, const int16_t* __rest
 // The sample of component c that reconstruct_host puts at (x, y) of its upsampled row.
 __device__ inline int upsampled(const FrameComp& c, const uint8_t* __restrict__ p, int x, int y, int width, int hmax, int vmax) {
     const int pw = (int)c.pw, sh = hmax / (int)c.h, sv = vmax / (int)c.v, cwpx = (int)c.cwpx, chpx = (int)c.chpx;
-    if (sh == 1 && sv == 1) return p[(size_t)y * pw + x];  // (inside plane_len: see FrameComp)
+    if ((int)c.h == hmax && (int)c.v == vmax) return p[(size_t)y * pw + x];
     if (sh == 2 && (sv == 1 || sv == 2) && hmax % (int)c.h == 0 && vmax % (int)c.v == 0) {
         const int i = x >> 1;
         if (sv == 1) {  // h2v1 fancy upsampling

@@ -16,8 +16,8 @@ namespace jpg {
 // One component of a decoded frame as the reconstruction needs it.  Its coefficients are bw * bh blocks of 64 int16 in
 // natural order (row-major block grid), starting at block `blk0` of the frame's coefficient storage; its plane is
 // (bw * 8) x (bh * 8) u8 samples, row stride pw = bw * 8, at byte `plane_off` of the frame's plane storage, `plane_len`
-// bytes long: at least pw * (height - 1) + width, so that the straight copy of a component whose sampling factor does not
-// divide the frame's maximum (hmax / h == 1 with h < hmax) reads inside the plane; bytes past the blocks are zero.
+// = pw * bh * 8 bytes long, all of them written by the IDCT.  The upsampler reads no sample beyond column cwpx - 1 or row
+// chpx - 1 of a subsampled component, and none beyond the frame's width and height of one at the frame's own factors.
 struct FrameComp {
     uint32_t h, v, bw, bh, pw, cwpx, chpx, blk0;
     uint64_t plane_off, plane_len;
@@ -26,7 +26,7 @@ struct FrameComp {
 struct Frame {
     uint32_t width, height, hmax, vmax, nc, nblocks;
     FrameComp c[3];
-    uint64_t plane_bytes;  // sum of plane_len (each rounded up to 8 bytes)
+    uint64_t plane_bytes;  // sum of plane_len (each a multiple of 64)
 };
 
 // Storage for the coefficients: called once per stream, after the frame header, with the frame's layout (coefficient count

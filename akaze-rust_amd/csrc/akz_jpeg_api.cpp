@@ -93,11 +93,6 @@ int reconstruct(akz_ctx* c, int slot, const Staged& st, uint8_t* d_dst) {
         AKZ_HIP_TRY(hipMemcpyAsync(c->jpeg_coef.p, c->jpeg_pin[slot].p, coef_bytes, hipMemcpyHostToDevice, s));
     }
     AKZ_HIP_TRY(hipEventRecord(c->jpeg_up[slot], s));
-    for (uint32_t k = 0; k < f.nc; ++k) {  // plane bytes past the blocks read as zero (see FrameComp)
-        const uint64_t blocks = (uint64_t)f.c[k].pw * f.c[k].bh * 8;
-        if (f.c[k].plane_len > blocks)
-            AKZ_HIP_TRY(hipMemsetAsync(d_plane + f.c[k].plane_off + blocks, 0, f.c[k].plane_len - blocks, s));
-    }
     {
         StageTimer t(c, kStageIngest, s);
         t.kernel(AKZ_KR_JPEG_IDCT, f.nc, f.width, f.height, 1, 1, (uint64_t)f.nblocks * 64);

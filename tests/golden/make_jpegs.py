@@ -1,24 +1,25 @@
 """Regenerates the JPEG fixtures of tests/golden/jpeg/ (the input of tests/test_gpu_jpeg.py and tests/test_jpeg_host.py).
 
 Every sampling the host decoder reconstructs differently gets a file: grayscale, 4:4:4, 4:2:2 and 4:2:0 (written by
-Pillow), 4:4:0 (h1v2), 4:1:1 (h4v1) and a mixed 3:2:1 horizontal sampling (written by the small baseline encoder below,
-since Pillow cannot), progressive 4:2:0, restart intervals, quality 100, sizes below and above one MCU (1x1, 2x2, 17x9,
+Pillow), 4:4:0 (h1v2), 4:1:1 (h4v1) and a mixed 3:2:1 horizontal sampling (written by the small baseline encoder of
+tests/jpeg_numpy.py, since Pillow cannot), progressive 4:2:0, restart intervals, quality 100, sizes below and above one MCU (1x1, 2x2, 17x9,
 chroma one sample wide), and extreme.jpg: 16-bit (pq=1) quantisation tables near 65535 and coefficients near +-32767, so
 that dequantised values approach +-2^31.  Deterministic: numpy's seeded generator and fixed encoder settings.
-Run from the repo root:  python tests/golden/make_jpegs.py
+The files the baseline encoder writes are listed in ENCODED with the function that gives their coefficients, so that a test
+can state what they decode to.  Run from the repo root:  python tests/golden/make_jpegs.py
 """
 import io
 import os
-import struct
+import sys
 
 import numpy as np
-from PIL import Image
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "jpeg")
+HERE = os.path.dirname(os.path.abspath(__file__))
+if os.path.dirname(HERE) not in sys.path:
+    sys.path.insert(0, os.path.dirname(HERE))
+from jpeg_numpy import dct_matrix, encode  # noqa: E402
 
-ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
-          62, 63]
+OUT = os.path.join(HERE, "jpeg")
 
 
 def picture(w, h, seed):
@@ -34,6 +35,7 @@ def picture(w, h, seed):
 
 
 def pillow(name, w, h, seed, mode="RGB", **kw):
+    from PIL import Image  # (only the files Pillow writes need it)
     px = picture(w, h, seed)
     im = Image.fromarray(px, "RGB")
     if mode == "L":
@@ -43,119 +45,14 @@ def pillow(name, w, h, seed, mode="RGB", **kw):
     return name, buf.getvalue()
 
 
-# ---- a minimal baseline encoder: any sampling factors, 8- or 16-bit tables, flat Huffman codes ------------------------
-class Bits:
-    def __init__(self):
-        self.out = bytearray()
-        self.acc = 0
-        self.n = 0
-
-    def put(self, code, length):
-        for i in range(length - 1, -1, -1):
-            self.acc = (self.acc << 1) | ((code >> i) & 1)
-            self.n += 1
-            if self.n == 8:
-                self.out.append(self.acc)
-                if self.acc == 0xFF:
-                    self.out.append(0)
-                self.acc = self.n = 0
-
-    def flush(self):
-        while self.n:
-            self.put(1, 1)
-        return bytes(self.out)
-
-
-def category(v):
-    return 0 if v == 0 else int(abs(int(v))).bit_length()
-
-
-def magnitude_bits(v, s):
-    return v if v >= 0 else v + (1 << s) - 1
-
-
-# Flat codes: DC categories 0..11 as 4-bit codes, AC symbols EOB, ZRL and every (run, size 1..15) as 8-bit codes.  Sizes up to
-# 15 reach the whole int16 range that extreme.jpg needs (the Annex K tables stop at 10).
-DC_SYMS = list(range(12))
-AC_SYMS = [0x00, 0xF0] + [(r << 4) | s for r in range(16) for s in range(1, 16)]
-DC_CODE = {s: (i, 4) for i, s in enumerate(DC_SYMS)}
-AC_CODE = {s: (i, 8) for i, s in enumerate(AC_SYMS)}
-
-
-def segment(marker, body):
-    return struct.pack(">BBH", 0xFF, marker, len(body) + 2) + body
-
-
-def encode(w, h, comps, coefs, qtabs):
-    """comps: [(h, v, tq)]; coefs[k]: int array [bh, bw, 64] (quantised, natural order) covering whole MCUs; qtabs: {tq: 64
-    values in natural order}."""
-    hmax, vmax = max(c[0] for c in comps), max(c[1] for c in comps)
-    if len(comps) == 1:
-        hmax = vmax = 1
-    mcux, mcuy = -(-w // (8 * hmax)), -(-h // (8 * vmax))
-    out = bytearray(b"\xff\xd8")
-    for tq, tab in sorted(qtabs.items()):
-        pq = 1 if max(tab) > 255 else 0
-        vals = [tab[ZIGZAG[i]] for i in range(64)]
-        out += segment(0xDB, bytes([(pq << 4) | tq]) + (struct.pack(">64H", *vals) if pq else bytes(vals)))
-    sof = struct.pack(">BHHB", 8, h, w, len(comps))
-    for i, (ch, cv, tq) in enumerate(comps):
-        sof += bytes([i + 1, (ch << 4) | cv, tq])
-    out += segment(0xC0, sof)
-    for tc, syms, length in ((0, DC_SYMS, 4), (1, AC_SYMS, 8)):
-        counts = [0] * 16
-        counts[length - 1] = len(syms)
-        out += segment(0xC4, bytes([tc << 4]) + bytes(counts) + bytes(syms))
-    sos = bytes([len(comps)]) + b"".join(bytes([i + 1, 0x00]) for i in range(len(comps))) + bytes([0, 63, 0])
-    out += segment(0xDA, sos)
-    bits = Bits()
-    pred = [0] * len(comps)
-    for my in range(mcuy):
-        for mx in range(mcux):
-            for k, (ch, cv, _) in enumerate(comps):
-                if len(comps) == 1:
-                    ch = cv = 1
-                for vv in range(cv):
-                    for hh in range(ch):
-                        blk = coefs[k][my * cv + vv, mx * ch + hh]
-                        diff = int(blk[0]) - pred[k]
-                        pred[k] = int(blk[0])
-                        s = category(diff)
-                        bits.put(*DC_CODE[s])
-                        bits.put(magnitude_bits(diff, s), s)
-                        run = 0
-                        for i in range(1, 64):
-                            v = int(blk[ZIGZAG[i]])
-                            if v == 0:
-                                run += 1
-                                continue
-                            while run > 15:
-                                bits.put(*AC_CODE[0xF0])
-                                run -= 16
-                            s = category(v)
-                            bits.put(*AC_CODE[(run << 4) | s])
-                            bits.put(magnitude_bits(v, s), s)
-                            run = 0
-                        if run:
-                            bits.put(*AC_CODE[0x00])
-    out += bits.flush() + b"\xff\xd9"
-    return bytes(out)
-
-
-def dct_matrix():
-    k = np.arange(8)
-    m = np.cos((2 * k[None, :] + 1) * k[:, None] * np.pi / 16) * 0.5
-    m[0] /= np.sqrt(2)
-    return m
-
-
 STD_LUMA_Q = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51,
               87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101,
               72, 92, 95, 98, 112, 100, 103, 99]
 
 
-def encode_picture(w, h, seed, factors):
-    """Colour picture with Y/Cb/Cr sampling factors [(h, v)] x 3, quality ~75 with the Annex K luma table for all planes."""
+def picture_coefs(w, h, seed, factors):
+    """Colour picture with Y/Cb/Cr sampling factors [(h, v)] x 3, quality ~75 with the Annex K luma table for all planes:
+    the arguments of jpeg_numpy.encode."""
     rgb = picture(w, h, seed).astype(np.float64)
     ycc = [0.299 * rgb[..., 0] + 0.587 * rgb[..., 1] + 0.114 * rgb[..., 2],
            -0.168736 * rgb[..., 0] - 0.331264 * rgb[..., 1] + 0.5 * rgb[..., 2] + 128,
@@ -180,12 +77,13 @@ def encode_picture(w, h, seed, factors):
         d = np.einsum("ij,abjk,lk->abil", D, blocks, D).reshape(mcuy * cv, mcux * ch, 64)
         coefs.append(np.round(d / q).astype(np.int64))
     comps = [(fh, fv, 0) for fh, fv in factors]
-    return encode(w, h, comps, coefs, {0: [int(v) for v in q]})
+    return w, h, comps, coefs, {0: [int(v) for v in q]}
 
 
-def extreme():
+def extreme_coefs():
     """4:2:0, 64x16: 16-bit tables near 65535, AC coefficients of 2^14 .. 2^15 - 1 in magnitude, and DC values that walk
-    (in steps of 2047, the largest baseline DC difference) up to 32752 in Y and +-8188 in the chroma blocks."""
+    (in steps of 2047, the largest baseline DC difference) up to 32752 in Y and +-8188 in the chroma blocks: the arguments
+    of jpeg_numpy.encode."""
     rng = np.random.default_rng(7)
     mcux, mcuy = 4, 1
     comps = [(2, 2, 0), (1, 1, 1), (1, 1, 1)]
@@ -205,7 +103,19 @@ def extreme():
                         blk[idx] = rng.choice([-1, 1], size=12) * rng.integers(1 << 14, 1 << 15, size=12)
         coefs.append(c)
     tabs = {0: [65535 - i for i in range(64)], 1: [65000 + 7 * i for i in range(64)]}
-    return encode(64, 16, comps, coefs, tabs)
+    return 64, 16, comps, coefs, tabs
+
+
+# the files the baseline encoder writes: name -> the arguments of jpeg_numpy.encode
+ENCODED = {
+    "s440_45x37.jpg": lambda: picture_coefs(45, 37, 18, [(1, 2), (1, 1), (1, 1)]),
+    "s440_3x3.jpg": lambda: picture_coefs(3, 3, 19, [(1, 2), (1, 1), (1, 1)]),
+    "s411_53x19.jpg": lambda: picture_coefs(53, 19, 20, [(4, 1), (1, 1), (1, 1)]),
+    "s411_3x7.jpg": lambda: picture_coefs(3, 7, 21, [(4, 1), (1, 1), (1, 1)]),
+    "s321_41x13.jpg": lambda: picture_coefs(41, 13, 22, [(3, 1), (2, 1), (1, 1)]),
+    "s420_custom_29x23.jpg": lambda: picture_coefs(29, 23, 23, [(2, 2), (1, 1), (1, 1)]),
+    "extreme.jpg": extreme_coefs,
+}
 
 
 def main():
@@ -228,14 +138,7 @@ def main():
         pillow("prog444_31x17.jpg", 31, 17, 15, quality=85, subsampling=0, progressive=True),
         pillow("rst420_120x88.jpg", 120, 88, 16, quality=85, subsampling=2, restart_marker_blocks=3),
         pillow("rst422_65x33.jpg", 65, 33, 17, quality=85, subsampling=1, restart_marker_blocks=1),
-        ("s440_45x37.jpg", encode_picture(45, 37, 18, [(1, 2), (1, 1), (1, 1)])),
-        ("s440_3x3.jpg", encode_picture(3, 3, 19, [(1, 2), (1, 1), (1, 1)])),
-        ("s411_53x19.jpg", encode_picture(53, 19, 20, [(4, 1), (1, 1), (1, 1)])),
-        ("s411_3x7.jpg", encode_picture(3, 7, 21, [(4, 1), (1, 1), (1, 1)])),
-        ("s321_41x13.jpg", encode_picture(41, 13, 22, [(3, 1), (2, 1), (1, 1)])),
-        ("s420_custom_29x23.jpg", encode_picture(29, 23, 23, [(2, 2), (1, 1), (1, 1)])),
-        ("extreme.jpg", extreme()),
-    ]
+    ] + [(name, encode(*args())) for name, args in ENCODED.items()]
     for name, data in files:
         with open(os.path.join(OUT, name), "wb") as f:
             f.write(data)
