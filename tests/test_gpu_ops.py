@@ -1,5 +1,7 @@
 """GPU parity tests, one per op of the C ABI, against the CPU oracle on the same seeded inputs.
-Bar: bit-exact (f32 results compared by value so that -0.0 == +0.0, NaNs never expected)."""
+Bar: bit-exact (f32 results compared by value so that -0.0 == +0.0, NaNs never expected).
+The oracle is not the planes' only witness: tests/test_gpu_scalespace.py holds the same ops, on smaller and odder shapes, to
+tests/scalespace_numpy.py, a numpy statement written from the reference's text without the oracle."""
 import os
 
 import numpy as np
