@@ -1,7 +1,9 @@
 """k_orientation and k_mldb as stand-alone ops on keypoints the detector did NOT produce (akz_result_describe_keypoints:
 ops::scale_space_extrema::compute_main_orientation, ops::descriptors::extract_descriptors): at and beyond the border, on
 every level, with octaves that are not their level's, at degenerate scales and angles, with non-finite fields, at every
-keypoint count around the kernels' workgroup sizes, on every image of a batch and with 1 / 2 / 3 channels.
+keypoint count around the kernels' workgroup sizes, on every image of a batch and with 1 / 2 / 3 channels; and on the two
+families built so that a NEARLY right kernel goes wrong, tie keypoints and mirror planes (the planes and keypoints are
+tests/describe_cases.py's; tests/test_describe_teeth_host.py proves which deviations they catch).
 
 Expected values come from tests/mldb_numpy.py -- a numpy statement of the two ops written from the reference's text and held
 to the oracle by tests/test_describe_host.py -- in its `clamped` form, the product's contract.  Where the statement says that
@@ -11,14 +13,12 @@ generated (none is filtered out)."""
 import numpy as np
 import pytest
 
+import describe_cases as D
 import mldb_numpy as M
 
 SIZES = [(517, 389), (163, 81), (64, 40)]
-KINDS = ("wide", "ints", "flat_gradients", "ly_not_positive")
+KINDS = D.KINDS
 INVALID_ARG = -1
-SPECIAL_ANGLES = [0.0, -0.0, np.pi / 4, -np.pi / 4, 3 * np.pi / 4, -3 * np.pi / 4, np.pi / 2, -np.pi / 2, np.pi, -np.pi, 1000.0]
-ANGLES = np.array(SPECIAL_ANGLES + list(np.linspace(-np.pi, np.pi, 14)[1:-1]), np.float32)  # 23 of them
-OCTAVES = (0, 0, -1, 1, 0, 30, 0)  # relative to the level's octave; 30: the largest the entry point accepts
 
 
 def bits(a):
@@ -26,54 +26,10 @@ def bits(a):
 
 
 def crafted_planes(amd, w, h, kind, seed):
-    """Lt, Lx, Ly of every level of a w x h pyramid, made up: the ops under test read planes, not images.
-    wide: both signs over 40 binades, so that any change in the order of the additions shows; ints: small integers, so
-    that cell means tie exactly and a `>=` in place of `>` would flip bits; flat_gradients: Lx = Ly = 0, no orientation
-    window is longer than zero and the given angle has to come back; ly_not_positive: every orientation sample skipped."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for lv in amd.plan_levels(w, h):
-        shape = (lv["h"], lv["w"])
-
-        def wide():
-            return (rng.choice([-1.0, 1.0], shape) * np.exp2(rng.uniform(-20, 20, shape)) * rng.uniform(1, 2, shape)).astype(np.float32)
-
-        if kind == "wide":
-            p = dict(Lt=wide(), Lx=wide(), Ly=wide())
-        elif kind == "ints":
-            p = {n: rng.integers(-2, 3, shape).astype(np.float32) for n in ("Lt", "Lx", "Ly")}
-        elif kind == "flat_gradients":
-            p = dict(Lt=wide(), Lx=np.zeros(shape, np.float32), Ly=np.zeros(shape, np.float32))
-        else:
-            ly = -np.abs(wide())
-            ly[rng.uniform(size=shape) < 0.2] = 0.0
-            ly[rng.uniform(size=shape) < 0.1] = -0.0
-            p = dict(Lt=wide(), Lx=wide(), Ly=ly)
-        out.append(p)
-    return out
+    return D.crafted_planes(amd.plan_levels(w, h), kind, seed)
 
 
-def crafted_keypoints(levels):
-    """Per level: 10 x 9 positions (the corners, the edges, a few pixels outside, exactly w - 1, halves) x 6 sizes (scale 0,
-    1, 3, the level's natural one, ten planes wide, negative); octave and angle cycle through OCTAVES and ANGLES with the
-    running index (7 and 23 are coprime to each other and to the 540 keypoints of a level, so every pairing turns up).
-    The position is given in LEVEL pixels of the descriptor, which divides by the keypoint's own octave."""
-    rows = []
-    i = 0
-    for lvl, lv in enumerate(levels):
-        lw, lh, o = lv["w"], lv["h"], lv["octave"]
-        xs = [-3.0, 0.0, 0.5, 2.5, lw // 2 + 0.5, lw - 1.5, lw - 1.0, lw + 2.0, lw + 5.0, lw + 9.0]
-        ys = [-3.0, 0.0, 0.5, 2.5, lh // 4 + 0.25, lh // 2 + 0.5, lh - 1.5, lh - 1.0, lh + 2.0]
-        sizes = [0.0, 2.0, 6.0, lv["esigma"] * 1.5 / 2 ** o, 2.0 * lw, -4.0]  # in level pixels: scale = round(size / 2)
-        for py in ys:
-            for px in xs:
-                for sz in sizes:
-                    rel = OCTAVES[i % len(OCTAVES)]
-                    okp = 30 if rel == 30 else max(0, o + rel)
-                    r = 2.0 ** okp
-                    rows.append((px * r, py * r, 0.0, sz * r, okp, lvl, ANGLES[i % len(ANGLES)], 0))
-                    i += 1
-    return np.array(rows, M.KEYPOINT_DTYPE)
+crafted_keypoints, nonfinite_keypoints = D.crafted_keypoints, D.nonfinite_keypoints
 
 
 def upload(ctx, amd, w, h, planes, ch):
@@ -135,23 +91,6 @@ def test_crafted_planes_and_keypoints(ctx, amd, size, kind, ch):
         print(f"{w}x{h} ints {ch}ch: {ties} exact ties among the 4x4 grid's intensity means of level 0")
         assert ties >= 100
     res.close()
-
-
-def nonfinite_keypoints(levels):
-    rows = []
-    vals = [np.nan, np.inf, -np.inf, 1e30, -1e30]
-    for lvl, lv in enumerate(levels):
-        r = 2.0 ** lv["octave"]
-        base = [(lv["w"] // 2) * r, (lv["h"] // 3) * r, 0.0, 4.0 * r, lv["octave"], lvl, 0.37, 0]
-        for field in (0, 1, 3, 6):  # x, y, size, angle
-            for v in vals:
-                row = list(base)
-                row[field] = v
-                rows.append(tuple(row))
-        for v in vals:  # ... and all four at once
-            rows.append((v, v, 0.0, v, lv["octave"], lvl, v, 0))
-        rows.append((np.inf, -np.inf, 0.0, np.nan, 30, lvl, -np.inf, 0))
-    return np.array(rows, M.KEYPOINT_DTYPE)
 
 
 @pytest.mark.gpu
@@ -337,4 +276,69 @@ def test_binding_row_width_on_a_result_without_keypoints(ctx, amd, ch, nb):
     assert_rows(got_k, got_d, kps, exp_a, exp_d, f"{ch} channels, {nb}-byte rows")
     if (162 * ch) % 8:  # the bits behind the last comparison stay zero
         assert not (got_d[:, -1] >> ((162 * ch) % 8)).any()
+    res.close()
+
+
+_FAMILY = {}
+
+
+def family(amd, name, w, h):
+    """(source planes, keypoints, meta) of a tie or mirror case, built once per size; one keypoint is dropped so that the
+    count is a multiple neither of 4 (k_mldb's workgroup) nor of 32 (k_orientation's)"""
+    if (name, w, h) not in _FAMILY:
+        levels = amd.plan_levels(w, h)
+        if name == "tie":
+            src = D.crafted_planes(levels, "wide", seed=w + 11)
+            kps, meta = D.tie_keypoints(levels, src, seed=w + 12)
+        else:
+            src = D.mirror_planes(levels, seed=w + 13)
+            kps, meta = D.mirror_keypoints(levels)
+        assert len(kps) % 4 == 0
+        _FAMILY[(name, w, h)] = (src, kps[:-1].copy(), meta[:-1].copy())
+    return _FAMILY[(name, w, h)]
+
+
+FAMILY_CASES = [(n, s, ch) for n in ("tie", "mirror") for s in ((163, 81), (64, 40)) for ch in (3, 2, 1)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,size,ch", FAMILY_CASES, ids=[f"{n}-{s[0]}x{s[1]}-{ch}ch" for n, s, ch in FAMILY_CASES])
+def test_tie_keypoints_and_mirror_planes(ctx, amd, name, size, ch):
+    """The inputs on which a nearly right kernel goes wrong (tests/describe_cases.py; tests/test_describe_teeth_host.py shows
+    which deviations they catch): tie keypoints, one lattice sample of which is decided by the last bit of
+    descriptors.rs:112-113 as written, and mirror planes, on which mirrored cells hold the same samples in the opposite
+    order, so that comparisons are decided by the rounding of the sums and of the division.  Every float word and descriptor
+    byte equals the statement's clamped form."""
+    w, h = size
+    src, kps, meta = family(amd, name, w, h)
+    assert len(kps) % 4 and set(kps["class_id"]) == set(range(len(src)))
+    res = upload(ctx, amd, w, h, src, ch)
+    planes, octaves = result_planes(res, len(src))
+    for l, p in enumerate(src):
+        assert all(planes[l][i].tobytes() == p[n].tobytes() for i, n in enumerate(("Lt", "Lx", "Ly"))), l
+    # the cases are what they claim, from the statement's side alone
+    if name == "tie":
+        apart = D.tie_rounds_apart(kps, meta)
+        print(f"tie {w}x{h}: {int(apart.sum())} of {len(kps)} keypoints have a sample that two associations round apart")
+        assert apart.all()
+        assert all(((meta["coord"] == c) & (meta["sign"] == s) & (meta["variant"] == v)).sum() >= len(src)
+                   for c in (0, 1) for s in (-1, 1) for v in range(len(D.TIE_VARIANTS)))
+    else:
+        vals = np.zeros((29, 3, len(kps)), np.float32)
+        for l in range(len(src)):
+            sel = kps["class_id"] == l
+            vals[:, :, sel] = M.mldb_values(*planes[l], kps[sel], kps["angle"][sel], ch, "clamped")
+        pairs, close, tied = D.mirror_closeness(vals, meta, ch)
+        print(f"mirror {w}x{h} {ch}ch: {pairs} mirrored cell pairs, {close} with means within 4 ulp, {tied} equal")
+        assert 2 * close >= pairs and tied >= 100
+    for orient in (True, False):
+        what = f"{name} {w}x{h} {ch}ch orient={orient}"
+        got_k, got_d = res.describe_keypoints(kps, compute_orientation=orient)
+        exp_a, exp_d, cov = M.describe(planes, octaves, kps, ch, "clamped", orient)
+        assert_rows(got_k, got_d, kps, exp_a, exp_d, what)
+        if name == "mirror" and not orient:  # every sample inside the plane: the reference completes, and says the same
+            ref_a, ref_d, rcov = M.describe(planes, octaves, kps, ch, "reference", orient)
+            assert rcov.completes.all() and not rcov.next_row.any()
+            assert not (cov.left | cov.right | cov.top | cov.bottom).any()
+            assert np.array_equal(ref_d, exp_d) and np.array_equal(bits(ref_a), bits(exp_a))
     res.close()
