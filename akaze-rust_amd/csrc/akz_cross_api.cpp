@@ -149,6 +149,11 @@ int akz_debug_match_tile_rows(uint32_t* rows) {  // include/akaze_hip_debug.h
     *rows = launch::match_mfma_tile_rows();
     return AKZ_OK;
 }
+int akz_debug_match_seed_rows(uint32_t n0, uint32_t* rows) {  // include/akaze_hip_debug.h
+    if (!rows) return AKZ_ERR_INVALID_ARG;
+    *rows = launch::match_cols_seed_rows(n0);
+    return AKZ_OK;
+}
 
 int akz_match_features_seeded_cross_pairs(akz_ctx* c, const akz_feature_set* sets, uint64_t n_sets, const uint64_t* pairs, uint64_t n_pairs,
                                           uint64_t desc_bytes, const akz_ransac_options* options, akz_match* out, uint64_t* n_out, float* model,

@@ -517,6 +517,7 @@ def lib():
         "akz_debug_keypoint_budget_tiles": ([pu32, pu32], i32),
         "akz_debug_match_pairs_split": ([vp, i32, pf64], i32),
         "akz_debug_match_tile_rows": ([C.POINTER(C.c_uint32)], i32),
+        "akz_debug_match_seed_rows": ([u32, C.POINTER(C.c_uint32)], i32),
         "akz_write_features": ([C.c_char_p, vp, u64, vp, u64], i32),
         "akz_read_features": ([C.c_char_p, vp, vp, u64, u64, pu64, pu64, pu64], i32),
         "akz_write_matches": ([C.c_char_p, vp, u64], i32),

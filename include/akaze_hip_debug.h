@@ -37,6 +37,10 @@ int akz_debug_set_match_chunks(akz_ctx* ctx, uint32_t pair_chunks, uint32_t set_
 /* Test hook: the train rows per LDS tile of the matrix-core matcher (launch::match_mfma_tile_rows()), so that tests can place
    their set sizes one below, at and one above it.  No GPU call, no context. */
 int akz_debug_match_tile_rows(uint32_t* rows);
+/* Test hook: the query rows that seed the opposite direction of akz_descriptor_match_sets_mutual_device for a query set of n0
+   rows (launch::match_cols_seed_rows(n0): min(n0, AKZ_MM_SEED_TILES tiles)); the rows from there on enter through the atomic
+   candidate path, so tests can plant rows on both sides of that boundary.  No GPU call, no context. */
+int akz_debug_match_seed_rows(uint32_t n0, uint32_t* rows);
 /* Test hook: force the number of train chunks of the k-nearest-neighbour scan (akz_descriptor_match_knn*), so that tests reach
    the merge of the chunks' partial lists at a few hundred rows; 0 = automatic (the default).  The counterpart of pair_chunks
    above.  Results are identical for every value. */

@@ -13,7 +13,12 @@ pytestmark = pytest.mark.gpu
 
 N0 = (33, 513)
 CHUNKS = (1, 2, 3, 5)
-TOP2 = ((1.5, 10000), (0.99, 12))  # (ratio, threshold)
+# (ratio, threshold): every list is non-empty and shorter than n0 on every case (asserted below, and chosen on the CPU in
+# tests/test_match_statement_host.py: 19 .. 29 of 33 and 362 .. 381 of 513 at (1.5, 10000), 7 .. 19 and 182 .. 210 at (1.5, 2), where
+# the threshold cuts the list).  The former (0.99, 12) gave EMPTY lists on all but one case -- in these sets min == second for every
+# query --; it stays in ALSO so that nothing this test held before is lost, but nothing is learnt from it.
+TOP2 = ((1.5, 10000), (1.5, 2))
+ALSO = ((0.99, 12),)
 
 
 def train_sizes(T):
@@ -33,8 +38,9 @@ def sets(n0, n1):
 def expected(amd, ref, n0, n1):
     """inputs and what the two statements say about them (no GPU call)"""
     d0, d1 = sets(n0, n1)
-    top2 = {rt: ref.descriptor_match(d0, d1, rt[1], rt[0]) for rt in TOP2}
-    assert len(top2[TOP2[0]]) > 0, (n0, n1)  # the equalities below are not about empty lists
+    top2 = {rt: ref.descriptor_match(d0, d1, rt[1], rt[0]) for rt in TOP2 + ALSO}
+    for rt in TOP2:
+        assert 0 < len(top2[rt]) < n0, (n0, n1, rt)  # the equalities below are not about empty lists, nor about lists of everything
     return d0, d1, top2, {k: amd.descriptor_match_knn_host(d0, d1, k) for k in (8, 1)}
 
 

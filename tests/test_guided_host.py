@@ -7,6 +7,7 @@ import itertools
 import numpy as np
 import pytest
 
+from match_numpy import scan_admitted
 from test_match_pairs_host import _status
 
 F32 = np.float32
@@ -47,25 +48,14 @@ def np_gate(kind, model, x0, y0, x1, y1, radius):
 
 
 def np_guided(k0, d0, k1, d1, model, kind, radius, threshold, ratio):
-    """feature_matching.rs:37-81 with `if !gate { continue }` at the top of the inner loop."""
+    """feature_matching.rs:37-81 with `if !gate { continue }` at the top of the inner loop: the gate is stated here, the scan over
+    the rows it admits is the one of tests/match_numpy.py."""
     n0, n1 = len(d0), len(d1)
     x1, y1 = k1["x"][:n1].astype(F32), k1["y"][:n1].astype(F32)
-    bits1 = np.unpackbits(d1, axis=1)
-    out = []
-    for i in range(n0):
-        ok = np_gate(kind, model, F32(k0["x"][i]), F32(k0["y"][i]), x1, y1, radius) if n1 else np.zeros(0, bool)
-        dist = (np.unpackbits(d0[i])[None, :] != bits1).sum(axis=1)
-        mn = second = threshold
-        mj = 0
-        for j in np.flatnonzero(ok):
-            d = int(dist[j])
-            if d < mn:
-                second, mn, mj = mn, d, int(j)
-            elif d < second:
-                second = d
-        if float(mn) < float(second) * (ratio * ratio) and mn < threshold:
-            out.append((i, mj, float(mn)))
-    return out
+    ok = np.zeros((n0, n1), bool)
+    for i in range(n0 if n1 else 0):
+        ok[i] = np_gate(kind, model, F32(k0["x"][i]), F32(k0["y"][i]), x1, y1, radius)
+    return _as_list(scan_admitted(d0, d1, ok, threshold, ratio))
 
 
 def _as_list(m):

@@ -1,6 +1,6 @@
 """k-nearest-neighbour matching on the host (akz_descriptor_match_knn_host; no GPU call): the whole buffers -- records, padding
-slots and counts -- against an independent numpy statement written here (np.unpackbits of the XOR, summed; a stable argsort per
-row, which orders by (distance, index); a cut at the threshold and at k), the tie rule on a train set of repeated rows, the
+slots and counts -- against the independent numpy statement of tests/match_numpy.py (distances from np.unpackbits; a stable argsort
+per row, which orders by (distance, index); a cut at the threshold and at k), the tie rule on a train set of repeated rows, the
 refusals, the two empty cases and the declarations."""
 import ctypes as C
 import os
@@ -9,36 +9,17 @@ import re
 import numpy as np
 import pytest
 
+from match_numpy import NO_ROW, distances, knn
 from test_match_pairs_host import ROOT
 
 NEW_SYMBOLS = ("akz_descriptor_match_knn_host", "akz_descriptor_match_knn", "akz_descriptor_match_knn_device")
-NO_ROW = np.uint64(0xFFFFFFFFFFFFFFFF)
 KS = (1, 2, 3, 5, 8)
 
 
-def distances(a, b):
-    """(n0, n1) hamming distances over every byte of the rows"""
-    if len(a) == 0 or len(b) == 0:
-        return np.zeros((len(a), len(b)), np.int64)
-    return np.unpackbits(a[:, None, :] ^ b[None, :, :], axis=2).sum(axis=2, dtype=np.int64)
-
-
 def numpy_knn(amd, a, b, k, thr, dist=None):
-    """the statement of include/akaze_hip.h in numpy -> (records (n0, k), counts (n0,))"""
-    dist = distances(a, b) if dist is None else dist
-    n0, n1 = dist.shape
-    out = np.zeros((n0, k), amd.MATCH_DTYPE)
-    out["index_0"] = np.arange(n0, dtype=np.uint64)[:, None]
-    out["index_1"] = NO_ROW
-    out["distance"] = np.inf
-    counts = np.zeros(n0, np.uint32)
-    if n1:
-        order = np.argsort(dist, axis=1, kind="stable")                  # ascending distance, ascending index among equals
-        for i in range(n0):
-            js = [j for j in order[i] if dist[i, j] < thr][:k]
-            counts[i] = len(js)
-            out["index_1"][i, :len(js)] = js
-            out["distance"][i, :len(js)] = dist[i, js]
+    """the statement of include/akaze_hip.h in numpy (tests/match_numpy.py) -> (records (n0, k), counts (n0,))"""
+    out, counts = knn(a, b, k, thr, dist)
+    assert out.dtype == amd.MATCH_DTYPE
     return out, counts
 
 
