@@ -9,39 +9,16 @@
 #include <vector>
 
 #include "akz_ctx.hpp"
+#include "akz_match_rule.hpp"
 
 namespace {
 
-// descriptor_match (feature_matching.rs:37-81) on the host: both distances start at the threshold, strict '<' updates in
-// ascending j (the lowest index among equal minima), kept iff (double)min < (double)second * ratio^2 and min < threshold
-void host_scan(const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes, uint32_t thr, double ratio2,
-               std::vector<akz_match>& out) {
-    out.clear();
-    for (uint64_t i = 0; i < n0; ++i) {
-        const uint8_t* a = d0 + i * desc_bytes;
-        uint32_t min_d = thr, second = thr;
-        uint64_t min_j = 0;
-        for (uint64_t j = 0; j < n1; ++j) {
-            const uint8_t* b = d1 + j * desc_bytes;
-            uint32_t d = 0;
-            uint64_t t = 0;
-            for (; t + 8 <= desc_bytes; t += 8) {
-                uint64_t wa, wb;
-                std::memcpy(&wa, a + t, 8);
-                std::memcpy(&wb, b + t, 8);
-                d += (uint32_t)__builtin_popcountll(wa ^ wb);
-            }
-            for (; t < desc_bytes; ++t) d += (uint32_t)__builtin_popcount((unsigned)(a[t] ^ b[t]));
-            if (d < min_d) {
-                second = min_d;
-                min_d = d;
-                min_j = j;
-            } else if (d < second) {
-                second = d;
-            }
-        }
-        if ((double)min_d < (double)second * ratio2 && min_d < thr) out.push_back(akz_match{i, min_j, (double)min_d});
-    }
+// descriptor_match (feature_matching.rs:37-81) on the host: the ungated scan of akz_match_rule.hpp
+std::vector<akz_match> host_scan(const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes, uint32_t thr, double ratio2) {
+    std::vector<akz_match> out;
+    akz::host_match_scan(d0, n0, d1, n1, desc_bytes, thr, ratio2, [](uint64_t, uint64_t) { return true; },
+                         [&](const akz_match& m) { out.push_back(m); });
+    return out;
 }
 
 bool host_args_ok(const char* name, const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes, const akz_match* out,
@@ -60,11 +37,10 @@ extern "C" {
 int akz_descriptor_match_cross_host(const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes,
                                     uint64_t distance_threshold, double lowes_ratio, akz_match* out, uint64_t* n_out) {
     if (!host_args_ok("descriptor_match_cross_host: ", d0, n0, d1, n1, desc_bytes, out, n_out)) return AKZ_ERR_INVALID_ARG;
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
+    const uint32_t thr = akz::clamp_threshold(distance_threshold);
     const double ratio2 = lowes_ratio * lowes_ratio;
-    std::vector<akz_match> fwd, rev;
-    host_scan(d0, n0, d1, n1, desc_bytes, thr, ratio2, fwd);
-    host_scan(d1, n1, d0, n0, desc_bytes, thr, ratio2, rev);
+    const std::vector<akz_match> fwd = host_scan(d0, n0, d1, n1, desc_bytes, thr, ratio2);
+    const std::vector<akz_match> rev = host_scan(d1, n1, d0, n0, desc_bytes, thr, ratio2);
     std::vector<uint64_t> back((size_t)n1, ~0ull);  // row of B -> the row of A its reverse record names
     for (const akz_match& r : rev) back[(size_t)r.index_0] = r.index_1;
     uint64_t cnt = 0;

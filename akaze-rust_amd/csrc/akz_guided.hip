@@ -22,6 +22,7 @@
 
 #include "akz_homography.hpp"
 #include "akz_internal.hpp"
+#include "akz_match_rule.hpp"
 
 namespace akz {
 namespace {
@@ -79,7 +80,7 @@ __global__ void __launch_bounds__(GT) k_match_guided(const uint4* __restrict__ r
     for (int k = 0; k < 9; ++k) m[k] = models[(size_t)gp.model * 9 + k];
     const Gate<KIND> gate(m, kx[qrow], ky[qrow], radius);
     const bool on = found == nullptr || found[gp.model] != 0;  // (uniform) a pair without a model: records of an empty scan
-    unsigned min_d = threshold, second = threshold, min_j = 0;
+    NearestTwo best = NearestTwo::start(threshold);
     const unsigned begin = on ? min(gp.n1, ch * gp.chunk_rows) : gp.n1, end = min(gp.n1, begin + gp.chunk_rows);
     auto feed = [&](unsigned r, unsigned base) {  // a row inside the gate: its distance, then the reference's update rule
         unsigned d = 0;
@@ -91,13 +92,7 @@ __global__ void __launch_bounds__(GT) k_match_guided(const uint4* __restrict__ r
             d += __popc(q[k].z ^ t.z);
             d += __popc(q[k].w ^ t.w);
         }
-        if (d < min_d) {  // (feature_matching.rs:41-49)
-            second = min_d;
-            min_d = d;
-            min_j = base + r;
-        } else if (d < second) {
-            second = d;
-        }
+        best.feed(d, base + r);
     };
     for (unsigned base = begin; base < end; base += GT) {
         const unsigned nrows = min((unsigned)GT, end - base);
@@ -123,11 +118,7 @@ __global__ void __launch_bounds__(GT) k_match_guided(const uint4* __restrict__ r
             if (gate.pass(p.x, p.y)) feed(r, base);
         }
     }
-    if (live) {
-        MatchRec rec;
-        rec.min_d = min_d; rec.second_d = second; rec.min_j = min_j; rec._pad = 0;
-        out[gp.rec_off + (size_t)ch * gp.n0 + i] = rec;
-    }
+    if (live) out[gp.rec_off + (size_t)ch * gp.n0 + i] = best.record();
 }
 
 }  // namespace

@@ -3,6 +3,7 @@
 // the guided stage of the RANSAC pairs calls (pairs_tail, akz_match_api.cpp).
 #include "akz_ctx.hpp"
 #include "akz_homography.hpp"
+#include "akz_match_rule.hpp"
 
 namespace {
 // the refusals every guided call shares; false: refused (message set)
@@ -32,7 +33,6 @@ bool pair_args_ok(const char* name, const akz_keypoint* kp0, uint64_t n_kp0, con
     if (why) set_error(std::string(name) + why);
     return why == nullptr;
 }
-uint32_t clamp_threshold(uint64_t t) { return (uint32_t)std::min<uint64_t>(t, 0x7fffffffull); }
 }  // namespace
 
 // The sizes one launch of the guided scan takes, checked with the other refusals before any GPU work: rows of a set below
@@ -70,7 +70,7 @@ std::vector<GuidedPairSpec> guided_specs(const PairsCall& q, const SetsBlock& bl
 int guided_enqueue(akz_ctx* c, const std::vector<GuidedPairSpec>& spec, const SetsBlock& b, int kind, const float* d_models, const int32_t* d_found,
                    float radius, uint64_t distance_threshold, double lowes_ratio, akz_match* d_out, uint64_t* d_cnt) {
     hipStream_t st = c->stream;
-    const uint32_t thr = clamp_threshold(distance_threshold), block = launch::match_guided_block();
+    const uint32_t thr = akz::clamp_threshold(distance_threshold), block = launch::match_guided_block();
     AKZ_HIP_TRY(hipMemsetAsync(d_cnt, 0, spec.size() * sizeof(uint64_t), st));
     // A pair's train rows are cut into chunks so that the launch fills the chip: 256 compute units take eight workgroups of
     // four waves each, and a chunk should still be a few LDS tiles long (akz_debug_set_match_chunks forces the pair count).
@@ -121,38 +121,14 @@ int akz_descriptor_match_guided_host(const akz_keypoint* kp0, uint64_t n_kp0, co
         return AKZ_ERR_INVALID_ARG;
     float m[9];
     std::memcpy(m, model, sizeof(m));
-    const uint32_t thr = clamp_threshold(distance_threshold);
-    const double ratio2 = lowes_ratio * lowes_ratio;
+    // feature_matching.rs:37-81 with the gate at the top of the inner loop
+    const auto gate = [&](uint64_t i, uint64_t j) {
+        return model_kind == AKZ_GUIDED_HOMOGRAPHY ? akz::homography_inlier(m, kp0[i].x, kp0[i].y, kp1[j].x, kp1[j].y, radius)
+                                                   : akz::fundamental_near_line(m, kp0[i].x, kp0[i].y, kp1[j].x, kp1[j].y, radius);
+    };
     uint64_t cnt = 0;
-    for (uint64_t i = 0; i < n_d0; ++i) {  // feature_matching.rs:37-81 with the gate at the top of the inner loop
-        const uint8_t* a = d0 + i * desc_bytes;
-        const float x0 = kp0[i].x, y0 = kp0[i].y;
-        uint32_t min_d = thr, second = thr;
-        uint64_t min_j = 0;
-        for (uint64_t j = 0; j < n_d1; ++j) {
-            const bool pass = model_kind == AKZ_GUIDED_HOMOGRAPHY ? akz::homography_inlier(m, x0, y0, kp1[j].x, kp1[j].y, radius)
-                                                                  : akz::fundamental_near_line(m, x0, y0, kp1[j].x, kp1[j].y, radius);
-            if (!pass) continue;
-            const uint8_t* b = d1 + j * desc_bytes;
-            uint32_t d = 0;
-            uint64_t t = 0;
-            for (; t + 8 <= desc_bytes; t += 8) {
-                uint64_t wa, wb;
-                std::memcpy(&wa, a + t, 8);
-                std::memcpy(&wb, b + t, 8);
-                d += (uint32_t)__builtin_popcountll(wa ^ wb);
-            }
-            for (; t < desc_bytes; ++t) d += (uint32_t)__builtin_popcount((unsigned)(a[t] ^ b[t]));
-            if (d < min_d) {
-                second = min_d;
-                min_d = d;
-                min_j = j;
-            } else if (d < second) {
-                second = d;
-            }
-        }
-        if ((double)min_d < (double)second * ratio2 && min_d < thr) out[cnt++] = akz_match{i, min_j, (double)min_d};
-    }
+    akz::host_match_scan(d0, n_d0, d1, n_d1, desc_bytes, akz::clamp_threshold(distance_threshold), lowes_ratio * lowes_ratio, gate,
+                         [&](const akz_match& r) { out[cnt++] = r; });
     *n_out = cnt;
     return AKZ_OK;
 }

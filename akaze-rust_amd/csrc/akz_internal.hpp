@@ -375,6 +375,7 @@ struct MldbMirror {
 void mldb_counted(hipStream_t s, const LevelTable& lt, const KpParam* d_kp, const uint32_t* d_nkp, uint32_t first, uint32_t last, OrientOut* d_sums,
                   uint32_t sums_stride, bool libm_fma, uint32_t* d_flag, uint32_t channels, uint8_t* d_desc64, const MldbMirror* mirror = nullptr);
 void libm_eval(hipStream_t s, const float* a, const float* b, float* out3, uint64_t n, bool fma, uint32_t* d_flag);
+// the popcount scan and the kernels that turn chunk records into lists (akz_kernels.hip; the rule: akz_match_rule.hpp)
 uint32_t match_num_chunks(uint32_t n0, uint32_t n1);
 // Both scans write one record per (chunk of the train set, query): d_rec[chunk * n0 + query]; match_compact merges a
 // query's chunk records (ascending rows: the lowest row wins among equal minima) and applies the ratio test.

@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "akz_internal.hpp"
+#include "akz_match_rule.hpp"
 #include "akz_pm_g2.hpp"
 #include "akz_libm.hpp"
 #include "akz_prep_passes.hpp"
@@ -1188,15 +1189,6 @@ __device__ __forceinline__ unsigned hamming64(const uint4 (&q)[4], const uint4* 
     }
     return d;
 }
-__device__ __forceinline__ void top2_feed(unsigned d, unsigned j, unsigned& min_d, unsigned& second, unsigned& min_j) {
-    if (d < min_d) {  // the reference's update rule (feature_matching.rs:41-49)
-        second = min_d;
-        min_d = d;
-        min_j = j;
-    } else if (d < second) {
-        second = d;
-    }
-}
 // blockIdx.x: 256 queries (one per thread, in registers); blockIdx.y: a chunk of the train set, staged
 // through LDS 256 rows at a time.  Each workgroup writes the chunk-local (min, second, argmin) of its
 // queries; k_match_compact folds the chunks in index order, which reproduces the sequential scan exactly
@@ -1210,7 +1202,7 @@ __global__ void __launch_bounds__(MT) k_match(const uint4* __restrict__ d0, unsi
     const bool live = i < n0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) q[k] = live ? d0[(size_t)i * 4 + k] : make_uint4(0, 0, 0, 0);
-    unsigned min_d = threshold, second = threshold, min_j = 0;
+    NearestTwo best = NearestTwo::start(threshold);  // the rule: akz_match_rule.hpp
     const unsigned begin = blockIdx.y * chunk_rows, end = min(n1, begin + chunk_rows);
     for (unsigned base = begin; base < end; base += MT) {
         const unsigned rows = min((unsigned)MT, end - base);
@@ -1221,18 +1213,22 @@ __global__ void __launch_bounds__(MT) k_match(const uint4* __restrict__ d0, unsi
         for (; r + 4 <= rows; r += 4) {  // four independent popcount chains per iteration
             const unsigned da = hamming64(q, s_tile + (r + 0) * 4, tail_mask), db = hamming64(q, s_tile + (r + 1) * 4, tail_mask);
             const unsigned dc = hamming64(q, s_tile + (r + 2) * 4, tail_mask), dd = hamming64(q, s_tile + (r + 3) * 4, tail_mask);
-            top2_feed(da, base + r + 0, min_d, second, min_j);
-            top2_feed(db, base + r + 1, min_d, second, min_j);
-            top2_feed(dc, base + r + 2, min_d, second, min_j);
-            top2_feed(dd, base + r + 3, min_d, second, min_j);
+            best.feed(da, base + r + 0);
+            best.feed(db, base + r + 1);
+            best.feed(dc, base + r + 2);
+            best.feed(dd, base + r + 3);
         }
-        for (; r < rows; ++r) top2_feed(hamming64(q, s_tile + r * 4, tail_mask), base + r, min_d, second, min_j);
+        for (; r < rows; ++r) best.feed(hamming64(q, s_tile + r * 4, tail_mask), base + r);
     }
-    if (live) {
-        MatchRec m;
-        m.min_d = min_d; m.second_d = second; m.min_j = min_j; m._pad = 0;
-        out[(size_t)blockIdx.y * n0 + i] = m;
-    }
+    if (live) out[(size_t)blockIdx.y * n0 + i] = best.record();
+}
+// A query's records over the chunks of one train set (part[chunk][query]), folded in ascending row order: the strict '<'
+// of the rule keeps the lowest row among equal minima, as the sequential scan does.
+__device__ __forceinline__ NearestTwo fold_chunks(const MatchRec* __restrict__ part, unsigned n0, unsigned chunks, unsigned query,
+                                                  unsigned threshold) {
+    NearestTwo best = NearestTwo::start(threshold);
+    for (unsigned c = 0; c < chunks; ++c) best.fold(part[(size_t)c * n0 + query]);
+    return best;
 }
 // Merge of every query's records over the chunks of one train set, one thread per query (the pair call has up to a
 // hundred chunks: too many records for the single workgroup of k_match_compact to fold on its own).
@@ -1240,19 +1236,10 @@ __global__ void k_match_merge(const MatchRec* __restrict__ part, unsigned n0, un
                               MatchRec* __restrict__ out) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n0) return;
-    unsigned min_d = threshold, second = threshold, min_j = 0;
-    for (unsigned c = 0; c < chunks; ++c) {
-        const MatchRec m = part[(size_t)c * n0 + i];
-        top2_feed(m.min_d, m.min_j, min_d, second, min_j);
-        if (m.second_d < second) second = m.second_d;  // second_d >= min_d of its chunk >= min_d
-    }
-    MatchRec o;
-    o.min_d = min_d; o.second_d = second; o.min_j = min_j; o._pad = 0;
-    out[i] = o;
+    out[i] = fold_chunks(part, n0, chunks, i, threshold).record();
 }
 
-// Merge of a query's records over the chunks of one train set (chunks in ascending row order: the strict '<' of
-// top2_feed keeps the lowest row among equal minima, as the sequential scan does), then the Lowe ratio^2 + threshold
+// Merge of a query's records over the chunks of one train set (fold_chunks), then the Lowe ratio^2 + threshold
 // test (feature_matching.rs:61-63) and ordered compaction; one workgroup per train set.
 __global__ void __launch_bounds__(1024) k_match_compact(const MatchRec* __restrict__ rec, unsigned n0, unsigned chunks,
                                                         unsigned threshold, double ratio2,
@@ -1262,7 +1249,9 @@ __global__ void __launch_bounds__(1024) k_match_compact(const MatchRec* __restri
     // back), the waves publish their counts per group of 1024, ONE barrier, and every thread finds the place of its
     // matches from the 16 x 16 table -- two barriers per 16 K queries instead of three per 1 K.  (Many chunks are still
     // merged by k_match_merge first: this is one workgroup, and one compute unit's load path folds 11 chunks of 11 K
-    // queries in 35 us.)
+    // queries in 35 us.)  k_match_compact_cols (akz_match.hip) repeats this body with another source of a row's state: an
+    // edit here belongs there too.  (One force-inlined __device__ body under both was measured: 28 instead of 12 bytes
+    // of scratch here, 106 instead of 96 VGPRs there, 1 to 5 us slower -- CHANGELOG round 40.)
     constexpr int IT = 16;
     __shared__ unsigned s_cnt[IT][16];
     __shared__ unsigned s_base;
@@ -1280,14 +1269,9 @@ __global__ void __launch_bounds__(1024) k_match_compact(const MatchRec* __restri
             bool keep = false;
             md[it] = mj[it] = 0u;
             if (i < n0) {
-                unsigned min_d = threshold, second = threshold, min_j = 0;
-                for (unsigned c = 0; c < chunks; ++c) {  // ascending rows: the strict '<' keeps the lowest row among equal minima
-                    const MatchRec p = rec[(size_t)c * n0 + i];
-                    top2_feed(p.min_d, p.min_j, min_d, second, min_j);
-                    if (p.second_d < second) second = p.second_d;  // second_d >= min_d of its chunk >= min_d
-                }
-                md[it] = min_d; mj[it] = min_j;
-                keep = ((double)min_d < (double)second * ratio2) && (min_d < threshold);
+                const NearestTwo best = fold_chunks(rec, n0, chunks, i, threshold);
+                md[it] = best.min_d; mj[it] = best.min_j;
+                keep = best.accepted(ratio2, threshold);
             }
             const unsigned long long bal = __ballot(keep);
             if (lane == 0) s_cnt[it][wave] = (unsigned)__popcll(bal);
@@ -1337,15 +1321,11 @@ __global__ void __launch_bounds__(256) k_match_merge_compact(const MatchRec* __r
     __shared__ unsigned s_prefix;
     const unsigned b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const unsigned i = b * 256u + tid;
-    unsigned min_d = threshold, second = threshold, min_j = 0;
+    NearestTwo best = NearestTwo::start(threshold);
     bool keep = false;
     if (i < n0) {
-        for (unsigned c = 0; c < chunks; ++c) {  // ascending rows: the strict '<' keeps the lowest row among equal minima
-            const MatchRec m = part[(size_t)c * n0 + i];
-            top2_feed(m.min_d, m.min_j, min_d, second, min_j);
-            if (m.second_d < second) second = m.second_d;
-        }
-        keep = ((double)min_d < (double)second * ratio2) && (min_d < threshold);
+        best = fold_chunks(part, n0, chunks, i, threshold);
+        keep = best.accepted(ratio2, threshold);
     }
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) s_cnt[wave] = (unsigned)__popcll(bal);
@@ -1376,7 +1356,7 @@ __global__ void __launch_bounds__(256) k_match_merge_compact(const MatchRec* __r
     const unsigned prefix = s_prefix;
     if (keep) {
         akz_match o;
-        o.index_0 = i; o.index_1 = min_j; o.distance = (double)min_d;
+        o.index_0 = i; o.index_1 = best.min_j; o.distance = (double)best.min_d;
         out[prefix + below + (unsigned)__popcll(bal & ((1ull << lane) - 1ull))] = o;
     }
     if (b == gridDim.x - 1 && tid == 0) *n_out = (unsigned long long)prefix + total;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "akz_ctx.hpp"
+#include "akz_match_rule.hpp"
 
 namespace {
 
@@ -30,7 +31,7 @@ bool knn_args_ok(const char* name, const void* d0, uint64_t n0, const void* d1, 
 // scan, merge and records of n0 x n1 64-byte rows on the device, enqueued on c->stream
 int knn_enqueue(akz_ctx* c, const uint8_t* d_d0, uint32_t n0, const uint8_t* d_d1, uint32_t n1, uint32_t k, uint64_t distance_threshold,
                 akz_match* d_out, uint32_t* d_counts) {
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
+    const uint32_t thr = akz::clamp_threshold(distance_threshold);
     const uint32_t chunks = launch::knn_chunks(n0, n1, c->settings.dbg_knn_chunks);
     const uint32_t q_rows = launch::match_mfma_rows(n0, true), t_rows = launch::match_mfma_rows(n1, false);
     AKZ_TRY(ensure(c, c->kn_part, launch::knn_part_bytes(n0, chunks, k)));
@@ -59,23 +60,14 @@ extern "C" {
 int akz_descriptor_match_knn_host(const uint8_t* d0, uint64_t n0, const uint8_t* d1, uint64_t n1, uint64_t desc_bytes, uint64_t k,
                                   uint64_t distance_threshold, akz_match* out, uint32_t* counts) {
     if (!knn_args_ok("descriptor_match_knn_host: ", d0, n0, d1, n1, desc_bytes, k, out, counts)) return AKZ_ERR_INVALID_ARG;
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
+    const uint32_t thr = akz::clamp_threshold(distance_threshold);
     for (uint64_t i = 0; i < n0; ++i) {
         const uint8_t* a = d0 + i * desc_bytes;
         uint32_t kd[AKZ_KNN_MAX_K];
         uint64_t kj[AKZ_KNN_MAX_K];
         uint32_t cnt = 0;
         for (uint64_t j = 0; j < n1; ++j) {
-            const uint8_t* b = d1 + j * desc_bytes;
-            uint32_t d = 0;
-            uint64_t t = 0;
-            for (; t + 8 <= desc_bytes; t += 8) {
-                uint64_t wa, wb;
-                std::memcpy(&wa, a + t, 8);
-                std::memcpy(&wb, b + t, 8);
-                d += (uint32_t)__builtin_popcountll(wa ^ wb);
-            }
-            for (; t < desc_bytes; ++t) d += (uint32_t)__builtin_popcount((unsigned)(a[t] ^ b[t]));
+            const uint32_t d = akz::hamming_bytes(a, d1 + j * desc_bytes, desc_bytes);
             // rows come in ascending j: among equal distances the earlier row stays in front, and a full list takes d only below its worst
             if (d >= thr || (cnt == k && d >= kd[cnt - 1])) continue;
             uint32_t at = cnt < k ? cnt++ : cnt - 1;

@@ -6,7 +6,7 @@
 //     hamming(a, b) = |a| + |b| - 2 <a, b>      (a: train row, b: query row),
 // and the inner products of all (train, query) pairs are one integer GEMM with K = 512: exact integer
 // arithmetic, so distances, indices and therefore the match list are identical to the popcount scan
-// (k_match in akz_kernels.hip, which stays the path for small sets), at a multiple of its rate — the popcount
+// (k_match in akz_kernels.hip, which matcher mode 0 and rows of 62..64 bytes take), at a multiple of its rate — the popcount
 // kernel is bound by the vector ALU (16 xor + 16 bit-count-accumulate per pair), this one by
 // v_mfma_i32_32x32x32_i8.
 //
@@ -21,7 +21,7 @@
 // has its column (query) on the lane and rows (i & 3) + 8 (i >> 2) + 4 h, i = 0..15, in the registers
 // (cdna_hip_programming.md, C/D layout): ascending train index inside a lane, so the reference's update rule
 // applies directly; the two lanes of a column are merged at the end of the chunk with the order-free form of the
-// rule ((distance, index) lexicographic minimum; second = min of the others), and the chunks by k_match_compact.
+// rule (merge_disjoint, akz_match_rule.hpp), and the chunks by k_match_compact.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +30,7 @@
 
 #include "akz_fp4_scan.hpp"
 #include "akz_internal.hpp"
+#include "akz_match_rule.hpp"
 
 namespace akz {
 namespace {
@@ -377,20 +378,10 @@ __global__ void __launch_bounds__(MM_NT) k_match_mfma(const uint8_t* __restrict_
     for (int b = 0; b < MM_NB; ++b) {
         const unsigned o_min = __shfl_xor(min_d[b], 32, 64), o_sec = __shfl_xor(second[b], 32, 64);
         const unsigned o_j = __shfl_xor(min_j[b], 32, 64);
-        unsigned m = min_d[b], s2 = second[b], j = min_j[b];
-        if (o_min < m || (o_min == m && o_min < threshold && o_j < j)) {  // the other lane holds the winner
-            s2 = min(o_sec, m);
-            m = o_min;
-            j = o_j;
-        } else {
-            s2 = min(s2, o_min);
-        }
+        NearestTwo best{min_d[b], second[b], min_j[b]};
+        best.merge_disjoint(NearestTwo{o_min, o_sec, o_j}, threshold);
         const unsigned q = q_first + 32 * b + r;
-        if (h == 0 && q < n0) {
-            MatchRec rec;
-            rec.min_d = m; rec.second_d = s2; rec.min_j = j; rec._pad = 0;
-            out[(size_t)record * n0 + q] = rec;
-        }
+        if (h == 0 && q < n0) out[(size_t)record * n0 + q] = best.record();
     }
 }
 
@@ -626,19 +617,9 @@ __global__ void __launch_bounds__(fp4::NT) k_match_fp4(const uint8_t* __restrict
     v.settle();
     // the two lanes of a column hold disjoint row sets: order-free merge, then one record per live query
     const unsigned o_min = __shfl_xor(v.min_d, 32, 64), o_sec = __shfl_xor(v.second, 32, 64), o_j = __shfl_xor(v.min_j, 32, 64);
-    unsigned m = v.min_d, s2 = v.second, j = v.min_j;
-    if (o_min < m || (o_min == m && o_min < threshold && o_j < j)) {
-        s2 = min(o_sec, m);
-        m = o_min;
-        j = o_j;
-    } else {
-        s2 = min(s2, o_min);
-    }
-    if (h == 0 && q < n0) {
-        MatchRec rec;
-        rec.min_d = m; rec.second_d = s2; rec.min_j = j; rec._pad = 0;
-        out[(size_t)record * n0 + q] = rec;
-    }
+    NearestTwo best{v.min_d, v.second, v.min_j};
+    best.merge_disjoint(NearestTwo{o_min, o_sec, o_j}, threshold);
+    if (h == 0 && q < n0) out[(size_t)record * n0 + q] = best.record();
 }
 
 // ---- the opposite direction's state and lists (COLS) ----------------------------------------------------------------
@@ -660,7 +641,9 @@ __global__ void __launch_bounds__(1024) k_match_compact_cols(const unsigned long
                                                              const unsigned* __restrict__ csecond, const ColSet* __restrict__ sets,
                                                              unsigned threshold, double ratio2, akz_match* __restrict__ out,
                                                              unsigned long long* __restrict__ n_out) {
-    constexpr int IT = 16;  // (rounds of 16 x 1024 rows, two barriers each: as k_match_compact)
+    // (rounds of 16 x 1024 rows, two barriers each: the body of k_match_compact in akz_kernels.hip with another source of a
+    // row's state -- an edit here belongs there too; why the two do not share one function is said there)
+    constexpr int IT = 16;
     __shared__ unsigned s_cnt[IT][16];
     __shared__ unsigned s_base;
     const ColSet cs = sets[blockIdx.x];
@@ -677,10 +660,9 @@ __global__ void __launch_bounds__(1024) k_match_compact_cols(const unsigned long
             md[it] = mj[it] = 0u;
             if (i < cs.rows) {
                 const unsigned long long b = cbest[(size_t)cs.row0 + i];
-                const unsigned second = csecond[(size_t)cs.row0 + i];
-                md[it] = (unsigned)(b >> 32);
-                mj[it] = (unsigned)b;
-                keep = ((double)md[it] < (double)second * ratio2) && (md[it] < threshold);
+                const NearestTwo best{(unsigned)(b >> 32), csecond[(size_t)cs.row0 + i], (unsigned)b};
+                md[it] = best.min_d; mj[it] = best.min_j;
+                keep = best.accepted(ratio2, threshold);
             }
             const unsigned long long bal = __ballot(keep);
             if (lane == 0) s_cnt[it][wave] = (unsigned)__popcll(bal);

@@ -2,6 +2,7 @@
 // what they all share (pairs_validate .. pairs_scans, the front and the tail: pairs_front, pairs_keep, pairs_tail), the call that draws
 // its samples on the host between the two (match_pairs_impl<Model>), and its entry points for both models, one pair or many.
 #include "akz_ctx.hpp"
+#include "akz_match_rule.hpp"
 
 // Merge of a query set's chunk records (rec[chunk][query], then room for n0 merged records), ratio test and ordered
 // compaction: what every scan of one train set ends with (akz_descriptor_match_device, the guided scan), on c->stream.
@@ -58,7 +59,7 @@ static int match_device_impl(akz_ctx* c, const uint8_t* d_d0, uint64_t n0, const
         set_error("descriptor_match: bad arguments");
         return AKZ_ERR_INVALID_ARG;
     }
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
+    const uint32_t thr = akz::clamp_threshold(distance_threshold);
     // the scan runs on the matrix cores (integer GEMM on the unpacked bits, identical records): 24 us against 29 for the
     // popcount kernel at 128 x 128, 35 against 190 at 1024 x 1024, 3.0 ms against 9.9 at 90 K x 90 K; mode 0 keeps the
     // popcount kernel selectable
@@ -149,7 +150,7 @@ static int match_sets_impl(akz_ctx* c, const uint8_t* d_q, uint64_t n0, const ui
     hipStream_t st = alt ? c->aux : c->stream;
     CtxOwned::MatchSide& m = c->ms[alt];
     const bool mutual = cols && c->settings.match_mode >= 2;
-    const uint32_t thr = (uint32_t)std::min<uint64_t>(distance_threshold, 0x7fffffffull);
+    const uint32_t thr = akz::clamp_threshold(distance_threshold);
     const uint32_t tr = launch::match_mfma_tile_rows();
     const uint32_t q_rows = launch::match_mfma_rows((uint32_t)n0, true);
     // padded train image: every set starts on a tile boundary
